@@ -6,7 +6,11 @@ Workload (BASELINE.json configs[1]): pcr=loam, 65 536-point scan vs 1 M-point su
 reference does, PCR/src/LoamRegister.cpp:110), inputs resident in HBM.  One "step" = one
 scan2Map call through the C ABI (pcr_scan2map_device).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up with W steps, times exactly K steps (cut into --windows windows; value and ms_per_step
+are the median window's), writes the last step's outputs with --dump-outputs and prints the line.  --full also
+measures everything else: rooflines from profiled passes, the kept-index / stateless / host-buffer legs, the CPU
+baseline with pose parity, the sharded run's N = 1 origin and the extra configurations (configs[2..4], the drive).
 N > 1: one rank per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this
 process IS a rank; started plainly (`python bench.py --gpus N`) it is the LAUNCHER: before anything
 touches the GPU it starts N fresh child processes (RANK, LOCAL_RANK, WORLD_SIZE, MASTER_* set), waits
@@ -73,11 +77,46 @@ def timed_windows(step, barrier, steps, windows):
     return out
 
 
+def split_windows(step, barrier, steps, windows):
+    """The headline's timing: exactly `steps` timed steps, step(0) .. step(steps - 1), cut into `windows` back-to-back windows of
+    (nearly) equal length, each bracketed by barrier + synchronize -> (seconds per window, steps per window)"""
+    windows = max(1, min(windows, steps))
+    sizes = [steps // windows + (w < steps % windows) for w in range(windows)]
+    secs, i = [], 0
+    for n in sizes:
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            step(i)
+            i += 1
+        barrier()
+        secs.append(time.perf_counter() - t0)
+    return secs, sizes
+
+
+def median_step(secs, sizes):
+    """seconds per step of the median window (windows ranked by their time per step)"""
+    return float(np.median([s / n for s, n in zip(secs, sizes)]))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: what the timed path handed its caller in its last step, one DIR/<name>.npy per array, float64"""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), np.asarray(a, dtype=np.float64))
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps of the headline (all windows together)")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: rooflines from profiled passes, the kept-index, stateless and host-buffer "
+                         "legs, the CPU baseline with pose parity, the sharded run's N = 1 origin and the extra configurations; off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned to its caller (the refined 4x4 pose and the convergence flag) "
+                         "as DIR/<name>.npy, float64; rank 0's")
     ap.add_argument("--map-points", type=int, default=None, help="default 1 000 000 (configs[1]); 10 000 000 with --shard-map (configs[3])")
     ap.add_argument("--dry-run", action="store_true", help="every rank prints the environment it was started with and leaves: no GPU, no measurement")
     ap.add_argument("--master-port", type=int, default=0, help="launcher only: rendezvous port of the ranks it starts (0 = pick a free one)")
@@ -93,15 +132,15 @@ def parse():
                     help="> 1: additionally time S independent handles (one HIP stream and one host thread each) registering "
                          "scans concurrently on the same GPU; reported as \"concurrent\", never as \"value\"")
     ap.add_argument("--full-target", action="store_true", help="vgicp / ndt: prepare the whole target on every call (pcr_params.full_target = 1) instead of the scan's region, for A/B runs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-budget-s", type=float, default=8.0, help="wall-clock bound of EACH CPU leg (per thread count / index flavour / method)")
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each; value = the median window")
-    ap.add_argument("--no-extra", action="store_true", help="skip the configs[2] (vgicp) and configs[4] (ndt) lines embedded as \"extra\"")
-    ap.add_argument("--extra-steps", type=int, default=40)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and pose parity")
+    ap.add_argument("--cpu-budget-s", type=float, default=8.0, help="--full: wall-clock bound of EACH CPU leg (per thread count / index flavour / method)")
+    ap.add_argument("--windows", type=int, default=5, help="back-to-back windows the --steps timed steps are cut into; value = the median window")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the configs[2] (vgicp) and configs[4] (ndt) lines embedded as \"extra\"")
+    ap.add_argument("--extra-steps", type=int, default=40, help="--full: timed steps per window of each \"extra\" line")
     ap.add_argument("--secondary-map-points", type=int, default=0, help="--method vgicp|ndt: map size instead of the configuration's (rehearsals and tests)")
-    ap.add_argument("--no-twin", action="store_true", help="skip the stateless twins (pcr_params.index_no_hints = 1) and the host-buffer legs: counter passes "
+    ap.add_argument("--no-twin", action="store_true", help="--full: skip the stateless twins (pcr_params.index_no_hints = 1) and the host-buffer legs: counter passes "
                                                         "(scripts/profile_round.sh) then see the dispatches of ONE leg, the one the line's figures are of")
-    ap.add_argument("--sequence-scans", type=int, default=64, help="scans of the drive behind extra.sequence (the caller's workload: key frames, sub-map assembly, "
+    ap.add_argument("--sequence-scans", type=int, default=64, help="--full: scans of the drive behind extra.sequence (the caller's workload: key frames, sub-map assembly, "
                                                                     "pcr_scan2map_submap with init = previous pose); 0 skips it")
     args = ap.parse_args()
     if args.map_points is None:
@@ -344,9 +383,12 @@ def secondary(args, method=None, steps=None, warmup=None, embedded=False):
         rank_info.update(tile_points=int(tile.points.shape[0]), tile_core_points=int(tile.n_core), tile_axis=int(tile.axis),
                          tile_lo=float(tile.lo[tile.axis]), tile_hi=float(tile.hi[tile.axis]), halo=float(tile.halo), transport=ci["transport"])
 
+    last = {}
+
     def step(i):
         pose = inits[i % args.scans].copy()
-        reg.scan2Map(d_scans[i % args.scans], d_map, pose)
+        last["converged"] = reg.scan2Map(d_scans[i % args.scans], d_map, pose)
+        last["pose"] = pose
         return pose
 
     reg.set_profile(0)
@@ -358,24 +400,32 @@ def secondary(args, method=None, steps=None, warmup=None, embedded=False):
             dist.barrier()
         torch.cuda.synchronize()
 
-    wins = timed_windows(step, barrier, steps, max(1, args.windows))
+    if embedded:      # an "extra" line of a --full run: windows of `steps` steps each
+        wins = timed_windows(step, barrier, steps, max(1, args.windows))
+        sizes = [steps] * len(wins)
+    else:
+        wins, sizes = split_windows(step, barrier, steps, args.windows)
     if world_size > 1:
         t = torch.tensor(wins, dtype=torch.float64, device="cpu" if rehearse else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wins = [float(v) for v in t.tolist()]
-    elapsed = float(np.median(wins))
+    per_step = median_step(wins, sizes)
+    if rank == 0 and args.dump_outputs and not embedded:
+        dump_outputs(args.dump_outputs, last)
+    full = args.full or embedded
     if sharded:
         # every rank has to take part in every further call (each one is a chain of collectives): the per-rank report and, on rank 0 alone,
         # the N = 1 origin of the curve (the SAME scans against the WHOLE map, an unsharded handle) while the others wait at a barrier
-        reg.set_profile(1)
-        prep = aln = 0.0
-        for i in range(4):
-            step(i); st = reg.stats(); prep += st["index_ms"] / 4; aln += st["solve_ms"] / 4
-        reg.set_profile(0)
-        rank_info.update(target_prep_ms=prep, align_ms=aln)
+        if full:
+            reg.set_profile(1)
+            prep = aln = 0.0
+            for i in range(4):
+                step(i); st = reg.stats(); prep += st["index_ms"] / 4; aln += st["solve_ms"] / 4
+            reg.set_profile(0)
+            rank_info.update(target_prep_ms=prep, align_ms=aln)
         all_ranks = gather_ranks(dist, world_size, rank_info)
         n1 = None
-        if world_size >= 1:      # (one rank too: the same call with and without the exchange on one card is what the exchange costs)
+        if full:      # (one rank too: the same call with and without the exchange on one card is what the exchange costs)
             if rank == 0:
                 cls = VgicpRegister if method == "vgicp" else NdtRegister
                 reg1 = cls(device=local_rank, **(dict(vgicp_resolution=0.5) if method == "vgicp" else {}))
@@ -410,9 +460,9 @@ def secondary(args, method=None, steps=None, warmup=None, embedded=False):
         dist.barrier()
         dist.destroy_process_group()
         return
-    out = {"metric": f"scans/s ({workload.split(',')[0]}, BASELINE configs[{cfg - 1}])", "value": steps * (1 if sharded else world_size) / elapsed, "unit": "scans/s",
-           "n_gpus": world_size, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
-           "windows_ms": [1e3 * v for v in wins],
+    out = {"metric": f"scans/s ({workload.split(',')[0]}, BASELINE configs[{cfg - 1}])", "value": (1 if sharded else world_size) / per_step, "unit": "scans/s",
+           "n_gpus": world_size, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * per_step,
+           "windows_ms": [1e3 * v for v in wins], "window_steps": sizes,
            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f64" if method == "vgicp" else "f32",
            "data": "synthetic" + (" (REHEARSAL: all ranks on one card)" if rehearse else ""),
            "config": {"workload": workload, "scans_cycled": args.scans, "parallelism": parallelism},
@@ -421,6 +471,12 @@ def secondary(args, method=None, steps=None, warmup=None, embedded=False):
         out["ranks"] = all_ranks
         if n1:
             out["n1"] = n1
+        print(json.dumps(out), flush=True)
+        if world_size > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    if not full:
         print(json.dumps(out), flush=True)
         if world_size > 1:
             dist.barrier()
@@ -796,9 +852,12 @@ def main():
         rank_info.update(tile_points=int(tile.points.shape[0]), tile_core_points=int(tile.n_core), tile_axis=int(tile.axis),
                          tile_lo=float(tile.lo[tile.axis]), tile_hi=float(tile.hi[tile.axis]), transport=ci["transport"])
 
+    last = {}
+
     def step(i):
         pose = inits[i % args.scans].copy()
-        reg.scan2Map(d_scans[i % args.scans], d_map, pose)
+        last["converged"] = reg.scan2Map(d_scans[i % args.scans], d_map, pose)
+        last["pose"] = pose
         return pose
 
     reg.set_profile(0)
@@ -810,21 +869,22 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # EXACTLY args.steps steps per timed window, bracketed by barrier + synchronize; several windows back to back, the MAX over
-    # ranks of each, and the MEDIAN window is the one reported (a 200-step window is 50 ms: one stray host hiccup moves it by percent)
-    wins = timed_windows(step, barrier, args.steps, max(1, args.windows))
+    # EXACTLY args.steps timed steps, cut into --windows windows back to back, each bracketed by barrier + synchronize; the MAX over
+    # ranks of each, and the MEDIAN window (by time per step) is the one reported: one stray host hiccup moves a single window by percent
+    wins, sizes = split_windows(step, barrier, args.steps, args.windows)
     if world_size > 1:
         t = torch.tensor(wins, dtype=torch.float64, device="cpu" if rehearse else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wins = [float(v) for v in t.tolist()]
-    elapsed = float(np.median(wins))
-    units = args.steps * (1 if args.shard_map else world_size)
-    value = units / elapsed
+    per_step = median_step(wins, sizes)
+    value = (1 if args.shard_map else world_size) / per_step
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     out = {
         "metric": "scans/s (65 k-pt scan vs 1 M-pt submap, LOAM 10 iters) + pose RMSE vs CPU ref",
         "value": value, "unit": "scans/s", "n_gpus": world_size, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "windows_ms": [1e3 * v for v in wins], "higher_is_better": True, "scaling": scaling,
+        "ms_per_step": 1e3 * per_step, "windows_ms": [1e3 * v for v in wins], "window_steps": sizes, "higher_is_better": True, "scaling": scaling,
         "vs_baseline": None, "dtype": "f64", "data": "synthetic" + (" (REHEARSAL: all ranks on one card)" if rehearse else ""),
         "config": {"workload": f"pcr=loam, {N_SCAN}-pt 64-beam scan vs {args.map_points}-pt submap, {args.iters} GN iters, "
                                "early exit off, index rebuilt per call (previous call's bounding box and tile layout reused as checked hints), inputs in HBM",
@@ -863,6 +923,14 @@ def main():
         ct = time.perf_counter() - c0
         out["concurrent"] = {"streams": args.streams, "value": per * args.streams / ct, "unit": "scans/s",
                              "scans": per * args.streams, "note": "independent handles (pcr_params.loam_coresident = 1), one stream and one host thread each, same GPU"}
+    if not args.full:
+        out["ranks"] = gather_ranks(dist, world_size, rank_info)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world_size > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # ---- roofline of the dominant kernel (loam_iterate_kernel), live, HIP events on its stream.  Rank 0 reports it; with a sharded
     #      map every rank has to take part in the calls (each one is a chain of collectives) ----
     k_ms, k_n, idx_ms, tot_ms = 0.0, 0, 0.0, 0.0

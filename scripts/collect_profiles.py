@@ -24,7 +24,7 @@ f = newest("stats/**/*kernel_stats.csv")
 if f:
     rows = list(csv.DictReader(open(f)))
     with open(os.path.join(dst, f"{tag}_kernel_stats.csv"), "w") as o:
-        o.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline\n")
+        o.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline\n")
         o.write("Name,Calls,TotalDurationNs,AverageNs,Percentage,MinNs,MaxNs\n")
         for r in rows:
             o.write(",".join([kname(r["Name"]), r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["Percentage"], r["MinNs"], r["MaxNs"]]) + "\n")
@@ -34,7 +34,7 @@ for m in ("vgicp", "ndt"):
     if f:
         rows = list(csv.DictReader(open(f)))
         with open(os.path.join(dst, f"{tag}_{m}_kernel_stats.csv"), "w") as o:
-            o.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --method {m} --steps 40 --warmup 5 --no-cpu-baseline\n")
+            o.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --method {m} --steps 40 --warmup 5 --no-cpu-baseline\n")
             o.write("Name,Calls,TotalDurationNs,AverageNs,Percentage,MinNs,MaxNs\n")
             for r in rows:
                 o.write(",".join([kname(r["Name"]), r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["Percentage"], r["MinNs"], r["MaxNs"]]) + "\n")

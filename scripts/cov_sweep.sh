@@ -10,7 +10,7 @@ for cfg in "$@"; do
   OUT=$R/gpurun_out/covsweep_$1_$2_$3
   rm -rf $OUT && mkdir -p $OUT
   bad=$(cd $R && timeout -k 10 100 python scripts/cov_debug.py 2>&1 | grep -E "^bad" | head -1)
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --method vgicp --steps 30 --warmup 5 --no-cpu-baseline --no-extra --windows 1 > $OUT/stats.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --method vgicp --steps 30 --warmup 5 --no-cpu-baseline --no-extra --windows 1 > $OUT/stats.log 2>&1
   f=$(find $OUT/stats -name '*kernel_stats.csv' | head -1)
   python3 - "$f" "$cfg" "$bad" $OUT/stats.log <<'PY'
 import csv, sys, json

@@ -7,7 +7,7 @@ m=$1; tag=$2
 OUT=$R/gpurun_out/pmc_$tag
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$R/bench.py --method $m --steps 20 --warmup 3 --no-cpu-baseline --no-extra --windows 1"
+ARGS="$R/bench.py --full --method $m --steps 20 --warmup 3 --no-cpu-baseline --no-extra --windows 1"
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS --output-format csv -d $OUT/a -- python3 $ARGS > $OUT/a.log 2>&1
 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM_RD SQ_IFETCH SQ_INSTS_SMEM --output-format csv -d $OUT/b -- python3 $ARGS > $OUT/b.log 2>&1
 python3 - $OUT <<'PY'

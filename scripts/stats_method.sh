@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/stats_$tag
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 STEPS=40
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --method $m --steps $STEPS --warmup 5 --no-cpu-baseline --no-extra --windows 1 "$@" > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --method $m --steps $STEPS --warmup 5 --no-cpu-baseline --no-extra --windows 1 "$@" > $OUT/stats.log 2>&1
 f=$(find $OUT/stats -name '*kernel_stats.csv' | head -1)
 cp "$f" $OUT/kernel_stats.csv
 python3 - "$f" <<'PY'

@@ -4,7 +4,7 @@ out=${1:-gpurun_out/sweep_src}
 mkdir -p $out
 export PCR_LIB=$(pwd)/ab/libdev.so      # (the loader's override: the product library is not touched)
 run() {      # cell0 ratio levels
-  r=$(PCR_COV_CELL0=$1 PCR_COV_RATIO=$2 PCR_COV_LEVELS=$3 timeout -k 10 200 python bench.py --method vgicp --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value'],1), round(d['ms_per_step'],4), round(d['roofline']['target_prep_ms'],4), round(d['roofline']['align_ms'],4))")
+  r=$(PCR_COV_CELL0=$1 PCR_COV_RATIO=$2 PCR_COV_LEVELS=$3 timeout -k 10 200 python bench.py --full --method vgicp --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value'],1), round(d['ms_per_step'],4), round(d['roofline']['target_prep_ms'],4), round(d['roofline']['align_ms'],4))")
   echo "cell0 $1 ratio $2 levels $3 -> $r"
 }
 run 1 6 2

@@ -76,6 +76,45 @@ def test_a_failing_rank_fails_the_launch():
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_split_windows_times_exactly_the_given_steps():
+    """--steps is the number of timed steps: the windows share them out, every step index once, in order"""
+    import bench
+    seen = []
+    secs, sizes = bench.split_windows(seen.append, lambda: None, 23, 5)
+    assert seen == list(range(23)) and sizes == [5, 5, 5, 4, 4] and len(secs) == 5
+    seen.clear()
+    _, sizes = bench.split_windows(seen.append, lambda: None, 3, 5)       # fewer steps than windows: one step per window
+    assert seen == [0, 1, 2] and sizes == [1, 1, 1]
+    assert bench.median_step([1.0, 2.0, 9.0], [1, 1, 1]) == 2.0 and bench.median_step([10.0, 4.0, 3.0], [5, 4, 1]) == 2.0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_given_steps_and_dumps_the_last_pose(gpu, tmp_path):
+    """A plain run: the headline alone (none of --full's legs), exactly --steps timed steps, and --dump-outputs holds what the last of
+    them returned -- the pose a fresh handle computes from the same seeded inputs, bit for bit."""
+    import bench
+    import numpy as np
+    import torch
+    from simpleslam_amd import LoamRegister, synth
+    out = tmp_path / "out"
+    cmd = [sys.executable, BENCH, "--steps", "5", "--warmup", "1", "--windows", "2", "--map-points", "200000", "--scans", "2", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _line(r.stdout)
+    assert d["steps"] == 5 and sum(d["window_steps"]) == 5 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6 * d["value"]
+    assert not {"roofline", "index_kept", "no_index_hints", "host_buffers", "loc_static", "cpu_baseline", "extra"} & set(d)
+    pose, conv = np.load(out / "pose.npy"), np.load(out / "converged.npy")
+    assert pose.dtype == np.float64 and pose.shape == (4, 4) and conv.dtype == np.float64
+    # the last timed step is step 4: scan 4 % 2 = 0 from its perturbed start (bench.main's seeds)
+    world, m = synth.make_map(200_000, seed=bench.SEED + 2)
+    scan, T = synth.make_scan(world, 0, seed=bench.SEED + 2)
+    p = synth.perturb(T, bench.SEED + 2)
+    c = LoamRegister(device=0, loam_iters=10, loam_early_exit=0).scan2Map(torch.from_numpy(scan).cuda(), torch.from_numpy(m).cuda(), p)
+    np.testing.assert_array_equal(pose, p)
+    assert float(conv) == float(c)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("shard", [False, True])
 def test_two_ranks_rehearsed_on_one_card(shard):
@@ -85,7 +124,7 @@ def test_two_ranks_rehearsed_on_one_card(shard):
     N = 1 origin of the sharded curve."""
     env = _clean_env()
     env["PCR_BENCH_REHEARSE"] = "1"
-    cmd = [sys.executable, BENCH, "--gpus", "2", "--steps", "6", "--warmup", "2", "--windows", "1", "--map-points", "200000", "--scans", "2",
+    cmd = [sys.executable, BENCH, "--gpus", "2", "--full", "--steps", "6", "--warmup", "2", "--windows", "1", "--map-points", "200000", "--scans", "2",
            "--no-cpu-baseline", "--no-extra"] + (["--shard-map"] if shard else [])
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -110,7 +149,7 @@ def test_two_ranks_rehearsed_sharded_ndt_and_vgicp(method):
     between GPUs), the per-rank report and the N = 1 origin of the curve in the line."""
     env = _clean_env()
     env["PCR_BENCH_REHEARSE"] = "1"
-    cmd = [sys.executable, BENCH, "--gpus", "2", "--method", method, "--shard-map", "--steps", "4", "--warmup", "2", "--windows", "1", "--scans", "2",
+    cmd = [sys.executable, BENCH, "--gpus", "2", "--full", "--method", method, "--shard-map", "--steps", "4", "--warmup", "2", "--windows", "1", "--scans", "2",
            "--secondary-map-points", "300000", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -1,7 +1,7 @@
 """What of the path is PINNED to the reference's own code: the three nanoflann clients (pcl_adaptor / kfs_adaptor / vov_adaptor,
 third_parties/nanoflann) are compiled from where they lie into oracle/_ref and their answers are committed as
-tests/golden/knn_nanoflann.npz and ref_nanoflann_more.npz (scripts/make_golden.py, make_golden_ref.py).  These tests hold the
-CPU oracle (not gpu) and the HIP path (gpu) to them.  Everything else of the path (Eigen, PCL, FLANN arithmetic) is
+tests/golden/knn_nanoflann.npz, ref_nanoflann_more.npz and ref_nanoflann_live.npz (scripts/make_golden.py, make_golden_ref.py,
+make_golden_ref_live.py).  These tests hold the CPU oracle (not gpu) and the HIP path (gpu) to them.  Everything else of the path (Eigen, PCL, FLANN arithmetic) is
 restated and remains parity-unpinned: DESIGN.md section 2."""
 import os
 
@@ -148,35 +148,34 @@ def test_the_two_unpinnable_readings_are_bounded_by_measurement():
     assert dt < 1e-5 and dr < 1e-6
 
 
-needs_ref = pytest.mark.skipif(not oracle.ref_available(), reason="oracle/_ref not built (needs /root/reference at build time)")
+@pytest.fixture(scope="module")
+def live():
+    """the reference's answers for the two tests below and test_oracle.py's live k-NN (scripts/make_golden_ref_live.py)"""
+    return np.load(os.path.join(G, "ref_nanoflann_live.npz"))
 
 
-@needs_ref
-def test_loam_oracle_on_reference_nanoflann():
+def test_loam_oracle_on_reference_nanoflann(live):
     """The LOAM restatement searching through the reference's own tree (oracle_set_knn_backend) instead of its kd-tree: same
-    poses bit for bit on a cloud without exact ties -- the k-NN stage of the oracle IS the reference's, not a look-alike."""
+    poses bit for bit on a cloud without exact ties -- the k-NN stage of the oracle IS the reference's, not a look-alike.
+    The run through the reference's tree is stored (loam_pose / loam_converged)."""
     from simpleslam_amd import synth
     world, m = synth.make_map(50_000, seed=77)
     scan, T = synth.make_scan(world, 0, seed=77, beams=16, azimuths=512)
     T0 = synth.perturb(T, 77)
     prm = oracle.loam_params(iters=6, early_exit=0, threads=4)
     own = oracle.loam_scan2map(scan, m, T0, prm)
-    try:
-        oracle.use_reference_nanoflann(True)
-        ref = oracle.loam_scan2map(scan, m, T0, prm)
-    finally:
-        oracle.use_reference_nanoflann(False)
-    np.testing.assert_array_equal(own[0], ref[0])
-    assert own[1] == ref[1]
+    np.testing.assert_array_equal(own[0], live["loam_pose"])
+    assert int(own[1]) == int(live["loam_converged"])
 
 
-@needs_ref
-def test_reference_radius_search_is_the_strict_squared_distance_set(more):
+def test_reference_radius_search_is_the_strict_squared_distance_set(more, live):
     """PointCloudKdtree::radiusSearch (pcl_adaptor.hpp:60-78): the set is { i : |p_i - q|^2 < r^2 } with the squared distances
-    nanoflann accumulates in double -- what oracle/submap_oracle.c and the gated fitness restate."""
+    nanoflann accumulates in double -- what oracle/submap_oracle.c and the gated fitness restate.  The tree's answers are stored
+    (radius_idx / radius_d2, radius_counts per query)."""
     pts = more["knn_points"]
-    for q in more["knn_queries"][:32, :3].astype(np.float64):
-        idx, d2 = oracle.ref_radius(pts, q, 0.75)
+    ends = np.cumsum(live["radius_counts"])
+    for q, e, n in zip(more["knn_queries"][:32, :3].astype(np.float64), ends, live["radius_counts"]):
+        idx, d2 = live["radius_idx"][e - n:e], live["radius_d2"][e - n:e]
         d = ((pts[:, :3].astype(np.float64) - q) ** 2)
         full = d[:, 0] + d[:, 1] + d[:, 2]
         np.testing.assert_array_equal(np.sort(idx), np.flatnonzero(full < 0.75 * 0.75))
