@@ -169,7 +169,10 @@ int pcr_invalidate_target(pcr_handle* h);
  * this call evaluates the score (once; later calls return the cached value) against the target the handle holds at that moment --
  * what PCL's getFitnessScore() does with input_, final_transformation_ and the current target tree.  1.797e308 (DBL_MAX) when no
  * point has a neighbour or no target is prepared, like PCL.  (A handle of a sharded target evaluates it with the alignment instead:
- * every rank takes part in the sum.) */
+ * every rank takes part in the sum.)  The distances are PCL's float distances bit for bit; only the order of the double sum differs.
+ * A voxel lattice that holds the scan's region only hands the search to the covariance search grid, which holds every point.  An index
+ * cut to a region (a target too spread out for the dense tables: its bulk, or the room around a scan) answers only when every source point's
+ * nearest indexed point is provably nearer than the cut faces; otherwise this returns -1 and pcr_last_error names the cut. */
 double pcr_fitness(pcr_handle* h);
 
 /* ---- introspection used by tests and bench.py ---- */
@@ -394,9 +397,16 @@ int pcr_get_params(const pcr_handle* h, pcr_params* out);
 /* The fitness score of the reference's test/align.cpp:29-61: the source transformed by `pose` (float, as
  * pcl::transformPointCloud), 1-NN in the handle's current target, mean of the squared distances that are <= max_sq
  * (align.cpp uses 1.0); *n_in = points counted.  score = -1 when none is (align.cpp:56-59).  Any method's handle with a target.
- * An NDT handle whose last pcr_scan2map indexed the scan's region only (pcr_stats.region_index) indexes the target again, in full, when
- * that target came in as a HOST buffer (it still lies in the handle's staging copy); a DEVICE target is the caller's and may be gone: the
- * call fails and says so (pcr_set_target, or pcr_params.full_target = 1, avoid it). */
+ * The distances are float, bit for bit PCL's, and the gate is the comparison in double (a float distance against max_sq): *n_in is
+ * exact, and the score differs from a brute-force one only by the order of the double sum.  Source points with a coordinate that is
+ * not finite are not counted.
+ * A handle whose last pcr_scan2map indexed the scan's region only (pcr_stats.region_index): VGICP searches its covariance search grid,
+ * which holds every point; NDT indexes the target again, in full, when that target came in as a HOST buffer (it still lies in the
+ * handle's staging copy); a DEVICE target is the caller's and may be gone: the call fails and says so (pcr_set_target, or
+ * pcr_params.full_target = 1, avoid it).
+ * An index cut to a region (a target too spread out for the dense tables: its bulk, or the room around a scan): when a source point's
+ * nearest indexed point is not provably nearer than the cut faces (and than the gate), the call fails, score = -1, *n_in = 0, and the
+ * message names the cut -- it never returns the score of the part that was indexed. */
 int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double pose[16],
                       double max_sq, double* score, int64_t* n_in);
 

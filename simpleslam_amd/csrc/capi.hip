@@ -2172,6 +2172,14 @@ int pcr_voxel_filter_end(pcr_handle* h, size_t* n_out) {
 
 }  // extern "C"
 hipStream_t pcr_internal_stream(const pcr_handle* h) { return h ? h->stream : nullptr; }
+
+// An index cut to a region (a target too spread out for the dense tables: its bulk, or the room around a scan) cannot tell the nearest target
+// point of a source point that lies beyond a cut face, or nearer to one than to every point it holds.  Such a score is refused, never guessed.
+static std::string cut_fitness_message(double n) {
+    return std::to_string((long long)n) + " source points may have their nearest target point in the part of the target the index was cut off "
+           "(a target too spread out for the dense index, a stray point far from the map?): no fitness score against a cut index";
+}
+
 extern "C" {
 
 double pcr_fitness(pcr_handle* h) {
@@ -2189,10 +2197,21 @@ double pcr_fitness(pcr_handle* h) {
             if (set_device(h) || ensure_out32(h)) return -1.0;
             h->seq += 1.0;
             // (a lattice that holds the scan's region only cannot answer a nearest-neighbour question; the grid its covariances were searched on holds every point)
-            const GridIndex& fit_grid = (h->grid.filtered && h->cov_l1.valid && !h->cov_l1.filtered) ? h->cov_l1 : h->grid;
+            const bool full_search_grid = h->cov_l1.valid && !h->cov_l1.filtered;
+            if (h->grid.filtered && !full_search_grid) {
+                h->err = "the voxel lattice of the last pcr_scan2map holds the scan's region only (pcr_stats.region_index) and no grid of every target point is at hand";
+                h->fitness = -1.0;
+                return -1.0;
+            }
+            const GridIndex& fit_grid = h->grid.filtered ? h->cov_l1 : h->grid;
             if (fitness_launch(fit_grid, h->fit_src.as<float>(), h->fit_n, h->fit_stride, h->fit_pose, 1.7976931348623157e308, h->vg_partials.as<double>(),
                                h->out32_dev, h->stream, h->seq, nullptr) != hipSuccess) { h->err = "fitness_launch failed"; return -1.0; }
             if (wait_result(h, &h->out32_host[31], h->seq)) return -1.0;
+            if (h->out32_host[2] > 0) {      // (fitness_kernel: points whose nearest target point may lie beyond a cut face of the index)
+                h->err = cut_fitness_message(h->out32_host[2]);
+                h->fitness = -1.0;
+                return -1.0;
+            }
             h->fitness = h->out32_host[1] > 0 ? h->out32_host[0] / h->out32_host[1] : 1.7976931348623157e308;
         }
     }
@@ -2606,15 +2625,31 @@ int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t strid
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
     if (!h->have_target || !h->grid.valid) return fail(h, "no target: register a scan or call pcr_set_target first");
     if (n_src > 0xfffffff0ull) return fail(h, "source cloud too large");
+    const GridIndex* fit_grid = &h->grid;
     if (h->grid.filtered) {
-        // The last pcr_scan2map (NDT) indexed only the target points of its scan's region; a nearest-neighbour search needs them all.
-        // A target that came in as a HOST buffer still lies in this handle's staging copy and is indexed again, in full; a device buffer
-        // is the caller's and may be gone.
-        if (h->method != kNdt || h->tgt_ptr != h->tgt_stage.as<float>() || !h->tgt_n)
+        // The last pcr_scan2map (NDT, VGICP) indexed only the target points of its scan's region; a nearest-neighbour search needs them all.
+        // VGICP searched its covariances on a grid of its own that holds every point (pcr_fitness answers from it too).  Otherwise a target
+        // that came in as a HOST buffer still lies in this handle's staging copy and is indexed again, in full; a device buffer is the
+        // caller's and may be gone.
+        const bool staged = h->tgt_ptr == h->tgt_stage.as<float>() && h->tgt_n;
+        if (h->method == kVgicp && h->cov_l1.valid && !h->cov_l1.filtered) {
+            fit_grid = &h->cov_l1;
+        } else if (h->method == kVgicp && staged) {
+            // (cov_l1 is the search grid of the next preparation's covariances: it is built again there, whatever it holds)
+            const double scale = h->cov_scale_hint >= 1.3 ? h->cov_scale_hint : 1.0;
+            if (settle_grid(h, h->cov_l1, h->tgt_ptr, h->tgt_n, h->tgt_stride, h->prm.vgicp_resolution * scale, 0, nullptr)) return 1;
+            fit_grid = &h->cov_l1;
+        } else if (h->method == kNdt && staged) {
+            h->nd_target_ready = false;
+            if (settle_grid(h, h->grid, h->tgt_ptr, h->tgt_n, h->tgt_stride, (double)(float)h->prm.ndt_resolution, 1)) return 1;
+        } else if (h->method == kVgicp) {
+            return fail(h, "the voxel lattice of the last pcr_scan2map holds the scan's region only (pcr_stats.region_index), its search grid does not hold "
+                           "every point either, and the target was a device buffer: call pcr_set_target, or set pcr_params.full_target, before asking for "
+                           "a fitness score against it");
+        } else {
             return fail(h, "the target index of the last pcr_scan2map holds the scan's region only (pcr_stats.region_index) and the target was a device buffer: "
                            "call pcr_set_target, or set pcr_params.full_target, before asking for a fitness score against it");
-        h->nd_target_ready = false;
-        if (settle_grid(h, h->grid, h->tgt_ptr, h->tgt_n, h->tgt_stride, (double)(float)h->prm.ndt_resolution, 1)) return 1;
+        }
     }
     const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
@@ -2627,7 +2662,7 @@ int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t strid
         if (h->have_halo) shard_extent(h, ft.ext_lo, ft.ext_hi);
     }
     h->seq += 1.0;
-    H_TRY(fitness_launch(h->grid, d_src, n_src, stride_bytes / 4, pose, max_sq, h->vg_partials.as<double>(), h->out32_dev, h->stream, h->seq,
+    H_TRY(fitness_launch(*fit_grid, d_src, n_src, stride_bytes / 4, pose, max_sq, h->vg_partials.as<double>(), h->out32_dev, h->stream, h->seq,
                          h->use_tile ? &ft : nullptr));
     if (wait_result(h, &h->out32_host[31], h->seq)) return 1;
     if (sharded(h) && ranks_allreduce(h, h->out32_host, 3)) return 1;
@@ -2635,6 +2670,7 @@ int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t strid
     *score = cnt > 0 ? h->out32_host[0] / cnt : -1.0;      // align.cpp:56-59
     if (n_in) *n_in = (int64_t)cnt;
     if (h->use_tile && h->out32_host[2] > 0) return fail(h, "sharded fitness: a source point's nearest map point may lie beyond this rank's halo");
+    if (h->out32_host[2] > 0) { *score = -1.0; if (n_in) *n_in = 0; return fail(h, cut_fitness_message(h->out32_host[2])); }
     return 0;
 }
 

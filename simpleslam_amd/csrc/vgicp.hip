@@ -12,6 +12,8 @@
 //         that pose in the same pass), fixed-order reductions
 //   V6 LM driver                  lsq_registration_impl.hpp:53-171 -> host code in capi.hip
 // Also the PCL fitness score (pcl::Registration::getFitnessScore, VgicpRegister.cpp:42-45).
+#include <float.h>
+#include <math.h>
 #include <string.h>
 
 #include "pcr_internal.h"
@@ -729,14 +731,24 @@ __global__ __launch_bounds__(256) void fitness_kernel(GridView g, const float* _
     __shared__ double shc[256];
     __shared__ double shv[256];
     double acc = 0.0, cnt = 0.0, viol = 0.0;
+    // an index cut to a region (header.clamped: the bulk of the cloud, or the room around a scan) holds every target point between the faces of
+    // its lattice's interior; beyond a face marked in cut_mask lie points it left out.  Those faces bound the search as a tile's halo does.
+    const GridHeader& gh = *g.hdr;
+    const int cut = gh.clamped && !gh.empty ? gh.cut_mask : 0;
+    double cut_lo[3], cut_hi[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        cut_lo[d] = (cut >> d) & 1 ? (gh.org[d] + kPad + gh.shift) * gh.cell : -1e300;
+        cut_hi[d] = (cut >> (3 + d)) & 1 ? (gh.org[d] + gh.dims[d] - kPad + gh.shift) * gh.cell : 1e300;
+    }
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n_src; i += gridDim.x * 256) {
         const float* p = src + (size_t)i * stride;
         const float qx = T.m[0] * p[0] + T.m[4] * p[1] + T.m[8] * p[2] + T.m[12];
         const float qy = T.m[1] * p[0] + T.m[5] * p[1] + T.m[9] * p[2] + T.m[13];
         const float qz = T.m[2] * p[0] + T.m[6] * p[1] + T.m[10] * p[2] + T.m[14];
+        const double qd[3] = {(double)qx, (double)qy, (double)qz};
         double margin = 1e300;
         if (tile.use) {         // sharded target: the rank whose tile holds the transformed point scores it
-            const double qd[3] = {(double)qx, (double)qy, (double)qz};
             bool in = true;
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
@@ -745,6 +757,10 @@ __global__ __launch_bounds__(256) void fitness_kernel(GridView g, const float* _
             }
             if (!in) continue;
         }
+        if (cut && isfinite(qx) && isfinite(qy) && isfinite(qz)) {      // (a point with a coordinate that is not finite is at no finite distance from anything)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) margin = fmin(margin, fmin(qd[d] - cut_lo[d], cut_hi[d] - qd[d]));
+        }
         KeyList<1> L;
         ring_knn<1>(one_level(g), qx, qy, qz, max_range, L);
         float d = 3.0e38f;
@@ -752,9 +768,10 @@ __global__ __launch_bounds__(256) void fitness_kernel(GridView g, const float* _
             d = __uint_as_float((uint32_t)(L.k[0] >> 32));
             if (d <= max_range) { acc += (double)d; cnt += 1.0; }
         }
-        // the nearest point of the rank's cloud is the map's nearest only if it is nearer than the faces of the region the
+        // the nearest point of the rank's cloud (of the cut index) is the map's nearest only if it is nearer than the faces of the region the
         // cloud is complete in (or than the gate: farther points do not count anyway)
-        if (tile.use && margin < 1e29 && !(sqrt((double)d) * (1.0 + 1e-6) < margin) && !(sqrt((double)max_range) < margin)) viol += 1.0;
+        if ((tile.use || cut) && margin < 1e29 && !(sqrt((double)d) * (1.0 + 1e-6) < margin) && !(sqrt((double)max_range) * (1.0 + 1e-6) < margin))
+            viol += 1.0;
     }
     sh[threadIdx.x] = acc; shc[threadIdx.x] = cnt; shv[threadIdx.x] = viol;
     __syncthreads();
@@ -876,7 +893,10 @@ hipError_t fitness_launch(const GridIndex& grid, const float* d_src, size_t n_sr
     PoseF16 T;
     for (int i = 0; i < 16; ++i) T.m[i] = (float)pose[i];
     const uint32_t nb = vgicp_blocks((uint32_t)n_src);
-    const float mr = max_range >= 3.0e38 ? 3.0e38f : (float)max_range;
+    // the gate is "squared distance <= max_range" in double (PCL: float distances against a double max_range); distances are floats, so
+    // the largest float not above max_range is the same gate
+    float mr = max_range >= (double)FLT_MAX ? FLT_MAX : (float)max_range;
+    if ((double)mr > max_range) mr = nextafterf(mr, -FLT_MAX);
     FitTile ft;
     memset(&ft, 0, sizeof ft);
     if (tile) ft = *tile;

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import fitness_ref
 import oracle
 from simpleslam_amd import VgicpRegister, synth
 
@@ -101,8 +102,9 @@ def test_scan2map_matches_oracle(gpu, vg_world):
     assert et < 0.05 and er < 5e-3
     # final pose went through Matrix4f (VgicpRegister.cpp:37)
     np.testing.assert_array_equal(pose, pose.astype(np.float32).astype(np.float64))
-    # fitness score (pcl::Registration::getFitnessScore)
-    np.testing.assert_allclose(reg.getFitnessScore(), oracle.fitness_score(w["scan"], w["map"], pose), rtol=1e-6)
+    # fitness score (pcl::Registration::getFitnessScore): the same float distances, summed in another order
+    np.testing.assert_allclose(reg.getFitnessScore(), oracle.fitness_score(w["scan"], w["map"], pose),
+                               rtol=fitness_ref.sum_order_rtol(len(w["scan"])), atol=0)
 
 
 def test_device_resident_optimiser_equals_the_host_driven_one(gpu, vg_world):
@@ -241,7 +243,7 @@ def test_gated_fitness_of_align_cpp(gpu, vg_world):
         reg.scan2Map(w["scan"], w["map"], pose)                  # (a handle's later calls may index the scan's region only: the score must not care)
         got, n_in = reg.fitnessGated(w["scan"], T, gate)
         assert n_in == n_want
-        np.testing.assert_allclose(got, want, rtol=1e-6)
+        np.testing.assert_allclose(got, want, rtol=fitness_ref.sum_order_rtol(n_want), atol=0)
         far = np.eye(4); far[:3, 3] = [0.0, 0.0, 500.0]
         assert reg.fitnessGated(w["scan"], far, 1.0) == (-1.0, 0)
 
@@ -371,6 +373,14 @@ def test_region_list_of_a_map_sized_target_matches_the_whole_target(gpu):
         # the fitness score is a nearest-neighbour question about the WHOLE target: a lattice that holds the region's points only hands it to the
         # grid the covariances were searched on, which holds every point -- the same number as with the full preparation
         assert reg.getFitnessScore() == full.getFitnessScore(), (k, off)
+        if k >= 1:      # ... and the reference's number, ungated (getFitnessScore) and gated (fitnessGated)
+            _, d2 = oracle.knn_f32(m, fitness_ref.transform_f32(scan, p), 1)
+            want, n = fitness_ref.gated_from_sq(d2[:, 0], fitness_ref.DBL_MAX)
+            np.testing.assert_allclose(reg.getFitnessScore(), want, rtol=fitness_ref.sum_order_rtol(n), atol=0, err_msg=str(k))
+            want_g, n_g = fitness_ref.gated_from_sq(d2[:, 0], 1.0)
+            got_g, n_in = reg.fitnessGated(scan, p, 1.0)
+            assert n_in == n_g, (k, n_in, n_g)
+            np.testing.assert_allclose(got_g, want_g, rtol=fitness_ref.sum_order_rtol(n_g), atol=0, err_msg=str(k))
         if k == 0:
             assert reg.stats()["region_index"] == 0      # nothing to go by yet: the whole cloud is indexed
     assert full.stats()["region_repeats"] == 0 and full.stats()["region_index"] == 0
@@ -424,12 +434,14 @@ def test_gated_fitness_against_a_region_only_index_of_a_device_target_is_refused
     w = vg_world
     d_scan, d_map = torch.from_numpy(w["scan"]).cuda(), torch.from_numpy(w["map"]).cuda()
     reg = NdtRegister()
-    for _ in range(2):
+    for k in range(4):      # (from the second call on, once the lattice of an earlier full build can be taken over)
         pose = w["init"].copy()
         reg.scan2Map(d_scan, d_map, pose)
-    if reg.stats()["region_index"]:
-        with pytest.raises(PcrError, match="region only"):
-            reg.fitnessGated(d_scan, w["init"], 1.0)
+        if k >= 1 and reg.stats()["region_index"] == 1:
+            break
+    assert reg.stats()["region_index"] == 1
+    with pytest.raises(PcrError, match="region only"):
+        reg.fitnessGated(d_scan, w["init"], 1.0)
     full = NdtRegister(full_target=1)
     for _ in range(2):
         pose = w["init"].copy()
