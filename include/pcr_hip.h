@@ -410,6 +410,75 @@ int pcr_get_params(const pcr_handle* h, pcr_params* out);
 int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double pose[16],
                       double max_sq, double* score, int64_t* n_in);
 
+/* ---- Relocalisation from a coarse pose ----------------------------------------------------------------------------------------------
+ * The caller: the localisation program's operator sets the robot's pose by a click (/initialpose, dataproxy/src/RelocDataProxy.cpp:34-48)
+ * and LidarOdometry::generateOdom takes that click as the initial guess of ONE scan2Map (frontend/src/LidarOdometry.cpp:67-77, 121-126,
+ * 184).  A click is off by a metre or more and 10-30 degrees of yaw, outside the basin of convergence of LOAM, NDT and VGICP.
+ * pcr_relocalize scores a lattice of (x, y, yaw) hypotheses around it, refines the best few and keeps the one that fits best. */
+
+/* The most poses one pcr_fitness_batch or pcr_reloc_hypotheses call takes (2^20), and the most source points it scores per pose (2^26). */
+#define PCR_RELOC_MAX_POSES 1048576u
+#define PCR_BATCH_MAX_POINTS 67108864u
+
+/* pcr_fitness_gated for K poses (16 doubles each, column-major, host memory) of one source in one pass.  For every pose k, scores[k] and
+ * n_in[k] are what pcr_fitness_gated returns for that pose: *n_in exact, the score that of another summation order at most.  For a
+ * subset of up to 131 072 points the sum is taken in pcr_fitness_gated's own order: the results are bit for bit the single-pose call's.
+ * Two calls return identical bytes (no atomics).
+ * score_points: 0, or a value >= n_src, scores every point; otherwise the points i_j = floor(j n_src / score_points) (64-bit integer
+ * arithmetic), j = 0 .. score_points - 1, indexed on the device in place.
+ * The index searched is pcr_fitness_gated's (a region-only lattice: VGICP's covariance grid, or an NDT host target indexed again).
+ * An index cut to a region: a pose with a point whose nearest target point cannot be proved gets scores[k] = -1, n_in[k] = -1 (where
+ * pcr_fitness_gated fails); the others are scored, and the call returns 0.
+ * K <= PCR_RELOC_MAX_POSES, and at most PCR_BATCH_MAX_POINTS points are scored per pose (n_src, or score_points when it is smaller;
+ * more is refused with a message).  Sharded handles and handles with a query tile (pcr_set_query_tile) are refused. */
+int pcr_fitness_batch(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double* poses, size_t K,
+                      double max_sq, size_t score_points, double* scores, int64_t* n_in);
+
+typedef struct pcr_reloc_params {
+    uint32_t struct_size;         /* sizeof(pcr_reloc_params), set by pcr_reloc_default_params */
+    double xy_range, xy_step;     /* half-width and step of the x and y search, m (default 2, 0.5) */
+    double yaw_range, yaw_step;   /* half-width and step of the yaw search, rad (default 30 and 5 degrees) */
+    double max_sq;                /* gate of both scores (the reference's test/align.cpp: 1.0) */
+    int32_t refine_top;           /* distinct coarse winners refined by the handle's method (default 4) */
+    int32_t pad_;
+    uint64_t score_points;        /* source subset of the coarse score (pcr_fitness_batch; default 4096) */
+} pcr_reloc_params;
+void pcr_reloc_default_params(pcr_reloc_params* p);
+
+/* The hypothesis lattice around `coarse` (no device work).  nx = floor(xy_range / xy_step + 1e-9), nk = floor(yaw_range / yaw_step + 1e-9)
+ * (0 for a zero range).  Hypothesis (i, j, k), i, j in [-nx, nx], k in [-nk, nk], is number h = ((k + nk)(2nx + 1) + (j + nx))(2nx + 1) + (i + nx)
+ * (yaw outermost, then y, then x); its pose: translation t_c + (i xy_step, j xy_step, 0), rotation Rz(k yaw_step) R_c (about the map's z
+ * axis through the sensor), row by row with c = cos, s = sin (C library, double): row0 = c R0 - s R1, row1 = s R0 + c R1, row2 = R2.
+ * poses: capacity x 16 doubles; *K = the number written.  Refused with a message (pcr_last_error(NULL)): a non-positive step with a
+ * nonzero range, K > PCR_RELOC_MAX_POSES, refine_top < 1, a NULL or too small output. */
+int pcr_reloc_hypotheses(const double coarse[16], const pcr_reloc_params* p, double* poses, size_t capacity, size_t* K);
+
+typedef struct pcr_reloc_candidate {
+    int64_t hypothesis;           /* lattice number h of the pose the refinement started from */
+    int64_t coarse_n_in;          /* its coarse score (the score_points subset) */
+    double coarse_score;
+    double pose[16];              /* the refined pose (pcr_align from the hypothesis) */
+    int32_t converged;
+    int32_t pad_;
+    int64_t n_in;                 /* the refined pose's score on the whole source */
+    double score;
+} pcr_reloc_candidate;
+
+/* Relocalise: the preconditions of pcr_align (a kept target).  1. every hypothesis of pcr_reloc_hypotheses(pose_inout) is scored by
+ * pcr_fitness_batch on the score_points subset; 2. they are ranked by (-n_in, score, h), ascending, leaving out those with n_in <= 0 or
+ * refused; 3. down the ranking a hypothesis is taken unless one taken already lies within 1 of it in each of i, j and k (no yaw wrap),
+ * until refine_top are; 4. the click itself (0, 0, 0) is added when it was not taken; 5. each candidate is refined by pcr_align from its
+ * hypothesis pose -- bit for bit pcr_align's result; 6. the refined poses are scored on the WHOLE source (pcr_fitness_batch) and the
+ * first by (-n_in, score, candidate order) is chosen; 7. it is written to pose_inout / *converged, every candidate to cands (in the order
+ * taken, the click last when it was added) and the chosen one's index to *chosen.
+ * Fails (with a message) when no hypothesis has a point within the gate (a click far off the map), when a refinement fails (not
+ * converging is no failure), when capacity < refine_top + 1, or when n_src > PCR_BATCH_MAX_POINTS (the final score covers every point).
+ * State of the handle afterwards: pcr_fitness() (VGICP's getFitnessScore) evaluates the CHOSEN pose -- what it returns after a pcr_align
+ * from the chosen hypothesis.  pcr_get_stats, pcr_get_trace and pcr_get_timeline describe the last refinement, i.e. candidate
+ * *n_cands - 1 (the click when it was added), not necessarily the chosen one. */
+int pcr_relocalize(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const pcr_reloc_params* p,
+                   double pose_inout[16], int* converged, pcr_reloc_candidate* cands, size_t capacity, size_t* n_cands, size_t* chosen);
+
 #ifdef __cplusplus
 }
 #endif

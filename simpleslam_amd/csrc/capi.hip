@@ -82,6 +82,7 @@ struct pcr_handle {
     uint32_t last_blocks = 0;        // linearisation blocks of the last LOAM call (timeline readout)
     // source
     DeviceBuf src_stage;
+    DeviceBuf rl_poses, rl_part, rl_out, rl_src;   // pcr_fitness_batch: the poses in float, the [pose][chunk] partials, the sums; pcr_relocalize: its staged host source
     GridIndex vf_grid;               // pcl::VoxelGrid lattice of the cloud being down-sampled (pcr_voxel_filter)
     DeviceBuf vf_in, vf_out, vf_head, vf_sums, vf_count;
 
@@ -1838,6 +1839,7 @@ void pcr_destroy(pcr_handle* h) {
     if (dev_env("PCR_VF_DEBUG") && h->vf_builds) fprintf(stderr, "voxel filter: %llu index builds, %llu of them over a box or layout that did not hold the cloud\n", h->vf_builds, h->vf_stale);      // (development builds)
     if (h->comm && g_rccl.destroy) g_rccl.destroy(h->comm);
     h->grid.release(); h->tgt_stage.release(); h->src_stage.release();
+    h->rl_poses.release(); h->rl_part.release(); h->rl_out.release(); h->rl_src.release();
     peer_close(h);
     if (h->peer_own) (void)hipFree(h->peer_own);
     if (h->peer_status_host) (void)hipHostFree(h->peer_status_host);
@@ -2616,16 +2618,10 @@ int pcr_set_params(pcr_handle* h, const pcr_params* p) {
     return 0;
 }
 
-int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double pose[16], double max_sq,
-                      double* score, int64_t* n_in) {
-    if (!h) return 1;
-    h->err.clear();
-    if (!pose || !score) return fail(h, "pose or score is NULL");
-    if (n_src && !src) return fail(h, "NULL cloud with nonzero size");
-    if (check_stride(h, stride_bytes) || set_device(h)) return 1;
-    if (!h->have_target || !h->grid.valid) return fail(h, "no target: register a scan or call pcr_set_target first");
-    if (n_src > 0xfffffff0ull) return fail(h, "source cloud too large");
-    const GridIndex* fit_grid = &h->grid;
+// The index a nearest-neighbour score of the handle's current target runs on (pcr_fitness_gated, pcr_fitness_batch); it may index the
+// target again.
+static int fit_grid_for(pcr_handle* h, const GridIndex** out) {
+    *out = &h->grid;
     if (h->grid.filtered) {
         // The last pcr_scan2map (NDT, VGICP) indexed only the target points of its scan's region; a nearest-neighbour search needs them all.
         // VGICP searched its covariances on a grid of its own that holds every point (pcr_fitness answers from it too).  Otherwise a target
@@ -2633,12 +2629,12 @@ int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t strid
         // caller's and may be gone.
         const bool staged = h->tgt_ptr == h->tgt_stage.as<float>() && h->tgt_n;
         if (h->method == kVgicp && h->cov_l1.valid && !h->cov_l1.filtered) {
-            fit_grid = &h->cov_l1;
+            *out = &h->cov_l1;
         } else if (h->method == kVgicp && staged) {
             // (cov_l1 is the search grid of the next preparation's covariances: it is built again there, whatever it holds)
             const double scale = h->cov_scale_hint >= 1.3 ? h->cov_scale_hint : 1.0;
             if (settle_grid(h, h->cov_l1, h->tgt_ptr, h->tgt_n, h->tgt_stride, h->prm.vgicp_resolution * scale, 0, nullptr)) return 1;
-            fit_grid = &h->cov_l1;
+            *out = &h->cov_l1;
         } else if (h->method == kNdt && staged) {
             h->nd_target_ready = false;
             if (settle_grid(h, h->grid, h->tgt_ptr, h->tgt_n, h->tgt_stride, (double)(float)h->prm.ndt_resolution, 1)) return 1;
@@ -2651,6 +2647,20 @@ int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t strid
                            "call pcr_set_target, or set pcr_params.full_target, before asking for a fitness score against it");
         }
     }
+    return 0;
+}
+
+int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double pose[16], double max_sq,
+                      double* score, int64_t* n_in) {
+    if (!h) return 1;
+    h->err.clear();
+    if (!pose || !score) return fail(h, "pose or score is NULL");
+    if (n_src && !src) return fail(h, "NULL cloud with nonzero size");
+    if (check_stride(h, stride_bytes) || set_device(h)) return 1;
+    if (!h->have_target || !h->grid.valid) return fail(h, "no target: register a scan or call pcr_set_target first");
+    if (n_src > 0xfffffff0ull) return fail(h, "source cloud too large");
+    const GridIndex* fit_grid = nullptr;
+    if (fit_grid_for(h, &fit_grid)) return 1;
     const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
     if (ensure_out32(h)) return 1;
@@ -2822,6 +2832,243 @@ int pcr_comm_init(pcr_handle* h, const void* unique_id128, int rank, int nranks)
     peer_close(h);      // (one transport at a time)
     h->nranks = nranks; h->rank = rank;
     h->host_ar = nullptr; h->host_ar_user = nullptr;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- relocalisation from a coarse pose (pcr_fitness_batch, pcr_reloc_hypotheses, pcr_relocalize) ----------------------------------------
+namespace {
+
+// The lattice's half-widths in steps and its size, or a message.
+int reloc_dims(const pcr_reloc_params* p, long long* nx, long long* nk, size_t* K, std::string* err) {
+    if (!p) { *err = "pcr_reloc_params is NULL"; return 1; }
+    if (p->struct_size != sizeof(pcr_reloc_params)) { *err = "pcr_reloc_params.struct_size mismatch (start from pcr_reloc_default_params)"; return 1; }
+    if (!(p->xy_range >= 0.0) || !(p->yaw_range >= 0.0) || !std::isfinite(p->xy_range) || !std::isfinite(p->yaw_range)) {
+        *err = "xy_range and yaw_range must be finite and >= 0"; return 1;
+    }
+    if (p->xy_range > 0.0 && !(p->xy_step > 0.0)) { *err = "xy_step must be > 0 when xy_range is not 0"; return 1; }
+    if (p->yaw_range > 0.0 && !(p->yaw_step > 0.0)) { *err = "yaw_step must be > 0 when yaw_range is not 0"; return 1; }
+    if (p->refine_top < 1) { *err = "refine_top must be >= 1"; return 1; }
+    if (std::isnan(p->max_sq)) { *err = "max_sq is NaN"; return 1; }
+    const double fx = p->xy_range > 0.0 ? floor(p->xy_range / p->xy_step + 1e-9) : 0.0;
+    const double fk = p->yaw_range > 0.0 ? floor(p->yaw_range / p->yaw_step + 1e-9) : 0.0;
+    const double k = (2.0 * fx + 1.0) * (2.0 * fx + 1.0) * (2.0 * fk + 1.0);
+    if (!(k <= (double)PCR_RELOC_MAX_POSES)) {
+        *err = "the lattice has " + std::to_string(k) + " hypotheses, more than PCR_RELOC_MAX_POSES (" + std::to_string(PCR_RELOC_MAX_POSES) + ")";
+        return 1;
+    }
+    *nx = (long long)fx; *nk = (long long)fk; *K = (size_t)k;
+    return 0;
+}
+
+// Pose of hypothesis number hyp: translation t_c + (i step, j step, 0), rotation Rz(k yaw_step) R_c, row by row.
+void reloc_pose(const double C[16], const pcr_reloc_params* p, long long nx, long long nk, size_t hyp, double out[16]) {
+    const long long w = 2 * nx + 1;
+    const long long i = (long long)(hyp % (size_t)w) - nx, j = (long long)((hyp / (size_t)w) % (size_t)w) - nx, k = (long long)(hyp / (size_t)(w * w)) - nk;
+    const double a = (double)k * p->yaw_step, c = cos(a), s = sin(a);
+    for (int col = 0; col < 4; ++col) {      // column-major: entry (row, col) at col * 4 + row
+        const double r0 = C[col * 4], r1 = C[col * 4 + 1];
+        out[col * 4] = c * r0 - s * r1;
+        out[col * 4 + 1] = s * r0 + c * r1;
+        out[col * 4 + 2] = C[col * 4 + 2];
+        out[col * 4 + 3] = C[col * 4 + 3];
+    }
+    out[12] = C[12] + (double)i * p->xy_step;
+    out[13] = C[13] + (double)j * p->xy_step;
+    out[14] = C[14];
+}
+
+// The points scored per pose are capped at PCR_BATCH_MAX_POINTS (2^26 = 2^18 chunks of 256): with at least 8 poses per launch the
+// [pose][chunk] partials then stay within kPartMax = 2^21 entries (32 MB).
+int batch_points_check(pcr_handle* h, size_t n_src, size_t score_points) {
+    const size_t m = score_points == 0 || score_points >= n_src ? n_src : score_points;
+    if (m > PCR_BATCH_MAX_POINTS)
+        return fail(h, "pcr_fitness_batch scores at most PCR_BATCH_MAX_POINTS (" + std::to_string(PCR_BATCH_MAX_POINTS) + ") points per pose, " +
+                       std::to_string(m) + " were asked for: set score_points");
+    return 0;
+}
+
+// pcr_fitness_batch on a device source (arguments checked): poses in groups whose partials stay within kPartMax entries.
+int fitness_batch_run(pcr_handle* h, const GridIndex& grid, const float* d_src, size_t n_src, size_t stride_floats, const double* poses, size_t K,
+                      double max_sq, size_t score_points, double* scores, int64_t* n_in) {
+    static constexpr size_t kPartMax = size_t(1) << 21, kGroupMax = 16384;
+    const size_t m = score_points == 0 || score_points >= n_src ? n_src : score_points;
+    if (batch_points_check(h, n_src, score_points)) return 1;
+    const size_t chunks = std::max<size_t>((m + 255) / 256, 1);      // <= 2^18
+    const size_t group = std::min(kGroupMax, kPartMax / chunks / 8 * 8);      // >= 8: group x chunks <= kPartMax
+    std::vector<float> pf;
+    std::vector<RelocSum> sums;
+    for (size_t k0 = 0; k0 < K; k0 += group) {
+        const size_t g = std::min(group, K - k0);
+        pf.assign(g * 16, 0.f);
+        for (size_t q = 0; q < g * 16; ++q) pf[q] = (float)poses[k0 * 16 + q];
+        sums.resize(g);
+        H_TRY(h->rl_poses.reserve(g * 16 * sizeof(float)));
+        H_TRY(h->rl_part.reserve(g * chunks * sizeof(RelocPart)));
+        H_TRY(h->rl_out.reserve(g * sizeof(RelocSum)));
+        H_TRY(hipMemcpyAsync(h->rl_poses.p, pf.data(), g * 16 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        H_TRY(fitness_batch_launch(grid, d_src, n_src, stride_floats, m, h->rl_poses.as<float>(), g, max_sq, h->rl_part.as<RelocPart>(),
+                                   h->rl_out.as<RelocSum>(), h->stream));
+        H_TRY(hipMemcpyAsync(sums.data(), h->rl_out.p, g * sizeof(RelocSum), hipMemcpyDeviceToHost, h->stream));
+        H_TRY(hipStreamSynchronize(h->stream));
+        for (size_t q = 0; q < g; ++q) {
+            const RelocSum& r = sums[q];
+            if (r.viol > 0) { scores[k0 + q] = -1.0; n_in[k0 + q] = -1; continue; }      // (pcr_fitness_gated fails for this pose: cut_fitness_message)
+            const double cnt = (double)r.cnt;
+            scores[k0 + q] = cnt > 0 ? r.sum / cnt : -1.0;
+            n_in[k0 + q] = (int64_t)r.cnt;
+        }
+    }
+    return 0;
+}
+
+int batch_preconditions(pcr_handle* h, size_t n_src, size_t stride_bytes) {
+    if (check_stride(h, stride_bytes) || set_device(h)) return 1;
+    if (sharded(h)) return fail(h, "pcr_fitness_batch / pcr_relocalize do not serve sharded handles");
+    if (h->use_tile) return fail(h, "pcr_fitness_batch / pcr_relocalize do not serve a handle with a query tile (pcr_set_query_tile)");
+    if (!h->have_target || !h->grid.valid) return fail(h, "no target: register a scan or call pcr_set_target first");
+    if (n_src > 0xfffffff0ull) return fail(h, "source cloud too large");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pcr_fitness_batch(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double* poses, size_t K,
+                      double max_sq, size_t score_points, double* scores, int64_t* n_in) {
+    if (!h) return 1;
+    h->err.clear();
+    if (K > PCR_RELOC_MAX_POSES) return fail(h, "K = " + std::to_string(K) + " is more than PCR_RELOC_MAX_POSES (" + std::to_string(PCR_RELOC_MAX_POSES) + ")");
+    if (K && (!poses || !scores || !n_in)) return fail(h, "poses, scores or n_in is NULL");
+    if (n_src && !src) return fail(h, "NULL cloud with nonzero size");
+    if (batch_preconditions(h, n_src, stride_bytes)) return 1;
+    const GridIndex* fit_grid = nullptr;
+    if (fit_grid_for(h, &fit_grid)) return 1;
+    if (K == 0) return 0;
+    if (batch_points_check(h, n_src, score_points)) return 1;
+    const float* d_src = (const float*)src;
+    if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
+    return fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, poses, K, max_sq, score_points, scores, n_in);
+}
+
+void pcr_reloc_default_params(pcr_reloc_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->struct_size = sizeof(pcr_reloc_params);
+    p->xy_range = 2.0; p->xy_step = 0.5;
+    p->yaw_range = 30.0 * M_PI / 180.0; p->yaw_step = 5.0 * M_PI / 180.0;
+    p->max_sq = 1.0;
+    p->refine_top = 4;
+    p->score_points = 4096;
+}
+
+int pcr_reloc_hypotheses(const double coarse[16], const pcr_reloc_params* p, double* poses, size_t capacity, size_t* K) {
+    g_create_error.clear();
+    long long nx = 0, nk = 0;
+    size_t k = 0;
+    if (!coarse || !K) { g_create_error = "pcr_reloc_hypotheses: coarse or K is NULL"; return 1; }
+    if (reloc_dims(p, &nx, &nk, &k, &g_create_error)) { g_create_error = "pcr_reloc_hypotheses: " + g_create_error; return 1; }
+    *K = k;
+    if (!poses || capacity < k) {
+        g_create_error = "pcr_reloc_hypotheses: the output holds " + std::to_string(poses ? capacity : 0) + " poses, the lattice has " + std::to_string(k);
+        return 1;
+    }
+    for (size_t q = 0; q < k; ++q) reloc_pose(coarse, p, nx, nk, q, poses + q * 16);
+    return 0;
+}
+
+int pcr_relocalize(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const pcr_reloc_params* p,
+                   double pose_inout[16], int* converged, pcr_reloc_candidate* cands, size_t capacity, size_t* n_cands, size_t* chosen) {
+    if (!h) return 1;
+    h->err.clear();
+    if (!pose_inout || !cands || !n_cands || !chosen) return fail(h, "pose_inout, cands, n_cands or chosen is NULL");
+    if (n_src && !src) return fail(h, "NULL cloud with nonzero size");
+    long long nx = 0, nk = 0;
+    size_t K = 0;
+    std::string e;
+    if (reloc_dims(p, &nx, &nk, &K, &e)) return fail(h, e);
+    if (capacity < (size_t)p->refine_top + 1) return fail(h, "cands holds " + std::to_string(capacity) + " candidates, refine_top + 1 = " + std::to_string(p->refine_top + 1) + " are needed");
+    if (batch_preconditions(h, n_src, stride_bytes)) return 1;
+    if (ensure_full_target(h)) return 1;      // (pcr_align's precondition; the coarse score then runs on the full index too)
+    const float* d_src = (const float*)src;
+    if (!on_device && stage_host(h, &h->rl_src, src, n_src, stride_bytes, &d_src)) return 1;      // once, for every step below
+
+    // 1. the coarse score of every hypothesis on the subset
+    double click[16];
+    memcpy(click, pose_inout, sizeof click);
+    std::vector<double> poses(K * 16), score(K);
+    std::vector<int64_t> nin(K);
+    for (size_t q = 0; q < K; ++q) reloc_pose(click, p, nx, nk, q, &poses[q * 16]);
+    const GridIndex* fit_grid = nullptr;
+    if (fit_grid_for(h, &fit_grid)) return 1;
+    if (fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, poses.data(), K, p->max_sq, (size_t)p->score_points, score.data(), nin.data())) return 1;
+    // 2. ranked by (-n_in, score, h); refused hypotheses and those with nothing in the gate are not ranked
+    std::vector<size_t> rank;
+    for (size_t q = 0; q < K; ++q) if (nin[q] > 0) rank.push_back(q);
+    if (rank.empty())
+        return fail(h, "relocalisation: no hypothesis has a source point within the gate (max_sq = " + std::to_string(p->max_sq) +
+                       ") of the target: is the coarse pose on the map?");
+    std::sort(rank.begin(), rank.end(), [&](size_t a, size_t b) {
+        if (nin[a] != nin[b]) return nin[a] > nin[b];
+        if (score[a] != score[b]) return score[a] < score[b];
+        return a < b;
+    });
+    // 3. distinct winners: none within one step of another in each of i, j and k; 4. the click itself
+    const long long w = 2 * nx + 1;
+    auto ijk = [&](size_t q, long long* o) { o[0] = (long long)(q % (size_t)w); o[1] = (long long)((q / (size_t)w) % (size_t)w); o[2] = (long long)(q / (size_t)(w * w)); };
+    std::vector<size_t> taken;
+    for (size_t q : rank) {
+        if (taken.size() >= (size_t)p->refine_top) break;
+        long long a[3], b[3];
+        ijk(q, a);
+        bool near = false;
+        for (size_t t : taken) { ijk(t, b); near = near || (llabs(a[0] - b[0]) <= 1 && llabs(a[1] - b[1]) <= 1 && llabs(a[2] - b[2]) <= 1); }
+        if (!near) taken.push_back(q);
+    }
+    const size_t centre = (size_t)((nk * w + nx) * w + nx);
+    if (std::find(taken.begin(), taken.end(), centre) == taken.end()) taken.push_back(centre);
+    // 5. each candidate refined by pcr_align from its hypothesis pose
+    const size_t nc = taken.size();
+    std::vector<double> refined(nc * 16);
+    for (size_t c = 0; c < nc; ++c) {
+        pcr_reloc_candidate& o = cands[c];
+        memset(&o, 0, sizeof o);
+        o.hypothesis = (int64_t)taken[c];
+        o.coarse_n_in = nin[taken[c]];
+        o.coarse_score = score[taken[c]];
+        memcpy(o.pose, &poses[taken[c] * 16], sizeof o.pose);
+        int conv = 0;
+        if (pcr_align(h, d_src, n_src, stride_bytes, 1, o.pose, &conv)) {
+            const std::string why = h->err;
+            *n_cands = c;
+            return fail(h, "relocalisation: refining hypothesis " + std::to_string(taken[c]) + ": " + why);
+        }
+        o.converged = conv;
+        memcpy(&refined[c * 16], o.pose, sizeof o.pose);
+    }
+    *n_cands = nc;
+    // 6. the refined poses scored on the whole source; the first by (-n_in, score, candidate order); the click when none has a point in the gate
+    std::vector<double> fs(nc);
+    std::vector<int64_t> fn(nc);
+    if (fit_grid_for(h, &fit_grid)) return 1;
+    if (fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, refined.data(), nc, p->max_sq, 0, fs.data(), fn.data())) return 1;
+    size_t best = nc - 1;
+    bool any = false;
+    for (size_t c = 0; c < nc; ++c) {
+        cands[c].n_in = fn[c];
+        cands[c].score = fs[c];
+        if (fn[c] <= 0) continue;
+        if (!any || fn[c] > fn[best] || (fn[c] == fn[best] && fs[c] < fs[best])) { best = c; any = true; }
+    }
+    if (!any) best = (size_t)(std::find(taken.begin(), taken.end(), centre) - taken.begin());
+    // 7. the chosen pose.  pcr_fitness() evaluates the pose of the handle's last alignment (VGICP: fit_pose, kept by run_vgicp); that was the last
+    // candidate's, so it is pointed at the chosen one -- the same scan, the same target: what a fresh pcr_align from the chosen hypothesis leaves
+    memcpy(pose_inout, cands[best].pose, 16 * sizeof(double));
+    if (h->fit_pending) { memcpy(h->fit_pose, cands[best].pose, sizeof h->fit_pose); h->fitness = 1.7976931348623157e308; }
+    if (converged) *converged = cands[best].converged;
+    *chosen = best;
     return 0;
 }
 

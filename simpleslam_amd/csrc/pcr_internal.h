@@ -363,6 +363,13 @@ struct FitTile { int32_t use, pad_; double lo[3], hi[3], ext_lo[3], ext_hi[3]; }
 hipError_t fitness_launch(const GridIndex& grid, const float* d_src, size_t n_src, size_t stride_floats, const double pose[16], double max_range,
                           double* d_partials, double* d_out32, hipStream_t s, double seq = 0.0, const FitTile* tile = nullptr);
 uint32_t vgicp_blocks(uint32_t n_src);
+// pcr_fitness_batch (reloc.hip): the gated score of n_poses poses (d_poses: 16 floats each, column-major) of the subset i_j = floor(j n_src / m),
+// j < m, of the source.  d_part: n_poses x ceil(m / 256) partials; d_out[h]: the sum of the counted squared distances, their number, and the
+// number of points whose nearest target point may lie beyond a cut face of the index (fitness_kernel's out32[0..2])
+struct RelocPart { double sum; uint32_t cnt, viol; };
+struct RelocSum { double sum; unsigned long long cnt, viol, pad_; };
+hipError_t fitness_batch_launch(const GridIndex& grid, const float* d_src, size_t n_src, size_t stride_floats, size_t m, const float* d_poses,
+                                size_t n_poses, double max_sq, RelocPart* d_part, RelocSum* d_out, hipStream_t s);
 
 // pcl::VoxelGrid on the device (voxel_filter.hip); grid must have been built with pcl_mode = 1
 // (two launches queued behind the build; they read the header themselves and do nothing when it says overflow, stale or empty.  d_inten: n floats,

@@ -100,6 +100,31 @@ public:
         isConverge = conv != 0;
         return isConverge;
     }
+    // Relocalisation from a coarse pose (pcr_relocalize) against the target set by setTarget: the reloc branch of
+    // LidarOdometry::generateOdom (frontend/src/LidarOdometry.cpp:121-126), where the operator's click (RelocDataProxy.cpp:34-48) is `res`.
+    // `res` becomes the chosen candidate's refined pose; p = nullptr: pcr_reloc_default_params.  Fails like align: logs, returns false and
+    // leaves `res` alone.  cands / chosen (optional): every refined candidate and the index of the one taken.
+    bool relocalize(const PC_cPtr& src, pose_t& res, const pcr_reloc_params* p = nullptr, std::vector<pcr_reloc_candidate>* cands = nullptr,
+                    size_t* chosen = nullptr) {
+        pcr_reloc_params dp;
+        pcr_reloc_default_params(&dp);
+        if (!p) p = &dp;
+        std::vector<pcr_reloc_candidate> c((size_t)(p->refine_top > 0 ? p->refine_top : 0) + 1);
+        size_t nc = 0, ch = 0;
+        int conv = 0;
+        pose_t out = res;
+        if (pcr_relocalize(h_, src->points.data(), src->size(), sizeof(PointXYZI), 0, p, out.data(), &conv, c.data(), c.size(), &nc, &ch)) {
+            logError(pcr_last_error(h_));
+            return isConverge = false;
+        }
+        lastError_.clear();
+        res = out;
+        c.resize(nc);
+        if (cands) *cands = c;
+        if (chosen) *chosen = ch;
+        isConverge = conv != 0;
+        return isConverge;
+    }
     pcr_handle* handle() { return h_; }
     // getFitnessScore of the reference's test/align.cpp:29-61: mean squared 1-NN distance (<= max_sq) of the source under `pose`
     // against the target of the last registration; -1 when no point is that close
@@ -218,6 +243,17 @@ public:
             have_target_ = true;
         }
         isConverge = reg_->align(src, res);
+        lastError_ = reg_->lastError();
+        return isConverge;
+    }
+    // the reloc branch of generateOdom against the static map: `dst` indexed at the first call, as scan2Map does
+    bool relocalize(const PC_cPtr& src, const PC_cPtr& dst, pose_t& res, const pcr_reloc_params* p = nullptr,
+                    std::vector<pcr_reloc_candidate>* cands = nullptr, size_t* chosen = nullptr) {
+        if (!have_target_) {
+            try { reg_->setTarget(dst); } catch (const std::exception& e) { logError(e.what()); return isConverge = false; }
+            have_target_ = true;
+        }
+        isConverge = reg_->relocalize(src, res, p, cands, chosen);
         lastError_ = reg_->lastError();
         return isConverge;
     }

@@ -12,6 +12,9 @@
 // one line per FURTHER scan, "<scan.pcd> <init_pose.txt>"; every scan (the first included) goes through PCR::StaticMapRegister (the map is
 // indexed at the first call and stays in HBM) AND through a fresh plain registrar's scan2Map: both poses are printed and must be equal.
 // Prints the refined pose (17 significant digits), the converged flag and the elapsed time of scan2Map.
+// --reloc [xy_range yaw_range_deg]: the reloc branch of generateOdom (LidarOdometry.cpp:121-126): init_pose.txt is the operator's coarse click,
+// and the scan goes through PCR::StaticMapRegister::relocalize (pcr_relocalize; default window +-2 m, +-30 deg).  Prints every refined
+// candidate, the chosen hypothesis and its pose.
 //
 // Older forms, kept for the raw-float fixtures of the test suite (x y z intensity records):
 //   loc_harness <method> <map.f32> <scan.f32> <init_pose.txt> [downSampleVoxelGridSize]
@@ -19,6 +22,7 @@
 // (the second builds the map like MapManager::updateMap: keyframes.txt holds one line per key frame, "<cloud.f32> r00 r01 .. r33";
 // the sub-map is assembled on the device around the initial position (8 m, grid) and never copied back).
 #include <chrono>
+#include <cstdlib>
 #include <cstdio>
 #include <fstream>
 #include <string>
@@ -55,8 +59,22 @@ static bool ends_with(const std::string& s, const char* suffix) {
     return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
 }
 
+// --reloc at argv[i]: followed by both window values (true), by none (false), or by one only (refused: usage)
+static bool is_value(const char* a) { return a[0] != '-' || (a[1] >= '0' && a[1] <= '9') || a[1] == '.'; }
+static bool reloc_window_given(int argc, char** argv, int i) {
+    const int values = (i + 1 < argc && is_value(argv[i + 1])) + (i + 2 < argc && is_value(argv[i + 1]) && is_value(argv[i + 2]));
+    if (values == 1) throw std::invalid_argument("--reloc takes both window values (xy_range and yaw_range_deg) or none");
+    for (int k = 1; k <= values; ++k) {
+        char* end = nullptr;
+        (void)std::strtod(argv[i + k], &end);
+        if (end == argv[i + k] || *end) throw std::invalid_argument(std::string("--reloc: not a number: ") + argv[i + k]);
+    }
+    return values == 2;
+}
+
 // test/loc.cpp as it is wired: configuration -> MapManager(pcd_file) -> LidarOdometry (factory on frontend.pcr) -> one scan
 static int run_from_config(int argc, char** argv) {
+    for (int i = 4; i < argc; ++i) if (std::string(argv[i]) == "--reloc") (void)reloc_window_given(argc, argv, i);      // (before any work)
     config::Params::load(argv[1]);
     auto cfg = config::Params::getInstance();
     const auto pcr_type = cfg["frontend"]["pcr"].get<std::string>();                 // LidarOdometry.cpp:32
@@ -75,6 +93,30 @@ static int run_from_config(int argc, char** argv) {
     const size_t scan_before = scan->size();
     if (downsample) pcp::voxelDownSample(scan, grid_size);                           // LidarOdometry.cpp:170-171
     PCR::pose_t pose = read_pose(argv[3]);
+    for (int i = 4; i < argc; ++i) {
+        if (std::string(argv[i]) != "--reloc") continue;
+        pcr_reloc_params rp;
+        pcr_reloc_default_params(&rp);
+        if (reloc_window_given(argc, argv, i)) {
+            rp.xy_range = std::stod(argv[i + 1]);
+            rp.yaw_range = std::stod(argv[i + 2]) * 3.14159265358979323846 / 180.0;
+        }
+        auto loc = PCR::makeStaticMapRegister(pcr_type);
+        std::vector<pcr_reloc_candidate> cands;
+        size_t chosen = 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        const bool conv = loc->relocalize(scan, map, pose, &rp, &cands, &chosen);
+        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (!loc->lastError().empty()) { std::fprintf(stderr, "error: %s\n", loc->lastError().c_str()); return 3; }
+        std::printf("pcr %s  reloc  map %zu  scan %zu  window %.9g m %.9g rad  candidates %zu  relocalize %.6f s\n", pcr_type.c_str(), map->size(),
+                    scan->size(), rp.xy_range, rp.yaw_range, cands.size(), sec);
+        for (size_t c = 0; c < cands.size(); ++c)
+            std::printf("candidate %zu hypothesis %lld coarse %lld %.17g refined %lld %.17g converged %d\n", c, (long long)cands[c].hypothesis,
+                        (long long)cands[c].coarse_n_in, cands[c].coarse_score, (long long)cands[c].n_in, cands[c].score, (int)cands[c].converged);
+        std::printf("chosen %zu hypothesis %lld converged %d\n", chosen, (long long)cands[chosen].hypothesis, (int)conv);
+        for (int r = 0; r < 4; ++r) std::printf("%.17g %.17g %.17g %.17g\n", pose(r, 0), pose(r, 1), pose(r, 2), pose(r, 3));
+        return 0;
+    }
     for (int i = 4; i + 1 < argc; ++i) {
         if (std::string(argv[i]) != "--static") continue;
         // the static-map loop: scans[0] = the one of the command line, the others from the list
@@ -119,12 +161,21 @@ static int run_from_config(int argc, char** argv) {
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s <params.json> <scan.pcd> <init_pose.txt> [--no-downsample]\n"
+        std::fprintf(stderr, "usage: %s <params.json> <scan.pcd> <init_pose.txt> [--no-downsample] [--static <list> | --reloc [xy_range yaw_range_deg]]\n"
                              "       %s <loam|ndt|vgicp> <map.f32> <scan.f32> <init_pose.txt> [grid]\n", argv[0], argv[0]);
         return 2;
     }
     try {
         if (ends_with(argv[1], ".json")) return run_from_config(argc, argv);
+    } catch (const std::invalid_argument& e) {
+        std::fprintf(stderr, "error: %s\nusage: %s <params.json> <scan.pcd> <init_pose.txt> [--no-downsample] [--static <list> | --reloc [xy_range yaw_range_deg]]\n",
+                     e.what(), argv[0]);
+        return 2;
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+    try {
         if (argc < 5) throw std::runtime_error("the raw-float form needs <method> <map.f32> <scan.f32> <init_pose.txt>");
         auto reg = PCR::makeRegister(argv[1]);
         const std::string map_arg = argv[2];

@@ -63,7 +63,7 @@ ABI_SYMBOLS = [
     "pcr_ndt_opt_create", "pcr_ndt_opt_destroy", "pcr_ndt_opt_request", "pcr_ndt_opt_feed", "pcr_ndt_opt_result", "pcr_ndt_opt_counts",
     "pcr_vgicp_opt_create", "pcr_vgicp_opt_destroy", "pcr_vgicp_opt_request", "pcr_vgicp_opt_feed", "pcr_vgicp_opt_result",
     "pcr_sc_default_params", "pcr_sc_create", "pcr_sc_destroy", "pcr_sc_last_error", "pcr_sc_size", "pcr_sc_add", "pcr_sc_descriptor", "pcr_sc_distance",
-    "pcr_sc_query",
+    "pcr_sc_query", "pcr_fitness_batch", "pcr_reloc_default_params", "pcr_reloc_hypotheses", "pcr_relocalize",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -74,6 +74,18 @@ class ScParams(C.Structure):
     """struct pcr_sc_params (include/pcr_hip.h)."""
     _fields_ = [("lidar_height", C.c_double), ("num_exclude_recent", C.c_int32), ("build_tree_gap", C.c_int32), ("num_candidates", C.c_int32),
                 ("pad", C.c_int32), ("search_ratio", C.c_double), ("dist_thres", C.c_double)]
+
+
+class RelocParams(C.Structure):
+    """struct pcr_reloc_params (include/pcr_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("xy_range", C.c_double), ("xy_step", C.c_double), ("yaw_range", C.c_double),
+                ("yaw_step", C.c_double), ("max_sq", C.c_double), ("refine_top", C.c_int32), ("pad_", C.c_int32), ("score_points", C.c_uint64)]
+
+
+class RelocCandidate(C.Structure):
+    """struct pcr_reloc_candidate (include/pcr_hip.h)."""
+    _fields_ = [("hypothesis", C.c_int64), ("coarse_n_in", C.c_int64), ("coarse_score", C.c_double), ("pose", C.c_double * 16),
+                ("converged", C.c_int32), ("pad_", C.c_int32), ("n_in", C.c_int64), ("score", C.c_double)]
 
 
 _lib = None
@@ -185,6 +197,12 @@ def load_library():
     L.pcr_sc_descriptor.argtypes = [vp, C.c_size_t, vp, vp, vp]
     L.pcr_sc_distance.argtypes = [vp, C.c_size_t, C.c_size_t, dp, ip]
     L.pcr_sc_query.argtypes = [vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_float), dp]
+    L.pcr_fitness_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, C.c_size_t, C.c_double, C.c_size_t, dp, C.POINTER(C.c_int64)]
+    L.pcr_reloc_default_params.argtypes = [C.POINTER(RelocParams)]
+    L.pcr_reloc_default_params.restype = None
+    L.pcr_reloc_hypotheses.argtypes = [dp, C.POINTER(RelocParams), dp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pcr_relocalize.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(RelocParams), dp, ip, C.POINTER(RelocCandidate), C.c_size_t,
+                                 C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -201,6 +219,33 @@ def default_params(**overrides):
 
 class PcrError(RuntimeError):
     pass
+
+
+def reloc_params(**overrides):
+    """pcr_reloc_default_params with fields overridden (xy_range, xy_step, yaw_range, yaw_step in radians, max_sq, refine_top, score_points)."""
+    p = RelocParams()
+    load_library().pcr_reloc_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if k not in ("xy_range", "xy_step", "yaw_range", "yaw_step", "max_sq", "refine_top", "score_points"):
+            raise AttributeError(f"pcr_reloc_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def reloc_hypotheses(coarse, **params):
+    """pcr_reloc_hypotheses: the (K, 4, 4) lattice of poses around `coarse` (yaw outermost, then y, then x; include/pcr_hip.h)."""
+    L = load_library()
+    p = reloc_params(**params)
+    c = _pose_in(coarse)
+    dp = C.POINTER(C.c_double)
+    K = C.c_size_t(0)
+    rc = L.pcr_reloc_hypotheses(c.ctypes.data_as(dp), C.byref(p), None, 0, C.byref(K))
+    if rc != 0 and K.value == 0:
+        raise PcrError(L.pcr_last_error(None).decode())
+    out = np.zeros((K.value, 16))
+    if L.pcr_reloc_hypotheses(c.ctypes.data_as(dp), C.byref(p), out.ctypes.data_as(dp), K.value, C.byref(K)) != 0:
+        raise PcrError(L.pcr_last_error(None).decode())
+    return out.reshape(-1, 4, 4).transpose(0, 2, 1).copy()
 
 
 def _cloud(x):
@@ -436,6 +481,41 @@ class PointCloudRegister:
         score, cnt = C.c_double(0), C.c_int64(0)
         self._check(self._lib.pcr_fitness_gated(self._h, p, n, s, dev, pc.ctypes.data_as(C.POINTER(C.c_double)), float(max_sq), C.byref(score), C.byref(cnt)))
         return score.value, int(cnt.value)
+
+    def fitnessBatch(self, src, poses, max_sq=1.0, score_points=0):
+        """pcr_fitness_batch: fitnessGated of every pose of `poses` (K, 4, 4) in one pass -> (scores (K,) float64, n_in (K,) int64).  A pose a
+        cut index cannot score gets (-1, -1).  score_points: 0 = every point, else the subset floor(j n / score_points)."""
+        p, n, s, dev, _k = _cloud(src)
+        P = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+        cm = np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(-1)      # column-major per pose
+        K = P.shape[0]
+        scores = np.zeros(K, np.float64)
+        n_in = np.zeros(K, np.int64)
+        dp = C.POINTER(C.c_double)
+        self._check(self._lib.pcr_fitness_batch(self._h, p, n, s, dev, cm.ctypes.data_as(dp), K, float(max_sq), int(score_points),
+                                                scores.ctypes.data_as(dp), n_in.ctypes.data_as(C.POINTER(C.c_int64))))
+        return scores, n_in
+
+    def relocalize(self, src, pose, **params):
+        """pcr_relocalize from the coarse pose `pose` (4x4, updated in place as align() does) against the kept target (setTarget):
+        -> (converged, candidates, chosen).  candidates: one dict per refined hypothesis (hypothesis, coarse_n_in, coarse_score, pose,
+        converged, n_in, score); chosen: the index of the one taken.  params: fields of pcr_reloc_params (reloc_params)."""
+        p, n, s, dev, _k = _cloud(src)
+        rp = reloc_params(**params)
+        pose_np = np.asarray(pose)
+        if pose_np.shape != (4, 4):
+            raise ValueError("pose must be 4x4")
+        pc = _pose_in(pose_np)
+        cap = rp.refine_top + 1
+        cands = (RelocCandidate * cap)()
+        conv, nc, ch = C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.pcr_relocalize(self._h, p, n, s, dev, C.byref(rp), pc.ctypes.data_as(C.POINTER(C.c_double)), C.byref(conv),
+                                             cands, cap, C.byref(nc), C.byref(ch)))
+        pose_np[...] = _pose_out(pc)
+        out = [dict(hypothesis=c.hypothesis, coarse_n_in=c.coarse_n_in, coarse_score=c.coarse_score, pose=_pose_out(np.array(c.pose[:])),
+                    converged=bool(c.converged), n_in=c.n_in, score=c.score) for c in cands[:nc.value]]
+        self.isConverge = bool(conv.value)
+        return self.isConverge, out, int(ch.value)
 
     def _check(self, rc):
         if rc != 0:
