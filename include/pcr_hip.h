@@ -291,6 +291,13 @@ int pcr_sc_add(pcr_sc* sc, const void* pts, size_t n, size_t stride_bytes, int o
 int pcr_sc_descriptor(const pcr_sc* sc, size_t id, double* desc_row_major_20x60, double* ring_key_20, double* sector_key_60);
 int pcr_sc_distance(const pcr_sc* sc, size_t id1, size_t id2, double* dist, int* shift);
 int pcr_sc_query(pcr_sc* sc, long long id, long long* match, float* yaw_rad, double* min_dist);
+/* distanceBtnScanContext of an outside scan (lidar frame, not added) against EVERY stored context, on the device.
+ * dist[i], shift[i] are exactly what pcr_sc_distance(q, i) returns if the same cloud were added as context q:
+ * same sector-key alignment, same 2*round(0.5*(float)search_ratio*60)+1 shifts in ascending order, strict '<',
+ * DBL_MAX / 0 for a context against which every column is empty. dist, shift: pcr_sc_size() entries each.
+ * Every context's descriptor is kept in HBM as float (4 800 B each, what pcr_sc_add binned); the query is binned into a scratch
+ * buffer and never enters the database.  On an empty database the call returns 0 and writes nothing. */
+int pcr_sc_distances(pcr_sc* sc, const void* pts, size_t n, size_t stride_bytes, int on_device, double* dist, int32_t* shift);
 
 /* The NDT optimiser on its own (host only, no GPU): pclomp's computeTransformation + computeStepLengthMT (ndt_omp_impl.hpp:81-171,
  * 735-932) as the state machine that pcr_scan2map runs on the device (csrc/ndt_opt.h), driven from outside -- the caller evaluates what
@@ -478,6 +485,46 @@ typedef struct pcr_reloc_candidate {
  * *n_cands - 1 (the click when it was added), not necessarily the chosen one. */
 int pcr_relocalize(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const pcr_reloc_params* p,
                    double pose_inout[16], int* converged, pcr_reloc_candidate* cands, size_t capacity, size_t* n_cands, size_t* chosen);
+
+/* ---- Global relocalisation: no pose at all (start-up, or tracking lost) ----------------------------------------------------------------
+ * The places are the key frames whose ScanContext is nearest the scan's (pcr_sc_distances against every stored context); around each
+ * place's coarse pose a pcr_relocalize lattice is scored, all places in one pass, and the best refined pose is chosen. */
+typedef struct pcr_global_reloc_params {
+    uint32_t struct_size;      /* set by pcr_global_reloc_default_params */
+    int32_t places;            /* best contexts tried, by (dist, id) ascending (default 5) */
+    double max_dist;           /* contexts with dist > max_dist are not tried (default DBL_MAX: no limit) */
+    pcr_reloc_params local;    /* lattice around each place, gate, refine_top PER PLACE, score_points;
+                                  default +-2 m @ 0.5 m, +-9 deg @ 3 deg, refine_top 2, max_sq 1, 4096 points */
+} pcr_global_reloc_params;
+void pcr_global_reloc_default_params(pcr_global_reloc_params* p);
+
+typedef struct pcr_global_reloc_candidate {
+    int64_t place;             /* context / key-frame index */
+    double sc_dist; int32_t sc_shift; int32_t pad_;
+    pcr_reloc_candidate c;     /* hypothesis (within that place's lattice), coarse and final scores, refined pose */
+} pcr_global_reloc_candidate;
+
+/* Host-only (no device work): the coarse pose of a place, kf_pose * Rz(-yaw) with yaw = deg2rad<float>(6 * shift) as pcr_sc_query forms
+ * it -- the rotation about the key frame's own z: with c = cos(yaw), s = sin(yaw) (C library, double), column 0 becomes c C0 - s C1 and
+ * column 1 becomes s C0 + c C1 -- and its pcr_reloc_hypotheses lattice (capacity x 16 doubles, *K = the number written).  Refused with a
+ * message (pcr_last_error(NULL)) as pcr_reloc_hypotheses refuses. */
+int pcr_global_reloc_hypotheses(const double kf_pose[16], int32_t shift, const pcr_reloc_params* local,
+                                double* poses, size_t capacity, size_t* K);
+
+/* Global relocalisation: the preconditions of pcr_relocalize (a kept target, e.g. the whole map; no shards, no query tile), and a
+ * ScanContext database on the handle's device with one context per key frame, kf_poses its n_kf = pcr_sc_size() poses (16 doubles
+ * each, column-major).  1. pcr_sc_distances of src (the registration's own cloud, sensor frame); the places are the best p->places
+ * contexts by (dist, id), leaving out those at DBL_MAX or beyond max_dist; 2. every place's pcr_global_reloc_hypotheses lattice, all
+ * places in ONE pcr_fitness_batch pass on the score_points subset; 3. per place, ranking and distinct winners exactly as steps 2-3 of
+ * pcr_relocalize (no click is added); 4. each candidate refined by pcr_align from its hypothesis pose (bit for bit pcr_align), the
+ * refined poses scored on the whole source in one pass, and the first by (-n_in, score, candidate order) chosen -- candidate 0 when
+ * none has a point in the gate.  Candidates are ordered by place rank, then in the order taken; capacity >= places * local.refine_top.
+ * Fails with a message, the handle untouched, when no place qualifies or no hypothesis of any place has a point within the gate.
+ * The handle afterwards: as after pcr_relocalize (pcr_fitness() evaluates the chosen pose).  Refused parameters and outputs are reported
+ * through pcr_last_error(h), or pcr_last_error(NULL) when h is NULL. */
+int pcr_relocalize_global(pcr_handle* h, pcr_sc* sc, const double* kf_poses, size_t n_kf, const void* src, size_t n_src, size_t stride_bytes,
+                          int on_device, const pcr_global_reloc_params* p, double pose_out[16], int* converged,
+                          pcr_global_reloc_candidate* cands, size_t capacity, size_t* n_cands, size_t* chosen);
 
 #ifdef __cplusplus
 }

@@ -5,4 +5,5 @@ pcr.py (host mirror of the reference's PCR::PointCloudRegister plugin), synth.py
 (deterministic synthetic clouds for tests and bench.py).
 """
 from .pcr import (LoamRegister, NdtRegister, PcrError, PointCloudRegister, ScanContext, SubMap, VgicpRegister,  # noqa: F401
-                  default_params, load_library, make_register, reloc_hypotheses, reloc_params)
+                  default_params, global_reloc_hypotheses, global_reloc_params, load_library, make_register, reloc_hypotheses,
+                  reloc_params)

@@ -2932,6 +2932,80 @@ int batch_preconditions(pcr_handle* h, size_t n_src, size_t stride_bytes) {
     return 0;
 }
 
+// pcr_relocalize step 2: hypotheses 0 .. K-1 of one lattice with a point in the gate, ranked by (-n_in, score, h); refused ones (n_in = -1)
+// and those with nothing in the gate are not ranked
+std::vector<size_t> reloc_rank(const double* score, const int64_t* nin, size_t K) {
+    std::vector<size_t> rank;
+    for (size_t q = 0; q < K; ++q) if (nin[q] > 0) rank.push_back(q);
+    std::sort(rank.begin(), rank.end(), [&](size_t a, size_t b) {
+        if (nin[a] != nin[b]) return nin[a] > nin[b];
+        if (score[a] != score[b]) return score[a] < score[b];
+        return a < b;
+    });
+    return rank;
+}
+
+// (i, j, k) lattice coordinates of hypothesis q, each counted from 0
+void reloc_ijk(size_t q, long long nx, long long* o) {
+    const long long w = 2 * nx + 1;
+    o[0] = (long long)(q % (size_t)w); o[1] = (long long)((q / (size_t)w) % (size_t)w); o[2] = (long long)(q / (size_t)(w * w));
+}
+
+// pcr_relocalize step 3: down the ranking, a hypothesis is taken unless one taken already lies within one step of it in each of i, j and k
+std::vector<size_t> reloc_distinct(const std::vector<size_t>& rank, long long nx, int32_t refine_top) {
+    std::vector<size_t> taken;
+    for (size_t q : rank) {
+        if (taken.size() >= (size_t)refine_top) break;
+        long long a[3], b[3];
+        reloc_ijk(q, nx, a);
+        bool near = false;
+        for (size_t t : taken) { reloc_ijk(t, nx, b); near = near || (llabs(a[0] - b[0]) <= 1 && llabs(a[1] - b[1]) <= 1 && llabs(a[2] - b[2]) <= 1); }
+        if (!near) taken.push_back(q);
+    }
+    return taken;
+}
+
+// pcr_relocalize step 5: the candidate of hypothesis `hyp` (its pose, coarse score) refined by pcr_align from that pose.  On failure: the message.
+int reloc_refine(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_bytes, size_t hyp, const double pose[16], double coarse_score,
+                 int64_t coarse_n_in, pcr_reloc_candidate& o, std::string* why) {
+    memset(&o, 0, sizeof o);
+    o.hypothesis = (int64_t)hyp;
+    o.coarse_n_in = coarse_n_in;
+    o.coarse_score = coarse_score;
+    memcpy(o.pose, pose, sizeof o.pose);
+    int conv = 0;
+    if (pcr_align(h, d_src, n_src, stride_bytes, 1, o.pose, &conv)) { *why = h->err; return 1; }
+    o.converged = conv;
+    return 0;
+}
+
+// pcr_relocalize step 6: the refined poses scored on the whole source in one pass; *best = the first by (-n_in, score, candidate order),
+// *any = false when none has a point in the gate (*best is then left alone)
+int reloc_choose(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_bytes, double max_sq, pcr_reloc_candidate* const* cands, size_t nc,
+                 size_t* best, bool* any) {
+    std::vector<double> refined(nc * 16), fs(nc);
+    std::vector<int64_t> fn(nc);
+    for (size_t c = 0; c < nc; ++c) memcpy(&refined[c * 16], cands[c]->pose, 16 * sizeof(double));
+    const GridIndex* fit_grid = nullptr;
+    if (fit_grid_for(h, &fit_grid)) return 1;
+    if (fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, refined.data(), nc, max_sq, 0, fs.data(), fn.data())) return 1;
+    *any = false;
+    for (size_t c = 0; c < nc; ++c) {
+        cands[c]->n_in = fn[c];
+        cands[c]->score = fs[c];
+        if (fn[c] <= 0) continue;
+        if (!*any || fn[c] > fn[*best] || (fn[c] == fn[*best] && fs[c] < fs[*best])) { *best = c; *any = true; }
+    }
+    return 0;
+}
+
+// pcr_relocalize step 7, the handle's side: pcr_fitness() evaluates the pose of the handle's last alignment (VGICP: fit_pose, kept by
+// run_vgicp); that was the last candidate's, so it is pointed at the chosen one -- the same scan, the same target: what a fresh pcr_align
+// from the chosen hypothesis leaves
+void reloc_point_fitness_at(pcr_handle* h, const double pose[16]) {
+    if (h->fit_pending) { memcpy(h->fit_pose, pose, sizeof h->fit_pose); h->fitness = 1.7976931348623157e308; }
+}
+
 }  // namespace
 
 extern "C" {
@@ -3005,69 +3079,190 @@ int pcr_relocalize(pcr_handle* h, const void* src, size_t n_src, size_t stride_b
     if (fit_grid_for(h, &fit_grid)) return 1;
     if (fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, poses.data(), K, p->max_sq, (size_t)p->score_points, score.data(), nin.data())) return 1;
     // 2. ranked by (-n_in, score, h); refused hypotheses and those with nothing in the gate are not ranked
-    std::vector<size_t> rank;
-    for (size_t q = 0; q < K; ++q) if (nin[q] > 0) rank.push_back(q);
+    const std::vector<size_t> rank = reloc_rank(score.data(), nin.data(), K);
     if (rank.empty())
         return fail(h, "relocalisation: no hypothesis has a source point within the gate (max_sq = " + std::to_string(p->max_sq) +
                        ") of the target: is the coarse pose on the map?");
-    std::sort(rank.begin(), rank.end(), [&](size_t a, size_t b) {
-        if (nin[a] != nin[b]) return nin[a] > nin[b];
-        if (score[a] != score[b]) return score[a] < score[b];
-        return a < b;
-    });
     // 3. distinct winners: none within one step of another in each of i, j and k; 4. the click itself
+    std::vector<size_t> taken = reloc_distinct(rank, nx, p->refine_top);
     const long long w = 2 * nx + 1;
-    auto ijk = [&](size_t q, long long* o) { o[0] = (long long)(q % (size_t)w); o[1] = (long long)((q / (size_t)w) % (size_t)w); o[2] = (long long)(q / (size_t)(w * w)); };
-    std::vector<size_t> taken;
-    for (size_t q : rank) {
-        if (taken.size() >= (size_t)p->refine_top) break;
-        long long a[3], b[3];
-        ijk(q, a);
-        bool near = false;
-        for (size_t t : taken) { ijk(t, b); near = near || (llabs(a[0] - b[0]) <= 1 && llabs(a[1] - b[1]) <= 1 && llabs(a[2] - b[2]) <= 1); }
-        if (!near) taken.push_back(q);
-    }
     const size_t centre = (size_t)((nk * w + nx) * w + nx);
     if (std::find(taken.begin(), taken.end(), centre) == taken.end()) taken.push_back(centre);
     // 5. each candidate refined by pcr_align from its hypothesis pose
     const size_t nc = taken.size();
-    std::vector<double> refined(nc * 16);
+    std::vector<pcr_reloc_candidate*> cp(nc);
     for (size_t c = 0; c < nc; ++c) {
-        pcr_reloc_candidate& o = cands[c];
-        memset(&o, 0, sizeof o);
-        o.hypothesis = (int64_t)taken[c];
-        o.coarse_n_in = nin[taken[c]];
-        o.coarse_score = score[taken[c]];
-        memcpy(o.pose, &poses[taken[c] * 16], sizeof o.pose);
-        int conv = 0;
-        if (pcr_align(h, d_src, n_src, stride_bytes, 1, o.pose, &conv)) {
-            const std::string why = h->err;
+        cp[c] = &cands[c];
+        std::string why;
+        if (reloc_refine(h, d_src, n_src, stride_bytes, taken[c], &poses[taken[c] * 16], score[taken[c]], nin[taken[c]], cands[c], &why)) {
             *n_cands = c;
             return fail(h, "relocalisation: refining hypothesis " + std::to_string(taken[c]) + ": " + why);
         }
-        o.converged = conv;
-        memcpy(&refined[c * 16], o.pose, sizeof o.pose);
     }
     *n_cands = nc;
     // 6. the refined poses scored on the whole source; the first by (-n_in, score, candidate order); the click when none has a point in the gate
-    std::vector<double> fs(nc);
-    std::vector<int64_t> fn(nc);
-    if (fit_grid_for(h, &fit_grid)) return 1;
-    if (fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, refined.data(), nc, p->max_sq, 0, fs.data(), fn.data())) return 1;
     size_t best = nc - 1;
     bool any = false;
-    for (size_t c = 0; c < nc; ++c) {
-        cands[c].n_in = fn[c];
-        cands[c].score = fs[c];
-        if (fn[c] <= 0) continue;
-        if (!any || fn[c] > fn[best] || (fn[c] == fn[best] && fs[c] < fs[best])) { best = c; any = true; }
-    }
+    if (reloc_choose(h, d_src, n_src, stride_bytes, p->max_sq, cp.data(), nc, &best, &any)) return 1;
     if (!any) best = (size_t)(std::find(taken.begin(), taken.end(), centre) - taken.begin());
-    // 7. the chosen pose.  pcr_fitness() evaluates the pose of the handle's last alignment (VGICP: fit_pose, kept by run_vgicp); that was the last
-    // candidate's, so it is pointed at the chosen one -- the same scan, the same target: what a fresh pcr_align from the chosen hypothesis leaves
+    // 7. the chosen pose
     memcpy(pose_inout, cands[best].pose, 16 * sizeof(double));
-    if (h->fit_pending) { memcpy(h->fit_pose, cands[best].pose, sizeof h->fit_pose); h->fitness = 1.7976931348623157e308; }
+    reloc_point_fitness_at(h, cands[best].pose);
     if (converged) *converged = cands[best].converged;
+    *chosen = best;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- global relocalisation (pcr_global_reloc_hypotheses, pcr_relocalize_global) ----------------------------------------------------------
+namespace {
+
+// The coarse pose of a place: kf_pose * Rz(-yaw), yaw = deg2rad<float>(6 deg * shift) exactly as pcr_sc_query forms it.  Column by column
+// (c = cos(yaw), s = sin(yaw), double): col0 = c C0 - s C1, col1 = s C0 + c C1, col2 and col3 as they are.
+void place_pose(const double T[16], int32_t shift, double out[16]) {
+    const float yaw = (float)((double)((360.0f / 60.0f) * (float)shift) * 3.14159265358979323846 / 180.0);      // deg2rad<float>
+    const double c = cos((double)yaw), s = sin((double)yaw);
+    memcpy(out, T, 16 * sizeof(double));
+    for (int r = 0; r < 4; ++r) {
+        out[r] = c * T[r] - s * T[4 + r];
+        out[4 + r] = s * T[r] + c * T[4 + r];
+    }
+}
+
+int global_params_check(const pcr_global_reloc_params* p, long long* nx, long long* nk, size_t* K, std::string* err) {
+    if (!p) { *err = "pcr_global_reloc_params is NULL"; return 1; }
+    if (p->struct_size != sizeof(pcr_global_reloc_params)) {
+        *err = "pcr_global_reloc_params.struct_size mismatch (start from pcr_global_reloc_default_params)"; return 1;
+    }
+    if (p->places < 1) { *err = "places must be >= 1"; return 1; }
+    if (std::isnan(p->max_dist)) { *err = "max_dist is NaN"; return 1; }
+    if (reloc_dims(&p->local, nx, nk, K, err)) { *err = "local lattice: " + *err; return 1; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pcr_global_reloc_default_params(pcr_global_reloc_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->struct_size = sizeof(pcr_global_reloc_params);
+    p->places = 5;
+    p->max_dist = 1.7976931348623157e308;
+    pcr_reloc_default_params(&p->local);
+    p->local.yaw_range = 9.0 * M_PI / 180.0; p->local.yaw_step = 3.0 * M_PI / 180.0;      // the yaw of a place is known to one 6-degree sector
+    p->local.refine_top = 2;
+}
+
+int pcr_global_reloc_hypotheses(const double kf_pose[16], int32_t shift, const pcr_reloc_params* local, double* poses, size_t capacity, size_t* K) {
+    g_create_error.clear();
+    if (!kf_pose || !K) { g_create_error = "pcr_global_reloc_hypotheses: kf_pose or K is NULL"; return 1; }
+    long long nx = 0, nk = 0;
+    size_t k = 0;
+    if (reloc_dims(local, &nx, &nk, &k, &g_create_error)) { g_create_error = "pcr_global_reloc_hypotheses: " + g_create_error; return 1; }
+    *K = k;
+    if (!poses || capacity < k) {
+        g_create_error = "pcr_global_reloc_hypotheses: the output holds " + std::to_string(poses ? capacity : 0) + " poses, the lattice has " + std::to_string(k);
+        return 1;
+    }
+    double coarse[16];
+    place_pose(kf_pose, shift, coarse);
+    for (size_t q = 0; q < k; ++q) reloc_pose(coarse, local, nx, nk, q, poses + q * 16);
+    return 0;
+}
+
+int pcr_relocalize_global(pcr_handle* h, pcr_sc* sc, const double* kf_poses, size_t n_kf, const void* src, size_t n_src, size_t stride_bytes,
+                          int on_device, const pcr_global_reloc_params* p, double pose_out[16], int* converged,
+                          pcr_global_reloc_candidate* cands, size_t capacity, size_t* n_cands, size_t* chosen) {
+    // argument errors go to the handle, or to pcr_last_error(NULL) when there is none
+    auto refuse = [&](const std::string& m) { if (h) return fail(h, m); g_create_error = "pcr_relocalize_global: " + m; return 1; };
+    g_create_error.clear();
+    if (h) h->err.clear();
+    long long nx = 0, nk = 0;
+    size_t K = 0;
+    std::string e;
+    if (global_params_check(p, &nx, &nk, &K, &e)) return refuse(e);
+    const size_t need = (size_t)p->places * (size_t)p->local.refine_top;
+    if (!pose_out || !cands || !n_cands || !chosen) return refuse("pose_out, cands, n_cands or chosen is NULL");
+    if (capacity < need) return refuse("cands holds " + std::to_string(capacity) + " candidates, places x refine_top = " + std::to_string(need) + " are needed");
+    if (!h) return refuse("the handle is NULL");
+    if (!sc) return fail(h, "sc is NULL");
+    if (n_src && !src) return fail(h, "NULL cloud with nonzero size");
+    size_t M = 0;
+    pcr_sc_size(sc, &M);
+    if (n_kf != M) return fail(h, "n_kf = " + std::to_string(n_kf) + " key-frame poses for " + std::to_string(M) + " ScanContexts: one pose per context");
+    if (M && !kf_poses) return fail(h, "kf_poses is NULL");
+    if (sc_device(sc) != h->device) return fail(h, "the ScanContext database lives on device " + std::to_string(sc_device(sc)) + ", the handle on " + std::to_string(h->device));
+    if (batch_preconditions(h, n_src, stride_bytes)) return 1;
+    if (batch_points_check(h, n_src, 0)) return 1;      // (the final score covers every point)
+
+    // 1. the places: the scan's ScanContext distance to every key frame's, best by (dist, id); none at DBL_MAX or beyond max_dist
+    std::vector<double> dist(M);
+    std::vector<int32_t> shift(M);
+    if (pcr_sc_distances(sc, src, n_src, stride_bytes, on_device, dist.data(), shift.data()))
+        return fail(h, std::string("global relocalisation: ScanContext distances: ") + pcr_sc_last_error(sc));
+    if (set_device(h)) return 1;
+    std::vector<size_t> place;
+    for (size_t i = 0; i < M; ++i) if (dist[i] != 1.7976931348623157e308 && dist[i] <= p->max_dist) place.push_back(i);
+    const size_t np = std::min(place.size(), (size_t)p->places);
+    std::partial_sort(place.begin(), place.begin() + np, place.end(), [&](size_t a, size_t b) { return dist[a] != dist[b] ? dist[a] < dist[b] : a < b; });
+    place.resize(np);
+    if (place.empty())
+        return fail(h, "global relocalisation: no place qualifies (" + std::to_string(M) + " contexts, max_dist = " + std::to_string(p->max_dist) +
+                       "): is the scan from the mapped area, and were its key frames added to the ScanContext database?");
+    if (np * K > (size_t)PCR_RELOC_MAX_POSES)
+        return fail(h, "global relocalisation: " + std::to_string(np) + " places x " + std::to_string(K) + " hypotheses is more than PCR_RELOC_MAX_POSES (" +
+                       std::to_string(PCR_RELOC_MAX_POSES) + ")");
+    if (ensure_full_target(h)) return 1;      // (pcr_align's precondition; the coarse score then runs on the full index too)
+    const float* d_src = (const float*)src;
+    if (!on_device && stage_host(h, &h->rl_src, src, n_src, stride_bytes, &d_src)) return 1;      // once, for every step below
+
+    // 2. every place's lattice around its coarse pose, all in one batched score on the subset
+    std::vector<double> poses(np * K * 16), score(np * K);
+    std::vector<int64_t> nin(np * K);
+    for (size_t pl = 0; pl < np; ++pl) {
+        double coarse[16];
+        place_pose(kf_poses + place[pl] * 16, shift[place[pl]], coarse);
+        for (size_t q = 0; q < K; ++q) reloc_pose(coarse, &p->local, nx, nk, q, &poses[(pl * K + q) * 16]);
+    }
+    const GridIndex* fit_grid = nullptr;
+    if (fit_grid_for(h, &fit_grid)) return 1;
+    if (fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, poses.data(), np * K, p->local.max_sq, (size_t)p->local.score_points,
+                          score.data(), nin.data())) return 1;
+    // 3. per place: ranked by (-n_in, score, h), distinct winners (pcr_relocalize steps 2-3, no click)
+    std::vector<std::pair<size_t, size_t>> taken;      // (place rank, hypothesis)
+    for (size_t pl = 0; pl < np; ++pl)
+        for (size_t q : reloc_distinct(reloc_rank(&score[pl * K], &nin[pl * K], K), nx, p->local.refine_top)) taken.emplace_back(pl, q);
+    if (taken.empty())
+        return fail(h, "global relocalisation: no hypothesis of the " + std::to_string(np) + " places has a source point within the gate (max_sq = " +
+                       std::to_string(p->local.max_sq) + ") of the target: is the target the whole map?");
+    // 4. each candidate refined by pcr_align; the refined poses scored on the whole source, the first by (-n_in, score, candidate order)
+    const size_t nc = taken.size();
+    std::vector<pcr_reloc_candidate*> cp(nc);
+    for (size_t c = 0; c < nc; ++c) {
+        const size_t pl = taken[c].first, q = taken[c].second, at = pl * K + q;
+        pcr_global_reloc_candidate& o = cands[c];
+        memset(&o, 0, sizeof o);
+        o.place = (int64_t)place[pl];
+        o.sc_dist = dist[place[pl]];
+        o.sc_shift = shift[place[pl]];
+        cp[c] = &o.c;
+        std::string why;
+        if (reloc_refine(h, d_src, n_src, stride_bytes, q, &poses[at * 16], score[at], nin[at], o.c, &why)) {
+            *n_cands = c;
+            return fail(h, "global relocalisation: refining hypothesis " + std::to_string(q) + " of place " + std::to_string(place[pl]) + ": " + why);
+        }
+    }
+    *n_cands = nc;
+    size_t best = 0;
+    bool any = false;
+    if (reloc_choose(h, d_src, n_src, stride_bytes, p->local.max_sq, cp.data(), nc, &best, &any)) return 1;
+    // 5. the chosen pose; the handle as after pcr_relocalize
+    memcpy(pose_out, cands[best].c.pose, 16 * sizeof(double));
+    reloc_point_fitness_at(h, cands[best].c.pose);
+    if (converged) *converged = cands[best].c.converged;
     *chosen = best;
     return 0;
 }

@@ -367,6 +367,8 @@ uint32_t vgicp_blocks(uint32_t n_src);
 // j < m, of the source.  d_part: n_poses x ceil(m / 256) partials; d_out[h]: the sum of the counted squared distances, their number, and the
 // number of points whose nearest target point may lie beyond a cut face of the index (fitness_kernel's out32[0..2])
 struct RelocPart { double sum; uint32_t cnt, viol; };
+// the device a ScanContext database lives on (scancontext.hip)
+int sc_device(const pcr_sc* sc);
 struct RelocSum { double sum; unsigned long long cnt, viol, pad_; };
 hipError_t fitness_batch_launch(const GridIndex& grid, const float* d_src, size_t n_src, size_t stride_floats, size_t m, const float* d_poses,
                                 size_t n_poses, double max_sq, RelocPart* d_part, RelocSum* d_out, hipStream_t s);

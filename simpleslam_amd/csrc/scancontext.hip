@@ -6,6 +6,8 @@
 // and stays host C++, restated line by line: ring key / sector key (:198-229), fastAlignUsingVkey (:94-114),
 // distanceBtnScanContext (:116-150), computeSimularity (:68-92), query with its lazily rebuilt candidate tree (:231-279;
 // an exact 10-NN over the 20-dimensional ring keys, by brute force here instead of nanoflann's VectorOfVectorsKdTree).
+// Every descriptor is also kept in HBM (float, 4 800 B per context) for pcr_sc_distances: distanceBtnScanContext of an outside scan
+// against EVERY stored context, one wave per context (sc_rank_kernel), each sum in the host's order so that the result is the host's bit for bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -114,6 +116,124 @@ __global__ __launch_bounds__(256) void sc_polar_kernel(const float* __restrict__
     }
 }
 
+// The query's column norms (sqrt of the r = 0..19 sum of squares) and sector key (r = 0..19 sum, / 20), in the order pcr_sc_add and
+// sc_distance take them on the host.  keys[0, 60): norms, [60, 120): sector key.  One block of 64.
+__global__ __launch_bounds__(64) void sc_query_keys_kernel(const float* __restrict__ q /* [ring][sector], kNoPoint = empty */, double* __restrict__ keys) {
+    const int c = threadIdx.x;
+    if (c >= kSectors) return;
+    double nrm = 0, sum = 0;
+    for (int r = 0; r < kRings; ++r) {
+        const float v = q[r * kSectors + c];
+        const double x = v == kNoPoint ? 0.0 : (double)v;
+        nrm += x * x;
+        sum += x;
+    }
+    keys[c] = sqrt(nrm);
+    keys[kSectors + c] = sum / kRings;
+}
+
+constexpr int kRankWaves = 4;                        // contexts per block per step: one wave each
+constexpr int kShiftGroup = 8;                       // shifts whose 60 cosine terms are staged in LDS at once
+
+struct RankBest { double d; int s; };
+// (d, s) lexicographic minimum, NaN never winning: the strict '<' of distanceBtnScanContext over ascending shifts
+__device__ inline RankBest rank_min(RankBest a, RankBest b) { return (b.d < a.d || (b.d == a.d && b.s < a.s)) ? b : a; }
+__device__ inline RankBest wave_rank_min(RankBest v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        RankBest w;
+        w.d = __shfl_xor(v.d, o, 64);
+        w.s = __shfl_xor(v.s, o, 64);
+        v = rank_min(v, w);
+    }
+    return v;
+}
+
+// dist[i], shift[i] = distanceBtnScanContext(query, context i) as pcr_sc_distance(q, i) computes it on the host: the query unshifted, the
+// context shifted.  One wave per context (all waves of a block step together, so the block barriers are uniform):
+//   lanes 0..59: the context's column norms and sector key (sequential r = 0..19 sums);
+//   lanes 0..59: the fast-align norm of shift s (sequential c = 0..59 sum, sqrt), then a wave arg-min, the lowest shift winning ties;
+//   all lanes: the (shift, column) cosine terms of up to kShiftGroup shifts, each a sequential r = 0..19 dot, staged in LDS;
+//   one lane per shift: the sequential col = 0..59 sum with its count of non-empty column pairs, then 1 - sum / eff;
+//   the minimum over the shifts by (d, s) with NaN (eff = 0) excluded -- the host's strict '<' over ascending shifts.
+// A context against which no shift has a non-empty column pair gets (DBL_MAX, 0), as on the host.
+__global__ __launch_bounds__(256) void sc_rank_kernel(const float* __restrict__ db /* M x [ring][sector] */, unsigned int M,
+                                                      const float* __restrict__ q, const double* __restrict__ qkeys, int radius,
+                                                      double* __restrict__ dist, int* __restrict__ shift) {
+    __shared__ float s_q[kRings * kSectors];
+    __shared__ double s_qn[kSectors], s_qk[kSectors];
+    __shared__ float4 s_b4[kRankWaves][kRings * kSectors / 4];
+    __shared__ double s_bn[kRankWaves][kSectors], s_bk[kRankWaves][kSectors];
+    __shared__ double s_term[kRankWaves][kShiftGroup * kSectors];
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    for (int i = tid; i < kRings * kSectors; i += 256) { const float v = q[i]; s_q[i] = v == kNoPoint ? 0.f : v; }
+    if (tid < kSectors) { s_qn[tid] = qkeys[tid]; s_qk[tid] = qkeys[kSectors + tid]; }
+    const int n_shift = 2 * radius + 1 < kSectors ? 2 * radius + 1 : kSectors;
+    const float* s_b = reinterpret_cast<const float*>(s_b4[w]);
+    __syncthreads();
+    for (unsigned int base = blockIdx.x * kRankWaves; base < M; base += gridDim.x * kRankWaves) {
+        const unsigned int ctx = base + w;
+        const bool live = ctx < M;
+        // the context, empty bins (kNoPoint) as the host's 0.0
+        const float4* src4 = reinterpret_cast<const float4*>(db + (size_t)(live ? ctx : 0) * (kRings * kSectors));
+        for (int i = lane; i < kRings * kSectors / 4; i += 64) {
+            float4 v = live ? src4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            v.x = v.x == kNoPoint ? 0.f : v.x; v.y = v.y == kNoPoint ? 0.f : v.y;
+            v.z = v.z == kNoPoint ? 0.f : v.z; v.w = v.w == kNoPoint ? 0.f : v.w;
+            s_b4[w][i] = v;
+        }
+        __syncthreads();
+        if (lane < kSectors) {
+            double nrm = 0, sum = 0;
+            for (int r = 0; r < kRings; ++r) { const double x = (double)s_b[r * kSectors + lane]; nrm += x * x; sum += x; }
+            s_bn[w][lane] = sqrt(nrm);
+            s_bk[w][lane] = sum / kRings;
+        }
+        __syncthreads();
+        // fastAlignUsingVkey: shift s compares query key c with context key c - s
+        RankBest fa{__builtin_inf(), 1 << 30};
+        if (lane < kSectors) {
+            double s2 = 0;
+            for (int c = 0; c < kSectors; ++c) { const int k = c - lane < 0 ? c - lane + kSectors : c - lane; const double d = s_qk[c] - s_bk[w][k]; s2 += d * d; }
+            fa.d = sqrt(s2);
+            fa.s = lane;
+        }
+        const int a0 = wave_rank_min(fa).s;
+        // the shifts a0 - radius .. a0 + radius (mod 60; all 60 when that covers the circle): order does not matter to a (d, s) minimum
+        RankBest best{__builtin_inf(), 1 << 30};
+        for (int g0 = 0; g0 < n_shift; g0 += kShiftGroup) {
+            const int gn = n_shift - g0 < kShiftGroup ? n_shift - g0 : kShiftGroup;
+            for (int t = lane; t < gn * kSectors; t += 64) {
+                const int j = t / kSectors, col = t - j * kSectors;
+                const int s = n_shift == kSectors ? g0 + j : ((a0 - radius + g0 + j) % kSectors + kSectors) % kSectors;
+                const int sc = col - s < 0 ? col - s + kSectors : col - s;
+                double dot = 0;
+                for (int r = 0; r < kRings; ++r) dot += (double)s_q[r * kSectors + col] * (double)s_b[r * kSectors + sc];
+                const double na = s_qn[col], nb = s_bn[w][sc];
+                s_term[w][t] = (na == 0 || nb == 0) ? __builtin_nan("") : dot / (na * nb);      // (a term itself is always finite)
+            }
+            __syncthreads();
+            RankBest mine{__builtin_inf(), 1 << 30};
+            if (lane < gn) {
+                double sum = 0;
+                int eff = 0;
+                for (int col = 0; col < kSectors; ++col) {
+                    const double t = s_term[w][lane * kSectors + col];
+                    if (t == t) { sum = sum + t; eff = eff + 1; }
+                }
+                const double d = 1.0 - sum / eff;
+                if (d == d) { mine.d = d; mine.s = n_shift == kSectors ? g0 + lane : ((a0 - radius + g0 + lane) % kSectors + kSectors) % kSectors; }
+            }
+            best = rank_min(best, wave_rank_min(mine));
+            __syncthreads();
+        }
+        if (live && lane == 0) {
+            const bool any = best.d < __builtin_inf();
+            dist[ctx] = any ? best.d : 1.7976931348623157e308;      // DBL_MAX / 0: no shift had a non-empty column pair
+            shift[ctx] = any ? best.s : 0;
+        }
+    }
+}
+
 struct Desc { double m[kRings * kSectors]; };        // row-major [ring][sector]
 
 }  // namespace
@@ -126,8 +246,13 @@ struct pcr_sc {
     size_t tree_size = 0;                                // ring_sub_.size(): contexts visible to the candidate search
     float* d_desc = nullptr;
     float* d_stage = nullptr; size_t stage_cap = 0;
+    float* d_db = nullptr; size_t db_cap = 0;            // every context's descriptor as binned (kNoPoint = empty), [context][ring][sector]
+    float* d_query = nullptr; double* d_qkeys = nullptr; // pcr_sc_distances: the outside scan's descriptor and its column norms + sector key
+    double* d_dist = nullptr; int* d_shift = nullptr; size_t res_cap = 0;
     std::string err;
 };
+
+namespace pcr { int sc_device(const pcr_sc* sc) { return sc->device; } }      // (pcr_internal.h)
 
 static thread_local std::string g_sc_err;
 static int scfail(pcr_sc* s, const std::string& m) { if (s) s->err = m; else g_sc_err = m; return 1; }
@@ -197,8 +322,8 @@ pcr_sc* pcr_sc_create(int device, const pcr_sc_params* p) {
 void pcr_sc_destroy(pcr_sc* sc) {
     if (!sc) return;
     (void)hipSetDevice(sc->device);
-    if (sc->d_desc) (void)hipFree(sc->d_desc);
-    if (sc->d_stage) (void)hipFree(sc->d_stage);
+    for (void* p : {(void*)sc->d_desc, (void*)sc->d_stage, (void*)sc->d_db, (void*)sc->d_query, (void*)sc->d_qkeys, (void*)sc->d_dist, (void*)sc->d_shift})
+        if (p) (void)hipFree(p);
     delete sc;
 }
 
@@ -206,10 +331,12 @@ const char* pcr_sc_last_error(const pcr_sc* sc) { return sc ? sc->err.c_str() : 
 
 int pcr_sc_size(const pcr_sc* sc, size_t* n) { if (!sc || !n) return 1; *n = sc->polar.size(); return 0; }
 
-/* addContext (:56-66): descriptor of a (down-sampled) scan in the lidar frame + its ring and sector keys */
-int pcr_sc_add(pcr_sc* sc, const void* pts, size_t n, size_t stride_bytes, int on_device) {
-    if (!sc) return 1;
-    sc->err.clear();
+}  // extern "C"
+
+namespace {
+
+// The argument checks of pcr_sc_add / pcr_sc_distances, then the polar binning of the cloud into `desc` (1200 floats, preset to kNoPoint).
+int sc_bin_cloud(pcr_sc* sc, const void* pts, size_t n, size_t stride_bytes, int on_device, float* desc) {
     if (n && !pts) return scfail(sc, "NULL cloud with nonzero size");
     if (stride_bytes < 12 || stride_bytes % 4) return scfail(sc, "stride_bytes must be a multiple of 4 and >= 12");
     if (n > 0xfffffff0ull) return scfail(sc, "cloud too large");
@@ -228,13 +355,48 @@ int pcr_sc_add(pcr_sc* sc, const void* pts, size_t n, size_t stride_bytes, int o
     }
     float init[kRings * kSectors];
     for (float& v : init) v = kNoPoint;
-    S_TRY(hipMemcpy(sc->d_desc, init, sizeof init, hipMemcpyHostToDevice));
+    S_TRY(hipMemcpy(desc, init, sizeof init, hipMemcpyHostToDevice));
     if (n) {
         const int blocks = (int)std::min<size_t>(1024, (n + 255) / 256);
         hipLaunchKernelGGL(sc_polar_kernel, dim3(blocks), dim3(256), 0, 0, d_pts, (unsigned int)n, (unsigned int)(stride_bytes / 4),
-                           (float)sc->prm.lidar_height, sc->d_desc);
+                           (float)sc->prm.lidar_height, desc);
         S_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+// Room in the device store for one more context: the store doubles (at least 64 contexts); a failed growth leaves it as it was.
+int sc_reserve_one(pcr_sc* sc) {
+    const size_t n = sc->polar.size();
+    if (n < sc->db_cap) return 0;
+    const size_t cap = std::max<size_t>(64, 2 * sc->db_cap);
+    const size_t per = (size_t)kRings * kSectors * sizeof(float);
+    float* p = nullptr;
+    const hipError_t e = hipMalloc((void**)&p, cap * per);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return scfail(sc, "the device store of " + std::to_string(n) + " contexts cannot grow to " + std::to_string(cap) + ": " + hipGetErrorString(e));
+    }
+    if (n) {
+        const hipError_t c = hipMemcpy(p, sc->d_db, n * per, hipMemcpyDeviceToDevice);
+        if (c != hipSuccess) { (void)hipFree(p); return scfail(sc, std::string("growing the device store: ") + hipGetErrorString(c)); }
+    }
+    if (sc->d_db) (void)hipFree(sc->d_db);
+    sc->d_db = p; sc->db_cap = cap;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* addContext (:56-66): descriptor of a (down-sampled) scan in the lidar frame + its ring and sector keys */
+int pcr_sc_add(pcr_sc* sc, const void* pts, size_t n, size_t stride_bytes, int on_device) {
+    if (!sc) return 1;
+    sc->err.clear();
+    if (sc_bin_cloud(sc, pts, n, stride_bytes, on_device, sc->d_desc)) return 1;
+    if (sc_reserve_one(sc)) return 1;
+    S_TRY(hipMemcpy(sc->d_db + sc->polar.size() * (kRings * kSectors), sc->d_desc, kRings * kSectors * sizeof(float), hipMemcpyDeviceToDevice));
     float host[kRings * kSectors];
     S_TRY(hipMemcpy(host, sc->d_desc, sizeof host, hipMemcpyDeviceToHost));
     Desc d;
@@ -270,6 +432,40 @@ int pcr_sc_distance(const pcr_sc* sc, size_t id1, size_t id2, double* dist, int*
     }
     if (dist) *dist = best;
     if (shift) *shift = arg;
+    return 0;
+}
+
+/* distanceBtnScanContext of an outside scan against every stored context, on the device (sc_rank_kernel) */
+int pcr_sc_distances(pcr_sc* sc, const void* pts, size_t n, size_t stride_bytes, int on_device, double* dist, int32_t* shift) {
+    if (!sc) return 1;
+    sc->err.clear();
+    const size_t M = sc->polar.size();
+    if (M && (!dist || !shift)) return scfail(sc, "dist or shift is NULL");
+    if (M > 0xffffffffull - kRankWaves) return scfail(sc, "too many contexts");
+    S_TRY(hipSetDevice(sc->device));
+    if (!sc->d_query) {
+        S_TRY(hipMalloc((void**)&sc->d_query, kRings * kSectors * sizeof(float)));
+        S_TRY(hipMalloc((void**)&sc->d_qkeys, 2 * kSectors * sizeof(double)));
+    }
+    if (sc_bin_cloud(sc, pts, n, stride_bytes, on_device, sc->d_query)) return 1;
+    if (M == 0) return 0;
+    if (M > sc->res_cap) {
+        if (sc->d_dist) (void)hipFree(sc->d_dist);
+        if (sc->d_shift) (void)hipFree(sc->d_shift);
+        sc->d_dist = nullptr; sc->d_shift = nullptr; sc->res_cap = 0;
+        S_TRY(hipMalloc((void**)&sc->d_dist, sc->db_cap * sizeof(double)));
+        S_TRY(hipMalloc((void**)&sc->d_shift, sc->db_cap * sizeof(int)));
+        sc->res_cap = sc->db_cap;
+    }
+    const int radius = std::max(0, (int)round(0.5 * (double)(float)sc->prm.search_ratio * kSectors));      // as pcr_sc_distance
+    hipLaunchKernelGGL(sc_query_keys_kernel, dim3(1), dim3(64), 0, 0, sc->d_query, sc->d_qkeys);
+    S_TRY(hipGetLastError());
+    const unsigned int blocks = (unsigned int)std::min<size_t>((M + kRankWaves - 1) / kRankWaves, 8192);
+    hipLaunchKernelGGL(sc_rank_kernel, dim3(blocks), dim3(256), 0, 0, sc->d_db, (unsigned int)M, sc->d_query, sc->d_qkeys, std::min(radius, kSectors),
+                       sc->d_dist, sc->d_shift);
+    S_TRY(hipGetLastError());
+    S_TRY(hipMemcpy(dist, sc->d_dist, M * sizeof(double), hipMemcpyDeviceToHost));
+    S_TRY(hipMemcpy(shift, sc->d_shift, M * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -17,6 +17,8 @@
 #include "../../../include/pcr_hip.h"
 #include "../config/params.hpp"
 
+namespace context { class ScanContext; }
+
 namespace PCR {
 
 using scalar_t = double;                       // common/types/basic.hpp:16
@@ -125,6 +127,12 @@ public:
         isConverge = conv != 0;
         return isConverge;
     }
+    // Global relocalisation (pcr_relocalize_global) against the target set by setTarget -- the whole map: no pose at all, at start-up or
+    // when tracking is lost.  sc holds one ScanContext per key frame, kf_poses their poses.  `res` becomes the chosen candidate's refined
+    // pose; p = nullptr: pcr_global_reloc_default_params.  Fails like align: logs, returns false and leaves `res` alone.
+    inline bool relocalizeGlobal(const PC_cPtr& src, const context::ScanContext& sc, const std::vector<pose_t>& kf_poses, pose_t& res,
+                                 const pcr_global_reloc_params* p = nullptr, std::vector<pcr_global_reloc_candidate>* cands = nullptr,
+                                 size_t* chosen = nullptr);
     pcr_handle* handle() { return h_; }
     // getFitnessScore of the reference's test/align.cpp:29-61: mean squared 1-NN distance (<= max_sq) of the source under `pose`
     // against the target of the last registration; -1 when no point is that close
@@ -257,6 +265,18 @@ public:
         lastError_ = reg_->lastError();
         return isConverge;
     }
+    // global relocalisation against the static map: `dst` indexed at the first call, as scan2Map does
+    bool relocalizeGlobal(const PC_cPtr& src, const PC_cPtr& dst, const context::ScanContext& sc, const std::vector<pose_t>& kf_poses, pose_t& res,
+                          const pcr_global_reloc_params* p = nullptr, std::vector<pcr_global_reloc_candidate>* cands = nullptr,
+                          size_t* chosen = nullptr) {
+        if (!have_target_) {
+            try { reg_->setTarget(dst); } catch (const std::exception& e) { logError(e.what()); return isConverge = false; }
+            have_target_ = true;
+        }
+        isConverge = reg_->relocalizeGlobal(src, sc, kf_poses, res, p, cands, chosen);
+        lastError_ = reg_->lastError();
+        return isConverge;
+    }
     scalar_t getFitnessScore() override { return reg_->getFitnessScore(); }
     HipRegister& inner() { return *reg_; }
 };
@@ -295,8 +315,43 @@ public:
         return {(int)match, yaw};
     }
     size_t size() const { size_t n = 0; pcr_sc_size(s_, &n); return n; }
+    // distanceBtnScanContext of an outside scan (not added) against every stored context, on the device: what distance(q, i) would be
+    // had the scan been added as context q
+    void distances(const PCR::PointCloud& scan_down, std::vector<double>& dist, std::vector<int32_t>& shift) const {
+        dist.assign(size(), 0.0);
+        shift.assign(dist.size(), 0);
+        if (pcr_sc_distances(s_, scan_down.points.data(), scan_down.size(), sizeof(PCR::PointXYZI), 0, dist.data(), shift.data()))
+            throw std::runtime_error(pcr_sc_last_error(s_));
+    }
+    pcr_sc* handle() const { return s_; }
 };
 }  // namespace context
+
+namespace PCR {
+inline bool HipRegister::relocalizeGlobal(const PC_cPtr& src, const context::ScanContext& sc, const std::vector<pose_t>& kf_poses, pose_t& res,
+                                          const pcr_global_reloc_params* p, std::vector<pcr_global_reloc_candidate>* cands, size_t* chosen) {
+    static_assert(sizeof(pose_t) == 16 * sizeof(double), "key-frame poses are handed over as 16 doubles each");
+    pcr_global_reloc_params dp;
+    pcr_global_reloc_default_params(&dp);
+    if (!p) p = &dp;
+    std::vector<pcr_global_reloc_candidate> c((size_t)(p->places > 0 ? p->places : 0) * (size_t)(p->local.refine_top > 0 ? p->local.refine_top : 0) + 1);
+    size_t nc = 0, ch = 0;
+    int conv = 0;
+    pose_t out = res;
+    if (pcr_relocalize_global(h_, sc.handle(), kf_poses.empty() ? nullptr : kf_poses.front().data(), kf_poses.size(), src->points.data(), src->size(),
+                              sizeof(PointXYZI), 0, p, out.data(), &conv, c.data(), c.size(), &nc, &ch)) {
+        logError(pcr_last_error(h_));
+        return isConverge = false;
+    }
+    lastError_.clear();
+    res = out;
+    c.resize(nc);
+    if (cands) *cands = c;
+    if (chosen) *chosen = ch;
+    isConverge = conv != 0;
+    return isConverge;
+}
+}  // namespace PCR
 
 // common/pcp/pcp.hpp:14-28 (pcl::VoxelGrid with leaf = grid_size on all axes), on the device
 namespace pcp {

@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "pcr_vgicp_opt_create", "pcr_vgicp_opt_destroy", "pcr_vgicp_opt_request", "pcr_vgicp_opt_feed", "pcr_vgicp_opt_result",
     "pcr_sc_default_params", "pcr_sc_create", "pcr_sc_destroy", "pcr_sc_last_error", "pcr_sc_size", "pcr_sc_add", "pcr_sc_descriptor", "pcr_sc_distance",
     "pcr_sc_query", "pcr_fitness_batch", "pcr_reloc_default_params", "pcr_reloc_hypotheses", "pcr_relocalize",
+    "pcr_sc_distances", "pcr_global_reloc_default_params", "pcr_global_reloc_hypotheses", "pcr_relocalize_global",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -86,6 +87,16 @@ class RelocCandidate(C.Structure):
     """struct pcr_reloc_candidate (include/pcr_hip.h)."""
     _fields_ = [("hypothesis", C.c_int64), ("coarse_n_in", C.c_int64), ("coarse_score", C.c_double), ("pose", C.c_double * 16),
                 ("converged", C.c_int32), ("pad_", C.c_int32), ("n_in", C.c_int64), ("score", C.c_double)]
+
+
+class GlobalRelocParams(C.Structure):
+    """struct pcr_global_reloc_params (include/pcr_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("places", C.c_int32), ("max_dist", C.c_double), ("local", RelocParams)]
+
+
+class GlobalRelocCandidate(C.Structure):
+    """struct pcr_global_reloc_candidate (include/pcr_hip.h)."""
+    _fields_ = [("place", C.c_int64), ("sc_dist", C.c_double), ("sc_shift", C.c_int32), ("pad_", C.c_int32), ("c", RelocCandidate)]
 
 
 _lib = None
@@ -203,6 +214,12 @@ def load_library():
     L.pcr_reloc_hypotheses.argtypes = [dp, C.POINTER(RelocParams), dp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.pcr_relocalize.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(RelocParams), dp, ip, C.POINTER(RelocCandidate), C.c_size_t,
                                  C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.pcr_sc_distances.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, C.POINTER(C.c_int32)]
+    L.pcr_global_reloc_default_params.argtypes = [C.POINTER(GlobalRelocParams)]
+    L.pcr_global_reloc_default_params.restype = None
+    L.pcr_global_reloc_hypotheses.argtypes = [dp, C.c_int32, C.POINTER(RelocParams), dp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pcr_relocalize_global.argtypes = [vp, vp, dp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(GlobalRelocParams), dp, ip,
+                                        C.POINTER(GlobalRelocCandidate), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -246,6 +263,48 @@ def reloc_hypotheses(coarse, **params):
     if L.pcr_reloc_hypotheses(c.ctypes.data_as(dp), C.byref(p), out.ctypes.data_as(dp), K.value, C.byref(K)) != 0:
         raise PcrError(L.pcr_last_error(None).decode())
     return out.reshape(-1, 4, 4).transpose(0, 2, 1).copy()
+
+
+_LOCAL_FIELDS = ("xy_range", "xy_step", "yaw_range", "yaw_step", "max_sq", "refine_top", "score_points")
+
+
+def global_reloc_params(**overrides):
+    """pcr_global_reloc_default_params with fields overridden: places, max_dist, and the fields of the per-place lattice (pcr_reloc_params:
+    xy_range, xy_step, yaw_range, yaw_step in radians, max_sq, refine_top, score_points)."""
+    p = GlobalRelocParams()
+    load_library().pcr_global_reloc_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if k in ("places", "max_dist"):
+            setattr(p, k, v)
+        elif k in _LOCAL_FIELDS:
+            setattr(p.local, k, v)
+        else:
+            raise AttributeError(f"pcr_global_reloc_params has no field {k!r}")
+    return p
+
+
+def global_reloc_hypotheses(kf_pose, shift, **local):
+    """pcr_global_reloc_hypotheses: the (K, 4, 4) lattice around the coarse pose of a place, kf_pose * Rz(-yaw) with yaw the float
+    deg2rad(6 * shift) of pcr_sc_query.  local: fields of the per-place lattice (default: global_reloc_params().local)."""
+    L = load_library()
+    p = global_reloc_params(**local).local
+    c = _pose_in(kf_pose)
+    if isinstance(shift, (bool, float)) or not isinstance(shift, (int, np.integer)):
+        raise TypeError(f"shift must be an integer, not {type(shift).__name__}")
+    dp = C.POINTER(C.c_double)
+    K = C.c_size_t(0)
+    rc = L.pcr_global_reloc_hypotheses(c.ctypes.data_as(dp), int(shift), C.byref(p), None, 0, C.byref(K))
+    if rc != 0 and K.value == 0:
+        raise PcrError(L.pcr_last_error(None).decode())
+    out = np.zeros((K.value, 16))
+    if L.pcr_global_reloc_hypotheses(c.ctypes.data_as(dp), int(shift), C.byref(p), out.ctypes.data_as(dp), K.value, C.byref(K)) != 0:
+        raise PcrError(L.pcr_last_error(None).decode())
+    return out.reshape(-1, 4, 4).transpose(0, 2, 1).copy()
+
+
+def _cand_dict(c):
+    return dict(hypothesis=c.hypothesis, coarse_n_in=c.coarse_n_in, coarse_score=c.coarse_score, pose=_pose_out(np.array(c.pose[:])),
+                converged=bool(c.converged), n_in=c.n_in, score=c.score)
 
 
 def _cloud(x):
@@ -512,8 +571,39 @@ class PointCloudRegister:
         self._check(self._lib.pcr_relocalize(self._h, p, n, s, dev, C.byref(rp), pc.ctypes.data_as(C.POINTER(C.c_double)), C.byref(conv),
                                              cands, cap, C.byref(nc), C.byref(ch)))
         pose_np[...] = _pose_out(pc)
-        out = [dict(hypothesis=c.hypothesis, coarse_n_in=c.coarse_n_in, coarse_score=c.coarse_score, pose=_pose_out(np.array(c.pose[:])),
-                    converged=bool(c.converged), n_in=c.n_in, score=c.score) for c in cands[:nc.value]]
+        out = [_cand_dict(c) for c in cands[:nc.value]]
+        self.isConverge = bool(conv.value)
+        return self.isConverge, out, int(ch.value)
+
+    def relocalizeGlobal(self, src, sc, kf_poses, pose, **params):
+        """pcr_relocalize_global: relocalise with no prior against the kept target (setTarget: the whole map).  sc: the ScanContext
+        database with one context per key frame, kf_poses: their (M, 4, 4) poses; `pose` (4x4) receives the chosen pose in place.
+        -> (converged, candidates, chosen).  candidates: one dict per refined hypothesis (place, sc_dist, sc_shift and relocalize's
+        fields; hypothesis numbers the pose within its place's lattice).  params: fields of pcr_global_reloc_params (global_reloc_params)."""
+        if not isinstance(sc, ScanContext):
+            raise TypeError("sc must be a ScanContext")
+        p, n, s, dev, _k = _cloud(src)
+        gp = global_reloc_params(**params)
+        pose_np = np.asarray(pose)
+        if pose_np.shape != (4, 4) or pose_np.dtype != np.float64:
+            raise ValueError("pose must be a float64 4x4 array (written in place)")
+        kf = np.asarray(kf_poses, np.float64)
+        if kf.ndim != 3 or kf.shape[1:] != (4, 4):
+            raise ValueError("kf_poses must have shape (M, 4, 4)")
+        kf_cm = np.ascontiguousarray(kf.transpose(0, 2, 1)).reshape(-1)      # column-major per pose
+        cap = max(gp.places, 0) * max(gp.local.refine_top, 0)
+        cands = (GlobalRelocCandidate * max(cap, 1))()
+        out_pose = np.zeros(16)
+        conv, nc, ch = C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+        dp = C.POINTER(C.c_double)
+        self._check(self._lib.pcr_relocalize_global(self._h, sc._s, kf_cm.ctypes.data_as(dp), kf.shape[0], p, n, s, dev, C.byref(gp),
+                                                    out_pose.ctypes.data_as(dp), C.byref(conv), cands, cap, C.byref(nc), C.byref(ch)))
+        pose_np[...] = _pose_out(out_pose)
+        out = []
+        for g in cands[:nc.value]:
+            d = dict(place=int(g.place), sc_dist=g.sc_dist, sc_shift=int(g.sc_shift))
+            d.update(_cand_dict(g.c))
+            out.append(d)
         self.isConverge = bool(conv.value)
         return self.isConverge, out, int(ch.value)
 
@@ -816,6 +906,16 @@ class ScanContext:
         d, sh = C.c_double(0), C.c_int(0)
         self._check(self._lib.pcr_sc_distance(self._s, int(i), int(j), C.byref(d), C.byref(sh)))
         return d.value, sh.value
+
+    def distances(self, cloud):
+        """distanceBtnScanContext of `cloud` (lidar frame; not added) against every stored context, on the device
+        -> (dist float64[M], shift int32[M]): entry i is distance(q, i) had the cloud been added as context q."""
+        p, n, s, dev, _keep = _cloud(cloud)
+        m = len(self)
+        dist, shift = np.zeros(m, np.float64), np.zeros(m, np.int32)
+        self._check(self._lib.pcr_sc_distances(self._s, p, n, s, dev, dist.ctypes.data_as(C.POINTER(C.c_double)),
+                                               shift.ctypes.data_as(C.POINTER(C.c_int32))))
+        return dist, shift
 
     def query(self, i):
         """-> (match or -1, yaw as float32, best candidate distance or None when the search did not run)"""
