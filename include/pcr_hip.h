@@ -69,8 +69,7 @@ typedef struct pcr_params {
     int32_t record_trace;      /* 1: keep per-iteration normal equations for pcr_get_trace */
 
     /* ---- switches (all 0 by default; none of them changes a result except where noted).  The library reads NO environment
-     * variable: what used to be PCR_* variables and pcr_params.reserved[] are these fields, or exist only in a development build
-     * (make DEV=1, csrc/pcr_internal.h: dev_env). ---- */
+     * variable: what used to be PCR_* variables and pcr_params.reserved[] are these fields, or were removed. ---- */
     int32_t index_no_hints;    /* 1: every target index is built from scratch -- fresh bounding box, no tile layout taken over from the
                                 *    previous build of this handle (three build launches instead of two; no state crosses calls) */
     int32_t ndt_evaluate_repeats; /* 1: NDT: every request of the line search becomes an evaluation pass, also one at the point just

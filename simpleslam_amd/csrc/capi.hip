@@ -58,10 +58,6 @@ std::mutex g_rccl_mu;
 
 }  // namespace
 
-#ifdef PCR_DEV_SWITCHES
-namespace pcr { int dev_stamps(unsigned long long* out, size_t count); }
-#endif
-
 struct pcr_handle {
     Method method = kLoam;
     pcr_params prm;
@@ -131,7 +127,6 @@ struct pcr_handle {
     DeviceBuf nd_ctl;                    // NdtCtl: the device-resident optimiser's state
     struct VfJob { const float* d_pts; size_t n, sf; double leaf; float* d_out; size_t cap; } vf_job = {};      // the filter that is queued (vf_enqueue / vf_settle)
     bool vf_inflight = false; size_t vf_inflight_n = 0;      // pcr_voxel_filter_begin has queued a filter that pcr_voxel_filter_end has not collected
-    unsigned long long vf_builds = 0, vf_stale = 0;      // index builds of the voxel filter, and how many found the reused box / layout too small
     char* vf_ret = nullptr;              // page-locked: what the voxel filter's last block reports (VfResult: the voxel count + the index header's verdict)
     DeviceBuf vg_reduced;                // sharded VGICP over the peer exchange: a pass's 32 sums folded over the rows and the ranks
     DeviceBuf nd_sums;                   // sharded device loop: the 48 sums of a pass, all-reduced in place
@@ -332,7 +327,6 @@ void fill_loam_args(pcr_handle* h, LoamArgs* a, const float* d_src, size_t n_src
     h->last_blocks = a->n_partials;
     a->trace = h->prm.record_trace ? h->loam_trace.as<LoamTrace>() : nullptr;
     a->result = h->result_dev;
-    a->ablate = dev_env("PCR_ABLATE") ? atoi(dev_env("PCR_ABLATE")) : 0;      // (only a -DPCR_ABLATION development build looks at it)
     a->coresident = h->prm.loam_coresident == 1;
     if (h->prm.loam_disable_cache == 0 && h->nn_cache.reserve((n_src + 1) * 192) == hipSuccess) a->nn_cache = (NnCacheEntry*)h->nn_cache.p;
     if (h->prm.record_timeline == 1 && h->timeline.reserve((size_t)(std::max(1, h->prm.loam_iters) + 1) * kMaxPartials * kTimelineSlots * sizeof(unsigned long long)) == hipSuccess)
@@ -517,7 +511,7 @@ int run_loam(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floa
             }
             ++launched;
             if (per_kernel) H_TRY(loam_launch_iteration(a, k, h->stream, h->ev_kernel[2 * k], h->ev_kernel[2 * k + 1]));
-            else H_TRY(loam_launch_iteration(a, k, h->stream, nullptr, nullptr, !shard));
+            else H_TRY(loam_launch_iteration(a, k, h->stream));
             if (h->host_ar) {
                 // the caller's collective: sums to the host, through fn, back (one host round trip per linearisation)
                 H_TRY(loam_launch_reduce(a, k, h->red_dev, h->stream));
@@ -709,11 +703,8 @@ int settle_grid(pcr_handle* h, GridIndex& g, const float* d_pts, size_t n, size_
 // beat the three levels four apart (0.5 / 2 / 8 m) this started with: the 8 m grid of a scan has a handful of cells holding most
 // of its points -- three blocks sorted the whole scan, 120 us -- and each level is an index build on the side stream; A/B of the
 // whole scan2map on one box: 3 x 4: 0.906 ms, 2 x 4: 0.917, 2 x 5: 0.890, 2 x 6: 0.875, 2 x 7: 0.900, 2 x 8: 0.880, 3 x 6: 0.975, 2 x 12: 1.25.
-// (PCR_COV_LEVELS / PCR_COV_RATIO override for such runs.)
-static int cov_levels_small() { static const int v = dev_env("PCR_COV_LEVELS") ? atoi(dev_env("PCR_COV_LEVELS")) : 2; return v < 1 ? 1 : (v > 3 ? 3 : v); }
-static double src_cell0() { static const double v = dev_env("PCR_COV_CELL0") ? atof(dev_env("PCR_COV_CELL0")) : 1.0; return v > 0 ? v : 1.0; }      // (development: cell of a scan's own search levels, in voxels)
-static double cov_ratio() { static const double v = dev_env("PCR_COV_RATIO") ? atof(dev_env("PCR_COV_RATIO")) : 6.0; return v; }
-int cov_levels(size_t n) { return n <= 300000 ? cov_levels_small() : 1; }
+static constexpr double kCovRatio = 6.0;      // cell of a level / cell of the level below
+int cov_levels(size_t n) { return n <= 300000 ? 2 : 1; }
 
 int vgicp_source_enqueue(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, bool marked = false, std::string* errp = nullptr);
 int vgicp_side_init(pcr_handle* h) {
@@ -754,7 +745,7 @@ int settle_cov_levels(pcr_handle* h, GridIndex& g, GridIndex& l1, GridIndex& l2,
     // pcr_vgicp_covariances, the redo path): built like vgicp_source_enqueue builds them -- one-level path, no hints: one scan's box and tile
     // layout do not hold the next (walls at other distances; measured there: every hint failed and the redo cost 0.9 ms)
     GridIndex* lv[3] = {&g, &l1, &l2};
-    const double cells[3] = {cell, cov_ratio() * cell, cov_ratio() * cov_ratio() * cell};
+    const double cells[3] = {cell, kCovRatio * cell, kCovRatio * kCovRatio * cell};
     const int levels = cov_levels(n);
     bool todo[3] = {true, levels > 1, levels > 2};
     if (after_clean) *after_clean = false;
@@ -769,8 +760,7 @@ int settle_cov_levels(pcr_handle* h, GridIndex& g, GridIndex& l1, GridIndex& l2,
         const bool ahead = ahead_cell > 0.0 && levels == 1 && attempt == 0 && !(h->clamp.use && may_cut);
         // ... on a stream of its own when the caller queues its work behind both (after_ahead): the two builds read the same cloud and
         // depend on nothing of each other, and neither fills the device (a chain of two or three launches of a few hundred blocks)
-        static const bool no_aux = dev_env("PCR_COV_NO_AUX") != nullptr;      // (A/B runs)
-        const bool aux = ahead && after_ahead != nullptr && h->aux_stream != nullptr && !no_aux;
+        const bool aux = ahead && after_ahead != nullptr && h->aux_stream != nullptr;
         auto build_ahead = [&](hipStream_t s) -> int {
             l1.no_hints = h->prm.index_no_hints != 0;
             if (l1.build(d_pts, n, stride_floats, ahead_cell, s, &h->err, 0.0, 0, nullptr, true) != hipSuccess) return 1;
@@ -857,7 +847,7 @@ int vgicp_source_enqueue(pcr_handle* h, const float* d_src, size_t n_src, size_t
     S_TRY(hipStreamWaitEvent(h->side_stream, h->ev_side_in, 0));
 #undef S_TRY
     GridIndex* lv[3] = {&h->src_grid, &h->src_l1, &h->src_l2};
-    const double cell = h->prm.vgicp_resolution, cells[3] = {cell, cov_ratio() * cell, cov_ratio() * cov_ratio() * cell};
+    const double cell = h->prm.vgicp_resolution, cells[3] = {cell, kCovRatio * cell, kCovRatio * kCovRatio * cell};
     const int levels = cov_levels(n_src);
     // from here on kernels reading the caller's d_src may be queued on the side stream: an error must not return before they
     // have drained (the caller is free to release d_src as soon as the call has failed)
@@ -868,13 +858,13 @@ int vgicp_source_enqueue(pcr_handle* h, const float* d_src, size_t n_src, size_t
         // (a scan's points crowd around the sensor: on the coarse level a few cells hold a third of the scan, and the tiled build leaves
         //  them to ONE block, 94-146 us in the trace; on the fine level the crowded tiles still cost 34 us where the one-level build
         //  -- histogram with ranks, scan of the table, scatter -- takes ~30 us for the whole level.  A/B: 0.571 -> 0.54 ms per scan)
-        lv[l]->prefer_one_level = dev_env("PCR_COV_SCAN_TILED") == nullptr;
+        lv[l]->prefer_one_level = true;
         // (one pass over the scan finds the box of both levels, and the headers go to the host from the kernel that makes them: a build
         //  without hints changes nothing in its header afterwards)
         lv[l]->header_mirror = &h->side_hdr[l];
         lv[l]->twin = (l == 0 && levels > 1) ? lv[1] : nullptr;
-        lv[l]->twin_cell = src_cell0() * cells[1];
-        e = lv[l]->build(d_src, n_src, stride_floats, src_cell0() * cells[l], h->side_stream, &err, 0.0);
+        lv[l]->twin_cell = cells[1];
+        e = lv[l]->build(d_src, n_src, stride_floats, cells[l], h->side_stream, &err, 0.0);
         lv[l]->twin = nullptr;
         if (e == hipSuccess && !lv[l]->mirrored && (e = hipMemcpyAsync(&h->side_hdr[l], lv[l]->header.p, sizeof(GridHeader), hipMemcpyDeviceToHost, h->side_stream)) != hipSuccess)
             err = std::string("hipMemcpyAsync(side header): ") + hipGetErrorString(e);
@@ -883,7 +873,7 @@ int vgicp_source_enqueue(pcr_handle* h, const float* d_src, size_t n_src, size_t
                                                  h->src_cov6.as<double>(), h->side_stream, nullptr, nullptr, &h->src_scratch,
                                                  (h->profile >= 2 && h->ev_cov[2] && n_src > 0 && n_src <= 300000) ? h->ev_cov + 2 : nullptr)) != hipSuccess)
         err = std::string("vgicp_launch_cov: ") + hipGetErrorString(e);
-    if (e == hipSuccess && h->profile >= 2 && h->ev_cov[2] && n_src > 0 && n_src <= 300000 && dev_env("PCR_COV_OLD") == nullptr) h->ev_cov_src_used = true;      // (the development switch takes the old kernel, which records none of the three event pairs)
+    if (e == hipSuccess && h->profile >= 2 && h->ev_cov[2] && n_src > 0 && n_src <= 300000) h->ev_cov_src_used = true;
     h->fit_copied_from = nullptr;
     if (e == hipSuccess && !sharded(h) && n_src > 0) {      // the scan, kept for a later pcr_fitness() (off the critical path here)
         const size_t bytes = n_src * stride_floats * sizeof(float);
@@ -981,10 +971,8 @@ int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t
     if (h->prm.vgicp_k_corr != 20) return fail(h, "this build supports vgicp_k_corr = 20 (the reference's value) only");
     if (!keep_clamp) h->clamp.use = 0;
     h->tgt_ptr = d_dst; h->tgt_n = n_dst; h->tgt_stride = stride_floats;
-    static const bool no_ahead = dev_env("PCR_COV_NO_AHEAD") != nullptr;      // (A/B runs)
-    static const bool no_early = dev_env("PCR_COV_NO_EARLY") != nullptr;
     bool ahead_ok = false;
-    const double ahead_cell = (!no_ahead && cov_levels(n_dst) == 1 && h->cov_scale_hint >= 1.3) ? res * h->cov_scale_hint : 0.0;
+    const double ahead_cell = (cov_levels(n_dst) == 1 && h->cov_scale_hint >= 1.3) ? res * h->cov_scale_hint : 0.0;
     CovCheck chk;
     const bool check = h->use_tile && h->have_halo;
     // prepared for one scan: covariances and voxels only where that scan can land (a cut index keeps the full preparation: its
@@ -999,7 +987,6 @@ int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t
     // the voxel kernel; A/B on one box, round 5: preparation 0.372 -> 0.344 ms).  Needs the covariance search on a grid of its own (the grid built
     // ahead: it holds every point, and serves the fitness score), the previous full build's header and tile layout as hints (build() checks), and
     // lookups that test the mask first (vgicp.hip: vgicp_lookup, RoiView::filtered).
-    static const bool no_filter = dev_env("PCR_VG_NO_FILTER") != nullptr;      // (A/B runs)
     BuildFilter bf;
     bf.enqueue_mask = [&]() -> hipError_t {
         if (roi_enqueue(h, *roi_scan, res, 1.0, &roi)) return hipErrorUnknown;      // 1 m of translation + 0.05 rad
@@ -1026,10 +1013,10 @@ int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t
     H_TRY(h->vox.reserve((n_dst + 1) * sizeof(VgicpVoxel)));
     const std::function<int()> early = [&]() -> int { return enqueue_rest(&h->cov_l1); };
     bool early_clean = false;
-    const bool try_early = want_roi && !no_early && ahead_cell > 0.0 && !h->clamp.use;
+    const bool try_early = want_roi && ahead_cell > 0.0 && !h->clamp.use;
     // (may_cut: a cloud too spread out for dense tables -- a stray point kilometres off -- is indexed over its bulk.  A rank of a sharded call
     //  too: its cloud is its own, the cut is its own decision, and a scan that reaches the cut fails the call on EVERY rank, run_vgicp)
-    const bool try_filter = try_early && !no_filter && h->prm.index_no_hints == 0;
+    const bool try_filter = try_early && h->prm.index_no_hints == 0;
     if (settle_cov_levels(h, h->grid, h->cov_l1, h->cov_l2, d_dst, n_dst, stride_floats, res, 0.5, &h->cov_hdr0, true, ahead_cell, &ahead_ok,
                           try_early ? &early : nullptr, &early_clean, before_wait, false, try_filter ? &bf : nullptr)) return 1;
     if (h->clamp.use) { ahead_ok = false; early_clean = false; }      // (the target was cut to its bulk in there: the grid built ahead covers the uncut cloud)
@@ -1321,7 +1308,6 @@ int ndt_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t s
     RoiView roi;
     memset(&roi, 0, sizeof roi);
     const bool want_roi = roi_scan && roi_scan->n_src > 0 && n_dst > 0;
-    static const bool no_filter = dev_env("PCR_NDT_NO_FILTER") != nullptr;      // (A/B runs)
     BuildFilter bf;
     bf.enqueue_mask = [&]() -> hipError_t {
         if (roi_enqueue(h, *roi_scan, res, 1.0 + res, &roi)) return hipErrorUnknown;      // 1 m of translation + the DIRECT7 face voxels, + 0.05 rad
@@ -1350,7 +1336,7 @@ int ndt_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t s
         bf.tail.min_points = min_points; bf.tail.capacity = (uint32_t)std::min<size_t>(max_vox, 0xffffffffu);
         const size_t cap_before = h->grid.cell_capacity;
         const void* const slot_before = h->nd_slot.p;
-        if (h->grid.build(d_dst, n_dst, stride_floats, res, h->stream, &h->err, 0.0, 1, nullptr, true, want_roi && !no_filter ? &bf : nullptr) != hipSuccess) return 1;
+        if (h->grid.build(d_dst, n_dst, stride_floats, res, h->stream, &h->err, 0.0, 1, nullptr, true, want_roi ? &bf : nullptr) != hipSuccess) return 1;
         // (the tile pass has been handed vox_slot and the list BEFORE the build: nothing in build() may move them -- it never grows the cell table, only
         //  callers do -- but a change that broke that would write through a freed pointer: refuse loudly instead)
         if (bf.tail_applied && (h->grid.cell_capacity != cap_before || h->nd_slot.p != slot_before))
@@ -1556,9 +1542,7 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
         if ((double)limit >= kProgressWindow) return fail(h, "ndt_max_iters exceeds the device loop's pass window (2^20 passes)");
         int enq = 0;
         const int first = 3;      // (the host enqueues a pass in a quarter of the time the device needs for one: it only has to stay two ahead)
-        static const bool two_launches = dev_env("PCR_NDT_TWO_LAUNCHES") != nullptr;      // the round's earlier form (pass kernel + fold/controller kernel), for A/B runs
         auto launch = [&](int index) -> hipError_t {
-            if (two_launches) return ndt_launch_pass(r.a, d_ctl, h->nd_out_dev, h->stream, seq);
             if (h->profile >= 2) {      // events at every launch's own begin and end (pcr_stats.kernel_ms)
                 while ((int)h->ev_kernel.size() < 2 * (index + 1)) { hipEvent_t e; hipError_t er = hipEventCreate(&e); if (er != hipSuccess) return er; h->ev_kernel.push_back(e); }
                 h->nd_prof_launches = index + 1;
@@ -1590,7 +1574,6 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
         }
         std::atomic_thread_fence(std::memory_order_acquire);
         h->nd_last_passes = out->passes;
-        if (dev_env("PCR_NDT_TICKS")) fprintf(stderr, "ndt passes %d: fold %.2f us/pass, controller %.2f us/pass (decide %.2f, tables %.2f)\n", out->passes, out->ticks[0] * 0.01 / std::max(1, out->passes), out->ticks[1] * 0.01 / std::max(1, out->passes), out->ticks[2] * 0.01 / std::max(1, out->passes), out->ticks[3] * 0.01 / std::max(1, out->passes));
         h->nd_grid_bad = out->grid_overflow || out->grid_stale;
         h->nd_grid_empty = out->grid_empty != 0;
         h->nd_grid_cells = out->grid_cells;
@@ -1727,13 +1710,10 @@ int do_scan2map(pcr_handle* h, const void* src, size_t n_src, const void* dst, s
         // queued first and the scan's side while the host waits for their headers (settle_cov_levels: before_wait).
         // (Measured and not kept: the scan's side queued by a host thread of its own at the same time as the target's -- 0.481 / 0.495 against
         //  0.496 / 0.494 ms: with both sides on the device from the start the call is bound by the device's work, not by the host's launches.)
-        static const bool src_first = dev_env("PCR_VG_SRC_FIRST") != nullptr;      // (development builds: the old order, for A/B runs)
-        int prc = 0;
         bool src_queued = false;
         const std::function<int()> queue_src = [&]() -> int { src_queued = true; return vgicp_source_enqueue(h, d_src, n_src, stride_bytes / 4, true); };
-        if (src_first) { prc = vgicp_source_enqueue(h, d_src, n_src, stride_bytes / 4); src_queued = true; }
-        else prc = vgicp_source_mark(h);
-        if (!prc) prc = vgicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4, use_roi ? &rs : nullptr, false, src_first ? nullptr : &queue_src);
+        int prc = vgicp_source_mark(h);
+        if (!prc) prc = vgicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4, use_roi ? &rs : nullptr, false, &queue_src);
         if (!prc && !src_queued) prc = queue_src();
         if (prc && h->side_pending) { (void)hipEventSynchronize(h->ev_side_done); h->side_pending = false; }
         if (agree_prepared(h, prc)) {
@@ -1836,7 +1816,6 @@ void pcr_destroy(pcr_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) { (void)hipStreamSynchronize(h->stream); pin_forget_stream(h->stream); }
-    if (dev_env("PCR_VF_DEBUG") && h->vf_builds) fprintf(stderr, "voxel filter: %llu index builds, %llu of them over a box or layout that did not hold the cloud\n", h->vf_builds, h->vf_stale);      // (development builds)
     if (h->comm && g_rccl.destroy) g_rccl.destroy(h->comm);
     h->grid.release(); h->tgt_stage.release(); h->src_stage.release();
     h->rl_poses.release(); h->rl_part.release(); h->rl_out.release(); h->rl_src.release();
@@ -2043,23 +2022,10 @@ int vf_begin(pcr_handle* h, const float* d_pts, size_t n, size_t sf, double leaf
 }
 int vf_settle(pcr_handle* h, uint32_t* count, int* too_fine) {
     volatile VfResult& ret = *reinterpret_cast<VfResult*>(h->vf_ret);
-    const size_t n = h->vf_job.n;
     for (int attempt = 0; attempt < 6; ++attempt) {
         if (attempt && vf_enqueue(h)) return 1;
         H_TRY(hipStreamSynchronize(h->stream));
-        ++h->vf_builds;
-        if (dev_env("PCR_VF_DEBUG") && n > 100000) {      // (development builds: the layout this build planned -- bins, tiles, the heaviest bin)
-            std::vector<uint32_t> lay(3 * kMaxBins + 32);
-            (void)hipMemcpy(lay.data(), h->vf_grid.layout[h->vf_grid.lay_idx].p, lay.size() * 4, hipMemcpyDeviceToHost);
-            const uint32_t nb = lay[3 * kMaxBins + 24], nt = lay[3 * kMaxBins + 25];
-            uint32_t room_max = 0, kmax = 0;
-            for (uint32_t b = 0; b < nb && b < (uint32_t)kMaxBins; ++b) { room_max = std::max(room_max, lay[b + 1] - lay[b]); kmax = std::max(kmax, lay[2 * kMaxBins + 16 + b] >> 26); }
-            fprintf(stderr, "voxel filter: n %zu used_hint %d used_layout %d tshift %d stale %d overflow %d | next layout: %u bins over %u tiles, widest room %u, deepest cut %u\n",
-                    n, (int)h->vf_grid.used_hint, (int)h->vf_grid.used_layout, h->vf_grid.tiled_shift, (int)ret.stale, (int)ret.overflow, nb, nt, room_max, kmax);
-        }
         if (ret.stale) {      // the box (or a bin's room) taken over from the previous call does not hold this cloud
-            ++h->vf_stale;
-            if (dev_env("PCR_VF_DEBUG")) fprintf(stderr, "voxel filter: n %zu leaf %g stale %d (1 box, 2 room, 3 layout)\n", n, h->vf_job.leaf, (int)ret.stale);
             // (the cell count the tile size goes by is kept once the box has its margin: a build without it takes the dense path -- 23 us instead of 11 for a scan)
             if (h->vf_grid.hint_margin == 0) { h->vf_grid.hint_margin = 16; h->vf_grid.hint_margin_z_pcl = 4; h->vf_grid.cells_hint = 0; }
             h->vf_grid.lay_room_shift = 1; h->vf_grid.lay_room_add = 256;
@@ -2269,10 +2235,6 @@ int pcr_vgicp_covariances(pcr_handle* h, const void* pts, size_t n, size_t strid
     H_TRY(hipStreamSynchronize(h->stream));
     return 0;
 }
-
-#ifdef PCR_DEV_SWITCHES
-int pcr_dev_read_stamps(unsigned long long* out, size_t count) { return pcr::dev_stamps(out, count); }
-#endif
 
 int pcr_vgicp_neighbours(pcr_handle* h, size_t n, uint32_t* nbr_out, uint32_t* queued_out) {
     if (!h) return 1;

@@ -372,19 +372,12 @@ __global__ __launch_bounds__(256) void grid_scatter_kernel(const float* __restri
 // global ones before: nothing downstream may depend on it, and nothing does (searches break distance ties on the
 // original index in .w; voxel statistics are fixed-point sums).
 // ======================================================================================================================
-#ifdef PCR_DEV_SWITCHES
-// development builds: s_memrealtime stamps of the bin and tile kernels ([kernel 0/1][block < 8192][8]), read back by pcr_dev_read_stamps
-__device__ unsigned long long* g_dev_stamps = nullptr;
-#define DEV_STAMP(kernel, slot) do { if (g_dev_stamps && threadIdx.x == 0 && blockIdx.x < 8192) g_dev_stamps[((size_t)(kernel) * 8192 + blockIdx.x) * 8 + (slot)] = wall_clock64(); } while (0)
-#else
-#define DEV_STAMP(kernel, slot) do { } while (0)
-#endif
 static constexpr int kBinStride = 16;                  // counters 64 bytes apart: memory-side atomics on one line serialise
 // (Measured, round 5: the same counters 16 to a line -- bin b at word (b & 15) * 512 + (b >> 4), so that the last block reads them back in 16 coalesced
 //  rows instead of one line per counter at ~2.3 ns a line -- shorten that block's tail from 3.6 to 3 us at 1 M points and make the claims come back after
 //  41 us instead of 16: a chunk of a map in generator order touches every ground tile, ~300 claims per counter, and sixteen counters' claims then queue up
 //  on one line.  What bounds the claim phase is the serial handling of the claims on its hottest LINE.)
-static constexpr int kBinPerDefault = 8;              // points per thread and chunk of the bin kernel
+static constexpr int kBinPerThread = 8;               // points per thread and chunk of the bin kernel
 
 // ---- BINS: the units of the two passes.  A build without a layout hint bins by TILE (2^shift consecutive cells: bin b = tile b).  A ground tile of a
 // 1 m grid over a 0.5 m map holds eight times the points of the median tile, and the tile pass lasted as long as its heaviest tile's ONE block (24 us of
@@ -451,7 +444,6 @@ __global__ __launch_bounds__(256) void grid_bin_kernel(const float* __restrict__
     uint32_t* const hist = dyn_lds;
     uint32_t* const sh_lay = dyn_lds + nb_max;      // kPlace: nb_max + 1 entries
     uint16_t* const sh_sub = reinterpret_cast<uint16_t*>(dyn_lds + 2 * (size_t)nb_max + 2);      // kSub: max_tiles entries (first bin | k << 13)
-    DEV_STAMP(0, 0);
     constexpr uint32_t kBinChunk = 256u * kBinPer;      // points a block histograms at a time
     // (requesting a block's first chunk of points before the header has arrived -- two independent round trips -- was measured, round 5: nothing at
     //  1 M points, 6-7 us WORSE at 10 M, where blocks queue up three to a CU)
@@ -513,9 +505,7 @@ __global__ __launch_bounds__(256) void grid_bin_kernel(const float* __restrict__
             base = __shfl(base, start, 64);
             loc[u] = base + (uint32_t)(lane - start);
         }
-        DEV_STAMP(0, 1);
         __syncthreads();
-        DEV_STAMP(0, 2);
         // the lane that opened a bin claims room for all the chunk's points of that bin: one global atomic per (chunk, bin)
         uint32_t cnt[kBinPer], got[kBinPer];
 #pragma unroll
@@ -526,7 +516,6 @@ __global__ __launch_bounds__(256) void grid_bin_kernel(const float* __restrict__
 #pragma unroll
         for (int u = 0; u < kBinPer; ++u) if (first[u]) hist[bin[u]] = got[u];
         __syncthreads();
-        DEV_STAMP(0, 3);
         if (kPlace) {
             bool over = false;
 #pragma unroll
@@ -551,7 +540,6 @@ __global__ __launch_bounds__(256) void grid_bin_kernel(const float* __restrict__
         for (int u = 0; u < kBinPer; ++u) if (first[u]) hist[bin[u]] = 0u;      // ready for the next chunk
         __syncthreads();
     }
-    DEV_STAMP(0, 4);
     // ---- the last block to finish turns the bin counters (64 bytes apart, written by device-scope atomics) into the compact
     //      exclusive scan the next two kernels read: bin_start[0 .. nb]  (the layout of the NEXT build is planned by a block of the tile
     //      pass, beside the others: tile_block0 -- here it was another block scan on the one chain every block of the next kernel waits for).
@@ -565,7 +553,6 @@ __global__ __launch_bounds__(256) void grid_bin_kernel(const float* __restrict__
         sh_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
     }
     __syncthreads();
-    DEV_STAMP(0, 5);
     if (!sh_last) return;
     const uint32_t per = (nb + 255u) / 256u;      // <= kMaxBins / 256 = 32
     const uint32_t b0 = threadIdx.x * per;
@@ -595,7 +582,6 @@ __global__ __launch_bounds__(256) void grid_bin_kernel(const float* __restrict__
     if (threadIdx.x == 255) bin_start[nb] = total;
     if (threadIdx.x == 0) *ticket = 0u;                        // ready for the next build
     if (kPacked && threadIdx.x == 0) *n_packed = 0u;           // (every block has read it: they all took the ticket after their loops)
-    DEV_STAMP(0, 6);
 }
 
 // ---- region-only builds: the points of the region, listed ----
@@ -782,7 +768,6 @@ __device__ void tile_block0(const GridHeader* __restrict__ hdr, int shift, const
     int deep = 0;      // some tile is cut four times or more
     for (uint32_t t = threadIdx.x; t < ntiles; t += kThreads) { const uint16_t e = lay_cur ? (uint16_t)lay_cur[kLaySub + t] : (uint16_t)t; sub[t] = e; deep |= (e >> 13) >= 4u ? 1 : 0; }
     const bool by_bins = __syncthreads_or(deep) != 0;
-    DEV_STAMP(1, 5);
     const int kmax = plan.cuts ? min(kMaxSplit, shift - 2) : 0;      // (no cuts: a layout that holds some -- planned when the cloud was smaller -- is merged back step by step)
     // a thread's run of tiles: an equal share of the tiles -- or, once some tile is cut deep, those whose first bin lies in its share of the BINS (the work
     // below is per bin: with equal shares of the tiles the thread that owned the eight tiles under the vehicle's path, cut into 64 slabs each, walked 512
@@ -830,7 +815,6 @@ __device__ void tile_block0(const GridHeader* __restrict__ hdr, int shift, const
         if (threadIdx.x == 0) { out[kLayMeta] = 0u; out[kLayMeta + 1] = 0u; }
         return;
     }
-    DEV_STAMP(1, 6);
     uint32_t nbin = (uint32_t)(off >> 40), pos = (uint32_t)(off & 0xffffffffffull);
     for (uint32_t t = t0; t < t1; ++t) {
         const uint32_t e = sub[t], base = e & 0x1fffu;
@@ -848,7 +832,6 @@ __device__ void tile_block0(const GridHeader* __restrict__ hdr, int shift, const
         }
     }
     if (threadIdx.x == kThreads - 1) { out[nbin] = pos; out[kLayMeta] = nbin; out[kLayMeta + 1] = ntiles; }      // (the last thread ends at the totals)
-    DEV_STAMP(1, 7);
 }
 
 // The other blocks: a bin each (a tile, or one of the slabs a heavy tile was cut into: see BINS above), bin after bin -- the grid is sized to what the
@@ -886,7 +869,6 @@ __global__ __launch_bounds__(kThreads) void grid_tile_kernel(const GridHeader* _
     __shared__ uint32_t sh4[kThreads / 64];
     __shared__ unsigned long long sh_sq[kThreads / 64];
     __shared__ uint32_t sh_tail_base;
-    DEV_STAMP(1, 0);
     const uint32_t first_blk = kPlan && plan.enabled ? 1u : 0u;
     const uint32_t blk = blockIdx.x - first_blk, nblk = gridDim.x - first_blk;      // (block 0 of a planning launch never uses them)
     // what this block needs to know of its first bin, requested beside the header (the indices are in bounds for every block of the grid: <= kMaxBins blocks)
@@ -984,7 +966,6 @@ __global__ __launch_bounds__(kThreads) void grid_tile_kernel(const GridHeader* _
         }
         if (threadIdx.x == 0) bin_count[(size_t)bin * kBinStride] = 0u;      // the counters are left zeroed: the state the next build expects
         __syncthreads();
-        if (bin == blk) DEV_STAMP(1, 1);
         // exclusive scan of the bin's counters -> cell_start (+ sum of count^2, the density estimate of the header)
         unsigned long long sq = 0;
         uint32_t carry = 0;
@@ -1050,7 +1031,6 @@ __global__ __launch_bounds__(kThreads) void grid_tile_kernel(const GridHeader* _
                 ++pos;
             }
         }
-        if (bin == blk) DEV_STAMP(1, 2);
         if (small) {
 #pragma unroll
             for (int u = 0; u < kTilePer; ++u) {
@@ -1077,9 +1057,7 @@ __global__ __launch_bounds__(kThreads) void grid_tile_kernel(const GridHeader* _
             }
         }
         __syncthreads();
-        if (bin == blk) DEV_STAMP(1, 3);
     }
-    DEV_STAMP(1, 4);
 }
 
 // sum of count^2 over the cells = sum of the tiles' sums -> header (only VGICP's choice of a search cell reads it)
@@ -1288,7 +1266,6 @@ hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, 
     valid = false;
     filtered = false;
     if (filter) { filter->applied = false; filter->tail_applied = false; }
-    const bool force_atomic_path = dev_env("PCR_INDEX_ATOMIC") != nullptr;      // A/B switch for profiling the two build paths
     if (n > 0xfffffff0ull) { if (err) *err = "target cloud too large (>= 2^32 points)"; return hipErrorInvalidValue; }
     const size_t n_res = std::max(n, reserve_points);      // (reserve_points: the caller knows its clouds will grow to that -- the sub-map assembly's concatenations)
     PCR_TRY(sorted.reserve((n_res + 16) * sizeof(float4)));   // padded: the search reads whole chunks
@@ -1319,14 +1296,11 @@ hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, 
     int tshift;
     // (the voxel filter's grids -- 65 536 points over 2.3 M cells of 0.5 m -- take tiles of 4 096 cells: half the bins for the bin pass's last block to read back,
     //  7 % off a scan's filter; 8 192 cells: slower again.  Round 5, scripts/seq_breakdown.py, two rounds on one box.)
-    static const int vf_cap = dev_env("PCR_VF_TILE_SHIFT_MAX") ? atoi(dev_env("PCR_VF_TILE_SHIFT_MAX")) : 12;
-    const int tshift_cap = cut_sparse ? vf_cap : 11;
+    const int tshift_cap = cut_sparse ? 12 : 11;
     if (cells_hint) { tshift = 2; while ((cells_hint >> tshift) > tiles_target && tshift < tshift_cap) ++tshift; }
     else { tshift = 8; while (((uint64_t)cap_eff >> tshift) + 2 > 2048 && tshift < 11) ++tshift; }
-    if (const char* e = dev_env("PCR_TILE_SHIFT")) tshift = std::max(2, atoi(e));      // (development: tile size sweep)
     while (((uint64_t)cap_eff >> tshift) + 2 > (uint64_t)kMaxBins) ++tshift;
-    const bool tiled_path = tshift <= kMaxTileShift && !force_atomic_path && !prefer_one_level;
-    if (dev_env("PCR_INDEX_DEBUG")) fprintf(stderr, "index build: n %zu cell %.3g capacity %zu cells_hint %llu cap_eff %zu tshift %d hint_ok %d lay_ok %d\n", n, cell, cell_capacity, (unsigned long long)cells_hint, cap_eff, tshift, (int)hint_ok, (int)lay_ok);
+    const bool tiled_path = tshift <= kMaxTileShift && !prefer_one_level;
     const bool reuse_header = allow_hint && !no_hints && hint_ok && tiled_path && hint_pcl == pcl_mode && hint_shift == shift && !cb.use && hint_cell == cell && tiled_shift == tshift;
     hint_ok = false;      // until the host has seen this build's header (confirm())
     used_hint = reuse_header;
@@ -1362,9 +1336,7 @@ hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, 
             PCR_TRY(hipMemsetAsync(bin_count.p, 0, bin_count.cap, s));      // builds expect and leave the counters zeroed
         }
         const bool vec = (stride_floats % 4 == 0) && ((uintptr_t)d_pts % 16 == 0);
-        int bin_per = kBinPerDefault;
-        if (const char* e = dev_env("PCR_BIN_PER")) bin_per = atoi(e);      // (development: chunk size sweep)
-        const size_t bin_chunk = (size_t)256 * bin_per;
+        const size_t bin_chunk = (size_t)256 * kBinPerThread;
         const int bin_blocks = (int)std::min<size_t>(4096, (n + bin_chunk - 1) / bin_chunk ? (n + bin_chunk - 1) / bin_chunk : 1);
         const int place_blocks = (int)std::min<size_t>(2048, (n + 1023) / 1024 ? (n + 1023) / 1024 : 1);
         // (a grid with many more cells than points: light tiles and heavy tiles by an instantiation each, see grid_tile_kernel)
@@ -1382,17 +1354,15 @@ hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, 
         // block, stays at 153-169 us: clouds whose tiles hold more than ~1 000 points on average are never cut.
         // (cut_sparse -- the voxel filter's index: a concatenation of raw key frames on the 0.5 m lattice is a sparse grid whose few tiles next to the vehicle's
         //  path hold tens of thousands of points each; one block sorted such a tile alone, 95 us of a 150 us build.  Its bins hold up to 4 096 points in registers.)
-        uint32_t hs = per8 ? 2048u : (sparse && cut_sparse ? 3072u : 0u);
-        if (const char* e = dev_env("PCR_BIN_SPLIT")) hs = (uint32_t)std::max(0, atoi(e));      // (development: 0 = tiles are never cut)
-        if (hs == 0u) hs = 0xffffffffu;
+        const uint32_t hs = per8 ? 2048u : (sparse && cut_sparse ? 3072u : 0xffffffffu);
         // bins a layout may hold: the tiles + two bins per `hs` points (a slab that was cut holds between hs / 2 and hs), never fewer than the tiles the table
         // can make, and never fewer than the layout in hand was planned for (the bin pass sizes its LDS by it)
         uint32_t nb_max = (uint32_t)std::min<uint64_t>((uint64_t)kMaxBins, std::max<uint64_t>((uint64_t)max_bins, (tiles_est ? tiles_est + 2 : (uint64_t)max_bins) + (hs != 0xffffffffu ? 2 * (uint64_t)n / hs : 0)));
         if (hs == 0xffffffffu && !(lay_ok && lay_cuts)) nb_max = max_bins;
         if (lay_ok && lay_shift == tshift) nb_max = std::max(nb_max, lay_nb_max);
         // Layout hint (see grid_bin_kernel<.., kPlace>): the previous build of this index left, next to its header, where each bin's
-        // points may go; a build that reuses the header places by it and skips the placing pass.  PCR_INDEX_NO_LAYOUT=1 switches it off.
-        const bool use_layout = reuse_header && lay_ok && lay_shift == tshift && lay_nb_max <= nb_max && dev_env("PCR_INDEX_NO_LAYOUT") == nullptr;
+        // points may go; a build that reuses the header places by it and skips the placing pass.
+        const bool use_layout = reuse_header && lay_ok && lay_shift == tshift && lay_nb_max <= nb_max;
         for (int i = 0; i < 2; ++i)
             if (!layout[i].p) { PCR_TRY(layout[i].reserve(kLayWords * sizeof(uint32_t))); PCR_TRY(hipMemsetAsync(layout[i].p, 0, kLayWords * sizeof(uint32_t), s)); }      // (meta word 0: no layout)
         if (use_layout) {      // room for every bin's slack, the children of a tile that is cut one step further get their parent's room each:
@@ -1422,10 +1392,10 @@ hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, 
 #define PCR_LAUNCH_BIN(VEC, PER, PLACE, SUB) hipLaunchKernelGGL((grid_bin_kernel<VEC, PER, PLACE, SUB>), dim3(bin_blocks), dim3(256), bin_lds, s, d_pts, n32, st, header.as<GridHeader>(), \
                                                     bin_count.as<uint32_t>(), ranks.as<uint32_t>(), tshift, max_bins, nb_bin, ticket.as<uint32_t>() + 8, bin_start.as<uint32_t>(), \
                                                     lay_cur, tiled.as<float4>(), tiled_cap, keep_mask, keep_mshift)
-#define PCR_LAUNCH_BIN_P(VEC, PLACE, SUB) do { if (bin_per == 4) PCR_LAUNCH_BIN(VEC, 4, PLACE, SUB); else if (bin_per == 8) PCR_LAUNCH_BIN(VEC, 8, PLACE, SUB); else PCR_LAUNCH_BIN(VEC, 16, PLACE, SUB); } while (0)
-        // region-only builds of large clouds: the region's points are listed first, the bin pass reads the list (grid_keep_kernel; PCR_NO_KEEP_PASS=1 in a
-        // development build: the bin pass tests the mask itself, as before)
-        const bool keep_pass = keep_mask != nullptr && n >= 2000000 && dev_env("PCR_NO_KEEP_PASS") == nullptr;      // (a 1 M-point lattice build -- VGICP's -- is 1.5 % SLOWER with the extra launch)
+#define PCR_LAUNCH_BIN_P(VEC, PLACE, SUB) PCR_LAUNCH_BIN(VEC, kBinPerThread, PLACE, SUB)
+        // region-only builds of large clouds: the region's points are listed first, the bin pass reads the list (grid_keep_kernel; smaller clouds: the bin
+        // pass tests the mask itself)
+        const bool keep_pass = keep_mask != nullptr && n >= 2000000;      // (a 1 M-point lattice build -- VGICP's -- is 1.5 % SLOWER with the extra launch)
         if (keep_pass) {
             PCR_TRY(kept.reserve((n + 16) * sizeof(float4)));
             uint32_t* const n_kept = ticket.as<uint32_t>() + 16;      // (zero between builds: the bin pass's last block puts it back)
@@ -1433,9 +1403,9 @@ hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, 
             const uint32_t kept_cap = (uint32_t)std::min<size_t>(kept.cap / sizeof(float4), 0xfffffff0u);
             if (vec) hipLaunchKernelGGL(grid_keep_kernel<true>, dim3(keep_blocks), dim3(256), 0, s, d_pts, n32, st, header.as<GridHeader>(), keep_mask, keep_mshift, kept.as<float4>(), kept_cap, n_kept);
             else hipLaunchKernelGGL(grid_keep_kernel<false>, dim3(keep_blocks), dim3(256), 0, s, d_pts, n32, st, header.as<GridHeader>(), keep_mask, keep_mshift, kept.as<float4>(), kept_cap, n_kept);
-            const int packed_blocks = std::min(bin_blocks, dev_env("PCR_PACKED_BLOCKS") ? atoi(dev_env("PCR_PACKED_BLOCKS")) : 512);      // (a block takes chunk after chunk: the list's length is the device's to know)
+            const int packed_blocks = std::min(bin_blocks, 512);      // (a block takes chunk after chunk: the list's length is the device's to know)
             const size_t lds8 = bin_lds;
-#define PCR_LAUNCH_BIN_PACKED(SUB) hipLaunchKernelGGL((grid_bin_kernel<true, 8, true, SUB, true>), dim3(packed_blocks), dim3(256), lds8, s, kept.as<float>(), n32, 4u, header.as<GridHeader>(), \
+#define PCR_LAUNCH_BIN_PACKED(SUB) hipLaunchKernelGGL((grid_bin_kernel<true, kBinPerThread, true, SUB, true>), dim3(packed_blocks), dim3(256), lds8, s, kept.as<float>(), n32, 4u, header.as<GridHeader>(), \
                                                     bin_count.as<uint32_t>(), ranks.as<uint32_t>(), tshift, max_bins, nb_bin, ticket.as<uint32_t>() + 8, bin_start.as<uint32_t>(), \
                                                     lay_cur, tiled.as<float4>(), tiled_cap, (const uint8_t*)nullptr, 0, n_kept)
             if (use_sub) PCR_LAUNCH_BIN_PACKED(true); else PCR_LAUNCH_BIN_PACKED(false);
@@ -1459,37 +1429,32 @@ hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, 
         // block 0 of the (first) tile launch plans the layout of the next build; the others take a bin each
         TilePlan plan;
         plan.lay_next = lay_next; plan.hs = hs; plan.nb_max = nb_max; plan.enabled = 1; plan.copy_only = filtered ? 1 : 0; plan.cuts = cuts_now ? 1 : 0; plan.room_shift = lay_room_shift; plan.room_add = lay_room_add; plan.pad_ = 0;
-        // the tile pass: as many blocks as the device holds at once (a block takes bin after bin), + block 0
-        static const int n_cu = [] { int dev = 0, v = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256; return v; }();
-        int per_cu = 0;      // (0 = a block per bin: persistent blocks -- 6 / 4 / 2 per CU by their registers -- measured no better at 1 M points and 6 % worse at 10 M, round 5)      // (blocks of 256 threads by their registers: 77 / 128 (130 with the tail) / 216 VGPRs)
-        if (const char* e = dev_env("PCR_TILE_PER_CU")) per_cu = std::max(0, atoi(e));      // (development: 0 = a block per bin, as before round 5)
+        // the tile pass: a block per bin, + block 0 (persistent blocks -- 6 / 4 / 2 per CU by their registers -- measured no better at 1 M points and
+        // 6 % worse at 10 M, round 5)
         // (a block per bin the host EXPECTS -- the tiles of the header it has seen + a bin per hs points when tiles are cut -- not per bin the table could
         //  make: a block that finds no bin still waits for the header, ~2 us of a slot each, and there were 3 000 of them at 10 M points; a block takes
         //  bin after bin, so more bins than blocks are served all the same)
         const uint32_t bins_bound = use_layout ? nb_max : max_bins;
         const uint32_t bins_expected = tiles_est ? (uint32_t)std::min<uint64_t>(bins_bound, tiles_est + 16 + (use_layout && hs != 0xffffffffu ? (uint64_t)n / hs : 0)) : bins_bound;
-        const int tile_blocks = (int)std::min<uint32_t>(bins_expected, per_cu > 0 ? (uint32_t)(n_cu * per_cu) : bins_expected) + 1;
+        const int tile_blocks = (int)bins_expected + 1;
 #define PCR_LAUNCH_TILE_R(PER, MODE, THREADS, TAIL, PLAN, RUNS) hipLaunchKernelGGL((grid_tile_kernel<PER, MODE, THREADS, TAIL, PLAN, RUNS>), dim3(tile_blocks), dim3(THREADS), (PLAN) ? tile_lds : (size_t)(1u << tshift) * 4, s, header.as<GridHeader>(), tile_sq.as<unsigned long long>(), \
                            bin_start.as<uint32_t>(), bin_count.as<uint32_t>(), tiled.as<float4>(), cell_start.as<uint32_t>(), sorted.as<float4>(), keys.as<uint32_t>(), tshift, \
                            use_layout ? lay_cur : (const uint32_t*)bin_start.as<uint32_t>(), use_layout ? lay_cur : (const uint32_t*)nullptr, plan, tail)
 #define PCR_LAUNCH_TILE_T(PER, MODE, THREADS, TAIL, PLAN) PCR_LAUNCH_TILE_R(PER, MODE, THREADS, TAIL, PLAN, false)
 #define PCR_LAUNCH_TILE(PER, MODE, THREADS) PCR_LAUNCH_TILE_T(PER, MODE, THREADS, false, true)
-        // (blocks of 1 024 threads for the 5 M and 10 M-point maps -- grid_tile_kernel<4, 0, 1024>, PCR_TILE_WIDE in a development build -- cut the
-        //  slowest tile of the 10 M-point map from 165 to 69 us and left the kernel at 165 us: one block per CU then, 19 rounds of ~8 us;
-        //  profiles/r04_notes.md)
-        static const int wide = dev_env("PCR_TILE_WIDE") ? atoi(dev_env("PCR_TILE_WIDE")) : 0;      // (development: average points per tile from which the wide blocks are used; 0 = never)
+        // (measured and not kept: blocks of 1 024 threads for the 5 M and 10 M-point maps cut the slowest tile of the 10 M-point map from 165 to 69 us
+        //  and left the kernel at 165 us: one block per CU then, 19 rounds of ~8 us; profiles/r04_notes.md)
         // (the tile pass lists NDT's voxel cells beside its own work: dense grids, tiles of at most 2^13 cells -- 32 per thread)
-        const bool with_tail = filtered && filter->want_tail && !sparse && tshift <= 13 && dev_env("PCR_NDT_NO_TAIL") == nullptr;
+        const bool with_tail = filtered && filter->want_tail && !sparse && tshift <= 13;
         if (with_tail) { tail = filter->tail; tail.mask = keep_mask; tail.mshift = keep_mshift; filter->tail_applied = true; }
         // (sparse grids: the launch of the light tiles carries no planning block -- its 58 registers are what lets eight of its blocks share a CU)
         // (the heavy bins of the voxel filter's clouds by blocks of 1 024 threads: what a block holds in registers is the same 4 096 points, a bin of 12 000 --
         //  three chunks, two sweeps each -- is through four times sooner)
-        if (coherent_input && sparse) { PCR_LAUNCH_TILE_R(1, 1, 256, false, false, true); if (dev_env("PCR_VF_NARROW")) PCR_LAUNCH_TILE_R(16, 2, 256, false, true, true); else PCR_LAUNCH_TILE_R(4, 2, 1024, false, true, true); }
+        if (coherent_input && sparse) { PCR_LAUNCH_TILE_R(1, 1, 256, false, false, true); PCR_LAUNCH_TILE_R(4, 2, 1024, false, true, true); }
         else if (coherent_input && !with_tail) { if (per8) PCR_LAUNCH_TILE_R(8, 0, 256, false, true, true); else PCR_LAUNCH_TILE_R(16, 0, 256, false, true, true); }
         else if (sparse) { PCR_LAUNCH_TILE_T(1, 1, 256, false, false); PCR_LAUNCH_TILE(16, 2, 256); }
         else if (with_tail) { if (per8) PCR_LAUNCH_TILE_T(8, 0, 256, true, true); else PCR_LAUNCH_TILE_T(16, 0, 256, true, true); }
         else if (per8) PCR_LAUNCH_TILE(8, 0, 256);
-        else if (wide > 0 && tiles_est && n / tiles_est >= (uint64_t)wide) PCR_LAUNCH_TILE(4, 0, 1024);
         else PCR_LAUNCH_TILE(16, 0, 256);
 #undef PCR_LAUNCH_TILE
 #undef PCR_LAUNCH_TILE_T
@@ -1517,20 +1482,5 @@ hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, 
     valid = true;
     return hipSuccess;
 }
-
-#ifdef PCR_DEV_SWITCHES
-// development builds: arm (allocate + clear) or read the stamp buffer of the bin / tile kernels
-static unsigned long long* g_stamps_host_ptr = nullptr;
-int dev_stamps(unsigned long long* out, size_t count) {
-    const size_t total = (size_t)2 * 8192 * 8;
-    if (!g_stamps_host_ptr) {
-        if (hipMalloc((void**)&g_stamps_host_ptr, total * 8) != hipSuccess) return 1;
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_dev_stamps), &g_stamps_host_ptr, sizeof(g_stamps_host_ptr)) != hipSuccess) return 1;
-    }
-    if (hipDeviceSynchronize() != hipSuccess) return 1;
-    if (out && hipMemcpy(out, g_stamps_host_ptr, std::min(count, total) * 8, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-    return hipMemset(g_stamps_host_ptr, 0, total * 8) != hipSuccess;
-}
-#endif
 
 }  // namespace pcr

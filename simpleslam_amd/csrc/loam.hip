@@ -26,14 +26,6 @@
 
 namespace pcr {
 
-// The phase-skipping switches of a development build (PCR_ABLATE, scripts/timeline_ablate.py) exist only in a build with
-// -DPCR_ABLATION: in the candidate loop their tests alone were two scalar branches per slot.
-#ifdef PCR_ABLATION
-static constexpr bool kAblation = true;
-#else
-static constexpr bool kAblation = false;
-#endif
-
 
 
 // ------------------------------------------------------------------------------
@@ -783,7 +775,7 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
     if (reuse) {
         x[0] = ce_in.x[0]; x[1] = ce_in.x[1]; x[2] = ce_in.x[2];
         plane_ok = (ce_in.flags & 4u) != 0;
-    } else if (real5 && !(kAblation && (a.ablate & 2))) {
+    } else if (real5) {
         double Aq[5][3];
 #pragma unroll
         for (int j = 0; j < 5; ++j) { Aq[j][0] = A[j][0]; Aq[j][1] = A[j][1]; Aq[j][2] = A[j][2]; }
@@ -817,8 +809,7 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
             tail.t.x[0] = x[0]; tail.t.x[1] = x[1]; tail.t.x[2] = x[2];
 #pragma unroll
             for (int j = 0; j < 5; ++j) tail.t.pidx[j] = s.idx[j];
-            const bool x_valid = real5 && !(kAblation && (a.ablate & 2));
-            tail.t.flags = (searched ? 1u : 0u) | (x_valid ? 2u : 0u) | (plane_ok ? 4u : 0u);
+            tail.t.flags = (searched ? 1u : 0u) | (real5 ? 2u : 0u) | (plane_ok ? 4u : 0u);
 #pragma unroll
             for (int f = 0; f < 3; ++f) dst[kNb + 1 + f] = tail.v[f];
         }
@@ -829,7 +820,6 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
 #pragma unroll
     for (int j = 0; j < 5; ++j) nn_idx[j] = s.idx[j];
     if (!gate_knn) return 1;
-    if (kAblation && (a.ablate & 2)) return 2;
     if (!plane_ok) return 2;
     const double xn = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
     const double dist = (qx * x[0] + qy * x[1] + qz * x[2] + 1.0) / xn;   // LoamRegister.hpp:75-77
@@ -885,7 +875,7 @@ __device__ bool loam_prologue(const LoamArgs& a, int k, double* sh_sum /* 8*32 *
     // Request this thread's share of the previous launch's partial sums together with the state it guards
     // (one memory round trip instead of two); they are simply unused when the loop has already finished.
     const int comp = t & 31, slice = t >> 5;
-    const uint32_t n_rows = a.n_prev ? a.n_prev : a.n_partials;      // rows of launch k - 1
+    const uint32_t n_rows = a.n_partials;      // rows of launch k - 1
     // the state first: loads complete in issue order, so testing `done` then waits for nothing younger
     const int prev_done = prev->done;
     const double prev_pose_t = t < 16 ? prev->pose[t] : 0.0;
@@ -936,12 +926,6 @@ __device__ bool loam_prologue(const LoamArgs& a, int k, double* sh_sum /* 8*32 *
         if (blockIdx.x == 0 && t == 0) { *cur = *prev; __hip_atomic_store(&a.result->progress, (k << 1) | 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
         __syncthreads();
         return true;
-    }
-    if (kAblation && (a.ablate & 4)) {
-        if (t == 0) { sh->done = k >= a.c.iters; sh->big_step = 0; }
-        if (blockIdx.x == 0 && t == 0) { *cur = *prev; cur->done = k >= a.c.iters; cur->iters_run = k; }
-        __syncthreads();
-        return k >= a.c.iters;
     }
     if (t < 32) {
         double v = sh_sum[t];
@@ -1076,17 +1060,14 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const 
     float pre_x = 0.f, pre_y = 0.f, pre_z = 0.f;
     const bool use_cache = k > 0 && a.nn_cache != nullptr;
     const float4* pre_src = nullptr;
-    // half blocks (LoamArgs::half): 128 queries per block, owned by the lower half of its threads; the upper half has none of its own and
-    // only takes its slice of the searches (loam_point: a block with 128 posted queries searches each with two lanes, in different waves)
-    const uint32_t qpb = a.half ? 128u : 256u;
-    const bool owner_lane = (uint32_t)tid < qpb;
+    const uint32_t qpb = 256u;      // queries per block
     {
         const uint32_t q = blk * qpb + (uint32_t)tid;
         // unconditional load of a clamped index: a conditional one makes the wave wait for it at the join
         const float* sp = a.n_src ? a.src + (size_t)(q < a.n_src ? q : a.n_src - 1u) * a.src_stride
                                   : reinterpret_cast<const float*>(a.partials);      // empty scan: any readable address
         pre_x = sp[0]; pre_y = sp[1]; pre_z = sp[2];
-        pre_src = (use_cache && owner_lane && q < a.n_src) ? reinterpret_cast<const float4*>(a.nn_cache + q) : nullptr;
+        pre_src = (use_cache && q < a.n_src) ? reinterpret_cast<const float4*>(a.nn_cache + q) : nullptr;
     }
     if (loam_prologue(a, k, sh_sum, &sh_pro, tl, pre_src, use_cache ? sh_pre + (tid & ~63) : nullptr)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // never leave with an LDS-DMA in flight
@@ -1114,7 +1095,7 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const 
     uint32_t n_hit = 0, n_search = 0, n_esc = 0;
     for (uint32_t base = blk * qpb; base < a.n_src; base += gridDim.x * qpb) {
         const uint32_t q = base + tid;
-        const bool valid = owner_lane && q < a.n_src;
+        const bool valid = q < a.n_src;
         double row[7] = {0, 0, 0, 0, 0, 0, 0};
         uint32_t nn[5] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
         int how = 0;
@@ -1122,7 +1103,9 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const 
         float sx = pre_x, sy = pre_y, sz = pre_z;
         union { NnCacheEntry e; float4 v[kEntryVec]; } ce;
         ce.e.flags = 0;
+        bool all_search = false;      // (later rounds of a grid-stride launch go the ordinary way)
         if (base == blk * qpb) {
+            all_search = sh_pro.big_step != 0;
             // EVERY wave waits for its own LDS-DMA, also one without a single valid query (its lanes fetched a dummy address):
             // the staging area is reused right after the barrier, and a transfer still in flight would land in the search
             // scratch of the other waves.
@@ -1140,7 +1123,6 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const 
                 if (use_cache) ce.e = a.nn_cache[q];
             }
         }
-        const bool all_search = sh_pro.big_step != 0 && base == blk * qpb && !a.half;      // (later rounds of a grid-stride launch go the ordinary way)
         const int st = loam_point<kGroup>(a, h, pose, sx, sy, sz, valid, ce.e, use_cache && valid && !all_search, sh_knn, sh_ex, row, nn, q, &how, &esc,
                                           base == blk * qpb ? tl : nullptr, all_search);
         if (valid && (a.dbg_status || a.dbg_nn || a.dbg_rows)) {
@@ -1279,19 +1261,7 @@ uint32_t loam_grid_blocks(uint32_t n_src) {
 // start/stop (optional): events that the packet processor stamps at the kernel's own begin and end (hipExtLaunchKernelGGL),
 // i.e. what a profiler reports as the kernel's duration -- events recorded around an ordinary launch also contain the
 // dispatch latency (~2 us here).
-hipError_t loam_launch_iteration(const LoamArgs& a_in, int k, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool allow_half) {
-    LoamArgs a = a_in;
-    a.half = 0; a.n_prev = 0;
-    // (development: launch 0 -- every query searches -- as twice the blocks of 128 queries, two lanes per query, two waves per SIMD)
-    static const int half0 = dev_env("PCR_LOAM_HALF0") ? atoi(dev_env("PCR_LOAM_HALF0")) : 0;
-    const bool can_half = allow_half && half0 > 0 && !a.reduced && !a.coresident && 2u * a.n_partials <= (uint32_t)kMaxPartials && !(start && stop);
-    if (can_half && k == 1) a.n_prev = 2u * a.n_partials;
-    if (can_half && k == 0) {
-        a.half = 1;
-        if (half0 == 1) hipLaunchKernelGGL((loam_iterate_kernel<8, 2>), dim3(2u * a.n_partials), dim3(256), 0, s, a, k);
-        else hipLaunchKernelGGL((loam_iterate_kernel<4, 2>), dim3(2u * a.n_partials), dim3(256), 0, s, a, k);
-        return hipGetLastError();
-    }
+hipError_t loam_launch_iteration(const LoamArgs& a, int k, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     if (start && stop) {
         if (a.coresident) hipExtLaunchKernelGGL((loam_iterate_kernel<4, 2>), dim3(a.n_partials), dim3(256), 0, s, start, stop, 0, a, k);
         else hipExtLaunchKernelGGL((loam_iterate_kernel<8, 1>), dim3(a.n_partials), dim3(256), 0, s, start, stop, 0, a, k);

@@ -652,10 +652,10 @@ __global__ __launch_bounds__(kNdtBlock, 2) void ndt_hessian_kernel(const NdtArgs
 }
 
 // ------------------------------------------------------------------------------
-// Device-resident optimiser: one PASS = ndt_pass_kernel (whatever the controller asked for: derivatives with or without
-// the Hessian, or computeHessian, at the pose it left in NdtCtl) + ndt_fold_ctl_kernel (fold of the partial sums and one step
-// of the state machine of ndt_opt.h).  The host enqueues passes ahead of the device and only watches a progress word; passes
-// enqueued beyond the end of the optimisation return at once.
+// Device-resident optimiser: one PASS evaluates whatever the controller asked for (derivatives with or without the Hessian,
+// or computeHessian, at the pose it left in NdtCtl), folds the partial sums and takes one step of the state machine of
+// ndt_opt.h.  The host enqueues passes ahead of the device and only watches a progress word; passes enqueued beyond the end
+// of the optimisation return at once.  ndt_pass_kernel is the evaluation alone (the sharded loops below).
 // ------------------------------------------------------------------------------
 __global__ __launch_bounds__(kNdtBlock, 2) void ndt_pass_kernel(const NdtArgs a, const NdtCtl* __restrict__ ctl) {
     __shared__ double sh[kNdtChunk * kNdtStride];
@@ -677,103 +677,10 @@ __global__ __launch_bounds__(512) void ndt_ctl_store_kernel(NdtCtl* __restrict__
 }
 
 static constexpr int kCtlWords = (int)((sizeof(NdtCtl) + 3) / 4);
-// One block of 768 threads.  Fold: a line-search pass carries 7 sums (score + gradient), the others 43; the threads are laid
-// out as [slice][component] with 8 or 48 components per slice, so that the 7-sum fold is a single round of loads (96 slices x
-// 11 blocks) instead of eight.  Controller: thread 0 takes the decisions (ndt_opt::ctl_decide), six lanes evaluate the six
-// sine/cosine pairs of the new pose at once, thread 0 fills the tables.
-__global__ __launch_bounds__(768) void ndt_fold_ctl_kernel(const double* __restrict__ partials, uint32_t nblocks, NdtCtl* __restrict__ ctl,
-                                                           const GridHeader* __restrict__ hdr, NdtOut* __restrict__ out, double seq, const uint32_t* __restrict__ roi_escapes) {
-    __shared__ double sh[96 * 8];                // = 16 * 48
-    __shared__ double sh_sums[48];
-    __shared__ double sh_sc[12];
-    __shared__ int sh_need;
-    __shared__ __attribute__((aligned(16))) uint32_t sh_ctl[kCtlWords];
-    const unsigned long long t_in = wall_clock64();
-    const int t = threadIdx.x;
-    // Everything this kernel needs from memory is requested in ONE round trip: the controller's state, and -- on the guess that this was
-    // a line-search pass, which ten of thirteen are -- the 7 sums of every block in the [96 slices][8 components] layout.
-    const int compL = t & 7, sliceL = t >> 3;
-    double vL[12];
-#pragma unroll
-    for (int u = 0; u < 12; ++u) { const uint32_t b = (uint32_t)(sliceL + 96 * u); vL[u] = b < nblocks ? partials[(size_t)b * 48 + compL] : 0.0; }
-    // the controller's state to LDS (thread 0 then works at LDS latency instead of one memory round trip per field)
-    for (int w = t; w < kCtlWords; w += 768) sh_ctl[w] = reinterpret_cast<const uint32_t*>(ctl)[w];
-    const int done = ctl->done, kind = ctl->kind;
-#pragma unroll
-    for (int u = 0; u < 12; ++u) asm volatile("" ::"v"(vL[u]));      // (keeps the speculative loads above the branches below)
-    if (done) return;                            // a pass enqueued beyond the end
-    const bool light = kind == kNdtPassDeriv;
-    const int cw = light ? 8 : 48, ns = 768 / cw;             // components per slice, slices
-    const int comp = t % cw, slice = t / cw;
-    double acc = 0.0;
-    if (light) {
-#pragma unroll
-        for (int u = 0; u < 12; ++u) acc += vL[u];
-    } else {
-        for (uint32_t b0 = slice; b0 < nblocks; b0 += (uint32_t)ns * 12u) {
-            double v[12];
-#pragma unroll
-            for (int u = 0; u < 12; ++u) { const uint32_t b = b0 + (uint32_t)(ns * u); v[u] = b < nblocks ? partials[(size_t)b * 48 + comp] : 0.0; }
-#pragma unroll
-            for (int u = 0; u < 12; ++u) acc += v[u];
-        }
-    }
-    sh[slice * cw + comp] = acc;
-    __syncthreads();
-    if (t < 48) {
-        double v = 0.0;
-        if (t < cw) {
-            v = sh[t];
-            for (int s2 = 1; s2 < ns; ++s2) v += sh[s2 * cw + t];
-        }
-        sh_sums[t] = v;                          // (a light pass leaves the Hessian slots at zero: ctl_decide does not read them)
-    }
-    __syncthreads();
-    unsigned long long t_a = 0;
-    if (t == 0) {
-        t_a = wall_clock64();
-        sh_need = ndt_opt::ctl_decide(reinterpret_cast<NdtCtl*>(sh_ctl), sh_sums) ? 1 : 0;
-        reinterpret_cast<NdtCtl*>(sh_ctl)->ticks[2] += (uint32_t)(wall_clock64() - t_a);
-    }
-    __syncthreads();
-    if (sh_need) {
-        if (t < 6) {
-            double sc[2];
-            ndt_opt::trig_pair(reinterpret_cast<const NdtCtl*>(sh_ctl)->x_t, t, sc);
-            sh_sc[2 * t] = sc[0]; sh_sc[2 * t + 1] = sc[1];
-        }
-        __syncthreads();
-        if (t == 0) {
-            const unsigned long long t_c = wall_clock64();
-            ndt_opt::ctl_tables(reinterpret_cast<NdtCtl*>(sh_ctl), sh_sc);
-            reinterpret_cast<NdtCtl*>(sh_ctl)->ticks[3] += (uint32_t)(wall_clock64() - t_c);
-        }
-    }
-    if (t == 0) {
-        NdtCtl* c = reinterpret_cast<NdtCtl*>(sh_ctl);
-        const unsigned long long t_b = wall_clock64();
-        c->ticks[0] += (uint32_t)(t_a - t_in); c->ticks[1] += (uint32_t)(t_b - t_a);
-    }
-    __syncthreads();
-    for (int w = t; w < kCtlWords; w += 768) reinterpret_cast<uint32_t*>(ctl)[w] = sh_ctl[w];
-    if (t == 0) {
-        const NdtCtl* c = reinterpret_cast<const NdtCtl*>(sh_ctl);
-        if (c->done) {
-            out->final_T = c->final_T; out->score = c->score;
-            out->conv = c->conv; out->nr_it = c->nr_it; out->n_deriv = c->n_deriv; out->n_hess = c->n_hess; out->bail = c->bail; out->passes = c->passes;
-            for (int i = 0; i < 4; ++i) out->ticks[i] = c->ticks[i];
-            out->grid_overflow = hdr->overflow; out->grid_empty = hdr->empty; out->grid_stale = hdr->stale; out->roi_escapes = roi_escapes ? (int32_t)min(*roi_escapes, 0x7fffffffu) : 0; out->grid_cells = hdr->n_cells;
-            __threadfence_system();
-            __hip_atomic_store(&out->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        } else {
-            __hip_atomic_store(&out->progress, seq * kProgressWindow + (double)c->passes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-}
 
 // ------------------------------------------------------------------------------
-// One launch per pass (the unsharded device loop).  A launch on this stream costs ~5 us of device time whatever it does, and the
-// fold/controller kernel above is a second one per pass: here its work is the PROLOGUE of the next pass instead -- every block
+// One launch per pass (the unsharded device loop).  A launch on this stream costs ~5 us of device time whatever it does, and a
+// fold/controller kernel would be a second one per pass: here its work is the PROLOGUE of the next pass instead -- every block
 // folds the rows of the previous launch and takes the controller step itself (same instructions on the same numbers: the blocks
 // agree to the bit, as loam_iterate_kernel's do), block 0 writes the new state and the progress word.  So that a block needs
 // 256 rows and not 1024, the blocks are 512 threads, one per CU.  State and rows are double-buffered by launch parity: launch k
@@ -822,7 +729,6 @@ __global__ __launch_bounds__(kProBlock, 1) void ndt_pass_pro_kernel(const NdtArg
     __shared__ double sh_sums[48];
     __shared__ double sh_sc[12];
     __shared__ int sh_need;
-    const unsigned long long t_in = wall_clock64();
     const int t = threadIdx.x;
     NdtCtl* const c = reinterpret_cast<NdtCtl*>(sh_ctl);
     // ONE round trip: the state and the rows of the previous launch, in the [10 slices][48 components] layout whatever that launch was
@@ -862,15 +768,10 @@ __global__ __launch_bounds__(kProBlock, 1) void ndt_pass_pro_kernel(const NdtArg
             sh_sums[t] = r;      // (a light pass leaves the Hessian slots at zero: ctl_decide does not read them)
         }
         __syncthreads();
-        unsigned long long t_a = 0;
         // the pass's 36 Hessian entries are taken in by lanes 1..36 of the wave whose lane 0 decides (same wave: their LDS stores are queued before
         // lane 0's loads of the Newton solve)
         if (t >= 1 && t <= 36) c->hess[t - 1] = ndt_opt::ctl_hess_entry(c->kind, c->phase, sh_sums, t - 1);
-        if (t == 0) {
-            t_a = wall_clock64();
-            sh_need = ndt_opt::ctl_decide(c, sh_sums, true) ? 1 : 0;
-            c->ticks[2] += (uint32_t)(wall_clock64() - t_a);
-        }
+        if (t == 0) sh_need = ndt_opt::ctl_decide(c, sh_sums, true) ? 1 : 0;
         __syncthreads();
         if (sh_need) {
             if (t < 6) {
@@ -880,7 +781,6 @@ __global__ __launch_bounds__(kProBlock, 1) void ndt_pass_pro_kernel(const NdtArg
             }
             __syncthreads();
             // pose and the four parts of the angle tables: five waves, one lane each
-            const unsigned long long t_c = wall_clock64();
             if ((t & 63) == 0) {
                 const int wave = t >> 6;
                 if (wave == 0) ndt_opt::pose_from_trig(c->x_t, sh_sc, &c->T);
@@ -890,11 +790,6 @@ __global__ __launch_bounds__(kProBlock, 1) void ndt_pass_pro_kernel(const NdtArg
                 else if (wave == 4) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 3);
             }
             __syncthreads();
-            if (t == 0) c->ticks[3] += (uint32_t)(wall_clock64() - t_c);
-        }
-        if (t == 0) {
-            const unsigned long long t_b = wall_clock64();
-            c->ticks[0] += (uint32_t)(t_a - t_in); c->ticks[1] += (uint32_t)(t_b - t_a);
         }
         __syncthreads();
         if (blockIdx.x == 0) {
@@ -905,7 +800,6 @@ __global__ __launch_bounds__(kProBlock, 1) void ndt_pass_pro_kernel(const NdtArg
                     const GridHeader* hdr = a.hdr;
                     out->final_T = c->final_T; out->score = c->score;
                     out->conv = c->conv; out->nr_it = c->nr_it; out->n_deriv = c->n_deriv; out->n_hess = c->n_hess; out->bail = c->bail; out->passes = c->passes;
-                    for (int i = 0; i < 4; ++i) out->ticks[i] = c->ticks[i];
                     out->grid_overflow = hdr->overflow; out->grid_empty = hdr->empty; out->grid_stale = hdr->stale; out->roi_escapes = a.roi_escapes ? (int32_t)min(*a.roi_escapes, 0x7fffffffu) : 0; out->grid_cells = hdr->n_cells;
                     __threadfence_system();
                     __hip_atomic_store(&out->seq, pa.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -935,7 +829,7 @@ __global__ __launch_bounds__(kProBlock, 1) void ndt_pass_pro_kernel(const NdtArg
 
 // ------------------------------------------------------------------------------
 // Sharded targets over RCCL: the sums of a pass have to cross the ranks between the fold and the controller step, so the
-// fold/controller kernel is cut in two around an ncclAllReduce on the same stream -- ndt_fold_kernel (this rank's 48 sums into
+// fold and the controller step are two kernels around an ncclAllReduce on the same stream -- ndt_fold_kernel (this rank's 48 sums into
 // a device buffer), all-reduce, ndt_ctl_kernel (one step of the state machine on the summed values).  Every rank holds the same
 // controller state and feeds it the same sums: the ranks decide alike and stay in step without ever talking about it.
 // ------------------------------------------------------------------------------
@@ -1155,8 +1049,7 @@ static void ndt_initial_ctl(NdtCtl* c, const NdtPose& T0, const double p[6], dou
     static_assert(sizeof(NdtCtl) % 4 == 0, "NdtCtl is copied word by word");
     memset(c, 0, sizeof *c);
     ndt_opt::ctl_init(c, T0, p, step_size, trans_eps, max_iters);
-    static const bool no_replay = dev_env("PCR_NDT_NO_REPLAY") != nullptr;
-    c->replay_off = (no_replay || no_replay_arg) ? 1 : 0;
+    c->replay_off = no_replay_arg ? 1 : 0;
 }
 hipError_t ndt_launch_ctl_init(NdtCtl* d_ctl, const NdtPose& T0, const double p[6], double step_size, double trans_eps, int max_iters, hipStream_t s, int no_replay_arg,
                                uint32_t* d_roi_escapes) {
@@ -1174,12 +1067,6 @@ void ndt_ctl_init_blob(BlobStore* b, NdtCtl* d_ctl, const NdtPose& T0, const dou
     ndt_initial_ctl(&c, T0, p, step_size, trans_eps, max_iters, no_replay_arg);
     memcpy(b->w, &c, sizeof c);
     b->dst = reinterpret_cast<uint32_t*>(d_ctl); b->zero = nullptr; b->n = (uint32_t)(sizeof c / 4); b->pad = 0;
-}
-hipError_t ndt_launch_pass(const NdtArgs& a, NdtCtl* d_ctl, NdtOut* d_out, hipStream_t s, double seq) {
-    const uint32_t nb = ndt_blocks(a.n_src);
-    hipLaunchKernelGGL(ndt_pass_kernel, dim3(nb), dim3(kNdtBlock), 0, s, a, d_ctl);
-    hipLaunchKernelGGL(ndt_fold_ctl_kernel, dim3(1), dim3(768), 0, s, a.partials, nb, d_ctl, a.hdr, d_out, seq, (const uint32_t*)a.roi_escapes);
-    return hipGetLastError();
 }
 // launch `index` of the one-launch-per-pass loop: d_ctl2 = two NdtCtl, d_rows2 = two buffers of kProRows * 48 doubles
 hipError_t ndt_launch_pass_pro(const NdtArgs& a_in, NdtCtl* d_ctl2, double* d_rows2, NdtOut* d_out, hipStream_t s, double seq, int index,

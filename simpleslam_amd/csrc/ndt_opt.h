@@ -6,8 +6,8 @@
 // scan at one pose.  Here the loop is turned inside out: ndt_ctl_step() consumes the sums of the pass that has just run and
 // leaves in NdtCtl what the NEXT pass must evaluate (pose, angle tables, which of the three kernels), or `done`.
 // The same function runs
-//   * on the device, in the single-block kernel that folds a pass's partial sums (ndt.hip: ndt_fold_ctl_kernel), so that an
-//     alignment is a chain of launches with no host round trip;
+//   * on the device, in the prologue of the next pass (ndt.hip: ndt_pass_pro_kernel) or in a kernel after the fold of a pass's partial
+//     sums (the sharded loops), so that an alignment is a chain of launches with no host round trip;
 //   * on the host, for sharded targets, where the sums of every pass cross the ranks through a host collective (capi.hip).
 // Host and device differ in two places, both marked below: the libm behind sin/cos, and the 6x6 Newton solve (the host keeps the
 // restated JacobiSVD::solve; the device eliminates with partial pivoting and hands the call back to the host -- `bail` -- when the
@@ -45,10 +45,9 @@ struct NdtCtl {
     int32_t open_interval, interval_converged, it, nr_it, conv, n_deriv, n_hess, bail;
     NdtPose final_T;
     int32_t done, passes;
-    uint32_t ticks[4];      // profiling: 100 MHz ticks spent in fold / controller step / write-back, summed over the passes
     // ---- the point (score, grad) were last evaluated at: a request for the same sums at the same point is answered from here ----
     double x_eval[6];
-    int32_t eval_valid, replayed, replay_off, need_h;      // need_h: see ctl_advance; replay_off: PCR_NDT_NO_REPLAY (A/B runs): every request becomes a pass
+    int32_t eval_valid, replayed, replay_off, need_h;      // need_h: see ctl_advance; replay_off: pcr_params.ndt_evaluate_repeats: every request becomes a pass
 };
 
 // what the device-resident loop reports to the host (host-mapped memory; `seq` is written last)
@@ -58,7 +57,6 @@ struct NdtOut {
     int32_t conv, nr_it, n_deriv, n_hess, bail, passes, grid_overflow, grid_empty, grid_stale;
     int32_t roi_escapes;    // lookups that hit a qualifying voxel outside the region the target was prepared for (RoiView): > 0 = repeat on the whole target
     uint64_t grid_cells;
-    uint32_t ticks[4];
     double batch;           // sharded device loop: seq * 65536 + 2 * (batches finished) + done, written by the last controller step of a batch
     double progress;        // number of passes consumed so far (written after every pass: the host keeps the queue ahead of it)
     double seq;             // == the call's sequence number once the loop has finished
@@ -327,7 +325,6 @@ NDT_HD inline void ctl_init(NdtCtl* c, const NdtPose& T0, const double p0[6], do
     c->step_min = trans_eps / 2; c->step_max = step_size;
     c->open_interval = 1; c->interval_converged = 0; c->it = 0; c->nr_it = 0; c->conv = 0; c->n_deriv = c->n_hess = 0; c->bail = 0;
     c->done = 0; c->passes = 0;
-    for (int i = 0; i < 4; ++i) c->ticks[i] = 0;
     for (int i = 0; i < 6; ++i) c->x_eval[i] = 0;
     c->eval_valid = 0; c->replayed = 0; c->replay_off = 0; c->need_h = 0;
 }

@@ -11,16 +11,6 @@
 
 #include "../../include/pcr_hip.h"
 
-// Development switches (sweeps, A/B runs, debug prints: PCR_TILE_SHIFT, PCR_BIN_PER, PCR_INDEX_ATOMIC, PCR_INDEX_NO_LAYOUT,
-// PCR_INDEX_DEBUG, PCR_COV_LEVELS, PCR_COV_RATIO, PCR_COV_NO_AHEAD, PCR_NDT_TWO_LAUNCHES, PCR_NDT_TICKS, PCR_NDT_NO_REPLAY, PCR_ABLATE)
-// exist only in a library built with `make DEV=1` (-DPCR_DEV_SWITCHES): the product reads no environment variable, what a caller
-// may select is a named field of pcr_params.
-#ifdef PCR_DEV_SWITCHES
-inline const char* dev_env(const char* name) { return getenv(name); }
-#else
-inline const char* dev_env(const char*) { return nullptr; }
-#endif
-
 namespace pcr {
 
 // ---------------------------------------------------------------------------
@@ -133,8 +123,6 @@ struct LoamArgs {
     double* partials;        // [2][kMaxPartials][kAccum]
     const double* reduced;   // non-null: partial sums already reduced (and all-reduced) into kAccum doubles
     uint32_t n_partials;     // blocks of the linearisation grid
-    uint32_t n_prev;         // rows the PREVIOUS launch wrote (0: n_partials) -- a launch of half blocks writes twice as many
-    uint32_t half;           // this launch: 128 queries per block (the upper half of its threads only helps searching), twice the blocks
     LoamTrace* trace;        // [iters] or null
     LoamResult* result;      // final pose (after T2SE3) and flags
     // optional per-point outputs (tests): null in production
@@ -145,9 +133,6 @@ struct LoamArgs {
     struct NnCacheEntry* nn_cache;   // [n_src] neighbours of the previous iteration (loam.hip), or null
     int32_t use_tile;
     double tile_lo[3], tile_hi[3];
-    // profiling aid (development builds: PCR_ABLATE): skip phases to price them.  bit0: candidate loop,
-    // bit1: plane fit and everything after it, bit2: prologue solve.  Results are then meaningless.
-    int32_t ablate;
     int32_t coresident;      // pcr_params.loam_coresident = 1: the two-waves-per-SIMD variant of the iterate kernel (loam.hip)
     int32_t rank_fail;       // sharded: this rank has no usable index (its grid view is a dummy marked overflow); told to the others
     // profiling aid (pcr_params.record_timeline = 1): [launch][block][kTimelineSlots] s_memrealtime stamps (100 MHz) taken by thread 0
@@ -416,7 +401,6 @@ struct NdtOut;
 hipError_t ndt_launch_ctl_init(NdtCtl* d_ctl, const NdtPose& T0, const double p[6], double step_size, double trans_eps, int max_iters, hipStream_t s, int no_replay = 0,
                                uint32_t* d_roi_escapes = nullptr);
 void ndt_ctl_init_blob(BlobStore* b, NdtCtl* d_ctl, const NdtPose& T0, const double p[6], double step_size, double trans_eps, int max_iters, int no_replay_arg);
-hipError_t ndt_launch_pass(const NdtArgs& a, NdtCtl* d_ctl, NdtOut* d_out, hipStream_t s, double seq);
 hipError_t ndt_launch_pass_pro(const NdtArgs& a, NdtCtl* d_ctl2, double* d_rows2, NdtOut* d_out, hipStream_t s, double seq, int index,
                                hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 hipError_t ndt_launch_pass_fold(const NdtArgs& a, NdtCtl* d_ctl, double* d_sums48, hipStream_t s);
@@ -433,7 +417,7 @@ static constexpr unsigned long long kPeerTimeoutTicks = 200000000ull;      // 2 
 struct PeerComm { double* buf[kMaxPeers]; int32_t rank, nranks; int32_t* status; };      // status: host-mapped word, set to 1 by an exchange that timed out (out of band: the sums may hold any value, NaN included)
 hipError_t loam_launch_peer_exchange(const LoamArgs& a, int k, const PeerComm& pc, double seq, double* d_out, hipStream_t s);
 hipError_t peer_launch_allreduce(double* d_inout, int n, int op, const PeerComm& pc, double seq, hipStream_t s);
-hipError_t loam_launch_iteration(const LoamArgs& a, int k, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr, bool allow_half = false);
+hipError_t loam_launch_iteration(const LoamArgs& a, int k, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 hipError_t loam_launch_finalize(const LoamArgs& a, int k, hipStream_t s);
 hipError_t loam_launch_reduce(const LoamArgs& a, int k, double* d_out, hipStream_t s);
 uint32_t loam_grid_blocks(uint32_t n_src);

@@ -383,7 +383,6 @@ __global__ __launch_bounds__(256) void vgicp_pass_pro_kernel(const VgicpArgs a_i
     __shared__ double sh_sum[8 * 32];
     __shared__ __attribute__((aligned(16))) uint32_t sh_ctl[kVgCtlWords];
     __shared__ double sh_sums[32];
-    const unsigned long long t_in = wall_clock64();
     const int t = threadIdx.x;
     VgCtl* const c = reinterpret_cast<VgCtl*>(sh_ctl);
     // one round trip: the state and the rows of the previous launch ([8 slices][32 components], 32 rows a thread for <= 256 rows)
@@ -428,11 +427,7 @@ __global__ __launch_bounds__(256) void vgicp_pass_pro_kernel(const VgicpArgs a_i
             sh_sums[t] = s;
         }
         __syncthreads();
-        if (t == 0) {
-            const unsigned long long t_a = wall_clock64();
-            vg_opt::ctl_step(c, sh_sums);
-            c->ticks[0] += (uint32_t)(t_a - t_in); c->ticks[1] += (uint32_t)(wall_clock64() - t_a);
-        }
+        if (t == 0) vg_opt::ctl_step(c, sh_sums);
         __syncthreads();
         if (blockIdx.x == 0) {
             for (int w = t; w < kVgCtlWords; w += 256) reinterpret_cast<uint32_t*>(pa.ctl_next)[w] = sh_ctl[w];
@@ -604,9 +599,7 @@ __global__ __launch_bounds__(256) void fitness_kernel(GridView g, const float* _
 // ---- host launchers ---------------------------------------------------------------
 hipError_t vgicp_launch_cov(const GridIndex& grid, const GridIndex* coarse1, const GridIndex* coarse2, const float* d_orig, size_t stride_floats,
                             size_t n, double* d_cov6, hipStream_t s, const CovCheck* check, const RoiView* roi, CovScratch* scratch, hipEvent_t* ev) {
-    static const bool old_kernel = dev_env("PCR_COV_OLD") != nullptr;      // (development builds: A/B against the lane-per-query kernel)
-    static const bool all_sizes = dev_env("PCR_COV_NEW_ALL") != nullptr;      // (development builds: map-sized clouds through cov_search.hip too)
-    if (scratch && (n <= 300000 || all_sizes) && n > 0 && !old_kernel) {      // scan-sized: two classes of queries (cov_search.hip)
+    if (scratch && n <= 300000 && n > 0) {      // scan-sized: two classes of queries (cov_search.hip)
         const hipError_t e = scratch->reserve(n);
         return e != hipSuccess ? e : cov_search_launch(grid, coarse1, coarse2, d_orig, stride_floats, n, d_cov6, s, check, roi, *scratch, ev);
     }
@@ -623,8 +616,7 @@ hipError_t vgicp_launch_cov(const GridIndex& grid, const GridIndex* coarse1, con
     const uint32_t* d_list = nullptr;
     const uint32_t* d_list_count = nullptr;
     int cov_blocks = blocks;
-    static const bool no_list = dev_env("PCR_COV_NO_LIST") != nullptr;      // (development builds: A/B)
-    if (n > 300000 && roi && roi->mask && scratch && !check && !no_list) {
+    if (n > 300000 && roi && roi->mask && scratch && !check) {
         const hipError_t e = scratch->reserve_region(n, s);
         if (e != hipSuccess) return e;
         scratch->region_idx ^= 1;

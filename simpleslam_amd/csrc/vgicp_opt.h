@@ -37,7 +37,6 @@ struct VgCtl {
     int32_t max_iters, lm_inner;
     int32_t kind, it, inner, parity;      // parity: which of the two correspondence buffers belongs to x0
     int32_t conv, done, passes, n_lin, n_err, outer;
-    uint32_t ticks[2];
 };
 
 // what the device-resident loop reports (host-mapped memory; `seq` is written last)
@@ -113,7 +112,6 @@ VG_HD void ctl_init(VgCtl* c, const Pose16& guess, int max_iters, int lm_inner, 
     c->max_iters = max_iters; c->lm_inner = lm_inner;
     c->kind = kVgPassLinearize; c->it = 0; c->inner = 0; c->parity = 0;
     c->conv = 0; c->done = max_iters <= 0 ? 1 : 0; c->passes = 0; c->n_lin = c->n_err = 0; c->outer = 0;
-    c->ticks[0] = c->ticks[1] = 0;
 }
 
 // one LM trial from the linearisation in c->lin: (H + lambda I) d = -b, delta = [so3_exp(d[0:3]); d[3:6]], xi = delta * x0   (:130-140)

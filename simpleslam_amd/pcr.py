@@ -20,7 +20,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PCR_LIB (read HERE, by the Python loader -- the library itself reads no environment variable): another build of the library to load instead of the
-# product, e.g. the development build ab/libdev.so of scripts/build_dev.sh.  The A/B and sweep scripts set it; nothing overwrites lib/libpcr_hip.so.
+# product, e.g. a variant ab/lib<tag>.so under A/B.  The A/B scripts set it; nothing overwrites lib/libpcr_hip.so.
 LIB_PATH = os.environ.get("PCR_LIB") or os.path.join(_HERE, "lib", "libpcr_hip.so")
 
 
