@@ -12,10 +12,14 @@
  * vector for it.  Restated from the published algorithm, PCL 1.10 filters/include/pcl/filters/impl/voxel_grid.hpp
  * (VoxelGrid<PointT>::applyFilter) and common/include/pcl/common/impl/accumulators.hpp (CentroidPoint):
  *   getMinMax3D over the finite points; inverse_leaf_size = 1 / leaf (float);
- *   min_b = floor(min_p * inv), max_b = floor(max_p * inv), div_b = max_b - min_b + 1; (dx*dy*dz) > INT_MAX -> warning
- *   and output = input; per finite point ijk = (int)(floor(p * inv) - (float)min_b),
- *   idx = ijk0 + ijk1 * div_b0 + ijk2 * div_b0 * div_b1; sort by idx; one CentroidPoint per run of equal idx:
- *   float sums of xyz and intensity in the order the sort left the points in, divided by the count (as float).
+ *   the too-fine test d = (int64)((max_p - min_p) * inv) + 1 per axis, in float, and dx * dy * dz > INT_MAX -> warning and
+ *   output = input (the reference's own copy of that test: third_parties/pclomp/src/voxel_grid_covariance_omp_impl.hpp:74-79;
+ *   it is NOT the lattice's count below, which can be one more per axis);
+ *   min_b = floor(min_p * inv), max_b = floor(max_p * inv), div_b = max_b - min_b + 1; per finite point
+ *   ijk = (int)(floor(p * inv) - (float)min_b), idx = ijk0 + ijk1 * div_b0 + ijk2 * div_b0 * div_b1; sort by idx; one CentroidPoint
+ *   per run of equal idx: float sums of xyz and intensity in the order the sort left the points in, divided by the count (as float).
+ * idx is formed in 64 bits here: just under PCL's limit div_b0 * div_b1 * div_b2 can exceed INT_MAX, where PCL's int idx wraps.
+ * What PCL's output order is then is not observable without PCL; this file keeps the ascending order of the true index.
  * PCL's std::sort is not stable, so the order inside a voxel -- and with it the last bits of the float sums -- is
  * unspecified there; this file uses input order (a stable sort), one of the admissible outcomes.
  */
@@ -26,7 +30,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-typedef struct { int idx; uint32_t pt; } vox_ref;
+typedef struct { int64_t idx; uint32_t pt; } vox_ref;
 
 static int cmp_ref(const void *a, const void *b)
 {
@@ -51,28 +55,33 @@ int oracle_voxel_filter(const float *pts, size_t n, size_t stride, float leaf, f
     }
     if (!n_fin) return 0;
     const float inv = 1.0f / leaf;
-    int min_b[3], div_b[3];
-    double cells = 1.0;
+    /* "Leaf size is too small for the input dataset": PCL's count, (int64)((max - min) * inv) + 1 in float (a span of 2^63 or
+     * more -- an infinite one included -- fits no int64 and is too fine by any count) */
+    double pcl_cells = 1.0;
     for (int d = 0; d < 3; ++d) {
-        const float lo = floorf(mn[d] * inv), hi = floorf(mx[d] * inv);
-        cells *= (double)hi - (double)lo + 1.0;
-        min_b[d] = fabsf(lo) < 2.0e9f ? (int)lo : 0;
-        div_b[d] = (double)hi - (double)lo + 1.0 < 2.0e9 ? (int)((double)hi - (double)lo + 1.0) : INT_MAX;
+        const float span = (mx[d] - mn[d]) * inv;
+        pcl_cells *= span < 9.2e18f ? (double)((int64_t)span + 1) : INFINITY;
     }
-    if (cells > (double)INT_MAX) {          /* "Leaf size is too small for the input dataset" */
+    if (pcl_cells > (double)INT_MAX) {
         *n_out = n;
         if (cap < n) return 2;
         memcpy(out, pts, n * stride * sizeof(float));
         return 1;
+    }
+    float min_f[3];      /* floor(min_p * inv): (float)min_b of voxel_grid.hpp */
+    int64_t div_b[3];
+    for (int d = 0; d < 3; ++d) {
+        min_f[d] = floorf(mn[d] * inv);
+        div_b[d] = (int64_t)floorf(mx[d] * inv) - (int64_t)min_f[d] + 1;
     }
     vox_ref *ref = (vox_ref *)malloc(sizeof(vox_ref) * n_fin);
     size_t m = 0;
     for (size_t i = 0; i < n; ++i) {
         const float *p = pts + i * stride;
         if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]))) continue;
-        const int i0 = (int)(floorf(p[0] * inv) - (float)min_b[0]);
-        const int i1 = (int)(floorf(p[1] * inv) - (float)min_b[1]);
-        const int i2 = (int)(floorf(p[2] * inv) - (float)min_b[2]);
+        const int64_t i0 = (int64_t)(floorf(p[0] * inv) - min_f[0]);
+        const int64_t i1 = (int64_t)(floorf(p[1] * inv) - min_f[1]);
+        const int64_t i2 = (int64_t)(floorf(p[2] * inv) - min_f[2]);
         ref[m].idx = i0 + i1 * div_b[0] + i2 * div_b[0] * div_b[1];
         ref[m].pt = (uint32_t)i;
         ++m;

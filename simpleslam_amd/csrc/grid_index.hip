@@ -112,7 +112,23 @@ __global__ __launch_bounds__(256) void grid_bbox_header_kernel(const float* __re
         h.pcl_mode = pcl_mode; h.inv_leaf_f = 1.0f / (float)cell; h.too_fine = 0; h.sum_sq = 0.f; h.sum_sq_u = 0ull;
         h.min_b[0] = h.min_b[1] = h.min_b[2] = 0;
         h.clamped = (clamp.use && !pcl_mode) ? 1 : 0; h.cut_mask = 0; h.stale = 0; h.pad2_ = 0;
-        double nc = 1.0, nc_tight = 1.0;      // (nc_tight: cells of the box WITHOUT the room left for the next cloud -- pcl's own count)
+        double nc = 1.0, nc_tight = 1.0;      // (nc_tight: pcl::VoxelGrid's own count of the box, for its too-fine test)
+        int mg_xy = margin_xy, mg_z = margin_z_pcl;
+        if (pcl_mode) {
+            // voxel_grid.hpp's too-fine test counts (int64)((max_p - min_p) * inverse_leaf_size) + 1 per axis, in float: NOT the lattice's
+            // floor(max_p * inv) - floor(min_p * inv) + 1, which can be one more per axis.  The room left for the next cloud is dropped when the
+            // padded box would need more cells than a dense table may hold while the box itself does not (a flat or thin cloud: 16 cells of
+            // margin in x and y multiply a one-voxel-thick box by 9 in z)
+            double padded = 1.0;
+            for (int d = 0; d < 3; ++d) {
+                const float lo = fminf(fminf(sh[0][d], sh[1][d]), fminf(sh[2][d], sh[3][d]));
+                const float hi = fmaxf(fmaxf(sh[0][3 + d], sh[1][3 + d]), fmaxf(sh[2][3 + d], sh[3][3 + d]));
+                if (!(lo <= hi)) continue;
+                nc_tight *= (double)truncf((hi - lo) * h.inv_leaf_f) + 1.0;
+                padded *= (double)floorf(hi * h.inv_leaf_f) - (double)floorf(lo * h.inv_leaf_f) + 1.0 + 2.0 * (d < 2 ? mg_xy : mg_z);
+            }
+            if (padded > 4.0e9) mg_xy = mg_z = 0;
+        }
         for (int d = 0; d < 3; ++d) {
             float lo = fminf(fminf(sh[0][d], sh[1][d]), fminf(sh[2][d], sh[3][d]));
             float hi = fmaxf(fmaxf(sh[0][3 + d], sh[1][3 + d]), fmaxf(sh[2][3 + d], sh[3][3 + d]));
@@ -126,10 +142,9 @@ __global__ __launch_bounds__(256) void grid_bbox_header_kernel(const float* __re
             if (pcl_mode) {
                 // pcl::VoxelGrid::applyFilter: min_b = floor(min_p * inverse_leaf_size), float arithmetic throughout
                 float flo = floorf(lo * h.inv_leaf_f), fhi = floorf(hi * h.inv_leaf_f);
-                nc_tight *= (double)fhi - (double)flo + 1.0;
                 // (after a hint has failed: voxel membership does not depend on where the lattice starts, and neither does the ORDER of the voxels -- idx sorts
                 //  by (z, y, x) whatever the box: NDT pads x and y, the voxel filter z as well)
-                const int mg = d < 2 ? margin_xy : margin_z_pcl;
+                const int mg = d < 2 ? mg_xy : mg_z;
                 if (!h.empty && mg) { flo -= (float)mg; fhi += (float)mg; }
                 const double dim = (double)fhi - (double)flo + 1.0;
                 h.min_b[d] = fabsf(flo) < 2.0e9f ? (int32_t)flo : 0;
@@ -149,7 +164,7 @@ __global__ __launch_bounds__(256) void grid_bbox_header_kernel(const float* __re
             h.dims[d] = dim < 2.0e9 ? (int32_t)dim : 0x7fffffff;
             nc *= dim;
         }
-        if (pcl_mode && nc_tight > 2147483647.0) h.too_fine = 1;      // (dx*dy*dz) > INT_MAX
+        if (pcl_mode && nc_tight > 2147483647.0) h.too_fine = 1;      // (dx*dy*dz) > INT_MAX: an infinite span included
         // keys are uint32 and the table holds n_cells + 1 starts
         if (h.too_fine) { h.overflow = 0; h.empty = 1; h.n_cells = 1; }      // nothing is indexed; the caller copies its input
         else if (nc + 1.0 > (double)capacity || nc > 4.0e9) { h.overflow = 1; h.n_cells = nc < 1.8e19 ? (uint64_t)nc : ~0ull; }
