@@ -56,6 +56,25 @@ struct Rccl {
 Rccl g_rccl;
 std::mutex g_rccl_mu;
 
+// A block of `count` T in host-mapped memory, which kernels write through `dev` and the host reads at `host`: allocated and
+// zeroed on first use, freed with its owner.
+template <class T> struct Mapped {
+    T* host = nullptr;
+    T* dev = nullptr;
+    Mapped() = default;
+    Mapped(const Mapped&) = delete;
+    Mapped& operator=(const Mapped&) = delete;
+    ~Mapped() { if (host) (void)hipHostFree(host); }
+    hipError_t ensure(size_t count = 1) {
+        if (host) return hipSuccess;
+        hipError_t e = hipHostMalloc((void**)&host, count * sizeof(T), hipHostMallocMapped);
+        if (e != hipSuccess) { host = nullptr; return e; }
+        memset(host, 0, count * sizeof(T));
+        if ((e = hipHostGetDevicePointer((void**)&dev, host, 0)) != hipSuccess) { (void)hipHostFree(host); host = dev = nullptr; }
+        return e;
+    }
+};
+
 }  // namespace
 
 struct pcr_handle {
@@ -84,8 +103,7 @@ struct pcr_handle {
 
     // LOAM work memory
     DeviceBuf loam_state, loam_partials, loam_trace, loam_reduced, dbg_status, dbg_rows, dbg_nn, nn_cache, timeline;
-    LoamResult* result_host = nullptr;   // host-mapped, written by the finalize kernel
-    LoamResult* result_dev = nullptr;
+    Mapped<LoamResult> result;           // written by the finalize kernel
     std::vector<LoamTrace> trace_host;
     int trace_iters = 0;
 
@@ -105,8 +123,7 @@ struct pcr_handle {
     DeviceBuf tgt_cov6, src_cov6, vox, corr_slot, corr_M, corr_slot2, corr_M2, vg_partials;
     CovScratch src_scratch, tgt_scratch;   // neighbour lists + queue of the covariance search of a scan-sized cloud: the source's runs on the side stream beside the target's
     double seq = 0.0;                    // completion numbers of the host-mapped result blocks below
-    double* out32_host = nullptr;        // host-mapped: 32 doubles written by sum_partials_kernel
-    double* out32_dev = nullptr;
+    Mapped<double> out32;                // 32 doubles written by sum_partials_kernel
     bool vg_target_ready = false;
     int vg_outer = 0, vg_lin = 0, vg_err = 0;
     DeviceBuf vg_ctl;                    // two VgCtl: the device-resident LM loop's state, by launch parity
@@ -117,21 +134,18 @@ struct pcr_handle {
     size_t fit_n = 0, fit_stride = 0;
     double fit_pose[16];
     bool fit_pending = false;
-    VgOut* vg_out_host = nullptr;        // host-mapped: its result and progress word
-    VgOut* vg_out_dev = nullptr;
+    Mapped<VgOut> vg_out;                // its result and progress word
 
     // NDT work memory
     DeviceBuf nd_slot, nd_vox, nd_count, nd_list, nd_partials;
-    double* out48_host = nullptr;        // host-mapped: 48 doubles written by ndt_sum_partials_kernel
-    double* out48_dev = nullptr;
+    Mapped<double> out48;                // 48 doubles written by ndt_sum_partials_kernel
     DeviceBuf nd_ctl;                    // NdtCtl: the device-resident optimiser's state
     struct VfJob { const float* d_pts; size_t n, sf; double leaf; float* d_out; size_t cap; } vf_job = {};      // the filter that is queued (vf_enqueue / vf_settle)
     bool vf_inflight = false; size_t vf_inflight_n = 0;      // pcr_voxel_filter_begin has queued a filter that pcr_voxel_filter_end has not collected
     char* vf_ret = nullptr;              // page-locked: what the voxel filter's last block reports (VfResult: the voxel count + the index header's verdict)
     DeviceBuf vg_reduced;                // sharded VGICP over the peer exchange: a pass's 32 sums folded over the rows and the ranks
     DeviceBuf nd_sums;                   // sharded device loop: the 48 sums of a pass, all-reduced in place
-    NdtOut* nd_out_host = nullptr;       // host-mapped: its result and progress word
-    NdtOut* nd_out_dev = nullptr;
+    Mapped<NdtOut> nd_out;               // its result and progress word
     bool clamp_from_bulk = false;        // pcr_set_target in progress: an untabulatable box may be cut to the bulk of the target
     uint64_t map_id = 0, map_gen = 0;    // pcr_scan2map_submap: the sub-map the target structures were built from
     long long target_builds = 0;         // ... and how often it had to build them
@@ -154,15 +168,13 @@ struct pcr_handle {
     bool peer_on = false;
     bool peer_exported = false;      // pcr_comm_peer_export has cleared the receive buffer for a session that pcr_comm_init_peer has not opened yet
     bool peer_broken = false;        // an exchange of the session timed out: the ranks' sequence numbers no longer agree, every further exchange is refused
-    int32_t* peer_status_host = nullptr;      // host-mapped: set by a kernel whose exchange timed out
-    int32_t* peer_status_dev = nullptr;
+    Mapped<int32_t> peer_status;     // set by a kernel whose exchange timed out
     PeerComm peer{};
     double peer_seq = 0.0;
     pcr_allreduce_fn host_ar = nullptr;     // or the caller's collective (pcr_comm_init_host)
     void* host_ar_user = nullptr;
     int nranks = 1, rank = 0;
-    double* red_host = nullptr;      // host-mapped, kAccum doubles: the LOAM sums on their way through the caller's collective
-    double* red_dev = nullptr;
+    Mapped<double> red;              // kAccum doubles: the LOAM sums on their way through the caller's collective
     DeviceBuf ar_stage;              // RCCL: staging of the 48 doubles the host-driven optimisers exchange
     DeviceBuf dummy_grid;            // a GridHeader marked overflow + empty: the grid view of a rank whose index failed
     DeviceBuf cov_viol;              // VGICP halo check: number of neighbourhoods that reach past the halo
@@ -209,7 +221,7 @@ void peer_close(pcr_handle* h) {
 // before an exchange is queued / after its results have arrived: a session in which an exchange timed out is over
 int peer_check(pcr_handle* h) {
     if (!h->peer_on) return 0;
-    if (h->peer_status_host && __atomic_load_n(h->peer_status_host, __ATOMIC_ACQUIRE) != 0) h->peer_broken = true;
+    if (h->peer_status.host && __atomic_load_n(h->peer_status.host, __ATOMIC_ACQUIRE) != 0) h->peer_broken = true;
     if (h->peer_broken)
         return fail(h, "peer exchange: a rank did not arrive within 2 s; the session is over (the ranks' sequence numbers no longer agree): "
                        "pcr_comm_peer_export + pcr_comm_init_peer on every rank start a new one");
@@ -247,6 +259,22 @@ int prof_end(pcr_handle* h) {
         h->stats.kernel_launches = h->nd_prof_launches;
     }
     return 0;
+}
+// the call's times from the events recorded at its start, after its target index and at its end (profiling level >= 1)
+int read_call_times(pcr_handle* h) {
+    float ms = 0;
+    H_TRY(hipEventElapsedTime(&ms, h->ev_start, h->ev_end)); h->stats.total_ms = ms;
+    H_TRY(hipEventElapsedTime(&ms, h->ev_start, h->ev_index)); h->stats.index_ms = ms;
+    H_TRY(hipEventElapsedTime(&ms, h->ev_index, h->ev_end)); h->stats.solve_ms = ms;
+    return 0;
+}
+// ... the end of a timed NDT / VGICP scan2map call: its end recorded and waited for, its times and counters read
+int end_timed_call(pcr_handle* h) {
+    if (h->profile < 1) return 0;
+    H_TRY(hipEventRecord(h->ev_end, h->stream));
+    H_TRY(hipEventSynchronize(h->ev_end));
+    if (read_call_times(h)) return 1;
+    return prof_end(h);
 }
 
 // Combine n (<= 64) doubles held in host memory over the ranks of a sharded handle, in place: the caller's collective, or RCCL
@@ -301,14 +329,8 @@ int ensure_loam_buffers(pcr_handle* h) {
     H_TRY(h->loam_reduced.reserve(kAccum * sizeof(double)));
     const int iters = std::max(1, h->prm.loam_iters);
     if (h->prm.record_trace) H_TRY(h->loam_trace.reserve((size_t)iters * sizeof(LoamTrace)));
-    if (!h->result_host) {
-        H_TRY(hipHostMalloc((void**)&h->result_host, sizeof(LoamResult), hipHostMallocMapped));
-        H_TRY(hipHostGetDevicePointer((void**)&h->result_dev, h->result_host, 0));
-    }
-    if (h->host_ar && !h->red_host) {
-        H_TRY(hipHostMalloc((void**)&h->red_host, kAccum * sizeof(double), hipHostMallocMapped));
-        H_TRY(hipHostGetDevicePointer((void**)&h->red_dev, h->red_host, 0));
-    }
+    H_TRY(h->result.ensure());
+    if (h->host_ar) H_TRY(h->red.ensure(kAccum));
     return 0;
 }
 
@@ -326,7 +348,7 @@ void fill_loam_args(pcr_handle* h, LoamArgs* a, const float* d_src, size_t n_src
     a->n_partials = loam_grid_blocks((uint32_t)n_src);
     h->last_blocks = a->n_partials;
     a->trace = h->prm.record_trace ? h->loam_trace.as<LoamTrace>() : nullptr;
-    a->result = h->result_dev;
+    a->result = h->result.dev;
     a->coresident = h->prm.loam_coresident == 1;
     if (h->prm.loam_disable_cache == 0 && h->nn_cache.reserve((n_src + 1) * 192) == hipSuccess) a->nn_cache = (NnCacheEntry*)h->nn_cache.p;
     if (h->prm.record_timeline == 1 && h->timeline.reserve((size_t)(std::max(1, h->prm.loam_iters) + 1) * kMaxPartials * kTimelineSlots * sizeof(unsigned long long)) == hipSuccess)
@@ -486,8 +508,8 @@ int run_loam(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floa
             a.grid.cell_start = reinterpret_cast<const uint32_t*>(h->dummy_grid.as<char>() + 512);
             a.rank_fail = 1; a.nn_cache = nullptr;
         }
-        if (shard) a.reduced = h->host_ar ? h->red_dev : h->loam_reduced.as<double>();
-        h->result_host->pad = 0;
+        if (shard) a.reduced = h->host_ar ? h->red.dev : h->loam_reduced.as<double>();
+        h->result.host->pad = 0;
         if (h->profile >= 1 && !index_timed) { H_TRY(hipEventRecord(h->ev_start, h->stream)); H_TRY(hipEventRecord(h->ev_index, h->stream)); }
         const bool per_kernel = h->profile >= 2;
         if (per_kernel) {
@@ -499,7 +521,7 @@ int run_loam(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floa
         // instead of queueing all of them: a loop that ends after launch 2 costs four launches, not eight.  Without early exit (BASELINE's ten fixed
         // iterations), sharded, or timed per kernel: everything is queued at once, as before.
         const bool paced = a.c.early_exit != 0 && !shard && !per_kernel && iters > 3;
-        volatile int32_t* const progress = &h->result_host->progress;
+        volatile int32_t* const progress = &h->result.host->progress;
         *progress = -1;
         int launched = 0;
         for (int k = 0; k < iters; ++k) {
@@ -514,9 +536,9 @@ int run_loam(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floa
             else H_TRY(loam_launch_iteration(a, k, h->stream));
             if (h->host_ar) {
                 // the caller's collective: sums to the host, through fn, back (one host round trip per linearisation)
-                H_TRY(loam_launch_reduce(a, k, h->red_dev, h->stream));
+                H_TRY(loam_launch_reduce(a, k, h->red.dev, h->stream));
                 H_TRY(hipStreamSynchronize(h->stream));
-                if (ranks_allreduce(h, h->red_host, kAccum)) return 1;
+                if (ranks_allreduce(h, h->red.host, kAccum)) return 1;
             } else if (h->peer_on) {
                 // fold + push to every peer + fold what arrived, one launch (the sums never leave the device)
                 h->peer_seq += 1.0;
@@ -533,14 +555,14 @@ int run_loam(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floa
         // spin on that word returns a few microseconds before the stream's completion signal wakes a sleeping thread
         // (a frontend thread is waiting for this pose anyway).  Timing with events, or a slow call, falls back to the sync.
         if (h->profile == 0) {
-            volatile int32_t* flag = &h->result_host->pad;
+            volatile int32_t* flag = &h->result.host->pad;
             for (int spin = 0; spin < 200000 && *flag != 1; ++spin) __builtin_ia32_pause();
             std::atomic_thread_fence(std::memory_order_acquire);
             if (*flag != 1) H_TRY(hipStreamSynchronize(h->stream));
         } else {
             H_TRY(hipStreamSynchronize(h->stream));
         }
-        const LoamResult r = *h->result_host;
+        const LoamResult r = *h->result.host;
         if (r.pad != 1) return fail(h, "LOAM finalize kernel did not complete");
         if (peer_check(h)) return 1;      // (an exchange of this call timed out: the ranks that waited stopped their loops -- slot 30 -- and the session is over)
         if (r.fail == 2 || rank_fail)      // (every rank sees the flag in the sums of the first linearisation: all return here together)
@@ -574,12 +596,7 @@ int run_loam(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floa
         h->stats.iterations = r.iters_run; h->stats.attempts = attempt + 1;
         h->stats.n_src = (int64_t)n_src; h->stats.n_dst = (int64_t)h->tgt_n;
         h->stats.kernel_ms = 0; h->stats.kernel_launches = 0;
-        if (h->profile >= 1) {
-            float ms = 0;
-            H_TRY(hipEventElapsedTime(&ms, h->ev_start, h->ev_end)); h->stats.total_ms = ms;
-            H_TRY(hipEventElapsedTime(&ms, h->ev_start, h->ev_index)); h->stats.index_ms = ms;
-            H_TRY(hipEventElapsedTime(&ms, h->ev_index, h->ev_end)); h->stats.solve_ms = ms;
-        }
+        if (h->profile >= 1 && read_call_times(h)) return 1;
         if (per_kernel) {
             // only launches that linearised count (the loop may have ended early)
             const int used = std::min(iters, r.converged || r.fail ? r.iters_run : iters);
@@ -658,11 +675,7 @@ int set_device(pcr_handle* h) {
 }
 
 int ensure_out32(pcr_handle* h) {
-    if (!h->out32_host) {
-        H_TRY(hipHostMalloc((void**)&h->out32_host, 32 * sizeof(double), hipHostMallocMapped));
-        memset(h->out32_host, 0, 32 * sizeof(double));
-        H_TRY(hipHostGetDevicePointer((void**)&h->out32_dev, h->out32_host, 0));
-    }
+    H_TRY(h->out32.ensure(32));
     H_TRY(h->vg_partials.reserve((size_t)512 * 32 * sizeof(double)));
     return 0;
 }
@@ -678,6 +691,52 @@ int wait_result(pcr_handle* h, const double* flag_word, double seq) {
         if (*f == seq) return 0;
     }
     H_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// How a device-resident optimiser's passes (run_vgicp, run_ndt) are queued ahead of the progress word of its result block
+struct PaceRule {
+    long first;       // passes queued before the first look
+    long ahead;       // passes kept queued beyond those the device has consumed
+    long refill;      // passes queued after a forced synchronisation
+    // A peer-exchange session: every rank must queue the same number of launches whatever it happens to see when, or the ranks'
+    // sequence numbers part and the next exchange waits out its timeout.  So never more than `ahead` beyond the passes consumed,
+    // and exactly P + ahead once the loop has finished after P passes (the launches beyond the end exchange nothing and leave);
+    // a profiler does not force a synchronisation, and the session is checked after one.
+    bool peer;
+};
+
+// Queue the passes of call `seq` by `rule` -- launch(i) queues pass i -- until the device loop writes `seq` into out->seq.
+// limit: the pass budget of the call; window_msg / budget_msg: the errors of a budget that exceeds the progress window, or
+// that ran out.
+template <class Out, class Launch>
+int pace_passes(pcr_handle* h, const Out* out, double seq, long limit, const PaceRule& rule, const char* window_msg, const char* budget_msg,
+                Launch&& launch) {
+    if ((double)limit >= kProgressWindow) return fail(h, window_msg);
+    const volatile double* f_seq = &out->seq;
+    const volatile double* f_prog = &out->progress;
+    const long cap = rule.peer ? limit + rule.ahead : limit;
+    long enq = 0, spins = 0;
+    for (; enq < rule.first; ++enq) H_TRY_DRAIN(launch(enq));
+    while (*f_seq != seq) {
+        const double pr = *f_prog;
+        const long consumed = (pr >= seq * kProgressWindow && pr < (seq + 1.0) * kProgressWindow) ? (long)(pr - seq * kProgressWindow) : 0;
+        if (enq - consumed < rule.ahead && enq < cap) { H_TRY_DRAIN(launch(enq)); ++enq; continue; }
+        __builtin_ia32_pause();
+        if (++spins > 400000 || (!rule.peer && h->profile != 0)) {      // a slow device (or a profiler): wait for what is queued, then look again
+            H_TRY(hipStreamSynchronize(h->stream));
+            if (*f_seq == seq) break;
+            if (rule.peer && peer_check(h)) return 1;
+            if (enq >= cap) return fail(h, budget_msg);      // (stream just drained)
+            spins = 0;
+            for (long k = 0; k < rule.refill && enq < cap; ++k, ++enq) H_TRY_DRAIN(launch(enq));
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (rule.peer) {
+        for (const long want = (long)out->passes + rule.ahead; enq < want; ++enq) H_TRY_DRAIN(launch(enq));
+        if (peer_check(h)) return 1;
+    }
     return 0;
 }
 
@@ -1066,6 +1125,23 @@ int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t
     return 0;
 }
 
+// The arguments of the handle's VGICP launches over a source (run_vgicp, pcr_vgicp_linearize): the whole target prepared, the index not cut
+VgicpArgs vgicp_args(const pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats) {
+    VgicpArgs a;
+    memset(&a, 0, sizeof a);      // (roi.mask = nullptr, escapes = nullptr)
+    a.src = d_src; a.n_src = (uint32_t)n_src; a.src_stride = (uint32_t)stride_floats;
+    a.src_cov6 = h->src_cov6.as<double>();
+    a.hdr = h->grid.header.as<GridHeader>();
+    a.cell_start = h->grid.cell_start.as<uint32_t>();
+    a.vox = h->vox.as<VgicpVoxel>();
+    a.corr_slot = h->corr_slot.as<uint32_t>(); a.corr_M = h->corr_M.as<double>();
+    a.corr_slot_next = h->corr_slot2.as<uint32_t>(); a.corr_M_next = h->corr_M2.as<double>();
+    a.partials = h->vg_partials.as<double>();
+    a.use_tile = h->use_tile;
+    for (int d = 0; d < 3; ++d) { a.tile_lo[d] = h->tile_lo[d]; a.tile_hi[d] = h->tile_hi[d]; }
+    return a;
+}
+
 int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) {
     if (!h->vg_target_ready) return fail(h, "no target prepared");
     if (n_src > 0xfffffff0ull) return fail(h, "source cloud too large");
@@ -1084,19 +1160,7 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
     H_TRY(h->corr_M.reserve((n_src + 1) * 6 * sizeof(double)));
     H_TRY(h->corr_slot2.reserve((n_src + 1) * sizeof(uint32_t)));
     H_TRY(h->corr_M2.reserve((n_src + 1) * 6 * sizeof(double)));
-    VgicpArgs a;
-    memset(&a, 0, sizeof a);      // (roi.mask = nullptr: the whole target is prepared, unless set below)
-    a.src = d_src; a.n_src = (uint32_t)n_src; a.src_stride = (uint32_t)stride_floats;
-    a.src_cov6 = h->src_cov6.as<double>();
-    a.hdr = h->grid.header.as<GridHeader>();
-    a.cell_start = h->grid.cell_start.as<uint32_t>();
-    a.vox = h->vox.as<VgicpVoxel>();
-    a.corr_slot = h->corr_slot.as<uint32_t>(); a.corr_M = h->corr_M.as<double>();
-    a.corr_slot_next = h->corr_slot2.as<uint32_t>(); a.corr_M_next = h->corr_M2.as<double>();
-    a.partials = h->vg_partials.as<double>();
-    a.use_tile = h->use_tile; a.pad_ = 0;
-    for (int d = 0; d < 3; ++d) { a.tile_lo[d] = h->tile_lo[d]; a.tile_hi[d] = h->tile_hi[d]; }
-    a.escapes = nullptr; a.guard_cells = 0; a.pad2_ = 0;
+    VgicpArgs a = vgicp_args(h, d_src, n_src, stride_floats);
     a.roi = roi_view(h);
     if (h->clamp.use) {      // the target index was cut to the bulk of the cloud (vgicp_prepare_target): watch where the scan goes
         H_TRY(h->cov_viol.reserve(16));
@@ -1113,82 +1177,36 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
     // ---- device-resident loop (vgicp_opt.h): launches are enqueued ahead of the device, the host watches a progress word.  Not for
     // sharded targets (every pass's sums cross the ranks) and not when pcr_params.host_optimiser asks for the host loop below ----
     // Sharded over the peer exchange (pcr_comm_init_peer) the loop stays on the device too: an exchange launch in front of every pass
-    // (vgicp.hip: vgicp_peer_exchange_kernel), and the host queues launches by a rule that gives every rank the same number of them (see run_ndt).
+    // (vgicp.hip: vgicp_peer_exchange_kernel), and the host queues launches by a rule that gives every rank the same number of them (PaceRule).
     const bool peer_loop = shard && h->peer_on && !h->host_ar && !h->comm;
     const bool on_device = n_src > 0 && (!shard || peer_loop) && h->prm.host_optimiser == 0 && h->prm.vgicp_max_iters > 0;
     if (h->roi_on && !on_device) return fail(h, "internal: a target prepared for one scan needs the device-resident loop");
     if (peer_loop && peer_check(h)) return 1;
     if (on_device) {
-        if (!h->vg_out_host) {
-            H_TRY(hipHostMalloc((void**)&h->vg_out_host, sizeof(VgOut), hipHostMallocMapped));
-            memset(h->vg_out_host, 0, sizeof(VgOut));
-            H_TRY(hipHostGetDevicePointer((void**)&h->vg_out_dev, h->vg_out_host, 0));
-        }
+        H_TRY(h->vg_out.ensure());
         H_TRY(h->vg_ctl.reserve(2 * sizeof(VgCtl)));
         H_TRY(h->vg_partials.reserve((size_t)2 * 512 * 32 * sizeof(double)));
         a.partials = h->vg_partials.as<double>();
         VgCtl* d_ctl = h->vg_ctl.as<VgCtl>();
-        VgOut* out = h->vg_out_host;
+        VgOut* out = h->vg_out.host;
         h->seq += 1.0;
         const double seq = h->seq;
         H_TRY(vgicp_launch_ctl_init(d_ctl, x0, h->prm.vgicp_max_iters, h->prm.vgicp_lm_inner, h->prm.vgicp_lm_init_scale, h->prm.vgicp_rot_eps, h->prm.vgicp_trans_eps, h->stream,
                                     h->roi_on ? h->roi_esc.as<uint32_t>() : nullptr));
         // every outer iteration takes at most lm_inner passes, plus the first linearisation and the launch that finishes
         const long limit = (long)h->prm.vgicp_max_iters * std::max(1, h->prm.vgicp_lm_inner) + 3;
-        if ((double)limit >= kProgressWindow) return fail(h, "vgicp_max_iters * vgicp_lm_inner exceeds the device loop's pass window (2^20)");
-        long enq = 0;
-        const volatile double* f_seq = &out->seq;
-        const volatile double* f_prog = &out->progress;
-        long spins = 0;
-        if (peer_loop) {
-            // never more than kAhead launches beyond the passes consumed, and exactly P + kAhead once the loop has finished after P passes: every
-            // rank queues the same number of exchanges whatever it happens to see when (the launches beyond the end exchange nothing)
-            const long kAhead = 3;
-            H_TRY(h->vg_reduced.reserve(64 * sizeof(double)));
-            auto launch = [&]() -> hipError_t {
-                if (enq > 0) h->peer_seq += 1.0;      // (the first launch of a call has nothing to exchange)
-                return vgicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), h->vg_out_dev, h->stream, seq, (int)enq, &h->peer, h->peer_seq, h->vg_reduced.as<double>());
-            };
-            for (;;) {
-                if (*f_seq == seq) break;
-                const double pr = *f_prog;
-                const long consumed = (pr >= seq * kProgressWindow && pr < (seq + 1.0) * kProgressWindow) ? (long)(pr - seq * kProgressWindow) : 0;
-                if (enq - consumed < kAhead && enq < limit + kAhead) { H_TRY_DRAIN(launch()); ++enq; continue; }
-                __builtin_ia32_pause();
-                if (++spins > 400000) {
-                    H_TRY(hipStreamSynchronize(h->stream));
-                    if (*f_seq == seq) break;
-                    if (peer_check(h)) return 1;
-                    if (enq >= limit + kAhead) return fail(h, "vgicp: the optimiser did not finish within its pass budget");
-                    spins = 0;
-                }
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-            for (const long want = (long)out->passes + kAhead; enq < want; ++enq) H_TRY_DRAIN(launch());
-            if (peer_check(h)) return 1;
-        } else {
+        if (peer_loop) H_TRY(h->vg_reduced.reserve(64 * sizeof(double)));
+        auto launch = [&](long i) -> hipError_t {
+            if (!peer_loop) return vgicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), h->vg_out.dev, h->stream, seq, (int)i);
+            if (i > 0) h->peer_seq += 1.0;      // (the first launch of a call has nothing to exchange)
+            return vgicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), h->vg_out.dev, h->stream, seq, (int)i, &h->peer, h->peer_seq, h->vg_reduced.as<double>());
+        };
         // (a pass is ~14 us, and the word that says one has begun is written ~6 us into it: with fewer than three launches ahead of
         // that word the queue runs dry while the host enqueues; a launch beyond the end costs ~5 us)
-        for (; enq < 4 && enq < limit; ++enq) H_TRY_DRAIN(vgicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), h->vg_out_dev, h->stream, seq, (int)enq));
-        for (;;) {
-            if (*f_seq == seq) break;
-            const double pr = *f_prog;
-            const long consumed = (pr >= seq * kProgressWindow && pr < (seq + 1.0) * kProgressWindow) ? (long)(pr - seq * kProgressWindow) : 0;
-            if (enq - consumed < 3 && enq < limit) {
-                H_TRY_DRAIN(vgicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), h->vg_out_dev, h->stream, seq, (int)enq)); ++enq;
-                continue;
-            }
-            __builtin_ia32_pause();
-            if (++spins > 400000 || h->profile != 0) {          // a slow device (or a profiler): wait for what is queued, then look again
-                H_TRY(hipStreamSynchronize(h->stream));
-                if (*f_seq == seq) break;
-                if (enq >= limit) return fail(h, "vgicp: the optimiser did not finish within its pass budget");      // (stream just drained)
-                spins = 0;
-                for (int k = 0; k < 4 && enq < limit; ++k, ++enq) H_TRY_DRAIN(vgicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), h->vg_out_dev, h->stream, seq, (int)enq));
-            }
-        }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
+        static constexpr PaceRule kRule{4, 3, 4, false}, kPeerRule{0, 3, 0, true};
+        if (pace_passes(h, out, seq, limit, peer_loop ? kPeerRule : kRule, "vgicp_max_iters * vgicp_lm_inner exceeds the device loop's pass window (2^20)",
+                        "vgicp: the optimiser did not finish within its pass budget", launch))
+            return 1;
         // some pass looked up a voxel outside the region the target was prepared for: its sums lack that correspondence.  The caller
         // prepares the whole target and repeats the call (2).
         if (h->roi_on && out->roi_escapes > 0) { h->roi_repeats += 1; return 2; }
@@ -1208,12 +1226,12 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
             VgicpArgs ap = a;
             if (c.parity) { ap.corr_slot = a.corr_slot_next; ap.corr_M = a.corr_M_next; ap.corr_slot_next = a.corr_slot; ap.corr_M_next = a.corr_M; }
             h->seq += 1.0;
-            if (c.kind == kVgPassLinearize) H_TRY(vgicp_launch_linearize(ap, c.xi, h->out32_dev, h->stream, h->seq));
-            else H_TRY(vgicp_launch_error(ap, c.xi, h->out32_dev, h->stream, h->seq));
-            if (wait_result(h, &h->out32_host[31], h->seq)) return 1;
-            if (shard && ranks_allreduce(h, h->out32_host, 29)) return 1;
+            if (c.kind == kVgPassLinearize) H_TRY(vgicp_launch_linearize(ap, c.xi, h->out32.dev, h->stream, h->seq));
+            else H_TRY(vgicp_launch_error(ap, c.xi, h->out32.dev, h->stream, h->seq));
+            if (wait_result(h, &h->out32.host[31], h->seq)) return 1;
+            if (shard && ranks_allreduce(h, h->out32.host, 29)) return 1;
             double sums[29];
-            for (int k = 0; k < 29; ++k) sums[k] = h->out32_host[k];
+            for (int k = 0; k < 29; ++k) sums[k] = h->out32.host[k];
             vg_opt::ctl_step(&c, sums);
         }
         x0 = c.x0; conv = c.conv != 0;
@@ -1248,17 +1266,17 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
         for (int d = 0; d < 3; ++d) { ft.lo[d] = h->tile_lo[d]; ft.hi[d] = h->tile_hi[d]; ft.ext_lo[d] = -1e300; ft.ext_hi[d] = 1e300; }
         if (h->have_halo) shard_extent(h, ft.ext_lo, ft.ext_hi);
     }
-    H_TRY(fitness_launch(h->grid, d_src, n_src, stride_floats, pose, 1.7976931348623157e308, h->vg_partials.as<double>(), h->out32_dev, h->stream, h->seq,
+    H_TRY(fitness_launch(h->grid, d_src, n_src, stride_floats, pose, 1.7976931348623157e308, h->vg_partials.as<double>(), h->out32.dev, h->stream, h->seq,
                          h->use_tile ? &ft : nullptr));
-    if (wait_result(h, &h->out32_host[31], h->seq)) return 1;
-    h->out32_host[3] = (double)esc;      // (this rank's scan points that reached a cut face of its index)
-    if (shard && ranks_allreduce(h, h->out32_host, 4)) return 1;
-    if (h->out32_host[3] > 0) { h->err = "a rank's target is too spread out for the dense voxel tables (a stray point far from the map?) and was cut to its bulk, but the scan reaches "
+    if (wait_result(h, &h->out32.host[31], h->seq)) return 1;
+    h->out32.host[3] = (double)esc;      // (this rank's scan points that reached a cut face of its index)
+    if (shard && ranks_allreduce(h, h->out32.host, 4)) return 1;
+    if (h->out32.host[3] > 0) { h->err = "a rank's target is too spread out for the dense voxel tables (a stray point far from the map?) and was cut to its bulk, but the scan reaches "
                                          "the part that was left out"; return 3; }
-    h->fitness = h->out32_host[1] > 0 ? h->out32_host[0] / h->out32_host[1] : 1.7976931348623157e308;
+    h->fitness = h->out32.host[1] > 0 ? h->out32.host[0] / h->out32.host[1] : 1.7976931348623157e308;
     // sharded: a source point farther from every map point than its rank's halo has its nearest neighbour on another rank; the
     // score is then not the map's and is reported as unavailable (the pose is unaffected)
-    if (h->use_tile && h->out32_host[2] > 0) h->fitness = -1.0;
+    if (h->use_tile && h->out32.host[2] > 0) h->fitness = -1.0;
     h->stats.iterations = h->vg_outer; h->stats.n_src = (int64_t)n_src; h->stats.n_dst = (int64_t)h->tgt_n;
     h->stats.kernel_launches = h->vg_lin + h->vg_err;
     return 0;
@@ -1375,6 +1393,7 @@ struct NdtRun {
     pcr_handle* h; NdtArgs a; NdtPose T; NdtAngles ang;
 };
 // the guess as the optimiser starts from it: handed over as Matrix4f (NdtRegister.cpp:27), its Euler angles as the parameters
+// (ndt_omp_impl.hpp:103-111)
 void ndt_initial_pose(const double pose[16], NdtPose* T0, double p0[6]) {
     float G[16];
     for (int i = 0; i < 16; ++i) G[i] = (float)pose[i];
@@ -1383,6 +1402,29 @@ void ndt_initial_pose(const double pose[16], NdtPose* T0, double p0[6]) {
     ndt_host::euler_xyz(T0->R, eul);     // Transform::rotation() taken as the linear part
     p0[0] = T0->t[0]; p0[1] = T0->t[1]; p0[2] = T0->t[2]; p0[3] = eul[0]; p0[4] = eul[1]; p0[5] = eul[2];
 }
+// ... and the final transformation as the caller's pose
+void ndt_pose_out(const NdtPose& T, double pose16[16]) {
+    for (int i = 0; i < 16; ++i) pose16[i] = 0;
+    for (int rr = 0; rr < 3; ++rr) { for (int c = 0; c < 3; ++c) pose16[c * 4 + rr] = (double)T.R[rr * 3 + c]; pose16[12 + rr] = (double)T.t[rr]; }
+    pose16[15] = 1.0;
+}
+
+// The arguments of the handle's NDT launches over a source (run_ndt, pcr_ndt_derivatives): no region, no profiling counters
+NdtArgs ndt_args(const pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats) {
+    NdtArgs a;
+    memset(&a, 0, sizeof a);
+    a.src = d_src; a.n_src = (uint32_t)n_src; a.src_stride = (uint32_t)stride_floats;
+    a.hdr = h->grid.header.as<GridHeader>(); a.vox_slot = h->nd_slot.as<uint32_t>(); a.vox = h->nd_vox.as<NdtVoxel>();
+    a.partials = h->nd_partials.as<double>();
+    a.use_tile = h->use_tile;
+    for (int d = 0; d < 3; ++d) { a.tile_lo[d] = h->tile_lo[d]; a.tile_hi[d] = h->tile_hi[d]; }
+    // Gauss constants (ndt_omp_impl.hpp:86-93)
+    const double res = (double)(float)h->prm.ndt_resolution;
+    const double c1 = 10 * (1 - h->prm.ndt_outlier_ratio), c2 = h->prm.ndt_outlier_ratio / pow(res, 3), d3 = -log(c2);
+    a.d1 = -log(c1 + c2) - d3;
+    a.d2 = -2 * log((-log(c1 * exp(-0.5) + c2) - d3) / a.d1);
+    return a;
+}
 
 // computeDerivatives at parameters p with the cloud transformed by T: score, gradient, Hessian
 int ndt_derivatives(NdtRun* r, const double p[6], bool compute_hessian, double* score, double grad[6], double hess[36]) {
@@ -1390,13 +1432,13 @@ int ndt_derivatives(NdtRun* r, const double p[6], bool compute_hessian, double* 
     ndt_host::angle_derivatives(p, &r->ang);
     if (r->a.n_src == 0) { *score = 0; memset(grad, 0, 6 * sizeof(double)); memset(hess, 0, 36 * sizeof(double)); return 0; }
     h->seq += 1.0;
-    H_TRY(ndt_launch_derivatives(r->a, r->T, r->ang, compute_hessian ? 1 : 0, h->out48_dev, h->stream, h->seq));
-    if (wait_result(h, &h->out48_host[47], h->seq)) return 1;
-    if (sharded(h) && ranks_allreduce(h, h->out48_host, 43)) return 1;      // score, gradient, Hessian summed over the ranks' tiles
+    H_TRY(ndt_launch_derivatives(r->a, r->T, r->ang, compute_hessian ? 1 : 0, h->out48.dev, h->stream, h->seq));
+    if (wait_result(h, &h->out48.host[47], h->seq)) return 1;
+    if (sharded(h) && ranks_allreduce(h, h->out48.host, 43)) return 1;      // score, gradient, Hessian summed over the ranks' tiles
     ++h->nd_deriv;
-    *score = h->out48_host[0];
-    for (int i = 0; i < 6; ++i) grad[i] = h->out48_host[1 + i];
-    for (int i = 0; i < 36; ++i) hess[i] = compute_hessian ? h->out48_host[7 + i] : 0.0;
+    *score = h->out48.host[0];
+    for (int i = 0; i < 6; ++i) grad[i] = h->out48.host[1 + i];
+    for (int i = 0; i < 36; ++i) hess[i] = compute_hessian ? h->out48.host[7 + i] : 0.0;
     return 0;
 }
 
@@ -1404,47 +1446,29 @@ int ndt_derivatives(NdtRun* r, const double p[6], bool compute_hessian, double* 
 int ndt_host_pass(NdtRun* r, const NdtCtl& c, double sums[43]) {
     pcr_handle* h = r->h;
     h->seq += 1.0;
-    if (c.kind == kNdtPassHessian) H_TRY(ndt_launch_hessian(r->a, c.T, c.ang, h->out48_dev, h->stream, h->seq));
-    else H_TRY(ndt_launch_derivatives(r->a, c.T, c.ang, c.kind == kNdtPassDerivH ? 1 : 0, h->out48_dev, h->stream, h->seq));
-    if (wait_result(h, &h->out48_host[47], h->seq)) return 1;
-    if (sharded(h) && ranks_allreduce(h, h->out48_host, 43)) return 1;      // score, gradient, Hessian summed over the ranks' tiles
-    for (int i = 0; i < 43; ++i) sums[i] = h->out48_host[i];
+    if (c.kind == kNdtPassHessian) H_TRY(ndt_launch_hessian(r->a, c.T, c.ang, h->out48.dev, h->stream, h->seq));
+    else H_TRY(ndt_launch_derivatives(r->a, c.T, c.ang, c.kind == kNdtPassDerivH ? 1 : 0, h->out48.dev, h->stream, h->seq));
+    if (wait_result(h, &h->out48.host[47], h->seq)) return 1;
+    if (sharded(h) && ranks_allreduce(h, h->out48.host, 43)) return 1;      // score, gradient, Hessian summed over the ranks' tiles
+    for (int i = 0; i < 43; ++i) sums[i] = h->out48.host[i];
     return 0;
 }
 
 int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) {
     using namespace ndt_host;
+    static constexpr const char *kWindowMsg = "ndt_max_iters exceeds the device loop's pass window (2^20 passes)",
+                                *kBudgetMsg = "ndt: the optimiser did not finish within its pass budget";
     if (!h->nd_target_ready) return fail(h, "no target prepared");
     if (n_src > 0xfffffff0ull) return fail(h, "source cloud too large");
-    if (!h->out48_host) {
-        H_TRY(hipHostMalloc((void**)&h->out48_host, 48 * sizeof(double), hipHostMallocMapped));
-        memset(h->out48_host, 0, 48 * sizeof(double));
-        H_TRY(hipHostGetDevicePointer((void**)&h->out48_dev, h->out48_host, 0));
-    }
-    if (!h->nd_out_host) {
-        H_TRY(hipHostMalloc((void**)&h->nd_out_host, sizeof(NdtOut), hipHostMallocMapped));
-        memset(h->nd_out_host, 0, sizeof(NdtOut));
-        H_TRY(hipHostGetDevicePointer((void**)&h->nd_out_dev, h->nd_out_host, 0));
-    }
+    H_TRY(h->out48.ensure(48));
+    H_TRY(h->nd_out.ensure());
     H_TRY(h->nd_partials.reserve((size_t)1024 * 48 * sizeof(double)));      // (one buffer of 1024 rows, or the two of 256 of the one-launch-per-pass loop)
     H_TRY(h->nd_ctl.reserve(2 * sizeof(NdtCtl)));
     NdtRun r;
-    memset(&r.a, 0, sizeof r.a);
     r.h = h;
-    r.a.src = d_src; r.a.n_src = (uint32_t)n_src; r.a.src_stride = (uint32_t)stride_floats;
-    r.a.hdr = h->grid.header.as<GridHeader>(); r.a.vox_slot = h->nd_slot.as<uint32_t>(); r.a.vox = h->nd_vox.as<NdtVoxel>();
-    r.a.partials = h->nd_partials.as<double>();
-    r.a.use_tile = h->use_tile; r.a.pad_ = 0;
-    for (int d = 0; d < 3; ++d) { r.a.tile_lo[d] = h->tile_lo[d]; r.a.tile_hi[d] = h->tile_hi[d]; }
+    r.a = ndt_args(h, d_src, n_src, stride_floats);
     r.a.roi_escapes = h->roi_on ? h->roi_esc.as<uint32_t>() : nullptr;
     r.a.pair_count = prof_counters(h);
-    {   // Gauss constants (ndt_omp_impl.hpp:86-93)
-        const double res = (double)(float)h->prm.ndt_resolution;
-        const double c1 = 10 * (1 - h->prm.ndt_outlier_ratio), c2 = h->prm.ndt_outlier_ratio / pow(res, 3);
-        const double d3 = -log(c2);
-        r.a.d1 = -log(c1 + c2) - d3;
-        r.a.d2 = -2 * log((-log(c1 * exp(-0.5) + c2) - d3) / r.a.d1);
-    }
     h->nd_iters = h->nd_deriv = h->nd_hess = 0;
     NdtPose T0;
     double p0[6];
@@ -1467,7 +1491,7 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
     bool sharded_done = false;
     if (dev_sharded) {
         NdtCtl* d_ctl = h->nd_ctl.as<NdtCtl>();
-        NdtOut* out = h->nd_out_host;
+        NdtOut* out = h->nd_out.host;
         H_TRY(h->nd_sums.reserve(64 * sizeof(double)));
         h->seq += 1.0;
         const double seq = h->seq;
@@ -1475,41 +1499,18 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
         const int limit = (h->prm.ndt_max_iters + 3) * 13 + 4, kBatch = 6;
         const volatile double* f_batch = &out->batch;
         if (h->peer_on) {
-            // Peer exchange: passes are queued a FIXED number ahead of the progress word, one at a time, like the unsharded loop -- with a rule that
-            // makes every rank queue the same number of them whatever it happens to see when: never more than kAhead beyond the passes consumed,
-            // and, once the loop has finished after P passes, exactly P + kAhead (a rank that saw the end early tops its queue up; the launches
-            // beyond the end exchange nothing and leave).  The ranks' sequence numbers -- one per queued launch -- then agree in the next call too.
-            const int kAhead = 3;
-            const volatile double* f_seq = &out->seq;
-            const volatile double* f_prog = &out->progress;
-            if ((double)limit >= kProgressWindow) return fail(h, "ndt_max_iters exceeds the device loop's pass window (2^20 passes)");
-            auto launch = [&]() -> hipError_t { h->peer_seq += 1.0; return ndt_launch_pass_peer(r.a, d_ctl, h->peer, h->peer_seq, h->nd_out_dev, h->stream, seq, 0); };
-            int enq = 0;
-            long spins = 0;
-            for (;;) {
-                if (*f_seq == seq) break;
-                const double pr = *f_prog;
-                const int consumed = (pr >= seq * kProgressWindow && pr < (seq + 1.0) * kProgressWindow) ? (int)(pr - seq * kProgressWindow) : 0;
-                if (enq - consumed < kAhead && enq < limit + kAhead) { H_TRY(launch()); ++enq; continue; }
-                __builtin_ia32_pause();
-                if (++spins > 400000) {      // a slow device (or a profiler): wait for what is queued, then look again
-                    H_TRY(hipStreamSynchronize(h->stream));
-                    if (*f_seq == seq) break;
-                    if (peer_check(h)) return 1;
-                    if (enq >= limit + kAhead) return fail(h, "ndt: the optimiser did not finish within its pass budget");
-                    spins = 0;
-                }
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-            for (const int want = out->passes + kAhead; enq < want; ++enq) H_TRY(launch());      // (every rank ends the call with the same number of launches queued)
-            if (peer_check(h)) return 1;
+            // Peer exchange: passes are queued a fixed number ahead of the progress word, one at a time, like the unsharded loop -- by the rule that
+            // leaves every rank with the same number of launches queued (PaceRule::peer): the ranks' sequence numbers, one per launch, agree in the next call too.
+            auto launch = [&](long) -> hipError_t { h->peer_seq += 1.0; return ndt_launch_pass_peer(r.a, d_ctl, h->peer, h->peer_seq, h->nd_out.dev, h->stream, seq, 0); };
+            static constexpr PaceRule kPeerRule{0, 3, 0, true};
+            if (pace_passes(h, out, seq, limit, kPeerRule, kWindowMsg, kBudgetMsg, launch)) return 1;
         } else
         for (int batch = 1, enq = 0;; ++batch) {
             for (int b = 0; b < kBatch; ++b, ++enq) {
                 H_TRY(ndt_launch_pass_fold(r.a, d_ctl, h->nd_sums.as<double>(), h->stream));      // (a rank with an empty scan still folds zeros and takes part)
                 const int rc = g_rccl.allreduce(h->nd_sums.p, h->nd_sums.p, 48, /*ncclFloat64*/ 8, /*ncclSum*/ 0, h->comm, h->stream);
                 if (rc != 0) return fail(h, "ncclAllReduce failed with code " + std::to_string(rc));
-                H_TRY(ndt_launch_ctl(r.a, d_ctl, h->nd_sums.as<double>(), h->nd_out_dev, h->stream, seq, b == kBatch - 1 ? batch : 0));
+                H_TRY(ndt_launch_ctl(r.a, d_ctl, h->nd_sums.as<double>(), h->nd_out.dev, h->stream, seq, b == kBatch - 1 ? batch : 0));
             }
             const double want0 = seq * 65536.0 + 2.0 * batch;
             long spins = 0;
@@ -1520,7 +1521,7 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
             std::atomic_thread_fence(std::memory_order_acquire);
             if (peer_check(h)) return 1;      // (an exchange of this batch timed out: the loop has stopped on the ranks that waited, the session is over)
             if (*f_batch == want0 + 1.0) break;
-            if (enq >= limit) return fail(h, "ndt: the optimiser did not finish within its pass budget");
+            if (enq >= limit) return fail(h, kBudgetMsg);
         }
         if (!out->bail) {      // (a nearly singular Newton system: every rank saw the same pivots and goes to the host loop below, with the SVD)
             final_T = out->final_T; conv = out->conv; nr_it = out->nr_it; score = out->score;
@@ -1530,7 +1531,7 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
     }
     if (on_device) {
         NdtCtl* d_ctl = h->nd_ctl.as<NdtCtl>();
-        NdtOut* out = h->nd_out_host;
+        NdtOut* out = h->nd_out.host;
         h->seq += 1.0;
         const double seq = h->seq;
         // (a scan2map call whose region was marked has stored this state with the mark pass: do_scan2map, BlobStore)
@@ -1539,40 +1540,19 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
         if (!stored) H_TRY(ndt_launch_ctl_init(d_ctl, T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters, h->stream, h->prm.ndt_evaluate_repeats,
                                                r.a.roi_escapes));
         const int limit = (h->prm.ndt_max_iters + 3) * 13 + 5;        // an iteration takes at most 1 + 10 + 1 passes; one launch more finishes
-        if ((double)limit >= kProgressWindow) return fail(h, "ndt_max_iters exceeds the device loop's pass window (2^20 passes)");
-        int enq = 0;
-        const int first = 3;      // (the host enqueues a pass in a quarter of the time the device needs for one: it only has to stay two ahead)
-        auto launch = [&](int index) -> hipError_t {
+        auto launch = [&](long i) -> hipError_t {
+            const int index = (int)i;
             if (h->profile >= 2) {      // events at every launch's own begin and end (pcr_stats.kernel_ms)
                 while ((int)h->ev_kernel.size() < 2 * (index + 1)) { hipEvent_t e; hipError_t er = hipEventCreate(&e); if (er != hipSuccess) return er; h->ev_kernel.push_back(e); }
                 h->nd_prof_launches = index + 1;
-                return ndt_launch_pass_pro(r.a, d_ctl, h->nd_partials.as<double>(), h->nd_out_dev, h->stream, seq, index, h->ev_kernel[2 * index], h->ev_kernel[2 * index + 1]);
+                return ndt_launch_pass_pro(r.a, d_ctl, h->nd_partials.as<double>(), h->nd_out.dev, h->stream, seq, index, h->ev_kernel[2 * index], h->ev_kernel[2 * index + 1]);
             }
-            return ndt_launch_pass_pro(r.a, d_ctl, h->nd_partials.as<double>(), h->nd_out_dev, h->stream, seq, index);
+            return ndt_launch_pass_pro(r.a, d_ctl, h->nd_partials.as<double>(), h->nd_out.dev, h->stream, seq, index);
         };
-        for (; enq < first; ++enq) H_TRY_DRAIN(launch(enq));
-        const volatile double* f_seq = &out->seq;
-        const volatile double* f_prog = &out->progress;
-        long spins = 0;
-        bool finished = false;
-        while (!finished) {
-            if (*f_seq == seq) { finished = true; break; }
-            const double pr = *f_prog;
-            const int consumed = (pr >= seq * kProgressWindow && pr < (seq + 1.0) * kProgressWindow) ? (int)(pr - seq * kProgressWindow) : 0;
-            if (enq - consumed < 2 && enq < limit) {       // two passes ahead of the device: a pass enqueued beyond the end costs ~10 us of device time
-                H_TRY_DRAIN(launch(enq)); ++enq;
-                continue;
-            }
-            __builtin_ia32_pause();
-            if (++spins > 400000 || h->profile != 0) {          // a slow device (or a profiler): wait for what is queued, then look again
-                H_TRY(hipStreamSynchronize(h->stream));
-                if (*f_seq == seq) { finished = true; break; }
-                if (enq >= limit) return fail(h, "ndt: the optimiser did not finish within its pass budget");
-                spins = 0;
-                for (int k = 0; k < 4 && enq < limit; ++k, ++enq) H_TRY_DRAIN(launch(enq));
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
+        // (the host enqueues a pass in a quarter of the time the device needs for one: it only has to stay two ahead -- a pass enqueued beyond
+        //  the end costs ~10 us of device time)
+        static constexpr PaceRule kRule{3, 2, 4, false};
+        if (pace_passes(h, out, seq, limit, kRule, kWindowMsg, kBudgetMsg, launch)) return 1;
         h->nd_last_passes = out->passes;
         h->nd_grid_bad = out->grid_overflow || out->grid_stale;
         h->nd_grid_empty = out->grid_empty != 0;
@@ -1600,9 +1580,7 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
         final_T = c.final_T; conv = c.conv; nr_it = c.nr_it; score = c.score;
         h->nd_deriv = c.n_deriv; h->nd_hess = c.n_hess;
     }
-    for (int i = 0; i < 16; ++i) pose[i] = 0;
-    for (int rr = 0; rr < 3; ++rr) { for (int c = 0; c < 3; ++c) pose[c * 4 + rr] = (double)final_T.R[rr * 3 + c]; pose[12 + rr] = (double)final_T.t[rr]; }
-    pose[15] = 1.0;
+    ndt_pose_out(final_T, pose);
     if (converged) *converged = conv ? 1 : 0;
     h->nd_iters = nr_it; h->nd_score = score;
     h->stats.iterations = nr_it; h->stats.kernel_launches = h->nd_deriv + h->nd_hess;
@@ -1680,16 +1658,7 @@ int do_scan2map(pcr_handle* h, const void* src, size_t n_src, const void* dst, s
             h->grid.hint_margin = 8; h->grid.cells_hint = 0;      // (a cloud that left the old box: its cell count is anybody's guess too)
             memcpy(pose, pose_in, sizeof pose_in);
         }
-        if (h->profile >= 1) {
-            H_TRY(hipEventRecord(h->ev_end, h->stream));
-            H_TRY(hipEventSynchronize(h->ev_end));
-            float ms = 0;
-            H_TRY(hipEventElapsedTime(&ms, h->ev_start, h->ev_end)); h->stats.total_ms = ms;
-            H_TRY(hipEventElapsedTime(&ms, h->ev_start, h->ev_index)); h->stats.index_ms = ms;
-            H_TRY(hipEventElapsedTime(&ms, h->ev_index, h->ev_end)); h->stats.solve_ms = ms;
-            if (prof_end(h)) return 1;
-        }
-        return 0;
+        return end_timed_call(h);
     }
     if (h->method == kVgicp) {
         // the reference keeps its target structures while the cloud POINTER is unchanged and goes stale
@@ -1728,16 +1697,7 @@ int do_scan2map(pcr_handle* h, const void* src, size_t n_src, const void* dst, s
             rrc = vgicp_align_recut(h, d_src, n_src, stride_bytes / 4, pose, converged);
         }
         if (rrc) return 1;
-        if (h->profile >= 1) {
-            H_TRY(hipEventRecord(h->ev_end, h->stream));
-            H_TRY(hipEventSynchronize(h->ev_end));
-            float ms = 0;
-            H_TRY(hipEventElapsedTime(&ms, h->ev_start, h->ev_end)); h->stats.total_ms = ms;
-            H_TRY(hipEventElapsedTime(&ms, h->ev_start, h->ev_index)); h->stats.index_ms = ms;
-            H_TRY(hipEventElapsedTime(&ms, h->ev_index, h->ev_end)); h->stats.solve_ms = ms;
-            if (prof_end(h)) return 1;
-        }
-        return 0;
+        return end_timed_call(h);
     }
     // the reference rebuilds its index on every call (LoamRegister.cpp:110); so do we
     h->clamp.use = 0;
@@ -1815,43 +1775,18 @@ pcr_handle* pcr_create(const char* method, const pcr_params* p) {
 void pcr_destroy(pcr_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); pin_forget_stream(h->stream); }
+    // nothing may still run when the memory goes: the device buffers and host-mapped blocks free themselves with the handle
+    for (hipStream_t s : {h->stream, h->side_stream, h->aux_stream}) if (s) (void)hipStreamSynchronize(s);
+    if (h->stream) pin_forget_stream(h->stream);
     if (h->comm && g_rccl.destroy) g_rccl.destroy(h->comm);
-    h->grid.release(); h->tgt_stage.release(); h->src_stage.release();
-    h->rl_poses.release(); h->rl_part.release(); h->rl_out.release(); h->rl_src.release();
     peer_close(h);
     if (h->peer_own) (void)hipFree(h->peer_own);
-    if (h->peer_status_host) (void)hipHostFree(h->peer_status_host);
     if (h->vf_ret) (void)hipHostFree(h->vf_ret);
-    h->prof_count.release();
-    for (hipEvent_t e : h->ev_cov) if (e) (void)hipEventDestroy(e);
-    h->vf_grid.release(); h->vf_in.release(); h->vf_out.release(); h->vf_head.release(); h->vf_sums.release(); h->vf_count.release();
-    if (h->side_stream) (void)hipStreamSynchronize(h->side_stream);
-    h->src_grid.release(); h->cov_l1.release(); h->cov_l2.release(); h->src_l1.release(); h->src_l2.release(); h->tgt_cov6.release(); h->src_cov6.release(); h->vox.release(); h->src_scratch.release(); h->tgt_scratch.release();
-    h->corr_slot.release(); h->corr_M.release(); h->corr_slot2.release(); h->corr_M2.release(); h->vg_partials.release(); h->vg_ctl.release(); h->vg_reduced.release(); h->fit_src.release();
-    if (h->vg_out_host) (void)hipHostFree(h->vg_out_host);
-    if (h->out32_host) (void)hipHostFree(h->out32_host);
-    h->nd_slot.release(); h->nd_vox.release(); h->nd_count.release(); h->nd_list.release(); h->nd_partials.release();
-    if (h->out48_host) (void)hipHostFree(h->out48_host);
-    if (h->nd_out_host) (void)hipHostFree(h->nd_out_host);
-    h->nd_ctl.release(); h->nd_sums.release();
-    h->loam_state.release(); h->loam_partials.release(); h->loam_trace.release(); h->loam_reduced.release();
-    h->dbg_status.release(); h->dbg_rows.release(); h->dbg_nn.release(); h->nn_cache.release(); h->timeline.release();
-    if (h->result_host) (void)hipHostFree(h->result_host);
-    if (h->red_host) (void)hipHostFree(h->red_host);
-    h->ar_stage.release(); h->dummy_grid.release(); h->cov_viol.release();
-    h->roi_mark[0].release(); h->roi_mark[1].release(); h->roi_tmp.release(); h->roi_mask.release(); h->roi_esc.release();
-    for (hipEvent_t e : h->ev_kernel) (void)hipEventDestroy(e);
-    if (h->ev_start) (void)hipEventDestroy(h->ev_start);
-    if (h->ev_index) (void)hipEventDestroy(h->ev_index);
-    if (h->ev_end) (void)hipEventDestroy(h->ev_end);
     if (h->side_hdr) (void)hipHostFree(h->side_hdr);
-    if (h->ev_side_in) (void)hipEventDestroy(h->ev_side_in);
-    if (h->ev_hdr) (void)hipEventDestroy(h->ev_hdr);
-    if (h->ev_aux_in) (void)hipEventDestroy(h->ev_aux_in);
-    if (h->ev_aux_done) (void)hipEventDestroy(h->ev_aux_done);
-    if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
-    if (h->ev_side_done) (void)hipEventDestroy(h->ev_side_done);
+    for (hipEvent_t e : h->ev_kernel) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->ev_cov) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {h->ev_start, h->ev_index, h->ev_end, h->ev_side_in, h->ev_side_done, h->ev_hdr, h->ev_aux_in, h->ev_aux_done}) if (e) (void)hipEventDestroy(e);
+    if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
     if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -2173,14 +2108,14 @@ double pcr_fitness(pcr_handle* h) {
             }
             const GridIndex& fit_grid = h->grid.filtered ? h->cov_l1 : h->grid;
             if (fitness_launch(fit_grid, h->fit_src.as<float>(), h->fit_n, h->fit_stride, h->fit_pose, 1.7976931348623157e308, h->vg_partials.as<double>(),
-                               h->out32_dev, h->stream, h->seq, nullptr) != hipSuccess) { h->err = "fitness_launch failed"; return -1.0; }
-            if (wait_result(h, &h->out32_host[31], h->seq)) return -1.0;
-            if (h->out32_host[2] > 0) {      // (fitness_kernel: points whose nearest target point may lie beyond a cut face of the index)
-                h->err = cut_fitness_message(h->out32_host[2]);
+                               h->out32.dev, h->stream, h->seq, nullptr) != hipSuccess) { h->err = "fitness_launch failed"; return -1.0; }
+            if (wait_result(h, &h->out32.host[31], h->seq)) return -1.0;
+            if (h->out32.host[2] > 0) {      // (fitness_kernel: points whose nearest target point may lie beyond a cut face of the index)
+                h->err = cut_fitness_message(h->out32.host[2]);
                 h->fitness = -1.0;
                 return -1.0;
             }
-            h->fitness = h->out32_host[1] > 0 ? h->out32_host[0] / h->out32_host[1] : 1.7976931348623157e308;
+            h->fitness = h->out32.host[1] > 0 ? h->out32.host[0] / h->out32.host[1] : 1.7976931348623157e308;
         }
     }
     return h->fitness;
@@ -2281,30 +2216,17 @@ int pcr_vgicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t str
     const int rc = run_vgicp(h, d_src, n_src, stride_bytes / 4, tmp, &conv);
     h->prm.vgicp_max_iters = saved;
     if (rc) return 1;
-    VgicpArgs a;
-    memset(&a, 0, sizeof a);      // (roi.mask = nullptr: the whole target is prepared, unless set below)
-    a.src = d_src; a.n_src = (uint32_t)n_src; a.src_stride = (uint32_t)(stride_bytes / 4);
-    a.src_cov6 = h->src_cov6.as<double>();
-    a.hdr = h->grid.header.as<GridHeader>();
-    a.cell_start = h->grid.cell_start.as<uint32_t>();
-    a.vox = h->vox.as<VgicpVoxel>();
-    a.corr_slot = h->corr_slot.as<uint32_t>(); a.corr_M = h->corr_M.as<double>();
-    a.corr_slot_next = h->corr_slot2.as<uint32_t>(); a.corr_M_next = h->corr_M2.as<double>();
-    a.partials = h->vg_partials.as<double>();
-    a.use_tile = h->use_tile; a.pad_ = 0;
-    a.escapes = nullptr; a.guard_cells = 0; a.pad2_ = 0;
-    for (int d = 0; d < 3; ++d) { a.tile_lo[d] = h->tile_lo[d]; a.tile_hi[d] = h->tile_hi[d]; }
     Pose16 T;
     memcpy(T.m, pose, sizeof T.m);
-    H_TRY(vgicp_launch_linearize(a, T, h->out32_dev, h->stream));
+    H_TRY(vgicp_launch_linearize(vgicp_args(h, d_src, n_src, stride_bytes / 4), T, h->out32.dev, h->stream));
     std::vector<uint32_t> slots(n_src);
     if (n_src) H_TRY(hipMemcpyAsync(slots.data(), h->corr_slot.p, n_src * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     H_TRY(hipStreamSynchronize(h->stream));
-    if (sharded(h) && ranks_allreduce(h, h->out32_host, 29)) return 1;
+    if (sharded(h) && ranks_allreduce(h, h->out32.host, 29)) return 1;
     int q = 0;
-    for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { H[r * 6 + c] = H[c * 6 + r] = h->out32_host[q++]; }
-    for (int r = 0; r < 6; ++r) b[r] = h->out32_host[21 + r];
-    if (error) *error = h->out32_host[27];
+    for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { H[r * 6 + c] = H[c * 6 + r] = h->out32.host[q++]; }
+    for (int r = 0; r < 6; ++r) b[r] = h->out32.host[21 + r];
+    if (error) *error = h->out32.host[27];
     if (n_corr) { int64_t c = 0; for (uint32_t v : slots) c += v != 0; *n_corr = c; }
     return 0;
 }
@@ -2319,33 +2241,20 @@ int pcr_ndt_derivatives(pcr_handle* h, const void* src, size_t n_src, size_t str
     if (ensure_full_target(h)) return 1;
     const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
-    if (!h->out48_host) {
-        H_TRY(hipHostMalloc((void**)&h->out48_host, 48 * sizeof(double), hipHostMallocMapped));
-        memset(h->out48_host, 0, 48 * sizeof(double));
-        H_TRY(hipHostGetDevicePointer((void**)&h->out48_dev, h->out48_host, 0));
-    }
+    H_TRY(h->out48.ensure(48));
     H_TRY(h->nd_partials.reserve((size_t)1024 * 48 * sizeof(double)));
     NdtRun r;
-    memset(&r.a, 0, sizeof r.a);
     r.h = h;
-    r.a.src = d_src; r.a.n_src = (uint32_t)n_src; r.a.src_stride = (uint32_t)(stride_bytes / 4);
-    r.a.hdr = h->grid.header.as<GridHeader>(); r.a.vox_slot = h->nd_slot.as<uint32_t>(); r.a.vox = h->nd_vox.as<NdtVoxel>();
-    r.a.partials = h->nd_partials.as<double>();
-    r.a.use_tile = h->use_tile; r.a.pad_ = 0;
-    for (int d = 0; d < 3; ++d) { r.a.tile_lo[d] = h->tile_lo[d]; r.a.tile_hi[d] = h->tile_hi[d]; }
-    const double res = (double)(float)h->prm.ndt_resolution;
-    const double c1 = 10 * (1 - h->prm.ndt_outlier_ratio), c2 = h->prm.ndt_outlier_ratio / pow(res, 3), d3 = -log(c2);
-    r.a.d1 = -log(c1 + c2) - d3;
-    r.a.d2 = -2 * log((-log(c1 * exp(-0.5) + c2) - d3) / r.a.d1);
+    r.a = ndt_args(h, d_src, n_src, stride_bytes / 4);
     ndt_host::pose_from_p(p, &r.T);
     double sc = 0;
     if (ndt_derivatives(&r, p, true, &sc, grad, hess)) return 1;
     if (score) *score = sc;
     if (hess_d && n_src) {
-        H_TRY(ndt_launch_hessian(r.a, r.T, r.ang, h->out48_dev, h->stream));
+        H_TRY(ndt_launch_hessian(r.a, r.T, r.ang, h->out48.dev, h->stream));
         H_TRY(hipStreamSynchronize(h->stream));
-        if (sharded(h) && ranks_allreduce(h, h->out48_host, 43)) return 1;
-        for (int i = 0; i < 36; ++i) hess_d[i] = h->out48_host[7 + i];
+        if (sharded(h) && ranks_allreduce(h, h->out48.host, 43)) return 1;
+        for (int i = 0; i < 36; ++i) hess_d[i] = h->out48.host[7 + i];
     }
     return 0;
 }
@@ -2356,23 +2265,13 @@ pcr_ndt_opt* pcr_ndt_opt_create(const double pose_guess[16], double step_size, d
     if (!pose_guess) return nullptr;
     pcr_ndt_opt* o = new pcr_ndt_opt;
     memset(&o->c, 0, sizeof o->c);
-    // guess handed over as Matrix4f, Euler angles of its linear part (NdtRegister.cpp:27, ndt_omp_impl.hpp:103-111): as run_ndt does
-    float G[16];
-    for (int i = 0; i < 16; ++i) G[i] = (float)pose_guess[i];
     NdtPose T0;
-    for (int rr = 0; rr < 3; ++rr) { for (int c = 0; c < 3; ++c) T0.R[rr * 3 + c] = G[c * 4 + rr]; T0.t[rr] = G[12 + rr]; }
-    float eul[3];
-    ndt_host::euler_xyz(T0.R, eul);
-    const double p0[6] = {T0.t[0], T0.t[1], T0.t[2], eul[0], eul[1], eul[2]};
+    double p0[6];
+    ndt_initial_pose(pose_guess, &T0, p0);      // (as run_ndt starts)
     ndt_opt::ctl_init(&o->c, T0, p0, step_size, trans_eps, max_iters);
     return o;
 }
 void pcr_ndt_opt_destroy(pcr_ndt_opt* o) { delete o; }
-static void ndt_pose_out(const NdtPose& T, double pose16[16]) {
-    for (int i = 0; i < 16; ++i) pose16[i] = 0;
-    for (int rr = 0; rr < 3; ++rr) { for (int c = 0; c < 3; ++c) pose16[c * 4 + rr] = (double)T.R[rr * 3 + c]; pose16[12 + rr] = (double)T.t[rr]; }
-    pose16[15] = 1.0;
-}
 int pcr_ndt_opt_request(const pcr_ndt_opt* o, int* kind, double p6[6], double pose16[16]) {
     if (!o || !kind) return 1;
     *kind = o->c.done ? kNdtPassNone : o->c.kind;
@@ -2634,15 +2533,15 @@ int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t strid
         if (h->have_halo) shard_extent(h, ft.ext_lo, ft.ext_hi);
     }
     h->seq += 1.0;
-    H_TRY(fitness_launch(*fit_grid, d_src, n_src, stride_bytes / 4, pose, max_sq, h->vg_partials.as<double>(), h->out32_dev, h->stream, h->seq,
+    H_TRY(fitness_launch(*fit_grid, d_src, n_src, stride_bytes / 4, pose, max_sq, h->vg_partials.as<double>(), h->out32.dev, h->stream, h->seq,
                          h->use_tile ? &ft : nullptr));
-    if (wait_result(h, &h->out32_host[31], h->seq)) return 1;
-    if (sharded(h) && ranks_allreduce(h, h->out32_host, 3)) return 1;
-    const double cnt = h->out32_host[1];
-    *score = cnt > 0 ? h->out32_host[0] / cnt : -1.0;      // align.cpp:56-59
+    if (wait_result(h, &h->out32.host[31], h->seq)) return 1;
+    if (sharded(h) && ranks_allreduce(h, h->out32.host, 3)) return 1;
+    const double cnt = h->out32.host[1];
+    *score = cnt > 0 ? h->out32.host[0] / cnt : -1.0;      // align.cpp:56-59
     if (n_in) *n_in = (int64_t)cnt;
-    if (h->use_tile && h->out32_host[2] > 0) return fail(h, "sharded fitness: a source point's nearest map point may lie beyond this rank's halo");
-    if (h->out32_host[2] > 0) { *score = -1.0; if (n_in) *n_in = 0; return fail(h, cut_fitness_message(h->out32_host[2])); }
+    if (h->use_tile && h->out32.host[2] > 0) return fail(h, "sharded fitness: a source point's nearest map point may lie beyond this rank's halo");
+    if (h->out32.host[2] > 0) { *score = -1.0; if (n_in) *n_in = 0; return fail(h, cut_fitness_message(h->out32.host[2])); }
     return 0;
 }
 
@@ -2731,15 +2630,12 @@ int pcr_comm_peer_export(pcr_handle* h, void* ipc_handle64) {
         const hipError_t e = hipExtMallocWithFlags((void**)&h->peer_own, bytes, hipDeviceMallocFinegrained);
         if (e != hipSuccess) { (void)hipGetLastError(); h->peer_own = nullptr; return fail(h, std::string("peer exchange: no fine-grained device memory for the receive buffer (") + hipGetErrorString(e) + ")"); }
     }
-    if (!h->peer_status_host) {
-        H_TRY(hipHostMalloc((void**)&h->peer_status_host, 64, hipHostMallocMapped));
-        H_TRY(hipHostGetDevicePointer((void**)&h->peer_status_dev, h->peer_status_host, 0));
-    }
+    H_TRY(h->peer_status.ensure(16));      // (64 bytes)
     // EVERY export starts a session from nothing: sequence words of an earlier session could otherwise match the new one's.  The ranks share their
     // handles only after every rank has exported (that exchange is the barrier): no peer writes into this buffer before it has been cleared.
     H_TRY(hipMemset(h->peer_own, 0, bytes));
     H_TRY(hipDeviceSynchronize());
-    *h->peer_status_host = 0;
+    *h->peer_status.host = 0;
     h->peer_exported = true;
     hipIpcMemHandle_t mh;
     H_TRY(hipIpcGetMemHandle(&mh, h->peer_own));
@@ -2770,7 +2666,7 @@ int pcr_comm_init_peer(pcr_handle* h, const void* ipc_handles, int rank, int nra
         }
         h->peer.buf[p] = (double*)mapped;
     }
-    h->peer.rank = rank; h->peer.nranks = nranks; h->peer.status = h->peer_status_dev;
+    h->peer.rank = rank; h->peer.nranks = nranks; h->peer.status = h->peer_status.dev;
     h->rank = rank; h->nranks = nranks;
     h->peer_seq = 0.0;
     h->peer_on = true; h->peer_broken = false;

@@ -64,7 +64,7 @@ struct GridView {            // what kernels need to query the index
 
 static constexpr int kPad = 2;           // pad cells per side (see grid_index.hip)
 // progress word of the device-resident optimisers (NdtOut / VgOut): call number * kProgressWindow + passes consumed.  The pass budget
-// of a call ((ndt_max_iters + 3) * 13 + 5, vgicp_max_iters * lm_inner + 3) must stay inside the window: checked where it is computed.
+// of a call ((ndt_max_iters + 3) * 13 + 5, vgicp_max_iters * lm_inner + 3) must stay inside the window: checked by pace_passes (capi.hip).
 static constexpr double kProgressWindow = 1048576.0;
 static constexpr int kBBoxBlocks = 256;  // partial bounding boxes
 
@@ -140,9 +140,15 @@ struct LoamArgs {
 };
 
 // host-side launchers (grid_index.hip / loam.hip)
+// A device allocation that frees itself with its owner; not copyable, so nothing else frees it too.  GridIndex and CovScratch, made
+// of these, are freed and kept from copies the same way.
 struct DeviceBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DeviceBuf() = default;
+    DeviceBuf(const DeviceBuf&) = delete;
+    DeviceBuf& operator=(const DeviceBuf&) = delete;
+    ~DeviceBuf() { release(); }
     hipError_t reserve(size_t bytes);
     void release();
     template <class T> T* as() const { return static_cast<T*>(p); }

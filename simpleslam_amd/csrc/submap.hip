@@ -70,6 +70,10 @@ __global__ __launch_bounds__(256) void submap_transform_pack_kernel(const float*
 
 struct Buf {
     void* p = nullptr; size_t cap = 0;
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { release(); }
     // keep: the contents move along (the key-frame store); the other buffers are written anew by every assembly
     hipError_t reserve(size_t bytes, bool keep = true) {
         if (bytes <= cap) return hipSuccess;
@@ -142,8 +146,7 @@ pcr_map* pcr_map_create(int device) {
 void pcr_map_destroy(pcr_map* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    pcr_destroy(m->filter);           // (first: it waits for whatever is still queued on its stream -- an assembly nobody collected reads the buffers below)
-    m->store.release(); m->concat.release(); m->submap.release(); m->desc.release();
+    pcr_destroy(m->filter);           // (first: it waits for whatever is still queued on its stream -- an assembly nobody collected reads the buffers m holds)
     if (m->desc_host) (void)hipHostFree(m->desc_host);
     delete m;
 }
