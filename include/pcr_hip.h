@@ -416,6 +416,35 @@ int pcr_get_params(const pcr_handle* h, pcr_params* out);
 int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double pose[16],
                       double max_sq, double* score, int64_t* n_in);
 
+/* ---- Neighbour queries on the kept target ---------------------------------------------------------------------------------------------
+ * The two operations of the reference's spatial index, nanoflann::PointCloudKdtree (third_parties/nanoflann/include/nanoflann/
+ * pcl_adaptor.hpp:47-78: nearestKSearch, radiusSearch), asked of the index this library keeps in HBM: the handle's kept target
+ * (pcr_set_target, or a host target of pcr_scan2map), on a handle of any method, always over the FULL cloud (a target that the last
+ * pcr_scan2map prepared for its scan's region only is prepared in full first, as pcr_align does).
+ * Semantics: float coordinates widened to double, d2 = dx*dx + dy*dy + dz*dz in double, added in that order -- the reference's
+ * metric_L2_Simple with Scalar = double, bit for bit.  idx is a point's position in the cloud the target was set from; points with a
+ * coordinate that is not finite are not indexed and do not renumber the others.  Results ascend by (d2, idx): ties go to the lower
+ * index (nanoflann's tie order follows its tree walk and is not reproduced).
+ * queries: n_q records of stride_bytes (x, y, z floats first; 16 or 32 bytes in the reference's clouds), host or device memory.  The
+ * outputs are host arrays.  Neither call changes what a later registration computes.  Sharded handles, handles with a query tile, and
+ * an index that was cut to a region of interest (a target whose box cannot be tabulated) are refused with a message. */
+#define PCR_KNN_MAX_K 32
+
+/* The k nearest target points of every query, 1 <= k <= PCR_KNN_MAX_K, with no range gate.  Row q of idx / d2 (k entries) ascends by
+ * (d2, idx); when the target holds fewer than k points, and for a query with a coordinate that is not finite, the rest of the row is
+ * idx = -1, d2 = +inf. */
+int pcr_knn(pcr_handle* h, const void* queries, size_t n_q, size_t stride_bytes, int on_device, int k, int64_t* idx, double* d2);
+
+/* The target points with d2 < radius * radius (strict, the square taken in double: RadiusResultSet::addPoint, pcl_adaptor.hpp:65) of
+ * every query; radius finite and > 0.  Query q's results are idx / d2 [offsets[q], offsets[q + 1]); offsets (n_q + 1 entries) and
+ * *n_total = offsets[n_q] are written whenever the search itself ran, and the counts are exact.  capacity: entries idx and d2 hold.
+ * capacity < *n_total: nothing is written to idx / d2, the call returns 1 with a message that names both numbers, and the caller
+ * sizes the arrays and calls again (the pcr_reloc_hypotheses pattern; idx and d2 may be NULL when capacity is 0).
+ * sorted = 1: every segment ascends by (d2, idx).  sorted = 0: the order inside a segment is unspecified.
+ * A query with a coordinate that is not finite has no results. */
+int pcr_radius_search(pcr_handle* h, const void* queries, size_t n_q, size_t stride_bytes, int on_device, double radius, int sorted,
+                      size_t capacity, uint64_t* offsets, int64_t* idx, double* d2, size_t* n_total);
+
 /* ---- Relocalisation from a coarse pose ----------------------------------------------------------------------------------------------
  * The caller: the localisation program's operator sets the robot's pose by a click (/initialpose, dataproxy/src/RelocDataProxy.cpp:34-48)
  * and LidarOdometry::generateOdom takes that click as the initial guess of ONE scan2Map (frontend/src/LidarOdometry.cpp:67-77, 121-126,

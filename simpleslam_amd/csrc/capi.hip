@@ -98,6 +98,7 @@ struct pcr_handle {
     // source
     DeviceBuf src_stage;
     DeviceBuf rl_poses, rl_part, rl_out, rl_src;   // pcr_fitness_batch: the poses in float, the [pose][chunk] partials, the sums; pcr_relocalize: its staged host source
+    DeviceBuf kq_idx, kq_d2, kq_idx2, kq_d22, kq_counts, kq_offsets;      // pcr_knn / pcr_radius_search: results (radius, sorted: filled into one pair, sorted into the other), counts, offsets
     GridIndex vf_grid;               // pcl::VoxelGrid lattice of the cloud being down-sampled (pcr_voxel_filter)
     DeviceBuf vf_in, vf_out, vf_head, vf_sums, vf_count;
 
@@ -2864,6 +2865,21 @@ void reloc_point_fitness_at(pcr_handle* h, const double pose[16]) {
     if (h->fit_pending) { memcpy(h->fit_pose, pose, sizeof h->fit_pose); h->fitness = 1.7976931348623157e308; }
 }
 
+// pcr_knn / pcr_radius_search: the full index of the kept target (prepared in full first, as pcr_relocalize does), its header checked on the host
+int query_index_for(pcr_handle* h, const char* who, size_t n_q, size_t stride_bytes, const GridIndex** grid) {
+    if (!h->have_target || !h->grid.valid) return fail(h, std::string(who) + ": no kept target: call pcr_set_target first");
+    if (batch_preconditions(h, n_q, stride_bytes)) { h->err = std::string(who) + ": " + h->err; return 1; }
+    if (ensure_full_target(h)) return 1;
+    if (fit_grid_for(h, grid)) return 1;
+    GridHeader hdr;
+    H_TRY(hipMemcpyAsync(&hdr, (*grid)->header.p, sizeof hdr, hipMemcpyDeviceToHost, h->stream));
+    H_TRY(hipStreamSynchronize(h->stream));
+    if (hdr.overflow || hdr.stale || (*grid)->filtered) return fail(h, std::string(who) + ": the target index is not complete (internal)");
+    if (hdr.clamped)
+        return fail(h, std::string(who) + ": the target's box cannot be tabulated and its index was cut to the bulk of the cloud: an exact query needs every point");
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2883,6 +2899,73 @@ int pcr_fitness_batch(pcr_handle* h, const void* src, size_t n_src, size_t strid
     const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
     return fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, poses, K, max_sq, score_points, scores, n_in);
+}
+
+int pcr_knn(pcr_handle* h, const void* queries, size_t n_q, size_t stride_bytes, int on_device, int k, int64_t* idx, double* d2) {
+    if (!h) return 1;
+    h->err.clear();
+    if (k < 1 || k > PCR_KNN_MAX_K) return fail(h, "pcr_knn: k = " + std::to_string(k) + " is outside 1 .. PCR_KNN_MAX_K (" + std::to_string(PCR_KNN_MAX_K) + ")");
+    if (n_q && (!queries || !idx || !d2)) return fail(h, "pcr_knn: queries, idx or d2 is NULL");
+    const GridIndex* grid = nullptr;
+    if (query_index_for(h, "pcr_knn", n_q, stride_bytes, &grid)) return 1;
+    if (n_q == 0) return 0;
+    const float* d_q = (const float*)queries;
+    if (!on_device && stage_host(h, &h->src_stage, queries, n_q, stride_bytes, &d_q)) return 1;
+    // in chunks: the results of 2^20 queries at k = 32 are 512 MB
+    const size_t chunk = size_t(1) << 20;
+    H_TRY(h->kq_idx.reserve(std::min(n_q, chunk) * (size_t)k * sizeof(int64_t)));
+    H_TRY(h->kq_d2.reserve(std::min(n_q, chunk) * (size_t)k * sizeof(double)));
+    for (size_t q0 = 0; q0 < n_q; q0 += chunk) {
+        const size_t m = std::min(chunk, n_q - q0);
+        H_TRY(knn_query_launch(*grid, d_q + q0 * (stride_bytes / 4), m, stride_bytes / 4, k, h->kq_idx.as<int64_t>(), h->kq_d2.as<double>(), h->stream));
+        H_TRY(hipMemcpyAsync(idx + q0 * (size_t)k, h->kq_idx.p, m * (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+        H_TRY(hipMemcpyAsync(d2 + q0 * (size_t)k, h->kq_d2.p, m * (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        H_TRY(hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}
+
+int pcr_radius_search(pcr_handle* h, const void* queries, size_t n_q, size_t stride_bytes, int on_device, double radius, int sorted,
+                      size_t capacity, uint64_t* offsets, int64_t* idx, double* d2, size_t* n_total) {
+    if (!h) return 1;
+    h->err.clear();
+    if (!(radius > 0.0) || !std::isfinite(radius)) return fail(h, "pcr_radius_search: radius must be finite and > 0");
+    if (!offsets || !n_total) return fail(h, "pcr_radius_search: offsets or n_total is NULL");
+    if (n_q && !queries) return fail(h, "pcr_radius_search: queries is NULL");
+    if (capacity && (!idx || !d2)) return fail(h, "pcr_radius_search: idx or d2 is NULL with a nonzero capacity");
+    if (n_q > 0x7fffffffull) return fail(h, "pcr_radius_search: more than 2^31 - 1 queries in one call");
+    const GridIndex* grid = nullptr;
+    if (query_index_for(h, "pcr_radius_search", n_q, stride_bytes, &grid)) return 1;
+    const float* d_q = (const float*)queries;
+    if (!on_device && n_q && stage_host(h, &h->src_stage, queries, n_q, stride_bytes, &d_q)) return 1;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "offsets are 64-bit");
+    H_TRY(h->kq_counts.reserve((n_q + 1) * sizeof(uint32_t)));
+    H_TRY(h->kq_offsets.reserve((n_q + 1) * sizeof(uint64_t)));
+    H_TRY(radius_count_launch(*grid, d_q, n_q, stride_bytes / 4, radius, h->kq_counts.as<uint32_t>(), h->kq_offsets.as<unsigned long long>(), h->stream));
+    H_TRY(hipMemcpyAsync(offsets, h->kq_offsets.p, (n_q + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    H_TRY(hipStreamSynchronize(h->stream));
+    const uint64_t total = offsets[n_q];
+    *n_total = (size_t)total;
+    if (total > (uint64_t)capacity)
+        return fail(h, "pcr_radius_search: the arrays hold " + std::to_string(capacity) + " entries, the search has " + std::to_string(total) +
+                       " results: size idx and d2 for *n_total and call again");
+    if (total == 0) return 0;
+    const size_t t = (size_t)total;
+    H_TRY(h->kq_idx.reserve(t * sizeof(int64_t)));
+    H_TRY(h->kq_d2.reserve(t * sizeof(double)));
+    H_TRY(radius_fill_launch(*grid, d_q, n_q, stride_bytes / 4, radius, h->kq_offsets.as<unsigned long long>(), h->kq_idx.as<int64_t>(), h->kq_d2.as<double>(), h->stream));
+    const void *r_idx = h->kq_idx.p, *r_d2 = h->kq_d2.p;
+    if (sorted) {
+        H_TRY(h->kq_idx2.reserve(t * sizeof(int64_t)));
+        H_TRY(h->kq_d22.reserve(t * sizeof(double)));
+        H_TRY(radius_sort_launch(n_q, h->kq_offsets.as<unsigned long long>(), h->kq_idx.as<int64_t>(), h->kq_d2.as<double>(), h->kq_idx2.as<int64_t>(),
+                                 h->kq_d22.as<double>(), h->stream));
+        r_idx = h->kq_idx2.p; r_d2 = h->kq_d22.p;
+    }
+    H_TRY(hipMemcpyAsync(idx, r_idx, t * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    H_TRY(hipMemcpyAsync(d2, r_d2, t * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    H_TRY(hipStreamSynchronize(h->stream));
+    return 0;
 }
 
 void pcr_reloc_default_params(pcr_reloc_params* p) {

@@ -364,6 +364,18 @@ struct RelocSum { double sum; unsigned long long cnt, viol, pad_; };
 hipError_t fitness_batch_launch(const GridIndex& grid, const float* d_src, size_t n_src, size_t stride_floats, size_t m, const float* d_poses,
                                 size_t n_poses, double max_sq, RelocPart* d_part, RelocSum* d_out, hipStream_t s);
 
+// pcr_knn / pcr_radius_search (knn_query.hip): exact queries in f64 on an index that holds every point of its cloud (any lattice kind; the
+// caller has checked the header: not overflowing, stale or cut).  d_idx / d_d2 of the k-NN: n_q x k, ascending by (d2, index), tails -1 / +inf.
+// The radius search in passes: the counts and their exclusive scan (d_offsets: n_q + 1), the fill of every query's segment, its sort by
+// (d2, index) from one pair of arrays into another.
+hipError_t knn_query_launch(const GridIndex& grid, const float* d_q, size_t n_q, size_t stride_floats, int k, int64_t* d_idx, double* d_d2, hipStream_t s);
+hipError_t radius_count_launch(const GridIndex& grid, const float* d_q, size_t n_q, size_t stride_floats, double radius, uint32_t* d_counts,
+                               unsigned long long* d_offsets, hipStream_t s);
+hipError_t radius_fill_launch(const GridIndex& grid, const float* d_q, size_t n_q, size_t stride_floats, double radius, const unsigned long long* d_offsets,
+                              int64_t* d_idx, double* d_d2, hipStream_t s);
+hipError_t radius_sort_launch(size_t n_q, const unsigned long long* d_offsets, const int64_t* d_in_idx, const double* d_in_d2, int64_t* d_out_idx,
+                              double* d_out_d2, hipStream_t s);
+
 // pcl::VoxelGrid on the device (voxel_filter.hip); grid must have been built with pcl_mode = 1
 // (two launches queued behind the build; they read the header themselves and do nothing when it says overflow, stale or empty.  d_inten: n floats,
 //  d_sums: n / 2048 + 2 words, d_wave: voxel_filter_wave_bytes(n); result_mapped: page-locked host memory the last block writes -- valid once the stream has been synchronised)

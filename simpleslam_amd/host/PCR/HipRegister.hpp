@@ -281,6 +281,69 @@ public:
     HipRegister& inner() { return *reg_; }
 };
 
+// The reference's spatial index, nanoflann::PointCloudKdtree<PointType, double> (third_parties/nanoflann/include/nanoflann/pcl_adaptor.hpp:11-78),
+// over the index a registrar keeps in HBM: the same two member names and argument orders -- one query of three doubles, std::vector outputs --
+// so that a call site such as test/align.cpp:47 changes its type and nothing else.  The cloud is the registrar's kept target: setInputCloud
+// hands it to the adapter's own handle (pcr_set_target); an adapter made over a registrar's handle queries the target that registrar holds.
+// Answers: pcr_knn / pcr_radius_search -- nanoflann's squared distances in double, ascending by (distance, index).  Failures throw.
+// Batched overloads take n records of stride_bytes (x, y, z floats first) and answer every query in one call.
+class PointCloudKdtree {
+    pcr_handle* h_ = nullptr;
+    bool own_ = false;
+public:
+    PointCloudKdtree() : h_(pcr_create("loam", nullptr)), own_(true) { if (!h_) throw std::runtime_error(pcr_last_error(nullptr)); }
+    explicit PointCloudKdtree(pcr_handle* h) : h_(h) {}
+    explicit PointCloudKdtree(HipRegister& reg) : h_(reg.handle()) {}
+    PointCloudKdtree(const PointCloudKdtree&) = delete;
+    PointCloudKdtree& operator=(const PointCloudKdtree&) = delete;
+    ~PointCloudKdtree() { if (own_) pcr_destroy(h_); }
+
+    void setInputCloud(const PC_cPtr& cloud) {
+        if (pcr_set_target(h_, cloud->points.data(), cloud->size(), sizeof(PointXYZI), 0)) throw std::runtime_error(pcr_last_error(h_));
+    }
+    size_t nearestKSearch(double* point, int k, std::vector<size_t>& k_indices, std::vector<double>& k_sqr_distances) const {
+        const float q[4] = {(float)point[0], (float)point[1], (float)point[2], 0.f};
+        std::vector<int64_t> idx((size_t)(k > 0 ? k : 0));
+        k_sqr_distances.assign(idx.size(), 0.0);
+        if (pcr_knn(h_, q, 1, sizeof q, 0, k, idx.data(), k_sqr_distances.data())) throw std::runtime_error(pcr_last_error(h_));
+        size_t n = 0;
+        while (n < idx.size() && idx[n] >= 0) ++n;
+        k_indices.assign(idx.size(), 0);
+        for (size_t i = 0; i < n; ++i) k_indices[i] = (size_t)idx[i];
+        return n;      // KNNResultSet::size(): the entries found
+    }
+    size_t radiusSearch(double* point, double radius, std::vector<size_t>& k_indices, std::vector<double>& k_sqr_distances, bool sorted = false) const {
+        const float q[4] = {(float)point[0], (float)point[1], (float)point[2], 0.f};
+        std::vector<uint64_t> offsets;
+        std::vector<int64_t> idx;
+        radiusSearch(q, 1, sizeof q, radius, offsets, idx, k_sqr_distances, sorted);
+        k_indices.assign(idx.begin(), idx.end());
+        return idx.size();
+    }
+    // n queries at once: idx / d2 hold n x k entries, row by row (idx -1, d2 +inf where the target has fewer than k points)
+    void nearestKSearch(const void* queries, size_t n, size_t stride_bytes, int k, std::vector<int64_t>& idx, std::vector<double>& d2,
+                        bool on_device = false) const {
+        idx.assign(n * (size_t)(k > 0 ? k : 0), -1);
+        d2.assign(idx.size(), 0.0);
+        if (pcr_knn(h_, queries, n, stride_bytes, on_device ? 1 : 0, k, idx.data(), d2.data())) throw std::runtime_error(pcr_last_error(h_));
+    }
+    // ... query q's neighbours are idx / d2 [offsets[q], offsets[q + 1]): counted first, then fetched into arrays of that size
+    void radiusSearch(const void* queries, size_t n, size_t stride_bytes, double radius, std::vector<uint64_t>& offsets, std::vector<int64_t>& idx,
+                      std::vector<double>& d2, bool sorted = false, bool on_device = false) const {
+        offsets.assign(n + 1, 0);
+        size_t total = 0;
+        // (sized for what the vectors already hold: a repeated search is answered by one call)
+        idx.resize(std::min(idx.size(), d2.size())); d2.resize(idx.size());
+        int rc = pcr_radius_search(h_, queries, n, stride_bytes, on_device ? 1 : 0, radius, sorted ? 1 : 0, idx.size(), offsets.data(), idx.data(), d2.data(), &total);
+        if (rc && total > idx.size()) {
+            idx.resize(total); d2.resize(total);
+            rc = pcr_radius_search(h_, queries, n, stride_bytes, on_device ? 1 : 0, radius, sorted ? 1 : 0, total, offsets.data(), idx.data(), d2.data(), &total);
+        }
+        if (rc) throw std::runtime_error(pcr_last_error(h_));
+        idx.resize(total); d2.resize(total);
+    }
+};
+
 // frontend/src/LidarOdometry.cpp:44-54
 inline PointCloudRegister::Ptr makeRegister(const std::string& pcr_type) {
     if (pcr_type == "loam") return std::make_shared<LoamRegister>();

@@ -1,10 +1,13 @@
 // kdtree_bench.cpp -- counterpart of the reference's test/benchmark/kdtree.cpp:58-127 (Google Benchmark of PCL-FLANN vs nanoflann:
 // index build, k = 5 and radius queries) for the spatial index of this library:
-//   kdtree_bench <map.f32> [queries.f32] [repeats]
-// prints the build time of the uniform-grid index over the map (seconds, device timeline) and the time per exact 5-NN query
-// (ns/query; the reference benchmarks one query at the origin in a loop, a GPU answers a whole cloud of queries per call: the map's
-// own points, or the given query cloud).  The reference's nanoflann on the same map is timed by bench.py's cpu_baseline leg
-// ("index": "nanoflann(_ref)") -- this program never touches the checker.
+//   kdtree_bench <map.f32> [queries.f32] [repeats] [k radius]
+// prints the build time of the uniform-grid index over the map (seconds, host clock around pcr_set_target) and the time per query of
+// one LOAM linearisation -- its 5-NN search inside the 1 m gate with the plane fit and the row (ns/query; the reference benchmarks one
+// query at the origin in a loop, a GPU answers a whole cloud of queries per call: the map's own points, or the given query cloud).
+// With k and radius two more lines follow: the general queries of the index, ungated and exact -- ns/query of pcr_knn at that k, and
+// ns/query and the mean number of neighbours of pcr_radius_search (sorted) at that radius, host clock around the call, best of
+// `repeats`.  The reference's nanoflann on the same map is timed by bench.py's cpu_baseline leg ("index": "nanoflann(_ref)") and by
+// scripts/knn_query_bench.py -- this program never touches the checker.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -25,7 +28,7 @@ static std::vector<float> load(const char* path) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s <map.f32> [queries.f32] [repeats]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s <map.f32> [queries.f32] [repeats] [k radius]\n", argv[0]); return 2; }
     try {
         const std::vector<float> map = load(argv[1]);
         const std::vector<float> qry = argc > 2 ? load(argv[2]) : map;
@@ -55,6 +58,28 @@ int main(int argc, char** argv) {
         std::printf("grid index: %zu points, build (host copy + index, best of %d) %.6f s\n", n_map, reps, build_s);
         std::printf("k = 5 exact queries inside the 1 m gate (+ plane fit and row, one linearisation): %zu queries, %.1f ns/query, %zu with 5 neighbours\n",
                     n_q, 1e9 * query_s / (double)n_q, found);
+        if (argc > 5) {
+            const int k = std::atoi(argv[4]);
+            const double radius = std::atof(argv[5]);
+            PCR::PointCloudKdtree tree(h);
+            std::vector<int64_t> idx;
+            std::vector<double> d2;
+            std::vector<uint64_t> offsets;
+            double knn_s = 1e30, rad_s = 1e30;
+            for (int r = 0; r < reps; ++r) {
+                const auto t0 = std::chrono::steady_clock::now();
+                tree.nearestKSearch(qry.data(), n_q, 16, k, idx, d2);
+                knn_s = std::min(knn_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+            }
+            for (int r = 0; r < reps; ++r) {
+                const auto t0 = std::chrono::steady_clock::now();
+                tree.radiusSearch(qry.data(), n_q, 16, radius, offsets, idx, d2, true);
+                rad_s = std::min(rad_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+            }
+            std::printf("pcr_knn k = %d: %zu queries, %.1f ns/query\n", k, n_q, 1e9 * knn_s / (double)n_q);
+            std::printf("pcr_radius_search r = %g: %zu queries, %.1f ns/query, mean count %.2f\n", radius, n_q, 1e9 * rad_s / (double)n_q,
+                        n_q ? (double)idx.size() / (double)n_q : 0.0);
+        }
         pcr_destroy(h);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());

@@ -63,7 +63,7 @@ ABI_SYMBOLS = [
     "pcr_ndt_opt_create", "pcr_ndt_opt_destroy", "pcr_ndt_opt_request", "pcr_ndt_opt_feed", "pcr_ndt_opt_result", "pcr_ndt_opt_counts",
     "pcr_vgicp_opt_create", "pcr_vgicp_opt_destroy", "pcr_vgicp_opt_request", "pcr_vgicp_opt_feed", "pcr_vgicp_opt_result",
     "pcr_sc_default_params", "pcr_sc_create", "pcr_sc_destroy", "pcr_sc_last_error", "pcr_sc_size", "pcr_sc_add", "pcr_sc_descriptor", "pcr_sc_distance",
-    "pcr_sc_query", "pcr_fitness_batch", "pcr_reloc_default_params", "pcr_reloc_hypotheses", "pcr_relocalize",
+    "pcr_sc_query", "pcr_knn", "pcr_radius_search", "pcr_fitness_batch", "pcr_reloc_default_params", "pcr_reloc_hypotheses", "pcr_relocalize",
     "pcr_sc_distances", "pcr_global_reloc_default_params", "pcr_global_reloc_hypotheses", "pcr_relocalize_global",
 ]
 
@@ -208,6 +208,9 @@ def load_library():
     L.pcr_sc_descriptor.argtypes = [vp, C.c_size_t, vp, vp, vp]
     L.pcr_sc_distance.argtypes = [vp, C.c_size_t, C.c_size_t, dp, ip]
     L.pcr_sc_query.argtypes = [vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_float), dp]
+    L.pcr_knn.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int64), dp]
+    L.pcr_radius_search.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), dp,
+                                    C.POINTER(C.c_size_t)]
     L.pcr_fitness_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, C.c_size_t, C.c_double, C.c_size_t, dp, C.POINTER(C.c_int64)]
     L.pcr_reloc_default_params.argtypes = [C.POINTER(RelocParams)]
     L.pcr_reloc_default_params.restype = None
@@ -554,6 +557,33 @@ class PointCloudRegister:
         self._check(self._lib.pcr_fitness_batch(self._h, p, n, s, dev, cm.ctypes.data_as(dp), K, float(max_sq), int(score_points),
                                                 scores.ctypes.data_as(dp), n_in.ctypes.data_as(C.POINTER(C.c_int64))))
         return scores, n_in
+
+    def knn(self, queries, k):
+        """pcr_knn: the k nearest points of the kept target (setTarget) of every query -> (idx (n, k) int64, d2 (n, k) float64), each row
+        ascending by (d2, idx); nanoflann's f64 distances on float coordinates, bit for bit.  Missing neighbours: idx -1, d2 +inf."""
+        p, n, s, dev, _k = _cloud(queries)
+        k = int(k)
+        idx = np.zeros((n, max(k, 0)), np.int64)
+        d2 = np.zeros((n, max(k, 0)), np.float64)
+        self._check(self._lib.pcr_knn(self._h, p, n, s, dev, k, idx.ctypes.data_as(C.POINTER(C.c_int64)), d2.ctypes.data_as(C.POINTER(C.c_double))))
+        return idx, d2
+
+    def radiusSearch(self, queries, radius, sorted=True):
+        """pcr_radius_search: the points of the kept target with d2 < radius^2 of every query -> (offsets (n + 1,) uint64, idx int64, d2 float64);
+        query q's results are [offsets[q], offsets[q + 1]), ascending by (d2, idx) when sorted.  Sized by a first call that only counts."""
+        p, n, s, dev, _k = _cloud(queries)
+        offsets = np.zeros(n + 1, np.uint64)
+        total = C.c_size_t(0)
+        op, ip, dp = C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+        rc = self._lib.pcr_radius_search(self._h, p, n, s, dev, float(radius), int(bool(sorted)), 0, offsets.ctypes.data_as(op), None, None, C.byref(total))
+        if rc != 0 and total.value == 0:
+            self._check(rc)
+        idx = np.zeros(total.value, np.int64)
+        d2 = np.zeros(total.value, np.float64)
+        if total.value:
+            self._check(self._lib.pcr_radius_search(self._h, p, n, s, dev, float(radius), int(bool(sorted)), total.value, offsets.ctypes.data_as(op),
+                                                    idx.ctypes.data_as(ip), d2.ctypes.data_as(dp), C.byref(total)))
+        return offsets, idx, d2
 
     def relocalize(self, src, pose, **params):
         """pcr_relocalize from the coarse pose `pose` (4x4, updated in place as align() does) against the kept target (setTarget):
