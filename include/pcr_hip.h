@@ -254,6 +254,47 @@ int pcr_map_wait(pcr_map* m, size_t* n_submap);
 int pcr_map_update_window(pcr_map* m, long long key, int search_num, double grid_size, size_t* n_submap);
 const void* pcr_map_submap(const pcr_map* m, size_t* n, size_t* stride_bytes);
 int pcr_map_submap_indices(const pcr_map* m, int64_t* idx, size_t capacity, size_t* n);
+/* ---- the store's life beyond the front end: what the back end does to MapManager's key frames ----
+ * Backend::optimHandler (backend/src/Backend.cpp:315-318): replace the poses of key frames first .. first+count-1 (16 doubles each,
+ * column-major).  Fails, leaving the store as it was, when first + count exceeds the key-frame count, when poses is NULL with count > 0, and
+ * on a view; count == 0 is a no-op.  No assembled sub-map (the parent's or a view's), no selection and no generation is touched -- the
+ * reference's mSubmap is left alone until the next updateMap too; the next pcr_map_update* on the parent or on a view selects by the new
+ * translations and transforms by the new poses cast to float.  An assembly that is queued (pcr_map_update_begin, on the parent or on a view)
+ * was selected under the old poses and finishes as such: it is waited for first. */
+int pcr_map_set_poses(pcr_map* m, size_t first, size_t count, const double* poses);
+/* Key frame i as it is stored (parent or view): device pointer -- valid until the next call that changes the store -- point count, stride and
+ * pose; the bytes are exactly those stored, stride_bytes / 4 floats per point.  NULL with pcr_map_last_error for an index out of range; NULL
+ * with *n = 0 for a key frame of 0 points.  This is lc_scan_ of LoopClosureManager::lcHandler (LoopClosureManager.cpp:92) without a host copy. */
+const void* pcr_map_keyframe(const pcr_map* m, size_t i, size_t* n, size_t* stride_bytes, double pose[16]);
+/* The same to host memory.  *n is always the key frame's size; when capacity_points < *n the call fails and writes nothing else. */
+int pcr_map_read_keyframe(const pcr_map* m, size_t i, void* out, size_t capacity_points, size_t* n, double pose[16]);
+/* MapManager::saveKfs (frontend/src/MapManager.cpp:211) and the loading constructor (:46): every key frame i >= first, in ascending order,
+ * is replaced by what pcr_voxel_filter gives for its cloud at grid_size, byte for byte (ascending voxel index; a grid too fine for PCL's
+ * integer voxel index leaves the key frame unchanged).  Key frames before `first` keep their offsets and bytes, the later ones are packed
+ * directly behind them and the store shrinks; its device memory is kept.  *store_points_after = points in the store afterwards.
+ * first == count is a no-op; first > count, a non-positive grid_size and a call on a view are errors.  Sub-maps already assembled, their
+ * selections and generations are untouched; queued assemblies on the parent and on all views are waited for first (they read the store).
+ * Should a filter fail, the key frames in front of the failing one stay filtered and every key frame stays readable. */
+int pcr_map_downsample_keyframes(pcr_map* m, size_t first, double grid_size, size_t* store_points_after);
+/* The session's product (test/vis_globalmap.cpp:33-66, and the file MapManager(pcd_file) loads): EVERY key frame selected, otherwise exactly
+ * pcr_map_update -- a new generation, transform, concatenate, voxel-filter; more than 0xfffffff0 points are an error, and a map whose extent
+ * is beyond pcl::VoxelGrid's index range at grid_size comes back unfiltered, as PCL returns it.  Parent or view. */
+int pcr_map_update_all(pcr_map* m, double grid_size, size_t* n_submap);
+/* A second (third, ...) sub-map over the SAME key frames: LoopClosureManager's lc_map_ (LoopClosureManager.cpp:85-99) beside MapManager's
+ * mSubmap.  The view has its own stream and filter, concatenation, sub-map, selection, queued-assembly state, id and generation, on the
+ * parent's device; it reads the parent's key frames, poses and point layout.  NULL on failure (pcr_map_last_error(parent)).
+ *   On a view work: pcr_map_update, _update_begin, _wait, _update_window, _update_all, _submap, _submap_indices, _generation, _keyframes,
+ *   _keyframe, _read_keyframe, pcr_scan2map_submap, pcr_map_destroy.
+ *   On a view fail, with a message that says it is a view: pcr_map_add_keyframe, _clear, _set_poses, _downsample_keyframes, pcr_map_view.
+ * The parent waits for every view's queued assembly before the store moves (pcr_map_add_keyframe), shrinks (_downsample_keyframes) or is
+ * emptied (_clear); pcr_map_clear also empties every view's selection and sub-map and starts a new generation on each.
+ * pcr_map_destroy(parent) waits for its views and detaches them: a detached view fails every call with "parent destroyed", except
+ * pcr_map_destroy(view), which frees it.  pcr_map_destroy(view) unregisters it from a living parent.
+ * THREADS (the reference's mLockKF: LoopClosureManager.cpp:27,39,89, MapManager.cpp:175): a view may be driven by another thread than its
+ * parent.  Calls that change the store -- pcr_map_add_keyframe, _clear, _set_poses, _downsample_keyframes and pcr_map_destroy of the parent
+ * -- must not overlap with ANY call on a view of it: that is the caller's lock.  Sub-map calls on the parent and on its views (_update*,
+ * _wait, _submap, pcr_scan2map_submap) may overlap with each other; each single pcr_map is still used by one thread at a time. */
+pcr_map* pcr_map_view(pcr_map* parent);
 /* Identity of the store and of the sub-map it currently holds: every pcr_map_update / pcr_map_update_window starts a new
  * generation.  This is the explicit version of what the reference's registrars approximate by comparing cloud POINTERS
  * (fast_gicp_impl.hpp:83-90): a structure built for generation g is valid exactly while the map reports g. */

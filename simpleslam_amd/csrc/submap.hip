@@ -10,11 +10,15 @@
 // Key frames stay in HBM; an update is one transform+concatenate launch plus pcr_voxel_filter, and the sub-map it
 // leaves in HBM is what pcr_scan2map_device takes as `dst` -- no host copy of the map on the registration path.
 // The result does not depend on the order in which the key frames are concatenated (centroids are summed in f64).
+// The back end shares the store: Backend::optimHandler's pose updates (pcr_map_set_poses), LoopClosureManager's lc_map_ as a
+// view with a sub-map of its own (pcr_map_view), the stored key frames read back (pcr_map_keyframe, pcr_map_read_keyframe), saveKfs's in-place
+// filter (pcr_map_downsample_keyframes) and the whole map (pcr_map_update_all) -- the same transform pass and voxel filter throughout.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <atomic>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -109,10 +113,23 @@ struct pcr_map {
     bool pending = false;             // an assembly is queued on the filter's stream and has not been collected (pcr_map_update_begin): n_submap is not known yet
     uint64_t id = 0, generation = 0;  // identity of this store and of the sub-map it currently holds (every update is a new generation)
     std::string err;
+    // A view (pcr_map_view: LoopClosureManager's lc_map_ beside MapManager's mSubmap) has everything above for ITS sub-map -- filter handle and stream,
+    // concat / submap / desc buffers, selection, pending flag, id and generation -- and reads stride, store, store_floats, kfs and max_kf_points of
+    // its parent (store_of); its own copies of those stay empty.
+    pcr_map* parent = nullptr;
+    bool detached = false;            // a view whose parent has been destroyed: every call fails, pcr_map_destroy frees it
+    std::vector<pcr_map*> views;      // (parent) the views that read this store
+    std::mutex views_mu;              // guards `views`: a view may be created and destroyed from different threads
+    Buf scratch;                      // (parent) pcr_map_downsample_keyframes filters a key frame into it and copies back
 };
 
 static thread_local std::string g_map_err;
 static int mfail(pcr_map* m, const std::string& s) { if (m) m->err = s; else g_map_err = s; return 1; }
+static int mfail(const pcr_map* m, const std::string& s) { return mfail(const_cast<pcr_map*>(m), s); }
+static const pcr_map* store_of(const pcr_map* m) { return m->parent ? m->parent : m; }
+// every entry point but pcr_map_destroy: a view that outlived its parent has no store to read
+#define M_ALIVE(m) do { if ((m)->detached) return mfail(m, "parent destroyed: this view can only be destroyed"); } while (0)
+#define M_OWNER(m, what) do { if ((m)->parent) return mfail(m, std::string(what) + ": this pcr_map is a view (pcr_map_view) and cannot change the store; call it on the parent"); } while (0)
 #define M_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return mfail(m, std::string(#x) + ": " + hipGetErrorString(_e)); } while (0)
 
 // collect the queued assembly, if any: the one synchronisation of an update (and the filter's second try when the index's hints did not hold)
@@ -124,6 +141,14 @@ static int finish_pending(pcr_map* m) {
     size_t n_out = 0;
     if (pcr_internal_vf_end(m->filter, &n_out)) return mfail(m, std::string("voxel filter: ") + pcr_last_error(m->filter));
     m->n_submap = n_out;
+    return 0;
+}
+
+// Every view's queued assembly has run: its transform pass is the one thing of a view that reads the parent's store (the filter behind it reads the
+// view's own concatenation).  The view keeps its pending flag and collects the result itself.
+static int views_quiesce(pcr_map* m) {
+    std::lock_guard<std::mutex> g(m->views_mu);
+    for (pcr_map* v : m->views) M_TRY(hipStreamSynchronize(pcr_internal_stream(v->filter)));
     return 0;
 }
 
@@ -143,9 +168,32 @@ pcr_map* pcr_map_create(int device) {
     return m;
 }
 
+pcr_map* pcr_map_view(pcr_map* parent) {
+    if (!parent) { g_map_err = "map is NULL"; return nullptr; }
+    parent->err.clear();
+    if (parent->detached) { mfail(parent, "parent destroyed: this view can only be destroyed"); return nullptr; }
+    if (parent->parent) { mfail(parent, "pcr_map_view: this pcr_map is a view (pcr_map_view) and cannot change the store; call it on the parent"); return nullptr; }
+    pcr_map* v = pcr_map_create(parent->device);
+    if (!v) { mfail(parent, g_map_err); return nullptr; }
+    v->parent = parent;
+    std::lock_guard<std::mutex> g(parent->views_mu);
+    parent->views.push_back(v);
+    return v;
+}
+
 void pcr_map_destroy(pcr_map* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
+    if (m->parent) {      // a view of a living store: the parent forgets it
+        std::lock_guard<std::mutex> g(m->parent->views_mu);
+        std::vector<pcr_map*>& vs = m->parent->views;
+        vs.erase(std::remove(vs.begin(), vs.end(), m), vs.end());
+    }
+    for (pcr_map* v : m->views) {      // a store with views: what they have queued reads it -- waited for; then they are on their own
+        (void)hipStreamSynchronize(pcr_internal_stream(v->filter));
+        v->parent = nullptr; v->detached = true;
+    }
+    m->views.clear();
     pcr_destroy(m->filter);           // (first: it waits for whatever is still queued on its stream -- an assembly nobody collected reads the buffers m holds)
     if (m->desc_host) (void)hipHostFree(m->desc_host);
     delete m;
@@ -156,6 +204,8 @@ const char* pcr_map_last_error(const pcr_map* m) { return m ? m->err.c_str() : g
 int pcr_map_add_keyframe(pcr_map* m, const void* pts, size_t n, size_t stride_bytes, int on_device, const double pose[16]) {
     if (!m) return 1;
     m->err.clear();
+    M_ALIVE(m);
+    M_OWNER(m, "pcr_map_add_keyframe");
     if (n && !pts) return mfail(m, "NULL cloud with nonzero size");
     if (!pose) return mfail(m, "NULL pose");
     if (stride_bytes < 12 || stride_bytes % 4) return mfail(m, "stride_bytes must be a multiple of 4 and >= 12");
@@ -163,6 +213,7 @@ int pcr_map_add_keyframe(pcr_map* m, const void* pts, size_t n, size_t stride_by
     else if (m->stride != stride_bytes) return mfail(m, "all key frames of a map must share one point layout");
     M_TRY(hipSetDevice(m->device));
     if (finish_pending(m)) return 1;      // (a queued assembly reads the store, which may move below)
+    if (views_quiesce(m)) return 1;       // (... and so does a view's)
     const size_t nf = n * (stride_bytes / 4);
     m->max_kf_points = std::max(m->max_kf_points, n);
     // (room for a window of key frames from the first one on: a store that grows is copied, and every growth is a device-wide stop)
@@ -183,26 +234,122 @@ int pcr_map_add_keyframe(pcr_map* m, const void* pts, size_t n, size_t stride_by
 int pcr_map_clear(pcr_map* m) {
     if (!m) return 1;
     m->err.clear();
+    M_ALIVE(m);
+    M_OWNER(m, "pcr_map_clear");
     M_TRY(hipSetDevice(m->device));
     (void)finish_pending(m); m->err.clear();
     m->kfs.clear(); m->selected.clear();
     m->store_floats = 0; m->n_submap = 0;
     m->generation += 1;           // whatever was built from the previous sub-map is stale
+    std::lock_guard<std::mutex> g(m->views_mu);
+    for (pcr_map* v : m->views) {      // ... and so is every view's: waited for, dropped, a new generation
+        (void)finish_pending(v); v->err.clear();
+        v->selected.clear();
+        v->n_submap = 0;
+        v->generation += 1;
+    }
     return 0;
 }
 
 int pcr_map_keyframes(const pcr_map* m, size_t* n_keyframes) {
     if (!m || !n_keyframes) return 1;
-    *n_keyframes = m->kfs.size();
+    M_ALIVE(m);
+    *n_keyframes = store_of(m)->kfs.size();
+    return 0;
+}
+
+int pcr_map_set_poses(pcr_map* m, size_t first, size_t count, const double* poses) {
+    if (!m) return 1;
+    m->err.clear();
+    M_ALIVE(m);
+    M_OWNER(m, "pcr_map_set_poses");
+    if (first > m->kfs.size() || count > m->kfs.size() - first) return mfail(m, "pcr_map_set_poses: first + count exceeds the number of key frames");
+    if (count == 0) return 0;
+    if (!poses) return mfail(m, "NULL poses");
+    // An assembly that is queued was selected, and its descriptors were written, under the poses as they are: it finishes as such before they change.
+    M_TRY(hipSetDevice(m->device));
+    M_TRY(hipStreamSynchronize(pcr_internal_stream(m->filter)));
+    if (views_quiesce(m)) return 1;
+    for (size_t i = 0; i < count; ++i) memcpy(m->kfs[first + i].pose, poses + 16 * i, 16 * sizeof(double));
+    return 0;      // (no sub-map, selection or generation is touched: the reference's mSubmap stays what it is until the next updateMap)
+}
+
+const void* pcr_map_keyframe(const pcr_map* m, size_t i, size_t* n, size_t* stride_bytes, double pose[16]) {
+    if (n) *n = 0;
+    if (stride_bytes) *stride_bytes = 0;
+    if (!m) return nullptr;
+    if (m->detached) { mfail(m, "parent destroyed: this view can only be destroyed"); return nullptr; }
+    const pcr_map* s = store_of(m);
+    if (stride_bytes) *stride_bytes = s->stride;
+    if (i >= s->kfs.size()) { mfail(m, "key-frame index out of range"); return nullptr; }
+    const pcr_map::Kf& k = s->kfs[i];
+    if (n) *n = k.n;
+    if (pose) memcpy(pose, k.pose, 16 * sizeof(double));
+    return k.n ? static_cast<const float*>(s->store.p) + k.off_floats : nullptr;
+}
+
+int pcr_map_read_keyframe(const pcr_map* m, size_t i, void* out, size_t capacity_points, size_t* n, double pose[16]) {
+    if (!m) return 1;
+    M_ALIVE(m);
+    const pcr_map* s = store_of(m);
+    if (i >= s->kfs.size()) return mfail(m, "key-frame index out of range");
+    const pcr_map::Kf& k = s->kfs[i];
+    if (n) *n = k.n;
+    if (capacity_points < k.n) return mfail(m, "output capacity too small: the key frame holds " + std::to_string(k.n) + " points");
+    if (k.n && !out) return mfail(m, "NULL output");
+    if (pose) memcpy(pose, k.pose, 16 * sizeof(double));
+    if (k.n == 0) return 0;
+    M_TRY(hipSetDevice(m->device));
+    // (the null stream's blocking copy: whatever wrote these bytes -- pcr_map_add_keyframe, pcr_map_downsample_keyframes -- synchronised before it returned)
+    M_TRY(hipMemcpy(out, static_cast<const float*>(s->store.p) + k.off_floats, k.n * s->stride, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int pcr_map_downsample_keyframes(pcr_map* m, size_t first, double grid_size, size_t* store_points_after) {
+    if (!m) return 1;
+    m->err.clear();
+    M_ALIVE(m);
+    M_OWNER(m, "pcr_map_downsample_keyframes");
+    if (first > m->kfs.size()) return mfail(m, "pcr_map_downsample_keyframes: first exceeds the number of key frames");
+    if (!(grid_size > 0)) return mfail(m, "grid_size must be positive");
+    const size_t sf = m->stride / 4;
+    if (store_points_after) *store_points_after = sf ? m->store_floats / sf : 0;
+    if (first == m->kfs.size()) return 0;
+    M_TRY(hipSetDevice(m->device));
+    if (finish_pending(m)) return 1;      // (queued assemblies read the store; this one's filter handle is about to be used)
+    if (views_quiesce(m)) return 1;
+    size_t largest = 0;
+    for (size_t i = first; i < m->kfs.size(); ++i) largest = std::max(largest, m->kfs[i].n);
+    if (largest > 0xfffffff0ull) return mfail(m, "key frame too large");
+    M_TRY(m->scratch.reserve((largest ? largest : 1) * m->stride, false));
+    hipStream_t fs = pcr_internal_stream(m->filter);
+    float* base = static_cast<float*>(m->store.p);
+    size_t w = m->kfs[first].off_floats;      // where the next key frame goes: never beyond where it is now
+    for (size_t i = first; i < m->kfs.size(); ++i) {
+        pcr_map::Kf& k = m->kfs[i];
+        size_t n_out = 0;
+        if (k.n) {
+            // into scratch and back: written in place, a key frame's result would land on points of it that the filter has yet to read
+            if (pcr_internal_vf_begin(m->filter, base + k.off_floats, k.n, m->stride, grid_size, m->scratch.p, k.n) || pcr_internal_vf_end(m->filter, &n_out))
+                return mfail(m, std::string("voxel filter: ") + pcr_last_error(m->filter));
+            M_TRY(hipMemcpyAsync(base + w, m->scratch.p, n_out * m->stride, hipMemcpyDeviceToDevice, fs));
+            M_TRY(hipStreamSynchronize(fs));      // (the key frame is in its place before its entry says so)
+        }
+        k.off_floats = w; k.n = n_out;
+        w += n_out * sf;
+    }
+    m->store_floats = w;
+    if (store_points_after) *store_points_after = w / sf;
     return 0;
 }
 
 // transform + concatenate the selected key frames (m->selected, ascending) and voxel-filter the result into m->submap
 static int assemble_selected(pcr_map* m, double grid_size, size_t* n_submap, bool wait = true) {
+    const pcr_map* s = store_of(m);
     std::vector<KfDesc> desc;
     size_t total = 0;
     for (long long i : m->selected) {
-        const pcr_map::Kf& k = m->kfs[(size_t)i];
+        const pcr_map::Kf& k = s->kfs[(size_t)i];
         if (k.n == 0) continue;
         if (total + k.n > 0xfffffff0ull) return mfail(m, "sub-map too large");
         KfDesc e;
@@ -212,10 +359,10 @@ static int assemble_selected(pcr_map* m, double grid_size, size_t* n_submap, boo
         total += k.n;
     }
     if (total == 0) return 0;
-    const size_t sf = m->stride / 4;
-    const size_t room = std::max(total, (size_t)kWindow * m->max_kf_points);      // (the concatenation of a window of key frames: the buffers, the filter's and its index's, start at that size)
-    M_TRY(m->concat.reserve(room * m->stride, false));
-    M_TRY(m->submap.reserve(room * m->stride, false));
+    const size_t stride = s->stride, sf = stride / 4;
+    const size_t room = std::max(total, (size_t)kWindow * s->max_kf_points);      // (the concatenation of a window of key frames: the buffers, the filter's and its index's, start at that size)
+    M_TRY(m->concat.reserve(room * stride, false));
+    M_TRY(m->submap.reserve(room * stride, false));
     pcr_internal_vf_reserve(m->filter, room);
     M_TRY(m->desc.reserve(desc.size() * sizeof(KfDesc), false));
     // the descriptors and the transform pass go onto the FILTER's stream, in front of the filter's own launches: one synchronisation -- the filter's,
@@ -225,7 +372,7 @@ static int assemble_selected(pcr_map* m, double grid_size, size_t* n_submap, boo
     if (desc.size() <= (size_t)kPackMax) {
         KfPack pack;
         memcpy(pack.d, desc.data(), desc.size() * sizeof(KfDesc));
-        hipLaunchKernelGGL(submap_transform_pack_kernel, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, fs, static_cast<const float*>(m->store.p),
+        hipLaunchKernelGGL(submap_transform_pack_kernel, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, fs, static_cast<const float*>(s->store.p),
                            pack, (int)desc.size(), (unsigned int)total, (unsigned int)sf, static_cast<float*>(m->concat.p));
     } else {
     if (m->desc_host_cap < desc.size()) {
@@ -236,11 +383,11 @@ static int assemble_selected(pcr_map* m, double grid_size, size_t* n_submap, boo
     }
     memcpy(m->desc_host, desc.data(), desc.size() * sizeof(KfDesc));      // (page-locked staging: the copy below does not block; the previous assembly's has completed -- its filter synchronised)
     M_TRY(hipMemcpyAsync(m->desc.p, m->desc_host, desc.size() * sizeof(KfDesc), hipMemcpyHostToDevice, fs));
-    hipLaunchKernelGGL(submap_transform_kernel, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, fs, static_cast<const float*>(m->store.p),
+    hipLaunchKernelGGL(submap_transform_kernel, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, fs, static_cast<const float*>(s->store.p),
                        static_cast<const KfDesc*>(m->desc.p), (int)desc.size(), (unsigned int)total, (unsigned int)sf, static_cast<float*>(m->concat.p));
     }
     M_TRY(hipGetLastError());
-    if (pcr_internal_vf_begin(m->filter, m->concat.p, total, m->stride, grid_size, m->submap.p, total))
+    if (pcr_internal_vf_begin(m->filter, m->concat.p, total, stride, grid_size, m->submap.p, total))
         return mfail(m, std::string("voxel filter: ") + pcr_last_error(m->filter));
     m->pending = true;
     if (!wait) return 0;
@@ -252,6 +399,7 @@ static int assemble_selected(pcr_map* m, double grid_size, size_t* n_submap, boo
 static int update_by_radius(pcr_map* m, const double position[3], double radius, double grid_size, size_t* n_submap, bool wait) {
     if (!m) return 1;
     m->err.clear();
+    M_ALIVE(m);
     if (!position) return mfail(m, "NULL position");
     if (!(grid_size > 0)) return mfail(m, "grid_size must be positive");
     M_TRY(hipSetDevice(m->device));
@@ -260,12 +408,13 @@ static int update_by_radius(pcr_map* m, const double position[3], double radius,
     m->n_submap = 0;
     m->generation += 1;           // whatever happens below, the previous sub-map is gone
     if (n_submap) *n_submap = 0;
-    if (m->kfs.empty()) return 0;                          // "no any keyframes to update!!" (MapManager.cpp:166-169)
+    const std::vector<pcr_map::Kf>& kfs = store_of(m)->kfs;
+    if (kfs.empty()) return 0;                             // "no any keyframes to update!!" (MapManager.cpp:166-169)
     // radius search over the key-frame positions: squared distance in double, accumulated x, y, z; strict '<'
     const double r2 = radius * radius;
-    for (size_t i = 0; i < m->kfs.size(); ++i) {
+    for (size_t i = 0; i < kfs.size(); ++i) {
         double d = 0;
-        for (int c = 0; c < 3; ++c) { const double e = position[c] - m->kfs[i].pose[12 + c]; d += e * e; }
+        for (int c = 0; c < 3; ++c) { const double e = position[c] - kfs[i].pose[12 + c]; d += e * e; }
         if (d < r2) m->selected.push_back((long long)i);
     }
     return assemble_selected(m, grid_size, n_submap, wait);
@@ -282,6 +431,7 @@ int pcr_map_update_begin(pcr_map* m, const double position[3], double radius, do
 int pcr_map_wait(pcr_map* m, size_t* n_submap) {
     if (!m) return 1;
     if (n_submap) *n_submap = 0;
+    M_ALIVE(m);
     if (m->pending) m->err.clear();
     if (finish_pending(m)) return 1;
     if (n_submap) *n_submap = m->n_submap;
@@ -291,6 +441,7 @@ int pcr_map_wait(pcr_map* m, size_t* n_submap) {
 int pcr_map_update_window(pcr_map* m, long long key, int search_num, double grid_size, size_t* n_submap) {
     if (!m) return 1;
     m->err.clear();
+    M_ALIVE(m);
     if (!(grid_size > 0)) return mfail(m, "grid_size must be positive");
     if (search_num < 0) return mfail(m, "search_num must not be negative");
     M_TRY(hipSetDevice(m->device));
@@ -299,7 +450,7 @@ int pcr_map_update_window(pcr_map* m, long long key, int search_num, double grid
     m->n_submap = 0;
     m->generation += 1;           // whatever happens below, the previous sub-map is gone
     if (n_submap) *n_submap = 0;
-    const long long count = (long long)m->kfs.size();
+    const long long count = (long long)store_of(m)->kfs.size();
     for (long long i = -(long long)search_num; i <= (long long)search_num; ++i) {      // LoopClosureManager.cpp:46-57
         const long long near = key + i;
         if (near >= 0 && near < count) m->selected.push_back(near);
@@ -307,16 +458,35 @@ int pcr_map_update_window(pcr_map* m, long long key, int search_num, double grid
     return assemble_selected(m, grid_size, n_submap);
 }
 
+int pcr_map_update_all(pcr_map* m, double grid_size, size_t* n_submap) {
+    if (!m) return 1;
+    m->err.clear();
+    M_ALIVE(m);
+    if (!(grid_size > 0)) return mfail(m, "grid_size must be positive");
+    M_TRY(hipSetDevice(m->device));
+    (void)finish_pending(m); m->err.clear();
+    m->selected.clear();
+    m->n_submap = 0;
+    m->generation += 1;           // whatever happens below, the previous sub-map is gone
+    if (n_submap) *n_submap = 0;
+    const size_t count = store_of(m)->kfs.size();
+    for (size_t i = 0; i < count; ++i) m->selected.push_back((long long)i);      // test/vis_globalmap.cpp:40-47
+    return assemble_selected(m, grid_size, n_submap);
+}
+
 const void* pcr_map_submap(const pcr_map* m, size_t* n, size_t* stride_bytes) {
     if (!m) return nullptr;
-    if (m->pending && finish_pending(const_cast<pcr_map*>(m))) { if (n) *n = 0; if (stride_bytes) *stride_bytes = m->stride; return nullptr; }      // (the queued assembly is collected by whoever asks for the sub-map first; its error is pcr_map_last_error's)
+    const size_t stride = m->detached ? 0 : store_of(m)->stride;
+    if (m->detached) mfail(m, "parent destroyed: this view can only be destroyed");
+    if (m->detached || (m->pending && finish_pending(const_cast<pcr_map*>(m)))) { if (n) *n = 0; if (stride_bytes) *stride_bytes = stride; return nullptr; }      // (the queued assembly is collected by whoever asks for the sub-map first; its error is pcr_map_last_error's)
     if (n) *n = m->n_submap;
-    if (stride_bytes) *stride_bytes = m->stride;
+    if (stride_bytes) *stride_bytes = stride;
     return m->n_submap ? m->submap.p : nullptr;
 }
 
 int pcr_map_generation(const pcr_map* m, uint64_t* id, uint64_t* generation) {
     if (!m) return 1;
+    M_ALIVE(m);
     if (id) *id = m->id;
     if (generation) *generation = m->generation;
     return 0;
@@ -324,6 +494,8 @@ int pcr_map_generation(const pcr_map* m, uint64_t* id, uint64_t* generation) {
 
 int pcr_map_submap_indices(const pcr_map* m, int64_t* idx, size_t capacity, size_t* n) {
     if (!m || !n) return 1;
+    *n = 0;
+    M_ALIVE(m);
     *n = m->selected.size();
     if (!idx) return 0;
     if (capacity < m->selected.size()) return 1;

@@ -145,11 +145,14 @@ public:
 
     // scan2Map with `dst` = the sub-map a SubMap keeps in HBM (the scan is uploaded, the map never leaves the device)
     bool scan2Map(const PC_cPtr& src, const class SubMap& dst, pose_t& res);
+    // ... with a source that is in HBM already, in the map's point layout: a stored key frame (SubMap::keyFramePointer), lcHandler's lc_scan_
+    bool scan2Map(const void* d_src, size_t n_src, const class SubMap& dst, pose_t& res);
 };
 
 // MapManager's key-frame store and sub-map (frontend/src/MapManager.cpp:151-201), kept in HBM
 class SubMap {
     pcr_map* m_ = nullptr;
+    explicit SubMap(pcr_map* view) : m_(view) {}
 public:
     SubMap() : m_(pcr_map_create(-1)) { if (!m_) throw std::runtime_error(pcr_map_last_error(nullptr)); }
     SubMap(const SubMap&) = delete;
@@ -157,6 +160,10 @@ public:
     ~SubMap() { pcr_map_destroy(m_); }
     void addKeyFrame(const PC_cPtr& pc, const pose_t& pose) {                 // KeyFrame{pc, pose}, common/types/basic.hpp:33-40
         if (pcr_map_add_keyframe(m_, pc->points.data(), pc->size(), sizeof(PointXYZI), 0, pose.data())) throw std::runtime_error(pcr_map_last_error(m_));
+    }
+    // ... from a cloud that is in HBM already (PointXYZI layout): a scan filtered with out_on_device = 1, another map's sub-map
+    void addKeyFrame(const void* d_pts, size_t n, const pose_t& pose) {
+        if (pcr_map_add_keyframe(m_, d_pts, n, sizeof(PointXYZI), 1, pose.data())) throw std::runtime_error(pcr_map_last_error(m_));
     }
     // MapManager::updateMap around `position`; returns the number of sub-map points
     size_t updateMap(const double position[3], double radius = 8.0 /* mSurroundingKeyframeSearchRadius */, double grid_size = 0.4) {
@@ -181,6 +188,55 @@ public:
         return idx;
     }
     const void* devicePointer(size_t* n, size_t* stride_bytes) const { return pcr_map_submap(m_, n, stride_bytes); }
+    size_t keyframes() const {
+        size_t n = 0;
+        if (pcr_map_keyframes(m_, &n)) throw std::runtime_error(pcr_map_last_error(m_));
+        return n;
+    }
+    // LoopClosureManager::loopFindNearKeyframes (LoopClosureManager.cpp:40-60): key frames key +- search_num as this object's sub-map.  On a
+    // view() it is lc_map_: the odometry sub-map of the parent stays what it is.
+    size_t loopFindNearKeyframes(long long key, int search_num, double grid_size = 0.4) {
+        size_t n = 0;
+        if (pcr_map_update_window(m_, key, search_num, grid_size, &n)) throw std::runtime_error(pcr_map_last_error(m_));
+        return n;
+    }
+    // the whole map (test/vis_globalmap.cpp:33-66): every key frame under its pose, concatenated, voxel-filtered
+    size_t updateAll(double grid_size = 0.4) {
+        size_t n = 0;
+        if (pcr_map_update_all(m_, grid_size, &n)) throw std::runtime_error(pcr_map_last_error(m_));
+        return n;
+    }
+    // Backend::optimHandler (Backend.cpp:315-318): the optimised poses of key frames first .. first + poses.size() - 1
+    void setPoses(size_t first, const std::vector<pose_t>& poses) {
+        static_assert(sizeof(pose_t) == 16 * sizeof(double), "poses are handed over as one array");
+        if (pcr_map_set_poses(m_, first, poses.size(), poses.empty() ? nullptr : poses[0].data())) throw std::runtime_error(pcr_map_last_error(m_));
+    }
+    // key frame i as stored, in HBM: valid until the store next changes
+    const void* keyFramePointer(size_t i, size_t* n, size_t* stride_bytes = nullptr, pose_t* pose = nullptr) const {
+        if (i >= keyframes()) throw std::runtime_error("key-frame index out of range");
+        return pcr_map_keyframe(m_, i, n, stride_bytes, pose ? pose->data() : nullptr);
+    }
+    // ... and on the host: KeyFrame{pc, pose}
+    PC_Ptr keyFrame(size_t i, pose_t* pose = nullptr) const {
+        size_t n = 0;
+        keyFramePointer(i, &n);
+        auto pc = std::make_shared<PointCloud>();
+        pc->points.resize(n);
+        if (pcr_map_read_keyframe(m_, i, pc->points.data(), n, &n, pose ? pose->data() : nullptr)) throw std::runtime_error(pcr_map_last_error(m_));
+        return pc;
+    }
+    // MapManager::saveKfs (MapManager.cpp:211) / MapManager() (:46): key frames first .. end voxel-filtered in place; returns the points in the store
+    size_t downSampleKeyFrames(size_t first, double grid_size) {
+        size_t n = 0;
+        if (pcr_map_downsample_keyframes(m_, first, grid_size, &n)) throw std::runtime_error(pcr_map_last_error(m_));
+        return n;
+    }
+    // another sub-map over the same key frames (pcr_map_view); this object must outlive it, or the view fails every call from then on
+    std::unique_ptr<SubMap> view() {
+        pcr_map* v = pcr_map_view(m_);
+        if (!v) throw std::runtime_error(pcr_map_last_error(m_));
+        return std::unique_ptr<SubMap>(new SubMap(v));
+    }
     const pcr_map* handle() const { return m_; }
     uint64_t generation() const { uint64_t id = 0, g = 0; pcr_map_generation(m_, &id, &g); return g; }
 };
@@ -190,6 +246,17 @@ inline bool HipRegister::scan2Map(const PC_cPtr& src, const SubMap& dst, pose_t&
     // (pcr_scan2map_submap): LidarOdometry registers several scans between two MapManager::updateMap calls.
     int conv = 0;
     if (pcr_scan2map_submap(h_, src->points.data(), src->size(), 0, dst.handle(), res.data(), &conv)) {
+        logError(pcr_last_error(h_));
+        return isConverge = false;
+    }
+    lastError_.clear();
+    isConverge = conv != 0;
+    return isConverge;
+}
+
+inline bool HipRegister::scan2Map(const void* d_src, size_t n_src, const SubMap& dst, pose_t& res) {
+    int conv = 0;
+    if (pcr_scan2map_submap(h_, d_src, n_src, 1, dst.handle(), res.data(), &conv)) {
         logError(pcr_last_error(h_));
         return isConverge = false;
     }

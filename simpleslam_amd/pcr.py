@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "pcr_comm_init_host", "pcr_set_shard", "pcr_set_params", "pcr_get_params", "pcr_fitness_gated",
     "pcr_map_create", "pcr_map_destroy", "pcr_map_last_error", "pcr_map_add_keyframe", "pcr_map_keyframes", "pcr_map_clear", "pcr_map_update", "pcr_map_update_begin", "pcr_map_wait", "pcr_map_update_window", "pcr_map_submap",
     "pcr_map_submap_indices", "pcr_map_generation", "pcr_scan2map_submap",
+    "pcr_map_set_poses", "pcr_map_keyframe", "pcr_map_read_keyframe", "pcr_map_downsample_keyframes", "pcr_map_update_all", "pcr_map_view",
     "pcr_ndt_opt_create", "pcr_ndt_opt_destroy", "pcr_ndt_opt_request", "pcr_ndt_opt_feed", "pcr_ndt_opt_result", "pcr_ndt_opt_counts",
     "pcr_vgicp_opt_create", "pcr_vgicp_opt_destroy", "pcr_vgicp_opt_request", "pcr_vgicp_opt_feed", "pcr_vgicp_opt_result",
     "pcr_sc_default_params", "pcr_sc_create", "pcr_sc_destroy", "pcr_sc_last_error", "pcr_sc_size", "pcr_sc_add", "pcr_sc_descriptor", "pcr_sc_distance",
@@ -195,6 +196,14 @@ def load_library():
     L.pcr_map_submap.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.pcr_map_submap.restype = vp
     L.pcr_map_submap_indices.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pcr_map_set_poses.argtypes = [vp, C.c_size_t, C.c_size_t, dp]
+    L.pcr_map_keyframe.argtypes = [vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), dp]
+    L.pcr_map_keyframe.restype = vp
+    L.pcr_map_read_keyframe.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), dp]
+    L.pcr_map_downsample_keyframes.argtypes = [vp, C.c_size_t, C.c_double, C.POINTER(C.c_size_t)]
+    L.pcr_map_update_all.argtypes = [vp, C.c_double, C.POINTER(C.c_size_t)]
+    L.pcr_map_view.argtypes = [vp]
+    L.pcr_map_view.restype = vp
     L.pcr_sc_default_params.argtypes = [C.POINTER(ScParams)]
     L.pcr_sc_default_params.restype = None
     L.pcr_sc_create.argtypes = [C.c_int, C.POINTER(ScParams)]
@@ -312,6 +321,9 @@ def _cand_dict(c):
 
 def _cloud(x):
     """-> (pointer, n, stride_bytes, on_device, keepalive)"""
+    if isinstance(x, tuple) and len(x) == 3:  # (device pointer, n, stride_bytes): SubMap.pointer() / SubMap.keyFramePointer(i)
+        p, n, s = x
+        return C.c_void_p(p), int(n), int(s), 1, None
     if hasattr(x, "data_ptr"):  # torch tensor
         import torch
         if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] < 3 or not x.is_contiguous():
@@ -797,17 +809,71 @@ class SubMap:
     and concatenates them and voxel-filters the result; `pointer()` is the device-resident sub-map that
     PointCloudRegister.scan2MapSubmap registers against without a host copy."""
 
-    def __init__(self, device=-1):
+    def __init__(self, device=-1, _view_of=None):
         self._lib = load_library()
+        self._parent = _view_of      # (a view holds its parent: Python cannot collect the store before the sub-maps that read it)
+        if _view_of is not None:
+            self._m = self._lib.pcr_map_view(_view_of._m)
+            if not self._m:
+                raise PcrError(self._lib.pcr_map_last_error(_view_of._m).decode())
+            return
         self._m = self._lib.pcr_map_create(int(device))
         if not self._m:
             raise PcrError(self._lib.pcr_map_last_error(None).decode())
+
+    def view(self):
+        """pcr_map_view: another sub-map over the same key frames (LoopClosureManager's lc_map_ beside MapManager's mSubmap) with its own stream,
+        buffers, selection and generation.  It reads this store and cannot change it."""
+        return SubMap(_view_of=self)
+
+    def setPoses(self, first, poses):
+        """pcr_map_set_poses (Backend::optimHandler, Backend.cpp:315-318): poses = (k, 4, 4) for key frames first .. first+k-1.  No sub-map and no
+        generation changes; the next update selects and transforms with them."""
+        P = np.asarray(poses, dtype=np.float64)
+        if P.ndim == 2:
+            P = P[None]
+        if P.ndim != 3 or P.shape[1:] != (4, 4):
+            raise ValueError("poses must have shape (k, 4, 4)")
+        cm = np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(-1)      # column-major, one after the other
+        self._check(self._lib.pcr_map_set_poses(self._m, int(first), P.shape[0], cm.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def keyFramePointer(self, i):
+        """pcr_map_keyframe -> (device pointer, number of points, stride in bytes) of stored key frame i: a source for scan2MapSubmap."""
+        if not 0 <= int(i) < self.keyframes():
+            raise PcrError("key-frame index out of range")
+        n, s = C.c_size_t(0), C.c_size_t(0)
+        p = self._lib.pcr_map_keyframe(self._m, int(i), C.byref(n), C.byref(s), None)
+        return p, n.value, s.value
+
+    def keyFrame(self, i):
+        """pcr_map_read_keyframe -> (host array of the stored points, 4x4 pose)."""
+        _, cnt, stride = self.keyFramePointer(i)
+        n, s = C.c_size_t(cnt), C.c_size_t(stride)
+        pose = np.zeros(16)
+        pp = pose.ctypes.data_as(C.POINTER(C.c_double))
+        out = np.zeros((n.value, max(s.value // 4, 1)), np.float32)
+        self._check(self._lib.pcr_map_read_keyframe(self._m, int(i), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n), pp))
+        return out, _pose_out(pose)
+
+    def downSampleKeyFrames(self, first, grid_size):
+        """pcr_map_downsample_keyframes (MapManager::saveKfs :211, MapManager() :46): key frames first .. end replaced by their voxel-filtered
+        clouds, the store compacted -> points in the store."""
+        n = C.c_size_t(0)
+        self._check(self._lib.pcr_map_downsample_keyframes(self._m, int(first), float(grid_size), C.byref(n)))
+        return n.value
+
+    def updateAll(self, grid_size=0.4):
+        """pcr_map_update_all (test/vis_globalmap.cpp:33-66): the whole map -- every key frame under its pose, concatenated, voxel-filtered."""
+        n = C.c_size_t(0)
+        self._check(self._lib.pcr_map_update_all(self._m, float(grid_size), C.byref(n)))
+        return n.value
 
     def __del__(self):
         try:
             if self._m:
                 self._lib.pcr_map_destroy(self._m)
                 self._m = None
+            self._parent = None
         except Exception:
             pass
 
@@ -821,7 +887,7 @@ class SubMap:
         self._check(self._lib.pcr_map_add_keyframe(self._m, p, n, s, dev, pc.ctypes.data_as(C.POINTER(C.c_double))))
 
     def generation(self):
-        """(store id, generation of the sub-map it holds): every updateMap / updateWindow starts a new generation."""
+        """(store id, generation of the sub-map it holds): every updateMap / loopFindNearKeyframes / updateAll starts a new generation; a view has an id of its own."""
         i, g = C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.pcr_map_generation(self._m, C.byref(i), C.byref(g)))
         return int(i.value), int(g.value)
