@@ -1,0 +1,389 @@
+// ndt_host.hip -- NDT host driver: pclomp::NormalDistributionsTransform::computeTransformation
+// (ndt_omp_impl.hpp:81-171) with the More-Thuente line search (:649-932).  pcr_ndt_derivatives and the pcr_ndt_opt_* entry points.
+
+#include <algorithm>
+
+#include "handle.h"
+
+using namespace pcr;
+using namespace pcr::host;
+
+namespace pcr {
+namespace host {
+
+// deferred: nothing is read back here -- the index is enqueued with the previous target's box as a hint and the cell table at its
+// current size; whether either was wrong (header.overflow / header.stale) comes back with the result of the alignment
+// (NdtOut), and the caller then prepares again the slow, checked way.  One host round trip less per scan.
+int ndt_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, bool deferred, const RoiScan* roi_scan) {
+    h->nd.target_ready = false;
+    h->roi_on = false;
+    const double res = (double)(float)h->prm.ndt_resolution;     // resolution_ is a float (ndt_omp.h)
+    if (!(res > 0)) return fail(h, "ndt_resolution must be positive");
+    // the voxel lattice is VoxelGridCovariance's own (leaf index = floor(p * inverse_leaf) - min_b in float,
+    // voxel_grid_covariance_omp_impl.hpp:218-220): GridHeader.pcl_mode, no pad cells
+    h->grid.no_hints = h->prm.index_no_hints != 0;
+    // prepared for one scan (pcr_scan2map): voxel Gaussians only where that scan can land (RoiView) -- and, when this build can take the
+    // lattice and the tile layout of an earlier full build as they are, an index of the region's points only (BuildFilter)
+    RoiView roi;
+    memset(&roi, 0, sizeof roi);
+    const bool want_roi = roi_scan && roi_scan->n_src > 0 && n_dst > 0;
+    BuildFilter bf;
+    bf.enqueue_mask = [&]() -> hipError_t {
+        if (roi_enqueue(h, *roi_scan, res, 1.0 + res, &roi)) return hipErrorUnknown;      // 1 m of translation + the DIRECT7 face voxels, + 0.05 rad
+        bf.mask = roi.mask; bf.mshift = roi.mshift;
+        return hipSuccess;
+    };
+    // setMinPointPerVoxel (pclomp/voxel_grid_covariance_omp.h:229-240): "Covariance calculation requires at least 3 points"
+    const int min_points = std::max(3, h->prm.ndt_min_points);
+    const size_t max_vox = n_dst / (size_t)min_points + 2;      // a voxel needs min_points points
+    H_TRY(h->nd.vox.reserve(max_vox * sizeof(NdtVoxel)));
+    H_TRY(h->nd.list.reserve((max_vox + 64) * sizeof(uint32_t)));
+    if (!h->nd.count.p) {      // two counters used alternately; each call leaves the other one cleared for the next (ndt_candidates_kernel)
+        H_TRY(h->nd.count.reserve(256));
+        H_TRY(hipMemsetAsync(h->nd.count.p, 0, 256, h->stream));
+    }
+    h->nd.count_idx ^= 1;
+    uint32_t* const nd_count = h->nd.count.as<uint32_t>() + 32 * h->nd.count_idx;
+    uint32_t* const nd_count_next = h->nd.count.as<uint32_t>() + 32 * (h->nd.count_idx ^ 1);
+    if (deferred) {
+        // (the cell table keeps its size in a deferred build, so the slots can be sized before it: a region-only build lists the voxel cells
+        //  and writes the slots in its tile pass -- TileTail)
+        if (h->grid.ensure_tables(h->stream, &h->err) != hipSuccess) return 1;
+        H_TRY(h->nd.slot.reserve(((size_t)h->grid.cell_capacity + 64) * sizeof(uint32_t)));
+        bf.want_tail = true;
+        bf.tail.vox_slot = h->nd.slot.as<uint32_t>(); bf.tail.list = h->nd.list.as<uint32_t>(); bf.tail.count = nd_count; bf.tail.count_next = nd_count_next;
+        bf.tail.min_points = min_points; bf.tail.capacity = (uint32_t)std::min<size_t>(max_vox, 0xffffffffu);
+        const size_t cap_before = h->grid.cell_capacity;
+        const void* const slot_before = h->nd.slot.p;
+        if (h->grid.build(d_dst, n_dst, stride_floats, res, h->stream, &h->err, 0.0, 1, nullptr, true, want_roi ? &bf : nullptr) != hipSuccess) return 1;
+        // (the tile pass has been handed vox_slot and the list BEFORE the build: nothing in build() may move them -- it never grows the cell table, only
+        //  callers do -- but a change that broke that would write through a freed pointer: refuse loudly instead)
+        if (bf.tail_applied && (h->grid.cell_capacity != cap_before || h->nd.slot.p != slot_before))
+            return fail(h, "internal: the cell table changed size inside a deferred NDT build whose tile pass lists the voxel cells");
+    } else if (settle_grid(h, h->grid, d_dst, n_dst, stride_floats, res, 1)) return 1;
+    h->tgt_ptr = d_dst; h->tgt_n = n_dst; h->tgt_stride = stride_floats; h->have_target = true;
+    H_TRY(h->nd.slot.reserve(((size_t)h->grid.cell_capacity + 64) * sizeof(uint32_t)));
+    if (bf.applied) { roi.filtered = 1; h->roi_on = true; }
+    else if (want_roi) {
+        if (roi_enqueue(h, *roi_scan, res, 1.0 + res, &roi)) return 1;
+        h->roi_on = true;
+    }
+    H_TRY(ndt_launch_voxels(h->grid, h->nd.slot.as<uint32_t>(), h->nd.vox.as<NdtVoxel>(), nd_count, nd_count_next, h->nd.list.as<uint32_t>(),
+                            max_vox, min_points, 0.01, h->stream, h->roi_on ? &roi : nullptr, bf.tail_applied));
+    h->nd.target_ready = true;
+    return 0;
+}
+
+}  // namespace host
+}  // namespace pcr
+
+namespace {
+
+namespace ndt_host {
+using namespace ndt_opt;      // pose_from_p, angle_derivatives, svd6_solve, the line search: shared with the device (ndt_opt.h)
+// Matrix3f::eulerAngles(0, 1, 2)
+void euler_xyz(const float R[9], float out[3]) {
+    const float pi = 3.14159265358979323846f;
+    float r0 = atan2f(R[1 * 3 + 2], R[2 * 3 + 2]);
+    const float c2 = sqrtf(R[0] * R[0] + R[1] * R[1]);
+    float r1;
+    if (r0 > 0.f) { r0 -= pi; r1 = atan2f(-R[2], -c2); }
+    else r1 = atan2f(-R[2], c2);
+    const float s1 = sinf(r0), c1 = cosf(r0);
+    const float r2 = atan2f(s1 * R[2 * 3 + 0] - c1 * R[1 * 3 + 0], c1 * R[1 * 3 + 1] - s1 * R[2 * 3 + 1]);
+    out[0] = -r0; out[1] = -r1; out[2] = -r2;
+}
+}  // namespace ndt_host
+
+struct NdtRun {
+    pcr_handle* h; NdtArgs a; NdtPose T; NdtAngles ang;
+};
+// the guess as the optimiser starts from it: handed over as Matrix4f (NdtRegister.cpp:27), its Euler angles as the parameters
+// (ndt_omp_impl.hpp:103-111)
+void ndt_initial_pose(const double pose[16], NdtPose* T0, double p0[6]) {
+    float G[16];
+    for (int i = 0; i < 16; ++i) G[i] = (float)pose[i];
+    for (int rr = 0; rr < 3; ++rr) { for (int c = 0; c < 3; ++c) T0->R[rr * 3 + c] = G[c * 4 + rr]; T0->t[rr] = G[12 + rr]; }
+    float eul[3];
+    ndt_host::euler_xyz(T0->R, eul);     // Transform::rotation() taken as the linear part
+    p0[0] = T0->t[0]; p0[1] = T0->t[1]; p0[2] = T0->t[2]; p0[3] = eul[0]; p0[4] = eul[1]; p0[5] = eul[2];
+}
+// ... and the final transformation as the caller's pose
+void ndt_pose_out(const NdtPose& T, double pose16[16]) {
+    for (int i = 0; i < 16; ++i) pose16[i] = 0;
+    for (int rr = 0; rr < 3; ++rr) { for (int c = 0; c < 3; ++c) pose16[c * 4 + rr] = (double)T.R[rr * 3 + c]; pose16[12 + rr] = (double)T.t[rr]; }
+    pose16[15] = 1.0;
+}
+
+// The arguments of the handle's NDT launches over a source (run_ndt, pcr_ndt_derivatives): no region, no profiling counters
+NdtArgs ndt_args(const pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats) {
+    NdtArgs a;
+    memset(&a, 0, sizeof a);
+    a.src = d_src; a.n_src = (uint32_t)n_src; a.src_stride = (uint32_t)stride_floats;
+    a.hdr = h->grid.header.as<GridHeader>(); a.vox_slot = h->nd.slot.as<uint32_t>(); a.vox = h->nd.vox.as<NdtVoxel>();
+    a.partials = h->nd.partials.as<double>();
+    a.use_tile = h->use_tile;
+    for (int d = 0; d < 3; ++d) { a.tile_lo[d] = h->tile_lo[d]; a.tile_hi[d] = h->tile_hi[d]; }
+    // Gauss constants (ndt_omp_impl.hpp:86-93)
+    const double res = (double)(float)h->prm.ndt_resolution;
+    const double c1 = 10 * (1 - h->prm.ndt_outlier_ratio), c2 = h->prm.ndt_outlier_ratio / pow(res, 3), d3 = -log(c2);
+    a.d1 = -log(c1 + c2) - d3;
+    a.d2 = -2 * log((-log(c1 * exp(-0.5) + c2) - d3) / a.d1);
+    return a;
+}
+
+// computeDerivatives at parameters p with the cloud transformed by T: score, gradient, Hessian
+int ndt_derivatives(NdtRun* r, const double p[6], bool compute_hessian, double* score, double grad[6], double hess[36]) {
+    pcr_handle* h = r->h;
+    ndt_host::angle_derivatives(p, &r->ang);
+    if (r->a.n_src == 0) { *score = 0; memset(grad, 0, 6 * sizeof(double)); memset(hess, 0, 36 * sizeof(double)); return 0; }
+    h->seq += 1.0;
+    H_TRY(ndt_launch_derivatives(r->a, r->T, r->ang, compute_hessian ? 1 : 0, h->nd.out48.dev, h->stream, h->seq));
+    if (wait_result(h, &h->nd.out48.host[47], h->seq)) return 1;
+    if (sharded(h) && ranks_allreduce(h, h->nd.out48.host, 43)) return 1;      // score, gradient, Hessian summed over the ranks' tiles
+    ++h->nd.deriv;
+    *score = h->nd.out48.host[0];
+    for (int i = 0; i < 6; ++i) grad[i] = h->nd.out48.host[1 + i];
+    for (int i = 0; i < 36; ++i) hess[i] = compute_hessian ? h->nd.out48.host[7 + i] : 0.0;
+    return 0;
+}
+
+// One evaluation pass of the host-driven loop: the kernel the controller asked for, the fold, the ranks' sum.
+int ndt_host_pass(NdtRun* r, const NdtCtl& c, double sums[43]) {
+    pcr_handle* h = r->h;
+    h->seq += 1.0;
+    if (c.kind == kNdtPassHessian) H_TRY(ndt_launch_hessian(r->a, c.T, c.ang, h->nd.out48.dev, h->stream, h->seq));
+    else H_TRY(ndt_launch_derivatives(r->a, c.T, c.ang, c.kind == kNdtPassDerivH ? 1 : 0, h->nd.out48.dev, h->stream, h->seq));
+    if (wait_result(h, &h->nd.out48.host[47], h->seq)) return 1;
+    if (sharded(h) && ranks_allreduce(h, h->nd.out48.host, 43)) return 1;      // score, gradient, Hessian summed over the ranks' tiles
+    for (int i = 0; i < 43; ++i) sums[i] = h->nd.out48.host[i];
+    return 0;
+}
+
+}  // namespace
+
+namespace pcr {
+namespace host {
+
+// pcr_scan2map, a target prepared for the scan's region: the optimiser's initial state at `pose` made a rider of the launch that marks
+// the region (roi_enqueue launches h->blob; run_ndt then starts without a launch for it)
+int ndt_ride_initial_state(pcr_handle* h, const double pose[16]) {
+    NdtPose T0;
+    double p0[6];
+    ndt_initial_pose(pose, &T0, p0);
+    H_TRY(h->nd.ctl.reserve(2 * sizeof(NdtCtl)));
+    ndt_ctl_init_blob(&h->blob, h->nd.ctl.as<NdtCtl>(), T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters, h->prm.ndt_evaluate_repeats);
+    h->blob_pending = true;
+    return 0;
+}
+
+int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) {
+    using namespace ndt_host;
+    static constexpr const char *kWindowMsg = "ndt_max_iters exceeds the device loop's pass window (2^20 passes)",
+                                *kBudgetMsg = "ndt: the optimiser did not finish within its pass budget";
+    if (!h->nd.target_ready) return fail(h, "no target prepared");
+    if (n_src > kMaxPoints) return fail(h, "source cloud too large");
+    H_TRY(h->nd.out48.ensure(48));
+    H_TRY(h->nd.out.ensure());
+    H_TRY(h->nd.partials.reserve((size_t)1024 * 48 * sizeof(double)));      // (one buffer of 1024 rows, or the two of 256 of the one-launch-per-pass loop)
+    H_TRY(h->nd.ctl.reserve(2 * sizeof(NdtCtl)));
+    NdtRun r;
+    r.h = h;
+    r.a = ndt_args(h, d_src, n_src, stride_floats);
+    r.a.roi_escapes = roi_view(h).escapes;      // (nullptr unless the target was prepared for one scan)
+    r.a.pair_count = prof_counters(h);
+    h->nd.iters = h->nd.deriv = h->nd.hess = 0;
+    NdtPose T0;
+    double p0[6];
+    ndt_initial_pose(pose, &T0, p0);
+
+    NdtPose final_T = T0;
+    int conv = 0, nr_it = 0;
+    double score = 0;
+    // ---- device-resident loop: passes are enqueued ahead of the device, the host watches a progress word.  Not for sharded
+    // targets (every pass's sums cross the ranks through the host) and not when pcr_params.host_optimiser asks for the host loop ----
+    // Sharded over RCCL the loop stays on the device as well: fold -> ncclAllReduce on the handle's stream -> controller step, in
+    // batches of a fixed number of passes -- whether another batch is due is decided from the controller state the ranks share, so
+    // every rank enqueues the same collectives.  (A host-supplied collective needs the host in every pass: the host loop below.)
+    // Sharded over the peer exchange (pcr_comm_init_peer) likewise, two launches per pass: the evaluation, then fold + exchange + controller step
+    // in one (ndt.hip: ndt_fold_exchange_ctl_kernel).
+    const bool dev_sharded = sharded(h) && (h->comm.rccl || h->comm.peer_on) && !h->comm.host_ar && n_src > 0 && h->prm.host_optimiser == 0;
+    bool on_device = n_src > 0 && !sharded(h) && h->prm.host_optimiser == 0;
+    if (h->roi_on && !on_device) return fail(h, "internal: a target prepared for one scan needs the device-resident loop");
+    h->nd_grid_checked = false; h->nd_grid_bad = false;
+    bool sharded_done = false;
+    if (dev_sharded) {
+        NdtCtl* d_ctl = h->nd.ctl.as<NdtCtl>();
+        NdtOut* out = h->nd.out.host;
+        H_TRY(h->nd.sums.reserve(64 * sizeof(double)));
+        h->seq += 1.0;
+        const double seq = h->seq;
+        H_TRY(ndt_launch_ctl_init(d_ctl, T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters, h->stream, h->prm.ndt_evaluate_repeats));
+        const int limit = (h->prm.ndt_max_iters + 3) * 13 + 4, kBatch = 6;
+        const volatile double* f_batch = &out->batch;
+        if (h->comm.peer_on) {
+            // Peer exchange: passes are queued a fixed number ahead of the progress word, one at a time, like the unsharded loop -- by the rule that
+            // leaves every rank with the same number of launches queued (PaceRule::peer): the ranks' sequence numbers, one per launch, agree in the next call too.
+            auto launch = [&](long) -> hipError_t { h->comm.peer_seq += 1.0; return ndt_launch_pass_peer(r.a, d_ctl, h->comm.peer, h->comm.peer_seq, h->nd.out.dev, h->stream, seq, 0); };
+            static constexpr PaceRule kPeerRule{0, 3, 0, true};
+            if (pace_passes(h, out, seq, limit, kPeerRule, kWindowMsg, kBudgetMsg, launch)) return 1;
+        } else
+        for (int batch = 1, enq = 0;; ++batch) {
+            for (int b = 0; b < kBatch; ++b, ++enq) {
+                H_TRY(ndt_launch_pass_fold(r.a, d_ctl, h->nd.sums.as<double>(), h->stream));      // (a rank with an empty scan still folds zeros and takes part)
+                if (rccl_sum(h, h->nd.sums.p, 48)) return 1;
+                H_TRY(ndt_launch_ctl(r.a, d_ctl, h->nd.sums.as<double>(), h->nd.out.dev, h->stream, seq, b == kBatch - 1 ? batch : 0));
+            }
+            const double want0 = seq * 65536.0 + 2.0 * batch;
+            long spins = 0;
+            while (!(*f_batch == want0 || *f_batch == want0 + 1.0)) {
+                __builtin_ia32_pause();
+                if (++spins > 400000 || h->profile != 0) { H_TRY(hipStreamSynchronize(h->stream)); if (!(*f_batch == want0 || *f_batch == want0 + 1.0)) return fail(h, "ndt: the sharded device loop lost its batch marker"); }
+            }
+            std::atomic_thread_fence(std::memory_order_acquire);
+            if (peer_check(h)) return 1;      // (an exchange of this batch timed out: the loop has stopped on the ranks that waited, the session is over)
+            if (*f_batch == want0 + 1.0) break;
+            if (enq >= limit) return fail(h, kBudgetMsg);
+        }
+        if (!out->bail) {      // (a nearly singular Newton system: every rank saw the same pivots and goes to the host loop below, with the SVD)
+            final_T = out->final_T; conv = out->conv; nr_it = out->nr_it; score = out->score;
+            h->nd.deriv = out->n_deriv; h->nd.hess = out->n_hess; h->nd.last_passes = out->passes;
+            sharded_done = true;
+        }
+    }
+    if (on_device) {
+        NdtCtl* d_ctl = h->nd.ctl.as<NdtCtl>();
+        NdtOut* out = h->nd.out.host;
+        h->seq += 1.0;
+        const double seq = h->seq;
+        // (a scan2map call whose region was marked has stored this state with the mark pass: do_scan2map, BlobStore)
+        const bool stored = h->blob_stored && h->roi_on;
+        h->blob_stored = false;
+        if (!stored) H_TRY(ndt_launch_ctl_init(d_ctl, T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters, h->stream, h->prm.ndt_evaluate_repeats,
+                                               r.a.roi_escapes));
+        const int limit = (h->prm.ndt_max_iters + 3) * 13 + 5;        // an iteration takes at most 1 + 10 + 1 passes; one launch more finishes
+        auto launch = [&](long i) -> hipError_t {
+            const int index = (int)i;
+            if (h->profile >= 2) {      // events at every launch's own begin and end (pcr_stats.kernel_ms)
+                while ((int)h->ev_kernel.size() < 2 * (index + 1)) { hipEvent_t e; hipError_t er = hipEventCreate(&e); if (er != hipSuccess) return er; h->ev_kernel.push_back(e); }
+                h->nd_prof_launches = index + 1;
+                return ndt_launch_pass_pro(r.a, d_ctl, h->nd.partials.as<double>(), h->nd.out.dev, h->stream, seq, index, h->ev_kernel[2 * index], h->ev_kernel[2 * index + 1]);
+            }
+            return ndt_launch_pass_pro(r.a, d_ctl, h->nd.partials.as<double>(), h->nd.out.dev, h->stream, seq, index);
+        };
+        // (the host enqueues a pass in a quarter of the time the device needs for one: it only has to stay two ahead -- a pass enqueued beyond
+        //  the end costs ~10 us of device time)
+        static constexpr PaceRule kRule{3, 2, 4, false};
+        if (pace_passes(h, out, seq, limit, kRule, kWindowMsg, kBudgetMsg, launch)) return 1;
+        h->nd.last_passes = out->passes;
+        h->nd_grid_bad = out->grid_overflow || out->grid_stale;
+        h->nd_grid_empty = out->grid_empty != 0;
+        h->nd_grid_cells = out->grid_cells;
+        h->nd_grid_checked = true;
+        if (h->nd_grid_bad) return 0;           // the caller prepares the target again and repeats the call
+        // a pass looked up a voxel the target was not prepared for (RoiView), or the loop wants the host's SVD: whole target, again
+        if (h->roi_on && (out->roi_escapes > 0 || out->bail)) { h->roi_repeats += 1; return 2; }
+        if (out->bail) on_device = false;       // the Newton system was (nearly) singular: the host loop below decides, with the SVD
+        else {
+            final_T = out->final_T; conv = out->conv; nr_it = out->nr_it; score = out->score;
+            h->nd.deriv = out->n_deriv; h->nd.hess = out->n_hess;
+        }
+    }
+    if (!on_device && !sharded_done) {
+        NdtCtl c;
+        ctl_init(&c, T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters);
+        c.replay_off = h->prm.ndt_evaluate_repeats ? 1 : 0;
+        double sums[43];
+        while (!c.done) {
+            if (n_src == 0) memset(sums, 0, sizeof sums);        // an empty scan: computeDerivatives sums nothing
+            else if (ndt_host_pass(&r, c, sums)) return 1;
+            ctl_step(&c, sums);
+        }
+        final_T = c.final_T; conv = c.conv; nr_it = c.nr_it; score = c.score;
+        h->nd.deriv = c.n_deriv; h->nd.hess = c.n_hess;
+    }
+    ndt_pose_out(final_T, pose);
+    if (converged) *converged = conv ? 1 : 0;
+    h->nd.iters = nr_it; h->nd.score = score;
+    h->stats.iterations = nr_it; h->stats.kernel_launches = h->nd.deriv + h->nd.hess;
+    h->stats.attempts = (on_device || sharded_done) ? h->nd.last_passes : 0;      // (the passes a device loop actually evaluated; 0: not such a loop)
+    h->stats.n_src = (int64_t)n_src; h->stats.n_dst = (int64_t)h->tgt_n;
+    return 0;
+}
+
+}  // namespace host
+}  // namespace pcr
+
+extern "C" {
+
+int pcr_ndt_derivatives(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double p[6],
+                        double* score, double grad[6], double hess[36], double* hess_d) {
+    if (!h) return 1;
+    h->err.clear();
+    if (h->method != kNdt) return fail(h, "pcr_ndt_derivatives needs an ndt handle");
+    if (check_stride(h, stride_bytes) || set_device(h)) return 1;
+    if (!h->nd.target_ready) return fail(h, "no target: call pcr_set_target first");
+    if (ensure_full_target(h)) return 1;
+    const float* d_src = (const float*)src;
+    if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
+    H_TRY(h->nd.out48.ensure(48));
+    H_TRY(h->nd.partials.reserve((size_t)1024 * 48 * sizeof(double)));
+    NdtRun r;
+    r.h = h;
+    r.a = ndt_args(h, d_src, n_src, stride_bytes / 4);
+    ndt_host::pose_from_p(p, &r.T);
+    double sc = 0;
+    if (ndt_derivatives(&r, p, true, &sc, grad, hess)) return 1;
+    if (score) *score = sc;
+    if (hess_d && n_src) {
+        H_TRY(ndt_launch_hessian(r.a, r.T, r.ang, h->nd.out48.dev, h->stream));
+        H_TRY(hipStreamSynchronize(h->stream));
+        if (sharded(h) && ranks_allreduce(h, h->nd.out48.host, 43)) return 1;
+        for (int i = 0; i < 36; ++i) hess_d[i] = h->nd.out48.host[7 + i];
+    }
+    return 0;
+}
+
+struct pcr_ndt_opt { NdtCtl c; };
+
+pcr_ndt_opt* pcr_ndt_opt_create(const double pose_guess[16], double step_size, double trans_eps, int max_iters) {
+    if (!pose_guess) return nullptr;
+    pcr_ndt_opt* o = new pcr_ndt_opt;
+    memset(&o->c, 0, sizeof o->c);
+    NdtPose T0;
+    double p0[6];
+    ndt_initial_pose(pose_guess, &T0, p0);      // (as run_ndt starts)
+    ndt_opt::ctl_init(&o->c, T0, p0, step_size, trans_eps, max_iters);
+    return o;
+}
+void pcr_ndt_opt_destroy(pcr_ndt_opt* o) { delete o; }
+int pcr_ndt_opt_request(const pcr_ndt_opt* o, int* kind, double p6[6], double pose16[16]) {
+    if (!o || !kind) return 1;
+    *kind = o->c.done ? kNdtPassNone : o->c.kind;
+    if (p6) for (int i = 0; i < 6; ++i) p6[i] = o->c.x_t[i];
+    if (pose16) ndt_pose_out(o->c.T, pose16);
+    return 0;
+}
+int pcr_ndt_opt_feed(pcr_ndt_opt* o, const double sums[43]) {
+    if (!o || !sums || o->c.done) return 1;
+    ndt_opt::ctl_step(&o->c, sums);
+    return 0;
+}
+int pcr_ndt_opt_result(const pcr_ndt_opt* o, double pose16[16], int* converged, int* iterations, int* done) {
+    if (!o) return 1;
+    if (pose16) ndt_pose_out(o->c.final_T, pose16);
+    if (converged) *converged = o->c.conv;
+    if (iterations) *iterations = o->c.nr_it;
+    if (done) *done = o->c.done;
+    return 0;
+}
+
+int pcr_ndt_opt_counts(const pcr_ndt_opt* o, int* evaluations, int* hessians, int* replayed) {
+    if (!o) return 1;
+    if (evaluations) *evaluations = o->c.n_deriv;
+    if (hessians) *hessians = o->c.n_hess;
+    if (replayed) *replayed = o->c.replayed;
+    return 0;
+}
+
+}  // extern "C"

@@ -51,7 +51,7 @@ struct GridHeader {
 };
 __host__ __device__ inline double grid_sum_sq(const GridHeader& h) { return h.sum_sq_u ? (double)h.sum_sq_u : (double)h.sum_sq; }
 
-// Region of interest for an index whose full bounding box cannot be tabulated (a far outlier in the cloud): see capi.hip
+// Region of interest for an index whose full bounding box cannot be tabulated (a far outlier in the cloud): see loam_host.hip
 struct ClampBox { double lo[3], hi[3]; int32_t use, pad_; };
 
 struct HeaderTwin { GridHeader* hdr; GridHeader* mirror; uint64_t capacity; double cell; };      // grid_bbox_header_kernel: a second header from the same box
@@ -64,7 +64,7 @@ struct GridView {            // what kernels need to query the index
 
 static constexpr int kPad = 2;           // pad cells per side (see grid_index.hip)
 // progress word of the device-resident optimisers (NdtOut / VgOut): call number * kProgressWindow + passes consumed.  The pass budget
-// of a call ((ndt_max_iters + 3) * 13 + 5, vgicp_max_iters * lm_inner + 3) must stay inside the window: checked by pace_passes (capi.hip).
+// of a call ((ndt_max_iters + 3) * 13 + 5, vgicp_max_iters * lm_inner + 3) must stay inside the window: checked by pace_passes (handle.h).
 static constexpr double kProgressWindow = 1048576.0;
 static constexpr int kBBoxBlocks = 256;  // partial bounding boxes
 
