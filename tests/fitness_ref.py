@@ -33,6 +33,16 @@ def transform_f32(src, pose):
     return q
 
 
+def sq_dist_f32(q, t):
+    """(len(q), len(t)) float32 squared distances, (dx dx + dy dy) + dz dz with dx = q - p: the one float expression of this project's
+    brute-force references (FLANN's L2_Simple<float>)."""
+    with np.errstate(all="ignore"):
+        dx = q[:, None, 0] - t[None, :, 0]
+        dy = q[:, None, 1] - t[None, :, 1]
+        dz = q[:, None, 2] - t[None, :, 2]
+        return (dx * dx + dy * dy) + dz * dz
+
+
 def nearest_sq(q, dst, chunk_elems=1 << 22):
     """Float32 squared distance from each query (n, 3 float32) to its nearest finite target point, and that point's row in `dst`
     (the lowest row among exact ties).  No finite target point: (inf, -1).  A query with a coordinate that is not finite: a NaN or
@@ -48,11 +58,7 @@ def nearest_sq(q, dst, chunk_elems=1 << 22):
     step = max(1, chunk_elems // t.shape[0])
     with np.errstate(all="ignore"):
         for a in range(0, q.shape[0], step):
-            qq = q[a:a + step]
-            dx = qq[:, None, 0] - t[None, :, 0]
-            dy = qq[:, None, 1] - t[None, :, 1]
-            dz = qq[:, None, 2] - t[None, :, 2]
-            d = (dx * dx + dy * dy) + dz * dz
+            d = sq_dist_f32(q[a:a + step], t)
             j = np.argmin(np.where(np.isnan(d), np.float32(np.inf), d), axis=1)      # (first minimum: the lowest row)
             d2[a:a + step] = d[np.arange(d.shape[0]), j]
             idx[a:a + step] = rows[j]

@@ -5,6 +5,7 @@ import os
 import numpy as np
 from scipy.spatial.transform import Rotation as Rot
 
+import cov_ref
 import oracle
 from simpleslam_amd import synth
 
@@ -64,26 +65,10 @@ def test_vgicp_voxels_and_linearize_match_numpy():
         assert n == same.sum()
         np.testing.assert_allclose(mean, m[same, :3].astype(np.float64).mean(0), rtol=1e-12)
         np.testing.assert_allclose(cov, dc[same].mean(0), rtol=1e-12, atol=1e-15)
-    # linearisation against a direct numpy transcription of fast_vgicp_impl.hpp:73-180
+    # linearisation against a direct numpy transcription of fast_vgicp_impl.hpp:73-180 (tests/cov_ref.py: linearize)
     lin = oracle.vgicp_linearize(scan, m, T0, sc, dc)
-    H, b, err, nc = np.zeros((6, 6)), np.zeros(6), 0.0, 0
-    vox = {}
-    for i, c in enumerate(map(tuple, coord)):
-        vox.setdefault(c, []).append(i)
-    R, t = T0[:3, :3], T0[:3, 3]
-    for i in range(scan.shape[0]):
-        tp = R @ scan[i, :3].astype(np.float64) + t
-        c = tuple(np.floor(tp / 1.0 - 0.5).astype(int))
-        if c not in vox:
-            continue
-        ids = vox[c]
-        mean, CB = m[ids, :3].astype(np.float64).mean(0), dc[ids].mean(0)
-        M = np.linalg.inv(CB + R @ sc[i] @ R.T)
-        e = mean - tp
-        w = np.sqrt(len(ids))
-        S = np.array([[0, -tp[2], tp[1]], [tp[2], 0, -tp[0]], [-tp[1], tp[0], 0]])
-        J = np.concatenate([S, -np.eye(3)], 1)
-        H += w * J.T @ M @ J; b += w * J.T @ M @ e; err += w * e @ M @ e; nc += 1
+    t = cov_ref.linearize(scan, m, T0, sc, dc, 1.0)
+    H, b, err, nc = t["H"], t["b"], t["err"], t["n"]
     assert nc == lin["n"] == int(g["n_corr"])
     np.testing.assert_allclose(lin["H"], H, rtol=1e-9, atol=1e-7)
     np.testing.assert_allclose(lin["b"], b, rtol=1e-8, atol=1e-7)
