@@ -92,6 +92,12 @@ typedef struct pcr_params {
                                 *    uploaded (a pitched hipMemcpy2DAsync into a staging area of the same stride; registration reads x, y, z and nothing
                                 *    else).  Off by default: measured on MI355X / ROCm 7.2 the pitched copy of a 1 M-point map takes 3.5 ms where the
                                 *    verbatim copy of twice the bytes takes 0.6 ms (profiles/r04_notes.md) */
+
+    /* GICP -- third_parties/pclomp/src/fast_gicp_impl.hpp:16-20.  A gicp handle also reads vgicp_resolution (the cell of its target index: it
+     * decides how many candidates a search visits, never a result), vgicp_k_corr, vgicp_max_iters, vgicp_lm_inner, vgicp_rot_eps,
+     * vgicp_trans_eps, vgicp_lm_init_scale, host_optimiser and index_no_hints. */
+    double gicp_max_corr_dist; /* FLT_MAX  a correspondence needs a squared distance below (float)d * (float)d, formed in float: +inf by default
+                                *    (fast_gicp_impl.hpp:18,136); VgicpRegister::initForLC sets 150 */
 } pcr_params;
 
 /* Per-call device timings, from HIP events on the handle's stream. */
@@ -126,7 +132,9 @@ typedef struct pcr_stats {
 
 void pcr_default_params(pcr_params* p);
 
-/* method = "loam" | "ndt" | "vgicp" (frontend.pcr).  NULL on failure; pcr_last_error(NULL)
+/* method = "loam" | "ndt" | "vgicp" | "gicp" (frontend.pcr; "gicp" is fast_gicp::FastGICP, the point-wise class FastVGICP derives from, under
+ * VgicpRegister's interface: every entry point a vgicp handle serves, the whole target prepared at every preparation; sharding -- pcr_set_shard,
+ * pcr_set_query_tile, pcr_comm_init* -- and a target whose box no dense table can hold are refused).  NULL on failure; pcr_last_error(NULL)
  * then holds the reason (unknown method: the reference factory throws,
  * LidarOdometry.cpp:50-54).  p == NULL uses the defaults. */
 pcr_handle* pcr_create(const char* method, const pcr_params* p);
@@ -199,11 +207,23 @@ int pcr_vgicp_covariances(pcr_handle* h, const void* pts, size_t n, size_t strid
  * point itself first), 0xffffffff where the cloud holds fewer; *queued_out = the queries the lane-per-query search handed to the
  * wave-per-query one (csrc/cov_search.hip).  fast_gicp_impl.hpp:250-253 (kdtree.nearestKSearch). */
 int pcr_vgicp_neighbours(pcr_handle* h, size_t n, uint32_t* nbr_out, uint32_t* queued_out);
+/* (pcr_vgicp_covariances and pcr_vgicp_neighbours serve gicp handles too: the covariances are the same.) */
 /* One FastVGICP::linearize (fast_vgicp_impl.hpp:119-180) at `pose` against the current target
  * (pcr_set_target): H (36, row-major, twist = [rotation; translation]), b (6), sum of errors,
  * number of source points with a voxel correspondence. */
 int pcr_vgicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device,
                         const double pose[16], double H[36], double b[6], double* error, int64_t* n_corr);
+/* GICP introspection (a gicp handle).  One FastGICP::update_correspondences + linearize (fast_gicp_impl.hpp:120-211) at `pose` against the kept
+ * target (pcr_set_target): every source point transformed in float (a Matrix4f, as pcl::transformPointCloud), its nearest target point in
+ * PCL's float metric (exact ties: the lower index), the gate d2 < (float)gicp_max_corr_dist^2, M = (C_B + R C_A R^T)^-1 in double; H (36,
+ * row-major, twist = [rotation; translation]), b (6), *error = the sum of e^T M e, *n_corr = source points with a correspondence.
+ * pose_eval (NULL, or a trial pose): *error_eval = compute_error(pose_eval) (:214-237) on the correspondences and matrices of the
+ * linearisation at `pose`, nothing searched again (0 without pose_eval).  Optional per-point outputs (host, may be NULL): corr[n_src] = original
+ * target index or -1, d2[n_src] = the correspondence's float squared distance (+inf where none), mahal6[n_src*6] = M as xx xy xz yy yz zz
+ * (zeros where none). */
+int pcr_gicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double pose[16],
+                       const double* pose_eval, double H[36], double b[6], double* error, double* error_eval, int64_t* n_corr,
+                       int32_t* corr, float* d2, double* mahal6);
 
 /* pcl::VoxelGrid<PointXYZI>::filter (leaf, leaf, leaf) -- the step before the path: every scan at
  * frontend/src/LidarOdometry.cpp:36,170-171, every rebuilt sub-map at frontend/src/MapManager.cpp:78,192 through

@@ -163,6 +163,18 @@ int do_scan2map(pcr_handle* h, const void* src, size_t n_src, const void* dst, s
         if (rrc) return 1;
         return end_timed_call(h);
     }
+    if (h->method == kGicp) {
+        // the whole target, every call: its index and covariances queued first, the scan's side while the host waits for the headers (as above)
+        bool src_queued = false;
+        const std::function<int()> queue_src = [&]() -> int { src_queued = true; return vgicp_source_enqueue(h, d_src, n_src, stride_bytes / 4, true); };
+        int prc = vgicp_source_mark(h);
+        if (!prc) prc = gicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4, &queue_src);
+        if (!prc && !src_queued) prc = queue_src();
+        if (prc) { (void)side_drain(h); return 1; }
+        if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
+        if (run_gicp(h, d_src, n_src, stride_bytes / 4, pose, converged)) { (void)side_drain(h); return 1; }
+        return end_timed_call(h);
+    }
     // the reference rebuilds its index on every call (LoamRegister.cpp:110); so do we
     h->clamp.use = 0;
     if (build_target(h, d_dst, n_dst, stride_bytes / 4)) {
@@ -184,6 +196,7 @@ int prepare_target_from(pcr_handle* h, const float* d_dst, size_t n_dst, size_t 
     h->map_id = 0; h->map_gen = 0;      // (pcr_scan2map_submap sets them after a successful preparation)
     if (h->method == kVgicp) return agree_prepared(h, vgicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4));
     if (h->method == kNdt) return agree_prepared(h, ndt_prepare_target(h, d_dst, n_dst, stride_bytes / 4));
+    if (h->method == kGicp) return gicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4);      // (never sharded: nothing to agree on)
     h->clamp.use = 0;
     // settle the cell-table size now so that pcr_align never has to rebuild
     int rc = build_target(h, d_dst, n_dst, stride_bytes / 4);
@@ -232,6 +245,7 @@ void pcr_default_params(pcr_params* p) {
     p->vgicp_resolution = 1.0; p->vgicp_k_corr = 20; p->vgicp_max_iters = 64; p->vgicp_lm_inner = 10;
     p->vgicp_rot_eps = 2e-3; p->vgicp_trans_eps = 5e-4; p->vgicp_lm_init_scale = 1e-9;
     p->record_trace = 0;
+    p->gicp_max_corr_dist = (double)FLT_MAX;
 }
 
 pcr_handle* pcr_create(const char* method, const pcr_params* p) {
@@ -241,6 +255,7 @@ pcr_handle* pcr_create(const char* method, const pcr_params* p) {
     if (!strcmp(method, "loam")) m = kLoam;
     else if (!strcmp(method, "ndt")) m = kNdt;
     else if (!strcmp(method, "vgicp")) m = kVgicp;
+    else if (!strcmp(method, "gicp")) m = kGicp;
     else {
         // the reference factory throws on an unknown frontend.pcr (LidarOdometry.cpp:50-54)
         g_create_error = std::string("such pcr type(") + method + ") is not exist";
@@ -338,7 +353,7 @@ int pcr_scan2map_submap(pcr_handle* h, const void* src, size_t n_src, int src_on
     }
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
     const bool current = h->map_id == id && h->map_gen == gen && h->have_target &&
-                         (h->method == kLoam ? h->grid.valid && !h->clamp.use : (h->method == kNdt ? h->nd.target_ready : h->vg.target_ready));
+                         (h->method == kLoam ? h->grid.valid && !h->clamp.use : (h->method == kNdt ? h->nd.target_ready : vgicp_family_target_ready(h)));
     // Sharded: prepare_target_from() ends in a collective (agree_prepared), so either every rank rebuilds or none does -- a rank
     // whose tile index was cut, or whose map is at another generation, must not enter that exchange while its peers are already
     // summing normal equations.  One MAX over the ranks of "I have to rebuild" decides for all.
@@ -347,7 +362,7 @@ int pcr_scan2map_submap(pcr_handle* h, const void* src, size_t n_src, int src_on
     if (need != 0.0) {
         // VGICP, a scan that is in HBM already: its side goes onto the side stream FIRST and runs beside the new sub-map's preparation (clouds of a few ten
         // thousand points: the device is mostly idle behind either)
-        if (h->method == kVgicp && !sharded(h) && src_on_device && n_src > 0 && src && vgicp_source_enqueue(h, static_cast<const float*>(src), n_src, stride_bytes / 4)) return 1;
+        if (vgicp_family(h) && !sharded(h) && src_on_device && n_src > 0 && src && vgicp_source_enqueue(h, static_cast<const float*>(src), n_src, stride_bytes / 4)) return 1;
         if (prepare_target_from(h, static_cast<const float*>(d_dst), n_dst, stride_bytes)) {
             (void)side_drain(h);      // (nothing of this call stays in flight)
             return 1;
@@ -371,13 +386,14 @@ int pcr_align(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes,
     const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
     if (h->method == kNdt) return run_ndt(h, d_src, n_src, stride_bytes / 4, pose_inout, converged);
-    if (h->method == kVgicp) {
+    if (vgicp_family(h)) {
         // the scan's own side (two index levels, the 20-neighbour search, the covariances) queued on the side stream with its headers mirrored to the host, as
         // pcr_scan2map queues it -- unless pcr_scan2map_submap has queued it already, ahead of the target's preparation.  Settled the checked way (a header
         // read back after every level: two host round trips with an idle device in between, ~55 us of a 0.3 ms call against a kept sub-map) only if that fails.
         if (!sharded(h) && n_src > 0 && !(h->side_pending && h->side_src == d_src && h->side_n == n_src && h->side_stride == stride_bytes / 4) &&
             vgicp_source_enqueue(h, d_src, n_src, stride_bytes / 4)) return 1;
-        const int rc = vgicp_align_recut(h, d_src, n_src, stride_bytes / 4, pose_inout, converged) ? 1 : 0;
+        const int rc = (h->method == kGicp ? run_gicp(h, d_src, n_src, stride_bytes / 4, pose_inout, converged)
+                                           : vgicp_align_recut(h, d_src, n_src, stride_bytes / 4, pose_inout, converged)) ? 1 : 0;
         (void)side_drain(h);      // (an alignment that failed before it collected the scan's side: nothing stays in flight behind the caller's back)
         return rc;
     }
@@ -386,7 +402,7 @@ int pcr_align(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes,
 
 int pcr_invalidate_target(pcr_handle* h) {
     if (!h) return 1;
-    h->have_target = false; h->grid.valid = false; h->vg.target_ready = false; h->nd.target_ready = false;
+    h->have_target = false; h->grid.valid = false; h->vg.target_ready = false; h->nd.target_ready = false; h->gi.target_ready = false;
     h->map_id = 0; h->map_gen = 0; h->roi_on = false;
     return 0;
 }
@@ -427,7 +443,7 @@ int pcr_set_params(pcr_handle* h, const pcr_params* p) {
     if (!p) return fail(h, "params is NULL");
     if (p->struct_size != sizeof(pcr_params)) return fail(h, "pcr_params.struct_size mismatch (start from pcr_get_params or pcr_default_params)");
     if (p->device >= 0 && p->device != h->device) return fail(h, "a handle cannot move to another device");
-    if (h->method == kVgicp && p->vgicp_k_corr != 20) return fail(h, "this build supports vgicp_k_corr = 20 (the reference's value) only");
+    if (vgicp_family(h) && p->vgicp_k_corr != 20) return fail(h, "this build supports vgicp_k_corr = 20 (the reference's value) only");
     const pcr_params old = h->prm;
     h->prm = *p;
     h->prm.device = old.device;
@@ -435,6 +451,8 @@ int pcr_set_params(pcr_handle* h, const pcr_params* p) {
     if (p->loam_knn_max_sq != old.loam_knn_max_sq && h->method == kLoam) { h->have_target = false; h->grid.valid = false; }
     if ((p->ndt_resolution != old.ndt_resolution || p->ndt_min_points != old.ndt_min_points) && h->method == kNdt) { h->nd.target_ready = false; h->have_target = false; h->grid.valid = false; }
     if (p->vgicp_resolution != old.vgicp_resolution && h->method == kVgicp) { h->vg.target_ready = false; h->have_target = false; h->grid.valid = false; }
+    // (gicp: the resolution is the cell of its index, k_corr the neighbourhood of its covariances; the gate and the optimiser settings are read at every call)
+    if ((p->vgicp_resolution != old.vgicp_resolution || p->vgicp_k_corr != old.vgicp_k_corr) && h->method == kGicp) { h->gi.target_ready = false; h->have_target = false; h->grid.valid = false; }
     return 0;
 }
 

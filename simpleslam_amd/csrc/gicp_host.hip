@@ -1,0 +1,232 @@
+// gicp_host.hip -- GICP host driver: fast_gicp::FastGICP (fast_gicp_impl.hpp:103-237) under PCL's align() and LsqRegistration
+// (vgicp_opt.h, the state machine VGICP runs), the preparation of its target and pcr_gicp_linearize.  The scan's side is VGICP's
+// (vgicp_host.hip: vgicp_source_enqueue / vgicp_source_settle).
+
+#include <algorithm>
+
+#include "handle.h"
+
+using namespace pcr;
+using namespace pcr::host;
+
+namespace pcr {
+namespace host {
+
+// The whole target, always: an index of every finite point for the exact 1-NN (h->grid, with the coarse level of a scan-sized cloud's
+// covariance search in h->cov_l1) and the covariance of every point.  A box no dense table can hold would need a cut index: refused.
+int gicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, const std::function<int()>* before_wait) {
+    h->gi.target_ready = false;
+    h->roi_on = false;
+    h->clamp.use = 0;
+    const double res = h->prm.vgicp_resolution;
+    if (!(res > 0)) return fail(h, "gicp: vgicp_resolution (the cell of the target index) must be positive");
+    if (h->prm.vgicp_k_corr != 20) return fail(h, "gicp: this build supports vgicp_k_corr = 20 (the reference's value) only");
+    if (sharded(h) || h->use_tile) return fail(h, "gicp: sharded targets are not supported in this version");
+    if (n_dst > kMaxPoints) return fail(h, "gicp: target cloud too large");
+    // Every pass reads b_j at its original index, so the points must live as long as the prepared target does: a device buffer of the
+    // caller's (pcr_scan2map_device, a sub-map) is copied into the handle's own staging area first, where pcr_set_target and the host
+    // entry points have put theirs already.  Index, covariances and passes all read that copy.
+    if (n_dst > 0 && d_dst != h->tgt_stage.as<float>()) {
+        const size_t bytes = n_dst * stride_floats * sizeof(float);
+        H_TRY(h->tgt_stage.reserve(bytes));
+        H_TRY(hipMemcpyAsync(h->tgt_stage.p, d_dst, bytes, hipMemcpyDeviceToDevice, h->stream));
+        d_dst = h->tgt_stage.as<float>();
+    }
+    h->tgt_ptr = d_dst; h->tgt_n = n_dst; h->tgt_stride = stride_floats;
+    H_TRY(h->gi.tgt_cov6.reserve((n_dst + 1) * 6 * sizeof(double)));
+    CovSettle opt;
+    bool untabulatable = false;
+    opt.hdr0_out = &h->vg.cov_hdr0; opt.before_wait = before_wait; opt.untabulatable = &untabulatable;
+    if (settle_cov_levels(h, h->grid, h->cov_l1, h->vg.cov_l2, d_dst, n_dst, stride_floats, res, opt)) {
+        h->err = untabulatable ? "gicp: the target's box cannot be tabulated (" + h->err + "; a stray point far from the map?): that needs a cut index, which gicp "
+                                 "does not support in this version"
+                               : "gicp: preparing the target: " + h->err;
+        return 1;
+    }
+    h->have_target = true;
+    // a map-sized cloud's covariances are searched on ONE level whose cell is sized for the 20-neighbour radius (vgicp_prepare_target)
+    const int levels = cov_levels(n_dst);
+    const GridIndex* cov_grid = &h->grid;
+    h->cov_scale_hint = 0.0;
+    if (levels == 1 && n_dst > 0 && grid_sum_sq(h->vg.cov_hdr0) > 0.0) {
+        const double occ = grid_sum_sq(h->vg.cov_hdr0) / (double)n_dst;
+        const double scale = std::min(8.0, sqrt(10.0 / std::max(occ, 1e-3)));
+        if (scale >= 1.3) {
+            if (settle_grid(h, h->cov_l1, d_dst, n_dst, stride_floats, res * scale, 0, nullptr)) return fail(h, "gicp: preparing the target: " + h->err);
+            h->cov_scale_hint = scale;
+            cov_grid = &h->cov_l1;
+        }
+    }
+    H_TRY(vgicp_launch_cov(*cov_grid, levels > 1 ? &h->cov_l1 : nullptr, levels > 2 ? &h->vg.cov_l2 : nullptr, d_dst, stride_floats, n_dst,
+                           h->gi.tgt_cov6.as<double>(), h->stream, nullptr, nullptr, &h->vg.tgt_scratch));
+    h->gi.target_ready = true;
+    return 0;
+}
+
+}  // namespace host
+}  // namespace pcr
+
+namespace {
+
+// the gate as the reference forms it: a float product (fast_gicp_impl.hpp:136); (float)FLT_MAX squared is +inf
+float gicp_thr2(const pcr_handle* h) {
+    const volatile float d = (float)h->prm.gicp_max_corr_dist;
+    return d * d;
+}
+
+// The arguments of the handle's GICP launches over a source
+GicpArgs gicp_args(const pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats) {
+    GicpArgs a;
+    memset(&a, 0, sizeof a);
+    a.src = d_src; a.n_src = (uint32_t)n_src; a.src_stride = (uint32_t)stride_floats;
+    a.src_cov6 = h->vg.src_cov6.as<double>();
+    a.grid = h->grid.view();
+    a.tgt = h->tgt_ptr; a.tgt_stride = (uint32_t)h->tgt_stride;
+    a.tgt_cov6 = h->gi.tgt_cov6.as<double>();
+    a.corr = h->gi.corr[0].as<uint32_t>(); a.corr_M = h->gi.M[0].as<double>();
+    a.corr_next = h->gi.corr[1].as<uint32_t>(); a.corr_M_next = h->gi.M[1].as<double>();
+    a.partials = h->vg_partials.as<double>();
+    a.thr2 = gicp_thr2(h);
+    return a;
+}
+
+// the scan's covariances settled, the correspondence buffers and the rows' memory in place
+int gicp_setup(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats) {
+    if (!h->gi.target_ready) return fail(h, "no target prepared");
+    if (sharded(h) || h->use_tile) return fail(h, "gicp: sharded handles are not supported in this version");
+    if (n_src > kMaxPoints) return fail(h, "source cloud too large");
+    if (ensure_out32(h)) return 1;
+    if (vgicp_source_settle(h, d_src, n_src, stride_floats)) return 1;
+    for (int k = 0; k < 2; ++k) {
+        H_TRY(h->gi.corr[k].reserve((n_src + 1) * sizeof(uint32_t)));
+        H_TRY(h->gi.M[k].reserve((n_src + 1) * 6 * sizeof(double)));
+    }
+    H_TRY(h->vg_partials.reserve((size_t)2 * 512 * 32 * sizeof(double)));
+    return 0;
+}
+
+}  // namespace
+
+namespace pcr {
+namespace host {
+
+int run_gicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) {
+    h->fit_pending = false;
+    const bool fit_side = h->fit_copied_from == d_src && d_src != nullptr;      // (the side stream copied this very scan)
+    h->fit_copied_from = nullptr;
+    if (gicp_setup(h, d_src, n_src, stride_floats)) return 1;
+    if (n_src > 0 && !fit_side) {      // the scan, kept for a later pcr_fitness()
+        H_TRY(h->fit_src.reserve(n_src * stride_floats * sizeof(float)));
+        H_TRY(hipMemcpyAsync(h->fit_src.p, d_src, n_src * stride_floats * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    }
+    const GicpArgs a = gicp_args(h, d_src, n_src, stride_floats);
+    Pose16 x0;
+    for (int i = 0; i < 16; ++i) x0.m[i] = (double)(float)pose[i];     // guess handed over as Matrix4f (VgicpRegister.cpp:36)
+    bool conv = false;
+    int outer = 0, n_lin = 0, n_err = 0;
+    // ---- device-resident loop (vgicp_opt.h): launches are enqueued ahead of the device, the host watches a progress word ----
+    const bool on_device = n_src > 0 && h->prm.host_optimiser == 0 && h->prm.vgicp_max_iters > 0;
+    if (on_device) {
+        H_TRY(h->gi.out.ensure());
+        H_TRY(h->gi.ctl.reserve(2 * sizeof(VgCtl)));
+        VgCtl* d_ctl = h->gi.ctl.as<VgCtl>();
+        VgOut* out = h->gi.out.host;
+        h->seq += 1.0;
+        const double seq = h->seq;
+        H_TRY(vgicp_launch_ctl_init(d_ctl, x0, h->prm.vgicp_max_iters, h->prm.vgicp_lm_inner, h->prm.vgicp_lm_init_scale, h->prm.vgicp_rot_eps, h->prm.vgicp_trans_eps, h->stream));
+        // every outer iteration takes at most lm_inner passes, plus the first linearisation and the launch that finishes
+        const long limit = (long)h->prm.vgicp_max_iters * std::max(1, h->prm.vgicp_lm_inner) + 3;
+        auto launch = [&](long i) -> hipError_t { return gicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), h->gi.out.dev, h->stream, seq, (int)i); };
+        static constexpr PaceRule kRule{4, 3, 4, false};      // (run_vgicp's)
+        if (pace_passes(h, out, seq, limit, kRule, "vgicp_max_iters * vgicp_lm_inner exceeds the device loop's pass window (2^20)",
+                        "gicp: the optimiser did not finish within its pass budget", launch))
+            return 1;
+        x0 = out->x0; conv = out->conv != 0;
+        outer = out->outer; n_lin = out->n_lin; n_err = out->n_err;
+        h->stats.attempts = out->passes;
+    } else {
+        // ---- host-driven loop: the same state machine, one host round trip per pass ----
+        VgCtl c;
+        memset(&c, 0, sizeof c);
+        vg_opt::ctl_init(&c, x0, h->prm.vgicp_max_iters, h->prm.vgicp_lm_inner, h->prm.vgicp_lm_init_scale, h->prm.vgicp_rot_eps, h->prm.vgicp_trans_eps);
+        while (!c.done) {
+            GicpArgs ap = a;
+            if (c.parity) { ap.corr = a.corr_next; ap.corr_M = a.corr_M_next; ap.corr_next = a.corr; ap.corr_M_next = a.corr_M; }
+            h->seq += 1.0;
+            if (c.kind == kVgPassLinearize) H_TRY(gicp_launch_linearize(ap, c.xi, h->out32.dev, h->stream, h->seq));
+            else H_TRY(gicp_launch_error(ap, c.xi, h->out32.dev, h->stream, h->seq));
+            if (wait_result(h, &h->out32.host[31], h->seq)) return 1;
+            double sums[29];
+            for (int k = 0; k < 29; ++k) sums[k] = h->out32.host[k];
+            vg_opt::ctl_step(&c, sums);
+        }
+        x0 = c.x0; conv = c.conv != 0;
+        outer = c.outer; n_lin = c.n_lin; n_err = c.n_err;
+        h->stats.attempts = c.passes;
+    }
+    for (int i = 0; i < 16; ++i) pose[i] = (double)(float)x0.m[i];     // final_transformation_ is a Matrix4f
+    if (converged) *converged = conv ? 1 : 0;
+    h->stats.iterations = outer; h->stats.n_src = (int64_t)n_src; h->stats.n_dst = (int64_t)h->tgt_n;
+    h->stats.kernel_launches = n_lin + n_err;
+    // pcl::Registration::getFitnessScore() is evaluated when asked for (pcr_fitness), as after a VGICP alignment
+    for (int i = 0; i < 16; ++i) h->fit_pose[i] = pose[i];
+    h->fit_n = n_src; h->fit_stride = stride_floats; h->fit_pending = true;
+    h->fitness = DBL_MAX;
+    return 0;
+}
+
+}  // namespace host
+}  // namespace pcr
+
+extern "C" {
+
+int pcr_gicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double pose[16], const double* pose_eval,
+                       double H[36], double b[6], double* error, double* error_eval, int64_t* n_corr, int32_t* corr, float* d2, double* mahal6) {
+    if (!h) return 1;
+    h->err.clear();
+    if (h->method != kGicp) return fail(h, "pcr_gicp_linearize needs a gicp handle");
+    if (!pose || !H || !b) return fail(h, "pose, H or b is NULL");
+    if (n_src && !src) return fail(h, "NULL cloud with nonzero size");
+    if (check_stride(h, stride_bytes) || set_device(h)) return 1;
+    if (!h->gi.target_ready || !h->have_target) return fail(h, "no target: call pcr_set_target first");
+    const float* d_src = (const float*)src;
+    if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
+    if (gicp_setup(h, d_src, n_src, stride_bytes / 4)) { (void)side_drain(h); return 1; }
+    H_TRY(h->gi.d2.reserve((n_src + 1) * sizeof(float)));
+    GicpArgs a = gicp_args(h, d_src, n_src, stride_bytes / 4);
+    a.d2_out = h->gi.d2.as<float>();
+    Pose16 T;
+    memcpy(T.m, pose, sizeof T.m);
+    H_TRY(gicp_launch_linearize(a, T, h->out32.dev, h->stream));
+    std::vector<uint32_t> cr(n_src);
+    if (n_src) {
+        H_TRY(hipMemcpyAsync(cr.data(), a.corr, n_src * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        if (d2) H_TRY(hipMemcpyAsync(d2, a.d2_out, n_src * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (mahal6) H_TRY(hipMemcpyAsync(mahal6, a.corr_M, n_src * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    H_TRY(hipStreamSynchronize(h->stream));
+    int q = 0;
+    for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { H[r * 6 + c] = H[c * 6 + r] = h->out32.host[q++]; }
+    for (int r = 0; r < 6; ++r) b[r] = h->out32.host[21 + r];
+    if (error) *error = h->out32.host[27];
+    int64_t nc = 0;
+    for (size_t i = 0; i < n_src; ++i) {
+        const bool has = cr[i] != 0xffffffffu;
+        nc += has;
+        if (corr) corr[i] = has ? (int32_t)cr[i] : -1;
+        // (the matrix of a point without a correspondence is whatever the buffer held: reported as zeros)
+        if (mahal6 && !has) for (int k = 0; k < 6; ++k) mahal6[i * 6 + k] = 0.0;
+    }
+    if (n_corr) *n_corr = nc;
+    if (pose_eval) {      // compute_error(pose_eval) on the correspondences just made (the trial pass; its own linearisation goes to the other buffer)
+        Pose16 Te;
+        memcpy(Te.m, pose_eval, sizeof Te.m);
+        a.d2_out = nullptr;
+        H_TRY(gicp_launch_error(a, Te, h->out32.dev, h->stream));
+        H_TRY(hipStreamSynchronize(h->stream));
+        if (error_eval) *error_eval = h->out32.host[28];
+    } else if (error_eval) *error_eval = 0.0;
+    return 0;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // handle.h -- struct pcr_handle and what the host units of the C ABI share (host code only; no kernel includes this).
 // The units: capi.hip (handle, scan2map / set_target / align, getters and setters), staging_host.hip, comm_host.hip,
-// loam_host.hip, vgicp_host.hip, ndt_host.hip, voxel_host.hip, query_host.hip.
+// loam_host.hip, vgicp_host.hip, gicp_host.hip, ndt_host.hip, voxel_host.hip, query_host.hip.
 // A nested struct of the handle belongs to the unit it is named after: that unit sets it up and writes it (pcr_destroy and
 // pcr_invalidate_target reach into all of them); where another unit looks into one, the member's comment says so.  What
 // several units share stays at the top level, with its users named.
@@ -22,7 +22,7 @@
 namespace pcr {
 namespace host {
 
-enum Method { kLoam = 0, kNdt = 1, kVgicp = 2 };
+enum Method { kLoam = 0, kNdt = 1, kVgicp = 2, kGicp = 3 };
 
 // A block of `count` T in host-mapped memory, which kernels write through `dev` and the host reads at `host`: allocated and
 // zeroed on first use, freed with its owner.
@@ -127,6 +127,17 @@ struct pcr_handle {
         pcr::DeviceBuf reduced;              // sharded VGICP over the peer exchange: a pass's 32 sums folded over the rows and the ranks
         pcr::DeviceBuf cov_viol;         // VGICP halo check: number of neighbourhoods that reach past the halo
     } vg;
+
+    // GICP work memory (gicp_host.hip).  The scan's side -- its index levels, covariances, the copy kept for the fitness score -- is VGICP's (vg.src_*,
+    // side_stream); the target is h->grid (every finite point, for the 1-NN) and h->cov_l1 / vg.cov_l2 (the levels of its covariance search).
+    struct Gicp {
+        pcr::DeviceBuf tgt_cov6;             // per target point, original order
+        pcr::DeviceBuf corr[2], M[2];        // the two correspondence buffers (original target index / Mahalanobis matrix per source point), chosen by the state's parity
+        pcr::DeviceBuf d2;                   // pcr_gicp_linearize: the correspondences' float distances
+        pcr::DeviceBuf ctl;                  // two VgCtl: the device-resident LM loop's state, by launch parity
+        pcr::host::Mapped<pcr::VgOut> out;   // its result and progress word
+        bool target_ready = false;           // (read by pcr_scan2map_submap and query; dropped by pcr_set_params, pcr_invalidate_target)
+    } gi;
 
     // region of interest of a target prepared for one scan (RoiView): two marking buffers used alternately, the dilated mask, the escape counter
     // (vgicp_host.hip: roi_enqueue, roi_view)
@@ -269,6 +280,43 @@ int vgicp_source_enqueue(pcr_handle* h, const float* d_src, size_t n_src, size_t
 int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, const RoiScan* roi_scan = nullptr, bool keep_clamp = false,
                          const std::function<int()>* before_wait = nullptr);
 int vgicp_align_recut(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged);
+
+// What settle_cov_levels does beyond building and sizing the levels
+struct CovSettle {
+    double shift0 = 0.0;                  // shift of the fine level's lattice, in cells
+    GridHeader* hdr0_out = nullptr;       // where the fine level's header goes, with its density figure
+    bool may_cut = false;                 // a box no dense table can hold is cut to the bulk of the cloud (h->clamp)
+    double ahead_cell = 0.0;              // a one-level cloud: the cell of its covariance grid, built ahead in l1 beside the fine level; 0: none
+    bool* ahead_ok = nullptr;             // ... whether that grid stands
+    // after_ahead (with a grid built ahead only): what the caller would enqueue once the headers have been read, enqueued BEFORE they are -- the
+    // host waits for the headers alone (an event behind their copies) while the device goes on; *after_clean tells whether what was enqueued
+    // stands (first attempt, nothing stale or overflowing, the grid built ahead usable).  Kernels queued that way see the flags in the headers
+    // and leave early; whatever they wrote is written again by the caller.
+    const std::function<int()>* after_ahead = nullptr;
+    bool* after_clean = nullptr;
+    const std::function<int()>* before_wait = nullptr;      // what the caller wants queued on OTHER streams while the host waits for the headers
+    // scan_levels: the levels of a SCAN (the source of an alignment that did not come through vgicp_source_enqueue: pcr_set_target + pcr_align,
+    // pcr_vgicp_covariances, the redo path): built like vgicp_source_enqueue builds them -- one-level path, no hints: one scan's box and tile
+    // layout do not hold the next (walls at other distances; measured there: every hint failed and the redo cost 0.9 ms)
+    bool scan_levels = false;
+    // filter0: the fine level may index the points of a region only (BuildFilter: possible when this build reuses the header and the tile layout of
+    // an earlier full build of the level -- build() decides and says so in filter0->applied)
+    BuildFilter* filter0 = nullptr;
+    bool* untabulatable = nullptr;        // set when the call fails because a level's box needs more cells than a dense table can have and may_cut is off
+};
+// the fine index plus the coarse ones of the covariance search, settled with one round trip (gicp prepares its target with it too)
+int settle_cov_levels(pcr_handle* h, GridIndex& g, GridIndex& l1, GridIndex& l2, const float* d_pts, size_t n, size_t stride_floats, double cell,
+                      const CovSettle& opt);
+int cov_levels(size_t n);      // index levels of a cloud's covariance search: 2 for a scan-sized cloud, 1 for a map-sized one
+// the scan's covariances (vg.src_cov6) ready on return, ordered before whatever the main stream runs next: collected from the side stream, or computed here
+int vgicp_source_settle(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats);
+
+// ---- gicp_host.hip ----
+int gicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, const std::function<int()>* before_wait = nullptr);
+int run_gicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged);
+// vgicp and gicp: the methods that keep the scan and score it on demand (pcr_fitness) and whose scan side runs on the side stream
+inline bool vgicp_family(const pcr_handle* h) { return h->method == kVgicp || h->method == kGicp; }
+inline bool vgicp_family_target_ready(const pcr_handle* h) { return h->method == kGicp ? h->gi.target_ready : h->vg.target_ready; }
 
 // ---- ndt_host.hip ----
 int ndt_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, bool deferred = false, const RoiScan* roi_scan = nullptr);

@@ -354,6 +354,31 @@ struct FitTile { int32_t use, pad_; double lo[3], hi[3], ext_lo[3], ext_hi[3]; }
 hipError_t fitness_launch(const GridIndex& grid, const float* d_src, size_t n_src, size_t stride_floats, const double pose[16], double max_range,
                           double* d_partials, double* d_out32, hipStream_t s, double seq = 0.0, const FitTile* tile = nullptr);
 uint32_t vgicp_blocks(uint32_t n_src);
+// the fold of a pass's [block][32] rows into d_out32 (vgicp.hip: sum_partials_kernel), `seq` written last into d_out32[31]
+hipError_t sum_partials_launch(const double* d_partials, uint32_t nblocks, double* d_out32, hipStream_t s, double seq = 0.0);
+
+// ---------------------------------------------------------------------------
+// GICP (gicp.hip): fast_gicp::FastGICP, correspondences by exact nearest neighbour
+// ---------------------------------------------------------------------------
+struct GicpArgs {
+    const float* src; uint32_t n_src, src_stride;
+    const double* src_cov6;      // per source point, original order
+    GridView grid;               // index of every finite target point
+    const float* tgt;            // the target's points as the caller gave them (b_j is read at the original index j)
+    uint32_t tgt_stride, pad_;
+    const double* tgt_cov6;      // per target point, original order
+    uint32_t* corr;              // [n_src] original index of the correspondence, 0xffffffff = none
+    double* corr_M;              // [n_src][6] Mahalanobis matrix of the correspondence
+    uint32_t* corr_next;         // the same two for the linearisation an LM trial pass computes ahead (gicp_launch_error)
+    double* corr_M_next;
+    double* partials;            // [blocks][32]
+    float thr2, pad2_;           // the gate: a correspondence needs d2 < thr2 (float; +inf by default)
+    float* d2_out;               // introspection (pcr_gicp_linearize): [n_src] float squared distance of the correspondence, +inf for none; else NULL
+};
+hipError_t gicp_launch_linearize(const GicpArgs& a, const Pose16& T, double* d_out32, hipStream_t s, double seq = 0.0);
+// out32[28] = compute_error(T) on a.corr / a.corr_M; out32[0..27] = the linearisation at T (correspondences into a.corr_*next)
+hipError_t gicp_launch_error(const GicpArgs& a, const Pose16& T, double* d_out32, hipStream_t s, double seq = 0.0);
+hipError_t gicp_launch_pass_pro(const GicpArgs& a, VgCtl* d_ctl2, double* d_rows2, VgOut* d_out, hipStream_t s, double seq, int index);
 // pcr_fitness_batch (reloc.hip): the gated score of n_poses poses (d_poses: 16 floats each, column-major) of the subset i_j = floor(j n_src / m),
 // j < m, of the source.  d_part: n_poses x ceil(m / 256) partials; d_out[h]: the sum of the counted squared distances, their number, and the
 // number of points whose nearest target point may lie beyond a cut face of the index (fitness_kernel's out32[0..2])

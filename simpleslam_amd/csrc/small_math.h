@@ -141,4 +141,14 @@ __host__ __device__ inline void t2se3(double* T) {
 }
 
 
+// inverse of a symmetric 3x3 (xx xy xz yy yz zz) by cofactors: the Mahalanobis matrices of VGICP and GICP (vgicp.hip, gicp.hip)
+__host__ __device__ __forceinline__ void inv3_sym(const double S[6], double M[6]) {
+    const double a = S[0], b = S[1], c = S[2], d = S[3], e = S[4], f = S[5];
+    const double A = d * f - e * e, B = c * e - b * f, Cc = b * e - c * d;
+    const double det = a * A + b * B + c * Cc;
+    const double id = 1.0 / det;
+    M[0] = A * id; M[1] = B * id; M[2] = Cc * id;
+    M[3] = (a * f - c * c) * id; M[4] = (b * c - a * e) * id; M[5] = (a * d - b * b) * id;
+}
+
 }  // namespace pcr

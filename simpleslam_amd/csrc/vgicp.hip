@@ -192,15 +192,6 @@ __global__ __launch_bounds__(256) void vgicp_voxel_kernel(GridView g, const doub
 // ------------------------------------------------------------------------------
 // V4/V5: one linearisation (update_correspondences + linearize)
 // ------------------------------------------------------------------------------
-__device__ __forceinline__ void inv3_sym(const double S[6], double M[6]) {
-    const double a = S[0], b = S[1], c = S[2], d = S[3], e = S[4], f = S[5];
-    const double A = d * f - e * e, B = c * e - b * f, Cc = b * e - c * d;
-    const double det = a * A + b * B + c * Cc;
-    const double id = 1.0 / det;
-    M[0] = A * id; M[1] = B * id; M[2] = Cc * id;
-    M[3] = (a * f - c * c) * id; M[4] = (b * c - a * e) * id; M[5] = (a * d - b * b) * id;
-}
-
 // roi: a voxel that exists but lies outside the prepared region is an ESCAPE (counted; the host prepares the whole target and repeats)
 __device__ __forceinline__ uint32_t vgicp_lookup(const GridHeader& h, const uint32_t* __restrict__ cell_start, const double tp[3], const RoiView& roi) {
     if (h.overflow || h.empty) return 0;
@@ -693,6 +684,12 @@ hipError_t vgicp_launch_error(const VgicpArgs& a, const Pose16& T, double* d_out
     const uint32_t nb = vgicp_blocks(a.n_src);
     hipLaunchKernelGGL(vgicp_linearize_kernel<true>, dim3(nb), dim3(256), 0, s, a, T);
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, a.partials, nb, d_out32, seq);
+    return hipGetLastError();
+}
+
+// (for the units whose passes leave their rows in the same [block][32] layout: gicp.hip)
+hipError_t sum_partials_launch(const double* d_partials, uint32_t nblocks, double* d_out32, hipStream_t s, double seq) {
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, d_partials, nblocks, d_out32, seq);
     return hipGetLastError();
 }
 

@@ -39,7 +39,13 @@ namespace {
 static constexpr double kCovRatio = 6.0;      // cell of a level / cell of the level below
 static constexpr size_t kScanSizedMax = 300000;
 bool scan_sized(size_t n) { return n <= kScanSizedMax; }
+}  // namespace
+namespace pcr {
+namespace host {
 int cov_levels(size_t n) { return scan_sized(n) ? 2 : 1; }
+}  // namespace host
+}  // namespace pcr
+namespace {
 
 int vgicp_side_init(pcr_handle* h) {
     if (!h->side_stream) {
@@ -64,28 +70,9 @@ int vgicp_side_init(pcr_handle* h) {
 
 // (inside settle_cov_levels: work may be in flight on the auxiliary stream -- never return before it has drained)
 #define H_TRY_AUX(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (aux) (void)hipStreamSynchronize(h->vg.aux_stream); return fail(h, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-// What settle_cov_levels does beyond building and sizing the levels
-struct CovSettle {
-    double shift0 = 0.0;                  // shift of the fine level's lattice, in cells
-    GridHeader* hdr0_out = nullptr;       // where the fine level's header goes, with its density figure
-    bool may_cut = false;                 // a box no dense table can hold is cut to the bulk of the cloud (h->clamp)
-    double ahead_cell = 0.0;              // a one-level cloud: the cell of its covariance grid, built ahead in l1 beside the fine level; 0: none
-    bool* ahead_ok = nullptr;             // ... whether that grid stands
-    // after_ahead (with a grid built ahead only): what the caller would enqueue once the headers have been read, enqueued BEFORE they are -- the
-    // host waits for the headers alone (an event behind their copies) while the device goes on; *after_clean tells whether what was enqueued
-    // stands (first attempt, nothing stale or overflowing, the grid built ahead usable).  Kernels queued that way see the flags in the headers
-    // and leave early; whatever they wrote is written again by the caller.
-    const std::function<int()>* after_ahead = nullptr;
-    bool* after_clean = nullptr;
-    const std::function<int()>* before_wait = nullptr;      // what the caller wants queued on OTHER streams while the host waits for the headers
-    // scan_levels: the levels of a SCAN (the source of an alignment that did not come through vgicp_source_enqueue: pcr_set_target + pcr_align,
-    // pcr_vgicp_covariances, the redo path): built like vgicp_source_enqueue builds them -- one-level path, no hints: one scan's box and tile
-    // layout do not hold the next (walls at other distances; measured there: every hint failed and the redo cost 0.9 ms)
-    bool scan_levels = false;
-    // filter0: the fine level may index the points of a region only (BuildFilter: possible when this build reuses the header and the tile layout of
-    // an earlier full build of the level -- build() decides and says so in filter0->applied)
-    BuildFilter* filter0 = nullptr;
-};
+}  // namespace
+namespace pcr {
+namespace host {
 // the fine index plus the coarse ones of the covariance search, settled with one round trip
 int settle_cov_levels(pcr_handle* h, GridIndex& g, GridIndex& l1, GridIndex& l2, const float* d_pts, size_t n, size_t stride_floats, double cell,
                       const CovSettle& opt) {
@@ -165,6 +152,7 @@ int settle_cov_levels(pcr_handle* h, GridIndex& g, GridIndex& l1, GridIndex& l2,
                     again = true;
                     break;
                 }
+                if (hdr[l].n_cells > 4000000000ull && opt.untabulatable) *opt.untabulatable = true;      // (grow_cells refuses it)
                 if (lv[l]->grow_cells(hdr[l].n_cells, &h->err) != hipSuccess) return 1;
                 again = true;
             }
@@ -174,6 +162,9 @@ int settle_cov_levels(pcr_handle* h, GridIndex& g, GridIndex& l1, GridIndex& l2,
     }
     return fail(h, "index could not be sized");
 }
+}  // namespace host
+}  // namespace pcr
+namespace {
 // ... of a scan that did not come through vgicp_source_enqueue (pcr_vgicp_covariances, the redo of vgicp_source_settle): its levels, the checked way
 int settle_scan_levels(pcr_handle* h, const float* d_pts, size_t n, size_t stride_floats) {
     CovSettle opt;
@@ -252,7 +243,8 @@ int vgicp_source_enqueue(pcr_handle* h, const float* d_src, size_t n_src, size_t
 }  // namespace host
 }  // namespace pcr
 
-namespace {
+namespace pcr {
+namespace host {
 
 // Source covariances ready on return (ordered before whatever the main stream runs next).
 int vgicp_source_settle(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats) {
@@ -281,7 +273,8 @@ int vgicp_source_settle(pcr_handle* h, const float* d_src, size_t n_src, size_t 
     return 0;
 }
 
-}  // namespace
+}  // namespace host
+}  // namespace pcr
 
 namespace pcr {
 namespace host {
@@ -637,14 +630,14 @@ double pcr_fitness(pcr_handle* h) {
     if (!h) return -1.0;
     // PointCloudRegister::getFitnessScore() returns 0 unless overridden (PointCloudRegister.hpp:34);
     // only VgicpRegister overrides it (VgicpRegister.cpp:42-45)
-    if (h->method != kVgicp) return 0.0;
+    if (!vgicp_family(h)) return 0.0;
     if (h->fit_pending) {
         // mean squared distance of the aligned scan to its nearest target points, against the target the handle holds NOW (PCL does
         // the same: input_ transformed by final_transformation_, searched in the current target tree)
         h->fit_pending = false;
         h->err.clear();
         h->fitness = DBL_MAX;
-        if (h->vg.target_ready && h->fit_n > 0) {
+        if (vgicp_family_target_ready(h) && h->fit_n > 0) {
             if (set_device(h) || ensure_out32(h)) return -1.0;
             h->seq += 1.0;
             // (a lattice that holds the scan's region only cannot answer a nearest-neighbour question; the grid its covariances were searched on holds every point)
@@ -672,7 +665,7 @@ double pcr_fitness(pcr_handle* h) {
 int pcr_vgicp_covariances(pcr_handle* h, const void* pts, size_t n, size_t stride_bytes, int on_device, double* cov_out) {
     if (!h) return 1;
     h->err.clear();
-    if (h->method != kVgicp) return fail(h, "pcr_vgicp_covariances needs a vgicp handle");
+    if (!vgicp_family(h)) return fail(h, "pcr_vgicp_covariances needs a vgicp or gicp handle");
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
     const float* d_pts = (const float*)pts;
     if (!on_device && stage_host(h, &h->src_stage, pts, n, stride_bytes, &d_pts)) return 1;
@@ -690,7 +683,7 @@ int pcr_vgicp_covariances(pcr_handle* h, const void* pts, size_t n, size_t strid
 int pcr_vgicp_neighbours(pcr_handle* h, size_t n, uint32_t* nbr_out, uint32_t* queued_out) {
     if (!h) return 1;
     h->err.clear();
-    if (h->method != kVgicp) return fail(h, "pcr_vgicp_neighbours needs a vgicp handle");
+    if (!vgicp_family(h)) return fail(h, "pcr_vgicp_neighbours needs a vgicp or gicp handle");
     if (set_device(h)) return 1;
     const CovScratch& sc = h->vg.src_scratch;
     if (!sc.nbr.p || !h->src_grid.valid || h->src_grid.n_points > n || !scan_sized(n)) return fail(h, "no neighbour lists of a cloud of that size: call pcr_vgicp_covariances on a scan-sized cloud first");

@@ -301,6 +301,23 @@ public:
     scalar_t getFitnessScore() override { return pcr_fitness(h_); }
 };
 
+// VgicpRegister with fast_gicp::FastGICP as its registrar (fast_gicp_impl.hpp:103-237): correspondences by exact nearest neighbour
+class GicpRegister : public HipRegister {
+public:
+    GicpRegister() : HipRegister("gicp") {}
+    explicit GicpRegister(const pcr_params& p) : HipRegister("gicp", &p) {}
+    // VgicpRegister::initForLC (VgicpRegister.cpp:21-28): here its setMaxCorrespondenceDistance(150) acts too (fast_gicp_impl.hpp:136)
+    void initForLC() {
+        pcr_params p;
+        if (pcr_get_params(h_, &p)) throw std::runtime_error(pcr_last_error(h_));
+        p.vgicp_max_iters = 100;
+        p.vgicp_trans_eps = 1e-6;
+        p.gicp_max_corr_dist = 150.0;
+        if (pcr_set_params(h_, &p)) throw std::runtime_error(pcr_last_error(h_));
+    }
+    scalar_t getFitnessScore() override { return pcr_fitness(h_); }
+};
+
 // The static-map adapter: test/loc.cpp loads the global map ONCE (MapManager::MapManager(pcd_file), frontend/src/MapManager.cpp:52-78) and
 // registers every scan against it -- through the unchanged scan2Map(src, dst, res) interface.  Wrapped around any registrar above it
 // indexes `dst` at its first call (pcr_set_target: the map crosses PCIe once) and aligns every later scan against what the device holds
@@ -416,6 +433,7 @@ inline PointCloudRegister::Ptr makeRegister(const std::string& pcr_type) {
     if (pcr_type == "loam") return std::make_shared<LoamRegister>();
     if (pcr_type == "ndt") return std::make_shared<NdtRegister>();
     if (pcr_type == "vgicp") return std::make_shared<VgicpRegister>();
+    if (pcr_type == "gicp") return std::make_shared<GicpRegister>();
     throw std::runtime_error("such pcr type(" + pcr_type + ") is not exist, please implemented your self!");
 }
 // ... the same registrar behind the static-map adapter (localisation against a map that is loaded once)

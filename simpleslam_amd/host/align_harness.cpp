@@ -1,5 +1,5 @@
 // align_harness.cpp -- ROS/PCL-free counterpart of the reference's test/align.cpp:
-//   align_harness <target.pcd|.f32> <source.pcd|.f32> <loam|ndt|vgicp> [init_pose.txt]
+//   align_harness <target.pcd|.f32> <source.pcd|.f32> <loam|ndt|vgicp|gicp> [init_pose.txt]
 // loads two clouds (PCD files as align.cpp:97-107 does -- pcp/pcd_io.hpp -- or raw float32 x y z intensity records), reads the optional initial pose (4x4 row-major text,
 // align.cpp:85-93), voxel-filters BOTH clouds at 0.1 m (align.cpp:128-129), runs ONE scan2Map through the plugin mirror
 // (align.cpp:144), and prints what align.cpp logs: the cloud sizes before and after the filter, the elapsed time, the gated
@@ -48,6 +48,7 @@ int main(int argc, char** argv) {
         if (method == "loam") pcr = std::make_shared<PCR::LoamRegister>();
         else if (method == "ndt") pcr = std::make_shared<PCR::NdtRegister>();
         else if (method == "vgicp") pcr = std::make_shared<PCR::VgicpRegister>();
+        else if (method == "gicp") pcr = std::make_shared<PCR::GicpRegister>();
         else { std::fprintf(stderr, "no such method!!\n"); return -1; }                                                   // align.cpp:118-121
         std::printf("target cloud size: %zu\nsource cloud size: %zu\n", target_cloud->size(), source_cloud->size());
         auto t0 = std::chrono::steady_clock::now();

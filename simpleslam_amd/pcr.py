@@ -39,6 +39,7 @@ class PcrParams(C.Structure):
         ("index_no_hints", C.c_int32), ("ndt_evaluate_repeats", C.c_int32), ("loam_disable_cache", C.c_int32), ("record_timeline", C.c_int32),
         ("loam_coresident", C.c_int32), ("loam_clamp_margin_mm", C.c_int32), ("full_target", C.c_int32), ("host_optimiser", C.c_int32),
         ("host_copy_xyz", C.c_int32),
+        ("gicp_max_corr_dist", C.c_double),
     ]
 
 
@@ -56,7 +57,7 @@ class PcrStats(C.Structure):
 ABI_SYMBOLS = [
     "pcr_default_params", "pcr_create", "pcr_destroy", "pcr_last_error", "pcr_scan2map", "pcr_scan2map_device", "pcr_host_pin", "pcr_host_unpin",
     "pcr_set_target", "pcr_align", "pcr_invalidate_target", "pcr_fitness", "pcr_loam_linearize", "pcr_get_trace", "pcr_get_trace_counts",
-    "pcr_vgicp_covariances", "pcr_vgicp_neighbours", "pcr_vgicp_linearize", "pcr_voxel_filter", "pcr_voxel_filter_begin", "pcr_voxel_filter_end", "pcr_get_timeline", "pcr_ndt_derivatives", "pcr_get_stats", "pcr_set_profile", "pcr_set_stream", "pcr_set_query_tile", "pcr_comm_unique_id", "pcr_comm_init", "pcr_comm_info", "pcr_comm_peer_export", "pcr_comm_init_peer",
+    "pcr_vgicp_covariances", "pcr_vgicp_neighbours", "pcr_vgicp_linearize", "pcr_gicp_linearize", "pcr_voxel_filter", "pcr_voxel_filter_begin", "pcr_voxel_filter_end", "pcr_get_timeline", "pcr_ndt_derivatives", "pcr_get_stats", "pcr_set_profile", "pcr_set_stream", "pcr_set_query_tile", "pcr_comm_unique_id", "pcr_comm_init", "pcr_comm_info", "pcr_comm_peer_export", "pcr_comm_init_peer",
     "pcr_comm_init_host", "pcr_set_shard", "pcr_set_params", "pcr_get_params", "pcr_fitness_gated",
     "pcr_map_create", "pcr_map_destroy", "pcr_map_last_error", "pcr_map_add_keyframe", "pcr_map_keyframes", "pcr_map_clear", "pcr_map_update", "pcr_map_update_begin", "pcr_map_wait", "pcr_map_update_window", "pcr_map_submap",
     "pcr_map_submap_indices", "pcr_map_generation", "pcr_scan2map_submap",
@@ -144,6 +145,7 @@ def load_library():
     L.pcr_vgicp_covariances.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp]
     L.pcr_vgicp_neighbours.argtypes = [vp, C.c_size_t, vp, vp]
     L.pcr_vgicp_linearize.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, dp, dp, dp, C.POINTER(C.c_int64)]
+    L.pcr_gicp_linearize.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int64), vp, vp, vp]
     L.pcr_ndt_derivatives.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, dp, dp, dp, dp]
     L.pcr_get_timeline.argtypes = [vp, vp, C.c_size_t, ip, ip]
     L.pcr_voxel_filter.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_double, vp, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
@@ -772,9 +774,49 @@ class VgicpRegister(PointCloudRegister):
         return dict(H=H.reshape(6, 6), b=b, err=err.value, n=int(nc.value))
 
 
+class GicpRegister(PointCloudRegister):
+    """PCR::VgicpRegister with fast_gicp::FastGICP as its registrar (fast_gicp_impl.hpp:103-237): correspondences by exact nearest
+    neighbour, the two covariances fused per pair."""
+    method = "gicp"
+    covariances = VgicpRegister.covariances      # (pcr_vgicp_covariances / pcr_vgicp_neighbours serve gicp handles: the same covariances)
+    neighbours = VgicpRegister.neighbours
+
+    def initForLC(self):
+        """VgicpRegister::initForLC (VgicpRegister.cpp:21-28): 100 iterations, transformation epsilon 1e-6, and
+        setMaxCorrespondenceDistance(150), which acts here (fast_gicp_impl.hpp:136)."""
+        self.set_params(vgicp_max_iters=100, vgicp_trans_eps=1e-6, gicp_max_corr_dist=150.0)
+
+    def linearize(self, src, pose, pose_eval=None, per_point=False):
+        """One update_correspondences + linearize at `pose` against the kept target (setTarget): dict(H, b, err, n[, err_eval][, corr, d2, M]).
+        err_eval = compute_error(pose_eval) on the correspondences of that linearisation; per_point: corr (n,) int32 with -1 for none,
+        d2 (n,) float32 with +inf for none, M (n,3,3)."""
+        p, n, s, dev, _k = _cloud(src)
+        pc = _pose_in(pose)
+        pe = _pose_in(pose_eval) if pose_eval is not None else None
+        H, b = np.zeros(36), np.zeros(6)
+        err, err_eval, nc = C.c_double(0), C.c_double(0), C.c_int64(0)
+        corr = np.zeros(n, np.int32) if per_point else None
+        d2 = np.zeros(n, np.float32) if per_point else None
+        m6 = np.zeros((n, 6)) if per_point else None
+        dp = C.POINTER(C.c_double)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._check(self._lib.pcr_gicp_linearize(self._h, p, n, s, dev, pc.ctypes.data_as(dp), pe.ctypes.data_as(dp) if pe is not None else None,
+                                                 H.ctypes.data_as(dp), b.ctypes.data_as(dp), C.byref(err), C.byref(err_eval), C.byref(nc),
+                                                 vp(corr), vp(d2), vp(m6)))
+        out = dict(H=H.reshape(6, 6), b=b, err=err.value, n=int(nc.value))
+        if pe is not None:
+            out["err_eval"] = err_eval.value
+        if per_point:
+            M = np.zeros((n, 3, 3))
+            M[:, 0, 0], M[:, 0, 1], M[:, 0, 2], M[:, 1, 1], M[:, 1, 2], M[:, 2, 2] = m6.T
+            M[:, 1, 0], M[:, 2, 0], M[:, 2, 1] = M[:, 0, 1], M[:, 0, 2], M[:, 1, 2]
+            out.update(corr=corr, d2=d2, M=M)
+        return out
+
+
 def make_register(pcr_type, **overrides):
-    """The reference's factory on cfg["frontend"]["pcr"] (LidarOdometry.cpp:32,44-54)."""
-    table = {"loam": LoamRegister, "ndt": NdtRegister, "vgicp": VgicpRegister}
+    """The reference's factory on cfg["frontend"]["pcr"] (LidarOdometry.cpp:32,44-54), plus "gicp"."""
+    table = {"loam": LoamRegister, "ndt": NdtRegister, "vgicp": VgicpRegister, "gicp": GicpRegister}
     if pcr_type not in table:
         raise RuntimeError(f"such pcr type({pcr_type}) is not exist, please implemented your self!")
     return table[pcr_type](**overrides)
