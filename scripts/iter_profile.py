@@ -31,6 +31,15 @@ t = tl[0]; ok = t[:, 10] > 0
 if ok.any():
     for a, b, n in ((2, 8, 'ranges'), (8, 9, 'first group'), (9, 10, 'stream'), (10, 3, 'decode + exchange')):
         print(f'  launch 0 dense search: {n:18s} {np.mean(t[ok, b] - t[ok, a]):6.2f} us')
+# the refine + plane stage ('plane' above: searched -> entry stamp), split by the stamps inside it
+sub = (('gather', 3, 12), ('dist+sort+proof', 12, 13), ('plane fit', 13, 14), ('plane gate', 14, 15), ('entry', 15, 4))
+print('refine + plane stage, mean block, us:  ' + ' | '.join(n for n, _, _ in sub) + ' | whole stage')
+for k in range(min(4, tl.shape[0])):
+    t = tl[k]; ok = (t[:, 6] > 0) & (t[:, 12] > 0)
+    if ok.any():
+        print(f'  launch {k}: ' + ' | '.join(f'{np.mean(t[ok, b] - t[ok, a]):5.2f}' for _, a, b in sub) + f' | {np.mean(t[ok, 4] - t[ok, 3]):5.2f}')
+import hashlib
+print('pose sha1', hashlib.sha1(np.ascontiguousarray(pose).tobytes()).hexdigest())
 reg.set_profile(2)
 pose = T0.copy(); reg.scan2Map(ds, dm, pose)
 print(reg.stats())

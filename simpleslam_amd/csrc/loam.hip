@@ -384,24 +384,22 @@ __device__ __forceinline__ void plane_qr_solve(double a[5][3], double x[3]) {
                 const int t = perm[k]; perm[k] = perm[j]; perm[j] = t;
             }
         }
+        // Straight-line code from here on (selects, no branches): one basic block per Householder step lets the independent
+        // sqrt / division sequences -- the four a[i][k] / den, tau, the two columns' downdates -- interleave.  Every value that
+        // is kept is computed by the same operations in the same order as in the branching form.
         double tail_sq = 0;
 #pragma unroll
         for (int i = k + 1; i < 5; ++i) tail_sq += a[i][k] * a[i][k];
         const double c0 = a[k][k];
-        double beta;
-        if (tail_sq <= 2.2250738585072014e-308) {
-            tau[k] = 0; beta = c0;
+        const bool tiny = tail_sq <= 2.2250738585072014e-308;
+        double beta_h = sqrt(c0 * c0 + tail_sq);
+        beta_h = c0 >= 0 ? -beta_h : beta_h;
+        const double den = c0 - beta_h;
 #pragma unroll
-            for (int i = k + 1; i < 5; ++i) a[i][k] = 0;
-        } else {
-            beta = sqrt(c0 * c0 + tail_sq);
-            if (c0 >= 0) beta = -beta;
-            const double den = c0 - beta;
-#pragma unroll
-            for (int i = k + 1; i < 5; ++i) a[i][k] /= den;
-            tau[k] = (beta - c0) / beta;
-        }
-        a[k][k] = beta;
+        for (int i = k + 1; i < 5; ++i) { const double q = a[i][k] / den; a[i][k] = tiny ? 0.0 : q; }
+        const double tau_h = (beta_h - c0) / beta_h;
+        tau[k] = tiny ? 0.0 : tau_h;
+        a[k][k] = tiny ? c0 : beta_h;
 #pragma unroll
         for (int j = k + 1; j < 3; ++j) {
             double tmp = 0;
@@ -414,44 +412,42 @@ __device__ __forceinline__ void plane_qr_solve(double a[5][3], double x[3]) {
         }
 #pragma unroll
         for (int j = k + 1; j < 3; ++j) {
-            if (nu[j] != 0) {
-                double temp = fabs(a[k][j]) / nu[j];
-                temp = (1.0 + temp) * (1.0 - temp);
-                if (temp < 0) temp = 0;
-                const double r = nu[j] / nd[j];
-                const double temp2 = temp * r * r;
-                if (temp2 <= downdate_thr) {
-                    double s = 0;
+            const bool nz = nu[j] != 0;
+            double temp = fabs(a[k][j]) / nu[j];
+            temp = (1.0 + temp) * (1.0 - temp);
+            temp = temp < 0 ? 0.0 : temp;
+            const double r = nu[j] / nd[j];
+            const double temp2 = temp * r * r;
+            const bool recompute = temp2 <= downdate_thr;
+            double s = 0;
 #pragma unroll
-                    for (int i = k + 1; i < 5; ++i) s += a[i][j] * a[i][j];
-                    nd[j] = sqrt(s); nu[j] = nd[j];
-                } else {
-                    nu[j] *= sqrt(temp);
-                }
-            }
+            for (int i = k + 1; i < 5; ++i) s += a[i][j] * a[i][j];
+            const double root = sqrt(recompute ? s : temp);
+            const double nu_new = recompute ? root : nu[j] * root;
+            nd[j] = (nz && recompute) ? root : nd[j];
+            nu[j] = nz ? nu_new : nu[j];
         }
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        if (k < nonzero) {
-            double tmp = 0;
+        const bool on = k < nonzero;
+        double tmp = 0;
 #pragma unroll
-            for (int i = k + 1; i < 5; ++i) tmp += a[i][k] * c[i];
-            tmp += c[k];
-            c[k] -= tau[k] * tmp;
+        for (int i = k + 1; i < 5; ++i) tmp += a[i][k] * c[i];
+        tmp += c[k];
+        const double ck = c[k] - tau[k] * tmp;
+        c[k] = on ? ck : c[k];
 #pragma unroll
-            for (int i = k + 1; i < 5; ++i) c[i] -= tau[k] * a[i][k] * tmp;
-        }
+        for (int i = k + 1; i < 5; ++i) { const double ci = c[i] - tau[k] * a[i][k] * tmp; c[i] = on ? ci : c[i]; }
     }
     double y[3] = {0, 0, 0};
 #pragma unroll
     for (int i = 2; i >= 0; --i) {
-        if (i < nonzero) {
-            double s = c[i];
+        double s = c[i];
 #pragma unroll
-            for (int j = i + 1; j < 3; ++j) if (j < nonzero) s -= a[i][j] * y[j];
-            y[i] = s / a[i][i];
-        }
+        for (int j = i + 1; j < 3; ++j) { const double t = s - a[i][j] * y[j]; s = (j < nonzero) ? t : s; }
+        const double q = s / a[i][i];
+        y[i] = (i < nonzero) ? q : 0.0;
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -575,6 +571,52 @@ struct MissExchange {
     } u;
 };
 
+// What one scan point leaves in its cache entry for the next launch.  loam_point only fills this in (registers); the caller
+// stores it once the block's accumulate phase is over (entry_store_wave).
+struct EntryWrite {
+    uint32_t what;             // bit0: neighbours  bit1: anchor  bit2: plane tail  bit3: invalidate only
+    Nb8 s;
+    float q[3];
+    double bound_sq;
+    double x[3];
+    uint32_t flags;
+};
+
+// The entries of a wave's 64 consecutive scan points are 12 KB of contiguous memory.  Written by their owners they are twelve
+// 16-byte stores per lane at a 192-byte lane stride -- 64 cache lines per instruction, 2.7 us of every launch that searches
+// (profiles/loam_refine_notes.md).  Here the wave transposes them through its own 12 KB slice of LDS (the block's search and
+// row scratch, dead by now) and stores 1 KB of contiguous memory per instruction; every 16-byte field is stored iff its owner
+// marked it (the owner's mask comes by lane permute), so a field that is not rewritten keeps what it holds.
+// e0: entry of the wave's lane 0.  stage: kEntryVec * 64 float4 of this wave.  All 64 lanes call it together.
+__device__ __forceinline__ void entry_store_wave(NnCacheEntry* __restrict__ e0, const EntryWrite& w, float4* stage) {
+    const int lane = threadIdx.x & 63;
+    if (w.what & 8u) e0[lane].flags = 0;
+    float4* const mine = stage + lane * kEntryVec;
+#pragma unroll
+    for (int j = 0; j < kNb; ++j) mine[j] = make_float4(w.s.x[j], w.s.y[j], w.s.z[j], __uint_as_float(w.s.idx[j]));
+    // the anchor of the entry: this search's query position and what it proved about everything it did not list
+    mine[kNb] = make_float4(w.q[0], w.q[1], w.q[2], __double2float_rd(sqrt(w.bound_sq) * (1.0 - 1e-15)));
+    union { struct { double x[3]; uint32_t pidx[5]; uint32_t flags; } t; float4 v[3]; } tail;
+    tail.t.x[0] = w.x[0]; tail.t.x[1] = w.x[1]; tail.t.x[2] = w.x[2];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) tail.t.pidx[j] = w.s.idx[j];
+    tail.t.flags = w.flags;
+#pragma unroll
+    for (int f = 0; f < 3; ++f) mine[kNb + 1 + f] = tail.v[f];
+    const uint32_t fields = ((w.what & 1u) ? 0x0ffu : 0u) | ((w.what & 2u) ? 0x100u : 0u) | ((w.what & 4u) ? 0xe00u : 0u);
+    // (same wave: its LDS operations complete in order, so the slice is visible to the reads below)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    float4* const dst = reinterpret_cast<float4*>(e0);
+#pragma unroll
+    for (int i = 0; i < kEntryVec; ++i) {
+        const uint32_t c = (uint32_t)(i * 64 + lane);      // 16-byte field c of the wave's 64 x 12
+        const uint32_t owner = c / (uint32_t)kEntryVec, f = c - owner * (uint32_t)kEntryVec;
+        const uint32_t m = (uint32_t)__shfl((int)fields, (int)owner, 64);
+        const float4 v = stage[c];
+        if ((m >> f) & 1u) dst[c] = v;
+    }
+}
+
 // ------------------------------------------------------------------------------
 // one scan point: returns status (0 accepted, 1 k-NN gate, 2 plane gate, 3 weight gate,
 // 4 outside this rank's query tile / no point);  row[0..5] = s*[n ; p x n], row[6] = s*d
@@ -584,7 +626,7 @@ template <int kGroup>
 __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h, const double* __restrict__ pose,
                                           float sx, float sy, float sz, bool valid, const NnCacheEntry& ce_in, bool have_entry,
                                           KnnRuns& sh, MissExchange& ex, double row[7], uint32_t nn_idx[5], uint32_t qi, int* how,
-                                          bool* escaped, unsigned long long* tl, const bool all_search = false) {
+                                          bool* escaped, EntryWrite& ew, unsigned long long* tl, const bool all_search = false) {
     const double ox = (double)sx, oy = (double)sy, oz = (double)sz;
     // LoamRegister.cpp:126-130: Isometry3d * Vector4d in f64, then cast to f32
     const float px = (float)(pose[0] * ox + pose[4] * oy + pose[8] * oz + pose[12] * 1.0);
@@ -741,9 +783,18 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
         float4 p8[kNb];
 #pragma unroll
         for (int j = 0; j < kNb; ++j) p8[j] = a.grid.pts[(searched && rp[j] != kNoPos) ? rp[j] : 0u];
+        if (tl) { float t_ = 0.f; for (int j = 0; j < kNb; ++j) t_ += p8[j].x; if (t_ == 1.2345e38f) state = 0u; tl[12] = wall_clock64(); }   // gather returned
 #pragma unroll
         for (int j = 0; j < kNb; ++j) nb8_set(s, j, p8[j], searched && state != 3u && rp[j] != kNoPos, qx, qy, qz);
-        nb8_sort(s);
+        // The keys arrive in ascending float-distance order, so the exact order usually holds already: tested the way
+        // knn_from_cache does, and the network is skipped by the whole wave.  (The first five in order and none of the other
+        // three before the fifth is all that is read below; the same network runs as soon as one lane is out of order.)
+        bool ord = true;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ord = ord & !knn_less(s.d[j + 1], s.idx[j + 1], s.d[j], s.idx[j]);
+#pragma unroll
+        for (int j = 5; j < kNb; ++j) ord = ord & !knn_less(s.d[j], s.idx[j], s.d[4], s.idx[4]);
+        if (!__all(ord)) nb8_sort(s);
         // a screened list is final when its fifth entry is strictly nearer than everything that is not listed
         const bool proven = state == 2u || (state == 1u && (s.idx[4] == 0xffffffffu ? !(bound_sq < a.c.knn_max_sq) : s.d[4] < bound_sq));
         if (searched && !proven) {
@@ -757,6 +808,7 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
         }
         bound_sq = fmin(bound_sq, a.c.knn_max_sq);      // points outside the 3x3x3 block are >= one cell (>= sqrt(max_sq)) away
     }
+    if (tl) { if (searched && s.d[4] == 1.2345e300) bound_sq = 0.0; tl[13] = wall_clock64(); }   // distances, order and proof done
     __syncthreads();   // ex.u.rows is written next
     *how = hit ? 1 : (miss ? 2 : 0);
     const bool real5 = searched && s.idx[4] != 0xffffffffu;     // five real neighbours present
@@ -775,11 +827,16 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
     if (reuse) {
         x[0] = ce_in.x[0]; x[1] = ce_in.x[1]; x[2] = ce_in.x[2];
         plane_ok = (ce_in.flags & 4u) != 0;
-    } else if (real5) {
+    }
+    const bool fit = real5 && !reuse;
+    if (fit) {
         double Aq[5][3];
 #pragma unroll
         for (int j = 0; j < 5; ++j) { Aq[j][0] = A[j][0]; Aq[j][1] = A[j][1]; Aq[j][2] = A[j][2]; }
         plane_qr_solve(Aq, x);
+    }
+    if (tl) { if (x[0] == 1.2345e300) x[1] = 0.0; tl[14] = wall_clock64(); }   // plane solved
+    if (fit) {
         const double xn0 = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
         plane_ok = true;           // LoamRegister.cpp:38-43
 #pragma unroll
@@ -788,32 +845,20 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
             if (fabs(dot + 1.0) > a.c.plane_thresh * xn0) plane_ok = false;
         }
     }
+    if (tl) { if (plane_ok && x[0] == 1.2345e300) x[1] = 0.0; tl[15] = wall_clock64(); }   // plane gate done
     // ---- remember everything for the next iteration ----
+    ew.what = 0u;
     if (a.nn_cache && in_range && !active) {
         // not handled by this launch (outside this rank's query tile): whatever entry is there -- a previous iteration's, a
         // previous scan's -- must not be trusted when the query comes back
-        a.nn_cache[qi].flags = 0;
+        ew.what = 8u;
     }
-    if (a.nn_cache && active) {
-        float4* const dst = reinterpret_cast<float4*>(a.nn_cache + qi);
-        if (miss || moved) {
-#pragma unroll
-            for (int j = 0; j < kNb; ++j) dst[j] = make_float4(s.x[j], s.y[j], s.z[j], __uint_as_float(s.idx[j]));
-        }
-        if (miss) {
-            // the anchor of the entry: this search's query position and what it proved about everything it did not list
-            dst[kNb] = make_float4(px, py, pz, __double2float_rd(sqrt(bound_sq) * (1.0 - 1e-15)));
-        }
-        if (miss || !reuse) {
-            union { struct { double x[3]; uint32_t pidx[5]; uint32_t flags; } t; float4 v[3]; } tail;
-            tail.t.x[0] = x[0]; tail.t.x[1] = x[1]; tail.t.x[2] = x[2];
-#pragma unroll
-            for (int j = 0; j < 5; ++j) tail.t.pidx[j] = s.idx[j];
-            tail.t.flags = (searched ? 1u : 0u) | (real5 ? 2u : 0u) | (plane_ok ? 4u : 0u);
-#pragma unroll
-            for (int f = 0; f < 3; ++f) dst[kNb + 1 + f] = tail.v[f];
-        }
-    }
+    if (a.nn_cache && active) ew.what = ((miss || moved) ? 1u : 0u) | (miss ? 2u : 0u) | ((miss || !reuse) ? 4u : 0u);
+    ew.s = s;
+    ew.q[0] = px; ew.q[1] = py; ew.q[2] = pz;
+    ew.bound_sq = bound_sq;
+    ew.x[0] = x[0]; ew.x[1] = x[1]; ew.x[2] = x[2];
+    ew.flags = (searched ? 1u : 0u) | (real5 ? 2u : 0u) | (plane_ok ? 4u : 0u);
     if (tl) tl[4] = wall_clock64();
     if (!valid) return 4;
     if (!searched) return 1;
@@ -1100,6 +1145,7 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const 
         uint32_t nn[5] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
         int how = 0;
         bool esc = false;
+        EntryWrite ew;
         float sx = pre_x, sy = pre_y, sz = pre_z;
         union { NnCacheEntry e; float4 v[kEntryVec]; } ce;
         ce.e.flags = 0;
@@ -1123,7 +1169,7 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const 
                 if (use_cache) ce.e = a.nn_cache[q];
             }
         }
-        const int st = loam_point<kGroup>(a, h, pose, sx, sy, sz, valid, ce.e, use_cache && valid && !all_search, sh_knn, sh_ex, row, nn, q, &how, &esc,
+        const int st = loam_point<kGroup>(a, h, pose, sx, sy, sz, valid, ce.e, use_cache && valid && !all_search, sh_knn, sh_ex, row, nn, q, &how, &esc, ew,
                                           base == blk * qpb ? tl : nullptr, all_search);
         if (valid && (a.dbg_status || a.dbg_nn || a.dbg_rows)) {
             const size_t oi = (size_t)q;
@@ -1144,6 +1190,10 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const 
             for (int i = 0; i < 32; ++i) acc += ra[i] * rb[i];
         }
         __syncthreads();
+        // The cache entries go out last, behind everything the block waits for; the rows and the search scratch are dead, so
+        // their LDS stages the transposition.  (wave-uniform test: nothing is staged or stored in a wave of unchanged entries)
+        if (__any(ew.what != 0u)) entry_store_wave(a.nn_cache + (q - (uint32_t)(tid & 63)), ew, reinterpret_cast<float4*>(sh_ov) + (tid >> 6) * (64 * kEntryVec));
+        if (base + gridDim.x * qpb < a.n_src) __syncthreads();      // (grid-stride launch: the next round reuses that LDS)
     }
     if (tl) tl[5] = wall_clock64();
     sh_sum[ch * 32 + e] = e < 28 ? acc : 0.0;
