@@ -6,8 +6,9 @@
 //      squared distance, (C_B + T C_A T^T)^-1 per pair
 //   linearize                :156-211  H, b, error over the pairs
 //   compute_error            :214-237  the error at a trial pose on the pairs of the last linearisation
-//   -> gicp_lin_body<false> (update_correspondences + linearize in one pass) and <true> (compute_error of an LM trial pose on the
-//      other correspondence buffer + the linearisation AT that pose), the sums through vgicp.hip's fixed-order reduction.
+//   -> gicp_lin_point (update_correspondences + linearize of one source point) and gicp_err_point (compute_error of one point), the
+//      two functions VGICP's pass does not have.  The pass around them -- the fixed-order reduction of the sums, the trial pass that
+//      also linearises at its pose, the device-resident loop's prologue -- is lsq_pass.h's, shared with vgicp.hip.
 // The covariances of both clouds are vgicp.hip's (vgicp_cov_kernel / cov_search.hip); the search is ring_search.h's exact 1-NN in
 // PCL's float metric, as the fitness score uses it.
 #include <float.h>
@@ -17,11 +18,11 @@
 #include "pcr_internal.h"
 #include "small_math.h"
 #include "vgicp_opt.h"
+#include "lsq_pass.h"
 #include "ring_search.h"
 
 namespace pcr {
 
-static constexpr int kLinStride = 258;      // (vgicp.hip: the row stride of the block reduction)
 static constexpr uint32_t kNoCorr = 0xffffffffu;
 
 // the pair of source point i at pose T: the nearest target point of T a_i in float (ties on the lower original index), gated;
@@ -108,146 +109,29 @@ __device__ __forceinline__ double gicp_err_point(const GicpArgs& a, const Pose16
     return er[0] * Me0 + er[1] * Me1 + er[2] * Me2;
 }
 
-// kWithError = false: update_correspondences + linearize at T -- pairs to a.corr / a.corr_M, partial sums [0..27].
-// kWithError = true: one pass for an LM trial pose T: [28] = compute_error(T) on the pairs of the last linearisation (a.corr / a.corr_M,
-// read only) AND the linearisation AT T (pairs to a.corr_next / a.corr_M_next, sums [0..27]) -- what vgicp_lin_body does for VGICP, so
-// that vg_opt::ctl_step and its parity rule serve both.  One source point per thread; the 28 or 29 sums leave through the same
-// fixed-order LDS reduction into [block][32] rows: no atomics, bit-for-bit repeatable.
-template <bool kWithError>
-__device__ __forceinline__ void gicp_lin_body(const GicpArgs& a, const Pose16& T, double* sh /* [29][kLinStride] */, double* sh_sum /* [8][32] */) {
-    constexpr int kRows = kWithError ? 29 : 28;
-    const int tid = threadIdx.x, e = tid & 31, ch = tid >> 5;
-    double acc = 0.0;
-    for (uint32_t base = blockIdx.x * 256; base < a.n_src; base += gridDim.x * 256) {
-        const uint32_t i = base + tid;
-        double v[28];
-#pragma unroll
-        for (int k = 0; k < 28; ++k) v[k] = 0.0;
-        double err = 0.0;
-        if (i < a.n_src) {
-            if (kWithError) {
-                err = gicp_err_point(a, T, i);
-                gicp_lin_point(a, T, i, v, a.corr_next, a.corr_M_next);
-            } else {
-                gicp_lin_point(a, T, i, v, a.corr, a.corr_M);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 28; ++k) sh[k * kLinStride + tid] = v[k];
-        if (kWithError) sh[28 * kLinStride + tid] = err;
-        __syncthreads();
-        if (e < kRows) {
-            const double* row = sh + e * kLinStride + ch * 32;
-#pragma unroll 8
-            for (int k = 0; k < 32; ++k) acc += row[k];
-        }
-        __syncthreads();
+// The pass of lsq_pass.h over GICP's point pairs
+struct GicpPass {
+    const GicpArgs& a;
+    __device__ __forceinline__ void lin(const Pose16& T, uint32_t i, double v[28], bool to_next) const {
+        gicp_lin_point(a, T, i, v, to_next ? a.corr_next : a.corr, to_next ? a.corr_M_next : a.corr_M);
     }
-    sh_sum[ch * 32 + e] = e < kRows ? acc : 0.0;
-    __syncthreads();
-    if (tid < 32) {
-        double s = sh_sum[tid];
-#pragma unroll
-        for (int c = 1; c < 8; ++c) s += sh_sum[c * 32 + tid];
-        a.partials[(size_t)blockIdx.x * 32 + tid] = s;
-    }
-}
+    __device__ __forceinline__ double err(const Pose16& T, uint32_t i) const { return gicp_err_point(a, T, i); }
+};
 
 template <bool kWithError>
 __global__ __launch_bounds__(256) void gicp_linearize_kernel(const GicpArgs a, const Pose16 T) {
     __shared__ double sh[(kWithError ? 29 : 28) * kLinStride];
     __shared__ double sh_sum[8 * 32];
-    gicp_lin_body<kWithError>(a, T, sh, sh_sum);
+    lsq_lin_body<kWithError>(GicpPass{a}, T, a.n_src, a.partials, sh, sh_sum);
 }
 
-// ------------------------------------------------------------------------------
-// Device-resident Levenberg-Marquardt loop: one launch per pass, whose prologue folds the rows of the previous launch and takes the
-// optimiser's step -- vgicp_pass_pro_kernel's prologue restated for an unsharded target (no peer exchange, no region): the same
-// fold order, the same vg_opt::ctl_step in every block, the same progress word and result block.
-// ------------------------------------------------------------------------------
-struct GicpProArgs {
-    const double* rows_prev;     // [rows_prev_n][32]
-    const VgCtl* ctl_prev;
-    VgCtl* ctl_next;
-    VgOut* out;
-    double seq;
-    uint32_t rows_prev_n;
-    int32_t first;
-};
-static constexpr int kVgCtlWords = (int)((sizeof(VgCtl) + 3) / 4);
-static_assert(sizeof(VgCtl) % 4 == 0, "VgCtl is copied word by word");
-
-__global__ __launch_bounds__(256) void gicp_pass_pro_kernel(const GicpArgs a_in, const GicpProArgs pa) {
+// a launch of the device-resident Levenberg-Marquardt loop (lsq_pass.h), of an unsharded target: no peer exchange, no region
+__global__ __launch_bounds__(256) void gicp_pass_pro_kernel(const GicpArgs a, const LsqProArgs pa) {
     __shared__ double sh[29 * kLinStride];
     __shared__ double sh_sum[8 * 32];
     __shared__ __attribute__((aligned(16))) uint32_t sh_ctl[kVgCtlWords];
     __shared__ double sh_sums[32];
-    const int t = threadIdx.x;
-    VgCtl* const c = reinterpret_cast<VgCtl*>(sh_ctl);
-    // the state and the rows of the previous launch ([8 slices][32 components], 32 rows a thread per 256 rows; 512 rows beyond 65 536 source points)
-    const int comp = t & 31, slice = t >> 5;
-    double acc = 0.0;
-    for (int w = t; w < kVgCtlWords; w += 256) sh_ctl[w] = reinterpret_cast<const uint32_t*>(pa.ctl_prev)[w];
-    if (!pa.first)
-        for (uint32_t r0 = 0; r0 < pa.rows_prev_n; r0 += 256) {
-            double v[32];
-#pragma unroll
-            for (int u = 0; u < 32; ++u) {
-                const uint32_t row = r0 + (uint32_t)(slice + 8 * u);
-                v[u] = row < pa.rows_prev_n ? pa.rows_prev[(size_t)row * 32 + comp] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 32; ++u) acc += v[u];
-        }
-    sh_sum[slice * 32 + comp] = acc;
-    __syncthreads();
-    if (c->done) {      // finished in an earlier launch: hand the state on to whatever is queued behind
-        if (blockIdx.x == 0) for (int w = t; w < kVgCtlWords; w += 256) reinterpret_cast<uint32_t*>(pa.ctl_next)[w] = sh_ctl[w];
-        return;
-    }
-    if (!pa.first) {
-        if (t < 32) {
-            double s = sh_sum[t];
-#pragma unroll
-            for (int k = 1; k < 8; ++k) s += sh_sum[k * 32 + t];
-            sh_sums[t] = s;
-        }
-        __syncthreads();
-        if (t == 0) vg_opt::ctl_step(c, sh_sums);
-        __syncthreads();
-        if (blockIdx.x == 0) {
-            for (int w = t; w < kVgCtlWords; w += 256) reinterpret_cast<uint32_t*>(pa.ctl_next)[w] = sh_ctl[w];
-            if (t == 0) {
-                VgOut* const out = pa.out;
-                if (c->done) {
-                    out->x0 = c->x0;
-                    out->conv = c->conv; out->outer = c->outer; out->n_lin = c->n_lin; out->n_err = c->n_err; out->passes = c->passes;
-                    out->roi_escapes = 0;
-                    __threadfence_system();
-                    __hip_atomic_store(&out->seq, pa.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                } else {
-                    __hip_atomic_store(&out->progress, pa.seq * kProgressWindow + (double)c->passes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-            }
-        }
-        if (c->done) return;
-    }
-    // the pose of this pass and the correspondence buffers, as scalars
-    Pose16 T;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const double v = c->xi.m[i];
-        T.m[i] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-    }
-    const int kind = __builtin_amdgcn_readfirstlane(c->kind), parity = __builtin_amdgcn_readfirstlane(c->parity);
-    GicpArgs a = a_in;
-    if (parity) {
-        a.corr = a_in.corr_next; a.corr_M = a_in.corr_M_next;
-        a.corr_next = a_in.corr; a.corr_M_next = a_in.corr_M;
-    }
-    __syncthreads();      // (sh_sum is reused by the body)
-    if (kind == kVgPassLinearize) gicp_lin_body<false>(a, T, sh, sh_sum);
-    else gicp_lin_body<true>(a, T, sh, sh_sum);
+    lsq_pass<false, GicpPass>(a, pa, nullptr, sh, sh_sum, sh_ctl, sh_sums);
 }
 
 // ---- host launchers ---------------------------------------------------------------
@@ -263,16 +147,12 @@ hipError_t gicp_launch_error(const GicpArgs& a, const Pose16& T, double* d_out32
     return sum_partials_launch(a.partials, nb, d_out32, s, seq);
 }
 
-// launch `index` of the device-resident loop: d_ctl2 = two VgCtl, d_rows2 = two buffers of 512 * 32 doubles (vgicp_launch_pass_pro's layout)
+// launch `index` of the device-resident loop (lsq_pass.h: lsq_pro_args)
 hipError_t gicp_launch_pass_pro(const GicpArgs& a_in, VgCtl* d_ctl2, double* d_rows2, VgOut* d_out, hipStream_t s, double seq, int index) {
     const uint32_t nb = vgicp_blocks(a_in.n_src);
     GicpArgs a = a_in;
-    a.partials = d_rows2 + (size_t)(index & 1) * 512 * 32;
-    GicpProArgs pa;
-    pa.rows_prev = d_rows2 + (size_t)((index + 1) & 1) * 512 * 32;
-    pa.ctl_prev = index == 0 ? d_ctl2 : d_ctl2 + ((index + 1) & 1);
-    pa.ctl_next = d_ctl2 + (index & 1);
-    pa.out = d_out; pa.seq = seq; pa.rows_prev_n = nb; pa.first = index == 0 ? 1 : 0;
+    a.partials = lsq_rows(d_rows2, index);
+    const LsqProArgs pa = lsq_pro_args(d_ctl2, d_rows2, d_out, seq, index, nb);
     hipLaunchKernelGGL(gicp_pass_pro_kernel, dim3(nb), dim3(256), 0, s, a, pa);
     return hipGetLastError();
 }

@@ -1,10 +1,10 @@
-// gicp_host.hip -- GICP host driver: fast_gicp::FastGICP (fast_gicp_impl.hpp:103-237) under PCL's align() and LsqRegistration
-// (vgicp_opt.h, the state machine VGICP runs), the preparation of its target and pcr_gicp_linearize.  The scan's side is VGICP's
-// (vgicp_host.hip: vgicp_source_enqueue / vgicp_source_settle).
+// gicp_host.hip -- GICP's host side: fast_gicp::FastGICP (fast_gicp_impl.hpp:103-237), the preparation of its target, its refusals and
+// pcr_gicp_linearize.  PCL's align() and the LsqRegistration loop around its passes are lsq_host.h's run_lsq, the driver VGICP runs too; the
+// scan's side is VGICP's (vgicp_host.hip: vgicp_source_enqueue / vgicp_source_settle).
 
 #include <algorithm>
 
-#include "handle.h"
+#include "lsq_host.h"
 
 using namespace pcr;
 using namespace pcr::host;
@@ -44,18 +44,13 @@ int gicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t 
         return 1;
     }
     h->have_target = true;
-    // a map-sized cloud's covariances are searched on ONE level whose cell is sized for the 20-neighbour radius (vgicp_prepare_target)
     const int levels = cov_levels(n_dst);
     const GridIndex* cov_grid = &h->grid;
     h->cov_scale_hint = 0.0;
-    if (levels == 1 && n_dst > 0 && grid_sum_sq(h->vg.cov_hdr0) > 0.0) {
-        const double occ = grid_sum_sq(h->vg.cov_hdr0) / (double)n_dst;
-        const double scale = std::min(8.0, sqrt(10.0 / std::max(occ, 1e-3)));
-        if (scale >= 1.3) {
-            if (settle_grid(h, h->cov_l1, d_dst, n_dst, stride_floats, res * scale, 0, nullptr)) return fail(h, "gicp: preparing the target: " + h->err);
-            h->cov_scale_hint = scale;
-            cov_grid = &h->cov_l1;
-        }
+    if (const double scale = cov_search_scale(h->vg.cov_hdr0, n_dst); scale > 0.0) {      // (a map-sized cloud: one level, of a cell of its own)
+        if (settle_grid(h, h->cov_l1, d_dst, n_dst, stride_floats, res * scale, 0, nullptr)) return fail(h, "gicp: preparing the target: " + h->err);
+        h->cov_scale_hint = scale;
+        cov_grid = &h->cov_l1;
     }
     H_TRY(vgicp_launch_cov(*cov_grid, levels > 1 ? &h->cov_l1 : nullptr, levels > 2 ? &h->vg.cov_l2 : nullptr, d_dst, stride_floats, n_dst,
                            h->gi.tgt_cov6.as<double>(), h->stream, nullptr, nullptr, &h->vg.tgt_scratch));
@@ -111,67 +106,20 @@ namespace pcr {
 namespace host {
 
 int run_gicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) {
-    h->fit_pending = false;
-    const bool fit_side = h->fit_copied_from == d_src && d_src != nullptr;      // (the side stream copied this very scan)
-    h->fit_copied_from = nullptr;
+    const bool kept = fitness_scan_kept(h, d_src);
     if (gicp_setup(h, d_src, n_src, stride_floats)) return 1;
-    if (n_src > 0 && !fit_side) {      // the scan, kept for a later pcr_fitness()
-        H_TRY(h->fit_src.reserve(n_src * stride_floats * sizeof(float)));
-        H_TRY(hipMemcpyAsync(h->fit_src.p, d_src, n_src * stride_floats * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    }
+    if (keep_scan_for_fitness(h, d_src, n_src, stride_floats, kept)) return 1;
     const GicpArgs a = gicp_args(h, d_src, n_src, stride_floats);
-    Pose16 x0;
-    for (int i = 0; i < 16; ++i) x0.m[i] = (double)(float)pose[i];     // guess handed over as Matrix4f (VgicpRegister.cpp:36)
-    bool conv = false;
-    int outer = 0, n_lin = 0, n_err = 0;
-    // ---- device-resident loop (vgicp_opt.h): launches are enqueued ahead of the device, the host watches a progress word ----
     const bool on_device = n_src > 0 && h->prm.host_optimiser == 0 && h->prm.vgicp_max_iters > 0;
-    if (on_device) {
-        H_TRY(h->gi.out.ensure());
-        H_TRY(h->gi.ctl.reserve(2 * sizeof(VgCtl)));
-        VgCtl* d_ctl = h->gi.ctl.as<VgCtl>();
-        VgOut* out = h->gi.out.host;
-        h->seq += 1.0;
-        const double seq = h->seq;
-        H_TRY(vgicp_launch_ctl_init(d_ctl, x0, h->prm.vgicp_max_iters, h->prm.vgicp_lm_inner, h->prm.vgicp_lm_init_scale, h->prm.vgicp_rot_eps, h->prm.vgicp_trans_eps, h->stream));
-        // every outer iteration takes at most lm_inner passes, plus the first linearisation and the launch that finishes
-        const long limit = (long)h->prm.vgicp_max_iters * std::max(1, h->prm.vgicp_lm_inner) + 3;
-        auto launch = [&](long i) -> hipError_t { return gicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), h->gi.out.dev, h->stream, seq, (int)i); };
-        static constexpr PaceRule kRule{4, 3, 4, false};      // (run_vgicp's)
-        if (pace_passes(h, out, seq, limit, kRule, "vgicp_max_iters * vgicp_lm_inner exceeds the device loop's pass window (2^20)",
-                        "gicp: the optimiser did not finish within its pass budget", launch))
-            return 1;
-        x0 = out->x0; conv = out->conv != 0;
-        outer = out->outer; n_lin = out->n_lin; n_err = out->n_err;
-        h->stats.attempts = out->passes;
-    } else {
-        // ---- host-driven loop: the same state machine, one host round trip per pass ----
-        VgCtl c;
-        memset(&c, 0, sizeof c);
-        vg_opt::ctl_init(&c, x0, h->prm.vgicp_max_iters, h->prm.vgicp_lm_inner, h->prm.vgicp_lm_init_scale, h->prm.vgicp_rot_eps, h->prm.vgicp_trans_eps);
-        while (!c.done) {
-            GicpArgs ap = a;
-            if (c.parity) { ap.corr = a.corr_next; ap.corr_M = a.corr_M_next; ap.corr_next = a.corr; ap.corr_M_next = a.corr_M; }
-            h->seq += 1.0;
-            if (c.kind == kVgPassLinearize) H_TRY(gicp_launch_linearize(ap, c.xi, h->out32.dev, h->stream, h->seq));
-            else H_TRY(gicp_launch_error(ap, c.xi, h->out32.dev, h->stream, h->seq));
-            if (wait_result(h, &h->out32.host[31], h->seq)) return 1;
-            double sums[29];
-            for (int k = 0; k < 29; ++k) sums[k] = h->out32.host[k];
-            vg_opt::ctl_step(&c, sums);
-        }
-        x0 = c.x0; conv = c.conv != 0;
-        outer = c.outer; n_lin = c.n_lin; n_err = c.n_err;
-        h->stats.attempts = c.passes;
-    }
-    for (int i = 0; i < 16; ++i) pose[i] = (double)(float)x0.m[i];     // final_transformation_ is a Matrix4f
-    if (converged) *converged = conv ? 1 : 0;
-    h->stats.iterations = outer; h->stats.n_src = (int64_t)n_src; h->stats.n_dst = (int64_t)h->tgt_n;
-    h->stats.kernel_launches = n_lin + n_err;
-    // pcl::Registration::getFitnessScore() is evaluated when asked for (pcr_fitness), as after a VGICP alignment
-    for (int i = 0; i < 16; ++i) h->fit_pose[i] = pose[i];
-    h->fit_n = n_src; h->fit_stride = stride_floats; h->fit_pending = true;
-    h->fitness = DBL_MAX;
+    auto device_pass = [&](long i, VgCtl* d_ctl, VgOut* d_out, double seq) { return gicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), d_out, h->stream, seq, (int)i); };
+    auto host_pass = [&](int kind, int parity, const Pose16& xi, double seq) {
+        return (kind == kVgPassLinearize ? gicp_launch_linearize : gicp_launch_error)(swapped(a, parity), xi, h->out32.dev, h->stream, seq);
+    };
+    LsqResult r;
+    if (run_lsq(h, pose, on_device, kLsqPace, "gicp: the optimiser did not finish within its pass budget", device_pass, host_pass, &r)) return 1;
+    lsq_report(h, r, n_src, pose, converged);
+    h->stats.attempts = r.passes;
+    arm_fitness(h, pose, n_src, stride_floats);
     return 0;
 }
 
@@ -205,10 +153,7 @@ int pcr_gicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t stri
         if (mahal6) H_TRY(hipMemcpyAsync(mahal6, a.corr_M, n_src * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
     H_TRY(hipStreamSynchronize(h->stream));
-    int q = 0;
-    for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { H[r * 6 + c] = H[c * 6 + r] = h->out32.host[q++]; }
-    for (int r = 0; r < 6; ++r) b[r] = h->out32.host[21 + r];
-    if (error) *error = h->out32.host[27];
+    unpack_lsq_sums(h->out32.host, H, b, error);
     int64_t nc = 0;
     for (size_t i = 0; i < n_src; ++i) {
         const bool has = cr[i] != 0xffffffffu;

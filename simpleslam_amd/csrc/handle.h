@@ -1,6 +1,6 @@
 // handle.h -- struct pcr_handle and what the host units of the C ABI share (host code only; no kernel includes this).
 // The units: capi.hip (handle, scan2map / set_target / align, getters and setters), staging_host.hip, comm_host.hip,
-// loam_host.hip, vgicp_host.hip, gicp_host.hip, ndt_host.hip, voxel_host.hip, query_host.hip.
+// loam_host.hip, vgicp_host.hip, gicp_host.hip (the two share lsq_host.h), ndt_host.hip, voxel_host.hip, query_host.hip.
 // A nested struct of the handle belongs to the unit it is named after: that unit sets it up and writes it (pcr_destroy and
 // pcr_invalidate_target reach into all of them); where another unit looks into one, the member's comment says so.  What
 // several units share stays at the top level, with its users named.
@@ -98,6 +98,8 @@ struct pcr_handle {
     pcr::GridIndex cov_l1;           // the TARGET cloud while its covariances are computed, indexed at 4x the cell (vgicp; query: the grid of every point a score runs on)
     double cov_scale_hint = 0.0;     // cell scale of the last map-sized target's covariance grid: built ahead of the density it is derived from (vgicp, query)
     pcr::DeviceBuf vg_partials;      // rows of a pass's sums: vgicp, the fitness scores of vgicp and query; sized by staging (ensure_out32)
+    pcr::DeviceBuf lsq_ctl;              // two VgCtl: the state of the device-resident LM loop of vgicp or gicp (lsq_host.h: run_lsq), by launch parity
+    pcr::host::Mapped<pcr::VgOut> lsq_out;   // its result and progress word
     double seq = 0.0;                    // completion numbers of the host-mapped result blocks below (vgicp, ndt, query)
     pcr::host::Mapped<double> out32;     // 32 doubles written by sum_partials_kernel (staging: ensure_out32; vgicp, query)
     // getFitnessScore() is a call of its own in the reference (VgicpRegister.cpp:42-45: PCL evaluates it when asked, from the source it
@@ -121,9 +123,6 @@ struct pcr_handle {
         pcr::DeviceBuf tgt_cov6, src_cov6, vox, corr_slot, corr_M, corr_slot2, corr_M2;
         pcr::CovScratch src_scratch, tgt_scratch;   // neighbour lists + queue of the covariance search of a scan-sized cloud: the source's runs on the side stream beside the target's
         bool target_ready = false;       // (read by pcr_scan2map_submap; dropped by pcr_set_params, pcr_set_shard, pcr_invalidate_target)
-        int outer = 0, lin = 0, err = 0;
-        pcr::DeviceBuf ctl;                  // two VgCtl: the device-resident LM loop's state, by launch parity
-        pcr::host::Mapped<pcr::VgOut> out;   // its result and progress word
         pcr::DeviceBuf reduced;              // sharded VGICP over the peer exchange: a pass's 32 sums folded over the rows and the ranks
         pcr::DeviceBuf cov_viol;         // VGICP halo check: number of neighbourhoods that reach past the halo
     } vg;
@@ -134,8 +133,6 @@ struct pcr_handle {
         pcr::DeviceBuf tgt_cov6;             // per target point, original order
         pcr::DeviceBuf corr[2], M[2];        // the two correspondence buffers (original target index / Mahalanobis matrix per source point), chosen by the state's parity
         pcr::DeviceBuf d2;                   // pcr_gicp_linearize: the correspondences' float distances
-        pcr::DeviceBuf ctl;                  // two VgCtl: the device-resident LM loop's state, by launch parity
-        pcr::host::Mapped<pcr::VgOut> out;   // its result and progress word
         bool target_ready = false;           // (read by pcr_scan2map_submap and query; dropped by pcr_set_params, pcr_invalidate_target)
     } gi;
 
@@ -326,7 +323,7 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
 // ---- query_host.hip ----
 std::string cut_fitness_message(double n);
 
-// How a device-resident optimiser's passes (run_vgicp, run_ndt) are queued ahead of the progress word of its result block
+// How a device-resident optimiser's passes (run_lsq, run_ndt) are queued ahead of the progress word of its result block
 struct PaceRule {
     long first;       // passes queued before the first look
     long ahead;       // passes kept queued beyond those the device has consumed

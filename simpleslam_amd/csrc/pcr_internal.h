@@ -312,6 +312,11 @@ struct VgicpArgs {
     int32_t guard_cells, pad2_;  //   guard_cells voxels of a face with target points beyond it (their voxels' covariances may lack neighbours); else NULL
     RoiView roi;                 // mask == nullptr: the whole target is prepared
 };
+// the arguments of a pass whose state has `parity` set: the two pairs of correspondence buffers change places (VgCtl::parity)
+__host__ __device__ inline VgicpArgs swapped(VgicpArgs a, int parity) {
+    if (parity) { uint32_t* const s = a.corr_slot; a.corr_slot = a.corr_slot_next; a.corr_slot_next = s; double* const m = a.corr_M; a.corr_M = a.corr_M_next; a.corr_M_next = m; }
+    return a;
+}
 
 // Halo check of a sharded target (pcr_set_shard): for every point inside [chk_lo, chk_hi) the 20th neighbour must be nearer
 // than the faces of [ext_lo, ext_hi) -- the region the rank's cloud is complete in; *violations counts the others.
@@ -375,6 +380,10 @@ struct GicpArgs {
     float thr2, pad2_;           // the gate: a correspondence needs d2 < thr2 (float; +inf by default)
     float* d2_out;               // introspection (pcr_gicp_linearize): [n_src] float squared distance of the correspondence, +inf for none; else NULL
 };
+__host__ __device__ inline GicpArgs swapped(GicpArgs a, int parity) {      // (as VgicpArgs')
+    if (parity) { uint32_t* const s = a.corr; a.corr = a.corr_next; a.corr_next = s; double* const m = a.corr_M; a.corr_M = a.corr_M_next; a.corr_M_next = m; }
+    return a;
+}
 hipError_t gicp_launch_linearize(const GicpArgs& a, const Pose16& T, double* d_out32, hipStream_t s, double seq = 0.0);
 // out32[28] = compute_error(T) on a.corr / a.corr_M; out32[0..27] = the linearisation at T (correspondences into a.corr_*next)
 hipError_t gicp_launch_error(const GicpArgs& a, const Pose16& T, double* d_out32, hipStream_t s, double seq = 0.0);

@@ -10,7 +10,7 @@
 //   V4/V5 correspondences, Mahalanobis, linearize, compute_error   fast_vgicp_impl.hpp:73-204
 //      -> vgicp_linearize_kernel<false> (linearize) and <true> (compute_error of an LM trial pose + the linearisation at
 //         that pose in the same pass), fixed-order reductions
-//   V6 LM driver                  lsq_registration_impl.hpp:53-171 -> host code in capi.hip
+//   V6 LM driver                  lsq_registration_impl.hpp:53-171 -> lsq_pass.h (the pass and the device loop's prologue), lsq_host.h: run_lsq
 // Also the PCL fitness score (pcl::Registration::getFitnessScore, VgicpRegister.cpp:42-45).
 #include <float.h>
 #include <math.h>
@@ -20,6 +20,7 @@
 #include "peer_exchange.h"
 #include "small_math.h"
 #include "vgicp_opt.h"
+#include "lsq_pass.h"
 #include "cov_math.h"
 #include "ring_search.h"
 
@@ -210,8 +211,6 @@ __device__ __forceinline__ uint32_t vgicp_lookup(const GridHeader& h, const uint
     return e > s ? s + 1 : 0;
 }
 
-static constexpr int kLinStride = 258;
-
 // one source point of update_correspondences + linearize at pose T: v[0..20] H (upper triangle), v[21..26] b, v[27] error;
 // the correspondence (voxel slot, Mahalanobis matrix) goes to slot_out / M_out
 __device__ __forceinline__ void vgicp_lin_point(const VgicpArgs& a, const GridHeader& h, const Pose16& T, uint32_t i, double v[28],
@@ -295,170 +294,36 @@ __device__ __forceinline__ double vgicp_err_point(const VgicpArgs& a, const Pose
     return vx.w * (er[0] * Me0 + er[1] * Me1 + er[2] * Me2);
 }
 
-// kWithError = false: linearize(T) -- correspondences to a.corr_slot / a.corr_M, partial sums [0..27].
-// kWithError = true: one pass for an LM trial pose T: [28] = compute_error(T) on the correspondences of the last linearisation
-// (a.corr_slot / a.corr_M, read only) AND, speculatively, the linearisation AT T (correspondences to a.corr_slot_next /
-// a.corr_M_next, sums [0..27]).  When the trial is accepted -- the usual case -- T is the next linearisation point and the
-// host swaps the buffers instead of paying another launch and round trip; when it is rejected the sums are dropped.
-// Both sums go through the same fixed-order block reduction as a stand-alone linearisation: bit-identical values.
-template <bool kWithError>
-__device__ __forceinline__ void vgicp_lin_body(const VgicpArgs& a, const Pose16& T, double* sh /* [29][kLinStride] */, double* sh_sum /* [8][32] */) {
-    constexpr int kRows = kWithError ? 29 : 28;
-    const GridHeader h = *a.hdr;
-    const int tid = threadIdx.x, e = tid & 31, ch = tid >> 5;
-    double acc = 0.0;
-    for (uint32_t base = blockIdx.x * 256; base < a.n_src; base += gridDim.x * 256) {
-        const uint32_t i = base + tid;
-        double v[28];
-#pragma unroll
-        for (int k = 0; k < 28; ++k) v[k] = 0.0;
-        double err = 0.0;
-        if (i < a.n_src) {
-            if (kWithError) {
-                err = vgicp_err_point(a, T, i);
-                vgicp_lin_point(a, h, T, i, v, a.corr_slot_next, a.corr_M_next);
-            } else {
-                vgicp_lin_point(a, h, T, i, v, a.corr_slot, a.corr_M);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 28; ++k) sh[k * kLinStride + tid] = v[k];
-        if (kWithError) sh[28 * kLinStride + tid] = err;
-        __syncthreads();
-        if (e < kRows) {
-            const double* row = sh + e * kLinStride + ch * 32;
-#pragma unroll 8
-            for (int k = 0; k < 32; ++k) acc += row[k];
-        }
-        __syncthreads();
+// The pass of lsq_pass.h over VGICP's voxel correspondences: the launch's arguments and the target index header, loaded once
+struct VgicpPass {
+    const VgicpArgs& a;
+    const GridHeader h;
+    __device__ __forceinline__ explicit VgicpPass(const VgicpArgs& a_) : a(a_), h(*a_.hdr) {}
+    __device__ __forceinline__ void lin(const Pose16& T, uint32_t i, double v[28], bool to_next) const {
+        vgicp_lin_point(a, h, T, i, v, to_next ? a.corr_slot_next : a.corr_slot, to_next ? a.corr_M_next : a.corr_M);
     }
-    sh_sum[ch * 32 + e] = e < kRows ? acc : 0.0;
-    __syncthreads();
-    if (tid < 32) {
-        double s = sh_sum[tid];
-#pragma unroll
-        for (int c = 1; c < 8; ++c) s += sh_sum[c * 32 + tid];
-        a.partials[(size_t)blockIdx.x * 32 + tid] = s;
-    }
-}
+    __device__ __forceinline__ double err(const Pose16& T, uint32_t i) const { return vgicp_err_point(a, T, i); }
+};
 
 template <bool kWithError>
 __global__ __launch_bounds__(256) void vgicp_linearize_kernel(const VgicpArgs a, const Pose16 T) {
     __shared__ double sh[(kWithError ? 29 : 28) * kLinStride];
     __shared__ double sh_sum[8 * 32];
-    vgicp_lin_body<kWithError>(a, T, sh, sh_sum);
+    lsq_lin_body<kWithError>(VgicpPass(a), T, a.n_src, a.partials, sh, sh_sum);
 }
 
-// ------------------------------------------------------------------------------
-// Device-resident Levenberg-Marquardt loop (unsharded targets): one launch per pass.  The prologue of a launch folds the 29 sums
-// of the previous one and takes the optimiser's step (vgicp_opt.h: vg_ctl_step) -- in every block, the same instructions on the
-// same numbers, as ndt_pass_pro_kernel and loam_iterate_kernel do; block 0 writes the new state and the progress word.  State and
-// rows are double-buffered by launch parity; the two correspondence buffers are chosen by the state's own parity (an accepted
-// trial makes the buffer it wrote the current one).  The loop ends in the prologue of the launch after its last pass.
-// ------------------------------------------------------------------------------
-struct VgProArgs {
-    const double* rows_prev;     // [rows_prev_n][32]
-    const VgCtl* ctl_prev;
-    VgCtl* ctl_next;
-    VgOut* out;
-    double seq;
-    uint32_t rows_prev_n;
-    int32_t first;
-    const double* reduced;       // sharded over the peer exchange: the previous launch's 32 sums, already folded over the rows AND the ranks (vgicp_peer_exchange_kernel)
-};
-static constexpr int kVgCtlWords = (int)((sizeof(VgCtl) + 3) / 4);
-static_assert(sizeof(VgCtl) % 4 == 0, "VgCtl is copied word by word");
-
-__global__ __launch_bounds__(256) void vgicp_pass_pro_kernel(const VgicpArgs a_in, const VgProArgs pa) {
+// a launch of the device-resident Levenberg-Marquardt loop (lsq_pass.h); roi: a target prepared for one scan reports its escapes with the result
+__global__ __launch_bounds__(256) void vgicp_pass_pro_kernel(const VgicpArgs a, const LsqProArgs pa) {
     __shared__ double sh[29 * kLinStride];
     __shared__ double sh_sum[8 * 32];
     __shared__ __attribute__((aligned(16))) uint32_t sh_ctl[kVgCtlWords];
     __shared__ double sh_sums[32];
-    const int t = threadIdx.x;
-    VgCtl* const c = reinterpret_cast<VgCtl*>(sh_ctl);
-    // one round trip: the state and the rows of the previous launch ([8 slices][32 components], 32 rows a thread for <= 256 rows)
-    const int comp = t & 31, slice = t >> 5;
-    double acc = 0.0;
-    if (pa.reduced) {      // (block-uniform) the sums arrive folded: slice 0 carries them, the others zeros
-        if (!pa.first && slice == 0) acc = pa.reduced[comp];
-        for (int w = t; w < kVgCtlWords; w += 256) sh_ctl[w] = reinterpret_cast<const uint32_t*>(pa.ctl_prev)[w];
-    } else {
-        double v[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) {
-            const uint32_t row = (uint32_t)(slice + 8 * u);
-            v[u] = (!pa.first && row < pa.rows_prev_n) ? pa.rows_prev[(size_t)row * 32 + comp] : 0.0;
-        }
-        for (int w = t; w < kVgCtlWords; w += 256) sh_ctl[w] = reinterpret_cast<const uint32_t*>(pa.ctl_prev)[w];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) acc += v[u];
-    }
-    if (!pa.first && !pa.reduced)
-        for (uint32_t r0 = 256; r0 < pa.rows_prev_n; r0 += 256) {      // (more than 65 536 source points: 512 rows)
-            double v[32];
-#pragma unroll
-            for (int u = 0; u < 32; ++u) {
-                const uint32_t row = r0 + (uint32_t)(slice + 8 * u);
-                v[u] = row < pa.rows_prev_n ? pa.rows_prev[(size_t)row * 32 + comp] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 32; ++u) acc += v[u];
-        }
-    sh_sum[slice * 32 + comp] = acc;
-    __syncthreads();
-    if (c->done) {      // finished in an earlier launch: hand the state on to whatever is queued behind
-        if (blockIdx.x == 0) for (int w = t; w < kVgCtlWords; w += 256) reinterpret_cast<uint32_t*>(pa.ctl_next)[w] = sh_ctl[w];
-        return;
-    }
-    if (!pa.first) {
-        if (t < 32) {
-            double s = sh_sum[t];
-#pragma unroll
-            for (int k = 1; k < 8; ++k) s += sh_sum[k * 32 + t];
-            sh_sums[t] = s;
-        }
-        __syncthreads();
-        if (t == 0) vg_opt::ctl_step(c, sh_sums);
-        __syncthreads();
-        if (blockIdx.x == 0) {
-            for (int w = t; w < kVgCtlWords; w += 256) reinterpret_cast<uint32_t*>(pa.ctl_next)[w] = sh_ctl[w];
-            if (t == 0) {
-                VgOut* const out = pa.out;
-                if (c->done) {
-                    out->x0 = c->x0;
-                    out->conv = c->conv; out->outer = c->outer; out->n_lin = c->n_lin; out->n_err = c->n_err; out->passes = c->passes;
-                    // (every pass ran in an earlier launch of this stream: the count is final)
-                    out->roi_escapes = a_in.roi.mask ? (int32_t)min(*a_in.roi.escapes, 0x7fffffffu) : 0;
-                    __threadfence_system();
-                    __hip_atomic_store(&out->seq, pa.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                } else {
-                    __hip_atomic_store(&out->progress, pa.seq * kProgressWindow + (double)c->passes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-            }
-        }
-        if (c->done) return;
-    }
-    // the pose of this pass and the correspondence buffers, as scalars
-    Pose16 T;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const double v = c->xi.m[i];
-        T.m[i] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-    }
-    const int kind = __builtin_amdgcn_readfirstlane(c->kind), parity = __builtin_amdgcn_readfirstlane(c->parity);
-    VgicpArgs a = a_in;
-    if (parity) {
-        a.corr_slot = a_in.corr_slot_next; a.corr_M = a_in.corr_M_next;
-        a.corr_slot_next = a_in.corr_slot; a.corr_M_next = a_in.corr_M;
-    }
-    __syncthreads();      // (sh_sum is reused by the body)
-    if (kind == kVgPassLinearize) vgicp_lin_body<false>(a, T, sh, sh_sum);
-    else vgicp_lin_body<true>(a, T, sh, sh_sum);
+    lsq_pass<true, VgicpPass>(a, pa, a.roi.mask ? a.roi.escapes : nullptr, sh, sh_sum, sh_ctl, sh_sums);
 }
 
 // Sharded targets over the peer exchange (pcr_comm_init_peer): between two passes ONE launch folds this rank's rows of the pass that has just run --
 // the order of vgicp_pass_pro_kernel's own fold -- pushes the 32 sums into every peer's receive buffer and folds what arrived in rank order
-// (peer_exchange.h); the next pass's prologue takes the result (VgProArgs::reduced) and the optimiser's step as ever, in every block, on every rank,
+// (peer_exchange.h); the next pass's prologue takes the result (LsqProArgs::reduced) and the optimiser's step as ever, in every block, on every rank,
 // on the same bits.  Two launches per pass and no host round trip, where the host-driven loop of a sharded target has one per pass.  Once the loop
 // has finished (the state the pass before left says so, on every rank in the same launch) nothing is exchanged.
 __global__ __launch_bounds__(256) void vgicp_peer_exchange_kernel(const double* __restrict__ rows, uint32_t n_rows, const VgCtl* __restrict__ ctl, const PeerComm pc,
@@ -466,18 +331,7 @@ __global__ __launch_bounds__(256) void vgicp_peer_exchange_kernel(const double* 
     __shared__ double sh_sum[8 * 32];
     const int t = threadIdx.x, comp = t & 31, slice = t >> 5;
     if (ctl->done) return;
-    double acc = 0.0;
-    for (uint32_t r0 = 0; r0 < n_rows; r0 += 256) {
-        double v[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) {
-            const uint32_t row = r0 + (uint32_t)(slice + 8 * u);
-            v[u] = row < n_rows ? rows[(size_t)row * 32 + comp] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 32; ++u) acc += v[u];
-    }
-    sh_sum[slice * 32 + comp] = acc;
+    sh_sum[slice * 32 + comp] = lsq_fold_rows<false>(rows, n_rows, 0, nullptr, nullptr);
     __syncthreads();
     double mine = 0.0;
     if (t < 32) {
@@ -619,7 +473,7 @@ hipError_t vgicp_launch_cov(const GridIndex& grid, const GridIndex* coarse1, con
         cov_blocks = std::min(blocks, 1024);      // (four blocks per CU resident at once; the kernel strides over the list)
     }
 #define PCR_COV_ARGS grid.view(), coarse1 ? coarse1->view() : grid.view(), coarse2 ? coarse2->view() : grid.view(), levels, d_orig, (uint32_t)stride_floats, (uint32_t)n, d_cov6, check ? 1 : 0, chk, rv, d_list, d_list_count
-    if (n <= 300000) {      // scan-sized (the same threshold as the choice of search levels, capi.hip: cov_levels)
+    if (n <= 300000) {      // scan-sized (the same threshold as the choice of search levels, vgicp_host.hip: cov_levels)
         if (ev) hipExtLaunchKernelGGL(vgicp_cov_kernel<true>, dim3(blocks), dim3(256), 0, s, ev[0], ev[1], 0, PCR_COV_ARGS);
         else hipLaunchKernelGGL(vgicp_cov_kernel<true>, dim3(blocks), dim3(256), 0, s, PCR_COV_ARGS);
     } else {
@@ -648,8 +502,7 @@ uint32_t vgicp_blocks(uint32_t n_src) {
 hipError_t vgicp_launch_linearize(const VgicpArgs& a, const Pose16& T, double* d_out32, hipStream_t s, double seq) {
     const uint32_t nb = vgicp_blocks(a.n_src);
     hipLaunchKernelGGL(vgicp_linearize_kernel<false>, dim3(nb), dim3(256), 0, s, a, T);
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, a.partials, nb, d_out32, seq);
-    return hipGetLastError();
+    return sum_partials_launch(a.partials, nb, d_out32, s, seq);
 }
 
 hipError_t vgicp_launch_ctl_init(VgCtl* d_ctl2, const Pose16& guess, int max_iters, int lm_inner, double lm_init_scale, double rot_eps, double trans_eps, hipStream_t s,
@@ -662,18 +515,14 @@ hipError_t vgicp_launch_ctl_init(VgCtl* d_ctl2, const Pose16& guess, int max_ite
     hipLaunchKernelGGL(vgicp_ctl_store_kernel, dim3(1), dim3(256), 0, s, d_ctl2, arg, d_roi_escapes);
     return hipGetLastError();
 }
-// launch `index` of the device-resident loop: d_ctl2 = two VgCtl, d_rows2 = two buffers of 512 * 32 doubles
+// launch `index` of the device-resident loop (lsq_pass.h: lsq_pro_args)
 // pc / xseq / d_reduced (sharded over the peer exchange, launches after the first): the exchange launch in front of the pass
 hipError_t vgicp_launch_pass_pro(const VgicpArgs& a_in, VgCtl* d_ctl2, double* d_rows2, VgOut* d_out, hipStream_t s, double seq, int index,
                                  const PeerComm* pc, double xseq, double* d_reduced) {
     const uint32_t nb = vgicp_blocks(a_in.n_src);
     VgicpArgs a = a_in;
-    a.partials = d_rows2 + (size_t)(index & 1) * 512 * 32;
-    VgProArgs pa;
-    pa.rows_prev = d_rows2 + (size_t)((index + 1) & 1) * 512 * 32;
-    pa.ctl_prev = index == 0 ? d_ctl2 : d_ctl2 + ((index + 1) & 1);
-    pa.ctl_next = d_ctl2 + (index & 1);
-    pa.out = d_out; pa.seq = seq; pa.rows_prev_n = nb; pa.first = index == 0 ? 1 : 0;
+    a.partials = lsq_rows(d_rows2, index);
+    LsqProArgs pa = lsq_pro_args(d_ctl2, d_rows2, d_out, seq, index, nb);
     pa.reduced = pc ? d_reduced : nullptr;
     if (pc && index > 0) hipLaunchKernelGGL(vgicp_peer_exchange_kernel, dim3(1), dim3(256), 0, s, pa.rows_prev, nb, pa.ctl_prev, *pc, xseq, d_reduced);
     hipLaunchKernelGGL(vgicp_pass_pro_kernel, dim3(nb), dim3(256), 0, s, a, pa);
@@ -683,11 +532,10 @@ hipError_t vgicp_launch_pass_pro(const VgicpArgs& a_in, VgCtl* d_ctl2, double* d
 hipError_t vgicp_launch_error(const VgicpArgs& a, const Pose16& T, double* d_out32, hipStream_t s, double seq) {
     const uint32_t nb = vgicp_blocks(a.n_src);
     hipLaunchKernelGGL(vgicp_linearize_kernel<true>, dim3(nb), dim3(256), 0, s, a, T);
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, a.partials, nb, d_out32, seq);
-    return hipGetLastError();
+    return sum_partials_launch(a.partials, nb, d_out32, s, seq);
 }
 
-// (for the units whose passes leave their rows in the same [block][32] layout: gicp.hip)
+// (every pass and score that leaves its rows in the [block][32] layout: here and gicp.hip)
 hipError_t sum_partials_launch(const double* d_partials, uint32_t nblocks, double* d_out32, hipStream_t s, double seq) {
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, d_partials, nblocks, d_out32, seq);
     return hipGetLastError();
@@ -706,8 +554,7 @@ hipError_t fitness_launch(const GridIndex& grid, const float* d_src, size_t n_sr
     memset(&ft, 0, sizeof ft);
     if (tile) ft = *tile;
     hipLaunchKernelGGL(fitness_kernel, dim3(nb), dim3(256), 0, s, grid.view(), d_src, (uint32_t)n_src, (uint32_t)stride_floats, T, mr, d_partials, ft);
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, d_partials, nb, d_out32, seq);
-    return hipGetLastError();
+    return sum_partials_launch(d_partials, nb, d_out32, s, seq);
 }
 
 }  // namespace pcr

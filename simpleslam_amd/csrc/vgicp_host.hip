@@ -1,10 +1,11 @@
-// vgicp_host.hip -- VGICP host driver: PCL align() + LsqRegistration (lsq_registration_impl.hpp:53-171)
+// vgicp_host.hip -- VGICP's host side: what is its own around PCL align() + LsqRegistration (lsq_registration_impl.hpp:53-171; the
+// driver is lsq_host.h's run_lsq, GICP's too) -- a cut index's escapes, a region's repeat, the peer loop, the sharded fitness score --
 // with the index levels of its covariance searches, the scan's side on its own stream, the region a target is prepared for
 // (roi_enqueue: NDT uses it too), pcr_fitness and the pcr_vgicp_* entry points.
 
 #include <algorithm>
 
-#include "handle.h"
+#include "lsq_host.h"
 
 using namespace pcr;
 using namespace pcr::host;
@@ -385,29 +386,22 @@ int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t
     if (settle_cov_levels(h, h->grid, h->cov_l1, h->vg.cov_l2, d_dst, n_dst, stride_floats, res, opt)) return 1;
     if (h->clamp.use) { ahead_ok = false; early_clean = false; }      // (the target was cut to its bulk in there: the grid built ahead covers the uncut cloud)
     h->have_target = true;
-    // A map-sized cloud is searched on ONE level whose cell is sized for the 20-neighbour radius, not for the voxel
-    // lattice: sum_sq / n is the occupancy of the cell a point lives in (averaged over the points); on a surface it grows
-    // with cell^2, and ~10 points per cell put ~4 K candidates into the 27-cell block (measured optimum).  (0.5 m voxels over a 0.5 m-spaced
-    // map: cell 1.25 m, 0.74 -> 0.50 ms for 1 M points, the extra index build included.)
+    // (a map-sized cloud is searched on ONE level of a cell of its own: cov_search_scale)
     const GridIndex* cov_grid = &h->grid;
     bool kept_ahead = false;
     if (bf.applied) {      // (the density figure of a region-only lattice is the region's: the search cell of the previous call stays -- it decides how many candidates a search visits, never its result)
         if (!ahead_ok && settle_grid(h, h->cov_l1, d_dst, n_dst, stride_floats, res * h->cov_scale_hint, 0, nullptr)) return 1;      // (the grid built ahead did not stand: built again, in full)
         kept_ahead = ahead_ok; cov_grid = &h->cov_l1;
-    } else if (cov_levels(n_dst) == 1 && n_dst > 0 && grid_sum_sq(h->vg.cov_hdr0) > 0.0) {
-        const double occ = grid_sum_sq(h->vg.cov_hdr0) / (double)n_dst;
-        const double scale = std::min(8.0, sqrt(10.0 / std::max(occ, 1e-3)));
-        if (scale >= 1.3) {
-            // the grid built ahead serves if its cell is within 15 % of what this cloud's density asks for (the cell only decides how
-            // many candidates a search visits, never its result)
-            const bool keep = ahead_ok && fabs(h->cov_scale_hint / scale - 1.0) <= 0.15;
-            if (!keep) {
-                if (settle_grid(h, h->cov_l1, d_dst, n_dst, stride_floats, res * scale, 0, h->clamp.use ? &h->clamp : nullptr)) return 1;
-                h->cov_scale_hint = scale;
-            }
-            kept_ahead = keep;
-            cov_grid = &h->cov_l1;
-        } else h->cov_scale_hint = 0.0;
+    } else if (const double scale = cov_search_scale(h->vg.cov_hdr0, n_dst); scale > 0.0) {
+        // the grid built ahead serves if its cell is within 15 % of what this cloud's density asks for (the cell only decides how
+        // many candidates a search visits, never its result)
+        const bool keep = ahead_ok && fabs(h->cov_scale_hint / scale - 1.0) <= 0.15;
+        if (!keep) {
+            if (settle_grid(h, h->cov_l1, d_dst, n_dst, stride_floats, res * scale, 0, h->clamp.use ? &h->clamp : nullptr)) return 1;
+            h->cov_scale_hint = scale;
+        }
+        kept_ahead = keep;
+        cov_grid = &h->cov_l1;
     } else h->cov_scale_hint = 0.0;
     if (check) {
         // sharded target (pcr_set_shard): the covariances of the points that can enter a voxel of the tile must be the whole
@@ -456,16 +450,11 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
     if (!h->vg.target_ready) return fail(h, "no target prepared");
     if (n_src > kMaxPoints) return fail(h, "source cloud too large");
     if (ensure_out32(h)) return 1;
+    const bool kept = fitness_scan_kept(h, d_src);
     // source covariances over the source's own index (fast_gicp_impl.hpp:103-108): already in flight when this is a
     // scan2map call, computed here otherwise
-    h->fit_pending = false;
-    const bool fit_side = h->fit_copied_from == d_src && d_src != nullptr;      // (the side stream copied this very scan)
-    h->fit_copied_from = nullptr;
     if (vgicp_source_settle(h, d_src, n_src, stride_floats)) return 1;
-    if (!sharded(h) && n_src > 0 && !fit_side) {
-        H_TRY(h->fit_src.reserve(n_src * stride_floats * sizeof(float)));
-        H_TRY(hipMemcpyAsync(h->fit_src.p, d_src, n_src * stride_floats * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    }
+    if (keep_scan_for_fitness(h, d_src, n_src, stride_floats, kept)) return 1;
     H_TRY(h->vg.corr_slot.reserve((n_src + 1) * sizeof(uint32_t)));
     H_TRY(h->vg.corr_M.reserve((n_src + 1) * 6 * sizeof(double)));
     H_TRY(h->vg.corr_slot2.reserve((n_src + 1) * sizeof(uint32_t)));
@@ -480,12 +469,8 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
     }
     const bool shard = sharded(h);      // every rank linearises its tile's share of the scan; H, b and the error are summed over the ranks
 
-    Pose16 x0;
-    for (int i = 0; i < 16; ++i) x0.m[i] = (double)(float)pose[i];     // guess handed over as Matrix4f (VgicpRegister.cpp:36)
-    bool conv = false;
-    h->vg.outer = h->vg.lin = h->vg.err = 0;
-    // ---- device-resident loop (vgicp_opt.h): launches are enqueued ahead of the device, the host watches a progress word.  Not for
-    // sharded targets (every pass's sums cross the ranks) and not when pcr_params.host_optimiser asks for the host loop below ----
+    // ---- the device-resident loop of lsq_host.h's run_lsq.  Not for sharded targets (every pass's sums cross the ranks) and not when
+    // pcr_params.host_optimiser asks for the host loop ----
     // Sharded over the peer exchange (pcr_comm_init_peer) the loop stays on the device too: an exchange launch in front of every pass
     // (vgicp.hip: vgicp_peer_exchange_kernel), and the host queues launches by a rule that gives every rank the same number of them (PaceRule).
     const bool peer_loop = shard && h->comm.peer_on && !h->comm.host_ar && !h->comm.rccl;
@@ -493,60 +478,31 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
     if (h->roi_on && !on_device) return fail(h, "internal: a target prepared for one scan needs the device-resident loop");
     if (peer_loop && peer_check(h)) return 1;
     if (on_device) {
-        H_TRY(h->vg.out.ensure());
-        H_TRY(h->vg.ctl.reserve(2 * sizeof(VgCtl)));
         H_TRY(h->vg_partials.reserve((size_t)2 * 512 * 32 * sizeof(double)));
         a.partials = h->vg_partials.as<double>();
-        VgCtl* d_ctl = h->vg.ctl.as<VgCtl>();
-        VgOut* out = h->vg.out.host;
-        h->seq += 1.0;
-        const double seq = h->seq;
-        H_TRY(vgicp_launch_ctl_init(d_ctl, x0, h->prm.vgicp_max_iters, h->prm.vgicp_lm_inner, h->prm.vgicp_lm_init_scale, h->prm.vgicp_rot_eps, h->prm.vgicp_trans_eps, h->stream,
-                                    a.roi.escapes));      // (nullptr unless the target was prepared for one scan)
-        // every outer iteration takes at most lm_inner passes, plus the first linearisation and the launch that finishes
-        const long limit = (long)h->prm.vgicp_max_iters * std::max(1, h->prm.vgicp_lm_inner) + 3;
         if (peer_loop) H_TRY(h->vg.reduced.reserve(64 * sizeof(double)));
-        auto launch = [&](long i) -> hipError_t {
-            if (!peer_loop) return vgicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), h->vg.out.dev, h->stream, seq, (int)i);
-            if (i > 0) h->comm.peer_seq += 1.0;      // (the first launch of a call has nothing to exchange)
-            return vgicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), h->vg.out.dev, h->stream, seq, (int)i, &h->comm.peer, h->comm.peer_seq, h->vg.reduced.as<double>());
-        };
-        // (a pass is ~14 us, and the word that says one has begun is written ~6 us into it: with fewer than three launches ahead of
-        // that word the queue runs dry while the host enqueues; a launch beyond the end costs ~5 us)
-        static constexpr PaceRule kRule{4, 3, 4, false}, kPeerRule{0, 3, 0, true};
-        if (pace_passes(h, out, seq, limit, peer_loop ? kPeerRule : kRule, "vgicp_max_iters * vgicp_lm_inner exceeds the device loop's pass window (2^20)",
-                        "vgicp: the optimiser did not finish within its pass budget", launch))
-            return 1;
-        // some pass looked up a voxel outside the region the target was prepared for: its sums lack that correspondence.  The caller
-        // prepares the whole target and repeats the call (2).
-        if (h->roi_on && out->roi_escapes > 0) { h->roi_repeats += 1; return 2; }
-        x0 = out->x0; conv = out->conv != 0;
-        h->vg.outer = out->outer; h->vg.lin = out->n_lin; h->vg.err = out->n_err;
-        h->stats.attempts = out->passes;      // (the passes the device loop evaluated)
     }
-    // ---- host-driven loop: the same state machine (vgicp_opt.h), one host round trip per pass; sharded, every pass's sums cross
-    // the ranks.  The LM trial pass (vgicp_launch_error) also linearises at the trial pose: once a trial is accepted that pose IS the
-    // next linearisation point, so its H, b, error and correspondences are already there (same values as a separate linearize()
-    // would return) and the state's parity says which of the two correspondence buffers they are in ----
-    if (!on_device) {
-        VgCtl c;
-        memset(&c, 0, sizeof c);
-        vg_opt::ctl_init(&c, x0, h->prm.vgicp_max_iters, h->prm.vgicp_lm_inner, h->prm.vgicp_lm_init_scale, h->prm.vgicp_rot_eps, h->prm.vgicp_trans_eps);
-        while (!c.done) {
-            VgicpArgs ap = a;
-            if (c.parity) { ap.corr_slot = a.corr_slot_next; ap.corr_M = a.corr_M_next; ap.corr_slot_next = a.corr_slot; ap.corr_M_next = a.corr_M; }
-            h->seq += 1.0;
-            if (c.kind == kVgPassLinearize) H_TRY(vgicp_launch_linearize(ap, c.xi, h->out32.dev, h->stream, h->seq));
-            else H_TRY(vgicp_launch_error(ap, c.xi, h->out32.dev, h->stream, h->seq));
-            if (wait_result(h, &h->out32.host[31], h->seq)) return 1;
-            if (shard && ranks_allreduce(h, h->out32.host, 29)) return 1;
-            double sums[29];
-            for (int k = 0; k < 29; ++k) sums[k] = h->out32.host[k];
-            vg_opt::ctl_step(&c, sums);
-        }
-        x0 = c.x0; conv = c.conv != 0;
-        h->vg.outer = c.outer; h->vg.lin = c.n_lin; h->vg.err = c.n_err;
-    }
+    auto device_pass = [&](long i, VgCtl* d_ctl, VgOut* d_out, double seq) -> hipError_t {
+        if (!peer_loop) return vgicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), d_out, h->stream, seq, (int)i);
+        if (i > 0) h->comm.peer_seq += 1.0;      // (the first launch of a call has nothing to exchange)
+        return vgicp_launch_pass_pro(a, d_ctl, h->vg_partials.as<double>(), d_out, h->stream, seq, (int)i, &h->comm.peer, h->comm.peer_seq, h->vg.reduced.as<double>());
+    };
+    // ---- its host-driven loop; sharded, every pass's sums cross the ranks.  The LM trial pass (vgicp_launch_error) also linearises at the
+    // trial pose: once a trial is accepted that pose IS the next linearisation point, so its H, b, error and correspondences are already
+    // there (same values as a separate linearize() would return) and the state's parity says which of the two correspondence buffers
+    // they are in ----
+    auto host_pass = [&](int kind, int parity, const Pose16& xi, double seq) {
+        return (kind == kVgPassLinearize ? vgicp_launch_linearize : vgicp_launch_error)(swapped(a, parity), xi, h->out32.dev, h->stream, seq);
+    };
+    static constexpr PaceRule kPeerRule{0, 3, 0, true};
+    LsqResult r;
+    if (run_lsq(h, pose, on_device, peer_loop ? kPeerRule : kLsqPace, "vgicp: the optimiser did not finish within its pass budget", device_pass, host_pass, &r, shard,
+                a.roi.escapes /* nullptr unless the target was prepared for one scan */))
+        return 1;
+    // some pass looked up a voxel outside the region the target was prepared for: its sums lack that correspondence.  The caller
+    // prepares the whole target and repeats the call (2).
+    if (h->roi_on && r.roi_escapes > 0) { h->roi_repeats += 1; return 2; }
+    if (r.on_device) h->stats.attempts = r.passes;      // (the passes the device loop evaluated)
     uint32_t esc = 0;
     if (a.escapes) {
         H_TRY(hipMemcpyAsync(&esc, a.escapes, sizeof esc, hipMemcpyDeviceToHost, h->stream));
@@ -557,16 +513,8 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
         if (esc && !shard) { h->err = "the target is too spread out for the dense voxel tables (a stray point far from the map?) and was cut to its bulk, but the scan reaches "
                                       "the part that was left out"; return 3; }
     }
-    for (int i = 0; i < 16; ++i) pose[i] = (double)(float)x0.m[i];     // final_transformation_ is a Matrix4f
-    if (converged) *converged = conv ? 1 : 0;
-    h->stats.iterations = h->vg.outer; h->stats.n_src = (int64_t)n_src; h->stats.n_dst = (int64_t)h->tgt_n;
-    h->stats.kernel_launches = h->vg.lin + h->vg.err;
-    if (!shard) {      // pcl::Registration::getFitnessScore() is evaluated when asked for (pcr_fitness), as in the reference
-        for (int i = 0; i < 16; ++i) h->fit_pose[i] = pose[i];
-        h->fit_n = n_src; h->fit_stride = stride_floats; h->fit_pending = true;
-        h->fitness = DBL_MAX;
-        return 0;
-    }
+    lsq_report(h, r, n_src, pose, converged);
+    if (!shard) { arm_fitness(h, pose, n_src, stride_floats); return 0; }
     // sharded: every rank takes part in the sum, so the score is evaluated here, with the call (VgicpRegister.cpp:42-45)
     h->seq += 1.0;
     FitTile ft;
@@ -587,8 +535,6 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
     // sharded: a source point farther from every map point than its rank's halo has its nearest neighbour on another rank; the
     // score is then not the map's and is reported as unavailable (the pose is unaffected)
     if (h->use_tile && h->out32.host[2] > 0) h->fitness = -1.0;
-    h->stats.iterations = h->vg.outer; h->stats.n_src = (int64_t)n_src; h->stats.n_dst = (int64_t)h->tgt_n;
-    h->stats.kernel_launches = h->vg.lin + h->vg.err;
     return 0;
 }
 
@@ -732,10 +678,7 @@ int pcr_vgicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t str
     if (n_src) H_TRY(hipMemcpyAsync(slots.data(), h->vg.corr_slot.p, n_src * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     H_TRY(hipStreamSynchronize(h->stream));
     if (sharded(h) && ranks_allreduce(h, h->out32.host, 29)) return 1;
-    int q = 0;
-    for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { H[r * 6 + c] = H[c * 6 + r] = h->out32.host[q++]; }
-    for (int r = 0; r < 6; ++r) b[r] = h->out32.host[21 + r];
-    if (error) *error = h->out32.host[27];
+    unpack_lsq_sums(h->out32.host, H, b, error);
     if (n_corr) { int64_t c = 0; for (uint32_t v : slots) c += v != 0; *n_corr = c; }
     return 0;
 }

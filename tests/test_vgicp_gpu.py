@@ -156,6 +156,62 @@ def test_device_resident_optimiser_equals_the_host_driven_one(gpu, vg_world):
         assert dt <= 2e-6 and dr <= 2e-6, (cap, dt, dr)
 
 
+def _scan_of_twin_groups(scan, n, copies=22, jitter=1e-3):
+    """n points: every (n // copies)-th point of `scan` repeated `copies` times (the first few once more) with a deterministic jitter far
+    below the spacing of the scan.  The 20 nearest neighbours of a point are then its own twins, so a point has the same covariance
+    whether the cloud is given whole or cut between two groups.  Returns the cloud, the index of a cut in its middle and the points
+    that were repeated."""
+    groups = n // copies
+    base = scan[:: len(scan) // groups][:groups]
+    counts = np.full(groups, copies)
+    counts[: n - copies * groups] += 1
+    big = np.repeat(base, counts, axis=0)
+    big[:, :3] += np.random.default_rng(65).uniform(-jitter, jitter, (n, 3)).astype(np.float32)
+    return np.ascontiguousarray(big), int(counts[: groups // 2].sum()), base
+
+
+def test_more_than_65536_source_points(gpu, vg_world):
+    """65 536 + 300 source points are 258 blocks of 256: the prologue of the device loop (and the peer exchange) folds a full first round
+    of 256 rows and a second round of two.  The device loop decides as the host-driven one (the bound of
+    test_device_resident_optimiser_equals_the_host_driven_one), one linearisation of the whole scan equals the sum of the linearisations
+    of its halves (another fold order: the bounds of test_golden_fixture, H's for b as well), and repeats bit for bit."""
+    from simpleslam_amd.pcr import default_params
+    w = vg_world
+    n = 65536 + 300
+    jitter = 1e-3
+    scan, cut, base = _scan_of_twin_groups(w["scan"], n, jitter=jitter)
+    assert scan.shape[0] == n and -(-n // 256) == 258
+    # (the premise, on the reference's search: twins are at most 2 r apart, r = sqrt(3) jitter, and points of two groups at least D - 2 r,
+    #  D the distance of the points repeated -- so the 20 neighbours of every point are its own twins once D > 4 r)
+    _, d2 = oracle.knn_f32(base, base[:, :3], 2)
+    assert np.sqrt(d2[:, 1].min()) > 8.0 * np.sqrt(3.0) * jitter
+    p_host = default_params()
+    p_host.host_optimiser = 1
+    dev, host = VgicpRegister(), VgicpRegister(params=p_host)
+    dev.setTarget(w["map"]); host.setTarget(w["map"])
+    pd, ph = w["init"].copy(), w["init"].copy()
+    assert dev.align(scan, pd) == host.align(scan, ph)
+    sd, sh = dev.stats(), host.stats()
+    print(f"device loop: {sd['iterations']} outer iterations, {sd['kernel_launches']} passes; host loop: {sh['iterations']}, {sh['kernel_launches']}")
+    assert (sd["iterations"], sd["kernel_launches"]) == (sh["iterations"], sh["kernel_launches"]), (sd, sh)
+    assert sd["kernel_launches"] >= 2      # (the fold of 258 rows ran, more than once)
+    assert sd["attempts"] == sd["kernel_launches"]      # (the passes the device loop says it evaluated)
+    dt, dr = synth.pose_error(pd, ph)
+    print(f"device loop vs host loop: {dt:.3e} m, {dr:.3e} rad")
+    assert dt <= 2e-6 and dr <= 2e-6, (dt, dr)
+    whole, again = dev.linearize(scan, w["init"]), dev.linearize(scan, w["init"])
+    lo, hi = dev.linearize(scan[:cut], w["init"]), dev.linearize(scan[cut:], w["init"])
+    assert whole["n"] == lo["n"] + hi["n"] and whole["n"] > 2000 and min(lo["n"], hi["n"]) > 0
+    print(f"whole vs halves: H {np.abs(whole['H'] - lo['H'] - hi['H']).max():.3e} of {np.abs(whole['H']).max():.3e}, "
+          f"b {np.abs(whole['b'] - lo['b'] - hi['b']).max():.3e}, err {abs(whole['err'] - lo['err'] - hi['err']):.3e} of {whole['err']:.3e}")
+    np.testing.assert_allclose(whole["H"], lo["H"] + hi["H"], rtol=1e-7, atol=1e-6)
+    np.testing.assert_allclose(whole["b"], lo["b"] + hi["b"], rtol=1e-7, atol=1e-6)
+    np.testing.assert_allclose(whole["err"], lo["err"] + hi["err"], rtol=1e-8)
+    assert again["n"] == whole["n"] and again["err"] == whole["err"]
+    np.testing.assert_array_equal(again["H"], whole["H"])
+    np.testing.assert_array_equal(again["b"], whole["b"])
+
+
 def test_half_metre_voxels(gpu, vg_world):
     """BASELINE config 3 asks for 0.5 m voxels (the reference hard-codes 1.0: SURVEY.md F9)."""
     w = vg_world
