@@ -405,6 +405,28 @@ int pcr_get_timeline(pcr_handle* h, uint64_t* out, size_t capacity, int* launche
 int pcr_ndt_derivatives(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device,
                         const double p[6], double* score, double grad[6], double hess[36], double* hess_d);
 
+/* NDT introspection: the voxel Gaussians of the current target (pcr_set_target), one record per voxel that was kept
+ * (VoxelGridCovariance::Leaf, voxel_grid_covariance_omp_impl.hpp:49-370): ijk = the voxel's lattice coordinates floorf(p * inverse_leaf)
+ * (not relative to the box's min_b), n = its points, mean, icov (row-major).  In no particular order.
+ * *count = the voxels kept, *rejected = the cells that had at least max(3, ndt_min_points) points but failed the eigenvalue or the
+ * inverse test (:337-341, :359-364).  out = NULL sizes the call; with out, capacity (in records) must be at least *count.
+ * A handle whose target pcr_scan2map prepared for that one scan's region only is refused: call pcr_set_target first. */
+typedef struct pcr_ndt_voxel {
+    int32_t ijk[3];
+    int32_t n;
+    double mean[3];
+    double icov[9];
+} pcr_ndt_voxel;
+int pcr_ndt_voxels(pcr_handle* h, pcr_ndt_voxel* out, size_t capacity, size_t* count, size_t* rejected);
+/* NDT introspection: the sums of one pass as the device-resident loop of pcr_scan2map / pcr_align computes and folds them (one launch
+ * per pass, the fold in the prologue of the next launch) -- where pcr_ndt_derivatives runs the kernels of the host-driven loop.  The
+ * loop's own two launches on a state that asks for one pass at p and ends: the sums are read from the state the second launch hands on.
+ *   kind 0: score, gradient, float Hessian (computeDerivatives)   1: score and gradient only (a line-search pass; hess = 0)
+ *        2: the double Hessian of computeHessian (score = 0, grad = 0)
+ * Handles without a communicator only (a tile set with pcr_set_shard is honoured). */
+int pcr_ndt_pass_sums(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double p[6], int kind,
+                      double* score, double grad[6], double hess[36]);
+
 int pcr_get_stats(pcr_handle* h, pcr_stats* out);
 /* 0: no timing events; 1: phase events (default); 2: also an event pair around every
  * launch of the dominant kernel (adds host work; for roofline measurement only). */

@@ -447,6 +447,8 @@ def _nd():
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_ndt_leaf_at.restype = C.c_int
         L.oracle_ndt_leaf_at.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(NdtParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_ndt_leaves.restype = C.c_size_t
+        L.oracle_ndt_leaves.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(NdtParams), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_svd6_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_ndt_trial_value.restype = C.c_double
         L.oracle_ndt_trial_value.argtypes = [C.c_double] * 9
@@ -510,6 +512,21 @@ def ndt_leaf_at(dst, p, params=None):
     mean, cov, icov = np.zeros(3), np.zeros(9), np.zeros(9)
     n = _nd().oracle_ndt_leaf_at(_p(dst), dst.shape[0], dst.shape[1], C.byref(params), _p(pp), _p(mean), _p(cov), _p(icov))
     return n, mean, cov.reshape(3, 3), icov.reshape(3, 3)
+
+
+def ndt_leaves(dst, params=None):
+    """Every voxel of the target with at least max(3, min_points) points, from one grid build, in ascending (z, y, x):
+    dict(ijk (m, 3) int32 = floorf(p * inv_leaf), n (m,) int32 with -1 for a voxel the eigenvalue or the inverse test rejected,
+    mean (m, 3), icov (m, 3, 3))."""
+    dst = _f32(dst)
+    params = params or ndt_params()
+    L = _nd()
+    stride = dst.shape[1] if dst.ndim == 2 else 4
+    m = int(L.oracle_ndt_leaves(_p(dst), dst.shape[0], stride, C.byref(params), 0, None, None, None, None))
+    ijk, n, mean, icov = np.zeros((m, 3), np.int32), np.zeros(m, np.int32), np.zeros((m, 3)), np.zeros((m, 3, 3))
+    if m:
+        L.oracle_ndt_leaves(_p(dst), dst.shape[0], stride, C.byref(params), m, _p(ijk), _p(n), _p(mean), _p(icov))
+    return dict(ijk=ijk, n=n, mean=mean, icov=icov)
 
 
 # ---------------------------------------------------------------------------

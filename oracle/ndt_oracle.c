@@ -171,6 +171,33 @@ int oracle_ndt_leaf_at(const float *pts, size_t n, size_t stride, const oracle_n
     return cnt;
 }
 
+/* every leaf with at least min_points points, from ONE grid build: its lattice coordinates floorf(p * inv_leaf) (not relative to
+ * min_b), n (-1: the leaf failed the eigenvalue or the inverse test, :337-341 / :359-364), mean, icov.  min_points is clamped to 3 as
+ * setMinPointPerVoxel does (voxel_grid_covariance_omp.h:229-240).  Returns the number of such leaves; the arrays (NULL to count only)
+ * receive the first `capacity` of them in ascending (z, y, x). */
+size_t oracle_ndt_leaves(const float *pts, size_t n, size_t stride, const oracle_ndt_params *prm, size_t capacity,
+                         int32_t *ijk, int32_t *cnt, double *mean, double *icov)
+{
+    oracle_ndt_params q = *prm;
+    if (q.min_points < 3) q.min_points = 3;
+    ndt_grid *g = ndt_grid_build(pts, n, stride, &q);
+    size_t found = 0;
+    if (g->leaves) {
+        for (int z = 0; z < g->div_b[2]; ++z) for (int y = 0; y < g->div_b[1]; ++y) for (int x = 0; x < g->div_b[0]; ++x) {
+            const leaf_t *l = &g->leaves[(size_t)x + (size_t)y * g->div_b[0] + (size_t)z * g->div_b[0] * g->div_b[1]];
+            if (l->n == 0 || (l->n > 0 && l->n < q.min_points)) continue;
+            if (ijk && found < capacity) {
+                ijk[found * 3] = x + g->min_b[0]; ijk[found * 3 + 1] = y + g->min_b[1]; ijk[found * 3 + 2] = z + g->min_b[2];
+                cnt[found] = l->n;
+                memcpy(mean + found * 3, l->mean, sizeof l->mean); memcpy(icov + found * 9, l->icov, sizeof l->icov);
+            }
+            ++found;
+        }
+    }
+    ndt_grid_free(g);
+    return found;
+}
+
 /* ---- transform helpers (float, as Eigen/PCL evaluate them) ---- */
 static void angle_axis_f(float angle, int axis, float R[9])
 {

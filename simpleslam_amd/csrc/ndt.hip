@@ -1055,6 +1055,10 @@ hipError_t ndt_launch_ctl_init(NdtCtl* d_ctl, const NdtPose& T0, const double p[
                                uint32_t* d_roi_escapes) {
     NdtCtl c;
     ndt_initial_ctl(&c, T0, p, step_size, trans_eps, max_iters, no_replay_arg);
+    return ndt_launch_ctl_state(d_ctl, c, s, d_roi_escapes);
+}
+// ... or any state the caller has made up (pcr_ndt_pass_sums: one pass and nothing after it)
+hipError_t ndt_launch_ctl_state(NdtCtl* d_ctl, const NdtCtl& c, hipStream_t s, uint32_t* d_roi_escapes) {
     NdtCtlArg a;
     memcpy(a.w, &c, sizeof c);
     hipLaunchKernelGGL(ndt_ctl_store_kernel, dim3(1), dim3(512), 0, s, d_ctl, a, d_roi_escapes);

@@ -2,6 +2,8 @@
 // (ndt_omp_impl.hpp:81-171) with the More-Thuente line search (:649-932).  pcr_ndt_derivatives and the pcr_ndt_opt_* entry points.
 
 #include <algorithm>
+#include <string>
+#include <vector>
 
 #include "handle.h"
 
@@ -341,6 +343,101 @@ int pcr_ndt_derivatives(pcr_handle* h, const void* src, size_t n_src, size_t str
         if (sharded(h) && ranks_allreduce(h, h->nd.out48.host, 43)) return 1;
         for (int i = 0; i < 36; ++i) hess_d[i] = h->nd.out48.host[7 + i];
     }
+    return 0;
+}
+
+/* ---- read-only introspection for the test suite: nothing below is called by pcr_scan2map / pcr_align ---- */
+
+int pcr_ndt_voxels(pcr_handle* h, pcr_ndt_voxel* out, size_t capacity, size_t* count, size_t* rejected) {
+    if (!h) return 1;
+    h->err.clear();
+    if (h->method != kNdt) return fail(h, "pcr_ndt_voxels needs an ndt handle");
+    if (set_device(h)) return 1;
+    if (!h->nd.target_ready) return fail(h, "no target: call pcr_set_target first");
+    if (h->roi_on) return fail(h, "pcr_ndt_voxels: pcr_scan2map prepared this target for that one scan's region only; call pcr_set_target for a target that is kept");
+    H_TRY(hipStreamSynchronize(h->stream));
+    GridHeader hd;
+    H_TRY(hipMemcpy(&hd, h->grid.header.p, sizeof hd, hipMemcpyDeviceToHost));
+    if (hd.overflow || hd.stale) return fail(h, "internal: the index of a target that pcr_set_target settled is incomplete");
+    size_t n_list = 0;
+    if (!hd.empty) {
+        // (the list's length: the counter this target's candidates pass counted in, capped like ndt_voxel_kernel caps it)
+        uint32_t cnt = 0;
+        H_TRY(hipMemcpy(&cnt, h->nd.count.as<uint32_t>() + 32 * h->nd.count_idx, sizeof cnt, hipMemcpyDeviceToHost));
+        const size_t max_vox = h->tgt_n / (size_t)std::max(3, h->prm.ndt_min_points) + 2;
+        n_list = std::min<size_t>(cnt, max_vox);
+    }
+    std::vector<uint32_t> list(n_list), slot(n_list ? (size_t)hd.n_cells : 0);
+    std::vector<NdtVoxel> vox(n_list);
+    if (n_list) {
+        H_TRY(hipMemcpy(list.data(), h->nd.list.p, n_list * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        H_TRY(hipMemcpy(slot.data(), h->nd.slot.p, slot.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        H_TRY(hipMemcpy(vox.data(), h->nd.vox.p, n_list * sizeof(NdtVoxel), hipMemcpyDeviceToHost));
+    }
+    size_t kept = 0;
+    for (size_t li = 0; li < n_list; ++li) {
+        const uint32_t t = list[li];
+        if (t >= slot.size()) return fail(h, "internal: a listed NDT cell lies outside the lattice");
+        if (slot[t] != (uint32_t)li + 1u) continue;      // rejected by the eigenvalue or the inverse test: the slot stayed 0
+        if (out && kept < capacity) {
+            const uint32_t d0 = (uint32_t)hd.dims[0], d1 = (uint32_t)hd.dims[1], row = t / d0, cz = row / d1;
+            pcr_ndt_voxel& o = out[kept];
+            // the lattice coordinate floorf(p * inv_leaf): the cell's position in the box + min_b (org holds the same number)
+            o.ijk[0] = (int32_t)(t - row * d0) + (int32_t)hd.org[0]; o.ijk[1] = (int32_t)(row - cz * d1) + (int32_t)hd.org[1]; o.ijk[2] = (int32_t)cz + (int32_t)hd.org[2];
+            o.n = vox[li].n;
+            memcpy(o.mean, vox[li].mean, sizeof o.mean);
+            memcpy(o.icov, vox[li].icov, sizeof o.icov);
+        }
+        ++kept;
+    }
+    if (count) *count = kept;
+    if (rejected) *rejected = n_list - kept;
+    if (out && capacity < kept) return fail(h, "pcr_ndt_voxels: room for " + std::to_string(capacity) + " voxels, the target has " + std::to_string(kept));
+    return 0;
+}
+
+int pcr_ndt_pass_sums(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double p[6], int kind,
+                      double* score, double grad[6], double hess[36]) {
+    if (!h) return 1;
+    h->err.clear();
+    if (h->method != kNdt) return fail(h, "pcr_ndt_pass_sums needs an ndt handle");
+    if (kind != kNdtPassDerivH && kind != kNdtPassDeriv && kind != kNdtPassHessian) return fail(h, "pcr_ndt_pass_sums: kind must be 0, 1 or 2");
+    if (!p || !grad || !hess) return fail(h, "pcr_ndt_pass_sums: p, grad or hess is NULL");
+    if (check_stride(h, stride_bytes) || set_device(h)) return 1;
+    if (!h->nd.target_ready) return fail(h, "no target: call pcr_set_target first");
+    if (sharded(h)) return fail(h, "pcr_ndt_pass_sums: a handle with a communicator does not run the one-launch-per-pass loop");
+    if (n_src > kMaxPoints) return fail(h, "source cloud too large");
+    if (ensure_full_target(h)) return 1;
+    if (score) *score = 0;
+    memset(grad, 0, 6 * sizeof(double)); memset(hess, 0, 36 * sizeof(double));
+    if (n_src == 0) return 0;      // (run_ndt does not start the device loop on an empty scan either)
+    const float* d_src = (const float*)src;
+    if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
+    H_TRY(h->nd.out.ensure());
+    H_TRY(h->nd.partials.reserve((size_t)1024 * 48 * sizeof(double)));
+    H_TRY(h->nd.ctl.reserve(2 * sizeof(NdtCtl)));
+    const NdtArgs a = ndt_args(h, d_src, n_src, stride_bytes / 4);
+    // A state that asks for ONE pass of `kind` at p and for nothing after it: the pass is taken as the evaluation that ends a line search
+    // of step 0 in an iteration past max_iters, so ctl_decide takes the sums in (score and gradient, or the Hessian), finds the loop
+    // converged and leaves them in the state it hands on.
+    NdtCtl c;
+    memset(&c, 0, sizeof c);
+    NdtPose T;
+    ndt_host::pose_from_p(p, &T);
+    ndt_opt::ctl_init(&c, T, p, 0.1, 1.0, 0);
+    c.kind = kind; c.phase = kNdtPhaseLsHess; c.nr_it = 1; c.a_t = 0.0;
+    NdtCtl* const d_ctl = h->nd.ctl.as<NdtCtl>();
+    h->seq += 1.0;
+    const double seq = h->seq;
+    H_TRY(ndt_launch_ctl_state(d_ctl, c, h->stream));
+    H_TRY(ndt_launch_pass_pro(a, d_ctl, h->nd.partials.as<double>(), h->nd.out.dev, h->stream, seq, 0));      // the pass
+    H_TRY(ndt_launch_pass_pro(a, d_ctl, h->nd.partials.as<double>(), h->nd.out.dev, h->stream, seq, 1));      // its prologue folds the rows and decides
+    H_TRY(hipMemcpyAsync(&c, d_ctl + 1, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    H_TRY(hipStreamSynchronize(h->stream));
+    if (h->nd.out.host->seq != seq || !c.done || c.bail || c.passes != 1) return fail(h, "internal: pcr_ndt_pass_sums: the loop did not end after its one pass");
+    if (score) *score = c.score;
+    for (int i = 0; i < 6; ++i) grad[i] = c.grad[i];
+    for (int i = 0; i < 36; ++i) hess[i] = c.hess[i];
     return 0;
 }
 

@@ -452,6 +452,7 @@ struct NdtCtl;
 struct NdtOut;
 hipError_t ndt_launch_ctl_init(NdtCtl* d_ctl, const NdtPose& T0, const double p[6], double step_size, double trans_eps, int max_iters, hipStream_t s, int no_replay = 0,
                                uint32_t* d_roi_escapes = nullptr);
+hipError_t ndt_launch_ctl_state(NdtCtl* d_ctl, const NdtCtl& c, hipStream_t s, uint32_t* d_roi_escapes = nullptr);
 void ndt_ctl_init_blob(BlobStore* b, NdtCtl* d_ctl, const NdtPose& T0, const double p[6], double step_size, double trans_eps, int max_iters, int no_replay_arg);
 hipError_t ndt_launch_pass_pro(const NdtArgs& a, NdtCtl* d_ctl2, double* d_rows2, NdtOut* d_out, hipStream_t s, double seq, int index,
                                hipEvent_t start = nullptr, hipEvent_t stop = nullptr);

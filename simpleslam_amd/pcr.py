@@ -57,7 +57,7 @@ class PcrStats(C.Structure):
 ABI_SYMBOLS = [
     "pcr_default_params", "pcr_create", "pcr_destroy", "pcr_last_error", "pcr_scan2map", "pcr_scan2map_device", "pcr_host_pin", "pcr_host_unpin",
     "pcr_set_target", "pcr_align", "pcr_invalidate_target", "pcr_fitness", "pcr_loam_linearize", "pcr_get_trace", "pcr_get_trace_counts",
-    "pcr_vgicp_covariances", "pcr_vgicp_neighbours", "pcr_vgicp_linearize", "pcr_gicp_linearize", "pcr_voxel_filter", "pcr_voxel_filter_begin", "pcr_voxel_filter_end", "pcr_get_timeline", "pcr_ndt_derivatives", "pcr_get_stats", "pcr_set_profile", "pcr_set_stream", "pcr_set_query_tile", "pcr_comm_unique_id", "pcr_comm_init", "pcr_comm_info", "pcr_comm_peer_export", "pcr_comm_init_peer",
+    "pcr_vgicp_covariances", "pcr_vgicp_neighbours", "pcr_vgicp_linearize", "pcr_gicp_linearize", "pcr_voxel_filter", "pcr_voxel_filter_begin", "pcr_voxel_filter_end", "pcr_get_timeline", "pcr_ndt_derivatives", "pcr_ndt_voxels", "pcr_ndt_pass_sums", "pcr_get_stats", "pcr_set_profile", "pcr_set_stream", "pcr_set_query_tile", "pcr_comm_unique_id", "pcr_comm_init", "pcr_comm_info", "pcr_comm_peer_export", "pcr_comm_init_peer",
     "pcr_comm_init_host", "pcr_set_shard", "pcr_set_params", "pcr_get_params", "pcr_fitness_gated",
     "pcr_map_create", "pcr_map_destroy", "pcr_map_last_error", "pcr_map_add_keyframe", "pcr_map_keyframes", "pcr_map_clear", "pcr_map_update", "pcr_map_update_begin", "pcr_map_wait", "pcr_map_update_window", "pcr_map_submap",
     "pcr_map_submap_indices", "pcr_map_generation", "pcr_scan2map_submap",
@@ -148,6 +148,8 @@ def load_library():
     L.pcr_gicp_linearize.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int64), vp, vp, vp]
     L.pcr_ndt_derivatives.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, dp, dp, dp, dp]
     L.pcr_get_timeline.argtypes = [vp, vp, C.c_size_t, ip, ip]
+    L.pcr_ndt_voxels.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.pcr_ndt_pass_sums.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, C.c_int, dp, dp, dp]
     L.pcr_voxel_filter.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_double, vp, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
     L.pcr_voxel_filter_begin.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_double, vp, C.c_size_t]
     L.pcr_voxel_filter_end.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -719,10 +721,24 @@ class NdtRegister(PointCloudRegister):
     """PCR::NdtRegister (reference PCR/src/NdtRegister.cpp)."""
     method = "ndt"
 
-    def derivatives(self, src, p6, double_hessian=False):
-        """One computeDerivatives pass at p = [t; roll pitch yaw] against the current target."""
+    def derivatives(self, src, p6, double_hessian=False, device_loop=False, kind=0):
+        """One computeDerivatives pass at p = [t; roll pitch yaw] against the current target, by the kernels of the host-driven loop.
+        device_loop=True: by the launches of the device-resident loop instead (pcr_ndt_pass_sums: the pass kernel scan2Map runs by default,
+        its rows folded in the prologue of the next launch); kind 0 = score, gradient, float Hessian, 1 = score and gradient only (a
+        line-search pass), 2 = the double Hessian alone (returned as hess_d)."""
         p, n, s, dev, _k = _cloud(src)
         p6 = np.ascontiguousarray(p6, np.float64).reshape(6)
+        if device_loop:
+            if double_hessian:
+                raise ValueError("device_loop: the double Hessian is a pass of its own, kind=2")
+            g, H = np.zeros(6), np.zeros(36)
+            sc = C.c_double(0)
+            dp = C.POINTER(C.c_double)
+            self._check(self._lib.pcr_ndt_pass_sums(self._h, p, n, s, dev, p6.ctypes.data_as(dp), int(kind), C.byref(sc), g.ctypes.data_as(dp),
+                                                    H.ctypes.data_as(dp)))
+            if kind == 2:
+                return dict(hess_d=H.reshape(6, 6))
+            return dict(score=sc.value, grad=g) if kind == 1 else dict(score=sc.value, grad=g, hess=H.reshape(6, 6))
         g, H = np.zeros(6), np.zeros(36)
         Hd = np.zeros(36) if double_hessian else None
         sc = C.c_double(0)
@@ -733,6 +749,20 @@ class NdtRegister(PointCloudRegister):
         if double_hessian:
             out["hess_d"] = Hd.reshape(6, 6)
         return out
+
+    def voxels(self):
+        """The voxel Gaussians of the current target (setTarget; pcr_ndt_voxels), sorted by (ix, iy, iz): dict(ijk (m, 3) int32 = the
+        lattice coordinates floorf(p * inv_leaf), n (m,), mean (m, 3), icov (m, 3, 3), rejected = cells with enough points whose
+        covariance failed the eigenvalue or the inverse test).  Raises on a handle whose target scan2Map prepared for one scan's region."""
+        cnt, rej = C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.pcr_ndt_voxels(self._h, None, 0, C.byref(cnt), C.byref(rej)))
+        rec = np.dtype([("ijk", np.int32, 3), ("n", np.int32), ("mean", np.float64, 3), ("icov", np.float64, (3, 3))])
+        assert rec.itemsize == 112
+        raw = np.zeros(cnt.value, rec)
+        if cnt.value:
+            self._check(self._lib.pcr_ndt_voxels(self._h, raw.ctypes.data_as(C.c_void_p), raw.size, C.byref(cnt), C.byref(rej)))
+        raw = raw[np.lexsort((raw["ijk"][:, 2], raw["ijk"][:, 1], raw["ijk"][:, 0]))]
+        return dict(ijk=raw["ijk"].copy(), n=raw["n"].copy(), mean=raw["mean"].copy(), icov=raw["icov"].copy(), rejected=int(rej.value))
 
 
 class VgicpRegister(PointCloudRegister):

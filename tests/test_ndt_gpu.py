@@ -32,12 +32,13 @@ def test_derivatives_match_oracle(gpu, nd_world):
         g = reg.derivatives(w["scan"], p, double_hessian=True)
         o = oracle.ndt_derivatives(w["scan"], w["map"], p, double_hessian=True)
         # (the float terms are the oracle's bit for bit -- the exponential is evaluated the way the C library does it, ndt.hip: ndt_expf --
-        #  what is left is the order of the double sums and the 1e-10 of the voxel Gaussians; 2e-5 before that)
+        #  what is left is the order of the double sums and the fixed-point grid of the voxel sums, bounded voxel by voxel in
+        #  tests/test_ndt_voxels_gpu.py; 2e-5 before that)
         assert abs(g["score"] - o["score"]) <= 1e-9 * abs(o["score"])
         gs, hs = np.abs(o["grad"]).max(), np.abs(o["hess"]).max()
         assert np.abs(g["grad"] - o["grad"]).max() <= 1e-7 * gs
         assert np.abs(g["hess"] - o["hess"]).max() <= 1e-8 * hs
-        assert np.abs(g["hess_d"] - o["hess_d"]).max() <= 1e-8 * hs     # double path: voxel Gaussians agree to ~1e-10
+        assert np.abs(g["hess_d"] - o["hess_d"]).max() <= 1e-8 * hs     # double path (the voxel Gaussians themselves: tests/test_ndt_voxels_gpu.py, bound in tests/ndt_voxel_ref.py)
 
 
 def test_scan2map_matches_oracle(gpu, nd_world):
