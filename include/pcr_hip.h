@@ -98,7 +98,31 @@ typedef struct pcr_params {
      * vgicp_trans_eps, vgicp_lm_init_scale, host_optimiser and index_no_hints. */
     double gicp_max_corr_dist; /* FLT_MAX  a correspondence needs a squared distance below (float)d * (float)d, formed in float: +inf by default
                                 *    (fast_gicp_impl.hpp:18,136); VgicpRegister::initForLC sets 150 */
+
+    /* fast_gicp's two public settings (third_parties/pclomp/src/pclomp/gicp_settings.hpp:6,10; FastGICP::setRegularizationMethod,
+     * FastVGICP::setVoxelAccumulationMode).  A value outside the range is refused by pcr_create and pcr_set_params; a change through
+     * pcr_set_params drops the prepared target. */
+    int32_t vgicp_regularization; /* PCR_REG_*, default PCR_REG_PLANE (fast_gicp_impl.hpp:20).  vgicp and gicp handles, the source's covariances and the
+                                *    target's alike (fast_gicp_impl.hpp:263-293), on the scatter C of the 20 neighbours with eigenvalues w, eigenvectors V:
+                                *    NONE C itself; MIN_EIG V diag(max(w, 1e-3)) V^T; NORMALIZED_MIN_EIG V diag(max(w / w_max, 1e-3)) V^T;
+                                *    PLANE V diag(1, 1, 1e-3) V^T; FROBENIUS (C_inv / |C_inv|_F)^-1 with C_inv = (C + 1e-3 I)^-1 */
+    int32_t vgicp_voxel_mode;  /* PCR_VOXEL_*, default PCR_VOXEL_ADDITIVE (fast_vgicp_impl.hpp:24).  vgicp handles only (a gicp handle has no voxels and
+                                *    ignores it).  ADDITIVE: mean of the points, mean of their covariances.  MULTIPLICATIVE
+                                *    (fast_vgicp_voxel.hpp:79-103): cov = (sum C_i^-1)^-1, mean = cov * sum C_i^-1 p_i.  ADDITIVE_WEIGHTED is ADDITIVE
+                                *    bit for bit: the vendored fast_gicp constructs the same AdditiveGaussianVoxel for both (fast_vgicp_voxel.hpp:138-141)
+                                *    and weighs a correspondence by sqrt(num_points) in every mode (fast_vgicp_impl.hpp:149,199) */
 } pcr_params;
+
+/* pcr_params.vgicp_regularization: fast_gicp::RegularizationMethod, in the enum's order */
+#define PCR_REG_NONE 0
+#define PCR_REG_MIN_EIG 1
+#define PCR_REG_NORMALIZED_MIN_EIG 2
+#define PCR_REG_PLANE 3
+#define PCR_REG_FROBENIUS 4
+/* pcr_params.vgicp_voxel_mode: fast_gicp::VoxelAccumulationMode, in the enum's order */
+#define PCR_VOXEL_ADDITIVE 0
+#define PCR_VOXEL_ADDITIVE_WEIGHTED 1
+#define PCR_VOXEL_MULTIPLICATIVE 2
 
 /* Per-call device timings, from HIP events on the handle's stream. */
 typedef struct pcr_stats {
@@ -418,6 +442,18 @@ typedef struct pcr_ndt_voxel {
     double icov[9];
 } pcr_ndt_voxel;
 int pcr_ndt_voxels(pcr_handle* h, pcr_ndt_voxel* out, size_t capacity, size_t* count, size_t* rejected);
+/* VGICP introspection (a vgicp handle): the Gaussian voxels of the kept target (pcr_set_target) as the fold left them
+ * (fast_vgicp_voxel.hpp:79-174, pcr_params.vgicp_voxel_mode), one record per voxel: ijk = the voxel's lattice coordinates floor(p / res - 0.5)
+ * (:158-160), n = its points, mean, cov = xx xy xz yy yz zz.  In no particular order.  *count = the voxels; out = NULL sizes the call; with
+ * out, capacity (in records) must be at least *count.  A handle whose target pcr_scan2map prepared for that one scan's region only is
+ * refused: call pcr_set_target first. */
+typedef struct pcr_vgicp_voxel {
+    int32_t ijk[3];
+    int32_t n;
+    double mean[3];
+    double cov[6];
+} pcr_vgicp_voxel;
+int pcr_vgicp_voxels(pcr_handle* h, pcr_vgicp_voxel* out, size_t capacity, size_t* count);
 /* NDT introspection: the sums of one pass as the device-resident loop of pcr_scan2map / pcr_align computes and folds them (one launch
  * per pass, the fold in the prologue of the next launch) -- where pcr_ndt_derivatives runs the kernels of the host-driven loop.  The
  * loop's own two launches on a state that asks for one pass at p and ends: the sums are read from the state the second launch hands on.

@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--map-points", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--regularization", type=int, default=3, help="pcr_params.vgicp_regularization (PCR_REG_*: 0 NONE .. 4 FROBENIUS; default 3 PLANE), both methods")
+    ap.add_argument("--voxel-mode", type=int, default=0, help="pcr_params.vgicp_voxel_mode (PCR_VOXEL_*: 0 ADDITIVE, 1 ADDITIVE_WEIGHTED, 2 MULTIPLICATIVE), vgicp")
     ap.add_argument("--calls", type=int, default=0, help="only this many gicp scan2map calls, nothing printed (for a kernel trace)")
     a = ap.parse_args()
     world, m = synth.make_map(a.map_points, seed=20261003)
@@ -42,7 +44,7 @@ def main():
         return
     poses = {}
     for method in ("vgicp", "gicp"):
-        reg = make_register(method)
+        reg = make_register(method, vgicp_regularization=a.regularization, vgicp_voxel_mode=a.voxel_mode)
         s2m, ali, idx, pas = [], [], [], []
         for k in range(a.warmup + a.reps):
             pose = init.copy()
@@ -62,7 +64,7 @@ def main():
             if k >= a.warmup:
                 ali.append(dt * 1e3)
         poses[method] = pose
-        row = dict(method=method, n_src=int(scan.shape[0]), n_dst=int(m.shape[0]), converged=bool(conv), iterations=st["iterations"], passes=st["attempts"],
+        row = dict(method=method, regularization=a.regularization, voxel_mode=a.voxel_mode, n_src=int(scan.shape[0]), n_dst=int(m.shape[0]), converged=bool(conv), iterations=st["iterations"], passes=st["attempts"],
                    scan2map_ms=_spread(s2m), index_ms=_spread(idx), pass_us=_spread(pas), align_ms=_spread(ali),
                    d_truth=[float("%.3g" % v) for v in synth.pose_error(pose, T)])
         if method == "gicp":

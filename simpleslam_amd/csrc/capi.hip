@@ -230,6 +230,17 @@ int ensure_full_target(pcr_handle* h) {
 }  // namespace host
 }  // namespace pcr
 
+namespace {
+// fast_gicp's two settings (gicp_settings.hpp:6,10): the field that is out of range, named; nullptr when both are in range
+const char* settings_out_of_range(const pcr_params& p) {
+    if (p.vgicp_regularization < PCR_REG_NONE || p.vgicp_regularization > PCR_REG_FROBENIUS)
+        return "vgicp_regularization must be 0 (NONE), 1 (MIN_EIG), 2 (NORMALIZED_MIN_EIG), 3 (PLANE) or 4 (FROBENIUS)";
+    if (p.vgicp_voxel_mode < PCR_VOXEL_ADDITIVE || p.vgicp_voxel_mode > PCR_VOXEL_MULTIPLICATIVE)
+        return "vgicp_voxel_mode must be 0 (ADDITIVE), 1 (ADDITIVE_WEIGHTED) or 2 (MULTIPLICATIVE)";
+    return nullptr;
+}
+}  // namespace
+
 extern "C" {
 
 void pcr_default_params(pcr_params* p) {
@@ -246,6 +257,7 @@ void pcr_default_params(pcr_params* p) {
     p->vgicp_rot_eps = 2e-3; p->vgicp_trans_eps = 5e-4; p->vgicp_lm_init_scale = 1e-9;
     p->record_trace = 0;
     p->gicp_max_corr_dist = (double)FLT_MAX;
+    p->vgicp_regularization = PCR_REG_PLANE; p->vgicp_voxel_mode = PCR_VOXEL_ADDITIVE;
 }
 
 pcr_handle* pcr_create(const char* method, const pcr_params* p) {
@@ -268,6 +280,8 @@ pcr_handle* pcr_create(const char* method, const pcr_params* p) {
         if (p->struct_size != sizeof(pcr_params)) { g_create_error = "pcr_params.struct_size mismatch (call pcr_default_params first)"; delete h; return nullptr; }
         h->prm = *p;
     }
+    // (before any device is touched: a machine without a GPU reports the bad field, not the missing device)
+    if (const char* bad = settings_out_of_range(h->prm)) { g_create_error = bad; delete h; return nullptr; }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0) {
@@ -444,6 +458,7 @@ int pcr_set_params(pcr_handle* h, const pcr_params* p) {
     if (p->struct_size != sizeof(pcr_params)) return fail(h, "pcr_params.struct_size mismatch (start from pcr_get_params or pcr_default_params)");
     if (p->device >= 0 && p->device != h->device) return fail(h, "a handle cannot move to another device");
     if (vgicp_family(h) && p->vgicp_k_corr != 20) return fail(h, "this build supports vgicp_k_corr = 20 (the reference's value) only");
+    if (const char* bad = settings_out_of_range(*p)) return fail(h, bad);
     const pcr_params old = h->prm;
     h->prm = *p;
     h->prm.device = old.device;
@@ -453,6 +468,12 @@ int pcr_set_params(pcr_handle* h, const pcr_params* p) {
     if (p->vgicp_resolution != old.vgicp_resolution && h->method == kVgicp) { h->vg.target_ready = false; h->have_target = false; h->grid.valid = false; }
     // (gicp: the resolution is the cell of its index, k_corr the neighbourhood of its covariances; the gate and the optimiser settings are read at every call)
     if ((p->vgicp_resolution != old.vgicp_resolution || p->vgicp_k_corr != old.vgicp_k_corr) && h->method == kGicp) { h->gi.target_ready = false; h->have_target = false; h->grid.valid = false; }
+    // the regularisation shaped every covariance the handle holds, the voxel mode the voxel map: the prepared target goes as it does with the resolution, and
+    // a scan's side that is still in flight (pcr_scan2map_submap queues it ahead) is collected and forgotten -- its covariances are the old setting's
+    const bool reg_changed = p->vgicp_regularization != old.vgicp_regularization;
+    if ((reg_changed || p->vgicp_voxel_mode != old.vgicp_voxel_mode) && h->method == kVgicp) { h->vg.target_ready = false; h->have_target = false; h->grid.valid = false; }
+    if (reg_changed && h->method == kGicp) { h->gi.target_ready = false; h->have_target = false; h->grid.valid = false; }
+    if (reg_changed && vgicp_family(h) && h->side_pending && !set_device(h)) (void)side_drain(h);
     return 0;
 }
 

@@ -3,6 +3,7 @@
 // lists + one arithmetic kernel: scan-sized clouds).
 #pragma once
 #include "pcr_internal.h"
+#include "small_math.h"
 
 namespace pcr {
 
@@ -53,7 +54,11 @@ __device__ inline void sym3_eig(const double A[6] /* xx xy xz yy yz zz */, doubl
 static constexpr int kCovK = 20;
 
 // fast_gicp_impl.hpp:255-262: the K neighbours (ORIGINAL indices, in (distance, index) order; 0xffffffff = none: a cloud of fewer than K
-// points) as f64, minus their mean, N N^T / k; JacobiSVD; PLANE regularisation.  Writes xx xy xz yy yz zz to dst; returns the neighbours found.
+// points) as f64, minus their mean, N N^T / k; the regularisation kReg (PCR_REG_*, fast_gicp_impl.hpp:263-293; JacobiSVD of a symmetric matrix read
+// as its eigen-decomposition, U = V).  Writes xx xy xz yy yz zz to dst; returns the neighbours found.
+// kReg is a template parameter, chosen on the host (COV_REG_DISPATCH): the PLANE instantiation is the code this function was before the other
+// modes existed, instruction for instruction, and no lane branches on the mode.
+template <int kReg = PCR_REG_PLANE>
 __device__ __forceinline__ int cov_from_neighbours(const uint32_t nb_idx[kCovK], const float* __restrict__ orig, uint32_t stride, double* __restrict__ dst) {
     double mx = 0, my = 0, mz = 0;
     int found = 0;
@@ -77,25 +82,62 @@ __device__ __forceinline__ int cov_from_neighbours(const uint32_t nb_idx[kCovK],
     }
 #pragma unroll
     for (int e = 0; e < 6; ++e) C[e] /= (double)kCovK;
-    double w[3], V[3][3];
-    sym3_eig(C, w, V);
-    // PLANE: singular values replaced by (1, 1, 1e-3)   fast_gicp_impl.hpp:279-281,292
-    const double val[3] = {1.0, 1.0, 1e-3};
     double out[6];
-    int o = 0;
+    if constexpr (kReg == PCR_REG_NONE) {
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
+        for (int e = 0; e < 6; ++e) out[e] = C[e];
+    } else if constexpr (kReg == PCR_REG_FROBENIUS) {
+        // (C_inv / |C_inv|_F)^-1, C_inv = (C + 1e-3 I)^-1: two inverses and a norm, as fast_gicp_impl.hpp:266-270 evaluates it
+        const double lambda = 1e-3;
+        const double Cl[6] = {C[0] + lambda, C[1], C[2], C[3] + lambda, C[4], C[5] + lambda};
+        double Ci[6];
+        inv3_sym(Cl, Ci);
+        const double nrm = sqrt(Ci[0] * Ci[0] + Ci[3] * Ci[3] + Ci[5] * Ci[5] + 2.0 * (Ci[1] * Ci[1] + Ci[2] * Ci[2] + Ci[4] * Ci[4]));
 #pragma unroll
-        for (int c = r; c < 3; ++c) {
-            double s = 0;
+        for (int e = 0; e < 6; ++e) Ci[e] /= nrm;
+        inv3_sym(Ci, out);
+    } else {
+        double w[3], V[3][3];
+        sym3_eig(C, w, V);
+        double val[3];
+        if constexpr (kReg == PCR_REG_PLANE) {
+            // PLANE: singular values replaced by (1, 1, 1e-3)   fast_gicp_impl.hpp:279-281,292
+            val[0] = 1.0; val[1] = 1.0; val[2] = 1e-3;
+        } else if constexpr (kReg == PCR_REG_MIN_EIG) {
+            // MIN_EIG: max(w, 1e-3)   fast_gicp_impl.hpp:282-284
 #pragma unroll
-            for (int e = 0; e < 3; ++e) s += V[r][e] * val[e] * V[c][e];
-            out[o++] = s;
+            for (int e = 0; e < 3; ++e) val[e] = fmax(w[e], 1e-3);
+        } else {
+            // NORMALIZED_MIN_EIG: max(w / w_max, 1e-3) (w descends: w[0] is the largest)   fast_gicp_impl.hpp:285-288
+            static_assert(kReg == PCR_REG_NORMALIZED_MIN_EIG, "kReg must be one of PCR_REG_*");
+#pragma unroll
+            for (int e = 0; e < 3; ++e) val[e] = fmax(w[e] / w[0], 1e-3);
+        }
+        int o = 0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int c = r; c < 3; ++c) {
+                double s = 0;
+#pragma unroll
+                for (int e = 0; e < 3; ++e) s += V[r][e] * val[e] * V[c][e];
+                out[o++] = s;
+            }
         }
     }
 #pragma unroll
     for (int e = 0; e < 6; ++e) dst[e] = out[e];
     return found;
 }
+
+// the kernel instantiation of a regularisation chosen at run time, on the host: CALL is a statement that uses the constant kReg
+#define COV_REG_DISPATCH(reg, CALL) \
+    switch (reg) { \
+        case PCR_REG_NONE: { constexpr int kReg = PCR_REG_NONE; CALL; } break; \
+        case PCR_REG_MIN_EIG: { constexpr int kReg = PCR_REG_MIN_EIG; CALL; } break; \
+        case PCR_REG_NORMALIZED_MIN_EIG: { constexpr int kReg = PCR_REG_NORMALIZED_MIN_EIG; CALL; } break; \
+        case PCR_REG_FROBENIUS: { constexpr int kReg = PCR_REG_FROBENIUS; CALL; } break; \
+        default: { constexpr int kReg = PCR_REG_PLANE; CALL; } break; \
+    }
 
 }  // namespace pcr

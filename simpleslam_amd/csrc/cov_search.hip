@@ -16,8 +16,8 @@
 //   B  cov_wave_kernel    WAVE per queued query, lanes = candidates: ring after ring, level after level like the old kernel, but a ring's
 //                         rows are fetched 64 at a time and its candidates 64 at a time, keys exact (distance bits << 32 | index); a
 //                         chunk's candidates below the current 20th key are merged into the list by rank counting in LDS.
-//   C  cov_from_nbr_kernel  lane per query: the covariance arithmetic (f64 sums in neighbour order, Jacobi eigen-decomposition, PLANE
-//                         regularisation) from the neighbour lists A and B leave in HBM.
+//   C  cov_from_nbr_kernel  lane per query: the covariance arithmetic (f64 sums in neighbour order, Jacobi eigen-decomposition, the
+//                         regularisation kReg: one instantiation per PCR_REG_*) from the neighbour lists A and B leave in HBM.
 //
 // Results are the old kernel's bit for bit (same neighbours in the same order into the same arithmetic: cov_math.h).
 #include <string.h>
@@ -487,6 +487,7 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(GridView g0, GridView g1,
 // ------------------------------------------------------------------------------
 // C: covariance of every point from its neighbour list (lane per cell-sorted point)
 // ------------------------------------------------------------------------------
+template <int kReg>
 __global__ __launch_bounds__(256) void cov_from_nbr_kernel(GridView g, const float* __restrict__ orig, uint32_t stride, uint32_t n_sorted_max,
                                                            const uint32_t* __restrict__ nbr, uint32_t n_cap, double* __restrict__ cov6,
                                                            const int use_check, const CovCheck chk) {
@@ -501,7 +502,7 @@ __global__ __launch_bounds__(256) void cov_from_nbr_kernel(GridView g, const flo
 #pragma unroll
     for (int i = 1; i < kCovK; ++i) nb_idx[i] = nbr[(size_t)i * n_cap + j];
     const float4 q = g.pts[j];
-    const int found = cov_from_neighbours(nb_idx, orig, stride, cov6 + (size_t)__float_as_uint(q.w) * 6);
+    const int found = cov_from_neighbours<kReg>(nb_idx, orig, stride, cov6 + (size_t)__float_as_uint(q.w) * 6);
     if (use_check) {
         // sharded target: this rank holds every map point inside [ext_lo, ext_hi) only.  The neighbourhood of a point that
         // can enter a voxel of the tile is the map's own iff its 20th neighbour is nearer than every face of that region.
@@ -546,7 +547,7 @@ void CovScratch::release() { nbr.release(); queue.release(); seed.release(); cou
 
 // The three kernels over one cloud (scratch reserved for >= n points by the caller, before anything was queued).
 hipError_t cov_search_launch(const GridIndex& grid, const GridIndex* coarse1, const GridIndex* coarse2, const float* d_orig, size_t stride_floats,
-                             size_t n, double* d_cov6, hipStream_t s, const CovCheck* check, const RoiView* roi, CovScratch& sc, hipEvent_t* ev) {
+                             size_t n, double* d_cov6, hipStream_t s, const CovCheck* check, const RoiView* roi, CovScratch& sc, int reg, hipEvent_t* ev) {
     const uint32_t blocks = (uint32_t)((n + 255) / 256 ? (n + 255) / 256 : 1);
     const int levels = coarse1 ? (coarse2 ? 3 : 2) : 1;
     CovCheck chk;
@@ -568,8 +569,9 @@ hipError_t cov_search_launch(const GridIndex& grid, const GridIndex* coarse1, co
     hipExtLaunchKernelGGL(cov_wave_kernel, dim3(2048), dim3(256), 0, s, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr, 0, grid.view(), coarse1 ? coarse1->view() : grid.view(),
                        coarse2 ? coarse2->view() : grid.view(), levels, sc.queue.as<uint32_t>(), sc.seed.as<unsigned long long>(), sc.count.as<uint32_t>(),
                        n_cap, sc.nbr.as<uint32_t>(), n_cap);
-    hipExtLaunchKernelGGL(cov_from_nbr_kernel, dim3(blocks), dim3(256), 0, s, ev ? ev[4] : nullptr, ev ? ev[5] : nullptr, 0, grid.view(), d_orig, (uint32_t)stride_floats, (uint32_t)n, sc.nbr.as<uint32_t>(), n_cap,
-                       d_cov6, check ? 1 : 0, chk);
+    // (the regularisation: one instantiation of the arithmetic kernel each, cov_math.h)
+    COV_REG_DISPATCH(reg, hipExtLaunchKernelGGL(cov_from_nbr_kernel<kReg>, dim3(blocks), dim3(256), 0, s, ev ? ev[4] : nullptr, ev ? ev[5] : nullptr, 0, grid.view(), d_orig,
+                                                (uint32_t)stride_floats, (uint32_t)n, sc.nbr.as<uint32_t>(), n_cap, d_cov6, check ? 1 : 0, chk))
     return hipGetLastError();
 }
 

@@ -53,7 +53,7 @@ int gicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t 
         cov_grid = &h->cov_l1;
     }
     H_TRY(vgicp_launch_cov(*cov_grid, levels > 1 ? &h->cov_l1 : nullptr, levels > 2 ? &h->vg.cov_l2 : nullptr, d_dst, stride_floats, n_dst,
-                           h->gi.tgt_cov6.as<double>(), h->stream, nullptr, nullptr, &h->vg.tgt_scratch));
+                           h->gi.tgt_cov6.as<double>(), h->stream, h->prm.vgicp_regularization, nullptr, nullptr, &h->vg.tgt_scratch));
     h->gi.target_ready = true;
     return 0;
 }

@@ -248,7 +248,7 @@ struct GridIndex {
 // ---------------------------------------------------------------------------
 // VGICP (vgicp.hip)
 // ---------------------------------------------------------------------------
-struct VgicpVoxel {          // fast_vgicp_voxel.hpp:59-82 (GaussianVoxel, ADDITIVE, finalized)
+struct VgicpVoxel {          // fast_vgicp_voxel.hpp:57-122 (GaussianVoxel, finalized: ADDITIVE or MULTIPLICATIVE)
     double mean[3];
     double cov[6];           // xx xy xz yy yz zz
     double w;                // sqrt(num_points)
@@ -335,12 +335,13 @@ struct CovScratch {
 };
 // ev (optional, profiling passes): 6 events = begin / end of the three kernels
 hipError_t cov_search_launch(const GridIndex& grid, const GridIndex* coarse1, const GridIndex* coarse2, const float* d_orig, size_t stride_floats,
-                             size_t n, double* d_cov6, hipStream_t s, const CovCheck* check, const RoiView* roi, CovScratch& sc, hipEvent_t* ev = nullptr);
+                             size_t n, double* d_cov6, hipStream_t s, const CovCheck* check, const RoiView* roi, CovScratch& sc, int reg, hipEvent_t* ev = nullptr);
 // scratch: scan-sized clouds (n <= 300 000) go through cov_search.hip when given one
+// reg: pcr_params.vgicp_regularization (PCR_REG_*, validated by the caller); mode: pcr_params.vgicp_voxel_mode (PCR_VOXEL_*): no defaults, a caller names them
 hipError_t vgicp_launch_cov(const GridIndex& grid, const GridIndex* coarse1, const GridIndex* coarse2, const float* d_orig, size_t stride_floats,
-                            size_t n, double* d_cov6, hipStream_t s, const CovCheck* check = nullptr, const RoiView* roi = nullptr, CovScratch* scratch = nullptr,
-                            hipEvent_t* ev = nullptr);
-hipError_t vgicp_launch_voxels(const GridIndex& grid, const double* d_cov6, VgicpVoxel* d_vox, hipStream_t s, const RoiView* roi = nullptr);
+                            size_t n, double* d_cov6, hipStream_t s, int reg, const CovCheck* check = nullptr, const RoiView* roi = nullptr,
+                            CovScratch* scratch = nullptr, hipEvent_t* ev = nullptr);
+hipError_t vgicp_launch_voxels(const GridIndex& grid, const double* d_cov6, VgicpVoxel* d_vox, hipStream_t s, int reg, int mode, const RoiView* roi = nullptr);
 // (seq: written last into d_out32[31] / d_out48[47], host-mapped: the completion word the host spins on)
 hipError_t vgicp_launch_linearize(const VgicpArgs& a, const Pose16& T, double* d_out32, hipStream_t s, double seq = 0.0);
 // device-resident Levenberg-Marquardt loop (vgicp_opt.h): state in HBM, result in host-mapped memory

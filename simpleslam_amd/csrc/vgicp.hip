@@ -3,9 +3,11 @@
 // Kernels for the reference's PCR::VgicpRegister::scan2Map (PCR/src/VgicpRegister.cpp:30-45),
 // i.e. fast_gicp::FastVGICP under PCL's align():
 //   V2 per-point covariances      fast_gicp_impl.hpp:241-297  (serial there: 20-NN over a FLANN
-//      kd-tree, 4x20 f64 neighbours, cov/20, JacobiSVD, PLANE regularisation U diag(1,1,1e-3) V^T)
+//      kd-tree, 4x20 f64 neighbours, cov/20, JacobiSVD, the regularisation: PLANE U diag(1,1,1e-3) V^T by default,
+//      pcr_params.vgicp_regularization for the other four of fast_gicp_impl.hpp:263-293)
 //      -> vgicp_cov_kernel: exact ring search on the uniform grid, float distances like FLANN
-//   V3 Gaussian voxel map         pclomp/fast_vgicp_voxel.hpp:105-174 (serial unordered_map, ADDITIVE)
+//   V3 Gaussian voxel map         pclomp/fast_vgicp_voxel.hpp:79-174 (serial unordered_map; ADDITIVE by default, MULTIPLICATIVE by
+//      pcr_params.vgicp_voxel_mode)
 //      -> vgicp_voxel_kernel: one thread per voxel, fixed-point sums (order independent)
 //   V4/V5 correspondences, Mahalanobis, linearize, compute_error   fast_vgicp_impl.hpp:73-204
 //      -> vgicp_linearize_kernel<false> (linearize) and <true> (compute_error of an LM trial pose + the linearisation at
@@ -71,7 +73,8 @@ __global__ __launch_bounds__(256) void vgicp_region_list_kernel(GridView g, uint
 }
 
 // list / list_count (optional): the sorted positions to process (vgicp_region_list_kernel) instead of every position with the region test
-template <bool kBatch>
+// kReg: the regularisation (PCR_REG_*), a template parameter of the arithmetic (cov_math.h), chosen on the host
+template <bool kBatch, int kReg>
 __global__ __launch_bounds__(256, kBatch ? 1 : 4) void vgicp_cov_kernel(GridView g, GridView g1, GridView g2, int n_levels, const float* __restrict__ orig,
                                                         uint32_t stride, uint32_t n_sorted_max, double* __restrict__ cov6, const int use_check,
                                                         const CovCheck chk, const RoiView roi, const uint32_t* __restrict__ list,
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(256, kBatch ? 1 : 4) void vgicp_cov_kernel(GridView
         uint32_t nb_idx[kCovK];
 #pragma unroll
         for (int i = 0; i < kCovK; ++i) nb_idx[i] = L.k[i] != ~0ull ? (uint32_t)L.k[i] : 0xffffffffu;
-        const int found = cov_from_neighbours(nb_idx, orig, stride, cov6 + (size_t)__float_as_uint(q.w) * 6);
+        const int found = cov_from_neighbours<kReg>(nb_idx, orig, stride, cov6 + (size_t)__float_as_uint(q.w) * 6);
         if (use_check) {
             // sharded target: this rank holds every map point inside [ext_lo, ext_hi) only.  The neighbourhood of a point that
             // can enter a voxel of the tile is the map's own iff its 20th neighbour is nearer than every face of that region.
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(256, kBatch ? 1 : 4) void vgicp_cov_kernel(GridView
 // (GridHeader.shift = 0.5), so a voxel IS a cell and its points are one contiguous run.
 // One thread per sorted point; the thread of a cell's first point folds the run and stores the
 // voxel at that position (no slot table, no counter).
-// Sums are fixed point (2^44 per unit), hence independent of the order of the points.
+// Sums are fixed point (2^44 per unit, or a scale chosen per voxel: fold_scaled), hence independent of the order of the points.
 // ------------------------------------------------------------------------------
 static constexpr double kFix = 17592186044416.0;   // 2^44
 
@@ -139,6 +142,91 @@ __device__ __forceinline__ bool lattice_key(const GridHeader& h, double x, doubl
     return true;
 }
 
+// ---- the fold beyond unit covariances ----
+// The fixed scale 2^44 is exact only while the terms stay below 1: PLANE and NORMALIZED_MIN_EIG under ADDITIVE.  Every other setting has terms
+// without a bound (the scatter itself; FROBENIUS up to (w_max + 1e-3) / 1e-3; an inverse covariance up to 1e3 and beyond), so the scale is
+// chosen per voxel: a first pass over the run takes the largest magnitude m of the terms (a maximum does not depend on the order); with e the
+// smallest exponent with m <= 2^e and c = ceil(log2 cnt), every term is rounded to a multiple of 2^-s, s = 62 - e - c, and added as a long long:
+// a term is at most 2^(62 - c), a sum at most 2^62.  The integer sums are exact, hence independent of the order; a term loses at most
+// 2^(c - 63) of the largest one, which for a thousand points is the rounding of a double.  A term that is not finite makes the voxel's
+// covariance NaN: it never reaches the integer conversion.
+enum { kFoldFixed = 0, kFoldScaled = 1, kFoldMult = 2 };
+
+__device__ __forceinline__ int fold_scale(double m, uint32_t cnt) {
+    int e = 0;
+    if (m != 0.0 && frexp(m, &e) == 0.5) --e;      // m <= 2^e, the smallest such e
+    const int c = cnt > 1u ? 32 - __clz((int)(cnt - 1u)) : 0;      // cnt <= 2^c
+    return 62 - e - c;
+}
+
+// one point's terms: ADDITIVE the covariance's six entries and the offset from the voxel's corner; MULTIPLICATIVE A = C^-1 (the 3x3 block of the
+// reference's 4x4 with (3,3) = 1, which is block diagonal: fast_vgicp_voxel.hpp:86-94) and B = A (p - corner)
+template <bool kMult>
+__device__ __forceinline__ void fold_terms(const float4& p, const double* __restrict__ cc, const double o[3], double A[6], double B[3]) {
+    const double d[3] = {(double)p.x - o[0], (double)p.y - o[1], (double)p.z - o[2]};
+    if constexpr (kMult) {
+        const double C[6] = {cc[0], cc[1], cc[2], cc[3], cc[4], cc[5]};
+        inv3_sym(C, A);
+        B[0] = A[0] * d[0] + A[1] * d[1] + A[2] * d[2]; B[1] = A[1] * d[0] + A[3] * d[1] + A[4] * d[2]; B[2] = A[2] * d[0] + A[4] * d[1] + A[5] * d[2];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) A[k] = cc[k];
+        B[0] = d[0]; B[1] = d[1]; B[2] = d[2];
+    }
+}
+
+template <bool kMult>
+__device__ __forceinline__ void fold_scaled(const GridView& g, const double* __restrict__ cov6, uint32_t j, uint32_t e, const double o[3], VgicpVoxel& v) {
+    const uint32_t cnt = e - j;
+    double mA = 0.0, mB = 0.0;
+    bool badA = false, badB = false;
+    for (uint32_t i = j; i < e; ++i) {
+        const float4 p = g.pts[i];
+        double A[6], B[3];
+        fold_terms<kMult>(p, cov6 + (size_t)__float_as_uint(p.w) * 6, o, A, B);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { const double t = fabs(A[k]); badA = badA || !(t <= DBL_MAX); mA = fmax(mA, t); }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { const double t = fabs(B[k]); badB = badB || !(t <= DBL_MAX); mB = fmax(mB, t); }
+    }
+    const double qnan = __builtin_nan("");
+    const int sA = badA ? 0 : fold_scale(mA, cnt), sB = badB ? 0 : fold_scale(mB, cnt);
+    long long a[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
+    for (uint32_t i = j; i < e; ++i) {
+        const float4 p = g.pts[i];
+        double A[6], B[3];
+        fold_terms<kMult>(p, cov6 + (size_t)__float_as_uint(p.w) * 6, o, A, B);
+        if (!badA) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) a[k] += llrint(ldexp(A[k], sA));
+        }
+        if (!badB) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) b[k] += llrint(ldexp(B[k], sB));
+        }
+    }
+    double SA[6], SB[3];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) SA[k] = badA ? qnan : ldexp((double)a[k], -sA);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) SB[k] = badB ? qnan : ldexp((double)b[k], -sB);
+    if constexpr (kMult) {
+        // finalize (fast_vgicp_voxel.hpp:96-102): cov = (sum A)^-1, mean = cov * sum A p = corner + cov * sum A (p - corner)
+        inv3_sym(SA, v.cov);
+        v.mean[0] = o[0] + (v.cov[0] * SB[0] + v.cov[1] * SB[1] + v.cov[2] * SB[2]);
+        v.mean[1] = o[1] + (v.cov[1] * SB[0] + v.cov[3] * SB[1] + v.cov[4] * SB[2]);
+        v.mean[2] = o[2] + (v.cov[2] * SB[0] + v.cov[4] * SB[1] + v.cov[5] * SB[2]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v.mean[k] = o[k] + SB[k] / (double)cnt;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) v.cov[k] = SA[k] / (double)cnt;
+    }
+}
+
+// kFold: kFoldFixed = ADDITIVE over covariances with entries <= 1 (PLANE, NORMALIZED_MIN_EIG): the fixed scale below; kFoldScaled = ADDITIVE over
+// any covariances, kFoldMult = MULTIPLICATIVE: a scale per voxel (fold_scaled)
+template <int kFold>
 __global__ __launch_bounds__(256) void vgicp_voxel_kernel(GridView g, const double* __restrict__ cov6, VgicpVoxel* __restrict__ vox, const RoiView roi) {
     const GridHeader h = *g.hdr;
     if (h.overflow || h.empty || h.stale) return;
@@ -155,34 +243,39 @@ __global__ __launch_bounds__(256) void vgicp_voxel_kernel(GridView g, const doub
         const double ox = (c[0] + h.shift) * h.cell, oy = (c[1] + h.shift) * h.cell, oz = (c[2] + h.shift) * h.cell;   // lower corner
         const uint32_t cnt = e - j;
         VgicpVoxel v;
-        const double inv = 1.0 / (double)cnt;
-        // Every term is rounded to a multiple of 2^-44 first, so the sums are exact and independent of the order.  While they provably
-        // stay below 2^53 (offsets < cell, covariance entries <= 1 in magnitude after the regularisation) the integers are added
-        // up as doubles -- one v_rndne_f64 and one v_add_f64 per term, where the f64 -> i64 conversion alone costs a dozen instructions.
-        if ((double)cnt * (h.cell > 1.0 ? h.cell : 1.0) <= 256.0) {
-            double dm[3] = {0, 0, 0}, dc[6] = {0, 0, 0, 0, 0, 0};
-            for (uint32_t i = j; i < e; ++i) {
-                const float4 p = g.pts[i];
-                dm[0] += rint(((double)p.x - ox) * kFix); dm[1] += rint(((double)p.y - oy) * kFix); dm[2] += rint(((double)p.z - oz) * kFix);
-                const double* cc = cov6 + (size_t)__float_as_uint(p.w) * 6;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) dc[k] += rint(cc[k] * kFix);
-            }
-            v.mean[0] = ox + dm[0] / kFix * inv; v.mean[1] = oy + dm[1] / kFix * inv; v.mean[2] = oz + dm[2] / kFix * inv;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) v.cov[k] = dc[k] / kFix * inv;
+        if constexpr (kFold != kFoldFixed) {
+            const double o[3] = {ox, oy, oz};
+            fold_scaled<kFold == kFoldMult>(g, cov6, j, e, o, v);
         } else {
-            long long sm[3] = {0, 0, 0}, sc[6] = {0, 0, 0, 0, 0, 0};
-            for (uint32_t i = j; i < e; ++i) {
-                const float4 p = g.pts[i];
-                sm[0] += llrint(((double)p.x - ox) * kFix); sm[1] += llrint(((double)p.y - oy) * kFix); sm[2] += llrint(((double)p.z - oz) * kFix);
-                const double* cc = cov6 + (size_t)__float_as_uint(p.w) * 6;
+            const double inv = 1.0 / (double)cnt;
+            // Every term is rounded to a multiple of 2^-44 first, so the sums are exact and independent of the order.  While they provably
+            // stay below 2^53 (offsets < cell, covariance entries <= 1 in magnitude after the regularisation) the integers are added
+            // up as doubles -- one v_rndne_f64 and one v_add_f64 per term, where the f64 -> i64 conversion alone costs a dozen instructions.
+            if ((double)cnt * (h.cell > 1.0 ? h.cell : 1.0) <= 256.0) {
+                double dm[3] = {0, 0, 0}, dc[6] = {0, 0, 0, 0, 0, 0};
+                for (uint32_t i = j; i < e; ++i) {
+                    const float4 p = g.pts[i];
+                    dm[0] += rint(((double)p.x - ox) * kFix); dm[1] += rint(((double)p.y - oy) * kFix); dm[2] += rint(((double)p.z - oz) * kFix);
+                    const double* cc = cov6 + (size_t)__float_as_uint(p.w) * 6;
 #pragma unroll
-                for (int k = 0; k < 6; ++k) sc[k] += llrint(cc[k] * kFix);
+                    for (int k = 0; k < 6; ++k) dc[k] += rint(cc[k] * kFix);
+                }
+                v.mean[0] = ox + dm[0] / kFix * inv; v.mean[1] = oy + dm[1] / kFix * inv; v.mean[2] = oz + dm[2] / kFix * inv;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) v.cov[k] = dc[k] / kFix * inv;
+            } else {
+                long long sm[3] = {0, 0, 0}, sc[6] = {0, 0, 0, 0, 0, 0};
+                for (uint32_t i = j; i < e; ++i) {
+                    const float4 p = g.pts[i];
+                    sm[0] += llrint(((double)p.x - ox) * kFix); sm[1] += llrint(((double)p.y - oy) * kFix); sm[2] += llrint(((double)p.z - oz) * kFix);
+                    const double* cc = cov6 + (size_t)__float_as_uint(p.w) * 6;
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) sc[k] += llrint(cc[k] * kFix);
+                }
+                v.mean[0] = ox + (double)sm[0] / kFix * inv; v.mean[1] = oy + (double)sm[1] / kFix * inv; v.mean[2] = oz + (double)sm[2] / kFix * inv;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) v.cov[k] = (double)sc[k] / kFix * inv;
             }
-            v.mean[0] = ox + (double)sm[0] / kFix * inv; v.mean[1] = oy + (double)sm[1] / kFix * inv; v.mean[2] = oz + (double)sm[2] / kFix * inv;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) v.cov[k] = (double)sc[k] / kFix * inv;
         }
         v.w = sqrt((double)cnt);   // fast_vgicp_impl.hpp:149
         v.n = cnt; v.pad = 0;
@@ -443,10 +536,10 @@ __global__ __launch_bounds__(256) void fitness_kernel(GridView g, const float* _
 
 // ---- host launchers ---------------------------------------------------------------
 hipError_t vgicp_launch_cov(const GridIndex& grid, const GridIndex* coarse1, const GridIndex* coarse2, const float* d_orig, size_t stride_floats,
-                            size_t n, double* d_cov6, hipStream_t s, const CovCheck* check, const RoiView* roi, CovScratch* scratch, hipEvent_t* ev) {
+                            size_t n, double* d_cov6, hipStream_t s, int reg, const CovCheck* check, const RoiView* roi, CovScratch* scratch, hipEvent_t* ev) {
     if (scratch && n <= 300000 && n > 0) {      // scan-sized: two classes of queries (cov_search.hip)
         const hipError_t e = scratch->reserve(n);
-        return e != hipSuccess ? e : cov_search_launch(grid, coarse1, coarse2, d_orig, stride_floats, n, d_cov6, s, check, roi, *scratch, ev);
+        return e != hipSuccess ? e : cov_search_launch(grid, coarse1, coarse2, d_orig, stride_floats, n, d_cov6, s, check, roi, *scratch, reg, ev);
     }
     const int blocks = (int)std::min<size_t>(65535, (n + 255) / 256 ? (n + 255) / 256 : 1);
     const int levels = coarse1 ? (coarse2 ? 3 : 2) : 1;
@@ -474,23 +567,26 @@ hipError_t vgicp_launch_cov(const GridIndex& grid, const GridIndex* coarse1, con
     }
 #define PCR_COV_ARGS grid.view(), coarse1 ? coarse1->view() : grid.view(), coarse2 ? coarse2->view() : grid.view(), levels, d_orig, (uint32_t)stride_floats, (uint32_t)n, d_cov6, check ? 1 : 0, chk, rv, d_list, d_list_count
     if (n <= 300000) {      // scan-sized (the same threshold as the choice of search levels, vgicp_host.hip: cov_levels)
-        if (ev) hipExtLaunchKernelGGL(vgicp_cov_kernel<true>, dim3(blocks), dim3(256), 0, s, ev[0], ev[1], 0, PCR_COV_ARGS);
-        else hipLaunchKernelGGL(vgicp_cov_kernel<true>, dim3(blocks), dim3(256), 0, s, PCR_COV_ARGS);
+        COV_REG_DISPATCH(reg, if (ev) hipExtLaunchKernelGGL((vgicp_cov_kernel<true, kReg>), dim3(blocks), dim3(256), 0, s, ev[0], ev[1], 0, PCR_COV_ARGS);
+                              else hipLaunchKernelGGL((vgicp_cov_kernel<true, kReg>), dim3(blocks), dim3(256), 0, s, PCR_COV_ARGS))
     } else {
-        if (ev) hipExtLaunchKernelGGL(vgicp_cov_kernel<false>, dim3(cov_blocks), dim3(256), 0, s, ev[0], ev[1], 0, PCR_COV_ARGS);
-        else hipLaunchKernelGGL(vgicp_cov_kernel<false>, dim3(cov_blocks), dim3(256), 0, s, PCR_COV_ARGS);
+        COV_REG_DISPATCH(reg, if (ev) hipExtLaunchKernelGGL((vgicp_cov_kernel<false, kReg>), dim3(cov_blocks), dim3(256), 0, s, ev[0], ev[1], 0, PCR_COV_ARGS);
+                              else hipLaunchKernelGGL((vgicp_cov_kernel<false, kReg>), dim3(cov_blocks), dim3(256), 0, s, PCR_COV_ARGS))
     }
 #undef PCR_COV_ARGS
     return hipGetLastError();
 }
 
-hipError_t vgicp_launch_voxels(const GridIndex& grid, const double* d_cov6, VgicpVoxel* d_vox, hipStream_t s, const RoiView* roi) {
+hipError_t vgicp_launch_voxels(const GridIndex& grid, const double* d_cov6, VgicpVoxel* d_vox, hipStream_t s, int reg, int mode, const RoiView* roi) {
     const size_t n = grid.n_points;
     const int blocks = (int)std::min<size_t>(65535, (n + 255) / 256 ? (n + 255) / 256 : 1);
     RoiView rv;
     memset(&rv, 0, sizeof rv);
     if (roi) rv = *roi;
-    hipLaunchKernelGGL(vgicp_voxel_kernel, dim3(blocks), dim3(256), 0, s, grid.view(), d_cov6, d_vox, rv);
+    // (ADDITIVE_WEIGHTED is ADDITIVE: fast_vgicp_voxel.hpp:138-141)
+    if (mode == PCR_VOXEL_MULTIPLICATIVE) hipLaunchKernelGGL(vgicp_voxel_kernel<kFoldMult>, dim3(blocks), dim3(256), 0, s, grid.view(), d_cov6, d_vox, rv);
+    else if (reg == PCR_REG_PLANE || reg == PCR_REG_NORMALIZED_MIN_EIG) hipLaunchKernelGGL(vgicp_voxel_kernel<kFoldFixed>, dim3(blocks), dim3(256), 0, s, grid.view(), d_cov6, d_vox, rv);
+    else hipLaunchKernelGGL(vgicp_voxel_kernel<kFoldScaled>, dim3(blocks), dim3(256), 0, s, grid.view(), d_cov6, d_vox, rv);
     return hipGetLastError();
 }
 

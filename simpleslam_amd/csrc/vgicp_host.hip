@@ -224,7 +224,7 @@ int vgicp_source_enqueue(pcr_handle* h, const float* d_src, size_t n_src, size_t
             err = std::string("hipMemcpyAsync(side header): ") + hipGetErrorString(e);
     }
     if (e == hipSuccess && (e = vgicp_launch_cov(h->src_grid, levels > 1 ? &h->vg.src_l1 : nullptr, levels > 2 ? &h->vg.src_l2 : nullptr, d_src, stride_floats, n_src,
-                                                 h->vg.src_cov6.as<double>(), h->side_stream, nullptr, nullptr, &h->vg.src_scratch,
+                                                 h->vg.src_cov6.as<double>(), h->side_stream, h->prm.vgicp_regularization, nullptr, nullptr, &h->vg.src_scratch,
                                                  (h->profile >= 2 && h->ev_cov[2] && n_src > 0 && scan_sized(n_src)) ? h->ev_cov + 2 : nullptr)) != hipSuccess)
         err = std::string("vgicp_launch_cov: ") + hipGetErrorString(e);
     if (e == hipSuccess && h->profile >= 2 && h->ev_cov[2] && n_src > 0 && scan_sized(n_src)) h->ev_cov_src_used = true;
@@ -270,7 +270,7 @@ int vgicp_source_settle(pcr_handle* h, const float* d_src, size_t n_src, size_t 
     if (settle_scan_levels(h, d_src, n_src, stride_floats)) return 1;
     H_TRY(h->vg.src_cov6.reserve((n_src + 1) * 6 * sizeof(double)));
     H_TRY(vgicp_launch_cov(h->src_grid, levels > 1 ? &h->vg.src_l1 : nullptr, levels > 2 ? &h->vg.src_l2 : nullptr, d_src, stride_floats, n_src,
-                           h->vg.src_cov6.as<double>(), h->stream, nullptr, nullptr, &h->vg.src_scratch));
+                           h->vg.src_cov6.as<double>(), h->stream, h->prm.vgicp_regularization, nullptr, nullptr, &h->vg.src_scratch));
     return 0;
 }
 
@@ -365,10 +365,11 @@ int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t
             h->roi_on = true;
         }
         H_TRY(vgicp_launch_cov(*cov_grid, cov_levels(n_dst) > 1 ? &h->cov_l1 : nullptr, cov_levels(n_dst) > 2 ? &h->vg.cov_l2 : nullptr, d_dst, stride_floats,
-                               n_dst, h->vg.tgt_cov6.as<double>(), h->stream, check ? &chk : nullptr, h->roi_on ? &roi : nullptr, &h->vg.tgt_scratch,
-                               (h->profile >= 2 && h->ev_cov[0] && !scan_sized(n_dst)) ? h->ev_cov : nullptr));
+                               n_dst, h->vg.tgt_cov6.as<double>(), h->stream, h->prm.vgicp_regularization, check ? &chk : nullptr, h->roi_on ? &roi : nullptr,
+                               &h->vg.tgt_scratch, (h->profile >= 2 && h->ev_cov[0] && !scan_sized(n_dst)) ? h->ev_cov : nullptr));
         if (h->profile >= 2 && h->ev_cov[0] && !scan_sized(n_dst)) h->ev_cov_tgt_used = true;
-        H_TRY(vgicp_launch_voxels(h->grid, h->vg.tgt_cov6.as<double>(), h->vg.vox.as<VgicpVoxel>(), h->stream, h->roi_on ? &roi : nullptr));
+        H_TRY(vgicp_launch_voxels(h->grid, h->vg.tgt_cov6.as<double>(), h->vg.vox.as<VgicpVoxel>(), h->stream, h->prm.vgicp_regularization, h->prm.vgicp_voxel_mode,
+                                  h->roi_on ? &roi : nullptr));
         return 0;
     };
     H_TRY(h->vg.tgt_cov6.reserve((n_dst + 1) * 6 * sizeof(double)));
@@ -620,7 +621,7 @@ int pcr_vgicp_covariances(pcr_handle* h, const void* pts, size_t n, size_t strid
     H_TRY(h->vg.src_cov6.reserve((n + 1) * 6 * sizeof(double)));
     H_TRY(hipMemsetAsync(h->vg.src_cov6.p, 0, (n + 1) * 6 * sizeof(double), h->stream));
     H_TRY(vgicp_launch_cov(h->src_grid, cov_levels(n) > 1 ? &h->vg.src_l1 : nullptr, cov_levels(n) > 2 ? &h->vg.src_l2 : nullptr, d_pts, stride_bytes / 4, n,
-                           h->vg.src_cov6.as<double>(), h->stream, nullptr, nullptr, &h->vg.src_scratch));
+                           h->vg.src_cov6.as<double>(), h->stream, h->prm.vgicp_regularization, nullptr, nullptr, &h->vg.src_scratch));
     H_TRY(hipMemcpyAsync(cov_out, h->vg.src_cov6.p, n * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     H_TRY(hipStreamSynchronize(h->stream));
     return 0;
@@ -680,6 +681,47 @@ int pcr_vgicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t str
     if (sharded(h) && ranks_allreduce(h, h->out32.host, 29)) return 1;
     unpack_lsq_sums(h->out32.host, H, b, error);
     if (n_corr) { int64_t c = 0; for (uint32_t v : slots) c += v != 0; *n_corr = c; }
+    return 0;
+}
+
+/* ---- read-only introspection for the test suite: not called by pcr_scan2map / pcr_align ---- */
+int pcr_vgicp_voxels(pcr_handle* h, pcr_vgicp_voxel* out, size_t capacity, size_t* count) {
+    if (!h) return 1;
+    h->err.clear();
+    if (h->method != kVgicp) return fail(h, "pcr_vgicp_voxels needs a vgicp handle");
+    if (set_device(h)) return 1;
+    if (!h->vg.target_ready) return fail(h, "no target: call pcr_set_target first");
+    if (h->roi_on) return fail(h, "pcr_vgicp_voxels: pcr_scan2map prepared this target for that one scan's region only; call pcr_set_target first, for a target that is kept");
+    H_TRY(hipStreamSynchronize(h->stream));
+    GridHeader hd;
+    H_TRY(hipMemcpy(&hd, h->grid.header.p, sizeof hd, hipMemcpyDeviceToHost));
+    if (hd.overflow || hd.stale) return fail(h, "internal: the index of a target that pcr_set_target settled is incomplete");
+    // a voxel is a cell of the index, stored at the position of the cell's first point (vgicp.hip: vgicp_voxel_kernel)
+    size_t kept = 0;
+    if (!hd.empty) {
+        std::vector<uint32_t> start((size_t)hd.n_cells + 1);
+        H_TRY(hipMemcpy(start.data(), h->grid.cell_start.p, start.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        const size_t n = start[hd.n_cells];
+        std::vector<VgicpVoxel> vox(out ? n : 0);
+        if (out && n) H_TRY(hipMemcpy(vox.data(), h->vg.vox.p, n * sizeof(VgicpVoxel), hipMemcpyDeviceToHost));
+        const uint32_t d0 = (uint32_t)hd.dims[0], d1 = (uint32_t)hd.dims[1];
+        for (size_t t = 0; t < (size_t)hd.n_cells; ++t) {
+            if (start[t + 1] <= start[t]) continue;
+            if (out && kept < capacity) {
+                const uint32_t row = (uint32_t)(t / d0), cz = row / d1;
+                const VgicpVoxel& v = vox[start[t]];
+                pcr_vgicp_voxel& o = out[kept];
+                // the lattice coordinate floor(p / res - 0.5): the cell's position in the box + the box's origin
+                o.ijk[0] = (int32_t)((uint32_t)t - row * d0) + (int32_t)hd.org[0]; o.ijk[1] = (int32_t)(row - cz * d1) + (int32_t)hd.org[1]; o.ijk[2] = (int32_t)cz + (int32_t)hd.org[2];
+                o.n = (int32_t)v.n;
+                memcpy(o.mean, v.mean, sizeof o.mean);
+                memcpy(o.cov, v.cov, sizeof o.cov);
+            }
+            ++kept;
+        }
+    }
+    if (count) *count = kept;
+    if (out && capacity < kept) return fail(h, "pcr_vgicp_voxels: room for " + std::to_string(capacity) + " voxels, the target has " + std::to_string(kept));
     return 0;
 }
 

@@ -71,6 +71,13 @@ protected:
         h_ = pcr_create(method, p);
         if (!h_) throw std::runtime_error(pcr_last_error(nullptr));
     }
+    // one int32 field of the live handle's parameters through pcr_get_params / pcr_set_params (a refused value throws)
+    void setField(int32_t pcr_params::*field, int value) {
+        pcr_params p;
+        if (pcr_get_params(h_, &p)) throw std::runtime_error(pcr_last_error(h_));
+        p.*field = value;
+        if (pcr_set_params(h_, &p)) throw std::runtime_error(pcr_last_error(h_));
+    }
 public:
     HipRegister(const HipRegister&) = delete;
     HipRegister& operator=(const HipRegister&) = delete;
@@ -298,6 +305,10 @@ public:
         p.vgicp_trans_eps = 1e-6;
         if (pcr_set_params(h_, &p)) throw std::runtime_error(pcr_last_error(h_));
     }
+    // fast_gicp::FastGICP::setRegularizationMethod / FastVGICP::setVoxelAccumulationMode (gicp_settings.hpp:6,10): PCR_REG_* / PCR_VOXEL_*.
+    // The prepared target is dropped when the value changes; a value out of range throws.
+    void setRegularizationMethod(int method) { setField(&pcr_params::vgicp_regularization, method); }
+    void setVoxelAccumulationMode(int mode) { setField(&pcr_params::vgicp_voxel_mode, mode); }
     scalar_t getFitnessScore() override { return pcr_fitness(h_); }
 };
 
@@ -315,6 +326,8 @@ public:
         p.gicp_max_corr_dist = 150.0;
         if (pcr_set_params(h_, &p)) throw std::runtime_error(pcr_last_error(h_));
     }
+    // fast_gicp::FastGICP::setRegularizationMethod (PCR_REG_*); the prepared target is dropped when the value changes
+    void setRegularizationMethod(int method) { setField(&pcr_params::vgicp_regularization, method); }
     scalar_t getFitnessScore() override { return pcr_fitness(h_); }
 };
 

@@ -40,7 +40,13 @@ class PcrParams(C.Structure):
         ("loam_coresident", C.c_int32), ("loam_clamp_margin_mm", C.c_int32), ("full_target", C.c_int32), ("host_optimiser", C.c_int32),
         ("host_copy_xyz", C.c_int32),
         ("gicp_max_corr_dist", C.c_double),
+        ("vgicp_regularization", C.c_int32), ("vgicp_voxel_mode", C.c_int32),
     ]
+
+
+# pcr_params.vgicp_regularization / vgicp_voxel_mode (include/pcr_hip.h: PCR_REG_*, PCR_VOXEL_*; fast_gicp's gicp_settings.hpp:6,10)
+REG_NONE, REG_MIN_EIG, REG_NORMALIZED_MIN_EIG, REG_PLANE, REG_FROBENIUS = range(5)
+VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = range(3)
 
 
 class PcrStats(C.Structure):
@@ -57,7 +63,7 @@ class PcrStats(C.Structure):
 ABI_SYMBOLS = [
     "pcr_default_params", "pcr_create", "pcr_destroy", "pcr_last_error", "pcr_scan2map", "pcr_scan2map_device", "pcr_host_pin", "pcr_host_unpin",
     "pcr_set_target", "pcr_align", "pcr_invalidate_target", "pcr_fitness", "pcr_loam_linearize", "pcr_get_trace", "pcr_get_trace_counts",
-    "pcr_vgicp_covariances", "pcr_vgicp_neighbours", "pcr_vgicp_linearize", "pcr_gicp_linearize", "pcr_voxel_filter", "pcr_voxel_filter_begin", "pcr_voxel_filter_end", "pcr_get_timeline", "pcr_ndt_derivatives", "pcr_ndt_voxels", "pcr_ndt_pass_sums", "pcr_get_stats", "pcr_set_profile", "pcr_set_stream", "pcr_set_query_tile", "pcr_comm_unique_id", "pcr_comm_init", "pcr_comm_info", "pcr_comm_peer_export", "pcr_comm_init_peer",
+    "pcr_vgicp_covariances", "pcr_vgicp_neighbours", "pcr_vgicp_linearize", "pcr_gicp_linearize", "pcr_voxel_filter", "pcr_voxel_filter_begin", "pcr_voxel_filter_end", "pcr_get_timeline", "pcr_ndt_derivatives", "pcr_ndt_voxels", "pcr_vgicp_voxels", "pcr_ndt_pass_sums", "pcr_get_stats", "pcr_set_profile", "pcr_set_stream", "pcr_set_query_tile", "pcr_comm_unique_id", "pcr_comm_init", "pcr_comm_info", "pcr_comm_peer_export", "pcr_comm_init_peer",
     "pcr_comm_init_host", "pcr_set_shard", "pcr_set_params", "pcr_get_params", "pcr_fitness_gated",
     "pcr_map_create", "pcr_map_destroy", "pcr_map_last_error", "pcr_map_add_keyframe", "pcr_map_keyframes", "pcr_map_clear", "pcr_map_update", "pcr_map_update_begin", "pcr_map_wait", "pcr_map_update_window", "pcr_map_submap",
     "pcr_map_submap_indices", "pcr_map_generation", "pcr_scan2map_submap",
@@ -149,6 +155,7 @@ def load_library():
     L.pcr_ndt_derivatives.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, dp, dp, dp, dp]
     L.pcr_get_timeline.argtypes = [vp, vp, C.c_size_t, ip, ip]
     L.pcr_ndt_voxels.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.pcr_vgicp_voxels.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.pcr_ndt_pass_sums.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, C.c_int, dp, dp, dp]
     L.pcr_voxel_filter.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_double, vp, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
     L.pcr_voxel_filter_begin.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_double, vp, C.c_size_t]
@@ -766,8 +773,25 @@ class NdtRegister(PointCloudRegister):
 
 
 class VgicpRegister(PointCloudRegister):
-    """PCR::VgicpRegister (reference PCR/src/VgicpRegister.cpp)."""
+    """PCR::VgicpRegister (reference PCR/src/VgicpRegister.cpp).  fast_gicp's two settings are keyword arguments like every other field of
+    pcr_params: vgicp_regularization=REG_* (FastGICP::setRegularizationMethod, default REG_PLANE) and vgicp_voxel_mode=VOXEL_*
+    (FastVGICP::setVoxelAccumulationMode, default VOXEL_ADDITIVE); set_params changes them on a live handle and drops the prepared target."""
     method = "vgicp"
+
+    def voxels(self):
+        """The Gaussian voxels of the kept target (setTarget; pcr_vgicp_voxels), sorted by (ix, iy, iz): dict(ijk (m, 3) int32 = the lattice
+        coordinates floor(p / res - 0.5), n (m,), mean (m, 3), cov (m, 3, 3)).  Raises on a handle whose target scan2Map prepared for one
+        scan's region."""
+        cnt = C.c_size_t(0)
+        self._check(self._lib.pcr_vgicp_voxels(self._h, None, 0, C.byref(cnt)))
+        rec = np.dtype([("ijk", np.int32, 3), ("n", np.int32), ("mean", np.float64, 3), ("cov6", np.float64, 6)])
+        assert rec.itemsize == 88
+        raw = np.zeros(cnt.value, rec)
+        if cnt.value:
+            self._check(self._lib.pcr_vgicp_voxels(self._h, raw.ctypes.data_as(C.c_void_p), raw.size, C.byref(cnt)))
+        raw = raw[np.lexsort((raw["ijk"][:, 2], raw["ijk"][:, 1], raw["ijk"][:, 0]))]
+        cov = raw["cov6"][:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
+        return dict(ijk=raw["ijk"].copy(), n=raw["n"].copy(), mean=raw["mean"].copy(), cov=cov.copy())
 
     def initForLC(self):
         """VgicpRegister::initForLC (VgicpRegister.cpp:21-28) on the live object, as LoopClosureManager's constructor calls it
@@ -807,7 +831,7 @@ class VgicpRegister(PointCloudRegister):
 class GicpRegister(PointCloudRegister):
     """PCR::VgicpRegister with fast_gicp::FastGICP as its registrar (fast_gicp_impl.hpp:103-237): correspondences by exact nearest
     neighbour, the two covariances fused per pair."""
-    method = "gicp"
+    method = "gicp"      # (vgicp_regularization=REG_* is read here too; vgicp_voxel_mode is ignored: there are no voxels)
     covariances = VgicpRegister.covariances      # (pcr_vgicp_covariances / pcr_vgicp_neighbours serve gicp handles: the same covariances)
     neighbours = VgicpRegister.neighbours
 
