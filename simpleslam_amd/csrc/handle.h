@@ -157,7 +157,6 @@ struct pcr_handle {
         pcr::DeviceBuf sums;                 // sharded device loop: the 48 sums of a pass, all-reduced in place
         pcr::host::Mapped<pcr::NdtOut> out;  // its result and progress word
         int count_idx = 0;
-        int last_passes = 8;             // passes the previous alignment took: how many are enqueued up front
         bool target_ready = false;       // (read by pcr_scan2map_submap; dropped by pcr_set_params, pcr_invalidate_target and query's fit_grid_for)
         int iters = 0, deriv = 0, hess = 0;
         double score = 0;
@@ -334,6 +333,8 @@ struct PaceRule {
     // a profiler does not force a synchronisation, and the session is checked after one.
     bool peer;
 };
+// the rule of every loop over the peer exchange (run_ndt, run_vgicp): nothing before the first look, three launches ahead
+static constexpr PaceRule kPeerPace{0, 3, 0, true};
 
 // Queue the passes of call `seq` by `rule` -- launch(i) queues pass i -- until the device loop writes `seq` into out->seq.
 // limit: the pass budget of the call; window_msg / budget_msg: the errors of a budget that exceeds the progress window, or

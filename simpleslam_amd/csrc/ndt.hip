@@ -679,6 +679,98 @@ __global__ __launch_bounds__(512) void ndt_ctl_store_kernel(NdtCtl* __restrict__
 static constexpr int kCtlWords = (int)((sizeof(NdtCtl) + 3) / 4);
 
 // ------------------------------------------------------------------------------
+// What every device loop puts around the state machine of ndt_opt.h: the fold of a pass's rows, the controller step spread over a
+// block, the result handed to the host.  All __forceinline__ (lsq_pass.h: a prologue in a function that returns to its caller
+// changed a kernel's schedule).
+// ------------------------------------------------------------------------------
+static constexpr int kFoldBlock = 768;
+static constexpr int kNdtFoldAll = -1;      // ndt_fold_rows: no masking rule (the host loop's fold: the host reads what its pass filled)
+
+// The fold of partials[nblocks][48] by a block of kFoldBlock threads, in a fixed order: 16 slices of 48 components, slice s adds the
+// rows s, s + 16, .. with 8 loads in flight, then the 16 slices are added in slice order.  Returns the component's sum in threads
+// t < 48 (zero in the others).  kind: the pass that wrote the rows -- a line-search pass fills 7 of the 48 slots, and slots >= 43 are
+// zero; kNdtPassNone reads nothing and gives zeros; kNdtFoldAll masks nothing.
+__device__ __forceinline__ double ndt_fold_rows(const double* __restrict__ partials, uint32_t nblocks, int kind, double* sh /* [16][48] */) {
+    const int t = threadIdx.x, comp = t % 48, slice = t / 48;
+    double acc = 0.0;
+    if (kind != kNdtPassNone) {
+        for (uint32_t b0 = slice; b0 < nblocks; b0 += 16 * 8) {
+            double v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { const uint32_t b = b0 + 16 * u; v[u] = b < nblocks ? partials[(size_t)b * 48 + comp] : 0.0; }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc += v[u];
+        }
+    }
+    sh[slice * 48 + comp] = acc;
+    __syncthreads();
+    double v = 0.0;
+    if (t < 48) {
+        v = sh[t];
+#pragma unroll
+        for (int s2 = 1; s2 < 16; ++s2) v += sh[s2 * 48 + t];
+        if (kind != kNdtFoldAll && ((kind == kNdtPassDeriv && t >= 7) || t >= kNdtComp)) v = 0.0;
+    }
+    return v;
+}
+
+// One step of the state machine by a block of kB threads: c = the state in LDS, sums = the 48 sums of the pass it asked for in LDS
+// (both written before a barrier).  The pass's 36 Hessian entries are taken in by lanes 1..36 of the wave whose lane 0 decides (same
+// wave: their LDS stores are queued before lane 0's loads of the Newton solve); six lanes evaluate the sine/cosine pairs; the pose
+// and the four parts of the angle tables take one lane of five waves.  (The parts of angle_tables_from_trig write disjoint rows
+// with the expressions of the whole: the tables do not depend on whether one lane computes them -- ndt_opt::ctl_tables, the host's
+// ctl_step -- or four.)  Ends with a barrier: every thread sees the next request in *c.
+template <int kB>
+__device__ __forceinline__ void ndt_ctl_step_block(NdtCtl* c, const double* sums) {
+    static_assert(kB >= 5 * 64, "pose and angle tables take five waves");
+    __shared__ double sh_sc[12];
+    __shared__ int sh_need;
+    const int t = threadIdx.x;
+    if (t >= 1 && t <= 36) c->hess[t - 1] = ndt_opt::ctl_hess_entry(c->kind, c->phase, sums, t - 1);
+    if (t == 0) sh_need = ndt_opt::ctl_decide(c, sums, true) ? 1 : 0;
+    __syncthreads();
+    if (sh_need) {
+        if (t < 6) {
+            double sc[2];
+            ndt_opt::trig_pair(c->x_t, t, sc);
+            sh_sc[2 * t] = sc[0]; sh_sc[2 * t + 1] = sc[1];
+        }
+        __syncthreads();
+        if ((t & 63) == 0) {
+            const int wave = t >> 6;
+            if (wave == 0) ndt_opt::pose_from_trig(c->x_t, sh_sc, &c->T);
+            else if (wave == 1) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 0);      // (a constant each: the other parts' rows are not compiled in)
+            else if (wave == 2) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 1);
+            else if (wave == 3) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 2);
+            else if (wave == 4) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 3);
+        }
+    }
+    __syncthreads();
+}
+
+// What ONE thread tells the host.  stepped (this launch took a step of the loop): the finished state, the index header's flags and the
+// escape counter with `seq` behind them -- or, with `progress`, the number of passes consumed so far (the host keeps its queue a fixed
+// number of passes ahead of it).  batch_mark (the RCCL loop): the end of a batch is marked whether or not the loop has finished: the
+// host decides only then whether another batch is due -- a decision every rank takes from the same state, so that all of them enqueue
+// the same collectives.
+__device__ __forceinline__ void ndt_publish(NdtOut* out, const NdtCtl* c, bool stepped, const GridHeader* hdr, const uint32_t* roi_escapes, double seq,
+                                            bool progress, int batch_mark = 0) {
+    if (stepped && c->done) {
+        out->final_T = c->final_T; out->score = c->score;
+        out->conv = c->conv; out->nr_it = c->nr_it; out->n_deriv = c->n_deriv; out->n_hess = c->n_hess; out->bail = c->bail; out->passes = c->passes;
+        out->grid_overflow = hdr->overflow; out->grid_empty = hdr->empty; out->grid_stale = hdr->stale; out->roi_escapes = roi_escapes ? (int32_t)min(*roi_escapes, 0x7fffffffu) : 0; out->grid_cells = hdr->n_cells;
+        __threadfence_system();
+        __hip_atomic_store(&out->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    } else if (stepped && progress) {
+        __hip_atomic_store(&out->progress, seq * kProgressWindow + (double)c->passes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (batch_mark) {
+        __threadfence_system();
+        __hip_atomic_store(&out->batch, seq * 65536.0 + 2.0 * (double)batch_mark + (c->done ? 1.0 : 0.0), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// ------------------------------------------------------------------------------
 // One launch per pass (the unsharded device loop).  A launch on this stream costs ~5 us of device time whatever it does, and a
 // fold/controller kernel would be a second one per pass: here its work is the PROLOGUE of the next pass instead -- every block
 // folds the rows of the previous launch and takes the controller step itself (same instructions on the same numbers: the blocks
@@ -727,13 +819,12 @@ __global__ __launch_bounds__(kProBlock, 1) void ndt_pass_pro_kernel(const NdtArg
     __shared__ double sh2[(kProBlock / 64) * 48 + 32];
     __shared__ __attribute__((aligned(16))) uint32_t sh_ctl[kCtlWords];
     __shared__ double sh_sums[48];
-    __shared__ double sh_sc[12];
-    __shared__ int sh_need;
     const int t = threadIdx.x;
     NdtCtl* const c = reinterpret_cast<NdtCtl*>(sh_ctl);
     // ONE round trip: the state and the rows of the previous launch, in the [10 slices][48 components] layout whatever that launch was
     // (since repeated line-search evaluations are no longer passes, most launches follow a pass with a Hessian; a line-search pass
-    // fills 7 of the 48 slots of a row and the rest is ignored)
+    // fills 7 of the 48 slots of a row and the rest is ignored).  Not ndt_fold_rows: 10 slices of 26 rows with the state's words requested
+    // beside them -- another order of additions, which the poses of this loop are pinned to
     const int comp = t % 48, slice = t / 48;      // 10 slices: t < 480
     double v[26];
 #pragma unroll
@@ -768,45 +859,10 @@ __global__ __launch_bounds__(kProBlock, 1) void ndt_pass_pro_kernel(const NdtArg
             sh_sums[t] = r;      // (a light pass leaves the Hessian slots at zero: ctl_decide does not read them)
         }
         __syncthreads();
-        // the pass's 36 Hessian entries are taken in by lanes 1..36 of the wave whose lane 0 decides (same wave: their LDS stores are queued before
-        // lane 0's loads of the Newton solve)
-        if (t >= 1 && t <= 36) c->hess[t - 1] = ndt_opt::ctl_hess_entry(c->kind, c->phase, sh_sums, t - 1);
-        if (t == 0) sh_need = ndt_opt::ctl_decide(c, sh_sums, true) ? 1 : 0;
-        __syncthreads();
-        if (sh_need) {
-            if (t < 6) {
-                double sc[2];
-                ndt_opt::trig_pair(c->x_t, t, sc);
-                sh_sc[2 * t] = sc[0]; sh_sc[2 * t + 1] = sc[1];
-            }
-            __syncthreads();
-            // pose and the four parts of the angle tables: five waves, one lane each
-            if ((t & 63) == 0) {
-                const int wave = t >> 6;
-                if (wave == 0) ndt_opt::pose_from_trig(c->x_t, sh_sc, &c->T);
-                else if (wave == 1) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 0);
-                else if (wave == 2) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 1);
-                else if (wave == 3) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 2);
-                else if (wave == 4) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 3);
-            }
-            __syncthreads();
-        }
-        __syncthreads();
+        ndt_ctl_step_block<kProBlock>(c, sh_sums);
         if (blockIdx.x == 0) {
             for (int w = t; w < kCtlWords; w += kProBlock) reinterpret_cast<uint32_t*>(pa.ctl_next)[w] = sh_ctl[w];
-            if (t == 0) {
-                NdtOut* const out = pa.out;
-                if (c->done) {
-                    const GridHeader* hdr = a.hdr;
-                    out->final_T = c->final_T; out->score = c->score;
-                    out->conv = c->conv; out->nr_it = c->nr_it; out->n_deriv = c->n_deriv; out->n_hess = c->n_hess; out->bail = c->bail; out->passes = c->passes;
-                    out->grid_overflow = hdr->overflow; out->grid_empty = hdr->empty; out->grid_stale = hdr->stale; out->roi_escapes = a.roi_escapes ? (int32_t)min(*a.roi_escapes, 0x7fffffffu) : 0; out->grid_cells = hdr->n_cells;
-                    __threadfence_system();
-                    __hip_atomic_store(&out->seq, pa.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                } else {
-                    __hip_atomic_store(&out->progress, pa.seq * kProgressWindow + (double)c->passes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-            }
+            if (t == 0) ndt_publish(pa.out, c, true, a.hdr, a.roi_escapes, pa.seq, true);
         }
         if (c->done) return;
     }
@@ -833,75 +889,30 @@ __global__ __launch_bounds__(kProBlock, 1) void ndt_pass_pro_kernel(const NdtArg
 // a device buffer), all-reduce, ndt_ctl_kernel (one step of the state machine on the summed values).  Every rank holds the same
 // controller state and feeds it the same sums: the ranks decide alike and stay in step without ever talking about it.
 // ------------------------------------------------------------------------------
-__global__ __launch_bounds__(768) void ndt_fold_kernel(const double* __restrict__ partials, uint32_t nblocks, const NdtCtl* __restrict__ ctl,
-                                                       double* __restrict__ sums48) {
+__global__ __launch_bounds__(kFoldBlock) void ndt_fold_kernel(const double* __restrict__ partials, uint32_t nblocks, const NdtCtl* __restrict__ ctl,
+                                                              double* __restrict__ sums48) {
     __shared__ double sh[16 * 48];
-    const int t = threadIdx.x, comp = t % 48, slice = t / 48;
-    const int kind = ctl->done ? kNdtPassNone : ctl->kind;
     // (a pass enqueued beyond the end still takes part in the collective that follows: with zeros)
-    double acc = 0.0;
-    if (kind != kNdtPassNone) {
-        for (uint32_t b0 = slice; b0 < nblocks; b0 += 16 * 8) {
-            double v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { const uint32_t b = b0 + 16 * u; v[u] = b < nblocks ? partials[(size_t)b * 48 + comp] : 0.0; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc += v[u];
-        }
-    }
-    sh[slice * 48 + comp] = acc;
-    __syncthreads();
-    if (t < 48) {
-        double v = sh[t];
-#pragma unroll
-        for (int s2 = 1; s2 < 16; ++s2) v += sh[s2 * 48 + t];
-        // a line-search pass fills 7 of the 48 slots of every block; the others hold what an earlier pass left there
-        sums48[t] = (kind == kNdtPassDeriv && t >= 7) || t >= kNdtComp ? 0.0 : v;
-    }
+    const double v = ndt_fold_rows(partials, nblocks, ctl->done ? kNdtPassNone : ctl->kind, sh);
+    if (threadIdx.x < 48) sums48[threadIdx.x] = v;
 }
 
-__global__ __launch_bounds__(64) void ndt_ctl_kernel(NdtCtl* __restrict__ ctl, const double* __restrict__ sums48, const GridHeader* __restrict__ hdr,
-                                                     NdtOut* __restrict__ out, double seq, int batch_mark, const uint32_t* __restrict__ roi_escapes) {
+static constexpr int kCtlBlock = 5 * 64;      // ndt_ctl_step_block's five waves
+__global__ __launch_bounds__(kCtlBlock) void ndt_ctl_kernel(NdtCtl* __restrict__ ctl, const double* __restrict__ sums48, const GridHeader* __restrict__ hdr,
+                                                            NdtOut* __restrict__ out, double seq, int batch_mark, const uint32_t* __restrict__ roi_escapes) {
     __shared__ double sh_sums[48];
-    __shared__ double sh_sc[12];
-    __shared__ int sh_need;
     __shared__ __attribute__((aligned(16))) uint32_t sh_ctl[kCtlWords];
     const int t = threadIdx.x;
+    NdtCtl* const c = reinterpret_cast<NdtCtl*>(sh_ctl);
     const int done_in = ctl->done;
     if (!done_in) {
-        for (int w = t; w < kCtlWords; w += 64) sh_ctl[w] = reinterpret_cast<const uint32_t*>(ctl)[w];
+        for (int w = t; w < kCtlWords; w += kCtlBlock) sh_ctl[w] = reinterpret_cast<const uint32_t*>(ctl)[w];
         if (t < 48) sh_sums[t] = sums48[t];
         __syncthreads();
-        if (t == 0) sh_need = ndt_opt::ctl_decide(reinterpret_cast<NdtCtl*>(sh_ctl), sh_sums) ? 1 : 0;
-        __syncthreads();
-        if (sh_need) {
-            if (t < 6) {
-                double sc[2];
-                ndt_opt::trig_pair(reinterpret_cast<const NdtCtl*>(sh_ctl)->x_t, t, sc);
-                sh_sc[2 * t] = sc[0]; sh_sc[2 * t + 1] = sc[1];
-            }
-            __syncthreads();
-            if (t == 0) ndt_opt::ctl_tables(reinterpret_cast<NdtCtl*>(sh_ctl), sh_sc);
-        }
-        __syncthreads();
-        for (int w = t; w < kCtlWords; w += 64) reinterpret_cast<uint32_t*>(ctl)[w] = sh_ctl[w];
+        ndt_ctl_step_block<kCtlBlock>(c, sh_sums);
+        for (int w = t; w < kCtlWords; w += kCtlBlock) reinterpret_cast<uint32_t*>(ctl)[w] = sh_ctl[w];
     }
-    if (t == 0) {
-        const NdtCtl* c = done_in ? ctl : reinterpret_cast<const NdtCtl*>(sh_ctl);
-        if (c->done && !done_in) {
-            out->final_T = c->final_T; out->score = c->score;
-            out->conv = c->conv; out->nr_it = c->nr_it; out->n_deriv = c->n_deriv; out->n_hess = c->n_hess; out->bail = c->bail; out->passes = c->passes;
-            out->grid_overflow = hdr->overflow; out->grid_empty = hdr->empty; out->grid_stale = hdr->stale; out->roi_escapes = roi_escapes ? (int32_t)min(*roi_escapes, 0x7fffffffu) : 0; out->grid_cells = hdr->n_cells;
-            __threadfence_system();
-            __hip_atomic_store(&out->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        // the end of a batch is marked whether or not the loop has finished: the host decides only then whether another batch is
-        // due -- a decision every rank takes from the same state, so that all of them enqueue the same collectives
-        if (batch_mark) {
-            __threadfence_system();
-            __hip_atomic_store(&out->batch, seq * 65536.0 + 2.0 * (double)batch_mark + (c->done ? 1.0 : 0.0), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    if (t == 0) ndt_publish(out, done_in ? ctl : c, !done_in, hdr, roi_escapes, seq, false, batch_mark);
 }
 
 // Sharded targets over the PEER exchange (pcr_comm_init_peer): the three pieces above in ONE launch -- this rank's rows folded, the 48 sums pushed
@@ -910,107 +921,38 @@ __global__ __launch_bounds__(64) void ndt_ctl_kernel(NdtCtl* __restrict__ ctl, c
 // host-supplied collective a round trip through the host per pass.  Every rank holds the same controller state and gets the same bits out of the
 // exchange: the ranks decide alike.  A launch queued beyond the end of the optimisation exchanges nothing (every rank's `done` flips in the same
 // launch; sequence numbers are per enqueued launch, so the ones that follow still agree).
-__global__ __launch_bounds__(768) void ndt_fold_exchange_ctl_kernel(const double* __restrict__ partials, uint32_t nblocks, NdtCtl* __restrict__ ctl, const PeerComm pc,
-                                                                    const double xseq, const GridHeader* __restrict__ hdr, NdtOut* __restrict__ out, double seq,
-                                                                    int batch_mark, const uint32_t* __restrict__ roi_escapes) {
+__global__ __launch_bounds__(kFoldBlock) void ndt_fold_exchange_ctl_kernel(const double* __restrict__ partials, uint32_t nblocks, NdtCtl* __restrict__ ctl, const PeerComm pc,
+                                                                           const double xseq, const GridHeader* __restrict__ hdr, NdtOut* __restrict__ out, double seq,
+                                                                           const uint32_t* __restrict__ roi_escapes) {
     __shared__ double sh[16 * 48];
     __shared__ double sh_sums[64];
-    __shared__ double sh_sc[12];
-    __shared__ int sh_need, sh_fail;
+    __shared__ int sh_fail;
     __shared__ __attribute__((aligned(16))) uint32_t sh_ctl[kCtlWords];
-    const int t = threadIdx.x, comp = t % 48, slice = t / 48;
-    const int done_in = ctl->done;
-    if (!done_in) {
-        const int kind = ctl->kind;
-        for (int w = t; w < kCtlWords; w += 768) sh_ctl[w] = reinterpret_cast<const uint32_t*>(ctl)[w];
-        double acc = 0.0;
-        if (kind != kNdtPassNone) {
-            for (uint32_t b0 = slice; b0 < nblocks; b0 += 16 * 8) {
-                double v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { const uint32_t b = b0 + 16 * u; v[u] = b < nblocks ? partials[(size_t)b * 48 + comp] : 0.0; }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) acc += v[u];
-            }
-        }
-        sh[slice * 48 + comp] = acc;
+    const int t = threadIdx.x;
+    NdtCtl* const c = reinterpret_cast<NdtCtl*>(sh_ctl);
+    if (ctl->done) return;
+    for (int w = t; w < kCtlWords; w += kFoldBlock) sh_ctl[w] = reinterpret_cast<const uint32_t*>(ctl)[w];
+    const double mine = ndt_fold_rows(partials, nblocks, ctl->kind, sh);
+    const bool ok = peer_exchange_block(pc, xseq, nullptr, mine, 48, 0, sh_sums);
+    if (t == 0) sh_fail = ok ? 0 : 1;
+    __syncthreads();
+    if (sh_fail) {      // a rank never arrived (the status word says so to the host): the loop ends here, on every rank that waited
+        if (t == 0) { c->done = 1; c->bail = 0; c->conv = 0; c->kind = kNdtPassNone; }
         __syncthreads();
-        double mine = 0.0;
-        if (t < 48) {
-            double v = sh[t];
-#pragma unroll
-            for (int s2 = 1; s2 < 16; ++s2) v += sh[s2 * 48 + t];
-            // a line-search pass fills 7 of the 48 slots of every block; the others hold what an earlier pass left there
-            mine = (kind == kNdtPassDeriv && t >= 7) || t >= kNdtComp ? 0.0 : v;
-        }
-        const bool ok = peer_exchange_block(pc, xseq, nullptr, mine, 48, 0, sh_sums);
-        if (t == 0) sh_fail = ok ? 0 : 1;
-        __syncthreads();
-        if (sh_fail) {      // a rank never arrived (the status word says so to the host): the loop ends here, on every rank that waited
-            if (t == 0) { NdtCtl* c = reinterpret_cast<NdtCtl*>(sh_ctl); c->done = 1; c->bail = 0; c->conv = 0; c->kind = kNdtPassNone; }
-        } else {
-            NdtCtl* const c = reinterpret_cast<NdtCtl*>(sh_ctl);
-            if (t >= 1 && t <= 36) c->hess[t - 1] = ndt_opt::ctl_hess_entry(c->kind, c->phase, sh_sums, t - 1);      // (lanes of the deciding lane's wave: see ndt_pass_pro_kernel)
-            if (t == 0) sh_need = ndt_opt::ctl_decide(c, sh_sums, true) ? 1 : 0;
-            __syncthreads();
-            if (sh_need) {
-                if (t < 6) {
-                    double sc[2];
-                    ndt_opt::trig_pair(c->x_t, t, sc);
-                    sh_sc[2 * t] = sc[0]; sh_sc[2 * t + 1] = sc[1];
-                }
-                __syncthreads();
-                // pose and the four parts of the angle tables: five waves, one lane each
-                if ((t & 63) == 0) {
-                    const int wave = t >> 6;
-                    if (wave == 0) ndt_opt::pose_from_trig(c->x_t, sh_sc, &c->T);
-                    else if (wave == 1) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 0);
-                    else if (wave == 2) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 1);
-                    else if (wave == 3) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 2);
-                    else if (wave == 4) ndt_opt::angle_tables_from_trig(sh_sc, &c->ang, 3);
-                }
-            }
-        }
-        __syncthreads();
-        for (int w = t; w < kCtlWords; w += 768) reinterpret_cast<uint32_t*>(ctl)[w] = sh_ctl[w];
+    } else {
+        ndt_ctl_step_block<kFoldBlock>(c, sh_sums);
     }
-    if (t == 0) {
-        const NdtCtl* c = done_in ? ctl : reinterpret_cast<const NdtCtl*>(sh_ctl);
-        if (c->done && !done_in) {
-            out->final_T = c->final_T; out->score = c->score;
-            out->conv = c->conv; out->nr_it = c->nr_it; out->n_deriv = c->n_deriv; out->n_hess = c->n_hess; out->bail = c->bail; out->passes = c->passes;
-            out->grid_overflow = hdr->overflow; out->grid_empty = hdr->empty; out->grid_stale = hdr->stale; out->roi_escapes = roi_escapes ? (int32_t)min(*roi_escapes, 0x7fffffffu) : 0; out->grid_cells = hdr->n_cells;
-            __threadfence_system();
-            __hip_atomic_store(&out->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        else if (!c->done) __hip_atomic_store(&out->progress, seq * kProgressWindow + (double)c->passes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (the host keeps its queue a fixed number of passes ahead of this)
-        if (batch_mark) {
-            __threadfence_system();
-            __hip_atomic_store(&out->batch, seq * 65536.0 + 2.0 * (double)batch_mark + (c->done ? 1.0 : 0.0), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    for (int w = t; w < kCtlWords; w += kFoldBlock) reinterpret_cast<uint32_t*>(ctl)[w] = sh_ctl[w];
+    if (t == 0) ndt_publish(out, c, true, hdr, roi_escapes, seq, true);
 }
 
-// fold per-block partials (48 doubles each) into 48 doubles, fixed order; 16 slices of 48 components, each
-// slice keeps 8 independent loads in flight
-// out lives in host-mapped memory: out[47] receives `seq` LAST (system-scope release), the word the host spins on
-__global__ __launch_bounds__(768) void ndt_sum_partials_kernel(const double* __restrict__ partials, uint32_t nblocks, double* __restrict__ out, double seq) {
+// The host loop's fold: all 48 components as they are, into host-mapped memory: out[47] receives `seq` LAST (system-scope release), the
+// word the host spins on
+__global__ __launch_bounds__(kFoldBlock) void ndt_sum_partials_kernel(const double* __restrict__ partials, uint32_t nblocks, double* __restrict__ out, double seq) {
     __shared__ double sh[16 * 48];
-    const int t = threadIdx.x, comp = t % 48, slice = t / 48;
-    double acc = 0.0;
-    for (uint32_t b0 = slice; b0 < nblocks; b0 += 16 * 8) {
-        double v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { const uint32_t b = b0 + 16 * u; v[u] = b < nblocks ? partials[(size_t)b * 48 + comp] : 0.0; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += v[u];
-    }
-    sh[slice * 48 + comp] = acc;
-    __syncthreads();
+    const int t = threadIdx.x;
+    const double v = ndt_fold_rows(partials, nblocks, kNdtFoldAll, sh);
     if (t < 47) {
-        double v = sh[t];
-#pragma unroll
-        for (int s2 = 1; s2 < 16; ++s2) v += sh[s2 * 48 + t];
         out[t] = v;
         __threadfence_system();
     }
@@ -1041,7 +983,7 @@ hipError_t ndt_launch_derivatives(const NdtArgs& a, const NdtPose& T, const NdtA
     const uint32_t nb = ndt_blocks(a.n_src);
     if (compute_hessian) hipLaunchKernelGGL((ndt_derivatives_kernel<true>), dim3(nb), dim3(kNdtBlock), 0, s, a, T, ang);
     else hipLaunchKernelGGL((ndt_derivatives_kernel<false>), dim3(nb), dim3(kNdtBlock), 0, s, a, T, ang);
-    hipLaunchKernelGGL(ndt_sum_partials_kernel, dim3(1), dim3(768), 0, s, a.partials, nb, d_out48, seq);
+    hipLaunchKernelGGL(ndt_sum_partials_kernel, dim3(1), dim3(kFoldBlock), 0, s, a.partials, nb, d_out48, seq);
     return hipGetLastError();
 }
 
@@ -1094,25 +1036,25 @@ hipError_t ndt_launch_pass_pro(const NdtArgs& a_in, NdtCtl* d_ctl2, double* d_ro
 hipError_t ndt_launch_pass_fold(const NdtArgs& a, NdtCtl* d_ctl, double* d_sums48, hipStream_t s) {
     const uint32_t nb = ndt_blocks(a.n_src);
     hipLaunchKernelGGL(ndt_pass_kernel, dim3(nb), dim3(kNdtBlock), 0, s, a, d_ctl);
-    hipLaunchKernelGGL(ndt_fold_kernel, dim3(1), dim3(768), 0, s, a.partials, nb, d_ctl, d_sums48);
+    hipLaunchKernelGGL(ndt_fold_kernel, dim3(1), dim3(kFoldBlock), 0, s, a.partials, nb, d_ctl, d_sums48);
     return hipGetLastError();
 }
 // one pass of the sharded loop over the peer exchange: the evaluation, then fold + exchange + controller step in one launch
-hipError_t ndt_launch_pass_peer(const NdtArgs& a, NdtCtl* d_ctl, const PeerComm& pc, double xseq, NdtOut* d_out, hipStream_t s, double seq, int batch_mark) {
+hipError_t ndt_launch_pass_peer(const NdtArgs& a, NdtCtl* d_ctl, const PeerComm& pc, double xseq, NdtOut* d_out, hipStream_t s, double seq) {
     const uint32_t nb = ndt_blocks(a.n_src);
     hipLaunchKernelGGL(ndt_pass_kernel, dim3(nb), dim3(kNdtBlock), 0, s, a, d_ctl);
-    hipLaunchKernelGGL(ndt_fold_exchange_ctl_kernel, dim3(1), dim3(768), 0, s, a.partials, nb, d_ctl, pc, xseq, a.hdr, d_out, seq, batch_mark, (const uint32_t*)a.roi_escapes);
+    hipLaunchKernelGGL(ndt_fold_exchange_ctl_kernel, dim3(1), dim3(kFoldBlock), 0, s, a.partials, nb, d_ctl, pc, xseq, a.hdr, d_out, seq, (const uint32_t*)a.roi_escapes);
     return hipGetLastError();
 }
 hipError_t ndt_launch_ctl(const NdtArgs& a, NdtCtl* d_ctl, const double* d_sums48, NdtOut* d_out, hipStream_t s, double seq, int batch_mark) {
-    hipLaunchKernelGGL(ndt_ctl_kernel, dim3(1), dim3(64), 0, s, d_ctl, d_sums48, a.hdr, d_out, seq, batch_mark, (const uint32_t*)a.roi_escapes);
+    hipLaunchKernelGGL(ndt_ctl_kernel, dim3(1), dim3(kCtlBlock), 0, s, d_ctl, d_sums48, a.hdr, d_out, seq, batch_mark, (const uint32_t*)a.roi_escapes);
     return hipGetLastError();
 }
 
 hipError_t ndt_launch_hessian(const NdtArgs& a, const NdtPose& T, const NdtAngles& ang, double* d_out48, hipStream_t s, double seq) {
     const uint32_t nb = ndt_blocks(a.n_src);
     hipLaunchKernelGGL(ndt_hessian_kernel, dim3(nb), dim3(kNdtBlock), 0, s, a, T, ang);
-    hipLaunchKernelGGL(ndt_sum_partials_kernel, dim3(1), dim3(768), 0, s, a.partials, nb, d_out48, seq);
+    hipLaunchKernelGGL(ndt_sum_partials_kernel, dim3(1), dim3(kFoldBlock), 0, s, a.partials, nb, d_out48, seq);
     return hipGetLastError();
 }
 

@@ -97,9 +97,6 @@ void euler_xyz(const float R[9], float out[3]) {
 }
 }  // namespace ndt_host
 
-struct NdtRun {
-    pcr_handle* h; NdtArgs a; NdtPose T; NdtAngles ang;
-};
 // the guess as the optimiser starts from it: handed over as Matrix4f (NdtRegister.cpp:27), its Euler angles as the parameters
 // (ndt_omp_impl.hpp:103-111)
 void ndt_initial_pose(const double pose[16], NdtPose* T0, double p0[6]) {
@@ -134,32 +131,24 @@ NdtArgs ndt_args(const pcr_handle* h, const float* d_src, size_t n_src, size_t s
     return a;
 }
 
-// computeDerivatives at parameters p with the cloud transformed by T: score, gradient, Hessian
-int ndt_derivatives(NdtRun* r, const double p[6], bool compute_hessian, double* score, double grad[6], double hess[36]) {
-    pcr_handle* h = r->h;
-    ndt_host::angle_derivatives(p, &r->ang);
-    if (r->a.n_src == 0) { *score = 0; memset(grad, 0, 6 * sizeof(double)); memset(hess, 0, 36 * sizeof(double)); return 0; }
+// One evaluation pass of the host-driven loop: the kernel `kind` names at pose T, the fold, the ranks' sum.
+int ndt_host_pass(pcr_handle* h, const NdtArgs& a, int kind, const NdtPose& T, const NdtAngles& ang, double sums[43]) {
     h->seq += 1.0;
-    H_TRY(ndt_launch_derivatives(r->a, r->T, r->ang, compute_hessian ? 1 : 0, h->nd.out48.dev, h->stream, h->seq));
-    if (wait_result(h, &h->nd.out48.host[47], h->seq)) return 1;
-    if (sharded(h) && ranks_allreduce(h, h->nd.out48.host, 43)) return 1;      // score, gradient, Hessian summed over the ranks' tiles
-    ++h->nd.deriv;
-    *score = h->nd.out48.host[0];
-    for (int i = 0; i < 6; ++i) grad[i] = h->nd.out48.host[1 + i];
-    for (int i = 0; i < 36; ++i) hess[i] = compute_hessian ? h->nd.out48.host[7 + i] : 0.0;
-    return 0;
-}
-
-// One evaluation pass of the host-driven loop: the kernel the controller asked for, the fold, the ranks' sum.
-int ndt_host_pass(NdtRun* r, const NdtCtl& c, double sums[43]) {
-    pcr_handle* h = r->h;
-    h->seq += 1.0;
-    if (c.kind == kNdtPassHessian) H_TRY(ndt_launch_hessian(r->a, c.T, c.ang, h->nd.out48.dev, h->stream, h->seq));
-    else H_TRY(ndt_launch_derivatives(r->a, c.T, c.ang, c.kind == kNdtPassDerivH ? 1 : 0, h->nd.out48.dev, h->stream, h->seq));
+    if (kind == kNdtPassHessian) H_TRY(ndt_launch_hessian(a, T, ang, h->nd.out48.dev, h->stream, h->seq));
+    else H_TRY(ndt_launch_derivatives(a, T, ang, kind == kNdtPassDerivH ? 1 : 0, h->nd.out48.dev, h->stream, h->seq));
     if (wait_result(h, &h->nd.out48.host[47], h->seq)) return 1;
     if (sharded(h) && ranks_allreduce(h, h->nd.out48.host, 43)) return 1;      // score, gradient, Hessian summed over the ranks' tiles
     for (int i = 0; i < 43; ++i) sums[i] = h->nd.out48.host[i];
     return 0;
+}
+
+// computeDerivatives (with the Hessian) at parameters p with the cloud transformed by T: the 43 sums, and the angle tables of p
+int ndt_derivatives(pcr_handle* h, const NdtArgs& a, const NdtPose& T, const double p[6], NdtAngles* ang, double sums[43]) {
+    ndt_host::angle_derivatives(p, ang);
+    memset(sums, 0, 43 * sizeof(double));      // (an empty scan sums nothing)
+    if (a.n_src == 0) return 0;
+    ++h->nd.deriv;
+    return ndt_host_pass(h, a, kNdtPassDerivH, T, *ang, sums);
 }
 
 }  // namespace
@@ -179,62 +168,64 @@ int ndt_ride_initial_state(pcr_handle* h, const double pose[16]) {
     return 0;
 }
 
-int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) {
-    using namespace ndt_host;
-    static constexpr const char *kWindowMsg = "ndt_max_iters exceeds the device loop's pass window (2^20 passes)",
-                                *kBudgetMsg = "ndt: the optimiser did not finish within its pass budget";
-    if (!h->nd.target_ready) return fail(h, "no target prepared");
-    if (n_src > kMaxPoints) return fail(h, "source cloud too large");
-    H_TRY(h->nd.out48.ensure(48));
-    H_TRY(h->nd.out.ensure());
-    H_TRY(h->nd.partials.reserve((size_t)1024 * 48 * sizeof(double)));      // (one buffer of 1024 rows, or the two of 256 of the one-launch-per-pass loop)
-    H_TRY(h->nd.ctl.reserve(2 * sizeof(NdtCtl)));
-    NdtRun r;
-    r.h = h;
-    r.a = ndt_args(h, d_src, n_src, stride_floats);
-    r.a.roi_escapes = roi_view(h).escapes;      // (nullptr unless the target was prepared for one scan)
-    r.a.pair_count = prof_counters(h);
-    h->nd.iters = h->nd.deriv = h->nd.hess = 0;
-    NdtPose T0;
-    double p0[6];
-    ndt_initial_pose(pose, &T0, p0);
+// Each of run_ndt's three loops hands the driver an NdtOut: a device loop the one it reported in, the host loop what it has of it (pose,
+// verdict, counters).  bail: a device loop met a (nearly) singular Newton system and the host loop decides, with the SVD.
+static constexpr const char *kNdtWindowMsg = "ndt_max_iters exceeds the device loop's pass window (2^20 passes)",
+                            *kNdtBudgetMsg = "ndt: the optimiser did not finish within its pass budget";
 
-    NdtPose final_T = T0;
-    int conv = 0, nr_it = 0;
-    double score = 0;
-    // ---- device-resident loop: passes are enqueued ahead of the device, the host watches a progress word.  Not for sharded
-    // targets (every pass's sums cross the ranks through the host) and not when pcr_params.host_optimiser asks for the host loop ----
-    // Sharded over RCCL the loop stays on the device as well: fold -> ncclAllReduce on the handle's stream -> controller step, in
-    // batches of a fixed number of passes -- whether another batch is due is decided from the controller state the ranks share, so
-    // every rank enqueues the same collectives.  (A host-supplied collective needs the host in every pass: the host loop below.)
-    // Sharded over the peer exchange (pcr_comm_init_peer) likewise, two launches per pass: the evaluation, then fold + exchange + controller step
-    // in one (ndt.hip: ndt_fold_exchange_ctl_kernel).
-    const bool dev_sharded = sharded(h) && (h->comm.rccl || h->comm.peer_on) && !h->comm.host_ar && n_src > 0 && h->prm.host_optimiser == 0;
-    bool on_device = n_src > 0 && !sharded(h) && h->prm.host_optimiser == 0;
-    if (h->roi_on && !on_device) return fail(h, "internal: a target prepared for one scan needs the device-resident loop");
-    h->nd_grid_checked = false; h->nd_grid_bad = false;
-    bool sharded_done = false;
-    if (dev_sharded) {
-        NdtCtl* d_ctl = h->nd.ctl.as<NdtCtl>();
-        NdtOut* out = h->nd.out.host;
-        H_TRY(h->nd.sums.reserve(64 * sizeof(double)));
-        h->seq += 1.0;
-        const double seq = h->seq;
-        H_TRY(ndt_launch_ctl_init(d_ctl, T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters, h->stream, h->prm.ndt_evaluate_repeats));
-        const int limit = (h->prm.ndt_max_iters + 3) * 13 + 4, kBatch = 6;
+// The device-resident loop of an unsharded handle: one launch per pass (ndt.hip: ndt_pass_pro_kernel), enqueued ahead of the device while
+// the host watches a progress word.
+static int ndt_loop_device(pcr_handle* h, const NdtArgs& a, const NdtPose& T0, const double p0[6], NdtOut* res) {
+    NdtCtl* d_ctl = h->nd.ctl.as<NdtCtl>();
+    NdtOut* out = h->nd.out.host;
+    const double seq = (h->seq += 1.0);
+    // (a scan2map call whose region was marked has stored this state with the mark pass: do_scan2map, BlobStore)
+    const bool stored = h->blob_stored && h->roi_on;
+    h->blob_stored = false;
+    if (!stored) H_TRY(ndt_launch_ctl_init(d_ctl, T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters, h->stream, h->prm.ndt_evaluate_repeats,
+                                           a.roi_escapes));
+    const int limit = (h->prm.ndt_max_iters + 3) * 13 + 5;        // an iteration takes at most 1 + 10 + 1 passes; one launch more finishes
+    auto launch = [&](long i) -> hipError_t {
+        const int index = (int)i;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        if (h->profile >= 2) {      // events at every launch's own begin and end (pcr_stats.kernel_ms)
+            while ((int)h->ev_kernel.size() < 2 * (index + 1)) { hipEvent_t e; hipError_t er = hipEventCreate(&e); if (er != hipSuccess) return er; h->ev_kernel.push_back(e); }
+            h->nd_prof_launches = index + 1; ev[0] = h->ev_kernel[2 * index]; ev[1] = h->ev_kernel[2 * index + 1];
+        }
+        return ndt_launch_pass_pro(a, d_ctl, h->nd.partials.as<double>(), h->nd.out.dev, h->stream, seq, index, ev[0], ev[1]);
+    };
+    // (the host enqueues a pass in a quarter of the time the device needs for one: it only has to stay two ahead -- a pass enqueued beyond
+    //  the end costs ~10 us of device time)
+    static constexpr PaceRule kRule{3, 2, 4, false};
+    if (pace_passes(h, out, seq, limit, kRule, kNdtWindowMsg, kNdtBudgetMsg, launch)) return 1;
+    *res = *out;
+    return 0;
+}
+
+// The device-resident loop of a sharded handle, two launches per pass or three: over the peer exchange (pcr_comm_init_peer) the evaluation, then
+// fold + exchange + controller step in one (ndt.hip: ndt_fold_exchange_ctl_kernel), paced like the unsharded loop; over RCCL fold -> ncclAllReduce
+// on the handle's stream -> controller step, in batches of a fixed number of passes -- whether another batch is due is decided from the
+// controller state the ranks share, so every rank enqueues the same collectives.  (A host-supplied collective needs the host in every
+// pass: the host loop.)
+static int ndt_loop_device_sharded(pcr_handle* h, const NdtArgs& a, const NdtPose& T0, const double p0[6], NdtOut* res) {
+    NdtCtl* d_ctl = h->nd.ctl.as<NdtCtl>();
+    NdtOut* out = h->nd.out.host;
+    H_TRY(h->nd.sums.reserve(64 * sizeof(double)));
+    const double seq = (h->seq += 1.0);
+    H_TRY(ndt_launch_ctl_init(d_ctl, T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters, h->stream, h->prm.ndt_evaluate_repeats));
+    const int limit = (h->prm.ndt_max_iters + 3) * 13 + 4, kBatch = 6;
+    if (h->comm.peer_on) {
+        // passes are queued a fixed number ahead of the progress word, one at a time -- by the rule that leaves every rank with the same number of
+        // launches queued (PaceRule::peer): the ranks' sequence numbers, one per launch, agree in the next call too.
+        auto launch = [&](long) -> hipError_t { h->comm.peer_seq += 1.0; return ndt_launch_pass_peer(a, d_ctl, h->comm.peer, h->comm.peer_seq, h->nd.out.dev, h->stream, seq); };
+        if (pace_passes(h, out, seq, limit, kPeerPace, kNdtWindowMsg, kNdtBudgetMsg, launch)) return 1;
+    } else {
         const volatile double* f_batch = &out->batch;
-        if (h->comm.peer_on) {
-            // Peer exchange: passes are queued a fixed number ahead of the progress word, one at a time, like the unsharded loop -- by the rule that
-            // leaves every rank with the same number of launches queued (PaceRule::peer): the ranks' sequence numbers, one per launch, agree in the next call too.
-            auto launch = [&](long) -> hipError_t { h->comm.peer_seq += 1.0; return ndt_launch_pass_peer(r.a, d_ctl, h->comm.peer, h->comm.peer_seq, h->nd.out.dev, h->stream, seq, 0); };
-            static constexpr PaceRule kPeerRule{0, 3, 0, true};
-            if (pace_passes(h, out, seq, limit, kPeerRule, kWindowMsg, kBudgetMsg, launch)) return 1;
-        } else
         for (int batch = 1, enq = 0;; ++batch) {
             for (int b = 0; b < kBatch; ++b, ++enq) {
-                H_TRY(ndt_launch_pass_fold(r.a, d_ctl, h->nd.sums.as<double>(), h->stream));      // (a rank with an empty scan still folds zeros and takes part)
+                H_TRY(ndt_launch_pass_fold(a, d_ctl, h->nd.sums.as<double>(), h->stream));      // (a rank with an empty scan still folds zeros and takes part)
                 if (rccl_sum(h, h->nd.sums.p, 48)) return 1;
-                H_TRY(ndt_launch_ctl(r.a, d_ctl, h->nd.sums.as<double>(), h->nd.out.dev, h->stream, seq, b == kBatch - 1 ? batch : 0));
+                H_TRY(ndt_launch_ctl(a, d_ctl, h->nd.sums.as<double>(), h->nd.out.dev, h->stream, seq, b == kBatch - 1 ? batch : 0));
             }
             const double want0 = seq * 65536.0 + 2.0 * batch;
             long spins = 0;
@@ -245,70 +236,72 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
             std::atomic_thread_fence(std::memory_order_acquire);
             if (peer_check(h)) return 1;      // (an exchange of this batch timed out: the loop has stopped on the ranks that waited, the session is over)
             if (*f_batch == want0 + 1.0) break;
-            if (enq >= limit) return fail(h, kBudgetMsg);
-        }
-        if (!out->bail) {      // (a nearly singular Newton system: every rank saw the same pivots and goes to the host loop below, with the SVD)
-            final_T = out->final_T; conv = out->conv; nr_it = out->nr_it; score = out->score;
-            h->nd.deriv = out->n_deriv; h->nd.hess = out->n_hess; h->nd.last_passes = out->passes;
-            sharded_done = true;
+            if (enq >= limit) return fail(h, kNdtBudgetMsg);
         }
     }
-    if (on_device) {
-        NdtCtl* d_ctl = h->nd.ctl.as<NdtCtl>();
-        NdtOut* out = h->nd.out.host;
-        h->seq += 1.0;
-        const double seq = h->seq;
-        // (a scan2map call whose region was marked has stored this state with the mark pass: do_scan2map, BlobStore)
-        const bool stored = h->blob_stored && h->roi_on;
-        h->blob_stored = false;
-        if (!stored) H_TRY(ndt_launch_ctl_init(d_ctl, T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters, h->stream, h->prm.ndt_evaluate_repeats,
-                                               r.a.roi_escapes));
-        const int limit = (h->prm.ndt_max_iters + 3) * 13 + 5;        // an iteration takes at most 1 + 10 + 1 passes; one launch more finishes
-        auto launch = [&](long i) -> hipError_t {
-            const int index = (int)i;
-            if (h->profile >= 2) {      // events at every launch's own begin and end (pcr_stats.kernel_ms)
-                while ((int)h->ev_kernel.size() < 2 * (index + 1)) { hipEvent_t e; hipError_t er = hipEventCreate(&e); if (er != hipSuccess) return er; h->ev_kernel.push_back(e); }
-                h->nd_prof_launches = index + 1;
-                return ndt_launch_pass_pro(r.a, d_ctl, h->nd.partials.as<double>(), h->nd.out.dev, h->stream, seq, index, h->ev_kernel[2 * index], h->ev_kernel[2 * index + 1]);
-            }
-            return ndt_launch_pass_pro(r.a, d_ctl, h->nd.partials.as<double>(), h->nd.out.dev, h->stream, seq, index);
-        };
-        // (the host enqueues a pass in a quarter of the time the device needs for one: it only has to stay two ahead -- a pass enqueued beyond
-        //  the end costs ~10 us of device time)
-        static constexpr PaceRule kRule{3, 2, 4, false};
-        if (pace_passes(h, out, seq, limit, kRule, kWindowMsg, kBudgetMsg, launch)) return 1;
-        h->nd.last_passes = out->passes;
-        h->nd_grid_bad = out->grid_overflow || out->grid_stale;
-        h->nd_grid_empty = out->grid_empty != 0;
-        h->nd_grid_cells = out->grid_cells;
-        h->nd_grid_checked = true;
+    *res = *out;      // (bail: every rank saw the same pivots and goes to the host loop)
+    return 0;
+}
+
+// The host-driven loop: the state machine on the host (with the SVD), one round trip per pass; sharded, every pass's sums cross the ranks.
+static int ndt_loop_host(pcr_handle* h, const NdtArgs& a, const NdtPose& T0, const double p0[6], NdtOut* res) {
+    NdtCtl c;
+    ndt_opt::ctl_init(&c, T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters);
+    c.replay_off = h->prm.ndt_evaluate_repeats ? 1 : 0;
+    double sums[43];
+    while (!c.done) {
+        if (a.n_src == 0) memset(sums, 0, sizeof sums);        // an empty scan: computeDerivatives sums nothing
+        else if (ndt_host_pass(h, a, c.kind, c.T, c.ang, sums)) return 1;
+        ndt_opt::ctl_step(&c, sums);
+    }
+    memset(res, 0, sizeof *res);
+    res->final_T = c.final_T; res->score = c.score; res->conv = c.conv; res->nr_it = c.nr_it; res->n_deriv = c.n_deriv; res->n_hess = c.n_hess; res->passes = c.passes;
+    return 0;
+}
+
+// Returns 0 with nd_grid_bad set when the index must be prepared again and the call repeated, 2 when a target prepared for the scan's
+// region has to give way to the whole target.
+int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) {
+    if (!h->nd.target_ready) return fail(h, "no target prepared");
+    if (n_src > kMaxPoints) return fail(h, "source cloud too large");
+    H_TRY(h->nd.out48.ensure(48));
+    H_TRY(h->nd.out.ensure());
+    H_TRY(h->nd.partials.reserve((size_t)1024 * 48 * sizeof(double)));      // (one buffer of 1024 rows, or the two of 256 of the one-launch-per-pass loop)
+    H_TRY(h->nd.ctl.reserve(2 * sizeof(NdtCtl)));
+    NdtArgs a = ndt_args(h, d_src, n_src, stride_floats);
+    a.roi_escapes = roi_view(h).escapes;      // (nullptr unless the target was prepared for one scan)
+    a.pair_count = prof_counters(h);
+    h->nd.iters = h->nd.deriv = h->nd.hess = 0;
+    NdtPose T0;
+    double p0[6];
+    ndt_initial_pose(pose, &T0, p0);
+
+    // The loop stays on the device unless pcr_params.host_optimiser asks for the host loop, the scan is empty, or the sums of a sharded
+    // handle cross the ranks through the host (pcr_comm_init_host).
+    const bool dev_sharded = sharded(h) && (h->comm.rccl || h->comm.peer_on) && !h->comm.host_ar && n_src > 0 && h->prm.host_optimiser == 0;
+    const bool on_device = n_src > 0 && !sharded(h) && h->prm.host_optimiser == 0;
+    if (h->roi_on && !on_device) return fail(h, "internal: a target prepared for one scan needs the device-resident loop");
+    h->nd_grid_checked = false; h->nd_grid_bad = false;
+    NdtOut res;
+    bool device_loop = false;      // res is a device loop's: it did not bail
+    if (dev_sharded) {
+        if (ndt_loop_device_sharded(h, a, T0, p0, &res)) return 1;
+        device_loop = !res.bail;
+    } else if (on_device) {
+        if (ndt_loop_device(h, a, T0, p0, &res)) return 1;
+        h->nd_grid_bad = res.grid_overflow || res.grid_stale;      // (what the loop saw in the index header: do_scan2map reads it)
+        h->nd_grid_empty = res.grid_empty != 0; h->nd_grid_cells = res.grid_cells; h->nd_grid_checked = true;
         if (h->nd_grid_bad) return 0;           // the caller prepares the target again and repeats the call
         // a pass looked up a voxel the target was not prepared for (RoiView), or the loop wants the host's SVD: whole target, again
-        if (h->roi_on && (out->roi_escapes > 0 || out->bail)) { h->roi_repeats += 1; return 2; }
-        if (out->bail) on_device = false;       // the Newton system was (nearly) singular: the host loop below decides, with the SVD
-        else {
-            final_T = out->final_T; conv = out->conv; nr_it = out->nr_it; score = out->score;
-            h->nd.deriv = out->n_deriv; h->nd.hess = out->n_hess;
-        }
+        if (h->roi_on && (res.roi_escapes > 0 || res.bail)) { h->roi_repeats += 1; return 2; }
+        device_loop = !res.bail;
     }
-    if (!on_device && !sharded_done) {
-        NdtCtl c;
-        ctl_init(&c, T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters);
-        c.replay_off = h->prm.ndt_evaluate_repeats ? 1 : 0;
-        double sums[43];
-        while (!c.done) {
-            if (n_src == 0) memset(sums, 0, sizeof sums);        // an empty scan: computeDerivatives sums nothing
-            else if (ndt_host_pass(&r, c, sums)) return 1;
-            ctl_step(&c, sums);
-        }
-        final_T = c.final_T; conv = c.conv; nr_it = c.nr_it; score = c.score;
-        h->nd.deriv = c.n_deriv; h->nd.hess = c.n_hess;
-    }
-    ndt_pose_out(final_T, pose);
-    if (converged) *converged = conv ? 1 : 0;
-    h->nd.iters = nr_it; h->nd.score = score;
-    h->stats.iterations = nr_it; h->stats.kernel_launches = h->nd.deriv + h->nd.hess;
-    h->stats.attempts = (on_device || sharded_done) ? h->nd.last_passes : 0;      // (the passes a device loop actually evaluated; 0: not such a loop)
+    if (!device_loop && ndt_loop_host(h, a, T0, p0, &res)) return 1;
+    ndt_pose_out(res.final_T, pose);
+    if (converged) *converged = res.conv ? 1 : 0;
+    h->nd.iters = res.nr_it; h->nd.score = res.score; h->nd.deriv = res.n_deriv; h->nd.hess = res.n_hess;
+    h->stats.iterations = res.nr_it; h->stats.kernel_launches = res.n_deriv + res.n_hess;
+    h->stats.attempts = device_loop ? res.passes : 0;      // (the passes a device loop actually evaluated; 0: not such a loop)
     h->stats.n_src = (int64_t)n_src; h->stats.n_dst = (int64_t)h->tgt_n;
     return 0;
 }
@@ -330,18 +323,17 @@ int pcr_ndt_derivatives(pcr_handle* h, const void* src, size_t n_src, size_t str
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
     H_TRY(h->nd.out48.ensure(48));
     H_TRY(h->nd.partials.reserve((size_t)1024 * 48 * sizeof(double)));
-    NdtRun r;
-    r.h = h;
-    r.a = ndt_args(h, d_src, n_src, stride_bytes / 4);
-    ndt_host::pose_from_p(p, &r.T);
-    double sc = 0;
-    if (ndt_derivatives(&r, p, true, &sc, grad, hess)) return 1;
-    if (score) *score = sc;
-    if (hess_d && n_src) {
-        H_TRY(ndt_launch_hessian(r.a, r.T, r.ang, h->nd.out48.dev, h->stream));
-        H_TRY(hipStreamSynchronize(h->stream));
-        if (sharded(h) && ranks_allreduce(h, h->nd.out48.host, 43)) return 1;
-        for (int i = 0; i < 36; ++i) hess_d[i] = h->nd.out48.host[7 + i];
+    const NdtArgs a = ndt_args(h, d_src, n_src, stride_bytes / 4);
+    NdtPose T;
+    NdtAngles ang;
+    ndt_host::pose_from_p(p, &T);
+    double sums[43];
+    if (ndt_derivatives(h, a, T, p, &ang, sums)) return 1;
+    if (score) *score = sums[0];
+    memcpy(grad, sums + 1, 6 * sizeof(double)); memcpy(hess, sums + 7, 36 * sizeof(double));
+    if (hess_d && n_src) {      // computeHessian at the same pose
+        if (ndt_host_pass(h, a, kNdtPassHessian, T, ang, sums)) return 1;
+        memcpy(hess_d, sums + 7, 36 * sizeof(double));
     }
     return 0;
 }
@@ -427,8 +419,7 @@ int pcr_ndt_pass_sums(pcr_handle* h, const void* src, size_t n_src, size_t strid
     ndt_opt::ctl_init(&c, T, p, 0.1, 1.0, 0);
     c.kind = kind; c.phase = kNdtPhaseLsHess; c.nr_it = 1; c.a_t = 0.0;
     NdtCtl* const d_ctl = h->nd.ctl.as<NdtCtl>();
-    h->seq += 1.0;
-    const double seq = h->seq;
+    const double seq = (h->seq += 1.0);
     H_TRY(ndt_launch_ctl_state(d_ctl, c, h->stream));
     H_TRY(ndt_launch_pass_pro(a, d_ctl, h->nd.partials.as<double>(), h->nd.out.dev, h->stream, seq, 0));      // the pass
     H_TRY(ndt_launch_pass_pro(a, d_ctl, h->nd.partials.as<double>(), h->nd.out.dev, h->stream, seq, 1));      // its prologue folds the rows and decides

@@ -495,9 +495,8 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
     auto host_pass = [&](int kind, int parity, const Pose16& xi, double seq) {
         return (kind == kVgPassLinearize ? vgicp_launch_linearize : vgicp_launch_error)(swapped(a, parity), xi, h->out32.dev, h->stream, seq);
     };
-    static constexpr PaceRule kPeerRule{0, 3, 0, true};
     LsqResult r;
-    if (run_lsq(h, pose, on_device, peer_loop ? kPeerRule : kLsqPace, "vgicp: the optimiser did not finish within its pass budget", device_pass, host_pass, &r, shard,
+    if (run_lsq(h, pose, on_device, peer_loop ? kPeerPace : kLsqPace, "vgicp: the optimiser did not finish within its pass budget", device_pass, host_pass, &r, shard,
                 a.roi.escapes /* nullptr unless the target was prepared for one scan */))
         return 1;
     // some pass looked up a voxel outside the region the target was prepared for: its sums lack that correspondence.  The caller

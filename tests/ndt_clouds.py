@@ -191,6 +191,19 @@ def room(n=3000):
     return _xyz0(np.concatenate([floor, wall_x, wall_y]))
 
 
+ROOM_SCAN_SIZES = (129, 513, 1025)
+
+
+def room_scan_case(n):
+    """(target, scan, guess) of a small alignment: the room, n of its points with 1 cm of noise, a guess 5 cm and 0.3 degrees off the identity"""
+    from simpleslam_amd import synth
+    m = room()
+    rng = np.random.default_rng([1209, n])
+    scan = m[rng.choice(len(m), n, replace=False)].copy()
+    scan[:, :3] += rng.normal(0.0, 0.01, (n, 3)).astype(np.float32)
+    return m, scan, synth.perturb(np.eye(4), 1209 + n, trans=0.05, rot_deg=0.3)
+
+
 def all_voxel_cases():
     """(name, cloud, resolution, min_points) of every voxel comparison"""
     cases = []

@@ -595,6 +595,38 @@ def test_ndt_peer_exchange_with_one_rank_equals_the_rccl_loop(gpu):
     assert t_peer < t_rccl * 1.25, (t_plain, t_peer, t_rccl)          # (bench.py --shard-map measures the price properly; here: not slower than the loop it replaces)
 
 
+# 129: one past a 128-thread block of ndt_pass_kernel; 513: a multiple of it plus one; 1025: 9 rows, so that a slice of the fold (ndt.hip:
+# ndt_fold_rows, 8 loads in flight) has a ragged tail.  tests/test_oracle_vgicp_ndt.py checks on the CPU that the oracle converges from these
+# guesses, on Newton systems far from singular, at all three sizes.
+@pytest.mark.parametrize("n", [129, 513, 1025])
+def test_ndt_sharded_device_loops_on_small_scans(gpu, n):
+    """The sharded device loops (ndt_pass_kernel, the fold of its rows, the controller step) over the peer exchange and over RCCL, one rank each, on
+    scans of a few blocks: the same pose bit for bit, the same iterations and passes; the iterations of the unsharded loop and its pose to the bar of
+    test_ndt_peer_exchange_with_one_rank_equals_the_rccl_loop (float poses whose sums were added in another order)."""
+    import torch
+    import ndt_clouds as nc
+    m, scan, init = nc.room_scan_case(n)
+    d_scan, d_map = torch.from_numpy(scan).cuda(), torch.from_numpy(m).cuda()
+    plain = make_register("ndt", full_target=1)
+    peer = make_register("ndt")
+    peer.comm_init_peer([peer.comm_peer_export()], 0, 1)
+    rccl = make_register("ndt")
+    rccl.comm_init(shard.unique_id(), 0, 1)
+    got = {}
+    for name, reg in (("plain", plain), ("peer", peer), ("rccl", rccl)):
+        p = init.copy()
+        conv = reg.scan2Map(d_scan, d_map, p)
+        got[name] = (p, conv, reg.stats())
+    np.testing.assert_array_equal(got["peer"][0], got["rccl"][0])
+    assert got["peer"][1] == got["rccl"][1] == got["plain"][1]
+    assert (got["peer"][2]["iterations"], got["peer"][2]["attempts"]) == (got["rccl"][2]["iterations"], got["rccl"][2]["attempts"])
+    assert got["peer"][2]["attempts"] > 0                      # (a device loop ran: the host loop reports 0)
+    assert got["peer"][2]["iterations"] == got["plain"][2]["iterations"]
+    for name in ("peer", "rccl"):
+        dt, dr = synth.pose_error(got[name][0], got["plain"][0])
+        assert dt <= 2e-6 and dr <= 2e-6, (name, dt, dr)
+
+
 def _peer_worker_vgicp(rank, world_size, port, q):
     import torch
     import torch.distributed as dist
