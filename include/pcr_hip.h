@@ -56,6 +56,22 @@ typedef struct pcr_params {
     int32_t ndt_max_iters;     /* 35 */
     int32_t ndt_min_points;    /* 6 points per voxel (pclomp/voxel_grid_covariance_omp.h:210) */
 
+    /* pclomp::NormalDistributionsTransform::setNeighborhoodSearchMethod (third_parties/pclomp/src/pclomp/ndt_omp.h:52-57,189-191): which voxels
+     * a transformed scan point is differentiated against.  Read by ndt handles ONLY (every other handle accepts any served value and ignores
+     * it).  A value outside 0..3, and PCR_NDT_KDTREE, are refused by pcr_create and pcr_set_params.  A change through pcr_set_params KEEPS
+     * the prepared target -- the voxel Gaussians do not depend on the neighbourhood -- and checks the halo of a sharded handle again. */
+    int32_t ndt_search;        /* PCR_NDT_*, default PCR_NDT_DIRECT7 (PCR/src/NdtRegister.cpp:13).  With c = floor(p / resolution) per axis, in float, a
+                                *    cell c + d counts when it lies inside the target's lattice box and its voxel was kept (>= ndt_min_points points, the
+                                *    eigenvalue and inverse tests passed) -- voxel_grid_covariance_omp_impl.hpp:374-441:
+                                *    DIRECT1 d = 0; DIRECT7 d = 0 and the six face cells; DIRECT26 the 26 cells of the 3 x 3 x 3 block around c, c itself
+                                *    EXCLUDED (pcl::getAllNeighborCellIndices).  The float derivative pass, its line-search variant and the double
+                                *    computeHessian pass all follow it (ndt_omp_impl.hpp:233-246, :572-585).
+                                *    KDTREE is not served, for three reasons: the reference searches FLANN over the voxel centroids, float running sums
+                                *    in input order (voxel_grid_covariance_omp_impl.hpp:289), so its result depends on the order of the target's rows,
+                                *    which nothing in this library does; voxels that failed the covariance tests (:337-341, :360-364) stay in that
+                                *    centroid cloud and radiusSearch returns them without an nr_points test (voxel_grid_covariance_omp.h:489-503), so
+                                *    the reference differentiates against whatever their icov_ holds; and FLANN is not available to pin either down. */
+
     /* VGICP -- PCR/src/VgicpRegister.cpp:13, third_parties/pclomp/src/fast_vgicp_impl.hpp:22-24,
      * fast_gicp_impl.hpp:16-20, lsq_registration_impl.hpp:11-18 */
     double vgicp_resolution;   /* 1.0 */
@@ -112,6 +128,12 @@ typedef struct pcr_params {
                                 *    bit for bit: the vendored fast_gicp constructs the same AdditiveGaussianVoxel for both (fast_vgicp_voxel.hpp:138-141)
                                 *    and weighs a correspondence by sqrt(num_points) in every mode (fast_vgicp_impl.hpp:149,199) */
 } pcr_params;
+
+/* pcr_params.ndt_search: pclomp::NeighborSearchMethod, in the enum's order */
+#define PCR_NDT_KDTREE 0
+#define PCR_NDT_DIRECT26 1
+#define PCR_NDT_DIRECT7 2
+#define PCR_NDT_DIRECT1 3
 
 /* pcr_params.vgicp_regularization: fast_gicp::RegularizationMethod, in the enum's order */
 #define PCR_REG_NONE 0
@@ -505,7 +527,9 @@ int pcr_comm_init_peer(pcr_handle* h, const void* ipc_handles, int rank, int nra
  * [lo - halo, hi + halo) (faces at +-1e30 are open).  What the halo must cover:
  *   loam   the k-NN gate radius (sqrt(loam_knn_max_sq) = 1 m, LoamRegister.cpp:59);
  *   ndt    lo, hi multiples of ndt_resolution and halo >= one voxel (two unless the resolution is a power of two): the
- *          DIRECT7 neighbourhood (ndt_omp_impl.hpp:242) reads the six face voxels, which must be complete;
+ *          DIRECT7 neighbourhood (ndt_omp_impl.hpp:242) reads the six face voxels, which must be complete.  DIRECT26 needs the
+ *          same (the halo extends the tile along every axis: a box that holds the edge and corner voxels too), DIRECT1 one
+ *          voxel less (none at a power-of-two resolution); the refusal names the pcr_params.ndt_search in force;
  *   vgicp  lo, hi on the voxel lattice ((k + 0.5) * vgicp_resolution, fast_vgicp_voxel.hpp:158-160) and a halo that holds
  *          the 20 nearest neighbours of every point of the tile (fast_gicp_impl.hpp:253): checked on the device for every
  *          point within one voxel of the tile -- a neighbourhood that reaches past the halo fails the call on all ranks.

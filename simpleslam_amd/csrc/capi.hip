@@ -237,6 +237,13 @@ const char* settings_out_of_range(const pcr_params& p) {
         return "vgicp_regularization must be 0 (NONE), 1 (MIN_EIG), 2 (NORMALIZED_MIN_EIG), 3 (PLANE) or 4 (FROBENIUS)";
     if (p.vgicp_voxel_mode < PCR_VOXEL_ADDITIVE || p.vgicp_voxel_mode > PCR_VOXEL_MULTIPLICATIVE)
         return "vgicp_voxel_mode must be 0 (ADDITIVE), 1 (ADDITIVE_WEIGHTED) or 2 (MULTIPLICATIVE)";
+    // pclomp::NeighborSearchMethod (ndt_omp.h:52-57).  Every handle is checked, as with the two above; only ndt handles read the value.
+    if (p.ndt_search < PCR_NDT_KDTREE || p.ndt_search > PCR_NDT_DIRECT1)
+        return "ndt_search must be 1 (DIRECT26), 2 (DIRECT7) or 3 (DIRECT1); 0 (KDTREE) is not served";
+    if (p.ndt_search == PCR_NDT_KDTREE)
+        return "ndt_search = 0 (KDTREE) is not served: the reference searches a kd-tree over float centroids summed in input order (the result "
+               "depends on the order of the target's rows), returns voxels its own covariance test rejected, and needs FLANN; use 1 (DIRECT26), "
+               "2 (DIRECT7) or 3 (DIRECT1)";
     return nullptr;
 }
 }  // namespace
@@ -258,6 +265,7 @@ void pcr_default_params(pcr_params* p) {
     p->record_trace = 0;
     p->gicp_max_corr_dist = (double)FLT_MAX;
     p->vgicp_regularization = PCR_REG_PLANE; p->vgicp_voxel_mode = PCR_VOXEL_ADDITIVE;
+    p->ndt_search = PCR_NDT_DIRECT7;
 }
 
 pcr_handle* pcr_create(const char* method, const pcr_params* p) {
@@ -459,6 +467,12 @@ int pcr_set_params(pcr_handle* h, const pcr_params* p) {
     if (p->device >= 0 && p->device != h->device) return fail(h, "a handle cannot move to another device");
     if (vgicp_family(h) && p->vgicp_k_corr != 20) return fail(h, "this build supports vgicp_k_corr = 20 (the reference's value) only");
     if (const char* bad = settings_out_of_range(*p)) return fail(h, bad);
+    // ndt_search: the voxel Gaussians do not depend on the neighbourhood, so the prepared target stays; the halo of a sharded handle was
+    // checked against the old setting and is checked again (nothing has been changed yet when it does not hold)
+    if (h->method == kNdt && h->use_tile && h->have_halo && p->ndt_search != h->prm.ndt_search) {
+        const double need = ndt_halo_need(p->ndt_search, (double)(float)p->ndt_resolution);
+        if (h->halo < need * (1.0 - 1e-12)) return fail(h, ndt_halo_message(p->ndt_search, need));
+    }
     const pcr_params old = h->prm;
     h->prm = *p;
     h->prm.device = old.device;

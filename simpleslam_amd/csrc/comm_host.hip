@@ -121,6 +121,29 @@ inline bool open_face(double v) { return !(fabs(v) < 1e29); }
 namespace pcr {
 namespace host {
 
+static const char* ndt_search_name(int search) {
+    return search == PCR_NDT_DIRECT26 ? "DIRECT26" : search == PCR_NDT_DIRECT1 ? "DIRECT1" : search == PCR_NDT_KDTREE ? "KDTREE" : "DIRECT7";
+}
+// What an ndt tile's halo must hold.  A scan point is evaluated by the rank whose tile [lo, hi) holds its transformed position; lo and hi are
+// multiples of the resolution.  Every voxel the point's neighbourhood reaches must be COMPLETE on that rank (all of its points present):
+//   the neighbourhood   DIRECT7 reaches one cell along an axis, DIRECT26 one cell along every axis at once -- the tile's extension
+//                       [lo - halo, hi + halo) is a box (shard_extent), so the one voxel per axis that holds the face cells holds the edge and
+//                       corner cells too; DIRECT1 reaches the point's own cell only: nothing
+//   the rounding        the point's cell is floorf(p / leaf) and a target point's voxel floorf(p * (1 / leaf)), both in float
+//                       (voxel_grid_covariance_omp_impl.hpp:380-382, :218-220): exact when the resolution is a power of two -- the cell then
+//                       lies inside the tile and its points inside the cell -- and otherwise off by up to one cell at a face: one voxel more
+double ndt_halo_need(int search, double res) {
+    int e;
+    const bool pow2 = frexp(res, &e) == 0.5;
+    return ((search == PCR_NDT_DIRECT1 ? 0.0 : 1.0) + (pow2 ? 0.0 : 1.0)) * res;
+}
+std::string ndt_halo_message(int search, double need) {
+    const std::string name = ndt_search_name(search);
+    return "ndt: the halo must hold what the " + name + " neighbourhood (pcr_params.ndt_search) reads" +
+           (search == PCR_NDT_DIRECT1 ? " (the point's own voxel where the float lattice rounds across a face)" : search == PCR_NDT_DIRECT26 ? " (the face, edge and corner voxels)" : " (the DIRECT7 face voxels)") +
+           ": >= " + std::to_string(need) + " m at this resolution";
+}
+
 void shard_extent(const pcr_handle* h, double ext_lo[3], double ext_hi[3]) {
     for (int d = 0; d < 3; ++d) {
         ext_lo[d] = open_face(h->tile_lo[d]) ? -1e300 : h->tile_lo[d] - h->halo;
@@ -169,7 +192,6 @@ int pcr_set_shard(pcr_handle* h, const double lo[3], const double hi[3], double 
         const double k = v / res - shift;
         return fabs(k - nearbyint(k)) <= 1e-9 * std::max(1.0, fabs(k));
     };
-    auto pow2 = [](double r) { int e; return frexp(r, &e) == 0.5; };
     if (h->method == kLoam) {
         const double gate = sqrt(std::max(0.0, h->prm.loam_knn_max_sq));
         if (halo < gate) return fail(h, "loam: the halo must cover the k-NN gate radius (" + std::to_string(gate) + " m, LoamRegister.cpp:59)");
@@ -177,8 +199,8 @@ int pcr_set_shard(pcr_handle* h, const double lo[3], const double hi[3], double 
         const double res = (double)(float)h->prm.ndt_resolution;
         for (int d = 0; d < 3; ++d)
             if (!on_lattice(lo[d], res, 0.0) || !on_lattice(hi[d], res, 0.0)) return fail(h, "ndt: tile bounds must be multiples of ndt_resolution (whole voxels per rank)");
-        const double need = (pow2(res) ? 1.0 : 2.0) * res;
-        if (halo < need * (1.0 - 1e-12)) return fail(h, "ndt: the halo must hold the DIRECT7 face voxels: >= " + std::to_string(need) + " m at this resolution");
+        const double need = ndt_halo_need(h->prm.ndt_search, res);
+        if (halo < need * (1.0 - 1e-12)) return fail(h, ndt_halo_message(h->prm.ndt_search, need));
     } else {
         const double res = h->prm.vgicp_resolution;
         for (int d = 0; d < 3; ++d)

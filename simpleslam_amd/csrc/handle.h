@@ -259,6 +259,9 @@ void peer_close(pcr_handle* h);
 int peer_check(pcr_handle* h);
 void comm_release(pcr_handle* h);
 void shard_extent(const pcr_handle* h, double ext_lo[3], double ext_hi[3]);
+// the halo an ndt tile needs under pcr_params.ndt_search at this resolution, and the refusal that names the setting (pcr_set_shard, pcr_set_params)
+double ndt_halo_need(int search, double res);
+std::string ndt_halo_message(int search, double need);
 
 // ---- loam_host.hip ----
 int build_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats);

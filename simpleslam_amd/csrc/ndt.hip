@@ -1,4 +1,4 @@
-// ndt.hip -- NDT scan-to-map (pclomp::NormalDistributionsTransform, DIRECT7) on gfx950.
+// ndt.hip -- NDT scan-to-map (pclomp::NormalDistributionsTransform; DIRECT7, DIRECT1 or DIRECT26) on gfx950.
 //
 // Kernels for the reference's PCR::NdtRegister::scan2Map (PCR/src/NdtRegister.cpp:21-31):
 //   N1 voxel Gaussians   voxel_grid_covariance_omp_impl.hpp:49-370 (serial std::map there)
@@ -6,7 +6,7 @@
 //         centred fixed-point sums (order independent) -> the reference's single-pass covariance expression, Jacobi eigen
 //         decomposition, eigenvalue inflation 0.01 * lambda_max, inverse
 //   N3 computeDerivatives / updateDerivatives   ndt_omp_impl.hpp:180-285,399-440,485-537
-//      -> ndt_derivatives_kernel: per source point, <= 7 neighbour cells (N6, :374-433),
+//      -> ndt_derivatives_kernel: per source point, the neighbour cells of pcr_params.ndt_search (N6, :374-441: <= 7 by default),
 //         FLOAT inner math exactly as the reference orders it, f64 accumulation, fixed-order sums
 //   N5 computeHessian / updateHessian           ndt_omp_impl.hpp:541-645 (serial, double)
 //      -> ndt_hessian_kernel
@@ -323,10 +323,43 @@ __global__ __launch_bounds__(256) void ndt_voxel_kernel(GridView g, const uint32
 }
 
 // ------------------------------------------------------------------------------
-// neighbourhood: centre cell then +x -x +y -y +z -z (:419-433)
+// neighbourhood (pcr_params.ndt_search, voxel_grid_covariance_omp_impl.hpp:374-441): kSearch is a template parameter of the lookup and of
+// the pass bodies, chosen on the host (NDT_SEARCH_DISPATCH) and compiled into every kernel that holds them.
+//   DIRECT7   centre cell then +x -x +y -y +z -z (:419-433)
+//   DIRECT1   the centre cell: the same table, cut after its first entry
+//   DIRECT26  the 3 x 3 x 3 block WITHOUT its centre.  No table and no 26 slots in registers (the bodies are bound by arithmetic and
+//             register pressure): the nine rows of the block are read -- vox_slot is dense with x fastest, so the three cells of a row are
+//             adjacent words -- and what is kept of them is one presence bit per cell, bit (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); the pair
+//             loop takes the bits lowest first (z outermost, x fastest: the fixed visiting order of all bodies) and reads a found cell's
+//             slot again, from the cache.
+// A candidate cell counts when it lies inside the lattice box and its voxel was kept; a point whose own cell lies one layer outside the box
+// still reaches the box's outer voxels under DIRECT7 and DIRECT26 (fx in [-1, dims]), and nothing under DIRECT1.
 // ------------------------------------------------------------------------------
+// what a body keeps of a point's neighbourhood between the lookup and its pair loop: the slots found, in table order (DIRECT7, DIRECT1) ...
+template <int kSearch> constexpr int kNdtSlots = kSearch == PCR_NDT_DIRECT7 ? 7 : 1;
+// ... or the block's presence bits and its centre (DIRECT26; the other settings carry an empty one along)
+struct NdtBlock {
+    uint32_t mask;      // cells found, not yet taken
+    int cx, cy, cz;     // the centre cell, in the box's coordinates
+};
+// neighbour k of the pair loop, which takes them in order
+template <int kSearch>
+__device__ __forceinline__ uint32_t ndt_take(const GridHeader& h, const uint32_t* __restrict__ vox_slot, const uint32_t* slots, NdtBlock& blk, int k) {
+    if constexpr (kSearch == PCR_NDT_DIRECT26) {
+        const uint32_t b = (uint32_t)__builtin_ctz(blk.mask);
+        blk.mask &= blk.mask - 1u;
+        const uint32_t bz = b / 9u, r = b - bz * 9u, by = r / 3u, bx = r - by * 3u;
+        const int x = blk.cx + (int)bx - 1, y = blk.cy + (int)by - 1, z = blk.cz + (int)bz - 1;      // (inside the box: the bit was set from this cell's slot)
+        return vox_slot[((uint64_t)z * (uint64_t)h.dims[1] + (uint64_t)y) * (uint64_t)h.dims[0] + (uint64_t)x];
+    } else {
+        return slots[k];
+    }
+}
+
+template <int kSearch>
 __device__ __forceinline__ int ndt_neighbours(const GridHeader& h, const uint32_t* __restrict__ vox_slot, float tx, float ty, float tz,
-                                              uint32_t slots[7], uint32_t* __restrict__ roi_escapes) {
+                                              uint32_t slots[kNdtSlots<kSearch>], NdtBlock& blk, uint32_t* __restrict__ roi_escapes) {
+    static_assert(kSearch == PCR_NDT_DIRECT26 || kSearch == PCR_NDT_DIRECT7 || kSearch == PCR_NDT_DIRECT1, "kSearch must be PCR_NDT_DIRECT26, _DIRECT7 or _DIRECT1");
     int n = 0;
     if (h.overflow || h.empty) return 0;
     // floor(p / leaf) evaluated in float like the reference (:380-382)
@@ -334,14 +367,39 @@ __device__ __forceinline__ int ndt_neighbours(const GridHeader& h, const uint32_
     const double fx = (double)floorf(tx / leaf) - h.org[0], fy = (double)floorf(ty / leaf) - h.org[1], fz = (double)floorf(tz / leaf) - h.org[2];
     if (!(fx >= -1.0 && fx <= (double)h.dims[0] && fy >= -1.0 && fy <= (double)h.dims[1] && fz >= -1.0 && fz <= (double)h.dims[2])) return 0;
     const int cx = (int)fx, cy = (int)fy, cz = (int)fz;
-    const int off[7][3] = {{0, 0, 0}, {1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+    if constexpr (kSearch == PCR_NDT_DIRECT26) {
+        uint32_t mask = 0u;
 #pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        const int x = cx + off[k][0], y = cy + off[k][1], z = cz + off[k][2];
-        if (x >= 0 && x < h.dims[0] && y >= 0 && y < h.dims[1] && z >= 0 && z < h.dims[2]) {
-            const uint32_t s = vox_slot[((uint64_t)z * (uint64_t)h.dims[1] + (uint64_t)y) * (uint64_t)h.dims[0] + (uint64_t)x];
-            if (s == kNdtUnprepared) { if (roi_escapes) atomicAdd(roi_escapes, 1u); }      // a voxel the target was not prepared for: the call is repeated on the whole target
-            else if (s) slots[n++] = s;
+        for (int dz = -1; dz <= 1; ++dz) {
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy) {
+                const int y = cy + dy, z = cz + dz;
+                if (y >= 0 && y < h.dims[1] && z >= 0 && z < h.dims[2]) {
+                    const uint32_t* const row = vox_slot + ((uint64_t)z * (uint64_t)h.dims[1] + (uint64_t)y) * (uint64_t)h.dims[0];
+#pragma unroll
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        if (dz == 0 && dy == 0 && dx == 0) continue;      // 26 cells: the centre voxel is not one of them
+                        const int x = cx + dx;
+                        if (x >= 0 && x < h.dims[0]) {
+                            const uint32_t s = row[x];
+                            if (s == kNdtUnprepared) { if (roi_escapes) atomicAdd(roi_escapes, 1u); }
+                            else if (s) { mask |= 1u << ((dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)); ++n; }
+                        }
+                    }
+                }
+            }
+        }
+        blk.mask = mask; blk.cx = cx; blk.cy = cy; blk.cz = cz;
+    } else {
+        const int off[7][3] = {{0, 0, 0}, {1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+#pragma unroll
+        for (int k = 0; k < kNdtSlots<kSearch>; ++k) {
+            const int x = cx + off[k][0], y = cy + off[k][1], z = cz + off[k][2];
+            if (x >= 0 && x < h.dims[0] && y >= 0 && y < h.dims[1] && z >= 0 && z < h.dims[2]) {
+                const uint32_t s = vox_slot[((uint64_t)z * (uint64_t)h.dims[1] + (uint64_t)y) * (uint64_t)h.dims[0] + (uint64_t)x];
+                if (s == kNdtUnprepared) { if (roi_escapes) atomicAdd(roi_escapes, 1u); }      // a voxel the target was not prepared for: the call is repeated on the whole target
+                else if (s) slots[n++] = s;
+            }
         }
     }
     return n;
@@ -438,7 +496,7 @@ __device__ __forceinline__ void ndt_block_reduce(double* sh /* [16][kB + 2] */, 
 // ------------------------------------------------------------------------------
 // N3: computeDerivatives
 // ------------------------------------------------------------------------------
-template <bool kHessian, int kB>
+template <int kSearch, bool kHessian, int kB>
 __device__ __forceinline__ void ndt_derivatives_body(const NdtArgs& a, const NdtPose& T, const NdtAngles& ang, double* sh, double* sh2) {
     constexpr int kComp = kHessian ? kNdtComp : 7;
     // the exponential's table in LDS (a per-lane index into constant memory serialises; the slot is the tail of sh2, which the
@@ -462,8 +520,9 @@ __device__ __forceinline__ void ndt_derivatives_body(const NdtArgs& a, const Ndt
             float tp[3];
 #pragma unroll
             for (int r = 0; r < 3; ++r) { float s = T.R[r * 3] * x4[0]; s += T.R[r * 3 + 1] * x4[1]; s += T.R[r * 3 + 2] * x4[2]; s += T.t[r]; tp[r] = s; }
-            uint32_t slots[7];
-            int nn = ndt_neighbours(h, a.vox_slot, tp[0], tp[1], tp[2], slots, a.roi_escapes);
+            uint32_t slots[kNdtSlots<kSearch>];
+            NdtBlock blk;
+            int nn = ndt_neighbours<kSearch>(h, a.vox_slot, tp[0], tp[1], tp[2], slots, blk, a.roi_escapes);
             if (a.use_tile && !ndt_in_tile(a, tp)) nn = 0;       // another rank's query
             if (a.pair_count && nn > 0) atomicAdd(a.pair_count + (kHessian ? 48 : 32), (uint32_t)nn);      // (profiling passes only)
             if (nn > 0) {
@@ -484,7 +543,7 @@ __device__ __forceinline__ void ndt_derivatives_body(const NdtArgs& a, const Ndt
                                         {0, xh[2], xh[3]}, {xh[6], xh[7], xh[8]}, {xh[9], xh[10], xh[11]},
                                         {0, xh[4], xh[5]}, {xh[9], xh[10], xh[11]}, {xh[12], xh[13], xh[14]}};
                 for (int k = 0; k < nn; ++k) {
-                    const NdtVoxel cell = a.vox[slots[k] - 1];
+                    const NdtVoxel cell = a.vox[ndt_take<kSearch>(h, a.vox_slot, slots, blk, k) - 1];
                     const double xt[3] = {(double)tp[0] - cell.mean[0], (double)tp[1] - cell.mean[1], (double)tp[2] - cell.mean[2]};
                     const float x4t[3] = {(float)xt[0], (float)xt[1], (float)xt[2]};
                     float ci[3][3];
@@ -554,7 +613,7 @@ __device__ __forceinline__ void ndt_derivatives_body(const NdtArgs& a, const Ndt
 // ------------------------------------------------------------------------------
 // N5: computeHessian (double)
 // ------------------------------------------------------------------------------
-template <int kB>
+template <int kSearch, int kB>
 __device__ __forceinline__ void ndt_hessian_body(const NdtArgs& a, const NdtPose& T, const NdtAngles& ang, double* sh, double* sh2) {
     const GridHeader h = *a.hdr;
     double acc[kNdtChunks] = {0.0, 0.0, 0.0};
@@ -569,8 +628,9 @@ __device__ __forceinline__ void ndt_hessian_body(const NdtArgs& a, const NdtPose
             float tp[3];
 #pragma unroll
             for (int r = 0; r < 3; ++r) { float s = T.R[r * 3] * xp[0]; s += T.R[r * 3 + 1] * xp[1]; s += T.R[r * 3 + 2] * xp[2]; s += T.t[r]; tp[r] = s; }
-            uint32_t slots[7];
-            int nn = ndt_neighbours(h, a.vox_slot, tp[0], tp[1], tp[2], slots, a.roi_escapes);
+            uint32_t slots[kNdtSlots<kSearch>];
+            NdtBlock blk;
+            int nn = ndt_neighbours<kSearch>(h, a.vox_slot, tp[0], tp[1], tp[2], slots, blk, a.roi_escapes);
             if (a.use_tile && !ndt_in_tile(a, tp)) nn = 0;
             if (nn > 0) {
                 const double x[3] = {(double)xp[0], (double)xp[1], (double)xp[2]};
@@ -589,7 +649,7 @@ __device__ __forceinline__ void ndt_hessian_body(const NdtArgs& a, const NdtPose
                                          {0, dh[2], dh[3]}, {dh[6], dh[7], dh[8]}, {dh[9], dh[10], dh[11]},
                                          {0, dh[4], dh[5]}, {dh[9], dh[10], dh[11]}, {dh[12], dh[13], dh[14]}};
                 for (int k = 0; k < nn; ++k) {
-                    const NdtVoxel cell = a.vox[slots[k] - 1];
+                    const NdtVoxel cell = a.vox[ndt_take<kSearch>(h, a.vox_slot, slots, blk, k) - 1];
                     const double xt[3] = {(double)tp[0] - cell.mean[0], (double)tp[1] - cell.mean[1], (double)tp[2] - cell.mean[2]};
                     const double* ci = cell.icov;
                     double cx[3];
@@ -639,16 +699,17 @@ __device__ __forceinline__ void ndt_hessian_body(const NdtArgs& a, const NdtPose
 }
 
 // the three evaluation kernels of the host-driven loop (pose and tables as kernel arguments)
-template <bool kHessian>
+template <int kSearch, bool kHessian>
 __global__ __launch_bounds__(kNdtBlock, 2) void ndt_derivatives_kernel(const NdtArgs a, const NdtPose T, const NdtAngles ang) {
     __shared__ double sh[kNdtChunk * kNdtStride];
     __shared__ double sh2[2 * 48 + 32];
-    ndt_derivatives_body<kHessian, kNdtBlock>(a, T, ang, sh, sh2);
+    ndt_derivatives_body<kSearch, kHessian, kNdtBlock>(a, T, ang, sh, sh2);
 }
+template <int kSearch>
 __global__ __launch_bounds__(kNdtBlock, 2) void ndt_hessian_kernel(const NdtArgs a, const NdtPose T, const NdtAngles ang) {
     __shared__ double sh[kNdtChunk * kNdtStride];
     __shared__ double sh2[2 * 48 + 32];
-    ndt_hessian_body<kNdtBlock>(a, T, ang, sh, sh2);
+    ndt_hessian_body<kSearch, kNdtBlock>(a, T, ang, sh, sh2);
 }
 
 // ------------------------------------------------------------------------------
@@ -657,15 +718,16 @@ __global__ __launch_bounds__(kNdtBlock, 2) void ndt_hessian_kernel(const NdtArgs
 // ndt_opt.h.  The host enqueues passes ahead of the device and only watches a progress word; passes enqueued beyond the end
 // of the optimisation return at once.  ndt_pass_kernel is the evaluation alone (the sharded loops below).
 // ------------------------------------------------------------------------------
+template <int kSearch>
 __global__ __launch_bounds__(kNdtBlock, 2) void ndt_pass_kernel(const NdtArgs a, const NdtCtl* __restrict__ ctl) {
     __shared__ double sh[kNdtChunk * kNdtStride];
     __shared__ double sh2[2 * 48 + 32];
     const int kind = ctl->kind;
     if (kind == kNdtPassNone) return;
     const NdtPose T = ctl->T;
-    if (kind == kNdtPassDerivH) ndt_derivatives_body<true, kNdtBlock>(a, T, ctl->ang, sh, sh2);
-    else if (kind == kNdtPassDeriv) ndt_derivatives_body<false, kNdtBlock>(a, T, ctl->ang, sh, sh2);
-    else ndt_hessian_body<kNdtBlock>(a, T, ctl->ang, sh, sh2);
+    if (kind == kNdtPassDerivH) ndt_derivatives_body<kSearch, true, kNdtBlock>(a, T, ctl->ang, sh, sh2);
+    else if (kind == kNdtPassDeriv) ndt_derivatives_body<kSearch, false, kNdtBlock>(a, T, ctl->ang, sh, sh2);
+    else ndt_hessian_body<kSearch, kNdtBlock>(a, T, ctl->ang, sh, sh2);
 }
 
 // the controller's initial state, prepared on the host (ndt_opt::ctl_init) and handed over as a kernel argument
@@ -814,6 +876,7 @@ __device__ __forceinline__ void lds_uniform_copy(const NdtCtl* c, NdtPose& T, Nd
         for (int k = 0; k < 3; ++k) { ang.h[r][k] = lds_uniform(&c->ang.h[r][k]); ang.hd[r][k] = lds_uniform(&c->ang.hd[r][k]); }
 }
 
+template <int kSearch>
 __global__ __launch_bounds__(kProBlock, 1) void ndt_pass_pro_kernel(const NdtArgs a, const NdtProArgs pa) {
     __shared__ double sh[kNdtChunk * (kProBlock + 2)];
     __shared__ double sh2[(kProBlock / 64) * 48 + 32];
@@ -871,15 +934,15 @@ __global__ __launch_bounds__(kProBlock, 1) void ndt_pass_pro_kernel(const NdtArg
     if (kind == kNdtPassDerivH) {
         NdtPose T; NdtAngles ang;
         lds_uniform_copy(c, T, ang);
-        ndt_derivatives_body<true, kProBlock>(a, T, ang, sh, sh2);
+        ndt_derivatives_body<kSearch, true, kProBlock>(a, T, ang, sh, sh2);
     } else if (kind == kNdtPassDeriv) {
         NdtPose T; NdtAngles ang;
         lds_uniform_copy(c, T, ang);
-        ndt_derivatives_body<false, kProBlock>(a, T, ang, sh, sh2);
+        ndt_derivatives_body<kSearch, false, kProBlock>(a, T, ang, sh, sh2);
     } else {
         NdtPose T; NdtAngles ang;
         lds_uniform_copy(c, T, ang);
-        ndt_hessian_body<kProBlock>(a, T, ang, sh, sh2);
+        ndt_hessian_body<kSearch, kProBlock>(a, T, ang, sh, sh2);
     }
 }
 
@@ -961,6 +1024,14 @@ __global__ __launch_bounds__(kFoldBlock) void ndt_sum_partials_kernel(const doub
 }
 
 // ---- host launchers ---------------------------------------------------------------
+// the kernel instantiation of the neighbourhood a handle asks for (NdtArgs.search = pcr_params.ndt_search, validated by pcr_create /
+// pcr_set_params: KDTREE never arrives here): CALL is a statement that uses the constant kSearch
+#define NDT_SEARCH_DISPATCH(search, CALL) \
+    switch (search) { \
+        case PCR_NDT_DIRECT26: { constexpr int kSearch = PCR_NDT_DIRECT26; CALL; } break; \
+        case PCR_NDT_DIRECT1: { constexpr int kSearch = PCR_NDT_DIRECT1; CALL; } break; \
+        default: { constexpr int kSearch = PCR_NDT_DIRECT7; CALL; } break; \
+    }
 uint32_t ndt_blocks(uint32_t n_src) {
     uint32_t b = (n_src + kNdtBlock - 1) / kNdtBlock;
     return b < 1 ? 1 : (b > 1024 ? 1024 : b);
@@ -981,8 +1052,8 @@ hipError_t ndt_launch_voxels(const GridIndex& grid, uint32_t* d_slot, NdtVoxel* 
 
 hipError_t ndt_launch_derivatives(const NdtArgs& a, const NdtPose& T, const NdtAngles& ang, int compute_hessian, double* d_out48, hipStream_t s, double seq) {
     const uint32_t nb = ndt_blocks(a.n_src);
-    if (compute_hessian) hipLaunchKernelGGL((ndt_derivatives_kernel<true>), dim3(nb), dim3(kNdtBlock), 0, s, a, T, ang);
-    else hipLaunchKernelGGL((ndt_derivatives_kernel<false>), dim3(nb), dim3(kNdtBlock), 0, s, a, T, ang);
+    NDT_SEARCH_DISPATCH(a.search, if (compute_hessian) hipLaunchKernelGGL((ndt_derivatives_kernel<kSearch, true>), dim3(nb), dim3(kNdtBlock), 0, s, a, T, ang);
+                                  else hipLaunchKernelGGL((ndt_derivatives_kernel<kSearch, false>), dim3(nb), dim3(kNdtBlock), 0, s, a, T, ang))
     hipLaunchKernelGGL(ndt_sum_partials_kernel, dim3(1), dim3(kFoldBlock), 0, s, a.partials, nb, d_out48, seq);
     return hipGetLastError();
 }
@@ -1027,22 +1098,22 @@ hipError_t ndt_launch_pass_pro(const NdtArgs& a_in, NdtCtl* d_ctl2, double* d_ro
     pa.ctl_next = d_ctl2 + (index & 1);
     pa.out = d_out; pa.seq = seq; pa.rows_prev_n = nb; pa.first = index == 0 ? 1 : 0;
     // (start / stop: events the packet processor stamps at the kernel's own begin and end -- profiling passes)
-    if (start || stop) hipExtLaunchKernelGGL(ndt_pass_pro_kernel, dim3(nb), dim3(kProBlock), 0, s, start, stop, 0, a, pa);
-    else hipLaunchKernelGGL(ndt_pass_pro_kernel, dim3(nb), dim3(kProBlock), 0, s, a, pa);
+    NDT_SEARCH_DISPATCH(a.search, if (start || stop) hipExtLaunchKernelGGL(ndt_pass_pro_kernel<kSearch>, dim3(nb), dim3(kProBlock), 0, s, start, stop, 0, a, pa);
+                                  else hipLaunchKernelGGL(ndt_pass_pro_kernel<kSearch>, dim3(nb), dim3(kProBlock), 0, s, a, pa))
     return hipGetLastError();
 }
 
 // one pass of the sharded device-resident loop, in three pieces around the caller's all-reduce of d_sums48
 hipError_t ndt_launch_pass_fold(const NdtArgs& a, NdtCtl* d_ctl, double* d_sums48, hipStream_t s) {
     const uint32_t nb = ndt_blocks(a.n_src);
-    hipLaunchKernelGGL(ndt_pass_kernel, dim3(nb), dim3(kNdtBlock), 0, s, a, d_ctl);
+    NDT_SEARCH_DISPATCH(a.search, hipLaunchKernelGGL(ndt_pass_kernel<kSearch>, dim3(nb), dim3(kNdtBlock), 0, s, a, d_ctl))
     hipLaunchKernelGGL(ndt_fold_kernel, dim3(1), dim3(kFoldBlock), 0, s, a.partials, nb, d_ctl, d_sums48);
     return hipGetLastError();
 }
 // one pass of the sharded loop over the peer exchange: the evaluation, then fold + exchange + controller step in one launch
 hipError_t ndt_launch_pass_peer(const NdtArgs& a, NdtCtl* d_ctl, const PeerComm& pc, double xseq, NdtOut* d_out, hipStream_t s, double seq) {
     const uint32_t nb = ndt_blocks(a.n_src);
-    hipLaunchKernelGGL(ndt_pass_kernel, dim3(nb), dim3(kNdtBlock), 0, s, a, d_ctl);
+    NDT_SEARCH_DISPATCH(a.search, hipLaunchKernelGGL(ndt_pass_kernel<kSearch>, dim3(nb), dim3(kNdtBlock), 0, s, a, d_ctl))
     hipLaunchKernelGGL(ndt_fold_exchange_ctl_kernel, dim3(1), dim3(kFoldBlock), 0, s, a.partials, nb, d_ctl, pc, xseq, a.hdr, d_out, seq, (const uint32_t*)a.roi_escapes);
     return hipGetLastError();
 }
@@ -1053,7 +1124,7 @@ hipError_t ndt_launch_ctl(const NdtArgs& a, NdtCtl* d_ctl, const double* d_sums4
 
 hipError_t ndt_launch_hessian(const NdtArgs& a, const NdtPose& T, const NdtAngles& ang, double* d_out48, hipStream_t s, double seq) {
     const uint32_t nb = ndt_blocks(a.n_src);
-    hipLaunchKernelGGL(ndt_hessian_kernel, dim3(nb), dim3(kNdtBlock), 0, s, a, T, ang);
+    NDT_SEARCH_DISPATCH(a.search, hipLaunchKernelGGL(ndt_hessian_kernel<kSearch>, dim3(nb), dim3(kNdtBlock), 0, s, a, T, ang))
     hipLaunchKernelGGL(ndt_sum_partials_kernel, dim3(1), dim3(kFoldBlock), 0, s, a.partials, nb, d_out48, seq);
     return hipGetLastError();
 }

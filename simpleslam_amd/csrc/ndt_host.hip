@@ -13,6 +13,16 @@ using namespace pcr::host;
 namespace pcr {
 namespace host {
 
+// The base margin, in metres, of the region a target is prepared for (roi_enqueue): 1 m of translation + what the neighbourhood reaches beyond the
+// cell a point lands in.  The region is a dilation by a CHEBYSHEV radius (grid_index.hip: every macro cell within r of a mark along x, then y,
+// then z -- a box, not a ball), so the one voxel per axis that holds DIRECT7's face cells holds DIRECT26's edge and corner cells as well: no
+// sqrt(3).  DIRECT1 keeps the voxel too: the mark pass places a point by floor(p / cell) in double and the lookup by floorf in float
+// (ndt_neighbours), which may differ by a cell at a face; a smaller margin would need that bounded first.
+static double ndt_roi_margin(int search, double res) {
+    (void)search;      // PCR_NDT_DIRECT26, _DIRECT7, _DIRECT1: one voxel per axis in every case, for the reasons above
+    return 1.0 + res;
+}
+
 // deferred: nothing is read back here -- the index is enqueued with the previous target's box as a hint and the cell table at its
 // current size; whether either was wrong (header.overflow / header.stale) comes back with the result of the alignment
 // (NdtOut), and the caller then prepares again the slow, checked way.  One host round trip less per scan.
@@ -31,7 +41,7 @@ int ndt_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t s
     const bool want_roi = roi_scan && roi_scan->n_src > 0 && n_dst > 0;
     BuildFilter bf;
     bf.enqueue_mask = [&]() -> hipError_t {
-        if (roi_enqueue(h, *roi_scan, res, 1.0 + res, &roi)) return hipErrorUnknown;      // 1 m of translation + the DIRECT7 face voxels, + 0.05 rad
+        if (roi_enqueue(h, *roi_scan, res, ndt_roi_margin(h->prm.ndt_search, res), &roi)) return hipErrorUnknown;      // 1 m of translation + the neighbourhood's voxel, + 0.05 rad
         bf.mask = roi.mask; bf.mshift = roi.mshift;
         return hipSuccess;
     };
@@ -67,7 +77,7 @@ int ndt_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t s
     H_TRY(h->nd.slot.reserve(((size_t)h->grid.cell_capacity + 64) * sizeof(uint32_t)));
     if (bf.applied) { roi.filtered = 1; h->roi_on = true; }
     else if (want_roi) {
-        if (roi_enqueue(h, *roi_scan, res, 1.0 + res, &roi)) return 1;
+        if (roi_enqueue(h, *roi_scan, res, ndt_roi_margin(h->prm.ndt_search, res), &roi)) return 1;
         h->roi_on = true;
     }
     H_TRY(ndt_launch_voxels(h->grid, h->nd.slot.as<uint32_t>(), h->nd.vox.as<NdtVoxel>(), nd_count, nd_count_next, h->nd.list.as<uint32_t>(),
@@ -122,6 +132,7 @@ NdtArgs ndt_args(const pcr_handle* h, const float* d_src, size_t n_src, size_t s
     a.hdr = h->grid.header.as<GridHeader>(); a.vox_slot = h->nd.slot.as<uint32_t>(); a.vox = h->nd.vox.as<NdtVoxel>();
     a.partials = h->nd.partials.as<double>();
     a.use_tile = h->use_tile;
+    a.search = h->prm.ndt_search;
     for (int d = 0; d < 3; ++d) { a.tile_lo[d] = h->tile_lo[d]; a.tile_hi[d] = h->tile_hi[d]; }
     // Gauss constants (ndt_omp_impl.hpp:86-93)
     const double res = (double)(float)h->prm.ndt_resolution;

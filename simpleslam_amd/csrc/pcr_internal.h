@@ -439,7 +439,8 @@ struct NdtArgs {
     const NdtVoxel* vox;
     double d1, d2;           // gauss_d1_, gauss_d2_ (ndt_omp_impl.hpp:86-93)
     double* partials;        // [blocks][48]
-    int32_t use_tile, pad_;  // sharded target: only source points whose transformed position lies in [tile_lo, tile_hi)
+    int32_t use_tile;        // sharded target: only source points whose transformed position lies in [tile_lo, tile_hi)
+    int32_t search;          // pcr_params.ndt_search (PCR_NDT_DIRECT*): read by the HOST launchers only, which pick the kernel instantiation by it
     double tile_lo[3], tile_hi[3];
     uint32_t* roi_escapes;   // target prepared for one scan (RoiView): count of lookups that hit a voxel it was not prepared for; else NULL
     uint32_t* pair_count;    // profiling passes only (pcr_set_profile >= 2), else NULL: [32] += (point, voxel) pairs of gradient-only passes, [48] += of passes with a Hessian

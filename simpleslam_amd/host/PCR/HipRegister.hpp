@@ -282,6 +282,9 @@ class NdtRegister : public HipRegister {
 public:
     NdtRegister() : HipRegister("ndt") {}
     explicit NdtRegister(const pcr_params& p) : HipRegister("ndt", &p) {}
+    // pclomp::NormalDistributionsTransform::setNeighborhoodSearchMethod (ndt_omp.h:189-191): PCR_NDT_DIRECT26 / _DIRECT7 / _DIRECT1, in pclomp's
+    // enum order.  The prepared target is kept (the voxel Gaussians do not depend on it); PCR_NDT_KDTREE or a value out of range throws.
+    void setNeighborhoodSearchMethod(int method) { setField(&pcr_params::ndt_search, method); }
 };
 
 class VgicpRegister : public HipRegister {

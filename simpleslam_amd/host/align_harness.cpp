@@ -1,5 +1,6 @@
 // align_harness.cpp -- ROS/PCL-free counterpart of the reference's test/align.cpp:
-//   align_harness <target.pcd|.f32> <source.pcd|.f32> <loam|ndt|vgicp|gicp> [init_pose.txt]
+//   align_harness <target.pcd|.f32> <source.pcd|.f32> <loam|ndt|vgicp|gicp> [init_pose.txt [ndt_search]]
+// (ndt_search: ndt only, NdtRegister::setNeighborhoodSearchMethod -- 1 DIRECT26, 2 DIRECT7 (the default), 3 DIRECT1)
 // loads two clouds (PCD files as align.cpp:97-107 does -- pcp/pcd_io.hpp -- or raw float32 x y z intensity records), reads the optional initial pose (4x4 row-major text,
 // align.cpp:85-93), voxel-filters BOTH clouds at 0.1 m (align.cpp:128-129), runs ONE scan2Map through the plugin mirror
 // (align.cpp:144), and prints what align.cpp logs: the cloud sizes before and after the filter, the elapsed time, the gated
@@ -46,7 +47,11 @@ int main(int argc, char** argv) {
         const std::string method = argv[3];
         PCR::PointCloudRegister::Ptr pcr;
         if (method == "loam") pcr = std::make_shared<PCR::LoamRegister>();
-        else if (method == "ndt") pcr = std::make_shared<PCR::NdtRegister>();
+        else if (method == "ndt") {
+            auto ndt = std::make_shared<PCR::NdtRegister>();
+            if (argc > 5) ndt->setNeighborhoodSearchMethod(std::stoi(argv[5]));
+            pcr = ndt;
+        }
         else if (method == "vgicp") pcr = std::make_shared<PCR::VgicpRegister>();
         else if (method == "gicp") pcr = std::make_shared<PCR::GicpRegister>();
         else { std::fprintf(stderr, "no such method!!\n"); return -1; }                                                   // align.cpp:118-121

@@ -32,6 +32,7 @@ class PcrParams(C.Structure):
         ("loam_pos_conv", C.c_double), ("loam_rot_conv", C.c_double),
         ("ndt_resolution", C.c_double), ("ndt_step_size", C.c_double), ("ndt_outlier_ratio", C.c_double),
         ("ndt_trans_eps", C.c_double), ("ndt_max_iters", C.c_int32), ("ndt_min_points", C.c_int32),
+        ("ndt_search", C.c_int32),
         ("vgicp_resolution", C.c_double), ("vgicp_k_corr", C.c_int32), ("vgicp_max_iters", C.c_int32),
         ("vgicp_lm_inner", C.c_int32), ("vgicp_rot_eps", C.c_double), ("vgicp_trans_eps", C.c_double),
         ("vgicp_lm_init_scale", C.c_double),
@@ -47,6 +48,8 @@ class PcrParams(C.Structure):
 # pcr_params.vgicp_regularization / vgicp_voxel_mode (include/pcr_hip.h: PCR_REG_*, PCR_VOXEL_*; fast_gicp's gicp_settings.hpp:6,10)
 REG_NONE, REG_MIN_EIG, REG_NORMALIZED_MIN_EIG, REG_PLANE, REG_FROBENIUS = range(5)
 VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = range(3)
+# pcr_params.ndt_search (include/pcr_hip.h: PCR_NDT_*; pclomp::NeighborSearchMethod, ndt_omp.h:52-57).  NDT_KDTREE is refused.
+NDT_KDTREE, NDT_DIRECT26, NDT_DIRECT7, NDT_DIRECT1 = range(4)
 
 
 class PcrStats(C.Structure):
@@ -725,7 +728,9 @@ class LoamRegister(PointCloudRegister):
 
 
 class NdtRegister(PointCloudRegister):
-    """PCR::NdtRegister (reference PCR/src/NdtRegister.cpp)."""
+    """PCR::NdtRegister (reference PCR/src/NdtRegister.cpp).  ndt_search=NDT_DIRECT26 | NDT_DIRECT7 | NDT_DIRECT1
+    (NormalDistributionsTransform::setNeighborhoodSearchMethod, default NDT_DIRECT7) is a keyword argument like every other field of
+    pcr_params, here and in make_register("ndt", ...); set_params changes it on a live handle and keeps the prepared target."""
     method = "ndt"
 
     def derivatives(self, src, p6, double_hessian=False, device_loop=False, kind=0):
