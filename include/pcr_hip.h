@@ -81,6 +81,22 @@ typedef struct pcr_params {
     double vgicp_rot_eps;      /* 2e-3 */
     double vgicp_trans_eps;    /* 5e-4 */
     double vgicp_lm_init_scale;/* 1e-9 */
+    /* fast_gicp::FastVGICP::setNeighborSearchMethod (third_parties/pclomp/src/pclomp/gicp_settings.hpp:8, fast_vgicp_impl.hpp:73-116,
+     * pclomp/fast_vgicp_voxel.hpp:10-44): which voxels a transformed scan point is paired with.  Read by vgicp handles ONLY (gicp, ndt and loam
+     * handles accept any served value and ignore it).  A value outside 0..3, and PCR_VGICP_DIRECT_RADIUS (the reference marks it "only
+     * VGICP_CUDA"), are refused by pcr_create and pcr_set_params.  A change through pcr_set_params KEEPS the prepared target -- the voxels do
+     * not depend on the neighbourhood -- and the correspondence buffers are sized again by the next call.  DIRECT7 and DIRECT27 are refused on
+     * a sharded handle (pcr_set_shard, pcr_comm_init*, pcr_set_params): a neighbour voxel may belong to another rank's tile. */
+    int32_t vgicp_search;      /* PCR_VGICP_*, default PCR_VGICP_DIRECT1 (fast_vgicp_impl.hpp:23).  With c = floor(T p / resolution - 0.5) per axis, in
+                                *    double, a PAIR (p, voxel) exists for every offset d of the setting's table for which the voxel c + d exists in the
+                                *    target; a cell outside the target's lattice box holds no voxel, and c + d is tested per axis, so a point whose own cell
+                                *    lies one layer outside the box still reaches the box's outer voxels under DIRECT7 / DIRECT27.
+                                *    DIRECT1 d = 0; DIRECT7 d = 0, then +x -x +y -y +z -z (fast_vgicp_voxel.hpp:21-29); DIRECT27 all of {-1, 0, 1}^3 with x
+                                *    outermost and z fastest, the centre INCLUDED (:31-41; unlike NDT's DIRECT26).
+                                *    Every pair is a term of H, b and the error exactly as the single pair is: M = (C_B + T C_A T^T)^-1, weight
+                                *    sqrt(num_points), J = [skew(T p) | -I]; compute_error at an LM trial pose reuses the pairs and the M of the last
+                                *    linearisation (fast_vgicp_impl.hpp:183-204).  A point's pairs are added in table order, then the fixed-order
+                                *    reduction: no atomics, the device loop equals the host loop and a repeated call gives the same bits. */
 
     int32_t record_trace;      /* 1: keep per-iteration normal equations for pcr_get_trace */
 
@@ -134,6 +150,12 @@ typedef struct pcr_params {
 #define PCR_NDT_DIRECT26 1
 #define PCR_NDT_DIRECT7 2
 #define PCR_NDT_DIRECT1 3
+
+/* pcr_params.vgicp_search: fast_gicp::NeighborSearchMethod, in the enum's order */
+#define PCR_VGICP_DIRECT27 0
+#define PCR_VGICP_DIRECT7 1
+#define PCR_VGICP_DIRECT1 2
+#define PCR_VGICP_DIRECT_RADIUS 3
 
 /* pcr_params.vgicp_regularization: fast_gicp::RegularizationMethod, in the enum's order */
 #define PCR_REG_NONE 0
@@ -256,7 +278,7 @@ int pcr_vgicp_neighbours(pcr_handle* h, size_t n, uint32_t* nbr_out, uint32_t* q
 /* (pcr_vgicp_covariances and pcr_vgicp_neighbours serve gicp handles too: the covariances are the same.) */
 /* One FastVGICP::linearize (fast_vgicp_impl.hpp:119-180) at `pose` against the current target
  * (pcr_set_target): H (36, row-major, twist = [rotation; translation]), b (6), sum of errors,
- * number of source points with a voxel correspondence. */
+ * number of (source point, voxel) pairs -- under PCR_VGICP_DIRECT1 the source points with a voxel correspondence. */
 int pcr_vgicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device,
                         const double pose[16], double H[36], double b[6], double* error, int64_t* n_corr);
 /* GICP introspection (a gicp handle).  One FastGICP::update_correspondences + linearize (fast_gicp_impl.hpp:120-211) at `pose` against the kept
@@ -476,6 +498,14 @@ typedef struct pcr_vgicp_voxel {
     double cov[6];
 } pcr_vgicp_voxel;
 int pcr_vgicp_voxels(pcr_handle* h, pcr_vgicp_voxel* out, size_t capacity, size_t* count);
+/* VGICP introspection: the pairs of the LAST pcr_vgicp_linearize on this handle (pcr_params.vgicp_search), one record per pair: row = the source
+ * point's row, ijk = the voxel's lattice coordinates (as pcr_vgicp_voxel's).  Ordered by row, a row's pairs in the order of the setting's table.
+ * *count = the pairs (pcr_vgicp_linearize's n_corr); out = NULL sizes the call; with out, capacity (in records) must be at least *count. */
+typedef struct pcr_vgicp_corr {
+    int32_t row;
+    int32_t ijk[3];
+} pcr_vgicp_corr;
+int pcr_vgicp_correspondences(pcr_handle* h, pcr_vgicp_corr* out, size_t capacity, size_t* count);
 /* NDT introspection: the sums of one pass as the device-resident loop of pcr_scan2map / pcr_align computes and folds them (one launch
  * per pass, the fold in the prologue of the next launch) -- where pcr_ndt_derivatives runs the kernels of the host-driven loop.  The
  * loop's own two launches on a state that asks for one pass at p and ends: the sums are read from the state the second launch hands on.
@@ -533,6 +563,8 @@ int pcr_comm_init_peer(pcr_handle* h, const void* ipc_handles, int rank, int nra
  *   vgicp  lo, hi on the voxel lattice ((k + 0.5) * vgicp_resolution, fast_vgicp_voxel.hpp:158-160) and a halo that holds
  *          the 20 nearest neighbours of every point of the tile (fast_gicp_impl.hpp:253): checked on the device for every
  *          point within one voxel of the tile -- a neighbourhood that reaches past the halo fails the call on all ranks.
+ *          pcr_params.vgicp_search must be PCR_VGICP_DIRECT1: under DIRECT7 / DIRECT27 a neighbour voxel may belong to another rank's tile, and
+ *          pcr_set_shard, pcr_comm_init* and pcr_set_params refuse the combination with a message that names the setting.
  * Misaligned bounds are refused.  lo[0] > hi[0] clears the tile. */
 int pcr_set_shard(pcr_handle* h, const double lo[3], const double hi[3], double halo);
 

@@ -244,6 +244,12 @@ const char* settings_out_of_range(const pcr_params& p) {
         return "ndt_search = 0 (KDTREE) is not served: the reference searches a kd-tree over float centroids summed in input order (the result "
                "depends on the order of the target's rows), returns voxels its own covariance test rejected, and needs FLANN; use 1 (DIRECT26), "
                "2 (DIRECT7) or 3 (DIRECT1)";
+    // fast_gicp::NeighborSearchMethod (gicp_settings.hpp:8).  Every handle is checked; only vgicp handles read the value.
+    if (p.vgicp_search < PCR_VGICP_DIRECT27 || p.vgicp_search > PCR_VGICP_DIRECT_RADIUS)
+        return "vgicp_search must be 0 (DIRECT27), 1 (DIRECT7) or 2 (DIRECT1); 3 (DIRECT_RADIUS) is not served";
+    if (p.vgicp_search == PCR_VGICP_DIRECT_RADIUS)
+        return "vgicp_search = 3 (DIRECT_RADIUS) is not served: the reference implements it in its CUDA variant only (gicp_settings.hpp:8) and "
+               "FastVGICP aborts on it (fast_vgicp_voxel.hpp:13-15); use 0 (DIRECT27), 1 (DIRECT7) or 2 (DIRECT1)";
     return nullptr;
 }
 }  // namespace
@@ -266,6 +272,7 @@ void pcr_default_params(pcr_params* p) {
     p->gicp_max_corr_dist = (double)FLT_MAX;
     p->vgicp_regularization = PCR_REG_PLANE; p->vgicp_voxel_mode = PCR_VOXEL_ADDITIVE;
     p->ndt_search = PCR_NDT_DIRECT7;
+    p->vgicp_search = PCR_VGICP_DIRECT1;
 }
 
 pcr_handle* pcr_create(const char* method, const pcr_params* p) {
@@ -473,6 +480,9 @@ int pcr_set_params(pcr_handle* h, const pcr_params* p) {
         const double need = ndt_halo_need(p->ndt_search, (double)(float)p->ndt_resolution);
         if (h->halo < need * (1.0 - 1e-12)) return fail(h, ndt_halo_message(p->ndt_search, need));
     }
+    // vgicp_search: the voxels do not depend on the neighbourhood, so the prepared target stays (the next call sizes the correspondence buffers by
+    // the setting in force); a sharded handle serves DIRECT1 only (nothing has been changed yet when it is refused)
+    if (const char* no = vgicp_search_shard_refusal(h, p->vgicp_search, false)) return fail(h, no);
     const pcr_params old = h->prm;
     h->prm = *p;
     h->prm.device = old.device;

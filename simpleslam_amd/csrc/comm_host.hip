@@ -202,6 +202,7 @@ int pcr_set_shard(pcr_handle* h, const double lo[3], const double hi[3], double 
         const double need = ndt_halo_need(h->prm.ndt_search, res);
         if (halo < need * (1.0 - 1e-12)) return fail(h, ndt_halo_message(h->prm.ndt_search, need));
     } else {
+        if (const char* no = vgicp_search_shard_refusal(h, h->prm.vgicp_search, true)) return fail(h, no);
         const double res = h->prm.vgicp_resolution;
         for (int d = 0; d < 3; ++d)
             if (!on_lattice(lo[d], res, 0.5) || !on_lattice(hi[d], res, 0.5))
@@ -220,6 +221,7 @@ int pcr_comm_init_host(pcr_handle* h, pcr_allreduce_fn fn, void* user, int rank,
     h->err.clear();
     if (!fn) { h->comm.host_ar = nullptr; h->comm.host_ar_user = nullptr; if (!h->comm.rccl) { h->comm.nranks = 1; h->comm.rank = 0; } return 0; }
     if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_comm_init_host)");
+    if (const char* no = vgicp_search_shard_refusal(h, h->prm.vgicp_search, true)) return fail(h, no);
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, "bad communicator arguments");
     if (h->comm.rccl) return fail(h, "an RCCL communicator is already set on this handle");
     if (h->stream) (void)hipStreamSynchronize(h->stream);
@@ -286,6 +288,7 @@ int pcr_comm_init_peer(pcr_handle* h, const void* ipc_handles, int rank, int nra
     if (!h) return 1;
     h->err.clear();
     if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_comm_init_peer)");
+    if (const char* no = vgicp_search_shard_refusal(h, h->prm.vgicp_search, true)) return fail(h, no);
     if (!ipc_handles || nranks < 1 || nranks > kMaxPeers || rank < 0 || rank >= nranks) return fail(h, "bad peer-exchange arguments (at most 8 ranks)");
     if (!h->comm.peer_own || !h->comm.peer_exported) return fail(h, "call pcr_comm_peer_export first (every rank, for every session), then share the handles");
     if (h->comm.rccl) return fail(h, "an RCCL communicator is already set on this handle");
@@ -318,6 +321,7 @@ int pcr_comm_init(pcr_handle* h, const void* unique_id128, int rank, int nranks)
     if (!h) return 1;
     h->err.clear();
     if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_comm_init)");
+    if (const char* no = vgicp_search_shard_refusal(h, h->prm.vgicp_search, true)) return fail(h, no);
     if (!unique_id128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(h, "bad communicator arguments");
     if (set_device(h)) return 1;
     std::lock_guard<std::mutex> lk(g_rccl_mu);

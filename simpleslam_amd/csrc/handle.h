@@ -121,6 +121,11 @@ struct pcr_handle {
         pcr::GridHeader cov_hdr0;        // header of the fine level of the last settle_cov_levels (density estimate)
         bool cov_l1_ahead = false;       // ... and whether that build is the one in h->cov_l1 now
         pcr::DeviceBuf tgt_cov6, src_cov6, vox, corr_slot, corr_M, corr_slot2, corr_M2;
+        pcr::DeviceBuf corr_T, corr_T2;  // pcr_params.vgicp_search = DIRECT7 / DIRECT27: the pose of the linearisation that wrote corr_slot / corr_slot2 (VgicpArgs::corr_T)
+        // the last pcr_vgicp_linearize, for pcr_vgicp_correspondences: its source rows and setting (corr_slot holds its pairs); any other call over a source drops it
+        bool lin_valid = false;
+        size_t lin_n = 0;
+        int lin_search = 0;
         pcr::CovScratch src_scratch, tgt_scratch;   // neighbour lists + queue of the covariance search of a scan-sized cloud: the source's runs on the side stream beside the target's
         bool target_ready = false;       // (read by pcr_scan2map_submap; dropped by pcr_set_params, pcr_set_shard, pcr_invalidate_target)
         pcr::DeviceBuf reduced;              // sharded VGICP over the peer exchange: a pass's 32 sums folded over the rows and the ranks
@@ -227,6 +232,14 @@ extern thread_local std::string g_create_error;
 
 inline int fail(pcr_handle* h, const std::string& msg) { h->err = msg; return 1; }
 inline bool sharded(const pcr_handle* h) { return h->comm.rccl != nullptr || h->comm.host_ar != nullptr || h->comm.peer_on; }
+// pcr_params.vgicp_search beyond DIRECT1 on a vgicp handle that has a tile or a communicator: a neighbour voxel may belong to another rank's tile, and no
+// halo rule serves that yet.  The refusal of pcr_set_shard, pcr_comm_init* and pcr_set_params, naming the setting; nullptr when there is nothing to refuse.
+inline const char* vgicp_search_shard_refusal(const pcr_handle* h, int search, bool becoming_sharded) {
+    if (h->method != kVgicp || search == PCR_VGICP_DIRECT1 || !(becoming_sharded || sharded(h) || h->use_tile)) return nullptr;
+    return search == PCR_VGICP_DIRECT7
+        ? "vgicp: pcr_params.vgicp_search = 1 (DIRECT7) is not served on a sharded handle (a neighbour voxel may belong to another rank's tile); use 2 (DIRECT1)"
+        : "vgicp: pcr_params.vgicp_search = 0 (DIRECT27) is not served on a sharded handle (a neighbour voxel may belong to another rank's tile); use 2 (DIRECT1)";
+}
 // profiling passes: the counters the kernels add to, or nullptr
 inline uint32_t* prof_counters(const pcr_handle* h) { return (h->profile >= 2 && h->prof_count.p) ? h->prof_count.as<uint32_t>() : nullptr; }
 // Whatever the scan's side has in flight on the side stream is waited for: nothing stays in flight behind the caller's back.

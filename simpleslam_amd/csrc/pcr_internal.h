@@ -301,12 +301,16 @@ struct VgicpArgs {
     const GridHeader* hdr;       // target index header (voxel lattice = index grid shifted by half a cell)
     const uint32_t* cell_start;  // of the target index: voxel = cell, stored at the position of the cell's first point
     const VgicpVoxel* vox;
-    uint32_t* corr_slot;         // [n_src] voxel slot + 1 of the correspondence, 0 = none
-    double* corr_M;              // [n_src][6] Mahalanobis matrix of the correspondence
-    uint32_t* corr_slot_next;    // the same two for the linearisation an LM trial pass computes ahead (vgicp_launch_error)
+    uint32_t* corr_slot;         // DIRECT1: [n_src] voxel slot + 1 of the correspondence, 0 = none.  DIRECT7 / DIRECT27 (K = 7 / 27 table entries):
+                                 //   [K + 1][n_src] -- row k the slot + 1 of the pair with table entry k, row K the point's presence bits (bit k)
+    double* corr_M;              // DIRECT1: [n_src][6] Mahalanobis matrix of the correspondence.  DIRECT7 / DIRECT27: not used (vgicp.hip: storage)
+    double* corr_T;              // DIRECT7 / DIRECT27: [16] the pose of the linearisation that wrote corr_slot: compute_error derives every pair's M from it
+    uint32_t* corr_slot_next;    // the same three for the linearisation an LM trial pass computes ahead (vgicp_launch_error)
     double* corr_M_next;
+    double* corr_T_next;
     double* partials;            // [blocks][32]
-    int32_t use_tile, pad_;      // sharded target: only source points whose transformed position lies in [tile_lo, tile_hi)
+    int32_t use_tile;            // sharded target: only source points whose transformed position lies in [tile_lo, tile_hi)
+    int32_t search;              // pcr_params.vgicp_search (PCR_VGICP_DIRECT*): read by the HOST launchers only, which pick the kernel instantiation by it
     double tile_lo[3], tile_hi[3];
     uint32_t* escapes;           // target index cut to the bulk of the cloud (header.clamped): count of source points that land within
     int32_t guard_cells, pad2_;  //   guard_cells voxels of a face with target points beyond it (their voxels' covariances may lack neighbours); else NULL
@@ -314,7 +318,11 @@ struct VgicpArgs {
 };
 // the arguments of a pass whose state has `parity` set: the two pairs of correspondence buffers change places (VgCtl::parity)
 __host__ __device__ inline VgicpArgs swapped(VgicpArgs a, int parity) {
-    if (parity) { uint32_t* const s = a.corr_slot; a.corr_slot = a.corr_slot_next; a.corr_slot_next = s; double* const m = a.corr_M; a.corr_M = a.corr_M_next; a.corr_M_next = m; }
+    if (parity) {
+        uint32_t* const s = a.corr_slot; a.corr_slot = a.corr_slot_next; a.corr_slot_next = s;
+        double* const m = a.corr_M; a.corr_M = a.corr_M_next; a.corr_M_next = m;
+        double* const t = a.corr_T; a.corr_T = a.corr_T_next; a.corr_T_next = t;
+    }
     return a;
 }
 

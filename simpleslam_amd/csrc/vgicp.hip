@@ -10,8 +10,9 @@
 //      pcr_params.vgicp_voxel_mode)
 //      -> vgicp_voxel_kernel: one thread per voxel, fixed-point sums (order independent)
 //   V4/V5 correspondences, Mahalanobis, linearize, compute_error   fast_vgicp_impl.hpp:73-204
-//      -> vgicp_linearize_kernel<false> (linearize) and <true> (compute_error of an LM trial pose + the linearisation at
-//         that pose in the same pass), fixed-order reductions
+//      -> vgicp_linearize_kernel<false, kSearch> (linearize) and <true, kSearch> (compute_error of an LM trial pose + the linearisation at
+//         that pose in the same pass), fixed-order reductions; kSearch = pcr_params.vgicp_search: DIRECT1 one voxel per point, DIRECT7 /
+//         DIRECT27 every occupied voxel of the 7 / 27 cells around it (fast_vgicp_voxel.hpp:10-44)
 //   V6 LM driver                  lsq_registration_impl.hpp:53-171 -> lsq_pass.h (the pass and the device loop's prologue), lsq_host.h: run_lsq
 // Also the PCL fitness score (pcl::Registration::getFitnessScore, VgicpRegister.cpp:42-45).
 #include <float.h>
@@ -304,10 +305,226 @@ __device__ __forceinline__ uint32_t vgicp_lookup(const GridHeader& h, const uint
     return e > s ? s + 1 : 0;
 }
 
+// ------------------------------------------------------------------------------
+// neighbourhood (pcr_params.vgicp_search; fast_vgicp_voxel.hpp:10-44, fast_vgicp_impl.hpp:73-116): kSearch is a template parameter of the
+// per-point functions, of VgicpPass and of the kernels that hold them, chosen on the host (VGICP_SEARCH_DISPATCH).
+//   DIRECT1   the point's own voxel: the code this unit had before the setting (vgicp_lookup, one slot and one M per point)
+//   DIRECT7   table: centre, +x -x +y -y +z -z          DIRECT27   table: {-1, 0, 1}^3, x outermost, z fastest, the centre INCLUDED
+// Under DIRECT7 / DIRECT27 a point has up to K = 7 / 27 pairs, one per table entry k whose voxel c + d_k exists; c + d_k is tested against
+// the lattice box per axis, so a point whose own cell lies one layer outside the box still reaches the box's outer voxels.
+// Two steps per point.  The LOOKUP walks the rows of the block -- the cell table is dense with x fastest, so the three cells of an x-row are four
+// adjacent words -- and leaves slot + 1 (0: none) of entry k at corr_slot[k][i] and the presence bits at corr_slot[K][i]: [K + 1][n_src], every
+// store and every later load coalesced over the wave.  The PAIR LOOP takes the set bits lowest first, which IS table order, and adds each
+// pair's terms into the thread's 28 sums; it is not unrolled (27 copies of the body would not fit the instruction cache).
+// Storage: M is NOT kept per pair.  DIRECT27 would write 27 x 48 B per point and pass (85 MB for a 65 536-point scan, twice that allocated for
+// the two buffer pairs) and read it back in compute_error; M = (C_B + T0 C_A T0^T)^-1 costs ~60 flops from the voxel record compute_error reads
+// anyway (its mean and weight share the record with C_B).  So the linearisation leaves its pose T0 beside its slots (corr_T) and
+// compute_error derives M again: T0 C_A T0^T once per point, one 3 x 3 inverse per pair.
+// ------------------------------------------------------------------------------
+template <int kSearch> constexpr int kVgPairs = kSearch == PCR_VGICP_DIRECT27 ? 27 : kSearch == PCR_VGICP_DIRECT7 ? 7 : 1;
+
+// the table entry of offset (dx, dy, dz), -1 when the table has none (constant after unrolling)
+template <int kSearch>
+__device__ __forceinline__ constexpr int vg_entry(int dx, int dy, int dz) {
+    if (kSearch == PCR_VGICP_DIRECT27) return (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1);
+    if (dx == 0 && dy == 0 && dz == 0) return 0;
+    if (kSearch != PCR_VGICP_DIRECT7) return -1;
+    if (dy == 0 && dz == 0) return dx > 0 ? 1 : 2;
+    if (dx == 0 && dz == 0) return dy > 0 ? 3 : 4;
+    if (dx == 0 && dy == 0) return dz > 0 ? 5 : 6;
+    return -1;
+}
+// ... and the offset of entry k
+template <int kSearch>
+__device__ __forceinline__ void vg_offset(int k, int d[3]) {
+    if constexpr (kSearch == PCR_VGICP_DIRECT27) {
+        const int kx = k / 9, r = k - kx * 9, ky = r / 3;
+        d[0] = kx - 1; d[1] = ky - 1; d[2] = r - ky * 3 - 1;
+    } else {
+        const int axis = (k - 1) >> 1, sgn = (k & 1) ? 1 : -1;      // 1 +x, 2 -x, 3 +y, 4 -y, 5 +z, 6 -z; 0: the centre (axis = -1)
+        d[0] = axis == 0 ? sgn : 0; d[1] = axis == 1 ? sgn : 0; d[2] = axis == 2 ? sgn : 0;
+    }
+}
+
+// the centre cell of a transformed point in the box's coordinates, or (-4, -4, -4) -- from where no table entry reaches the box -- when the index
+// holds nothing or the point lies more than one layer outside
+__device__ __forceinline__ void vg_centre(const GridHeader& h, const double tp[3], int c[3]) {
+    const double fx = floor(tp[0] / h.cell - h.shift) - h.org[0], fy = floor(tp[1] / h.cell - h.shift) - h.org[1], fz = floor(tp[2] / h.cell - h.shift) - h.org[2];
+    const bool ok = !(h.overflow || h.empty) && fx >= -1.0 && fx <= (double)h.dims[0] && fy >= -1.0 && fy <= (double)h.dims[1] && fz >= -1.0 && fz <= (double)h.dims[2];
+    c[0] = ok ? (int)fx : -4; c[1] = ok ? (int)fy : -4; c[2] = ok ? (int)fz : -4;
+}
+
+// the lookup of one point: slot + 1 of every table entry to slot_out[k][i], the presence bits to slot_out[K][i] and back.  A neighbour outside a
+// region-only mask is an escape exactly as a centre is (vgicp_lookup).
+template <int kSearch>
+__device__ __forceinline__ uint32_t vgicp_neighbours(const GridHeader& h, const uint32_t* __restrict__ cell_start, const int c[3], const RoiView& roi,
+                                                     uint32_t i, uint32_t n_src, uint32_t* __restrict__ slot_out) {
+    constexpr int K = kVgPairs<kSearch>;
+    const int d0 = h.dims[0], d1 = h.dims[1], d2 = h.dims[2];
+    uint32_t mask = 0u;
+#pragma unroll
+    for (int dz = -1; dz <= 1; ++dz) {
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+            const bool side = vg_entry<kSearch>(-1, dy, dz) >= 0 || vg_entry<kSearch>(1, dy, dz) >= 0;
+            if (!side && vg_entry<kSearch>(0, dy, dz) < 0) continue;      // (a row DIRECT7's table does not touch)
+            const int y = c[1] + dy, z = c[2] + dz;
+            const bool row_ok = y >= 0 && y < d1 && z >= 0 && z < d2;
+            const uint32_t base = ((uint32_t)z * (uint32_t)d1 + (uint32_t)y) * (uint32_t)d0;
+            // the row's words c[0] - 1 .. c[0] + 2 of the cell table (the table has one entry past the last cell): cell x is [w[x - c[0] + 1], w[x - c[0] + 2])
+            uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int j = side ? 0 : 1; j < (side ? 4 : 3); ++j) {
+                const int x = c[0] - 1 + j;
+                if (row_ok && x >= 0 && x <= d0) w[j] = cell_start[base + (uint32_t)x];
+            }
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int k = vg_entry<kSearch>(dx, dy, dz);
+                if (k < 0) continue;
+                const int x = c[0] + dx;
+                uint32_t slot = 0u;
+                if (row_ok && x >= 0 && x < d0) {
+                    const uint32_t s = w[dx + 1], e = w[dx + 2];
+                    const bool outside = roi.mask && roi.mask[roi_macro(h, roi.mshift, x, y, z)] == 0;
+                    // (a region-only index holds nothing outside the mask: there the words are not the whole target's, and the lookup is an escape
+                    //  whether or not a voxel is there)
+                    if (outside && (roi.filtered || e > s)) atomicAdd(roi.escapes, 1u);
+                    else if (e > s) slot = s + 1u;
+                }
+                slot_out[(size_t)k * n_src + i] = slot;
+                mask |= slot ? 1u << k : 0u;
+            }
+        }
+    }
+    slot_out[(size_t)K * n_src + i] = mask;
+    return mask;
+}
+
+// T C_A T^T of a source point (upper triangle), the part of a pair's combined covariance that does not depend on the voxel
+__device__ __forceinline__ void vg_rcr(const Pose16& T, const double* __restrict__ ca, double R6[6]) {
+    const double CA[3][3] = {{ca[0], ca[1], ca[2]}, {ca[1], ca[3], ca[4]}, {ca[2], ca[4], ca[5]}};
+    double RC[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) RC[r][c] = T.m[r] * CA[0][c] + T.m[4 + r] * CA[1][c] + T.m[8 + r] * CA[2][c];
+    int o = 0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = r; c < 3; ++c) { R6[o] = RC[r][0] * T.m[c] + RC[r][1] * T.m[4 + c] + RC[r][2] * T.m[8 + c]; ++o; }
+}
+
+// update_correspondences + linearize of one source point over its pairs (DIRECT7, DIRECT27): every pair's terms added to v in table order
+template <int kSearch>
+__device__ __forceinline__ void vgicp_lin_pairs(const VgicpArgs& a, const GridHeader& h, const Pose16& T, uint32_t i, double v[28],
+                                                uint32_t* __restrict__ slot_out, double* __restrict__ T_out) {
+    if (i == 0) {      // the pose these pairs belong to, for compute_error (one thread of the launch)
+#pragma unroll
+        for (int k = 0; k < 16; ++k) T_out[k] = T.m[k];
+    }
+    const float* sp = a.src + (size_t)i * a.src_stride;
+    const double p[3] = {(double)sp[0], (double)sp[1], (double)sp[2]};
+    double tp[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) tp[r] = T.m[r] * p[0] + T.m[4 + r] * p[1] + T.m[8 + r] * p[2] + T.m[12 + r] * 1.0;
+    int c[3];
+    vg_centre(h, tp, c);
+    if (a.use_tile && !(tp[0] >= a.tile_lo[0] && tp[0] < a.tile_hi[0] && tp[1] >= a.tile_lo[1] && tp[1] < a.tile_hi[1] &&
+                        tp[2] >= a.tile_lo[2] && tp[2] < a.tile_hi[2])) c[0] = c[1] = c[2] = -4;      // (a query tile: the host refuses these settings on a sharded handle)
+    uint32_t mask = vgicp_neighbours<kSearch>(h, a.cell_start, c, a.roi, i, a.n_src, slot_out);
+    if (a.escapes && h.clamped) {
+        // a cut index (vgicp_lin_point): guard_cells already holds the voxel these settings reach beyond the point's own
+        const double cc[3] = {floor(tp[0] / h.cell - h.shift) - h.org[0], floor(tp[1] / h.cell - h.shift) - h.org[1], floor(tp[2] / h.cell - h.shift) - h.org[2]};
+        const double g = (double)(kPad + a.guard_cells);
+        bool esc = false;
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+            esc = esc || ((h.cut_mask & (1 << d)) && cc[d] < g) || ((h.cut_mask & (8 << d)) && cc[d] >= (double)h.dims[d] - g);
+        if (esc) atomicAdd(a.escapes, 1u);
+    }
+    if (!mask) return;
+    double R6[6];
+    vg_rcr(T, a.src_cov6 + (size_t)i * 6, R6);
+    // J = [skew(Tp) | -I]   fast_vgicp_impl.hpp:156-158, so3.hpp:21-31
+    const double J[3][6] = {{0, -tp[2], tp[1], -1, 0, 0}, {tp[2], 0, -tp[0], 0, -1, 0}, {-tp[1], tp[0], 0, 0, 0, -1}};
+#pragma unroll 1
+    while (mask) {
+        const int k = __builtin_ctz(mask);
+        mask &= mask - 1u;
+        int d[3];
+        vg_offset<kSearch>(k, d);
+        // (inside the box and occupied: the bit was set from this cell's words; read again from the cache)
+        const uint32_t key = ((uint32_t)(c[2] + d[2]) * (uint32_t)h.dims[1] + (uint32_t)(c[1] + d[1])) * (uint32_t)h.dims[0] + (uint32_t)(c[0] + d[0]);
+        const VgicpVoxel vx = a.vox[a.cell_start[key]];
+        double S[6], M6[6];
+#pragma unroll
+        for (int o = 0; o < 6; ++o) S[o] = vx.cov[o] + R6[o];
+        inv3_sym(S, M6);   // (C_B + T C_A T^T)^-1, fast_vgicp_impl.hpp:104-115
+        const double M[3][3] = {{M6[0], M6[1], M6[2]}, {M6[1], M6[3], M6[4]}, {M6[2], M6[4], M6[5]}};
+        const double er[3] = {vx.mean[0] - tp[0], vx.mean[1] - tp[1], vx.mean[2] - tp[2]};
+        double Me[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) Me[r] = M[r][0] * er[0] + M[r][1] * er[1] + M[r][2] * er[2];
+        const double w = vx.w;
+        double MJ[3][6];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int cc = 0; cc < 6; ++cc) MJ[r][cc] = M[r][0] * J[0][cc] + M[r][1] * J[1][cc] + M[r][2] * J[2][cc];
+        int q = 0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int cc = r; cc < 6; ++cc) v[q++] += w * (J[0][r] * MJ[0][cc] + J[1][r] * MJ[1][cc] + J[2][r] * MJ[2][cc]);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) v[21 + r] += w * (J[0][r] * Me[0] + J[1][r] * Me[1] + J[2][r] * Me[2]);
+        v[27] += w * (er[0] * Me[0] + er[1] * Me[1] + er[2] * Me[2]);
+    }
+}
+
+// compute_error of one point over the pairs of the LAST linearisation (DIRECT7, DIRECT27): its slots, and every M derived again from its pose
+template <int kSearch>
+__device__ __forceinline__ double vgicp_err_pairs(const VgicpArgs& a, const Pose16& T, uint32_t i) {
+    constexpr int K = kVgPairs<kSearch>;
+    uint32_t mask = a.corr_slot[(size_t)K * a.n_src + i];
+    if (!mask) return 0.0;
+    Pose16 T0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) T0.m[k] = a.corr_T[k];
+    double R6[6];
+    vg_rcr(T0, a.src_cov6 + (size_t)i * 6, R6);
+    const float* sp = a.src + (size_t)i * a.src_stride;
+    const double p[3] = {(double)sp[0], (double)sp[1], (double)sp[2]};
+    double tp[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) tp[r] = T.m[r] * p[0] + T.m[4 + r] * p[1] + T.m[8 + r] * p[2] + T.m[12 + r] * 1.0;
+    double sum = 0.0;
+#pragma unroll 1
+    while (mask) {
+        const int k = __builtin_ctz(mask);
+        mask &= mask - 1u;
+        const VgicpVoxel vx = a.vox[a.corr_slot[(size_t)k * a.n_src + i] - 1u];
+        double S[6], M6[6];
+#pragma unroll
+        for (int o = 0; o < 6; ++o) S[o] = vx.cov[o] + R6[o];
+        inv3_sym(S, M6);
+        const double er[3] = {vx.mean[0] - tp[0], vx.mean[1] - tp[1], vx.mean[2] - tp[2]};
+        const double Me0 = M6[0] * er[0] + M6[1] * er[1] + M6[2] * er[2], Me1 = M6[1] * er[0] + M6[3] * er[1] + M6[4] * er[2],
+                     Me2 = M6[2] * er[0] + M6[4] * er[1] + M6[5] * er[2];
+        sum += vx.w * (er[0] * Me0 + er[1] * Me1 + er[2] * Me2);
+    }
+    return sum;
+}
+
 // one source point of update_correspondences + linearize at pose T: v[0..20] H (upper triangle), v[21..26] b, v[27] error;
-// the correspondence (voxel slot, Mahalanobis matrix) goes to slot_out / M_out
+// the correspondence (voxel slot, Mahalanobis matrix) goes to slot_out / M_out -- DIRECT7 / DIRECT27: the pairs' slots to slot_out, the pose to T_out
+template <int kSearch>
 __device__ __forceinline__ void vgicp_lin_point(const VgicpArgs& a, const GridHeader& h, const Pose16& T, uint32_t i, double v[28],
-                                                uint32_t* __restrict__ slot_out, double* __restrict__ M_out) {
+                                                uint32_t* __restrict__ slot_out, double* __restrict__ M_out, double* __restrict__ T_out) {
+    static_assert(kSearch == PCR_VGICP_DIRECT27 || kSearch == PCR_VGICP_DIRECT7 || kSearch == PCR_VGICP_DIRECT1, "kSearch must be PCR_VGICP_DIRECT27, _DIRECT7 or _DIRECT1");
+    if constexpr (kSearch != PCR_VGICP_DIRECT1) { vgicp_lin_pairs<kSearch>(a, h, T, i, v, slot_out, T_out); return; }
     const float* sp = a.src + (size_t)i * a.src_stride;
     const double p[3] = {(double)sp[0], (double)sp[1], (double)sp[2]};
     double tp[3];
@@ -372,7 +589,9 @@ __device__ __forceinline__ void vgicp_lin_point(const VgicpArgs& a, const GridHe
 
 // compute_error (fast_vgicp_impl.hpp:183-204) of one point: the correspondences and Mahalanobis matrices of the LAST
 // linearisation, new pose
+template <int kSearch>
 __device__ __forceinline__ double vgicp_err_point(const VgicpArgs& a, const Pose16& T, uint32_t i) {
+    if constexpr (kSearch != PCR_VGICP_DIRECT1) return vgicp_err_pairs<kSearch>(a, T, i);
     const uint32_t slot = a.corr_slot[i];
     if (!slot) return 0.0;
     const float* sp = a.src + (size_t)i * a.src_stride;
@@ -388,30 +607,32 @@ __device__ __forceinline__ double vgicp_err_point(const VgicpArgs& a, const Pose
 }
 
 // The pass of lsq_pass.h over VGICP's voxel correspondences: the launch's arguments and the target index header, loaded once
+template <int kSearch>
 struct VgicpPass {
     const VgicpArgs& a;
     const GridHeader h;
     __device__ __forceinline__ explicit VgicpPass(const VgicpArgs& a_) : a(a_), h(*a_.hdr) {}
     __device__ __forceinline__ void lin(const Pose16& T, uint32_t i, double v[28], bool to_next) const {
-        vgicp_lin_point(a, h, T, i, v, to_next ? a.corr_slot_next : a.corr_slot, to_next ? a.corr_M_next : a.corr_M);
+        vgicp_lin_point<kSearch>(a, h, T, i, v, to_next ? a.corr_slot_next : a.corr_slot, to_next ? a.corr_M_next : a.corr_M, to_next ? a.corr_T_next : a.corr_T);
     }
-    __device__ __forceinline__ double err(const Pose16& T, uint32_t i) const { return vgicp_err_point(a, T, i); }
+    __device__ __forceinline__ double err(const Pose16& T, uint32_t i) const { return vgicp_err_point<kSearch>(a, T, i); }
 };
 
-template <bool kWithError>
+template <bool kWithError, int kSearch>
 __global__ __launch_bounds__(256) void vgicp_linearize_kernel(const VgicpArgs a, const Pose16 T) {
     __shared__ double sh[(kWithError ? 29 : 28) * kLinStride];
     __shared__ double sh_sum[8 * 32];
-    lsq_lin_body<kWithError>(VgicpPass(a), T, a.n_src, a.partials, sh, sh_sum);
+    lsq_lin_body<kWithError>(VgicpPass<kSearch>(a), T, a.n_src, a.partials, sh, sh_sum);
 }
 
 // a launch of the device-resident Levenberg-Marquardt loop (lsq_pass.h); roi: a target prepared for one scan reports its escapes with the result
+template <int kSearch>
 __global__ __launch_bounds__(256) void vgicp_pass_pro_kernel(const VgicpArgs a, const LsqProArgs pa) {
     __shared__ double sh[29 * kLinStride];
     __shared__ double sh_sum[8 * 32];
     __shared__ __attribute__((aligned(16))) uint32_t sh_ctl[kVgCtlWords];
     __shared__ double sh_sums[32];
-    lsq_pass<true, VgicpPass>(a, pa, a.roi.mask ? a.roi.escapes : nullptr, sh, sh_sum, sh_ctl, sh_sums);
+    lsq_pass<true, VgicpPass<kSearch>>(a, pa, a.roi.mask ? a.roi.escapes : nullptr, sh, sh_sum, sh_ctl, sh_sums);
 }
 
 // Sharded targets over the peer exchange (pcr_comm_init_peer): between two passes ONE launch folds this rank's rows of the pass that has just run --
@@ -595,9 +816,18 @@ uint32_t vgicp_blocks(uint32_t n_src) {
     return b < 1 ? 1 : (b > 512 ? 512 : b);
 }
 
+// pcr_params.vgicp_search -> the kernel instantiation (VgicpArgs::search; validated by pcr_create / pcr_set_params)
+#define VGICP_SEARCH_DISPATCH(search, CALL) \
+    switch (search) { \
+        case PCR_VGICP_DIRECT27: { constexpr int kSearch = PCR_VGICP_DIRECT27; CALL; } break; \
+        case PCR_VGICP_DIRECT7: { constexpr int kSearch = PCR_VGICP_DIRECT7; CALL; } break; \
+        case PCR_VGICP_DIRECT1: { constexpr int kSearch = PCR_VGICP_DIRECT1; CALL; } break; \
+        default: return hipErrorInvalidValue; \
+    }
+
 hipError_t vgicp_launch_linearize(const VgicpArgs& a, const Pose16& T, double* d_out32, hipStream_t s, double seq) {
     const uint32_t nb = vgicp_blocks(a.n_src);
-    hipLaunchKernelGGL(vgicp_linearize_kernel<false>, dim3(nb), dim3(256), 0, s, a, T);
+    VGICP_SEARCH_DISPATCH(a.search, hipLaunchKernelGGL((vgicp_linearize_kernel<false, kSearch>), dim3(nb), dim3(256), 0, s, a, T))
     return sum_partials_launch(a.partials, nb, d_out32, s, seq);
 }
 
@@ -621,13 +851,13 @@ hipError_t vgicp_launch_pass_pro(const VgicpArgs& a_in, VgCtl* d_ctl2, double* d
     LsqProArgs pa = lsq_pro_args(d_ctl2, d_rows2, d_out, seq, index, nb);
     pa.reduced = pc ? d_reduced : nullptr;
     if (pc && index > 0) hipLaunchKernelGGL(vgicp_peer_exchange_kernel, dim3(1), dim3(256), 0, s, pa.rows_prev, nb, pa.ctl_prev, *pc, xseq, d_reduced);
-    hipLaunchKernelGGL(vgicp_pass_pro_kernel, dim3(nb), dim3(256), 0, s, a, pa);
+    VGICP_SEARCH_DISPATCH(a.search, hipLaunchKernelGGL(vgicp_pass_pro_kernel<kSearch>, dim3(nb), dim3(256), 0, s, a, pa))
     return hipGetLastError();
 }
 
 hipError_t vgicp_launch_error(const VgicpArgs& a, const Pose16& T, double* d_out32, hipStream_t s, double seq) {
     const uint32_t nb = vgicp_blocks(a.n_src);
-    hipLaunchKernelGGL(vgicp_linearize_kernel<true>, dim3(nb), dim3(256), 0, s, a, T);
+    VGICP_SEARCH_DISPATCH(a.search, hipLaunchKernelGGL((vgicp_linearize_kernel<true, kSearch>), dim3(nb), dim3(256), 0, s, a, T))
     return sum_partials_launch(a.partials, nb, d_out32, s, seq);
 }
 

@@ -323,6 +323,11 @@ RoiView roi_view(const pcr_handle* h) {      // the region the handle's target w
     return v;
 }
 
+// The base margin, in metres, of the region a VGICP target is prepared for: 1 m of translation, plus the voxel that DIRECT7 / DIRECT27 reach beyond
+// the cell a point lands in (pcr_params.vgicp_search).  The region is a dilation by a Chebyshev radius -- a box, not a ball (grid_index.hip) -- so
+// the one voxel per axis that holds DIRECT7's face cells holds DIRECT27's edge and corner cells as well.  DIRECT1 keeps what it had.
+static double vgicp_roi_margin(int search, double res) { return search == PCR_VGICP_DIRECT1 ? 1.0 : 1.0 + res; }
+
 // keep_clamp: the caller has set h->clamp (a region cut around a scan, vgicp_align_recut): index that region instead of deciding here
 int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, const RoiScan* roi_scan, bool keep_clamp,
                          const std::function<int()>* before_wait) {
@@ -351,7 +356,7 @@ int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t
     // lookups that test the mask first (vgicp.hip: vgicp_lookup, RoiView::filtered).
     BuildFilter bf;
     bf.enqueue_mask = [&]() -> hipError_t {
-        if (roi_enqueue(h, *roi_scan, res, 1.0, &roi)) return hipErrorUnknown;      // 1 m of translation + 0.05 rad
+        if (roi_enqueue(h, *roi_scan, res, vgicp_roi_margin(h->prm.vgicp_search, res), &roi)) return hipErrorUnknown;      // 1 m of translation (+ the neighbourhood's voxel) + 0.05 rad
         bf.mask = roi.mask; bf.mshift = roi.mshift;
         return hipSuccess;
     };
@@ -361,7 +366,7 @@ int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t
             roi.filtered = 1;
             h->roi_on = true;
         } else if (want_roi && !h->clamp.use) {
-            if (roi_enqueue(h, *roi_scan, res, 1.0, &roi)) return 1;      // 1 m of translation + 0.05 rad
+            if (roi_enqueue(h, *roi_scan, res, vgicp_roi_margin(h->prm.vgicp_search, res), &roi)) return 1;      // 1 m of translation (+ the neighbourhood's voxel) + 0.05 rad
             h->roi_on = true;
         }
         H_TRY(vgicp_launch_cov(*cov_grid, cov_levels(n_dst) > 1 ? &h->cov_l1 : nullptr, cov_levels(n_dst) > 2 ? &h->vg.cov_l2 : nullptr, d_dst, stride_floats,
@@ -430,6 +435,9 @@ int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t
 
 namespace {
 
+// entries of the table of a pcr_params.vgicp_search (rows of slots in VgicpArgs::corr_slot)
+size_t vgicp_table_entries(int search) { return search == PCR_VGICP_DIRECT27 ? 27 : search == PCR_VGICP_DIRECT7 ? 7 : 1; }
+
 // The arguments of the handle's VGICP launches over a source (run_vgicp, pcr_vgicp_linearize): the whole target prepared, the index not cut
 VgicpArgs vgicp_args(const pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats) {
     VgicpArgs a;
@@ -441,8 +449,10 @@ VgicpArgs vgicp_args(const pcr_handle* h, const float* d_src, size_t n_src, size
     a.vox = h->vg.vox.as<VgicpVoxel>();
     a.corr_slot = h->vg.corr_slot.as<uint32_t>(); a.corr_M = h->vg.corr_M.as<double>();
     a.corr_slot_next = h->vg.corr_slot2.as<uint32_t>(); a.corr_M_next = h->vg.corr_M2.as<double>();
+    a.corr_T = h->vg.corr_T.as<double>(); a.corr_T_next = h->vg.corr_T2.as<double>();
     a.partials = h->vg_partials.as<double>();
     a.use_tile = h->use_tile;
+    a.search = h->prm.vgicp_search;
     for (int d = 0; d < 3; ++d) { a.tile_lo[d] = h->tile_lo[d]; a.tile_hi[d] = h->tile_hi[d]; }
     return a;
 }
@@ -456,10 +466,21 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
     // scan2map call, computed here otherwise
     if (vgicp_source_settle(h, d_src, n_src, stride_floats)) return 1;
     if (keep_scan_for_fitness(h, d_src, n_src, stride_floats, kept)) return 1;
-    H_TRY(h->vg.corr_slot.reserve((n_src + 1) * sizeof(uint32_t)));
-    H_TRY(h->vg.corr_M.reserve((n_src + 1) * 6 * sizeof(double)));
-    H_TRY(h->vg.corr_slot2.reserve((n_src + 1) * sizeof(uint32_t)));
-    H_TRY(h->vg.corr_M2.reserve((n_src + 1) * 6 * sizeof(double)));
+    // the correspondence buffers, by the neighbourhood in force (VgicpArgs): DIRECT1 a slot and an M per point; DIRECT7 / DIRECT27 K + 1 rows of slots and
+    // the linearisation's pose
+    h->vg.lin_valid = false;
+    const int search = h->prm.vgicp_search;
+    if (sharded(h) && search != PCR_VGICP_DIRECT1) return fail(h, "internal: vgicp_search beyond DIRECT1 on a sharded handle");
+    const size_t slot_rows = search == PCR_VGICP_DIRECT1 ? 1 : vgicp_table_entries(search) + 1;
+    H_TRY(h->vg.corr_slot.reserve((n_src + 1) * slot_rows * sizeof(uint32_t)));
+    H_TRY(h->vg.corr_slot2.reserve((n_src + 1) * slot_rows * sizeof(uint32_t)));
+    if (search == PCR_VGICP_DIRECT1) {
+        H_TRY(h->vg.corr_M.reserve((n_src + 1) * 6 * sizeof(double)));
+        H_TRY(h->vg.corr_M2.reserve((n_src + 1) * 6 * sizeof(double)));
+    } else {
+        H_TRY(h->vg.corr_T.reserve(16 * sizeof(double)));
+        H_TRY(h->vg.corr_T2.reserve(16 * sizeof(double)));
+    }
     VgicpArgs a = vgicp_args(h, d_src, n_src, stride_floats);
     a.roi = roi_view(h);
     if (h->clamp.use) {      // the target index was cut to the bulk of the cloud (vgicp_prepare_target): watch where the scan goes
@@ -467,6 +488,7 @@ int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
         H_TRY(hipMemsetAsync(h->vg.cov_viol.p, 0, 16, h->stream));
         a.escapes = h->vg.cov_viol.as<uint32_t>() + 1;
         a.guard_cells = (int)ceil(std::max(4.0, 8.0 * h->prm.vgicp_resolution) / h->prm.vgicp_resolution);      // the reach of a 20-neighbour covariance (as pcr_set_shard's halo)
+        if (search != PCR_VGICP_DIRECT1) a.guard_cells += 1;      // ... around every voxel a point is paired with: one voxel beyond its own
     }
     const bool shard = sharded(h);      // every rank linearises its tile's share of the scan; H, b and the error are summed over the ranks
 
@@ -674,12 +696,53 @@ int pcr_vgicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t str
     Pose16 T;
     memcpy(T.m, pose, sizeof T.m);
     H_TRY(vgicp_launch_linearize(vgicp_args(h, d_src, n_src, stride_bytes / 4), T, h->out32.dev, h->stream));
-    std::vector<uint32_t> slots(n_src);
-    if (n_src) H_TRY(hipMemcpyAsync(slots.data(), h->vg.corr_slot.p, n_src * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    // the pairs: DIRECT1 one slot per point, DIRECT7 / DIRECT27 the K rows of slots (VgicpArgs::corr_slot; the presence bits behind them are not counted)
+    const size_t n_entries = vgicp_table_entries(h->prm.vgicp_search);
+    std::vector<uint32_t> slots(n_src * n_entries);
+    if (n_src) H_TRY(hipMemcpyAsync(slots.data(), h->vg.corr_slot.p, slots.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     H_TRY(hipStreamSynchronize(h->stream));
     if (sharded(h) && ranks_allreduce(h, h->out32.host, 29)) return 1;
     unpack_lsq_sums(h->out32.host, H, b, error);
     if (n_corr) { int64_t c = 0; for (uint32_t v : slots) c += v != 0; *n_corr = c; }
+    h->vg.lin_valid = true; h->vg.lin_n = n_src; h->vg.lin_search = h->prm.vgicp_search;
+    return 0;
+}
+
+int pcr_vgicp_correspondences(pcr_handle* h, pcr_vgicp_corr* out, size_t capacity, size_t* count) {
+    if (!h) return 1;
+    h->err.clear();
+    if (h->method != kVgicp) return fail(h, "pcr_vgicp_correspondences needs a vgicp handle");
+    if (set_device(h)) return 1;
+    if (!h->vg.lin_valid || !h->vg.target_ready || h->roi_on) return fail(h, "pcr_vgicp_correspondences: no linearisation to report; call pcr_vgicp_linearize first");
+    const size_t n_src = h->vg.lin_n, n_entries = vgicp_table_entries(h->vg.lin_search);
+    H_TRY(hipStreamSynchronize(h->stream));
+    GridHeader hd;
+    H_TRY(hipMemcpy(&hd, h->grid.header.p, sizeof hd, hipMemcpyDeviceToHost));
+    if (hd.overflow || hd.stale) return fail(h, "internal: the index of a target that pcr_set_target settled is incomplete");
+    size_t pairs = 0;
+    if (!hd.empty && n_src) {
+        std::vector<uint32_t> slots(n_src * n_entries), start((size_t)hd.n_cells + 1);
+        H_TRY(hipMemcpy(slots.data(), h->vg.corr_slot.p, slots.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        H_TRY(hipMemcpy(start.data(), h->grid.cell_start.p, start.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        const uint32_t d0 = (uint32_t)hd.dims[0], d1 = (uint32_t)hd.dims[1];
+        for (size_t i = 0; i < n_src; ++i)
+            for (size_t k = 0; k < n_entries; ++k) {
+                const uint32_t slot = slots[k * n_src + i];      // ([K][n_src]; DIRECT1: [n_src])
+                if (!slot) continue;
+                if (out && pairs < capacity) {
+                    // a voxel is stored at the position of its cell's first point: the cell is the LAST one that starts there (the empty cells in front of it start there too)
+                    const size_t t = (size_t)(std::upper_bound(start.begin(), start.end(), slot - 1u) - start.begin()) - 1;
+                    if (t >= (size_t)hd.n_cells || start[t] != slot - 1u) return fail(h, "internal: a correspondence that is no voxel of the target");
+                    const uint32_t row = (uint32_t)(t / d0), cz = row / d1;
+                    pcr_vgicp_corr& o = out[pairs];
+                    o.row = (int32_t)i;
+                    o.ijk[0] = (int32_t)((uint32_t)t - row * d0) + (int32_t)hd.org[0]; o.ijk[1] = (int32_t)(row - cz * d1) + (int32_t)hd.org[1]; o.ijk[2] = (int32_t)cz + (int32_t)hd.org[2];
+                }
+                ++pairs;
+            }
+    }
+    if (count) *count = pairs;
+    if (out && capacity < pairs) return fail(h, "pcr_vgicp_correspondences: room for " + std::to_string(capacity) + " pairs, the linearisation has " + std::to_string(pairs));
     return 0;
 }
 

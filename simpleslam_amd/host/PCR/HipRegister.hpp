@@ -312,6 +312,9 @@ public:
     // The prepared target is dropped when the value changes; a value out of range throws.
     void setRegularizationMethod(int method) { setField(&pcr_params::vgicp_regularization, method); }
     void setVoxelAccumulationMode(int mode) { setField(&pcr_params::vgicp_voxel_mode, mode); }
+    // fast_gicp::FastVGICP::setNeighborSearchMethod (gicp_settings.hpp:8): PCR_VGICP_DIRECT27 / _DIRECT7 / _DIRECT1, in fast_gicp's enum order.  The
+    // prepared target is kept (the voxels do not depend on it); PCR_VGICP_DIRECT_RADIUS or a value out of range throws.
+    void setNeighborSearchMethod(int method) { setField(&pcr_params::vgicp_search, method); }
     scalar_t getFitnessScore() override { return pcr_fitness(h_); }
 };
 

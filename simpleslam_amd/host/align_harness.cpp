@@ -1,6 +1,7 @@
 // align_harness.cpp -- ROS/PCL-free counterpart of the reference's test/align.cpp:
-//   align_harness <target.pcd|.f32> <source.pcd|.f32> <loam|ndt|vgicp|gicp> [init_pose.txt [ndt_search]]
-// (ndt_search: ndt only, NdtRegister::setNeighborhoodSearchMethod -- 1 DIRECT26, 2 DIRECT7 (the default), 3 DIRECT1)
+//   align_harness <target.pcd|.f32> <source.pcd|.f32> <loam|ndt|vgicp|gicp> [init_pose.txt [search]]
+// (search: ndt -- NdtRegister::setNeighborhoodSearchMethod: 1 DIRECT26, 2 DIRECT7 (the default), 3 DIRECT1;
+//          vgicp -- VgicpRegister::setNeighborSearchMethod: 0 DIRECT27, 1 DIRECT7, 2 DIRECT1 (the default))
 // loads two clouds (PCD files as align.cpp:97-107 does -- pcp/pcd_io.hpp -- or raw float32 x y z intensity records), reads the optional initial pose (4x4 row-major text,
 // align.cpp:85-93), voxel-filters BOTH clouds at 0.1 m (align.cpp:128-129), runs ONE scan2Map through the plugin mirror
 // (align.cpp:144), and prints what align.cpp logs: the cloud sizes before and after the filter, the elapsed time, the gated
@@ -52,7 +53,11 @@ int main(int argc, char** argv) {
             if (argc > 5) ndt->setNeighborhoodSearchMethod(std::stoi(argv[5]));
             pcr = ndt;
         }
-        else if (method == "vgicp") pcr = std::make_shared<PCR::VgicpRegister>();
+        else if (method == "vgicp") {
+            auto vgicp = std::make_shared<PCR::VgicpRegister>();
+            if (argc > 5) vgicp->setNeighborSearchMethod(std::stoi(argv[5]));
+            pcr = vgicp;
+        }
         else if (method == "gicp") pcr = std::make_shared<PCR::GicpRegister>();
         else { std::fprintf(stderr, "no such method!!\n"); return -1; }                                                   // align.cpp:118-121
         std::printf("target cloud size: %zu\nsource cloud size: %zu\n", target_cloud->size(), source_cloud->size());

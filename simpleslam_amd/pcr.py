@@ -35,7 +35,7 @@ class PcrParams(C.Structure):
         ("ndt_search", C.c_int32),
         ("vgicp_resolution", C.c_double), ("vgicp_k_corr", C.c_int32), ("vgicp_max_iters", C.c_int32),
         ("vgicp_lm_inner", C.c_int32), ("vgicp_rot_eps", C.c_double), ("vgicp_trans_eps", C.c_double),
-        ("vgicp_lm_init_scale", C.c_double),
+        ("vgicp_lm_init_scale", C.c_double), ("vgicp_search", C.c_int32),
         ("record_trace", C.c_int32),
         ("index_no_hints", C.c_int32), ("ndt_evaluate_repeats", C.c_int32), ("loam_disable_cache", C.c_int32), ("record_timeline", C.c_int32),
         ("loam_coresident", C.c_int32), ("loam_clamp_margin_mm", C.c_int32), ("full_target", C.c_int32), ("host_optimiser", C.c_int32),
@@ -48,6 +48,8 @@ class PcrParams(C.Structure):
 # pcr_params.vgicp_regularization / vgicp_voxel_mode (include/pcr_hip.h: PCR_REG_*, PCR_VOXEL_*; fast_gicp's gicp_settings.hpp:6,10)
 REG_NONE, REG_MIN_EIG, REG_NORMALIZED_MIN_EIG, REG_PLANE, REG_FROBENIUS = range(5)
 VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = range(3)
+# pcr_params.vgicp_search (include/pcr_hip.h: PCR_VGICP_*; fast_gicp::NeighborSearchMethod, gicp_settings.hpp:8).  VGICP_DIRECT_RADIUS is refused.
+VGICP_DIRECT27, VGICP_DIRECT7, VGICP_DIRECT1, VGICP_DIRECT_RADIUS = range(4)
 # pcr_params.ndt_search (include/pcr_hip.h: PCR_NDT_*; pclomp::NeighborSearchMethod, ndt_omp.h:52-57).  NDT_KDTREE is refused.
 NDT_KDTREE, NDT_DIRECT26, NDT_DIRECT7, NDT_DIRECT1 = range(4)
 
@@ -66,7 +68,7 @@ class PcrStats(C.Structure):
 ABI_SYMBOLS = [
     "pcr_default_params", "pcr_create", "pcr_destroy", "pcr_last_error", "pcr_scan2map", "pcr_scan2map_device", "pcr_host_pin", "pcr_host_unpin",
     "pcr_set_target", "pcr_align", "pcr_invalidate_target", "pcr_fitness", "pcr_loam_linearize", "pcr_get_trace", "pcr_get_trace_counts",
-    "pcr_vgicp_covariances", "pcr_vgicp_neighbours", "pcr_vgicp_linearize", "pcr_gicp_linearize", "pcr_voxel_filter", "pcr_voxel_filter_begin", "pcr_voxel_filter_end", "pcr_get_timeline", "pcr_ndt_derivatives", "pcr_ndt_voxels", "pcr_vgicp_voxels", "pcr_ndt_pass_sums", "pcr_get_stats", "pcr_set_profile", "pcr_set_stream", "pcr_set_query_tile", "pcr_comm_unique_id", "pcr_comm_init", "pcr_comm_info", "pcr_comm_peer_export", "pcr_comm_init_peer",
+    "pcr_vgicp_covariances", "pcr_vgicp_neighbours", "pcr_vgicp_linearize", "pcr_gicp_linearize", "pcr_voxel_filter", "pcr_voxel_filter_begin", "pcr_voxel_filter_end", "pcr_get_timeline", "pcr_ndt_derivatives", "pcr_ndt_voxels", "pcr_vgicp_voxels", "pcr_vgicp_correspondences", "pcr_ndt_pass_sums", "pcr_get_stats", "pcr_set_profile", "pcr_set_stream", "pcr_set_query_tile", "pcr_comm_unique_id", "pcr_comm_init", "pcr_comm_info", "pcr_comm_peer_export", "pcr_comm_init_peer",
     "pcr_comm_init_host", "pcr_set_shard", "pcr_set_params", "pcr_get_params", "pcr_fitness_gated",
     "pcr_map_create", "pcr_map_destroy", "pcr_map_last_error", "pcr_map_add_keyframe", "pcr_map_keyframes", "pcr_map_clear", "pcr_map_update", "pcr_map_update_begin", "pcr_map_wait", "pcr_map_update_window", "pcr_map_submap",
     "pcr_map_submap_indices", "pcr_map_generation", "pcr_scan2map_submap",
@@ -159,6 +161,7 @@ def load_library():
     L.pcr_get_timeline.argtypes = [vp, vp, C.c_size_t, ip, ip]
     L.pcr_ndt_voxels.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.pcr_vgicp_voxels.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pcr_vgicp_correspondences.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.pcr_ndt_pass_sums.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, C.c_int, dp, dp, dp]
     L.pcr_voxel_filter.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_double, vp, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
     L.pcr_voxel_filter_begin.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_double, vp, C.c_size_t]
@@ -780,8 +783,22 @@ class NdtRegister(PointCloudRegister):
 class VgicpRegister(PointCloudRegister):
     """PCR::VgicpRegister (reference PCR/src/VgicpRegister.cpp).  fast_gicp's two settings are keyword arguments like every other field of
     pcr_params: vgicp_regularization=REG_* (FastGICP::setRegularizationMethod, default REG_PLANE) and vgicp_voxel_mode=VOXEL_*
-    (FastVGICP::setVoxelAccumulationMode, default VOXEL_ADDITIVE); set_params changes them on a live handle and drops the prepared target."""
+    (FastVGICP::setVoxelAccumulationMode, default VOXEL_ADDITIVE); set_params changes them on a live handle and drops the prepared target.
+    vgicp_search=VGICP_DIRECT27 | VGICP_DIRECT7 | VGICP_DIRECT1 (FastVGICP::setNeighborSearchMethod, default VGICP_DIRECT1) is one too, here and
+    in make_register("vgicp", ...); set_params changes it and KEEPS the prepared target."""
     method = "vgicp"
+
+    def correspondences(self):
+        """The (source row, voxel) pairs of the last linearize() (pcr_vgicp_correspondences): dict(row (m,) int32, ijk (m, 3) int32 = the
+        voxel's lattice coordinates as voxels() reports them), ordered by row, a row's pairs in the order of the vgicp_search table."""
+        cnt = C.c_size_t(0)
+        self._check(self._lib.pcr_vgicp_correspondences(self._h, None, 0, C.byref(cnt)))
+        rec = np.dtype([("row", np.int32), ("ijk", np.int32, 3)])
+        assert rec.itemsize == 16
+        raw = np.zeros(cnt.value, rec)
+        if cnt.value:
+            self._check(self._lib.pcr_vgicp_correspondences(self._h, raw.ctypes.data_as(C.c_void_p), raw.size, C.byref(cnt)))
+        return dict(row=raw["row"].copy(), ijk=raw["ijk"].copy())
 
     def voxels(self):
         """The Gaussian voxels of the kept target (setTarget; pcr_vgicp_voxels), sorted by (ix, iy, iz): dict(ijk (m, 3) int32 = the lattice
