@@ -1,6 +1,8 @@
-"""MapManager::updateMap on the device (pcr_map_*) vs the CPU oracle: which key frames are used and which voxel every
-transformed point falls into are exact; centroids agree to PCL's float-accumulation rounding.  The assembled sub-map
-then serves as `dst` of scan2Map without leaving HBM."""
+"""MapManager::updateMap on the device (pcr_map_*) vs the CPU oracle: which key frames are used is exact, the number of occupied
+voxels is the oracle's, and centroids agree to PCL's float-accumulation rounding (5e-4 m -- a bar that a single point in the
+wrong voxel can pass).  Which voxel every transformed point falls into is asserted in tests/test_submap_exact_gpu.py, against
+tests/submap_ref.py: transformed points bit for bit, the voxel of every row, centroids to one ulp of the float64 mean.  The
+assembled sub-map then serves as `dst` of scan2Map without leaving HBM."""
 import numpy as np
 import pytest
 
