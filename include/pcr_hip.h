@@ -445,6 +445,20 @@ int pcr_ndt_opt_result(const pcr_ndt_opt* o, double pose16[16], int* converged, 
 /* evaluations = computeDerivatives calls of the reference's loop so far, hessians = its computeHessian calls, replayed = how many of the
  * evaluations were requests for score + gradient at the point they had just been evaluated at, answered without asking (ndt_opt.h) */
 int pcr_ndt_opt_counts(const pcr_ndt_opt* o, int* evaluations, int* hessians, int* replayed);
+/* pcr_ndt_opt_set_replay (before the first feed): off != 0 = every request becomes an evaluation, the reference's own schedule
+ * (pcr_params.ndt_evaluate_repeats); the decisions and the result must not depend on it.
+ * pcr_ndt_opt_create_device: the same object with its state in device memory: every feed uploads the sums and launches the controller
+ * step of the sharded device loop once (one block; the Newton solve is the device's guarded elimination, the trigonometry the device's),
+ * request / result / counts / state / tables read the copy that launch left.  NULL when there is no GPU.
+ * pcr_ndt_opt_state: bail = the device's Newton solve met a pivot below its guard and ended the run for the host to repeat (then done = 1,
+ * kind 3); late_h = Hessians asked for at a first trial point after the search had ended there; a_t = the current trial step;
+ * phase = ndt_opt.h's kNdtPhase*.  pcr_ndt_opt_tables: the angle tables of the request (computeAngleDerivatives: j_ang, h_ang as float,
+ * j_ang_a_.. and h_ang_a2_.. as double, row-major [8][3] / [15][3]).  pcr_ndt_opt_hessian: the 36 Hessian entries the state keeps. */
+pcr_ndt_opt* pcr_ndt_opt_create_device(const double pose_guess[16], double step_size, double trans_eps, int max_iters);
+int pcr_ndt_opt_set_replay(pcr_ndt_opt* o, int off);
+int pcr_ndt_opt_state(const pcr_ndt_opt* o, int* bail, int* late_h, double* a_t, int* phase);
+int pcr_ndt_opt_tables(const pcr_ndt_opt* o, float j[24], float h[45], double jd[24], double hd[45]);
+int pcr_ndt_opt_hessian(const pcr_ndt_opt* o, double hess[36]);
 
 /* The VGICP optimiser on its own (host only, no GPU): fast_gicp's LsqRegistration::computeTransformation + step_lm
  * (lsq_registration_impl.hpp:53-79, 125-171) as the state machine that pcr_scan2map runs on the device (csrc/vgicp_opt.h), driven

@@ -443,19 +443,50 @@ int pcr_ndt_pass_sums(pcr_handle* h, const void* src, size_t n_src, size_t strid
     return 0;
 }
 
-struct pcr_ndt_opt { NdtCtl c; };
+// d_*: a device object (pcr_ndt_opt_create_device): the state lives in device memory and every feed is one launch of ndt_ctl_kernel, the
+// controller step of the sharded device loop; `c` is then the copy that launch left behind.  All NULL: the host's ctl_step.
+struct pcr_ndt_opt { NdtCtl c; NdtCtl* d_ctl; double* d_sums; GridHeader* d_hdr; NdtOut* d_out; };
 
-pcr_ndt_opt* pcr_ndt_opt_create(const double pose_guess[16], double step_size, double trans_eps, int max_iters) {
+static pcr_ndt_opt* ndt_opt_new(const double pose_guess[16], double step_size, double trans_eps, int max_iters) {
     if (!pose_guess) return nullptr;
     pcr_ndt_opt* o = new pcr_ndt_opt;
-    memset(&o->c, 0, sizeof o->c);
+    memset(o, 0, sizeof *o);
     NdtPose T0;
     double p0[6];
     ndt_initial_pose(pose_guess, &T0, p0);      // (as run_ndt starts)
     ndt_opt::ctl_init(&o->c, T0, p0, step_size, trans_eps, max_iters);
     return o;
 }
-void pcr_ndt_opt_destroy(pcr_ndt_opt* o) { delete o; }
+pcr_ndt_opt* pcr_ndt_opt_create(const double pose_guess[16], double step_size, double trans_eps, int max_iters) {
+    return ndt_opt_new(pose_guess, step_size, trans_eps, max_iters);
+}
+pcr_ndt_opt* pcr_ndt_opt_create_device(const double pose_guess[16], double step_size, double trans_eps, int max_iters) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { (void)hipGetLastError(); return nullptr; }
+    pcr_ndt_opt* o = ndt_opt_new(pose_guess, step_size, trans_eps, max_iters);
+    if (!o) return nullptr;
+    const bool ok = hipMalloc(&o->d_ctl, sizeof(NdtCtl)) == hipSuccess && hipMalloc(&o->d_sums, 48 * sizeof(double)) == hipSuccess &&
+                    hipMalloc(&o->d_hdr, sizeof(GridHeader)) == hipSuccess && hipMalloc(&o->d_out, sizeof(NdtOut)) == hipSuccess &&
+                    hipMemset(o->d_sums, 0, 48 * sizeof(double)) == hipSuccess && hipMemset(o->d_hdr, 0, sizeof(GridHeader)) == hipSuccess &&
+                    hipMemset(o->d_out, 0, sizeof(NdtOut)) == hipSuccess && ndt_launch_ctl_state(o->d_ctl, o->c, nullptr) == hipSuccess &&
+                    hipDeviceSynchronize() == hipSuccess;
+    if (!ok) { pcr_ndt_opt_destroy(o); return nullptr; }
+    return o;
+}
+void pcr_ndt_opt_destroy(pcr_ndt_opt* o) {
+    if (!o) return;
+    if (o->d_ctl) (void)hipFree(o->d_ctl);
+    if (o->d_sums) (void)hipFree(o->d_sums);
+    if (o->d_hdr) (void)hipFree(o->d_hdr);
+    if (o->d_out) (void)hipFree(o->d_out);
+    delete o;
+}
+int pcr_ndt_opt_set_replay(pcr_ndt_opt* o, int off) {
+    if (!o || o->c.passes || o->c.done) return 1;      // (before the first feed)
+    o->c.replay_off = off ? 1 : 0;
+    if (o->d_ctl && (ndt_launch_ctl_state(o->d_ctl, o->c, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) return 1;
+    return 0;
+}
 int pcr_ndt_opt_request(const pcr_ndt_opt* o, int* kind, double p6[6], double pose16[16]) {
     if (!o || !kind) return 1;
     *kind = o->c.done ? kNdtPassNone : o->c.kind;
@@ -465,7 +496,38 @@ int pcr_ndt_opt_request(const pcr_ndt_opt* o, int* kind, double p6[6], double po
 }
 int pcr_ndt_opt_feed(pcr_ndt_opt* o, const double sums[43]) {
     if (!o || !sums || o->c.done) return 1;
-    ndt_opt::ctl_step(&o->c, sums);
+    if (!o->d_ctl) { ndt_opt::ctl_step(&o->c, sums); return 0; }
+    double s48[48];
+    for (int i = 0; i < 48; ++i) s48[i] = i < 43 ? sums[i] : 0.0;
+    NdtArgs a;
+    memset(&a, 0, sizeof a);
+    a.hdr = o->d_hdr;
+    // (a step that fails half-way may have moved the device's state past the copy here: the object ends, handed back like a bail)
+    const bool ok = hipMemcpy(o->d_sums, s48, sizeof s48, hipMemcpyHostToDevice) == hipSuccess &&
+                    ndt_launch_ctl(a, o->d_ctl, o->d_sums, o->d_out, nullptr, 1.0, 0) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(&o->c, o->d_ctl, sizeof o->c, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) { o->c.done = 1; o->c.conv = 0; o->c.bail = 1; o->c.kind = kNdtPassNone; return 1; }
+    return 0;
+}
+int pcr_ndt_opt_state(const pcr_ndt_opt* o, int* bail, int* late_h, double* a_t, int* phase) {
+    if (!o) return 1;
+    if (bail) *bail = o->c.bail;
+    if (late_h) *late_h = o->c.late_h;
+    if (a_t) *a_t = o->c.a_t;
+    if (phase) *phase = o->c.phase;
+    return 0;
+}
+int pcr_ndt_opt_tables(const pcr_ndt_opt* o, float j[24], float h[45], double jd[24], double hd[45]) {
+    if (!o) return 1;
+    if (j) memcpy(j, o->c.ang.j, sizeof o->c.ang.j);
+    if (h) memcpy(h, o->c.ang.h, sizeof o->c.ang.h);
+    if (jd) memcpy(jd, o->c.ang.jd, sizeof o->c.ang.jd);
+    if (hd) memcpy(hd, o->c.ang.hd, sizeof o->c.ang.hd);
+    return 0;
+}
+int pcr_ndt_opt_hessian(const pcr_ndt_opt* o, double hess[36]) {
+    if (!o || !hess) return 1;
+    for (int i = 0; i < 36; ++i) hess[i] = o->c.hess[i];
     return 0;
 }
 int pcr_ndt_opt_result(const pcr_ndt_opt* o, double pose16[16], int* converged, int* iterations, int* done) {

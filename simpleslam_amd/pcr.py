@@ -74,6 +74,7 @@ ABI_SYMBOLS = [
     "pcr_map_submap_indices", "pcr_map_generation", "pcr_scan2map_submap",
     "pcr_map_set_poses", "pcr_map_keyframe", "pcr_map_read_keyframe", "pcr_map_downsample_keyframes", "pcr_map_update_all", "pcr_map_view",
     "pcr_ndt_opt_create", "pcr_ndt_opt_destroy", "pcr_ndt_opt_request", "pcr_ndt_opt_feed", "pcr_ndt_opt_result", "pcr_ndt_opt_counts",
+    "pcr_ndt_opt_create_device", "pcr_ndt_opt_set_replay", "pcr_ndt_opt_state", "pcr_ndt_opt_tables", "pcr_ndt_opt_hessian",
     "pcr_vgicp_opt_create", "pcr_vgicp_opt_destroy", "pcr_vgicp_opt_request", "pcr_vgicp_opt_feed", "pcr_vgicp_opt_result",
     "pcr_sc_default_params", "pcr_sc_create", "pcr_sc_destroy", "pcr_sc_last_error", "pcr_sc_size", "pcr_sc_add", "pcr_sc_descriptor", "pcr_sc_distance",
     "pcr_sc_query", "pcr_knn", "pcr_radius_search", "pcr_fitness_batch", "pcr_reloc_default_params", "pcr_reloc_hypotheses", "pcr_relocalize",
@@ -176,6 +177,12 @@ def load_library():
     L.pcr_ndt_opt_feed.argtypes = [vp, dp]
     L.pcr_ndt_opt_result.argtypes = [vp, dp, ip, ip, ip]
     L.pcr_ndt_opt_counts.argtypes = [vp, ip, ip, ip]
+    L.pcr_ndt_opt_create_device.restype = vp
+    L.pcr_ndt_opt_create_device.argtypes = [dp, C.c_double, C.c_double, C.c_int]
+    L.pcr_ndt_opt_set_replay.argtypes = [vp, C.c_int]
+    L.pcr_ndt_opt_state.argtypes = [vp, ip, ip, dp, ip]
+    L.pcr_ndt_opt_tables.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), dp, dp]
+    L.pcr_ndt_opt_hessian.argtypes = [vp, dp]
     L.pcr_vgicp_opt_create.restype = vp
     L.pcr_vgicp_opt_create.argtypes = [dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]
     L.pcr_vgicp_opt_destroy.restype = None
