@@ -426,6 +426,21 @@ int pcr_sc_query(pcr_sc* sc, long long id, long long* match, float* yaw_rad, dou
  * Every context's descriptor is kept in HBM as float (4 800 B each, what pcr_sc_add binned); the query is binned into a scratch
  * buffer and never enters the database.  On an empty database the call returns 0 and writes nothing. */
 int pcr_sc_distances(pcr_sc* sc, const void* pts, size_t n, size_t stride_bytes, int on_device, double* dist, int32_t* shift);
+/* Loop discovery over a range of STORED contexts, on the device: for every query q of [first, first + count) and every candidate i of
+ * [0, q - num_exclude_recent), (dist, shift) exactly as pcr_sc_distance(sc, q, i) returns them (the query unshifted, the candidate
+ * shifted: the function is not symmetric), and of those the k best by (dist, i) ascending -- the lower index wins a tie.  Row q - first
+ * of idx, dist, shift (count * k entries each) holds them in that order; where q has fewer than k candidates (none at all while
+ * q <= num_exclude_recent) the tail is idx -1, dist DBL_MAX, shift 0.  A candidate at DBL_MAX (no non-empty column pair under any shift)
+ * is a candidate like any other and so sorts last, by index.  dist_thres is not applied: this is the ranking (the mirrors' findLoops
+ * applies it).  The reference's query refuses id <= numExcludeRecent + numCandidatesFromTree because its ring-key tree needs 10 entries to
+ * answer; the exhaustive ranking has no such floor, and it is never worse than the tree's 10 candidates.  k is 1..8.
+ * Fails with a message in pcr_sc_last_error, writing NOTHING, when k is out of range, first + count > pcr_sc_size(), or idx, dist or
+ * shift is NULL while count > 0; count == 0 returns 0.  The same call gives the same bits whatever the window: a row depends on its
+ * query alone.  The database and the candidate snapshot of pcr_sc_query are left as they are (the call caches each context's column
+ * norms and sector key in HBM, 960 B per context, computed once). */
+int pcr_sc_rank_stored(pcr_sc* sc, size_t first, size_t count, int k, int64_t* idx, double* dist, int32_t* shift);
+/* Host-only: the yaw of a match, trans::deg2rad<float>(6 degrees * shift), as pcr_sc_query forms it. */
+float pcr_sc_shift_yaw(int32_t shift);
 
 /* The NDT optimiser on its own (host only, no GPU): pclomp's computeTransformation + computeStepLengthMT (ndt_omp_impl.hpp:81-171,
  * 735-932) as the state machine that pcr_scan2map runs on the device (csrc/ndt_opt.h), driven from outside -- the caller evaluates what

@@ -8,6 +8,8 @@
 // an exact 10-NN over the 20-dimensional ring keys, by brute force here instead of nanoflann's VectorOfVectorsKdTree).
 // Every descriptor is also kept in HBM (float, 4 800 B per context) for pcr_sc_distances: distanceBtnScanContext of an outside scan
 // against EVERY stored context, one wave per context (sc_rank_kernel), each sum in the host's order so that the result is the host's bit for bit.
+// pcr_sc_rank_stored does the same for stored queries against stored candidates -- lcHandler's walk over a range of key frames
+// (LoopClosureManager.cpp:73) -- in tiles of 8 queries x 128 candidates (sc_rank_stored_kernel), the k best per query merged in a fixed order.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -116,11 +118,14 @@ __global__ __launch_bounds__(256) void sc_polar_kernel(const float* __restrict__
     }
 }
 
-// The query's column norms (sqrt of the r = 0..19 sum of squares) and sector key (r = 0..19 sum, / 20), in the order pcr_sc_add and
-// sc_distance take them on the host.  keys[0, 60): norms, [60, 120): sector key.  One block of 64.
+// Column norms (sqrt of the r = 0..19 sum of squares) and sector key (r = 0..19 sum, / 20) of the descriptor(s) at q, in the order pcr_sc_add
+// and sc_distance take them on the host.  Per descriptor keys[0, 60): norms, [60, 120): sector key.  One block of 64 per descriptor
+// (pcr_sc_distances: the one query; pcr_sc_rank_stored: a run of stored contexts).
 __global__ __launch_bounds__(64) void sc_query_keys_kernel(const float* __restrict__ q /* [ring][sector], kNoPoint = empty */, double* __restrict__ keys) {
     const int c = threadIdx.x;
     if (c >= kSectors) return;
+    q += (size_t)blockIdx.x * (kRings * kSectors);
+    keys += (size_t)blockIdx.x * (2 * kSectors);
     double nrm = 0, sum = 0;
     for (int r = 0; r < kRings; ++r) {
         const float v = q[r * kSectors + c];
@@ -148,14 +153,64 @@ __device__ inline RankBest wave_rank_min(RankBest v) {
     return v;
 }
 
-// dist[i], shift[i] = distanceBtnScanContext(query, context i) as pcr_sc_distance(q, i) computes it on the host: the query unshifted, the
-// context shifted.  One wave per context (all waves of a block step together, so the block barriers are uniform):
-//   lanes 0..59: the context's column norms and sector key (sequential r = 0..19 sums);
+// distanceBtnScanContext(query, context) as pcr_sc_distance(q, i) computes it on the host -- the query unshifted, the context shifted -- by ONE
+// wave, every wave of the block calling it together (its barriers are block-wide).  The per-pair body of sc_rank_kernel and
+// sc_rank_stored_kernel; both descriptors (empty bins as 0), their column norms and sector keys are in LDS, s_term is the wave's own
+// kShiftGroup * kSectors doubles:
 //   lanes 0..59: the fast-align norm of shift s (sequential c = 0..59 sum, sqrt), then a wave arg-min, the lowest shift winning ties;
-//   all lanes: the (shift, column) cosine terms of up to kShiftGroup shifts, each a sequential r = 0..19 dot, staged in LDS;
+//   all lanes: the (shift, column) cosine terms of up to kShiftGroup shifts, each a sequential r = 0..19 dot, staged in s_term;
 //   one lane per shift: the sequential col = 0..59 sum with its count of non-empty column pairs, then 1 - sum / eff;
 //   the minimum over the shifts by (d, s) with NaN (eff = 0) excluded -- the host's strict '<' over ascending shifts.
-// A context against which no shift has a non-empty column pair gets (DBL_MAX, 0), as on the host.
+// Returns (inf, 1 << 30) in every lane when no shift has a non-empty column pair (sc_pair_result turns that into DBL_MAX / 0).
+__device__ inline RankBest sc_pair_wave(const float* s_q, const double* s_qn, const double* s_qk, const float* s_b, const double* s_bn,
+                                        const double* s_bk, double* s_term, int lane, int radius, int n_shift) {
+    // fastAlignUsingVkey: shift s compares query key c with context key c - s
+    RankBest fa{__builtin_inf(), 1 << 30};
+    if (lane < kSectors) {
+        double s2 = 0;
+        for (int c = 0; c < kSectors; ++c) { const int k = c - lane < 0 ? c - lane + kSectors : c - lane; const double d = s_qk[c] - s_bk[k]; s2 += d * d; }
+        fa.d = sqrt(s2);
+        fa.s = lane;
+    }
+    const int a0 = wave_rank_min(fa).s;
+    // the shifts a0 - radius .. a0 + radius (mod 60; all 60 when that covers the circle): order does not matter to a (d, s) minimum
+    RankBest best{__builtin_inf(), 1 << 30};
+    for (int g0 = 0; g0 < n_shift; g0 += kShiftGroup) {
+        const int gn = n_shift - g0 < kShiftGroup ? n_shift - g0 : kShiftGroup;
+        for (int t = lane; t < gn * kSectors; t += 64) {
+            const int j = t / kSectors, col = t - j * kSectors;
+            const int s = n_shift == kSectors ? g0 + j : ((a0 - radius + g0 + j) % kSectors + kSectors) % kSectors;
+            const int sc = col - s < 0 ? col - s + kSectors : col - s;
+            double dot = 0;
+            for (int r = 0; r < kRings; ++r) dot += (double)s_q[r * kSectors + col] * (double)s_b[r * kSectors + sc];
+            const double na = s_qn[col], nb = s_bn[sc];
+            s_term[t] = (na == 0 || nb == 0) ? __builtin_nan("") : dot / (na * nb);      // (a term itself is always finite)
+        }
+        __syncthreads();
+        RankBest mine{__builtin_inf(), 1 << 30};
+        if (lane < gn) {
+            double sum = 0;
+            int eff = 0;
+            for (int col = 0; col < kSectors; ++col) {
+                const double t = s_term[lane * kSectors + col];
+                if (t == t) { sum = sum + t; eff = eff + 1; }
+            }
+            const double d = 1.0 - sum / eff;
+            if (d == d) { mine.d = d; mine.s = n_shift == kSectors ? g0 + lane : ((a0 - radius + g0 + lane) % kSectors + kSectors) % kSectors; }
+        }
+        best = rank_min(best, wave_rank_min(mine));
+        __syncthreads();
+    }
+    return best;
+}
+// what the host returns for it: DBL_MAX / 0 when no shift had a non-empty column pair
+__device__ inline RankBest sc_pair_result(RankBest best) {
+    return best.d < __builtin_inf() ? best : RankBest{1.7976931348623157e308, 0};
+}
+
+// dist[i], shift[i] = distanceBtnScanContext(query, context i) as pcr_sc_distance(q, i) computes it on the host (sc_pair_wave), for an outside
+// query against every stored context.  One wave per context (all waves of a block step together, so the block barriers are uniform);
+// lanes 0..59 first take the context's column norms and sector key (sequential r = 0..19 sums).
 __global__ __launch_bounds__(256) void sc_rank_kernel(const float* __restrict__ db /* M x [ring][sector] */, unsigned int M,
                                                       const float* __restrict__ q, const double* __restrict__ qkeys, int radius,
                                                       double* __restrict__ dist, int* __restrict__ shift) {
@@ -189,48 +244,123 @@ __global__ __launch_bounds__(256) void sc_rank_kernel(const float* __restrict__ 
             s_bk[w][lane] = sum / kRings;
         }
         __syncthreads();
-        // fastAlignUsingVkey: shift s compares query key c with context key c - s
-        RankBest fa{__builtin_inf(), 1 << 30};
+        const RankBest best = sc_pair_result(sc_pair_wave(s_q, s_qn, s_qk, s_b, s_bn[w], s_bk[w], s_term[w], lane, radius, n_shift));
+        if (live && lane == 0) { dist[ctx] = best.d; shift[ctx] = best.s; }
+    }
+}
+
+// ---- stored against stored: pcr_sc_rank_stored ----
+// For every query q of [first, first + count) the k best candidates i of [0, q - excl) by (dist, i), dist and shift as sc_pair_wave gives them.
+// The triangle is cut into tiles of kTileQ queries x kTileC candidates, one block each (blockIdx.x = query tile * nct + candidate tile):
+// the block keeps its queries' descriptors, norms and keys in LDS and streams the tile's candidates past them kStoredWaves at a time, one
+// per wave, so a staged candidate serves kTileQ pairs; the norms and keys of both sides come from `keys` (sc_query_keys_kernel over the
+// store, once per context).  The tile's (dist, shift) land in LDS, then wave j selects query j's k best of the tile -- k rounds, each the
+// (dist, i) minimum above the previous round's -- into part[((q - first) * nct + tile) * k + r], tail (DBL_MAX, -1, 0).
+// sc_rank_merge_kernel does the same selection over the lists of a query's tiles.  A tile with no pair inside the triangle exits at once.
+// No atomics and no dependence on scheduling: every list entry has one writer, and (dist, i) is a total order.
+constexpr int kTileQ = 8, kTileC = 128, kStoredWaves = 8;
+static_assert(kTileQ <= kStoredWaves && kTileC % kStoredWaves == 0 && kTileC % 64 == 0, "one selecting wave per query, whole steps, whole lanes");
+
+__global__ __launch_bounds__(64 * kStoredWaves) void sc_rank_stored_kernel(const float* __restrict__ db, const double* __restrict__ keys, unsigned int first,
+                                                                           unsigned int count, unsigned int nct, int excl, int radius, int k,
+                                                                           double* __restrict__ part_d, int* __restrict__ part_i, int* __restrict__ part_s) {
+    __shared__ float4 s_q4[kTileQ][kRings * kSectors / 4];
+    __shared__ double s_qn[kTileQ][kSectors], s_qk[kTileQ][kSectors];
+    __shared__ float4 s_b4[kStoredWaves][kRings * kSectors / 4];
+    __shared__ double s_bn[kStoredWaves][kSectors], s_bk[kStoredWaves][kSectors];
+    __shared__ double s_term[kStoredWaves][kShiftGroup * kSectors];
+    __shared__ double s_rd[kTileQ][kTileC];
+    __shared__ int s_rs[kTileQ][kTileC];
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const unsigned int qt = blockIdx.x / nct, ct = blockIdx.x - qt * nct;
+    const unsigned int q0 = first + qt * kTileQ;
+    const int nq = (int)(first + count - q0 < (unsigned int)kTileQ ? first + count - q0 : (unsigned int)kTileQ);
+    const long long c0 = (long long)ct * kTileC;
+    const long long lim_last = (long long)(q0 + nq - 1) - excl;      // candidates of the tile's last query: [0, lim_last)
+    if (c0 >= lim_last) return;                                      // the whole tile lies outside the triangle
+    const int n_shift = 2 * radius + 1 < kSectors ? 2 * radius + 1 : kSectors;
+    auto zero_empty = [](float4 v) {                                 // empty bins (kNoPoint) as the host's 0.0
+        v.x = v.x == kNoPoint ? 0.f : v.x; v.y = v.y == kNoPoint ? 0.f : v.y;
+        v.z = v.z == kNoPoint ? 0.f : v.z; v.w = v.w == kNoPoint ? 0.f : v.w;
+        return v;
+    };
+    for (int j = w; j < nq; j += kStoredWaves) {
+        const float4* src4 = reinterpret_cast<const float4*>(db + (size_t)(q0 + j) * (kRings * kSectors));
+        for (int i = lane; i < kRings * kSectors / 4; i += 64) s_q4[j][i] = zero_empty(src4[i]);
         if (lane < kSectors) {
-            double s2 = 0;
-            for (int c = 0; c < kSectors; ++c) { const int k = c - lane < 0 ? c - lane + kSectors : c - lane; const double d = s_qk[c] - s_bk[w][k]; s2 += d * d; }
-            fa.d = sqrt(s2);
-            fa.s = lane;
+            s_qn[j][lane] = keys[(size_t)(q0 + j) * (2 * kSectors) + lane];
+            s_qk[j][lane] = keys[(size_t)(q0 + j) * (2 * kSectors) + kSectors + lane];
         }
-        const int a0 = wave_rank_min(fa).s;
-        // the shifts a0 - radius .. a0 + radius (mod 60; all 60 when that covers the circle): order does not matter to a (d, s) minimum
-        RankBest best{__builtin_inf(), 1 << 30};
-        for (int g0 = 0; g0 < n_shift; g0 += kShiftGroup) {
-            const int gn = n_shift - g0 < kShiftGroup ? n_shift - g0 : kShiftGroup;
-            for (int t = lane; t < gn * kSectors; t += 64) {
-                const int j = t / kSectors, col = t - j * kSectors;
-                const int s = n_shift == kSectors ? g0 + j : ((a0 - radius + g0 + j) % kSectors + kSectors) % kSectors;
-                const int sc = col - s < 0 ? col - s + kSectors : col - s;
-                double dot = 0;
-                for (int r = 0; r < kRings; ++r) dot += (double)s_q[r * kSectors + col] * (double)s_b[r * kSectors + sc];
-                const double na = s_qn[col], nb = s_bn[w][sc];
-                s_term[w][t] = (na == 0 || nb == 0) ? __builtin_nan("") : dot / (na * nb);      // (a term itself is always finite)
-            }
-            __syncthreads();
-            RankBest mine{__builtin_inf(), 1 << 30};
-            if (lane < gn) {
-                double sum = 0;
-                int eff = 0;
-                for (int col = 0; col < kSectors; ++col) {
-                    const double t = s_term[w][lane * kSectors + col];
-                    if (t == t) { sum = sum + t; eff = eff + 1; }
-                }
-                const double d = 1.0 - sum / eff;
-                if (d == d) { mine.d = d; mine.s = n_shift == kSectors ? g0 + lane : ((a0 - radius + g0 + lane) % kSectors + kSectors) % kSectors; }
-            }
-            best = rank_min(best, wave_rank_min(mine));
-            __syncthreads();
+    }
+    const float* s_b = reinterpret_cast<const float*>(s_b4[w]);
+    __syncthreads();
+    for (long long c = c0; c < c0 + kTileC && c < lim_last; c += kStoredWaves) {      // (block-uniform)
+        const long long ctx = c + w;
+        const bool live = ctx < lim_last;                            // lim_last <= the last query's own index: inside the store
+        const float4* src4 = reinterpret_cast<const float4*>(db + (size_t)(live ? ctx : 0) * (kRings * kSectors));
+        for (int i = lane; i < kRings * kSectors / 4; i += 64) s_b4[w][i] = live ? zero_empty(src4[i]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (lane < kSectors) {
+            s_bn[w][lane] = live ? keys[(size_t)ctx * (2 * kSectors) + lane] : 0.0;
+            s_bk[w][lane] = live ? keys[(size_t)ctx * (2 * kSectors) + kSectors + lane] : 0.0;
         }
-        if (live && lane == 0) {
-            const bool any = best.d < __builtin_inf();
-            dist[ctx] = any ? best.d : 1.7976931348623157e308;      // DBL_MAX / 0: no shift had a non-empty column pair
-            shift[ctx] = any ? best.s : 0;
+        __syncthreads();
+        for (int j = 0; j < nq; ++j) {
+            if (c >= (long long)(q0 + j) - excl) continue;           // (block-uniform) none of this step's candidates is one of query j's
+            const RankBest best = sc_pair_result(sc_pair_wave(reinterpret_cast<const float*>(s_q4[j]), s_qn[j], s_qk[j], s_b, s_bn[w], s_bk[w],
+                                                              s_term[w], lane, radius, n_shift));
+            if (lane == 0) { s_rd[j][ctx - c0] = best.d; s_rs[j][ctx - c0] = best.s; }      // (entries past query j's limit are never read)
         }
+        // sc_pair_wave ends on a barrier, and a step no query took read nothing: the next step may overwrite s_b4
+    }
+    __syncthreads();
+    if (w >= nq) return;
+    const long long lim = (long long)(q0 + w) - excl - c0;           // query w's candidates in this tile: entries [0, lim)
+    const int n_in = lim < 0 ? 0 : lim > kTileC ? kTileC : (int)lim;
+    const size_t out = ((size_t)(q0 + w - first) * nct + ct) * (size_t)k;
+    RankBest prev{-__builtin_inf(), -1};
+    for (int r = 0; r < k; ++r) {
+        RankBest mine{__builtin_inf(), 1 << 30};
+        for (int t = lane; t < n_in; t += 64) {
+            const RankBest e{s_rd[w][t], t};
+            if (e.d > prev.d || (e.d == prev.d && e.s > prev.s)) mine = rank_min(mine, e);
+        }
+        const RankBest win = wave_rank_min(mine);
+        if (win.s == 1 << 30) {
+            if (lane == 0) { part_d[out + r] = 1.7976931348623157e308; part_i[out + r] = -1; part_s[out + r] = 0; }
+        } else if (lane == (win.s & 63)) {
+            part_d[out + r] = win.d; part_i[out + r] = (int)(c0 + win.s); part_s[out + r] = s_rs[w][win.s];
+        }
+        prev = win;
+    }
+}
+
+// The k best of query q = first + row over the lists of its candidate tiles (tile t holds candidates of q while t * kTileC < q - excl), by
+// (dist, i) as above; one wave per query.  Rows with no candidate get the tail: idx -1, DBL_MAX, shift 0.
+__global__ __launch_bounds__(256) void sc_rank_merge_kernel(const double* __restrict__ part_d, const int* __restrict__ part_i, const int* __restrict__ part_s,
+                                                            unsigned int first, unsigned int count, unsigned int nct, int excl, int k,
+                                                            long long* __restrict__ idx, double* __restrict__ dist, int* __restrict__ shift) {
+    const unsigned int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= count) return;
+    const long long lim = (long long)(first + row) - excl;
+    const size_t n_in = lim <= 0 ? 0 : (size_t)((lim + kTileC - 1) / kTileC) * (size_t)k;      // entries of the row's lists
+    const size_t in = (size_t)row * nct * (size_t)k, out = (size_t)row * (size_t)k;
+    RankBest prev{-__builtin_inf(), -1};
+    for (int r = 0; r < k; ++r) {
+        RankBest mine{__builtin_inf(), 0x7fffffff};
+        int at = 0;
+        for (size_t t = lane; t < n_in; t += 64) {
+            const RankBest e{part_d[in + t], part_i[in + t]};
+            if (e.s < 0) continue;                                   // a list's tail
+            if ((e.d > prev.d || (e.d == prev.d && e.s > prev.s)) && (e.d < mine.d || (e.d == mine.d && e.s < mine.s))) { mine = e; at = part_s[in + t]; }
+        }
+        const RankBest win = wave_rank_min(mine);
+        if (win.s == 0x7fffffff) {
+            if (lane == 0) { dist[out + r] = 1.7976931348623157e308; idx[out + r] = -1; shift[out + r] = 0; }
+        } else if (mine.s == win.s) {                                // one lane: a candidate stands in one list
+            dist[out + r] = win.d; idx[out + r] = win.s; shift[out + r] = at;
+        }
+        prev = win;
     }
 }
 
@@ -249,6 +379,11 @@ struct pcr_sc {
     float* d_db = nullptr; size_t db_cap = 0;            // every context's descriptor as binned (kNoPoint = empty), [context][ring][sector]
     float* d_query = nullptr; double* d_qkeys = nullptr; // pcr_sc_distances: the outside scan's descriptor and its column norms + sector key
     double* d_dist = nullptr; int* d_shift = nullptr; size_t res_cap = 0;
+    // pcr_sc_rank_stored: column norms + sector key of contexts [0, keys_n) (120 doubles each; a context never changes once added), the
+    // per-tile lists of one chunk of queries, and the merged result
+    double* d_keys = nullptr; size_t keys_cap = 0, keys_n = 0;
+    void* d_part = nullptr; size_t part_cap = 0;
+    void* d_rank = nullptr; size_t rank_cap = 0;
     std::string err;
 };
 
@@ -322,7 +457,8 @@ pcr_sc* pcr_sc_create(int device, const pcr_sc_params* p) {
 void pcr_sc_destroy(pcr_sc* sc) {
     if (!sc) return;
     (void)hipSetDevice(sc->device);
-    for (void* p : {(void*)sc->d_desc, (void*)sc->d_stage, (void*)sc->d_db, (void*)sc->d_query, (void*)sc->d_qkeys, (void*)sc->d_dist, (void*)sc->d_shift})
+    for (void* p : {(void*)sc->d_desc, (void*)sc->d_stage, (void*)sc->d_db, (void*)sc->d_query, (void*)sc->d_qkeys, (void*)sc->d_dist, (void*)sc->d_shift,
+                    (void*)sc->d_keys, sc->d_part, sc->d_rank})
         if (p) (void)hipFree(p);
     delete sc;
 }
@@ -469,6 +605,107 @@ int pcr_sc_distances(pcr_sc* sc, const void* pts, size_t n, size_t stride_bytes,
     return 0;
 }
 
+}  // extern "C"
+
+namespace {
+
+// a device buffer of at least `bytes` (contents not kept); a failed growth leaves none
+int sc_room(pcr_sc* sc, void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return 0;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    S_TRY(hipMalloc(p, bytes));
+    *cap = bytes;
+    return 0;
+}
+
+// column norms and sector keys of contexts [0, n) in d_keys: only those added since the last call are computed
+int sc_keys_upto(pcr_sc* sc, size_t n) {
+    if (n > sc->keys_cap) {
+        double* p = nullptr;
+        S_TRY(hipMalloc((void**)&p, sc->db_cap * 2 * kSectors * sizeof(double)));
+        if (sc->keys_n) {
+            const hipError_t c = hipMemcpy(p, sc->d_keys, sc->keys_n * 2 * kSectors * sizeof(double), hipMemcpyDeviceToDevice);
+            if (c != hipSuccess) { (void)hipFree(p); return scfail(sc, std::string("growing the key store: ") + hipGetErrorString(c)); }
+        }
+        if (sc->d_keys) (void)hipFree(sc->d_keys);
+        sc->d_keys = p; sc->keys_cap = sc->db_cap;
+    }
+    if (n > sc->keys_n) {
+        hipLaunchKernelGGL(sc_query_keys_kernel, dim3((unsigned int)(n - sc->keys_n)), dim3(64), 0, 0, sc->d_db + sc->keys_n * (kRings * kSectors),
+                           sc->d_keys + sc->keys_n * 2 * kSectors);
+        S_TRY(hipGetLastError());
+        sc->keys_n = n;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* distanceBtnScanContext of stored queries [first, first + count) against every older stored context, the k best each (sc_rank_stored_kernel) */
+int pcr_sc_rank_stored(pcr_sc* sc, size_t first, size_t count, int k, int64_t* idx, double* dist, int32_t* shift) {
+    if (!sc) return 1;
+    sc->err.clear();
+    const size_t M = sc->polar.size();
+    if (k < 1 || k > 8) return scfail(sc, "k must be 1..8, not " + std::to_string(k));
+    if (first > M || count > M - first) return scfail(sc, "first + count = " + std::to_string(first) + " + " + std::to_string(count) + " exceeds the " + std::to_string(M) + " stored contexts");
+    if (count == 0) return 0;
+    if (!idx) return scfail(sc, "idx is NULL");
+    if (!dist) return scfail(sc, "dist is NULL");
+    if (!shift) return scfail(sc, "shift is NULL");
+    if (sc->prm.num_exclude_recent < 0) return scfail(sc, "num_exclude_recent is negative");
+    if (M > 0x7fffff00ull) return scfail(sc, "too many contexts");
+    S_TRY(hipSetDevice(sc->device));
+    if (sc_keys_upto(sc, first + count)) return 1;
+    const int excl = sc->prm.num_exclude_recent;
+    const int radius = std::min(kSectors, std::max(0, (int)round(0.5 * (double)(float)sc->prm.search_ratio * kSectors)));      // as pcr_sc_distance
+    const size_t per_row = (size_t)k * (sizeof(double) + sizeof(long long) + sizeof(int));
+    if (sc_room(sc, &sc->d_rank, &sc->rank_cap, count * per_row)) return 1;
+    double* o_d = static_cast<double*>(sc->d_rank);
+    long long* o_i = reinterpret_cast<long long*>(o_d + count * k);
+    int* o_s = reinterpret_cast<int*>(o_i + count * k);
+    // candidate tiles of a query: ceil((q - excl) / kTileC).  The queries go in chunks whose per-tile lists fit kPartBytes; a query's
+    // row depends on no other query, so the chunking does not show in the result.
+    auto tiles_of = [&](size_t q) { return q > (size_t)excl ? (q - excl + kTileC - 1) / kTileC : 0; };
+    constexpr size_t kPartBytes = 64u << 20, kEntry = sizeof(double) + 2 * sizeof(int);
+    const size_t fit = kPartBytes / (std::max<size_t>(1, tiles_of(first + count - 1)) * k * kEntry);
+    const size_t rows = std::min<size_t>(std::max<size_t>(kTileQ, fit / kTileQ * kTileQ), (size_t)1 << 20);
+    for (size_t at = 0; at < count; at += rows) {
+        const size_t n = std::min(rows, count - at), nct = tiles_of(first + at + n - 1);
+        if (nct) {
+            if (sc_room(sc, &sc->d_part, &sc->part_cap, n * nct * k * kEntry)) return 1;
+            double* p_d = static_cast<double*>(sc->d_part);
+            int* p_i = reinterpret_cast<int*>(p_d + n * nct * k);
+            int* p_s = p_i + n * nct * k;
+            const size_t blocks = (n + kTileQ - 1) / kTileQ * nct;
+            if (blocks > 0x7fffffffull) return scfail(sc, "too many tiles in one launch");
+            hipLaunchKernelGGL(sc_rank_stored_kernel, dim3((unsigned int)blocks), dim3(64 * kStoredWaves), 0, 0, sc->d_db, sc->d_keys, (unsigned int)(first + at),
+                               (unsigned int)n, (unsigned int)nct, excl, radius, k, p_d, p_i, p_s);
+            S_TRY(hipGetLastError());
+        }
+        const double* p_d = static_cast<const double*>(sc->d_part);
+        const int* p_i = reinterpret_cast<const int*>(p_d + n * nct * k);
+        hipLaunchKernelGGL(sc_rank_merge_kernel, dim3((unsigned int)((n + 3) / 4)), dim3(256), 0, 0, p_d, p_i, p_i + n * nct * k, (unsigned int)(first + at),
+                           (unsigned int)n, (unsigned int)nct, excl, k, o_i + at * k, o_d + at * k, o_s + at * k);
+        S_TRY(hipGetLastError());
+    }
+    // into scratch first: a failed copy must leave the caller's arrays as they were
+    std::vector<char> host(count * per_row);
+    S_TRY(hipMemcpy(host.data(), sc->d_rank, host.size(), hipMemcpyDeviceToHost));
+    const char* h = host.data();
+    std::copy(reinterpret_cast<const double*>(h), reinterpret_cast<const double*>(h) + count * k, dist);
+    h += count * k * sizeof(double);
+    std::copy(reinterpret_cast<const long long*>(h), reinterpret_cast<const long long*>(h) + count * k, idx);
+    h += count * k * sizeof(long long);
+    std::copy(reinterpret_cast<const int*>(h), reinterpret_cast<const int*>(h) + count * k, shift);
+    return 0;
+}
+
+/* trans::deg2rad<float> of shift sectors of 6 degrees: the yaw of a match (:276) */
+float pcr_sc_shift_yaw(int32_t shift) { return (float)((double)((360.0f / (float)kSectors) * (float)shift) * 3.14159265358979323846 / 180.0); }
+
 /* query (:231-279): *match = -1 when there is no loop candidate; yaw = deg2rad(6 deg * shift) as a float */
 int pcr_sc_query(pcr_sc* sc, long long id, long long* match, float* yaw_rad, double* min_dist_out) {
     if (!sc || !match) return 1;
@@ -501,7 +738,7 @@ int pcr_sc_query(pcr_sc* sc, long long id, long long* match, float* yaw_rad, dou
     if (min_dist_out) *min_dist_out = min_dist;
     if (min_dist > (double)(float)sc->prm.dist_thres) return 0;
     *match = (long long)nn_idx;
-    if (yaw_rad) *yaw_rad = (float)((double)((360.0f / (float)kSectors) * (float)nn_align) * 3.14159265358979323846 / 180.0);      // deg2rad<float>
+    if (yaw_rad) *yaw_rad = pcr_sc_shift_yaw(nn_align);
     return 0;
 }
 

@@ -6,6 +6,7 @@
 // Mirrors (reference): PCR/include/PCR/PointCloudRegister.hpp:12-38, LoamRegister.hpp, NdtRegister.hpp,
 // VgicpRegister.hpp; the factory of frontend/src/LidarOdometry.cpp:44-54.
 #pragma once
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -466,9 +467,13 @@ inline std::shared_ptr<StaticMapRegister> makeStaticMapRegister(const std::strin
 namespace context {
 class ScanContext {
     pcr_sc* s_ = nullptr;
+    pcr_sc_params prm_;
 public:
     using QueryResult = std::pair<int, float>;                                  // {matched key frame or -1, yaw in rad}
-    explicit ScanContext(const pcr_sc_params* p = nullptr) : s_(pcr_sc_create(-1, p)) { if (!s_) throw std::runtime_error(pcr_sc_last_error(nullptr)); }
+    explicit ScanContext(const pcr_sc_params* p = nullptr) : s_(pcr_sc_create(-1, p)) {
+        if (!s_) throw std::runtime_error(pcr_sc_last_error(nullptr));
+        if (p) prm_ = *p; else pcr_sc_default_params(&prm_);
+    }
     ScanContext(const ScanContext&) = delete;
     ScanContext& operator=(const ScanContext&) = delete;
     ~ScanContext() { pcr_sc_destroy(s_); }
@@ -489,6 +494,30 @@ public:
         shift.assign(dist.size(), 0);
         if (pcr_sc_distances(s_, scan_down.points.data(), scan_down.size(), sizeof(PCR::PointXYZI), 0, dist.data(), shift.data()))
             throw std::runtime_error(pcr_sc_last_error(s_));
+    }
+    // Stored against stored, on the device (pcr_sc_rank_stored): for every query q of [first, first + count) the k best candidates i of
+    // [0, q - num_exclude_recent) by (distance(q, i), i); row q - first of each array, tail idx -1 / DBL_MAX / 0
+    struct Ranking { size_t first = 0, count = 0; int k = 0; std::vector<int64_t> idx; std::vector<double> dist; std::vector<int32_t> shift; };
+    Ranking rankStored(size_t first, size_t count, int k = 1) const {
+        Ranking r;
+        r.first = first; r.count = count; r.k = k;
+        const size_t n = count * (size_t)(k > 0 ? k : 0);
+        r.idx.assign(n, -1); r.dist.assign(n, std::numeric_limits<double>::max()); r.shift.assign(n, 0);
+        // (a vector of no elements may hand out a null pointer, which the call refuses when count > 0: k out of range is reported first)
+        if (pcr_sc_rank_stored(s_, first, count, k, r.idx.data(), r.dist.data(), r.shift.data())) throw std::runtime_error(pcr_sc_last_error(s_));
+        return r;
+    }
+    // LoopClosureManager::lcHandler's walk over key frames [first, first + count) in one call: the k = 1 ranking, then query's threshold
+    // (strict, ScanContext.cpp:273) and yaw.  match = -1 (yaw 0) when there is no candidate or min_dist > dist_thres.
+    struct Loop { int id; int match; float yaw; double min_dist; };
+    std::vector<Loop> findLoops(size_t first, size_t count) const {
+        const Ranking r = rankStored(first, count, 1);
+        std::vector<Loop> out(count);
+        for (size_t j = 0; j < count; ++j) {
+            const bool hit = r.idx[j] >= 0 && !(r.dist[j] > (double)(float)prm_.dist_thres);
+            out[j] = {(int)(first + j), hit ? (int)r.idx[j] : -1, hit ? pcr_sc_shift_yaw(r.shift[j]) : 0.f, r.dist[j]};
+        }
+        return out;
     }
     pcr_sc* handle() const { return s_; }
 };

@@ -79,6 +79,7 @@ ABI_SYMBOLS = [
     "pcr_sc_default_params", "pcr_sc_create", "pcr_sc_destroy", "pcr_sc_last_error", "pcr_sc_size", "pcr_sc_add", "pcr_sc_descriptor", "pcr_sc_distance",
     "pcr_sc_query", "pcr_knn", "pcr_radius_search", "pcr_fitness_batch", "pcr_reloc_default_params", "pcr_reloc_hypotheses", "pcr_relocalize",
     "pcr_sc_distances", "pcr_global_reloc_default_params", "pcr_global_reloc_hypotheses", "pcr_relocalize_global",
+    "pcr_sc_rank_stored", "pcr_sc_shift_yaw",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -251,6 +252,9 @@ def load_library():
     L.pcr_relocalize.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(RelocParams), dp, ip, C.POINTER(RelocCandidate), C.c_size_t,
                                  C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.pcr_sc_distances.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, C.POINTER(C.c_int32)]
+    L.pcr_sc_rank_stored.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int32)]
+    L.pcr_sc_shift_yaw.argtypes = [C.c_int32]
+    L.pcr_sc_shift_yaw.restype = C.c_float
     L.pcr_global_reloc_default_params.argtypes = [C.POINTER(GlobalRelocParams)]
     L.pcr_global_reloc_default_params.restype = None
     L.pcr_global_reloc_hypotheses.argtypes = [dp, C.c_int32, C.POINTER(RelocParams), dp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -1092,6 +1096,7 @@ class ScanContext:
                 raise ValueError(f"unknown ScanContext parameter {k}")
             setattr(p, k, v)
         self._height = float(p.lidar_height)
+        self._dist_thres = float(np.float32(p.dist_thres))            # the reference keeps scDistThres as a float
         self._s = self._lib.pcr_sc_create(int(device), C.byref(p))
         if not self._s:
             raise PcrError(self._lib.pcr_sc_last_error(None).decode())
@@ -1143,3 +1148,35 @@ class ScanContext:
         m, yaw, d = C.c_longlong(-1), C.c_float(0), C.c_double(0)
         self._check(self._lib.pcr_sc_query(self._s, int(i), C.byref(m), C.byref(yaw), C.byref(d)))
         return m.value, np.float32(yaw.value), (None if d.value == np.finfo(np.float64).max else d.value)
+
+    def rankStored(self, first, count, k=1):
+        """Stored contexts against stored contexts, on the device (pcr_sc_rank_stored): for every query q of [first, first + count)
+        the k best candidates i of [0, q - num_exclude_recent) by (distance(q, i), i) ascending
+        -> (idx int64, dist float64, shift int32), each (count, k), row q - first; the tail where fewer than k candidates exist is
+        idx -1, dist DBL_MAX, shift 0.  The threshold is not applied."""
+        first, count, k = int(first), int(count), int(k)
+        shape = (max(count, 0), max(k, 0))
+        idx, dist, shift = np.full(shape, -1, np.int64), np.full(shape, np.finfo(np.float64).max), np.zeros(shape, np.int32)
+        if first < 0 or count < 0:
+            raise PcrError("first and count must not be negative")
+        self._check(self._lib.pcr_sc_rank_stored(self._s, first, count, k, idx.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 dist.ctypes.data_as(C.POINTER(C.c_double)), shift.ctypes.data_as(C.POINTER(C.c_int32))))
+        return idx, dist, shift
+
+    def findLoops(self, first=0, count=None):
+        """LoopClosureManager::lcHandler's walk over key frames [first, first + count) (count=None: to the last one) in one call: per
+        query (id, match, yaw as float32, min_dist) from the k = 1 ranking.  match = -1, yaw = 0 when there is no candidate (min_dist
+        None) or min_dist > dist_thres; otherwise yaw = deg2rad(6 * shift) as query forms it."""
+        first = int(first)
+        count = len(self) - first if count is None else int(count)
+        idx, dist, shift = self.rankStored(first, count, 1)
+        out = []
+        for r in range(count):
+            i, d, s = int(idx[r, 0]), float(dist[r, 0]), int(shift[r, 0])
+            if i < 0:
+                out.append((first + r, -1, np.float32(0), None))
+            elif d > self._dist_thres:
+                out.append((first + r, -1, np.float32(0), d))
+            else:
+                out.append((first + r, i, np.float32(self._lib.pcr_sc_shift_yaw(s)), d))
+        return out
