@@ -125,6 +125,22 @@ typedef struct pcr_params {
                                 *    else).  Off by default: measured on MI355X / ROCm 7.2 the pitched copy of a 1 M-point map takes 3.5 ms where the
                                 *    verbatim copy of twice the bytes takes 0.6 ms (profiles/r04_notes.md) */
 
+    /* LIORF -- test/comp/liorf_scan2map.cpp (LioScan2map: LIO-SAM's surface scan-to-map).  Read by liorf handles only; every handle refuses a
+     * value out of range, by name (pcr_create, pcr_set_params).  (The block stands in front of the struct's last three fields, whose place
+     * at the end a test pins, as ndt_search and vgicp_search stand with their methods.)  The thresholds are the file's `double` literals: a float quantity is widened
+     * and compared in double, as the file's expressions do. */
+    int32_t liorf_iters;          /* 30   iteration cap (:392); >= 0 */
+    int32_t liorf_file_row;       /* 0    the pitch entry of a row is the derivative of the residual; 1: the file's own line 310, which has
+                                   *      sin(pitch) where the derivative has cos(pitch) in one term -- for a comparison with the program as written */
+    double liorf_knn_max_sq;      /* 1.0  gate on the squared 5th-neighbour distance, strict '<' (:186); > 0 */
+    double liorf_plane_thresh;    /* 0.2  a plane is invalid when one of its five points lies farther from it, strict '>' (:207); > 0 */
+    double liorf_point_thresh;    /* 0.1  a point is kept when its weight s exceeds this, strict '>' (:224); finite */
+    int32_t liorf_min_rows;       /* 50   fewer kept points: the pose is left alone (:268); >= 0 */
+    int32_t liorf_min_scan;       /* 30   nothing happens unless the scan has MORE points than this (:388); >= 0 */
+    double liorf_rot_conv_deg;    /* 0.05 converged: the angle step, in degrees, below this ... (:379); >= 0 */
+    double liorf_trans_conv_cm;   /* 0.05 ... and the translation step, in centimetres, below this; >= 0 */
+    double liorf_degenerate_eig;  /* 100  iteration 0: isDegenerate when the smallest eigenvalue of AtA is below this (:342); finite */
+
     /* GICP -- third_parties/pclomp/src/fast_gicp_impl.hpp:16-20.  A gicp handle also reads vgicp_resolution (the cell of its target index: it
      * decides how many candidates a search visits, never a result), vgicp_k_corr, vgicp_max_iters, vgicp_lm_inner, vgicp_rot_eps,
      * vgicp_trans_eps, vgicp_lm_init_scale, host_optimiser and index_no_hints. */
@@ -202,7 +218,8 @@ void pcr_default_params(pcr_params* p);
 
 /* method = "loam" | "ndt" | "vgicp" | "gicp" (frontend.pcr; "gicp" is fast_gicp::FastGICP, the point-wise class FastVGICP derives from, under
  * VgicpRegister's interface: every entry point a vgicp handle serves, the whole target prepared at every preparation; sharding -- pcr_set_shard,
- * pcr_set_query_tile, pcr_comm_init* -- and a target whose box no dense table can hold are refused).  NULL on failure; pcr_last_error(NULL)
+ * pcr_set_query_tile, pcr_comm_init* -- and a target whose box no dense table can hold are refused) | "liorf" (LIO-SAM's surface scan-to-map,
+ * the reference's test/comp/liorf_scan2map.cpp: see pcr_liorf_* below; the same two refusals).  NULL on failure; pcr_last_error(NULL)
  * then holds the reason (unknown method: the reference factory throws,
  * LidarOdometry.cpp:50-54).  p == NULL uses the defaults. */
 pcr_handle* pcr_create(const char* method, const pcr_params* p);
@@ -292,6 +309,40 @@ int pcr_vgicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t str
 int pcr_gicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double pose[16],
                        const double* pose_eval, double H[36], double b[6], double* error, double* error_eval, int64_t* n_corr,
                        int32_t* corr, float* d2, double* mahal6);
+
+/* ---- LIORF: LioScan2map of the reference's test/comp/liorf_scan2map.cpp (LIO-SAM's surface scan-to-map), a "liorf" handle ----
+ * Everything is float.  The pose is six numbers, transformTobeMapped = [roll, pitch, yaw, x, y, z]; pcr_scan2map / pcr_align take the
+ * six numbers out of the float cast of pose_inout once (pcr_liorf_pose_to_6dof), iterate on them on the device, and return
+ * pcr_liorf_6dof_to_pose of the final six.  DESIGN.md ("liorf") has the definition operation by operation; in short, per iteration:
+ * the float 4x4 of the six numbers; per scan point the float transform, the 5 nearest target points in PCL's float metric (ties on
+ * the lower index), the gate d2[4] < liorf_knn_max_sq, the float 5x3 column-pivoted Householder QR plane fit, the residual gate, the
+ * weight s and the row [arz, ary, arx, s pa, s pb, s pc | -s pd2] (the three angular entries are the exact derivatives of the residual:
+ * one term of the file's line 310 is not, and is replaced unless liorf_file_row = 1); the 21 + 6 sums of the rows' products in double by the fixed-order
+ * reduction, rounded to float once; the 6x6 system solved by Householder QR in float; the step ADDED to the six numbers.
+ * *converged = the last iteration's step was below liorf_rot_conv_deg and liorf_trans_conv_cm.  pcr_stats.iterations = linearisations
+ * performed: 0 when the scan has no more than liorf_min_scan points; a linearisation that keeps fewer than liorf_min_rows rows leaves
+ * the pose alone and ends the call there (the file's loop would repeat that linearisation unchanged until its cap).
+ * pcr_fitness() on a liorf handle is the file's own getFitnessScore: the mean of the float squared 1-NN distances d2 <= 1.0f of the
+ * last aligned scan at the returned pose, -1 when there is none.  It runs on the machinery of pcr_fitness_gated, whose gate is the
+ * same comparison -- a float distance, widened, against max_sq in double, '<=' -- so pcr_fitness_gated(max_sq = 1.0) is that score too.
+ * pcr_relocalize / pcr_relocalize_global work on a liorf handle: their refinements are pcr_align. */
+
+/* Host only (no GPU): pcl::getEulerAngles and the translation of a pose (16 doubles, column-major), through its float cast:
+ * roll = atan2f(t21, t22), pitch = asinf(-t20), yaw = atan2f(t10, t00); out6 = [roll, pitch, yaw, x, y, z]. */
+int pcr_liorf_pose_to_6dof(const double T[16], float out6[6]);
+/* Host only: pcl::getTransformation(x, y, z, roll, pitch, yaw) = Rz(yaw) Ry(pitch) Rx(roll), formed in float from A = cosf(yaw),
+ * B = sinf(yaw), C = cosf(pitch), D = sinf(pitch), E = cosf(roll), F = sinf(roll):  row 0 = [A C, A D F - B E, B F + A D E, x],
+ * row 1 = [B C, A E + B D F, B D E - A F, y], row 2 = [-D, C F, C E, z]; widened to 16 doubles, column-major. */
+int pcr_liorf_6dof_to_pose(const float in6[6], double T[16]);
+/* One linearisation (surfOptimization + the sums of LMOptimization) at the six numbers `six` against the kept target (pcr_set_target).
+ * T_used: the float 4x4 the DEVICE built from them, row-major (a reference can run the per-point stage on exactly that matrix).
+ * Per point (host arrays, may be NULL): kept[n] = 1 when the point gave a row; coeff4[n*4] = (s pa, s pb, s pc, s pd2), zeros where
+ * not kept.  AtA (36, row-major) and AtB (6): the double sums before the rounding to float; *n_kept = the rows. */
+int pcr_liorf_linearize(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const float six[6],
+                        float T_used[16], uint8_t* kept, float* coeff4, double AtA[36], double AtB[6], int64_t* n_kept);
+/* The last pcr_scan2map / pcr_align of a liorf handle: the final six numbers, isDegenerate (iteration 0: the smallest eigenvalue of the
+ * float AtA is below liorf_degenerate_eig; 0 when iteration 0 solved nothing) and the rows kept by the last linearisation. */
+int pcr_liorf_result(pcr_handle* h, float six[6], int* degenerate, int64_t* rows_last);
 
 /* pcl::VoxelGrid<PointXYZI>::filter (leaf, leaf, leaf) -- the step before the path: every scan at
  * frontend/src/LidarOdometry.cpp:36,170-171, every rebuilt sub-map at frontend/src/MapManager.cpp:78,192 through

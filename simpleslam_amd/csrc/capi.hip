@@ -175,6 +175,13 @@ int do_scan2map(pcr_handle* h, const void* src, size_t n_src, const void* dst, s
         if (run_gicp(h, d_src, n_src, stride_bytes / 4, pose, converged)) { (void)side_drain(h); return 1; }
         return end_timed_call(h);
     }
+    if (h->method == kLiorf) {
+        // kdtreeSurfFromMap->setInputCloud on every call (liorf_scan2map.cpp:390): the whole target indexed, every call
+        if (liorf_prepare_target(h, d_dst, n_dst, stride_bytes / 4)) return 1;
+        if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
+        if (run_liorf(h, d_src, n_src, stride_bytes / 4, pose, converged)) return 1;
+        return end_timed_call(h);
+    }
     // the reference rebuilds its index on every call (LoamRegister.cpp:110); so do we
     h->clamp.use = 0;
     if (build_target(h, d_dst, n_dst, stride_bytes / 4)) {
@@ -197,6 +204,7 @@ int prepare_target_from(pcr_handle* h, const float* d_dst, size_t n_dst, size_t 
     if (h->method == kVgicp) return agree_prepared(h, vgicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4));
     if (h->method == kNdt) return agree_prepared(h, ndt_prepare_target(h, d_dst, n_dst, stride_bytes / 4));
     if (h->method == kGicp) return gicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4);      // (never sharded: nothing to agree on)
+    if (h->method == kLiorf) return liorf_prepare_target(h, d_dst, n_dst, stride_bytes / 4);    // (the same)
     h->clamp.use = 0;
     // settle the cell-table size now so that pcr_align never has to rebuild
     int rc = build_target(h, d_dst, n_dst, stride_bytes / 4);
@@ -250,7 +258,8 @@ const char* settings_out_of_range(const pcr_params& p) {
     if (p.vgicp_search == PCR_VGICP_DIRECT_RADIUS)
         return "vgicp_search = 3 (DIRECT_RADIUS) is not served: the reference implements it in its CUDA variant only (gicp_settings.hpp:8) and "
                "FastVGICP aborts on it (fast_vgicp_voxel.hpp:13-15); use 0 (DIRECT27), 1 (DIRECT7) or 2 (DIRECT1)";
-    return nullptr;
+    // liorf_scan2map.cpp's constants.  Every handle is checked; only liorf handles read the values.
+    return liorf_params_out_of_range(p);
 }
 }  // namespace
 
@@ -273,6 +282,10 @@ void pcr_default_params(pcr_params* p) {
     p->vgicp_regularization = PCR_REG_PLANE; p->vgicp_voxel_mode = PCR_VOXEL_ADDITIVE;
     p->ndt_search = PCR_NDT_DIRECT7;
     p->vgicp_search = PCR_VGICP_DIRECT1;
+    // liorf_scan2map.cpp: :392, :186, :207, :224, :268, :388, :379, :342 (the thresholds are its double literals)
+    p->liorf_iters = 30; p->liorf_knn_max_sq = 1.0; p->liorf_plane_thresh = 0.2; p->liorf_point_thresh = 0.1;
+    p->liorf_min_rows = 50; p->liorf_min_scan = 30; p->liorf_rot_conv_deg = 0.05; p->liorf_trans_conv_cm = 0.05;
+    p->liorf_degenerate_eig = 100.0;
 }
 
 pcr_handle* pcr_create(const char* method, const pcr_params* p) {
@@ -283,6 +296,7 @@ pcr_handle* pcr_create(const char* method, const pcr_params* p) {
     else if (!strcmp(method, "ndt")) m = kNdt;
     else if (!strcmp(method, "vgicp")) m = kVgicp;
     else if (!strcmp(method, "gicp")) m = kGicp;
+    else if (!strcmp(method, "liorf")) m = kLiorf;
     else {
         // the reference factory throws on an unknown frontend.pcr (LidarOdometry.cpp:50-54)
         g_create_error = std::string("such pcr type(") + method + ") is not exist";
@@ -382,7 +396,7 @@ int pcr_scan2map_submap(pcr_handle* h, const void* src, size_t n_src, int src_on
     }
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
     const bool current = h->map_id == id && h->map_gen == gen && h->have_target &&
-                         (h->method == kLoam ? h->grid.valid && !h->clamp.use : (h->method == kNdt ? h->nd.target_ready : vgicp_family_target_ready(h)));
+                         (h->method == kLoam ? h->grid.valid && !h->clamp.use : (h->method == kNdt ? h->nd.target_ready : scored_target_ready(h)));
     // Sharded: prepare_target_from() ends in a collective (agree_prepared), so either every rank rebuilds or none does -- a rank
     // whose tile index was cut, or whose map is at another generation, must not enter that exchange while its peers are already
     // summing normal equations.  One MAX over the ranks of "I have to rebuild" decides for all.
@@ -426,12 +440,13 @@ int pcr_align(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes,
         (void)side_drain(h);      // (an alignment that failed before it collected the scan's side: nothing stays in flight behind the caller's back)
         return rc;
     }
+    if (h->method == kLiorf) return run_liorf(h, d_src, n_src, stride_bytes / 4, pose_inout, converged);
     return run_loam(h, d_src, n_src, stride_bytes / 4, pose_inout, converged, false);
 }
 
 int pcr_invalidate_target(pcr_handle* h) {
     if (!h) return 1;
-    h->have_target = false; h->grid.valid = false; h->vg.target_ready = false; h->nd.target_ready = false; h->gi.target_ready = false;
+    h->have_target = false; h->grid.valid = false; h->vg.target_ready = false; h->nd.target_ready = false; h->gi.target_ready = false; h->lf.target_ready = false;
     h->map_id = 0; h->map_gen = 0; h->roi_on = false;
     return 0;
 }

@@ -173,6 +173,7 @@ int pcr_set_query_tile(pcr_handle* h, const double lo[3], const double hi[3]) {
     h->err.clear();
     if (!lo || !hi || lo[0] > hi[0]) { h->use_tile = 0; h->have_halo = false; return 0; }
     if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_set_query_tile)");
+    if (h->method == kLiorf) return fail(h, "liorf: sharded targets are not supported in this version (pcr_set_query_tile)");
     // NDT and VGICP tiles must sit on the voxel lattice and come with a halo that is checked: pcr_set_shard
     if (h->method != kLoam) return fail(h, "pcr_set_query_tile serves loam handles; ndt and vgicp tiles are set with pcr_set_shard (voxel-aligned bounds + halo)");
     h->use_tile = 1; h->have_halo = false;
@@ -185,6 +186,7 @@ int pcr_set_shard(pcr_handle* h, const double lo[3], const double hi[3], double 
     h->err.clear();
     if (!lo || !hi || lo[0] > hi[0]) { h->use_tile = 0; h->have_halo = false; return 0; }
     if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_set_shard)");
+    if (h->method == kLiorf) return fail(h, "liorf: sharded targets are not supported in this version (pcr_set_shard)");
     if (!(halo >= 0.0)) return fail(h, "halo must be >= 0");
     for (int d = 0; d < 3; ++d) if (!(lo[d] < hi[d])) return fail(h, "tile bounds must satisfy lo < hi on every axis");
     auto on_lattice = [](double v, double res, double shift) {      // v = (k + shift) * res for an integer k, or an open face
@@ -221,6 +223,7 @@ int pcr_comm_init_host(pcr_handle* h, pcr_allreduce_fn fn, void* user, int rank,
     h->err.clear();
     if (!fn) { h->comm.host_ar = nullptr; h->comm.host_ar_user = nullptr; if (!h->comm.rccl) { h->comm.nranks = 1; h->comm.rank = 0; } return 0; }
     if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_comm_init_host)");
+    if (h->method == kLiorf) return fail(h, "liorf: sharded targets are not supported in this version (pcr_comm_init_host)");
     if (const char* no = vgicp_search_shard_refusal(h, h->prm.vgicp_search, true)) return fail(h, no);
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, "bad communicator arguments");
     if (h->comm.rccl) return fail(h, "an RCCL communicator is already set on this handle");
@@ -288,6 +291,7 @@ int pcr_comm_init_peer(pcr_handle* h, const void* ipc_handles, int rank, int nra
     if (!h) return 1;
     h->err.clear();
     if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_comm_init_peer)");
+    if (h->method == kLiorf) return fail(h, "liorf: sharded targets are not supported in this version (pcr_comm_init_peer)");
     if (const char* no = vgicp_search_shard_refusal(h, h->prm.vgicp_search, true)) return fail(h, no);
     if (!ipc_handles || nranks < 1 || nranks > kMaxPeers || rank < 0 || rank >= nranks) return fail(h, "bad peer-exchange arguments (at most 8 ranks)");
     if (!h->comm.peer_own || !h->comm.peer_exported) return fail(h, "call pcr_comm_peer_export first (every rank, for every session), then share the handles");
@@ -321,6 +325,7 @@ int pcr_comm_init(pcr_handle* h, const void* unique_id128, int rank, int nranks)
     if (!h) return 1;
     h->err.clear();
     if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_comm_init)");
+    if (h->method == kLiorf) return fail(h, "liorf: sharded targets are not supported in this version (pcr_comm_init)");
     if (const char* no = vgicp_search_shard_refusal(h, h->prm.vgicp_search, true)) return fail(h, no);
     if (!unique_id128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(h, "bad communicator arguments");
     if (set_device(h)) return 1;

@@ -1,6 +1,6 @@
 // handle.h -- struct pcr_handle and what the host units of the C ABI share (host code only; no kernel includes this).
 // The units: capi.hip (handle, scan2map / set_target / align, getters and setters), staging_host.hip, comm_host.hip,
-// loam_host.hip, vgicp_host.hip, gicp_host.hip (the two share lsq_host.h), ndt_host.hip, voxel_host.hip, query_host.hip.
+// loam_host.hip, vgicp_host.hip, gicp_host.hip (the two share lsq_host.h), liorf_host.hip, ndt_host.hip, voxel_host.hip, query_host.hip.
 // A nested struct of the handle belongs to the unit it is named after: that unit sets it up and writes it (pcr_destroy and
 // pcr_invalidate_target reach into all of them); where another unit looks into one, the member's comment says so.  What
 // several units share stays at the top level, with its users named.
@@ -17,12 +17,13 @@
 #include "pcr_internal.h"
 #include "ndt_opt.h"
 #include "vgicp_opt.h"
+#include "liorf_opt.h"
 #include "small_math.h"
 
 namespace pcr {
 namespace host {
 
-enum Method { kLoam = 0, kNdt = 1, kVgicp = 2, kGicp = 3 };
+enum Method { kLoam = 0, kNdt = 1, kVgicp = 2, kGicp = 3, kLiorf = 4 };
 
 // A block of `count` T in host-mapped memory, which kernels write through `dev` and the host reads at `host`: allocated and
 // zeroed on first use, freed with its owner.
@@ -140,6 +141,20 @@ struct pcr_handle {
         pcr::DeviceBuf d2;                   // pcr_gicp_linearize: the correspondences' float distances
         bool target_ready = false;           // (read by pcr_scan2map_submap and query; dropped by pcr_set_params, pcr_invalidate_target)
     } gi;
+
+    // LIORF work memory (liorf_host.hip).  The target is h->grid (every finite point, for the 5-NN) over the handle's own copy of the points (tgt_stage);
+    // the rows of a launch go to vg_partials, the scan kept for pcr_fitness() to fit_src.
+    struct Liorf {
+        pcr::DeviceBuf ctl;                  // two LiorfCtl: the state of the device-resident loop, by launch parity
+        pcr::host::Mapped<pcr::LiorfOut> out;    // its result and progress word
+        pcr::DeviceBuf kept, coeff, trace;   // pcr_liorf_linearize's per-point outputs; the per-iteration trace (pcr_params.record_trace)
+        bool target_ready = false;           // (read by pcr_scan2map_submap; dropped by pcr_invalidate_target)
+        // the last alignment, for pcr_liorf_result
+        bool have_result = false;
+        float six[6] = {0, 0, 0, 0, 0, 0};
+        int degenerate = 0;
+        long long rows_last = 0;
+    } lf;
 
     // region of interest of a target prepared for one scan (RoiView): two marking buffers used alternately, the dilated mask, the escape counter
     // (vgicp_host.hip: roi_enqueue, roi_view)
@@ -329,6 +344,15 @@ int run_gicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floa
 // vgicp and gicp: the methods that keep the scan and score it on demand (pcr_fitness) and whose scan side runs on the side stream
 inline bool vgicp_family(const pcr_handle* h) { return h->method == kVgicp || h->method == kGicp; }
 inline bool vgicp_family_target_ready(const pcr_handle* h) { return h->method == kGicp ? h->gi.target_ready : h->vg.target_ready; }
+
+// ---- liorf_host.hip ----
+int liorf_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats);
+int run_liorf(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged);
+// the liorf_* field of pcr_params that is out of range, named; nullptr when all are in range (pcr_create, pcr_set_params: every handle)
+const char* liorf_params_out_of_range(const pcr_params& p);
+// the methods whose pcr_fitness() scores the scan they keep, on demand, and whether their target stands
+inline bool scores_kept_scan(const pcr_handle* h) { return vgicp_family(h) || h->method == kLiorf; }
+inline bool scored_target_ready(const pcr_handle* h) { return h->method == kLiorf ? h->lf.target_ready : vgicp_family_target_ready(h); }
 
 // ---- ndt_host.hip ----
 int ndt_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, bool deferred = false, const RoiScan* roi_scan = nullptr);

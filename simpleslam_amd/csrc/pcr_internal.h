@@ -397,6 +397,35 @@ hipError_t gicp_launch_linearize(const GicpArgs& a, const Pose16& T, double* d_o
 // out32[28] = compute_error(T) on a.corr / a.corr_M; out32[0..27] = the linearisation at T (correspondences into a.corr_*next)
 hipError_t gicp_launch_error(const GicpArgs& a, const Pose16& T, double* d_out32, hipStream_t s, double seq = 0.0);
 hipError_t gicp_launch_pass_pro(const GicpArgs& a, VgCtl* d_ctl2, double* d_rows2, VgOut* d_out, hipStream_t s, double seq, int index);
+// ---------------------------------------------------------------------------
+// LIORF (liorf.hip): LioScan2map of the reference's test/comp/liorf_scan2map.cpp; the optimiser's state machine is liorf_opt.h
+// ---------------------------------------------------------------------------
+struct LiorfCtl;
+struct LiorfOut;
+struct LiorfConsts {
+    double knn_max_sq, plane_thresh, point_thresh, rot_conv_deg, trans_conv_cm, degenerate_eig;
+    int32_t iters, min_rows, file_row, pad_;
+};
+
+struct LiorfArgs {
+    const float* src; uint32_t n_src, src_stride;
+    GridView grid;               // index of every finite target point
+    const float* tgt;            // the target's points as the caller gave them (a neighbour is read at its original index)
+    uint32_t tgt_stride, pad_;
+    LiorfConsts c;
+    float six0[6];               // the initial six numbers, consumed by launch 0
+    double* partials;            // [blocks][32]: 21 AtA (upper triangle, row by row), 6 AtB, [27] the rows
+    // introspection (pcr_liorf_linearize), else NULL: kept[n_src], coeff4[n_src][4]
+    uint8_t* kept_out;
+    float* coeff_out;
+    LoamTrace* trace;            // [iters] per consumed linearisation (pcr_params.record_trace: JtJ = AtA, JtE = AtB, as rounded to float), or NULL
+};
+hipError_t liorf_launch_pass(const LiorfArgs& a, LiorfCtl* d_ctl2, double* d_rows2, LiorfOut* d_out, hipStream_t s, double seq, int index);
+// one linearisation at a.six0 and nothing else: the launch above on a state that ends after it, then the fold of its rows into d_out32
+// ([0..27] as the partials, `seq` into [31]); the float 4x4 it used is left in d_ctl2[0]
+hipError_t liorf_launch_linearize(const LiorfArgs& a, LiorfCtl* d_ctl2, double* d_rows2, LiorfOut* d_out, double* d_out32, hipStream_t s, double seq);
+uint32_t liorf_blocks(uint32_t n_src);
+
 // pcr_fitness_batch (reloc.hip): the gated score of n_poses poses (d_poses: 16 floats each, column-major) of the subset i_j = floor(j n_src / m),
 // j < m, of the source.  d_part: n_poses x ceil(m / 256) partials; d_out[h]: the sum of the counted squared distances, their number, and the
 // number of points whose nearest target point may lie beyond a cut face of the index (fitness_kernel's out32[0..2])

@@ -597,15 +597,17 @@ extern "C" {
 double pcr_fitness(pcr_handle* h) {
     if (!h) return -1.0;
     // PointCloudRegister::getFitnessScore() returns 0 unless overridden (PointCloudRegister.hpp:34);
-    // only VgicpRegister overrides it (VgicpRegister.cpp:42-45)
-    if (!vgicp_family(h)) return 0.0;
+    // only VgicpRegister overrides it (VgicpRegister.cpp:42-45); a liorf handle answers with liorf_scan2map.cpp's own getFitnessScore (:22-54)
+    if (!scores_kept_scan(h)) return 0.0;
+    const bool liorf = h->method == kLiorf;      // the file's score: d2 <= 1.0f counted, -1 when none is
     if (h->fit_pending) {
         // mean squared distance of the aligned scan to its nearest target points, against the target the handle holds NOW (PCL does
         // the same: input_ transformed by final_transformation_, searched in the current target tree)
         h->fit_pending = false;
         h->err.clear();
         h->fitness = DBL_MAX;
-        if (vgicp_family_target_ready(h) && h->fit_n > 0) {
+        if (liorf) h->fitness = -1.0;
+        if (scored_target_ready(h) && h->fit_n > 0) {
             if (set_device(h) || ensure_out32(h)) return -1.0;
             h->seq += 1.0;
             // (a lattice that holds the scan's region only cannot answer a nearest-neighbour question; the grid its covariances were searched on holds every point)
@@ -616,7 +618,7 @@ double pcr_fitness(pcr_handle* h) {
                 return -1.0;
             }
             const GridIndex& fit_grid = h->grid.filtered ? h->cov_l1 : h->grid;
-            if (fitness_launch(fit_grid, h->fit_src.as<float>(), h->fit_n, h->fit_stride, h->fit_pose, DBL_MAX, h->vg_partials.as<double>(),
+            if (fitness_launch(fit_grid, h->fit_src.as<float>(), h->fit_n, h->fit_stride, h->fit_pose, liorf ? 1.0 : DBL_MAX, h->vg_partials.as<double>(),
                                h->out32.dev, h->stream, h->seq, nullptr) != hipSuccess) { h->err = "fitness_launch failed"; return -1.0; }
             if (wait_result(h, &h->out32.host[31], h->seq)) return -1.0;
             if (h->out32.host[2] > 0) {      // (fitness_kernel: points whose nearest target point may lie beyond a cut face of the index)
@@ -624,7 +626,7 @@ double pcr_fitness(pcr_handle* h) {
                 h->fitness = -1.0;
                 return -1.0;
             }
-            h->fitness = h->out32.host[1] > 0 ? h->out32.host[0] / h->out32.host[1] : DBL_MAX;
+            h->fitness = h->out32.host[1] > 0 ? h->out32.host[0] / h->out32.host[1] : (liorf ? -1.0 : DBL_MAX);
         }
     }
     return h->fitness;

@@ -338,6 +338,22 @@ public:
     scalar_t getFitnessScore() override { return pcr_fitness(h_); }
 };
 
+// LioScan2map of the reference's test/comp/liorf_scan2map.cpp (LIO-SAM's surface scan-to-map) under the plugin interface: scan2Map takes the
+// six numbers out of `res`, iterates on the device and returns pcl::getTransformation of the final six
+class LiorfRegister : public HipRegister {
+public:
+    LiorfRegister() : HipRegister("liorf") {}
+    explicit LiorfRegister(const pcr_params& p) : HipRegister("liorf", &p) {}
+    // isDegenerate of the last scan2Map (iteration 0: the smallest eigenvalue of AtA below liorf_degenerate_eig)
+    bool isDegenerate() {
+        int deg = 0;
+        if (pcr_liorf_result(h_, nullptr, &deg, nullptr)) throw std::runtime_error(pcr_last_error(h_));
+        return deg != 0;
+    }
+    // the file's own getFitnessScore (:22-54): mean squared 1-NN distance over d2 <= 1, -1 when there is none
+    scalar_t getFitnessScore() override { return pcr_fitness(h_); }
+};
+
 // The static-map adapter: test/loc.cpp loads the global map ONCE (MapManager::MapManager(pcd_file), frontend/src/MapManager.cpp:52-78) and
 // registers every scan against it -- through the unchanged scan2Map(src, dst, res) interface.  Wrapped around any registrar above it
 // indexes `dst` at its first call (pcr_set_target: the map crosses PCIe once) and aligns every later scan against what the device holds
@@ -454,6 +470,7 @@ inline PointCloudRegister::Ptr makeRegister(const std::string& pcr_type) {
     if (pcr_type == "ndt") return std::make_shared<NdtRegister>();
     if (pcr_type == "vgicp") return std::make_shared<VgicpRegister>();
     if (pcr_type == "gicp") return std::make_shared<GicpRegister>();
+    if (pcr_type == "liorf") return std::make_shared<LiorfRegister>();
     throw std::runtime_error("such pcr type(" + pcr_type + ") is not exist, please implemented your self!");
 }
 // ... the same registrar behind the static-map adapter (localisation against a map that is loaded once)

@@ -1,5 +1,5 @@
 // align_harness.cpp -- ROS/PCL-free counterpart of the reference's test/align.cpp:
-//   align_harness <target.pcd|.f32> <source.pcd|.f32> <loam|ndt|vgicp|gicp> [init_pose.txt [search]]
+//   align_harness <target.pcd|.f32> <source.pcd|.f32> <loam|ndt|vgicp|gicp|liorf> [init_pose.txt [search]]
 // (search: ndt -- NdtRegister::setNeighborhoodSearchMethod: 1 DIRECT26, 2 DIRECT7 (the default), 3 DIRECT1;
 //          vgicp -- VgicpRegister::setNeighborSearchMethod: 0 DIRECT27, 1 DIRECT7, 2 DIRECT1 (the default))
 // loads two clouds (PCD files as align.cpp:97-107 does -- pcp/pcd_io.hpp -- or raw float32 x y z intensity records), reads the optional initial pose (4x4 row-major text,
@@ -7,6 +7,8 @@
 // (align.cpp:144), and prints what align.cpp logs: the cloud sizes before and after the filter, the elapsed time, the gated
 // fitness score (mean squared nearest-neighbour distance over the points within 1 m, align.cpp:29-61) and the final 4x4.
 // (The PCL visualiser at the end of align.cpp has no counterpart.)
+// With `liorf` it is the main of the reference's test/comp/liorf_scan2map.cpp instead: sub-map, scan and init_pose.txt as they are (that program
+// filters nothing), one scan2MapOptimization, then the final matrix and "fitness score : ..." as it prints them (:410-411).
 #include <chrono>
 #include <cstdio>
 #include <fstream>
@@ -59,6 +61,16 @@ int main(int argc, char** argv) {
             pcr = vgicp;
         }
         else if (method == "gicp") pcr = std::make_shared<PCR::GicpRegister>();
+        else if (method == "liorf") {
+            std::printf("pc points: %zu\n", source_cloud->size());                                                        // liorf_scan2map.cpp:102
+            auto liorf = std::make_shared<PCR::LiorfRegister>();
+            const bool conv = liorf->scan2Map(source_cloud, target_cloud, init_pose);
+            if (!conv) std::printf("not converge!!\n");
+            if (liorf->isDegenerate()) std::printf("degenerate!!\n");
+            for (int r = 0; r < 4; ++r) std::printf("%.9g %.9g %.9g %.9g\n", init_pose(r, 0), init_pose(r, 1), init_pose(r, 2), init_pose(r, 3));
+            std::printf("fitness score : %.9g\n", liorf->getFitnessScore());
+            return 0;
+        }
         else { std::fprintf(stderr, "no such method!!\n"); return -1; }                                                   // align.cpp:118-121
         std::printf("target cloud size: %zu\nsource cloud size: %zu\n", target_cloud->size(), source_cloud->size());
         auto t0 = std::chrono::steady_clock::now();

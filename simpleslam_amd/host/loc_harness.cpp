@@ -5,7 +5,7 @@
 //   "cores"                    -> PointCloudRegister's OpenMP team (PointCloudRegister.hpp:28-32; printed, the GPU has no use for it)
 //   "downSampleVoxelGridSize"  -> leaf of the voxel filter of the map (MapManager.cpp:57,78) and of every scan (LidarOdometry.cpp:33,36,170-171)
 //   "pcd_file"                 -> the global map, loaded with loadPCDFile (test/loc.cpp:34, MapManager.cpp:68)
-//   "frontend"."pcr"           -> loam | ndt | vgicp | gicp, the factory of LidarOdometry.cpp:32,44-54 (unknown: throws, as there)
+//   "frontend"."pcr"           -> loam | ndt | vgicp | gicp | liorf, the factory of LidarOdometry.cpp:32,44-54 (unknown: throws, as there)
 // The scan (what LidarDataProxy would deliver) is a PCD too; init_pose.txt is a 4x4 row-major pose (test/align.cpp:85-93).
 // --no-downsample skips both voxel filters for fixtures that already have the sizes BASELINE config 1 fixes (65 536 x 100 k).
 // --static <list>: the localisation loop of test/loc.cpp -- the map is loaded once, scan after scan is registered against it.  The list holds
@@ -162,7 +162,7 @@ static int run_from_config(int argc, char** argv) {
 int main(int argc, char** argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <params.json> <scan.pcd> <init_pose.txt> [--no-downsample] [--static <list> | --reloc [xy_range yaw_range_deg]]\n"
-                             "       %s <loam|ndt|vgicp|gicp> <map.f32> <scan.f32> <init_pose.txt> [grid]\n", argv[0], argv[0]);
+                             "       %s <loam|ndt|vgicp|gicp|liorf> <map.f32> <scan.f32> <init_pose.txt> [grid]\n", argv[0], argv[0]);
         return 2;
     }
     try {

@@ -40,6 +40,9 @@ class PcrParams(C.Structure):
         ("index_no_hints", C.c_int32), ("ndt_evaluate_repeats", C.c_int32), ("loam_disable_cache", C.c_int32), ("record_timeline", C.c_int32),
         ("loam_coresident", C.c_int32), ("loam_clamp_margin_mm", C.c_int32), ("full_target", C.c_int32), ("host_optimiser", C.c_int32),
         ("host_copy_xyz", C.c_int32),
+        ("liorf_iters", C.c_int32), ("liorf_file_row", C.c_int32), ("liorf_knn_max_sq", C.c_double), ("liorf_plane_thresh", C.c_double), ("liorf_point_thresh", C.c_double),
+        ("liorf_min_rows", C.c_int32), ("liorf_min_scan", C.c_int32), ("liorf_rot_conv_deg", C.c_double), ("liorf_trans_conv_cm", C.c_double),
+        ("liorf_degenerate_eig", C.c_double),
         ("gicp_max_corr_dist", C.c_double),
         ("vgicp_regularization", C.c_int32), ("vgicp_voxel_mode", C.c_int32),
     ]
@@ -80,6 +83,7 @@ ABI_SYMBOLS = [
     "pcr_sc_query", "pcr_knn", "pcr_radius_search", "pcr_fitness_batch", "pcr_reloc_default_params", "pcr_reloc_hypotheses", "pcr_relocalize",
     "pcr_sc_distances", "pcr_global_reloc_default_params", "pcr_global_reloc_hypotheses", "pcr_relocalize_global",
     "pcr_sc_rank_stored", "pcr_sc_shift_yaw",
+    "pcr_liorf_pose_to_6dof", "pcr_liorf_6dof_to_pose", "pcr_liorf_linearize", "pcr_liorf_result",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -162,6 +166,11 @@ def load_library():
     L.pcr_ndt_derivatives.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, dp, dp, dp, dp]
     L.pcr_get_timeline.argtypes = [vp, vp, C.c_size_t, ip, ip]
     L.pcr_ndt_voxels.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    fp = C.POINTER(C.c_float)
+    L.pcr_liorf_pose_to_6dof.argtypes = [dp, fp]
+    L.pcr_liorf_6dof_to_pose.argtypes = [fp, dp]
+    L.pcr_liorf_linearize.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, fp, fp, vp, vp, dp, dp, C.POINTER(C.c_int64)]
+    L.pcr_liorf_result.argtypes = [vp, fp, ip, C.POINTER(C.c_int64)]
     L.pcr_vgicp_voxels.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.pcr_vgicp_correspondences.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.pcr_ndt_pass_sums.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, C.c_int, dp, dp, dp]
@@ -901,9 +910,71 @@ class GicpRegister(PointCloudRegister):
         return out
 
 
+def liorf_pose_to_6dof(T):
+    """pcr_liorf_pose_to_6dof (host only): [roll, pitch, yaw, x, y, z] as float32 -- pcl::getEulerAngles and the translation of the float cast of T."""
+    c = _pose_in(T)
+    out = np.zeros(6, np.float32)
+    if load_library().pcr_liorf_pose_to_6dof(c.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise PcrError("pcr_liorf_pose_to_6dof failed")
+    return out
+
+
+def liorf_6dof_to_pose(six):
+    """pcr_liorf_6dof_to_pose (host only): pcl::getTransformation of [roll, pitch, yaw, x, y, z], formed in float; a 4x4 float64 array of float values."""
+    s = np.ascontiguousarray(six, dtype=np.float32).reshape(6)
+    buf = np.zeros(16)
+    if load_library().pcr_liorf_6dof_to_pose(s.ctypes.data_as(C.POINTER(C.c_float)), buf.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise PcrError("pcr_liorf_6dof_to_pose failed")
+    return _pose_out(buf)
+
+
+class LiorfRegister(PointCloudRegister):
+    """LioScan2map of the reference's test/comp/liorf_scan2map.cpp: LIO-SAM's surface scan-to-map (5-NN, float plane fit, weighted point-to-plane
+    rows, 6 x 6 normal equations on [roll, pitch, yaw, x, y, z]).  The liorf_* fields of pcr_params are keyword arguments; getFitnessScore() is the
+    file's own score (mean squared 1-NN distance over d2 <= 1, -1 when there is none)."""
+    method = "liorf"
+
+    def result(self):
+        """pcr_liorf_result of the last scan2Map / align: dict(six (6,) float32, degenerate bool, rows_last int)."""
+        six = np.zeros(6, np.float32)
+        deg, rows = C.c_int(0), C.c_int64(0)
+        self._check(self._lib.pcr_liorf_result(self._h, six.ctypes.data_as(C.POINTER(C.c_float)), C.byref(deg), C.byref(rows)))
+        return dict(six=six, degenerate=bool(deg.value), rows_last=int(rows.value))
+
+    def isDegenerate(self):
+        return self.result()["degenerate"]
+
+    def linearize(self, src, six):
+        """One linearisation at the six numbers against the kept target (setTarget; pcr_liorf_linearize): dict(T (4,4) float32 = the matrix the
+        device built, kept (n,) bool, coeff (n,4) float32, AtA (6,6), AtB (6,), n)."""
+        p, n, s, dev, _k = _cloud(src)
+        s6 = np.ascontiguousarray(six, dtype=np.float32).reshape(6)
+        T = np.zeros(16, np.float32)
+        kept = np.zeros(n, np.uint8)
+        coeff = np.zeros((n, 4), np.float32)
+        AtA, AtB = np.zeros(36), np.zeros(6)
+        nk = C.c_int64(0)
+        dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+        self._check(self._lib.pcr_liorf_linearize(self._h, p, n, s, dev, s6.ctypes.data_as(fp), T.ctypes.data_as(fp), kept.ctypes.data_as(C.c_void_p),
+                                                  coeff.ctypes.data_as(C.c_void_p), AtA.ctypes.data_as(dp), AtB.ctypes.data_as(dp), C.byref(nk)))
+        return dict(T=T.reshape(4, 4), kept=kept.astype(bool), coeff=coeff, AtA=AtA.reshape(6, 6), AtB=AtB, n=int(nk.value))
+
+    def trace(self):
+        """Per solved iteration of the last call (record_trace=1): dict(AtA (k,6,6), AtB (k,6), x (k,6), n (k,)) -- the float systems and steps."""
+        iters = max(int(self.params.liorf_iters), 1)
+        n_it = C.c_int32(0)
+        A, b, x = np.zeros(iters * 36), np.zeros(iters * 6), np.zeros(iters * 6)
+        n = np.zeros(iters, np.int64)
+        dp = C.POINTER(C.c_double)
+        self._check(self._lib.pcr_get_trace(self._h, C.byref(n_it), A.ctypes.data_as(dp), b.ctypes.data_as(dp), n.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            x.ctypes.data_as(dp)))
+        k = n_it.value
+        return dict(AtA=A.reshape(-1, 6, 6)[:k], AtB=b.reshape(-1, 6)[:k], x=x.reshape(-1, 6)[:k], n=n[:k])
+
+
 def make_register(pcr_type, **overrides):
-    """The reference's factory on cfg["frontend"]["pcr"] (LidarOdometry.cpp:32,44-54), plus "gicp"."""
-    table = {"loam": LoamRegister, "ndt": NdtRegister, "vgicp": VgicpRegister, "gicp": GicpRegister}
+    """The reference's factory on cfg["frontend"]["pcr"] (LidarOdometry.cpp:32,44-54), plus "gicp" and "liorf"."""
+    table = {"loam": LoamRegister, "ndt": NdtRegister, "vgicp": VgicpRegister, "gicp": GicpRegister, "liorf": LiorfRegister}
     if pcr_type not in table:
         raise RuntimeError(f"such pcr type({pcr_type}) is not exist, please implemented your self!")
     return table[pcr_type](**overrides)

@@ -261,3 +261,54 @@ def pose_error(Ta, Tb):
     # angle from the skew part: accurate near zero where acos is not
     s = 0.5 * np.linalg.norm([Rr[2, 1] - Rr[1, 2], Rr[0, 2] - Rr[2, 0], Rr[1, 0] - Rr[0, 1]])
     return dt, float(np.arctan2(s, c))
+
+
+# ---- small scenes of a few planes (the liorf tests): everything within +-10 m of the map frame's origin ----
+PLANE_SCENES = {
+    # (axis of the normal, its coordinate, the ranges of the two other axes in x < y < z order)
+    "corner": [(0, -3.0, (-3.0, 5.0), (-1.5, 3.0)), (1, -3.0, (-3.0, 5.0), (-1.5, 3.0)), (2, -1.5, (-3.0, 5.0), (-3.0, 5.0))],
+    "corridor": [(1, -2.0, (-8.0, 8.0), (-1.5, 2.5)), (1, 2.0, (-8.0, 8.0), (-1.5, 2.5)), (2, -1.5, (-8.0, 8.0), (-2.0, 2.0))],
+    "ground_wall": [(2, -1.5, (-3.0, 6.0), (-4.0, 4.0)), (0, -3.0, (-4.0, 4.0), (-1.5, 3.0))],
+}
+
+
+def _plane_points(plane, u, v, w):
+    axis, at, _, _ = plane
+    p = np.empty((len(u), 3))
+    others = [a for a in range(3) if a != axis]
+    p[:, others[0]], p[:, others[1]], p[:, axis] = u, v, at + w
+    return p
+
+
+def plane_scene(kind, n_map=20000, n_scan=2085, seed=0, noise=0.01):
+    """A scene of axis-aligned planes (PLANE_SCENES: "corner" constrains all six degrees of freedom, "corridor" leaves the translation along
+    x free, "ground_wall" the one along y): the map sampled on a jittered lattice, the scan at random on the same planes and expressed in the
+    sensor frame of T_true.  -> (scan (n_scan, 4) float32, map (n_map, 4) float32, T_true (4, 4)); intensity 0."""
+    planes = PLANE_SCENES[kind]
+    rng = np.random.default_rng([seed, 31, sorted(PLANE_SCENES).index(kind)])
+    area = np.array([(p[2][1] - p[2][0]) * (p[3][1] - p[3][0]) for p in planes])
+    counts = np.floor(n_map * area / area.sum()).astype(int)
+    counts[0] += n_map - counts.sum()
+    parts = []
+    for p, cnt in zip(planes, counts):
+        du, dv = p[2][1] - p[2][0], p[3][1] - p[3][0]
+        nu = max(int(np.ceil(np.sqrt(cnt * du / dv))), 1)
+        nv = int(np.ceil(cnt / nu))
+        gu, gv = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
+        sel = rng.permutation(nu * nv)[:cnt]
+        u = p[2][0] + (gu.ravel()[sel] + rng.uniform(0.1, 0.9, cnt)) * du / nu
+        v = p[3][0] + (gv.ravel()[sel] + rng.uniform(0.1, 0.9, cnt)) * dv / nv
+        parts.append(_plane_points(p, u, v, rng.normal(0, noise, cnt)))
+    m = np.concatenate(parts)[rng.permutation(n_map)]
+    which = rng.choice(len(planes), n_scan, p=area / area.sum())
+    s = np.empty((n_scan, 3))
+    for k, p in enumerate(planes):
+        sel = np.flatnonzero(which == k)
+        s[sel] = _plane_points(p, rng.uniform(p[2][0] + 0.3, p[2][1] - 0.3, len(sel)), rng.uniform(p[3][0] + 0.3, p[3][1] - 0.3, len(sel)),
+                               rng.normal(0, noise, len(sel)))
+    T = se3_exp([0.5, -0.3, -0.9, 0.05, -0.04, 0.3])
+    Ti = np.linalg.inv(T)
+    s = s @ Ti[:3, :3].T + Ti[:3, 3]
+    out_s, out_m = np.zeros((n_scan, 4), np.float32), np.zeros((n_map, 4), np.float32)
+    out_s[:, :3], out_m[:, :3] = s, m
+    return out_s, out_m, T
