@@ -1,10 +1,9 @@
-// capi.hip -- the C ABI of libpcr_hip.so (include/pcr_hip.h): handle management, the scan2map / set_target / align entry points
-// and the launch sequence they go through, the getters and setters.  The drivers of the methods and the other entry points are in
-// the *_host.hip units (handle.h lists them); host C++ only talks to the kernels through the launchers in pcr_internal.h.
+// capi.hip -- the C ABI of libpcr_hip.so (include/pcr_hip.h): handle management, the method table, what the scan2map / set_target /
+// align entry points do for every method before they go through it, the getters and setters.  What a method does behind its row of the
+// table is in its own *_host.hip unit, as are the other entry points (handle.h lists the units); no entry point here picks a driver or a readiness flag by naming a method.
+// Host C++ only talks to the kernels through the launchers in pcr_internal.h.
 
 #include <string.h>
-
-#include <functional>
 
 #include "handle.h"
 
@@ -16,6 +15,16 @@ namespace host {
 
 thread_local std::string g_create_error;
 
+// One row per Method, in the enum's order.  pcr_fitness of liorf is liorf_scan2map.cpp's own score (:22-54): d2 <= 1.0f counted, -1 when none is.
+static const MethodOps kMethods[] = {
+    {"loam", true, false, false, DBL_MAX, DBL_MAX, loam_scan2map, loam_prepare_target, loam_align, loam_target_from_changed},
+    {"ndt", true, true, false, DBL_MAX, DBL_MAX, ndt_scan2map, ndt_kept_target, run_ndt, ndt_target_from_changed},
+    {"vgicp", true, true, true, DBL_MAX, DBL_MAX, vgicp_scan2map, vgicp_kept_target, vgicp_align, vgicp_target_from_changed},
+    {"gicp", false, true, true, DBL_MAX, DBL_MAX, gicp_scan2map, gicp_kept_target, gicp_align, gicp_target_from_changed},
+    {"liorf", false, true, true, 1.0, -1.0, liorf_scan2map, liorf_prepare_target, run_liorf, liorf_target_from_changed},
+};
+const MethodOps& ops(const pcr_handle* h) { return kMethods[h->method]; }
+
 // the call's times from the events recorded at its start, after its target index and at its end (profiling level >= 1)
 int read_call_times(pcr_handle* h) {
     float ms = 0;
@@ -25,13 +34,8 @@ int read_call_times(pcr_handle* h) {
     return 0;
 }
 
-}  // namespace host
-}  // namespace pcr
-
-namespace {
-
 // profiling passes: the counters cleared (on the handle's stream, ahead of everything the call queues), the covariance events made
-int prof_begin(pcr_handle* h) {
+static int prof_begin(pcr_handle* h) {
     h->ev_cov_tgt_used = h->ev_cov_src_used = false; h->nd_prof_launches = 0;
     h->stats.aux_kernel_ms = 0; h->stats.region_points = h->stats.region_voxels = h->stats.pairs_grad = h->stats.pairs_hess = 0;
     if (h->profile < 2) return 0;
@@ -41,7 +45,7 @@ int prof_begin(pcr_handle* h) {
     return 0;
 }
 // ... read back once the call's work has drained
-int prof_end(pcr_handle* h) {
+static int prof_end(pcr_handle* h) {
     if (h->profile < 2 || !h->prof_count.p) return 0;
     uint32_t c[64];
     H_TRY(hipStreamSynchronize(h->stream));
@@ -62,7 +66,7 @@ int prof_end(pcr_handle* h) {
     return 0;
 }
 
-// ... the end of a timed NDT / VGICP scan2map call: its end recorded and waited for, its times and counters read
+// ... the end of a timed scan2map call (the methods whose passes are profiled): its end recorded and waited for, its times and counters read
 int end_timed_call(pcr_handle* h) {
     if (h->profile < 1) return 0;
     H_TRY(hipEventRecord(h->ev_end, h->stream));
@@ -71,9 +75,10 @@ int end_timed_call(pcr_handle* h) {
     return prof_end(h);
 }
 
-// a new registration starts: whatever pcr_fitness() could evaluate belongs to the previous one (a call that fails during
-// target preparation must not leave the new scan's points paired with the old pose)
-void drop_fitness_state(pcr_handle* h) { h->fit_pending = false; h->fit_n = 0; h->fit_copied_from = nullptr; h->fitness = -1.0; }
+}  // namespace host
+}  // namespace pcr
+
+namespace {
 
 int do_scan2map(pcr_handle* h, const void* src, size_t n_src, const void* dst, size_t n_dst, size_t stride_bytes,
                 double pose[16], int* converged, bool on_device) {
@@ -85,134 +90,21 @@ int do_scan2map(pcr_handle* h, const void* src, size_t n_src, const void* dst, s
     if ((n_src && !src) || (n_dst && !dst)) return fail(h, "NULL cloud with nonzero size");
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
     const float *d_src, *d_dst;
-    if (h->method != kLoam && prof_begin(h)) return 1;
+    if (ops(h).passes_profiled && prof_begin(h)) return 1;
     if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_start, h->stream));
     if (on_device) { d_src = (const float*)src; d_dst = (const float*)dst; }
     else {
         if (stage_host(h, &h->tgt_stage, dst, n_dst, stride_bytes, &d_dst)) return 1;
         if (stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
     }
-    if (h->method == kNdt) {
-        // NdtRegister::scan2Map calls setInputTarget every time, which rebuilds the voxel grid (NdtRegister.cpp:23)
-        // Unsharded: the index is enqueued unchecked (previous box as a hint, cell table as it is) and the alignment's own result
-        // says whether that held; if not, once more with the checked build.
-        const bool try_deferred = !sharded(h) && n_src > 0 && h->prm.host_optimiser == 0;
-        double pose_in[16];
-        memcpy(pose_in, pose, sizeof pose_in);
-        // (unsharded, device loop: the voxel Gaussians are prepared only where this scan can land -- RoiView; a call that leaves the
-        //  region is repeated on the whole target)
-        bool use_roi = try_deferred && h->prm.full_target == 0;
-        const RoiScan rs{d_src, n_src, stride_bytes / 4, pose_in};
-        for (int attempt = 0; attempt < 3; ++attempt) {
-            const bool deferred = try_deferred && attempt == 0;
-            h->blob_pending = h->blob_stored = false;
-            // the optimiser's initial state rides on the launch that marks the region (run_ndt then starts without a launch for it)
-            if (use_roi && ndt_ride_initial_state(h, pose)) return 1;
-            const int prep_rc = ndt_prepare_target(h, d_dst, n_dst, stride_bytes / 4, deferred, use_roi ? &rs : nullptr);
-            h->blob_pending = false;
-            if (agree_prepared(h, prep_rc)) { h->blob_stored = false; return 1; }
-            if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
-            const int rrc = run_ndt(h, d_src, n_src, stride_bytes / 4, pose, converged);
-            h->blob_stored = false;
-            if (rrc == 2) { use_roi = false; memcpy(pose, pose_in, sizeof pose_in); if (deferred && h->nd_grid_checked && !h->nd_grid_bad && !h->nd_grid_empty) { h->grid.confirm(); h->grid.note_cells(h->nd_grid_cells); } continue; }
-            if (rrc) return 1;
-            if (!deferred) break;
-            if (h->nd_grid_checked && !h->nd_grid_bad) { if (!h->nd_grid_empty) { h->grid.confirm(); h->grid.note_cells(h->nd_grid_cells); } break; }
-            // the hint or the table size did not hold (or the device loop handed over to the host before it could tell): checked build
-            h->grid.hint_margin = 8; h->grid.cells_hint = 0;      // (a cloud that left the old box: its cell count is anybody's guess too)
-            memcpy(pose, pose_in, sizeof pose_in);
-        }
-        return end_timed_call(h);
-    }
-    if (h->method == kVgicp) {
-        // the reference keeps its target structures while the cloud POINTER is unchanged and goes stale
-        // when the cloud is edited in place; this entry point always rebuilds them
-        // (source side first: its ~15 launches run on the side stream while the host is still queueing the target's.  Measured the other
-        //  way round -- target builds queued first, source side enqueued while the host waits for them -- 1.17 instead of 0.93 ms: the
-        //  two covariance kernels then run side by side for their whole length and slow each other down)
-        // The target exists for this scan only, so only the part of it the scan can reach is prepared (RoiView): the covariances of a
-        // 1 M-point map were 0.4 of a 0.85 ms call, of which the scan looks up a tenth.  Should the optimiser carry the scan out of that
-        // region, the whole target is prepared and the call repeated from the same guess.
-        const bool use_roi = !sharded(h) && n_src > 0 && h->prm.host_optimiser == 0 && h->prm.vgicp_max_iters > 0 && h->prm.full_target == 0;
-        double pose_in[16];
-        memcpy(pose_in, pose, sizeof pose_in);
-        const RoiScan rs{d_src, n_src, stride_bytes / 4, pose_in};
-        // Order of the two sides.  The scan's own covariances used to be the longest thing in a call (344 us) and were queued first; since
-        // they are searched in two classes (cov_search.hip: ~190 us with the scan's index levels) the target is the long pole, and the
-        // dozen launches of the scan's side cost the host ~100 us during which the main stream sat empty.  Now the target's builds are
-        // queued first and the scan's side while the host waits for their headers (settle_cov_levels: before_wait).
-        // (Measured and not kept: the scan's side queued by a host thread of its own at the same time as the target's -- 0.481 / 0.495 against
-        //  0.496 / 0.494 ms: with both sides on the device from the start the call is bound by the device's work, not by the host's launches.)
-        bool src_queued = false;
-        const std::function<int()> queue_src = [&]() -> int { src_queued = true; return vgicp_source_enqueue(h, d_src, n_src, stride_bytes / 4, true); };
-        int prc = vgicp_source_mark(h);
-        if (!prc) prc = vgicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4, use_roi ? &rs : nullptr, false, &queue_src);
-        if (!prc && !src_queued) prc = queue_src();
-        if (prc) (void)side_drain(h);
-        if (agree_prepared(h, prc)) {
-            (void)side_drain(h);
-            return 1;
-        }
-        if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
-        int rrc = vgicp_align_recut(h, d_src, n_src, stride_bytes / 4, pose, converged);
-        if (rrc == 2) {
-            memcpy(pose, pose_in, sizeof pose_in);
-            if (vgicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4, nullptr)) return 1;
-            rrc = vgicp_align_recut(h, d_src, n_src, stride_bytes / 4, pose, converged);
-        }
-        if (rrc) return 1;
-        return end_timed_call(h);
-    }
-    if (h->method == kGicp) {
-        // the whole target, every call: its index and covariances queued first, the scan's side while the host waits for the headers (as above)
-        bool src_queued = false;
-        const std::function<int()> queue_src = [&]() -> int { src_queued = true; return vgicp_source_enqueue(h, d_src, n_src, stride_bytes / 4, true); };
-        int prc = vgicp_source_mark(h);
-        if (!prc) prc = gicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4, &queue_src);
-        if (!prc && !src_queued) prc = queue_src();
-        if (prc) { (void)side_drain(h); return 1; }
-        if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
-        if (run_gicp(h, d_src, n_src, stride_bytes / 4, pose, converged)) { (void)side_drain(h); return 1; }
-        return end_timed_call(h);
-    }
-    if (h->method == kLiorf) {
-        // kdtreeSurfFromMap->setInputCloud on every call (liorf_scan2map.cpp:390): the whole target indexed, every call
-        if (liorf_prepare_target(h, d_dst, n_dst, stride_bytes / 4)) return 1;
-        if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
-        if (run_liorf(h, d_src, n_src, stride_bytes / 4, pose, converged)) return 1;
-        return end_timed_call(h);
-    }
-    // the reference rebuilds its index on every call (LoamRegister.cpp:110); so do we
-    h->clamp.use = 0;
-    if (build_target(h, d_dst, n_dst, stride_bytes / 4)) {
-        if (!sharded(h)) return 1;
-        h->grid.valid = false;         // sharded: run_loam tells the other ranks and all of them fail together
-        h->tgt_ptr = d_dst; h->tgt_n = n_dst; h->tgt_stride = stride_bytes / 4;
-    }
-    if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
-    h->clamp_allowed = true;           // this target exists for this scan only: a box that cannot be tabulated may be cut around it
-    const int rc = run_loam(h, d_src, n_src, stride_bytes / 4, pose, converged, true);
-    h->clamp_allowed = false;
-    if (h->clamp.use) { h->clamp.use = 0; h->have_target = false; h->grid.valid = false; }      // not an index pcr_align may reuse
-    return rc;
+    return ops(h).scan2map(h, d_src, n_src, d_dst, n_dst, stride_bytes / 4, pose, converged);
 }
 
 // target structures of the handle's method from points in HBM that outlive them (the staging copy of pcr_set_target, or a
 // pcr_map's sub-map for as long as its generation lasts)
 int prepare_target_from(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_bytes) {
     h->map_id = 0; h->map_gen = 0;      // (pcr_scan2map_submap sets them after a successful preparation)
-    if (h->method == kVgicp) return agree_prepared(h, vgicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4));
-    if (h->method == kNdt) return agree_prepared(h, ndt_prepare_target(h, d_dst, n_dst, stride_bytes / 4));
-    if (h->method == kGicp) return gicp_prepare_target(h, d_dst, n_dst, stride_bytes / 4);      // (never sharded: nothing to agree on)
-    if (h->method == kLiorf) return liorf_prepare_target(h, d_dst, n_dst, stride_bytes / 4);    // (the same)
-    h->clamp.use = 0;
-    // settle the cell-table size now so that pcr_align never has to rebuild
-    int rc = build_target(h, d_dst, n_dst, stride_bytes / 4);
-    h->clamp_from_bulk = true;          // a box that cannot be tabulated is cut to the bulk of the cloud (set_clamp_from_target_sample)
-    if (!rc) rc = settle_loam_index(h, nullptr, 0, 0, nullptr);
-    h->clamp_from_bulk = false;
-    if (rc) { h->have_target = false; h->grid.valid = false; }
-    return agree_prepared(h, rc);
+    return ops(h).prepare_target(h, d_dst, n_dst, stride_bytes / 4);
 }
 
 }  // namespace
@@ -291,19 +183,15 @@ void pcr_default_params(pcr_params* p) {
 pcr_handle* pcr_create(const char* method, const pcr_params* p) {
     g_create_error.clear();
     if (!method) { g_create_error = "method is NULL"; return nullptr; }
-    Method m;
-    if (!strcmp(method, "loam")) m = kLoam;
-    else if (!strcmp(method, "ndt")) m = kNdt;
-    else if (!strcmp(method, "vgicp")) m = kVgicp;
-    else if (!strcmp(method, "gicp")) m = kGicp;
-    else if (!strcmp(method, "liorf")) m = kLiorf;
-    else {
+    int m = 0;
+    while (m <= kLiorf && strcmp(method, kMethods[m].name)) ++m;
+    if (m > kLiorf) {
         // the reference factory throws on an unknown frontend.pcr (LidarOdometry.cpp:50-54)
         g_create_error = std::string("such pcr type(") + method + ") is not exist";
         return nullptr;
     }
     pcr_handle* h = new pcr_handle();
-    h->method = m;
+    h->method = (Method)m;
     pcr_default_params(&h->prm);
     if (p) {
         if (p->struct_size != sizeof(pcr_params)) { g_create_error = "pcr_params.struct_size mismatch (call pcr_default_params first)"; delete h; return nullptr; }
@@ -395,8 +283,7 @@ int pcr_scan2map_submap(pcr_handle* h, const void* src, size_t n_src, int src_on
         return do_scan2map(h, src, n_src, nullptr, 0, stride_bytes, pose_inout, converged, src_on_device != 0);
     }
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
-    const bool current = h->map_id == id && h->map_gen == gen && h->have_target &&
-                         (h->method == kLoam ? h->grid.valid && !h->clamp.use : (h->method == kNdt ? h->nd.target_ready : scored_target_ready(h)));
+    const bool current = h->map_id == id && h->map_gen == gen && h->have_target && target_prepared(h);
     // Sharded: prepare_target_from() ends in a collective (agree_prepared), so either every rank rebuilds or none does -- a rank
     // whose tile index was cut, or whose map is at another generation, must not enter that exchange while its peers are already
     // summing normal equations.  One MAX over the ranks of "I have to rebuild" decides for all.
@@ -428,25 +315,12 @@ int pcr_align(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes,
     drop_fitness_state(h);
     const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
-    if (h->method == kNdt) return run_ndt(h, d_src, n_src, stride_bytes / 4, pose_inout, converged);
-    if (vgicp_family(h)) {
-        // the scan's own side (two index levels, the 20-neighbour search, the covariances) queued on the side stream with its headers mirrored to the host, as
-        // pcr_scan2map queues it -- unless pcr_scan2map_submap has queued it already, ahead of the target's preparation.  Settled the checked way (a header
-        // read back after every level: two host round trips with an idle device in between, ~55 us of a 0.3 ms call against a kept sub-map) only if that fails.
-        if (!sharded(h) && n_src > 0 && !(h->side_pending && h->side_src == d_src && h->side_n == n_src && h->side_stride == stride_bytes / 4) &&
-            vgicp_source_enqueue(h, d_src, n_src, stride_bytes / 4)) return 1;
-        const int rc = (h->method == kGicp ? run_gicp(h, d_src, n_src, stride_bytes / 4, pose_inout, converged)
-                                           : vgicp_align_recut(h, d_src, n_src, stride_bytes / 4, pose_inout, converged)) ? 1 : 0;
-        (void)side_drain(h);      // (an alignment that failed before it collected the scan's side: nothing stays in flight behind the caller's back)
-        return rc;
-    }
-    if (h->method == kLiorf) return run_liorf(h, d_src, n_src, stride_bytes / 4, pose_inout, converged);
-    return run_loam(h, d_src, n_src, stride_bytes / 4, pose_inout, converged, false);
+    return ops(h).align(h, d_src, n_src, stride_bytes / 4, pose_inout, converged);
 }
 
 int pcr_invalidate_target(pcr_handle* h) {
     if (!h) return 1;
-    h->have_target = false; h->grid.valid = false; h->vg.target_ready = false; h->nd.target_ready = false; h->gi.target_ready = false; h->lf.target_ready = false;
+    h->have_target = false; h->grid.valid = false; h->target_ready = false;
     h->map_id = 0; h->map_gen = 0; h->roi_on = false;
     return 0;
 }
@@ -501,17 +375,12 @@ int pcr_set_params(pcr_handle* h, const pcr_params* p) {
     const pcr_params old = h->prm;
     h->prm = *p;
     h->prm.device = old.device;
-    // whatever was derived from a parameter that changed is dropped; the optimiser settings are read at every call
-    if (p->loam_knn_max_sq != old.loam_knn_max_sq && h->method == kLoam) { h->have_target = false; h->grid.valid = false; }
-    if ((p->ndt_resolution != old.ndt_resolution || p->ndt_min_points != old.ndt_min_points) && h->method == kNdt) { h->nd.target_ready = false; h->have_target = false; h->grid.valid = false; }
-    if (p->vgicp_resolution != old.vgicp_resolution && h->method == kVgicp) { h->vg.target_ready = false; h->have_target = false; h->grid.valid = false; }
-    // (gicp: the resolution is the cell of its index, k_corr the neighbourhood of its covariances; the gate and the optimiser settings are read at every call)
-    if ((p->vgicp_resolution != old.vgicp_resolution || p->vgicp_k_corr != old.vgicp_k_corr) && h->method == kGicp) { h->gi.target_ready = false; h->have_target = false; h->grid.valid = false; }
-    // the regularisation shaped every covariance the handle holds, the voxel mode the voxel map: the prepared target goes as it does with the resolution, and
-    // a scan's side that is still in flight (pcr_scan2map_submap queues it ahead) is collected and forgotten -- its covariances are the old setting's
+    // whatever was derived from a parameter that changed is dropped (each method's unit says what its target is derived from); the optimiser
+    // settings are read at every call.  (A loam handle never sets target_ready: there is none to clear.)
+    if (ops(h).target_from_changed(old, *p)) { h->target_ready = false; h->have_target = false; h->grid.valid = false; }
+    // the regularisation shaped every covariance the handle holds: a scan's side that is still in flight (pcr_scan2map_submap queues it ahead) is
+    // collected and forgotten -- its covariances are the old setting's
     const bool reg_changed = p->vgicp_regularization != old.vgicp_regularization;
-    if ((reg_changed || p->vgicp_voxel_mode != old.vgicp_voxel_mode) && h->method == kVgicp) { h->vg.target_ready = false; h->have_target = false; h->grid.valid = false; }
-    if (reg_changed && h->method == kGicp) { h->gi.target_ready = false; h->have_target = false; h->grid.valid = false; }
     if (reg_changed && vgicp_family(h) && h->side_pending && !set_device(h)) (void)side_drain(h);
     return 0;
 }

@@ -116,6 +116,12 @@ namespace {
 // pcr_set_shard: faces farther out than this are open (the outer tiles reach to +-1e30, shard.py)
 inline bool open_face(double v) { return !(fabs(v) < 1e29); }
 
+// the entry points that give a handle a tile or a communicator: a method whose row of the method table says it is not shardable refuses, by name
+int refuse_if_unshardable(pcr_handle* h, const char* entry_point) {
+    if (ops(h).shardable) return 0;
+    return fail(h, std::string(ops(h).name) + ": sharded targets are not supported in this version (" + entry_point + ")");
+}
+
 }  // namespace
 
 namespace pcr {
@@ -172,8 +178,7 @@ int pcr_set_query_tile(pcr_handle* h, const double lo[3], const double hi[3]) {
     if (!h) return 1;
     h->err.clear();
     if (!lo || !hi || lo[0] > hi[0]) { h->use_tile = 0; h->have_halo = false; return 0; }
-    if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_set_query_tile)");
-    if (h->method == kLiorf) return fail(h, "liorf: sharded targets are not supported in this version (pcr_set_query_tile)");
+    if (refuse_if_unshardable(h, "pcr_set_query_tile")) return 1;
     // NDT and VGICP tiles must sit on the voxel lattice and come with a halo that is checked: pcr_set_shard
     if (h->method != kLoam) return fail(h, "pcr_set_query_tile serves loam handles; ndt and vgicp tiles are set with pcr_set_shard (voxel-aligned bounds + halo)");
     h->use_tile = 1; h->have_halo = false;
@@ -185,8 +190,7 @@ int pcr_set_shard(pcr_handle* h, const double lo[3], const double hi[3], double 
     if (!h) return 1;
     h->err.clear();
     if (!lo || !hi || lo[0] > hi[0]) { h->use_tile = 0; h->have_halo = false; return 0; }
-    if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_set_shard)");
-    if (h->method == kLiorf) return fail(h, "liorf: sharded targets are not supported in this version (pcr_set_shard)");
+    if (refuse_if_unshardable(h, "pcr_set_shard")) return 1;
     if (!(halo >= 0.0)) return fail(h, "halo must be >= 0");
     for (int d = 0; d < 3; ++d) if (!(lo[d] < hi[d])) return fail(h, "tile bounds must satisfy lo < hi on every axis");
     auto on_lattice = [](double v, double res, double shift) {      // v = (k + shift) * res for an integer k, or an open face
@@ -210,11 +214,10 @@ int pcr_set_shard(pcr_handle* h, const double lo[3], const double hi[3], double 
             if (!on_lattice(lo[d], res, 0.5) || !on_lattice(hi[d], res, 0.5))
                 return fail(h, "vgicp: tile bounds must lie on the voxel lattice, (k + 0.5) * vgicp_resolution (fast_vgicp_voxel.hpp:158-160)");
         if (halo < res) return fail(h, "vgicp: the halo must be at least one voxel (and hold every tile point's 20 nearest neighbours: checked per call)");
+        h->target_ready = false;      // a target prepared for another tile was checked against another halo (vgicp_prepare_target: the halo check)
     }
     h->use_tile = 1; h->have_halo = true; h->halo = halo;
     for (int d = 0; d < 3; ++d) { h->tile_lo[d] = lo[d]; h->tile_hi[d] = hi[d]; }
-    // a target prepared for another tile was checked against another halo
-    h->vg.target_ready = false;
     return 0;
 }
 
@@ -222,8 +225,7 @@ int pcr_comm_init_host(pcr_handle* h, pcr_allreduce_fn fn, void* user, int rank,
     if (!h) return 1;
     h->err.clear();
     if (!fn) { h->comm.host_ar = nullptr; h->comm.host_ar_user = nullptr; if (!h->comm.rccl) { h->comm.nranks = 1; h->comm.rank = 0; } return 0; }
-    if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_comm_init_host)");
-    if (h->method == kLiorf) return fail(h, "liorf: sharded targets are not supported in this version (pcr_comm_init_host)");
+    if (refuse_if_unshardable(h, "pcr_comm_init_host")) return 1;
     if (const char* no = vgicp_search_shard_refusal(h, h->prm.vgicp_search, true)) return fail(h, no);
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, "bad communicator arguments");
     if (h->comm.rccl) return fail(h, "an RCCL communicator is already set on this handle");
@@ -290,8 +292,7 @@ int pcr_comm_peer_export(pcr_handle* h, void* ipc_handle64) {
 int pcr_comm_init_peer(pcr_handle* h, const void* ipc_handles, int rank, int nranks) {
     if (!h) return 1;
     h->err.clear();
-    if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_comm_init_peer)");
-    if (h->method == kLiorf) return fail(h, "liorf: sharded targets are not supported in this version (pcr_comm_init_peer)");
+    if (refuse_if_unshardable(h, "pcr_comm_init_peer")) return 1;
     if (const char* no = vgicp_search_shard_refusal(h, h->prm.vgicp_search, true)) return fail(h, no);
     if (!ipc_handles || nranks < 1 || nranks > kMaxPeers || rank < 0 || rank >= nranks) return fail(h, "bad peer-exchange arguments (at most 8 ranks)");
     if (!h->comm.peer_own || !h->comm.peer_exported) return fail(h, "call pcr_comm_peer_export first (every rank, for every session), then share the handles");
@@ -324,8 +325,7 @@ int pcr_comm_init_peer(pcr_handle* h, const void* ipc_handles, int rank, int nra
 int pcr_comm_init(pcr_handle* h, const void* unique_id128, int rank, int nranks) {
     if (!h) return 1;
     h->err.clear();
-    if (h->method == kGicp) return fail(h, "gicp: sharded targets are not supported in this version (pcr_comm_init)");
-    if (h->method == kLiorf) return fail(h, "liorf: sharded targets are not supported in this version (pcr_comm_init)");
+    if (refuse_if_unshardable(h, "pcr_comm_init")) return 1;
     if (const char* no = vgicp_search_shard_refusal(h, h->prm.vgicp_search, true)) return fail(h, no);
     if (!unique_id128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(h, "bad communicator arguments");
     if (set_device(h)) return 1;

@@ -15,7 +15,7 @@ namespace host {
 // The whole target, always: an index of every finite point for the exact 1-NN (h->grid, with the coarse level of a scan-sized cloud's
 // covariance search in h->cov_l1) and the covariance of every point.  A box no dense table can hold would need a cut index: refused.
 int gicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, const std::function<int()>* before_wait) {
-    h->gi.target_ready = false;
+    h->target_ready = false;
     h->roi_on = false;
     h->clamp.use = 0;
     const double res = h->prm.vgicp_resolution;
@@ -54,7 +54,7 @@ int gicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t 
     }
     H_TRY(vgicp_launch_cov(*cov_grid, levels > 1 ? &h->cov_l1 : nullptr, levels > 2 ? &h->vg.cov_l2 : nullptr, d_dst, stride_floats, n_dst,
                            h->gi.tgt_cov6.as<double>(), h->stream, h->prm.vgicp_regularization, nullptr, nullptr, &h->vg.tgt_scratch));
-    h->gi.target_ready = true;
+    h->target_ready = true;
     return 0;
 }
 
@@ -87,7 +87,7 @@ GicpArgs gicp_args(const pcr_handle* h, const float* d_src, size_t n_src, size_t
 
 // the scan's covariances settled, the correspondence buffers and the rows' memory in place
 int gicp_setup(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats) {
-    if (!h->gi.target_ready) return fail(h, "no target prepared");
+    if (!h->target_ready) return fail(h, "no target prepared");
     if (sharded(h) || h->use_tile) return fail(h, "gicp: sharded handles are not supported in this version");
     if (n_src > kMaxPoints) return fail(h, "source cloud too large");
     if (ensure_out32(h)) return 1;
@@ -123,6 +123,25 @@ int run_gicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floa
     return 0;
 }
 
+// ---- gicp's row of the method table (handle.h: MethodOps) ----
+int gicp_scan2map(pcr_handle* h, const float* d_src, size_t n_src, const float* d_dst, size_t n_dst, size_t stride_floats, double pose[16], int* converged) {
+    // the whole target, every call: its index and covariances queued first, the scan's side while the host waits for the headers (as vgicp_scan2map)
+    bool src_queued = false;
+    const std::function<int()> queue_src = [&]() -> int { src_queued = true; return vgicp_source_enqueue(h, d_src, n_src, stride_floats, true); };
+    int prc = vgicp_source_mark(h);
+    if (!prc) prc = gicp_prepare_target(h, d_dst, n_dst, stride_floats, &queue_src);
+    if (!prc && !src_queued) prc = queue_src();
+    if (prc) { (void)side_drain(h); return 1; }
+    if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
+    if (run_gicp(h, d_src, n_src, stride_floats, pose, converged)) { (void)side_drain(h); return 1; }
+    return end_timed_call(h);
+}
+int gicp_kept_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats) { return gicp_prepare_target(h, d_dst, n_dst, stride_floats); }      // (never sharded: nothing to agree on)
+int gicp_align(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) { return align_beside_scan_side(h, d_src, n_src, stride_floats, pose, converged, run_gicp); }
+// the resolution is the cell of its index, k_corr the neighbourhood of its covariances, the regularisation shaped them; the gate and the optimiser
+// settings are read at every call
+bool gicp_target_from_changed(const pcr_params& old_p, const pcr_params& new_p) { return new_p.vgicp_resolution != old_p.vgicp_resolution || new_p.vgicp_k_corr != old_p.vgicp_k_corr || new_p.vgicp_regularization != old_p.vgicp_regularization; }
+
 }  // namespace host
 }  // namespace pcr
 
@@ -136,7 +155,7 @@ int pcr_gicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t stri
     if (!pose || !H || !b) return fail(h, "pose, H or b is NULL");
     if (n_src && !src) return fail(h, "NULL cloud with nonzero size");
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
-    if (!h->gi.target_ready || !h->have_target) return fail(h, "no target: call pcr_set_target first");
+    if (!h->target_ready || !h->have_target) return fail(h, "no target: call pcr_set_target first");
     const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
     if (gicp_setup(h, d_src, n_src, stride_bytes / 4)) { (void)side_drain(h); return 1; }

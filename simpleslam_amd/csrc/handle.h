@@ -1,9 +1,10 @@
 // handle.h -- struct pcr_handle and what the host units of the C ABI share (host code only; no kernel includes this).
-// The units: capi.hip (handle, scan2map / set_target / align, getters and setters), staging_host.hip, comm_host.hip,
-// loam_host.hip, vgicp_host.hip, gicp_host.hip (the two share lsq_host.h), liorf_host.hip, ndt_host.hip, voxel_host.hip, query_host.hip.
-// A nested struct of the handle belongs to the unit it is named after: that unit sets it up and writes it (pcr_destroy and
-// pcr_invalidate_target reach into all of them); where another unit looks into one, the member's comment says so.  What
-// several units share stays at the top level, with its users named.
+// The units: capi.hip (handle, the method table, the common part of scan2map / set_target / align, getters and setters), staging_host.hip,
+// comm_host.hip, one unit per method -- loam_host.hip, ndt_host.hip, vgicp_host.hip, gicp_host.hip (the two share lsq_host.h), liorf_host.hip:
+// each owns the functions of its row of the table (MethodOps) --, fitness_host.hip, voxel_host.hip, query_host.hip.
+// A nested struct of the handle belongs to the unit it is named after: that unit sets it up and writes it (pcr_destroy reaches
+// into all of them); where another unit looks into one, the member's comment says so.  What several units share stays at the
+// top level, with its users named.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -69,6 +70,9 @@ struct pcr_handle {
     const float* tgt_ptr = nullptr;   // device pointer the index was built from (for rebuild on overflow) (capi, loam, vgicp, ndt, query)
     size_t tgt_n = 0, tgt_stride = 0;
     bool have_target = false;        // capi, loam, vgicp, ndt, query
+    // ndt, vgicp, gicp, liorf: the method's own target structures stand.  Set by the method's *_prepare_target alone; dropped by it, by pcr_set_params,
+    // pcr_invalidate_target, pcr_set_shard (vgicp) and query's fit_grid_for (ndt).  A loam handle never sets it: read through target_prepared()
+    bool target_ready = false;
     pcr::ClampBox clamp{};           // LOAM scan2map fallback: region of interest of a target whose full box cannot be tabulated (capi, loam, vgicp)
     bool clamp_allowed = false;      // set while a scan2map call (target rebuilt for this very scan) is running (capi, loam)
     bool clamp_from_bulk = false;    // pcr_set_target in progress: an untabulatable box may be cut to the bulk of the target (capi, loam)
@@ -105,7 +109,7 @@ struct pcr_handle {
     pcr::host::Mapped<double> out32;     // 32 doubles written by sum_partials_kernel (staging: ensure_out32; vgicp, query)
     // getFitnessScore() is a call of its own in the reference (VgicpRegister.cpp:42-45: PCL evaluates it when asked, from the source it
     // still holds): an unsharded alignment keeps a copy of the scan and the final pose, and pcr_fitness() evaluates the score on demand
-    // (vgicp; capi: drop_fitness_state; query: reloc_point_fitness_at)
+    // (fitness_host.hip; the drivers of vgicp, gicp and liorf keep the scan and arm the score; query: reloc_point_fitness_at)
     pcr::DeviceBuf fit_src;
     const float* fit_copied_from = nullptr;   // the scan fit_src holds (copied on the side stream by vgicp_source_enqueue)
     size_t fit_n = 0, fit_stride = 0;
@@ -128,7 +132,6 @@ struct pcr_handle {
         size_t lin_n = 0;
         int lin_search = 0;
         pcr::CovScratch src_scratch, tgt_scratch;   // neighbour lists + queue of the covariance search of a scan-sized cloud: the source's runs on the side stream beside the target's
-        bool target_ready = false;       // (read by pcr_scan2map_submap; dropped by pcr_set_params, pcr_set_shard, pcr_invalidate_target)
         pcr::DeviceBuf reduced;              // sharded VGICP over the peer exchange: a pass's 32 sums folded over the rows and the ranks
         pcr::DeviceBuf cov_viol;         // VGICP halo check: number of neighbourhoods that reach past the halo
     } vg;
@@ -139,7 +142,6 @@ struct pcr_handle {
         pcr::DeviceBuf tgt_cov6;             // per target point, original order
         pcr::DeviceBuf corr[2], M[2];        // the two correspondence buffers (original target index / Mahalanobis matrix per source point), chosen by the state's parity
         pcr::DeviceBuf d2;                   // pcr_gicp_linearize: the correspondences' float distances
-        bool target_ready = false;           // (read by pcr_scan2map_submap and query; dropped by pcr_set_params, pcr_invalidate_target)
     } gi;
 
     // LIORF work memory (liorf_host.hip).  The target is h->grid (every finite point, for the 5-NN) over the handle's own copy of the points (tgt_stage);
@@ -148,7 +150,6 @@ struct pcr_handle {
         pcr::DeviceBuf ctl;                  // two LiorfCtl: the state of the device-resident loop, by launch parity
         pcr::host::Mapped<pcr::LiorfOut> out;    // its result and progress word
         pcr::DeviceBuf kept, coeff, trace;   // pcr_liorf_linearize's per-point outputs; the per-iteration trace (pcr_params.record_trace)
-        bool target_ready = false;           // (read by pcr_scan2map_submap; dropped by pcr_invalidate_target)
         // the last alignment, for pcr_liorf_result
         bool have_result = false;
         float six[6] = {0, 0, 0, 0, 0, 0};
@@ -166,7 +167,7 @@ struct pcr_handle {
     bool roi_on = false;             // the target structures the handle holds cover only the region of the scan they were prepared for (capi, vgicp, ndt)
     long long roi_repeats = 0;       // calls that left the region and were repeated on the whole target (vgicp, ndt; capi: pcr_get_stats)
     pcr::BlobStore blob;             // the optimiser's initial state as a rider of the region's mark pass (pcr_internal.h: BlobStore) (ndt fills it, roi_enqueue launches it)
-    bool blob_pending = false;       //   filled in by this call and not launched yet (capi: do_scan2map, ndt, vgicp: roi_enqueue)
+    bool blob_pending = false;       //   filled in by this call and not launched yet (ndt, vgicp: roi_enqueue)
     bool blob_stored = false;        //   launched by this call: run_ndt needs no launch of its own for it
 
     // NDT work memory (ndt_host.hip)
@@ -177,11 +178,10 @@ struct pcr_handle {
         pcr::DeviceBuf sums;                 // sharded device loop: the 48 sums of a pass, all-reduced in place
         pcr::host::Mapped<pcr::NdtOut> out;  // its result and progress word
         int count_idx = 0;
-        bool target_ready = false;       // (read by pcr_scan2map_submap; dropped by pcr_set_params, pcr_invalidate_target and query's fit_grid_for)
         int iters = 0, deriv = 0, hess = 0;
         double score = 0;
     } nd;
-    bool nd_grid_checked = false, nd_grid_bad = false, nd_grid_empty = false;      // the device loop reported the state of the index header with its result (ndt: run_ndt writes; capi: do_scan2map reads)
+    bool nd_grid_checked = false, nd_grid_bad = false, nd_grid_empty = false;      // the device loop reported the state of the index header with its result (ndt: run_ndt writes, ndt_scan2map reads)
     uint64_t nd_grid_cells = 0;
 
     // the voxel filter (voxel_host.hip)
@@ -268,7 +268,31 @@ inline hipError_t side_drain(pcr_handle* h) {
 struct RoiScan { const float* d_src; size_t n_src, stride_floats; const double* pose; };
 
 // ---- capi.hip ----
+// What the entry points dispatch on, one row per Method (the table itself: capi.hip).  The functions of a row live in the method's own unit.
+typedef int Scan2MapFn(pcr_handle* h, const float* d_src, size_t n_src, const float* d_dst, size_t n_dst, size_t stride_floats, double pose[16], int* converged);
+typedef int PrepareTargetFn(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats);
+typedef int AlignFn(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged);
+typedef bool TargetFromChangedFn(const pcr_params& old_p, const pcr_params& new_p);
+struct MethodOps {
+    const char* name;                // pcr_create's lookup, the prefix of the refusal of a sharded target
+    bool shardable;                  // pcr_set_shard, pcr_set_query_tile and pcr_comm_init* serve the method
+    bool passes_profiled;            // pcr_scan2map starts the profiling passes (prof_begin) and the method ends the call with end_timed_call
+    bool scores_kept_scan;           // pcr_fitness() evaluates the scan the last alignment kept, on demand; else it returns 0
+    double fit_max_sq, fit_none;     // ... the score's gate and its value when no point counts
+    Scan2MapFn* scan2map;            // pcr_scan2map: the target prepared for this scan and the scan aligned to it (both clouds in HBM, ev_start recorded)
+    PrepareTargetFn* prepare_target; // a target that is kept, from points in HBM that outlive it: pcr_set_target, a sub-map, ensure_full_target
+    AlignFn* align;                  // pcr_align, once the handle has a target
+    TargetFromChangedFn* target_from_changed;      // pcr_set_params: what the prepared target was derived from has changed
+};
+Scan2MapFn loam_scan2map, ndt_scan2map, vgicp_scan2map, gicp_scan2map, liorf_scan2map;
+PrepareTargetFn loam_prepare_target, ndt_kept_target, vgicp_kept_target, gicp_kept_target, liorf_prepare_target;
+AlignFn loam_align, run_ndt, vgicp_align, gicp_align, run_liorf;
+TargetFromChangedFn loam_target_from_changed, ndt_target_from_changed, vgicp_target_from_changed, gicp_target_from_changed, liorf_target_from_changed;
+const MethodOps& ops(const pcr_handle* h);
+// the handle holds a target prepared in full by prepare_target (pcr_scan2map_submap: nothing to rebuild while the map's generation lasts)
+inline bool target_prepared(const pcr_handle* h) { return h->method == kLoam ? h->grid.valid && !h->clamp.use : h->target_ready; }
 int read_call_times(pcr_handle* h);
+int end_timed_call(pcr_handle* h);
 int ensure_full_target(pcr_handle* h);
 
 // ---- staging_host.hip ----
@@ -307,6 +331,8 @@ int vgicp_source_enqueue(pcr_handle* h, const float* d_src, size_t n_src, size_t
 int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, const RoiScan* roi_scan = nullptr, bool keep_clamp = false,
                          const std::function<int()>* before_wait = nullptr);
 int vgicp_align_recut(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged);
+// pcr_align of vgicp and gicp: the scan's side queued unless pcr_scan2map_submap has queued it, `run`, the side stream drained
+int align_beside_scan_side(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged, AlignFn* run);
 
 // What settle_cov_levels does beyond building and sizing the levels
 struct CovSettle {
@@ -341,23 +367,22 @@ int vgicp_source_settle(pcr_handle* h, const float* d_src, size_t n_src, size_t 
 // ---- gicp_host.hip ----
 int gicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, const std::function<int()>* before_wait = nullptr);
 int run_gicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged);
-// vgicp and gicp: the methods that keep the scan and score it on demand (pcr_fitness) and whose scan side runs on the side stream
+// vgicp and gicp: the methods whose scan side (its index levels and covariances) runs on the side stream
 inline bool vgicp_family(const pcr_handle* h) { return h->method == kVgicp || h->method == kGicp; }
-inline bool vgicp_family_target_ready(const pcr_handle* h) { return h->method == kGicp ? h->gi.target_ready : h->vg.target_ready; }
 
 // ---- liorf_host.hip ----
-int liorf_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats);
-int run_liorf(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged);
 // the liorf_* field of pcr_params that is out of range, named; nullptr when all are in range (pcr_create, pcr_set_params: every handle)
 const char* liorf_params_out_of_range(const pcr_params& p);
-// the methods whose pcr_fitness() scores the scan they keep, on demand, and whether their target stands
-inline bool scores_kept_scan(const pcr_handle* h) { return vgicp_family(h) || h->method == kLiorf; }
-inline bool scored_target_ready(const pcr_handle* h) { return h->method == kLiorf ? h->lf.target_ready : vgicp_family_target_ready(h); }
 
 // ---- ndt_host.hip ----
 int ndt_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, bool deferred = false, const RoiScan* roi_scan = nullptr);
 int ndt_ride_initial_state(pcr_handle* h, const double pose[16]);
-int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged);
+
+// ---- fitness_host.hip: the scan an alignment keeps for pcr_fitness() (the methods whose row says scores_kept_scan) ----
+void drop_fitness_state(pcr_handle* h);
+bool fitness_scan_kept(pcr_handle* h, const float* d_src);
+int keep_scan_for_fitness(pcr_handle* h, const float* d_src, size_t n, size_t stride_floats, bool kept);
+void arm_fitness(pcr_handle* h, const double pose[16], size_t n, size_t stride_floats);
 
 // ---- query_host.hip ----
 std::string cut_fitness_message(double n);

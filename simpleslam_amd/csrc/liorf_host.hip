@@ -29,7 +29,7 @@ const char* liorf_params_out_of_range(const pcr_params& p) {
 // The whole target, always: an index of every finite point for the exact 5-NN.  The cell decides how many candidates a search visits,
 // never a result.  A box no dense table can hold would need a cut index: refused.
 int liorf_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats) {
-    h->lf.target_ready = false;
+    h->target_ready = false;
     h->have_target = false;
     h->roi_on = false;
     h->clamp.use = 0;
@@ -53,7 +53,7 @@ int liorf_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t
         return 1;
     }
     h->have_target = true;
-    h->lf.target_ready = true;
+    h->target_ready = true;
     return 0;
 }
 
@@ -79,7 +79,7 @@ LiorfArgs liorf_args(const pcr_handle* h, const float* d_src, size_t n_src, size
 
 // the state's and the rows' memory in place
 int liorf_setup(pcr_handle* h, size_t n_src) {
-    if (!h->lf.target_ready || !h->have_target || !h->grid.valid) return fail(h, "no target prepared");
+    if (!h->target_ready || !h->have_target || !h->grid.valid) return fail(h, "no target prepared");
     if (sharded(h) || h->use_tile) return fail(h, "liorf: sharded handles are not supported in this version");
     if (n_src > kMaxPoints) return fail(h, "source cloud too large");
     if (ensure_out32(h)) return 1;
@@ -149,6 +149,17 @@ int run_liorf(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_flo
     return 0;
 }
 
+// ---- liorf's row of the method table (handle.h: MethodOps; its kept target is liorf_prepare_target -- never sharded: nothing to agree on --, its align run_liorf) ----
+int liorf_scan2map(pcr_handle* h, const float* d_src, size_t n_src, const float* d_dst, size_t n_dst, size_t stride_floats, double pose[16], int* converged) {
+    // kdtreeSurfFromMap->setInputCloud on every call (liorf_scan2map.cpp:390): the whole target indexed, every call
+    if (liorf_prepare_target(h, d_dst, n_dst, stride_floats)) return 1;
+    if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
+    if (run_liorf(h, d_src, n_src, stride_floats, pose, converged)) return 1;
+    return end_timed_call(h);
+}
+// the index has a fixed cell and holds every point: no parameter shapes it (the thresholds are read at every call)
+bool liorf_target_from_changed(const pcr_params&, const pcr_params&) { return false; }
+
 }  // namespace host
 }  // namespace pcr
 
@@ -185,7 +196,7 @@ int pcr_liorf_linearize(pcr_handle* h, const void* src, size_t n_src, size_t str
     if (!six || !AtA || !AtB) return fail(h, "six, AtA or AtB is NULL");
     if (n_src && !src) return fail(h, "NULL cloud with nonzero size");
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
-    if (!h->lf.target_ready || !h->have_target) return fail(h, "no target: call pcr_set_target first");
+    if (!h->target_ready || !h->have_target) return fail(h, "no target: call pcr_set_target first");
     const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
     if (liorf_setup(h, n_src)) return 1;

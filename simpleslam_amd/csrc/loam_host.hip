@@ -323,6 +323,36 @@ int run_loam(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floa
     return fail(h, "target index could not be sized");
 }
 
+// ---- loam's row of the method table (handle.h: MethodOps) ----
+int loam_scan2map(pcr_handle* h, const float* d_src, size_t n_src, const float* d_dst, size_t n_dst, size_t stride_floats, double pose[16], int* converged) {
+    // the reference rebuilds its index on every call (LoamRegister.cpp:110); so do we
+    h->clamp.use = 0;
+    if (build_target(h, d_dst, n_dst, stride_floats)) {
+        if (!sharded(h)) return 1;
+        h->grid.valid = false;         // sharded: run_loam tells the other ranks and all of them fail together
+        h->tgt_ptr = d_dst; h->tgt_n = n_dst; h->tgt_stride = stride_floats;
+    }
+    if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
+    h->clamp_allowed = true;           // this target exists for this scan only: a box that cannot be tabulated may be cut around it
+    const int rc = run_loam(h, d_src, n_src, stride_floats, pose, converged, true);
+    h->clamp_allowed = false;
+    if (h->clamp.use) { h->clamp.use = 0; h->have_target = false; h->grid.valid = false; }      // not an index pcr_align may reuse
+    return rc;
+}
+int loam_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats) {
+    h->clamp.use = 0;
+    // settle the cell-table size now so that pcr_align never has to rebuild
+    int rc = build_target(h, d_dst, n_dst, stride_floats);
+    h->clamp_from_bulk = true;          // a box that cannot be tabulated is cut to the bulk of the cloud (set_clamp_from_target_sample)
+    if (!rc) rc = settle_loam_index(h, nullptr, 0, 0, nullptr);
+    h->clamp_from_bulk = false;
+    if (rc) { h->have_target = false; h->grid.valid = false; }
+    return agree_prepared(h, rc);
+}
+int loam_align(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) { return run_loam(h, d_src, n_src, stride_floats, pose, converged, false); }
+// the gate sets the cell of the index
+bool loam_target_from_changed(const pcr_params& old_p, const pcr_params& new_p) { return new_p.loam_knn_max_sq != old_p.loam_knn_max_sq; }
+
 }  // namespace host
 }  // namespace pcr
 

@@ -1,6 +1,6 @@
 // lsq_host.h -- what the host drivers of the methods on fast_gicp::LsqRegistration's loop share (vgicp_host.hip, gicp_host.hip): the
-// Levenberg-Marquardt driver over the state machine of vgicp_opt.h, on the device or on the host, the scan kept for pcr_fitness(),
-// the search cell of a map-sized target's covariances, the layout of a pass's sums.  The device side is lsq_pass.h.
+// Levenberg-Marquardt driver over the state machine of vgicp_opt.h, on the device or on the host, the search cell of a map-sized target's
+// covariances, the layout of a pass's sums (liorf_host.hip takes that and the pace of the device loop from here).  The device side is lsq_pass.h.
 #pragma once
 #include <algorithm>
 
@@ -74,28 +74,6 @@ inline void lsq_report(pcr_handle* h, const LsqResult& r, size_t n_src, double p
     if (converged) *converged = r.conv ? 1 : 0;
     h->stats.iterations = r.outer; h->stats.n_src = (int64_t)n_src; h->stats.n_dst = (int64_t)h->tgt_n;
     h->stats.kernel_launches = r.n_lin + r.n_err;
-}
-
-// An alignment of scan d_src begins: whatever score was pending is dropped.  Returns whether fit_src holds this very scan already (the side
-// stream copied it: vgicp_source_enqueue).
-inline bool fitness_scan_kept(pcr_handle* h, const float* d_src) {
-    h->fit_pending = false;
-    const bool kept = h->fit_copied_from == d_src && d_src != nullptr;
-    h->fit_copied_from = nullptr;
-    return kept;
-}
-// ... and once the scan's side has settled, an unsharded handle keeps the scan for a later pcr_fitness()
-inline int keep_scan_for_fitness(pcr_handle* h, const float* d_src, size_t n, size_t stride_floats, bool kept) {
-    if (kept || sharded(h) || n == 0) return 0;
-    H_TRY(h->fit_src.reserve(n * stride_floats * sizeof(float)));
-    H_TRY(hipMemcpyAsync(h->fit_src.p, d_src, n * stride_floats * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    return 0;
-}
-// pcl::Registration::getFitnessScore() of that scan at `pose` is evaluated when asked for (pcr_fitness), as in the reference
-inline void arm_fitness(pcr_handle* h, const double pose[16], size_t n, size_t stride_floats) {
-    for (int i = 0; i < 16; ++i) h->fit_pose[i] = pose[i];
-    h->fit_n = n; h->fit_stride = stride_floats; h->fit_pending = true;
-    h->fitness = DBL_MAX;
 }
 
 // A map-sized cloud's covariances are searched on ONE level whose cell is sized for the 20-neighbour radius, not for the voxel lattice:

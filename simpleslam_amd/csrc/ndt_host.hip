@@ -27,7 +27,7 @@ static double ndt_roi_margin(int search, double res) {
 // current size; whether either was wrong (header.overflow / header.stale) comes back with the result of the alignment
 // (NdtOut), and the caller then prepares again the slow, checked way.  One host round trip less per scan.
 int ndt_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, bool deferred, const RoiScan* roi_scan) {
-    h->nd.target_ready = false;
+    h->target_ready = false;
     h->roi_on = false;
     const double res = (double)(float)h->prm.ndt_resolution;     // resolution_ is a float (ndt_omp.h)
     if (!(res > 0)) return fail(h, "ndt_resolution must be positive");
@@ -82,7 +82,7 @@ int ndt_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t s
     }
     H_TRY(ndt_launch_voxels(h->grid, h->nd.slot.as<uint32_t>(), h->nd.vox.as<NdtVoxel>(), nd_count, nd_count_next, h->nd.list.as<uint32_t>(),
                             max_vox, min_points, 0.01, h->stream, h->roi_on ? &roi : nullptr, bf.tail_applied));
-    h->nd.target_ready = true;
+    h->target_ready = true;
     return 0;
 }
 
@@ -190,7 +190,7 @@ static int ndt_loop_device(pcr_handle* h, const NdtArgs& a, const NdtPose& T0, c
     NdtCtl* d_ctl = h->nd.ctl.as<NdtCtl>();
     NdtOut* out = h->nd.out.host;
     const double seq = (h->seq += 1.0);
-    // (a scan2map call whose region was marked has stored this state with the mark pass: do_scan2map, BlobStore)
+    // (a scan2map call whose region was marked has stored this state with the mark pass: ndt_scan2map, BlobStore)
     const bool stored = h->blob_stored && h->roi_on;
     h->blob_stored = false;
     if (!stored) H_TRY(ndt_launch_ctl_init(d_ctl, T0, p0, h->prm.ndt_step_size, h->prm.ndt_trans_eps, h->prm.ndt_max_iters, h->stream, h->prm.ndt_evaluate_repeats,
@@ -273,7 +273,7 @@ static int ndt_loop_host(pcr_handle* h, const NdtArgs& a, const NdtPose& T0, con
 // Returns 0 with nd_grid_bad set when the index must be prepared again and the call repeated, 2 when a target prepared for the scan's
 // region has to give way to the whole target.
 int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) {
-    if (!h->nd.target_ready) return fail(h, "no target prepared");
+    if (!h->target_ready) return fail(h, "no target prepared");
     if (n_src > kMaxPoints) return fail(h, "source cloud too large");
     H_TRY(h->nd.out48.ensure(48));
     H_TRY(h->nd.out.ensure());
@@ -300,7 +300,7 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
         device_loop = !res.bail;
     } else if (on_device) {
         if (ndt_loop_device(h, a, T0, p0, &res)) return 1;
-        h->nd_grid_bad = res.grid_overflow || res.grid_stale;      // (what the loop saw in the index header: do_scan2map reads it)
+        h->nd_grid_bad = res.grid_overflow || res.grid_stale;      // (what the loop saw in the index header: ndt_scan2map reads it)
         h->nd_grid_empty = res.grid_empty != 0; h->nd_grid_cells = res.grid_cells; h->nd_grid_checked = true;
         if (h->nd_grid_bad) return 0;           // the caller prepares the target again and repeats the call
         // a pass looked up a voxel the target was not prepared for (RoiView), or the loop wants the host's SVD: whole target, again
@@ -317,6 +317,43 @@ int run_ndt(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_float
     return 0;
 }
 
+// ---- ndt's row of the method table (handle.h: MethodOps; its align is run_ndt) ----
+int ndt_scan2map(pcr_handle* h, const float* d_src, size_t n_src, const float* d_dst, size_t n_dst, size_t stride_floats, double pose[16], int* converged) {
+    // NdtRegister::scan2Map calls setInputTarget every time, which rebuilds the voxel grid (NdtRegister.cpp:23)
+    // Unsharded: the index is enqueued unchecked (previous box as a hint, cell table as it is) and the alignment's own result
+    // says whether that held; if not, once more with the checked build.
+    const bool try_deferred = !sharded(h) && n_src > 0 && h->prm.host_optimiser == 0;
+    double pose_in[16];
+    memcpy(pose_in, pose, sizeof pose_in);
+    // (unsharded, device loop: the voxel Gaussians are prepared only where this scan can land -- RoiView; a call that leaves the
+    //  region is repeated on the whole target)
+    bool use_roi = try_deferred && h->prm.full_target == 0;
+    const RoiScan rs{d_src, n_src, stride_floats, pose_in};
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        const bool deferred = try_deferred && attempt == 0;
+        h->blob_pending = h->blob_stored = false;
+        // the optimiser's initial state rides on the launch that marks the region (run_ndt then starts without a launch for it)
+        if (use_roi && ndt_ride_initial_state(h, pose)) return 1;
+        const int prep_rc = ndt_prepare_target(h, d_dst, n_dst, stride_floats, deferred, use_roi ? &rs : nullptr);
+        h->blob_pending = false;
+        if (agree_prepared(h, prep_rc)) { h->blob_stored = false; return 1; }
+        if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
+        const int rrc = run_ndt(h, d_src, n_src, stride_floats, pose, converged);
+        h->blob_stored = false;
+        if (rrc == 2) { use_roi = false; memcpy(pose, pose_in, sizeof pose_in); if (deferred && h->nd_grid_checked && !h->nd_grid_bad && !h->nd_grid_empty) { h->grid.confirm(); h->grid.note_cells(h->nd_grid_cells); } continue; }
+        if (rrc) return 1;
+        if (!deferred) break;
+        if (h->nd_grid_checked && !h->nd_grid_bad) { if (!h->nd_grid_empty) { h->grid.confirm(); h->grid.note_cells(h->nd_grid_cells); } break; }
+        // the hint or the table size did not hold (or the device loop handed over to the host before it could tell): checked build
+        h->grid.hint_margin = 8; h->grid.cells_hint = 0;      // (a cloud that left the old box: its cell count is anybody's guess too)
+        memcpy(pose, pose_in, sizeof pose_in);
+    }
+    return end_timed_call(h);
+}
+int ndt_kept_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats) { return agree_prepared(h, ndt_prepare_target(h, d_dst, n_dst, stride_floats)); }
+// the voxel Gaussians: the lattice's cell and the points a voxel needs
+bool ndt_target_from_changed(const pcr_params& old_p, const pcr_params& new_p) { return new_p.ndt_resolution != old_p.ndt_resolution || new_p.ndt_min_points != old_p.ndt_min_points; }
+
 }  // namespace host
 }  // namespace pcr
 
@@ -328,7 +365,7 @@ int pcr_ndt_derivatives(pcr_handle* h, const void* src, size_t n_src, size_t str
     h->err.clear();
     if (h->method != kNdt) return fail(h, "pcr_ndt_derivatives needs an ndt handle");
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
-    if (!h->nd.target_ready) return fail(h, "no target: call pcr_set_target first");
+    if (!h->target_ready) return fail(h, "no target: call pcr_set_target first");
     if (ensure_full_target(h)) return 1;
     const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
@@ -356,7 +393,7 @@ int pcr_ndt_voxels(pcr_handle* h, pcr_ndt_voxel* out, size_t capacity, size_t* c
     h->err.clear();
     if (h->method != kNdt) return fail(h, "pcr_ndt_voxels needs an ndt handle");
     if (set_device(h)) return 1;
-    if (!h->nd.target_ready) return fail(h, "no target: call pcr_set_target first");
+    if (!h->target_ready) return fail(h, "no target: call pcr_set_target first");
     if (h->roi_on) return fail(h, "pcr_ndt_voxels: pcr_scan2map prepared this target for that one scan's region only; call pcr_set_target for a target that is kept");
     H_TRY(hipStreamSynchronize(h->stream));
     GridHeader hd;
@@ -407,7 +444,7 @@ int pcr_ndt_pass_sums(pcr_handle* h, const void* src, size_t n_src, size_t strid
     if (kind != kNdtPassDerivH && kind != kNdtPassDeriv && kind != kNdtPassHessian) return fail(h, "pcr_ndt_pass_sums: kind must be 0, 1 or 2");
     if (!p || !grad || !hess) return fail(h, "pcr_ndt_pass_sums: p, grad or hess is NULL");
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
-    if (!h->nd.target_ready) return fail(h, "no target: call pcr_set_target first");
+    if (!h->target_ready) return fail(h, "no target: call pcr_set_target first");
     if (sharded(h)) return fail(h, "pcr_ndt_pass_sums: a handle with a communicator does not run the one-launch-per-pass loop");
     if (n_src > kMaxPoints) return fail(h, "source cloud too large");
     if (ensure_full_target(h)) return 1;

@@ -42,7 +42,7 @@ int fit_grid_for(pcr_handle* h, const GridIndex** out) {
             if (settle_grid(h, h->cov_l1, h->tgt_ptr, h->tgt_n, h->tgt_stride, h->prm.vgicp_resolution * scale, 0, nullptr)) return 1;
             *out = &h->cov_l1;
         } else if (h->method == kNdt && staged) {
-            h->nd.target_ready = false;
+            h->target_ready = false;
             if (settle_grid(h, h->grid, h->tgt_ptr, h->tgt_n, h->tgt_stride, (double)(float)h->prm.ndt_resolution, 1)) return 1;
         } else if (h->method == kVgicp) {
             return fail(h, "the voxel lattice of the last pcr_scan2map holds the scan's region only (pcr_stats.region_index), its search grid does not hold "

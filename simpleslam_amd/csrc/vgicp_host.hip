@@ -1,7 +1,7 @@
 // vgicp_host.hip -- VGICP's host side: what is its own around PCL align() + LsqRegistration (lsq_registration_impl.hpp:53-171; the
 // driver is lsq_host.h's run_lsq, GICP's too) -- a cut index's escapes, a region's repeat, the peer loop, the sharded fitness score --
 // with the index levels of its covariance searches, the scan's side on its own stream, the region a target is prepared for
-// (roi_enqueue: NDT uses it too), pcr_fitness and the pcr_vgicp_* entry points.
+// (roi_enqueue: NDT uses it too), its row of the method table and the pcr_vgicp_* entry points.
 
 #include <algorithm>
 
@@ -331,7 +331,7 @@ static double vgicp_roi_margin(int search, double res) { return search == PCR_VG
 // keep_clamp: the caller has set h->clamp (a region cut around a scan, vgicp_align_recut): index that region instead of deciding here
 int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats, const RoiScan* roi_scan, bool keep_clamp,
                          const std::function<int()>* before_wait) {
-    h->vg.target_ready = false;
+    h->target_ready = false;
     h->roi_on = false;
     const double res = h->prm.vgicp_resolution;
     if (!(res > 0)) return fail(h, "vgicp_resolution must be positive");
@@ -426,7 +426,7 @@ int vgicp_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t
         if (viol) return fail(h, std::to_string(viol) + " target points near this rank's tile have their 20 nearest neighbours reaching past the halo of " +
                                  std::to_string(h->halo) + " m: shard the map with a wider halo");
     }
-    h->vg.target_ready = true;
+    h->target_ready = true;
     return 0;
 }
 
@@ -458,7 +458,7 @@ VgicpArgs vgicp_args(const pcr_handle* h, const float* d_src, size_t n_src, size
 }
 
 int run_vgicp(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) {
-    if (!h->vg.target_ready) return fail(h, "no target prepared");
+    if (!h->target_ready) return fail(h, "no target prepared");
     if (n_src > kMaxPoints) return fail(h, "source cloud too large");
     if (ensure_out32(h)) return 1;
     const bool kept = fitness_scan_kept(h, d_src);
@@ -589,48 +589,65 @@ int vgicp_align_recut(pcr_handle* h, const float* d_src, size_t n_src, size_t st
     return rc;
 }
 
+// ---- vgicp's row of the method table (handle.h: MethodOps) ----
+int vgicp_scan2map(pcr_handle* h, const float* d_src, size_t n_src, const float* d_dst, size_t n_dst, size_t stride_floats, double pose[16], int* converged) {
+    // the reference keeps its target structures while the cloud POINTER is unchanged and goes stale
+    // when the cloud is edited in place; this entry point always rebuilds them
+    // (source side first: its ~15 launches run on the side stream while the host is still queueing the target's.  Measured the other
+    //  way round -- target builds queued first, source side enqueued while the host waits for them -- 1.17 instead of 0.93 ms: the
+    //  two covariance kernels then run side by side for their whole length and slow each other down)
+    // The target exists for this scan only, so only the part of it the scan can reach is prepared (RoiView): the covariances of a
+    // 1 M-point map were 0.4 of a 0.85 ms call, of which the scan looks up a tenth.  Should the optimiser carry the scan out of that
+    // region, the whole target is prepared and the call repeated from the same guess.
+    const bool use_roi = !sharded(h) && n_src > 0 && h->prm.host_optimiser == 0 && h->prm.vgicp_max_iters > 0 && h->prm.full_target == 0;
+    double pose_in[16];
+    memcpy(pose_in, pose, sizeof pose_in);
+    const RoiScan rs{d_src, n_src, stride_floats, pose_in};
+    // Order of the two sides.  The scan's own covariances used to be the longest thing in a call (344 us) and were queued first; since
+    // they are searched in two classes (cov_search.hip: ~190 us with the scan's index levels) the target is the long pole, and the
+    // dozen launches of the scan's side cost the host ~100 us during which the main stream sat empty.  Now the target's builds are
+    // queued first and the scan's side while the host waits for their headers (settle_cov_levels: before_wait).
+    // (Measured and not kept: the scan's side queued by a host thread of its own at the same time as the target's -- 0.481 / 0.495 against
+    //  0.496 / 0.494 ms: with both sides on the device from the start the call is bound by the device's work, not by the host's launches.)
+    bool src_queued = false;
+    const std::function<int()> queue_src = [&]() -> int { src_queued = true; return vgicp_source_enqueue(h, d_src, n_src, stride_floats, true); };
+    int prc = vgicp_source_mark(h);
+    if (!prc) prc = vgicp_prepare_target(h, d_dst, n_dst, stride_floats, use_roi ? &rs : nullptr, false, &queue_src);
+    if (!prc && !src_queued) prc = queue_src();
+    if (prc) (void)side_drain(h);
+    if (agree_prepared(h, prc)) {
+        (void)side_drain(h);
+        return 1;
+    }
+    if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_index, h->stream));
+    int rrc = vgicp_align_recut(h, d_src, n_src, stride_floats, pose, converged);
+    if (rrc == 2) {
+        memcpy(pose, pose_in, sizeof pose_in);
+        if (vgicp_prepare_target(h, d_dst, n_dst, stride_floats, nullptr)) return 1;
+        rrc = vgicp_align_recut(h, d_src, n_src, stride_floats, pose, converged);
+    }
+    if (rrc) return 1;
+    return end_timed_call(h);
+}
+int vgicp_kept_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats) { return agree_prepared(h, vgicp_prepare_target(h, d_dst, n_dst, stride_floats)); }
+int align_beside_scan_side(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged, AlignFn* run) {
+    // the scan's own side (two index levels, the 20-neighbour search, the covariances) queued on the side stream with its headers mirrored to the host, as
+    // pcr_scan2map queues it -- unless pcr_scan2map_submap has queued it already, ahead of the target's preparation.  Settled the checked way (a header
+    // read back after every level: two host round trips with an idle device in between, ~55 us of a 0.3 ms call against a kept sub-map) only if that fails.
+    if (!sharded(h) && n_src > 0 && !(h->side_pending && h->side_src == d_src && h->side_n == n_src && h->side_stride == stride_floats) &&
+        vgicp_source_enqueue(h, d_src, n_src, stride_floats)) return 1;
+    const int rc = run(h, d_src, n_src, stride_floats, pose, converged) ? 1 : 0;
+    (void)side_drain(h);      // (an alignment that failed before it collected the scan's side: nothing stays in flight behind the caller's back)
+    return rc;
+}
+int vgicp_align(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged) { return align_beside_scan_side(h, d_src, n_src, stride_floats, pose, converged, vgicp_align_recut); }
+// the resolution is the voxel; the regularisation shaped every covariance the handle holds, the voxel mode the voxel map
+bool vgicp_target_from_changed(const pcr_params& old_p, const pcr_params& new_p) { return new_p.vgicp_resolution != old_p.vgicp_resolution || new_p.vgicp_regularization != old_p.vgicp_regularization || new_p.vgicp_voxel_mode != old_p.vgicp_voxel_mode; }
+
 }  // namespace host
 }  // namespace pcr
 
 extern "C" {
-
-double pcr_fitness(pcr_handle* h) {
-    if (!h) return -1.0;
-    // PointCloudRegister::getFitnessScore() returns 0 unless overridden (PointCloudRegister.hpp:34);
-    // only VgicpRegister overrides it (VgicpRegister.cpp:42-45); a liorf handle answers with liorf_scan2map.cpp's own getFitnessScore (:22-54)
-    if (!scores_kept_scan(h)) return 0.0;
-    const bool liorf = h->method == kLiorf;      // the file's score: d2 <= 1.0f counted, -1 when none is
-    if (h->fit_pending) {
-        // mean squared distance of the aligned scan to its nearest target points, against the target the handle holds NOW (PCL does
-        // the same: input_ transformed by final_transformation_, searched in the current target tree)
-        h->fit_pending = false;
-        h->err.clear();
-        h->fitness = DBL_MAX;
-        if (liorf) h->fitness = -1.0;
-        if (scored_target_ready(h) && h->fit_n > 0) {
-            if (set_device(h) || ensure_out32(h)) return -1.0;
-            h->seq += 1.0;
-            // (a lattice that holds the scan's region only cannot answer a nearest-neighbour question; the grid its covariances were searched on holds every point)
-            const bool full_search_grid = h->cov_l1.valid && !h->cov_l1.filtered;
-            if (h->grid.filtered && !full_search_grid) {
-                h->err = "the voxel lattice of the last pcr_scan2map holds the scan's region only (pcr_stats.region_index) and no grid of every target point is at hand";
-                h->fitness = -1.0;
-                return -1.0;
-            }
-            const GridIndex& fit_grid = h->grid.filtered ? h->cov_l1 : h->grid;
-            if (fitness_launch(fit_grid, h->fit_src.as<float>(), h->fit_n, h->fit_stride, h->fit_pose, liorf ? 1.0 : DBL_MAX, h->vg_partials.as<double>(),
-                               h->out32.dev, h->stream, h->seq, nullptr) != hipSuccess) { h->err = "fitness_launch failed"; return -1.0; }
-            if (wait_result(h, &h->out32.host[31], h->seq)) return -1.0;
-            if (h->out32.host[2] > 0) {      // (fitness_kernel: points whose nearest target point may lie beyond a cut face of the index)
-                h->err = cut_fitness_message(h->out32.host[2]);
-                h->fitness = -1.0;
-                return -1.0;
-            }
-            h->fitness = h->out32.host[1] > 0 ? h->out32.host[0] / h->out32.host[1] : (liorf ? -1.0 : DBL_MAX);
-        }
-    }
-    return h->fitness;
-}
 
 int pcr_vgicp_covariances(pcr_handle* h, const void* pts, size_t n, size_t stride_bytes, int on_device, double* cov_out) {
     if (!h) return 1;
@@ -682,7 +699,7 @@ int pcr_vgicp_linearize(pcr_handle* h, const void* src, size_t n_src, size_t str
     h->err.clear();
     if (h->method != kVgicp) return fail(h, "pcr_vgicp_linearize needs a vgicp handle");
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
-    if (!h->vg.target_ready) return fail(h, "no target: call pcr_set_target first");
+    if (!h->target_ready) return fail(h, "no target: call pcr_set_target first");
     if (ensure_full_target(h)) return 1;
     const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
@@ -715,7 +732,7 @@ int pcr_vgicp_correspondences(pcr_handle* h, pcr_vgicp_corr* out, size_t capacit
     h->err.clear();
     if (h->method != kVgicp) return fail(h, "pcr_vgicp_correspondences needs a vgicp handle");
     if (set_device(h)) return 1;
-    if (!h->vg.lin_valid || !h->vg.target_ready || h->roi_on) return fail(h, "pcr_vgicp_correspondences: no linearisation to report; call pcr_vgicp_linearize first");
+    if (!h->vg.lin_valid || !h->target_ready || h->roi_on) return fail(h, "pcr_vgicp_correspondences: no linearisation to report; call pcr_vgicp_linearize first");
     const size_t n_src = h->vg.lin_n, n_entries = vgicp_table_entries(h->vg.lin_search);
     H_TRY(hipStreamSynchronize(h->stream));
     GridHeader hd;
@@ -754,7 +771,7 @@ int pcr_vgicp_voxels(pcr_handle* h, pcr_vgicp_voxel* out, size_t capacity, size_
     h->err.clear();
     if (h->method != kVgicp) return fail(h, "pcr_vgicp_voxels needs a vgicp handle");
     if (set_device(h)) return 1;
-    if (!h->vg.target_ready) return fail(h, "no target: call pcr_set_target first");
+    if (!h->target_ready) return fail(h, "no target: call pcr_set_target first");
     if (h->roi_on) return fail(h, "pcr_vgicp_voxels: pcr_scan2map prepared this target for that one scan's region only; call pcr_set_target first, for a target that is kept");
     H_TRY(hipStreamSynchronize(h->stream));
     GridHeader hd;
