@@ -27,6 +27,12 @@ for k in range(tl.shape[0]):
     t = tl[k]; ok = t[:, 6] > 0
     d = np.diff(t[ok][:, :7], axis=1).mean(axis=0)
     print(k, ' '.join(f'{names[i + 1]}:{d[i]:6.2f}' for i in range(6)), f'| mean stored {t[ok, 6].mean():6.2f} max stored {t[ok, 6].max():6.2f}')
+# the head of a launch ('prologue' above: entry -> prologue stamp), split by the stamps inside it (launch 0 has no previous launch to fold)
+print('head, mean block, us:  partial sums arrived | solved | pose ready | whole head')
+for k in range(1, tl.shape[0]):
+    t = tl[k]; ok = (t[:, 6] > 0) & (t[:, 7] > 0) & (t[:, 11] > 0)
+    if ok.any():
+        print(f'  launch {k}: ' + ' | '.join(f'{np.mean(t[ok, b] - t[ok, a]):5.2f}' for a, b in ((0, 7), (7, 11), (11, 1))) + f' | {np.mean(t[ok, 1] - t[ok, 0]):5.2f}')
 t = tl[0]; ok = t[:, 10] > 0
 if ok.any():
     for a, b, n in ((2, 8, 'ranges'), (8, 9, 'first group'), (9, 10, 'stream'), (10, 3, 'decode + exchange')):

@@ -901,11 +901,46 @@ __device__ __forceinline__ void lds_dma16(const float4* src, float4* lds_wave_ba
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(base) : "m0", "memory");
 }
 
+// What a launch needs before anything else: the kernels take these as their LEADING parameters, which gfx950 hands over in SGPRs at
+// wave launch (kernarg preload, csrc/Makefile) -- a by-value struct in first position is never preloaded, so every pointer in it costs
+// a scalar load of the kernarg segment before the first useful load can be issued.  LoamArgs carries the same values for the host and
+// the other kernels; the kernels below read them from here.
+struct LoamHead {
+    const double* partials;  // LoamArgs::partials
+    LoamState* state;        // LoamArgs::state
+    const double* reduced;   // LoamArgs::reduced
+    uint32_t n_partials;     // LoamArgs::n_partials
+};
+
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+
+// What the prologue folds, requested by the FIRST instructions of a kernel -- from the preloaded parameters alone, before anything that
+// waits for the rest of the kernarg segment: this thread's share of the previous launch's partial sums together with the state they
+// guard (one memory round trip instead of two).  Unconditional and branch-free: launch 0 and a finished loop simply do not use them.
+struct HeadLoads { int prev_done; double prev_pose_t, red; double pv[32]; };
+__device__ __forceinline__ void loam_head_issue(const LoamHead hd, int k, HeadLoads& L) {
+    const int t = threadIdx.x, comp = t & 31, slice = t >> 5;
+    const LoamState* prev = &hd.state[(k + 1) & 1];
+    // the state first: loads complete in issue order, so testing `done` then waits for nothing younger
+    L.prev_done = prev->done;
+    L.prev_pose_t = prev->pose[t & 15];
+    const double* const part0 = hd.partials + (size_t)((k + 1) & 1) * kMaxPartials * kAccum + comp;
+    const uint32_t last = hd.n_partials ? hd.n_partials - 1u : 0u;
+#pragma unroll
+    for (int u = 0; u < 32; ++u) {
+        const uint32_t b = (uint32_t)slice + 8u * u;
+        L.pv[u] = part0[(size_t)(b < last ? b : last) * kAccum];      // unconditional: rows past the end are masked in the fold
+    }
+    L.red = *(hd.reduced ? hd.reduced + comp : part0);       // sharded mode: sums already all-reduced
+}
+
 // pre_src / pre_dst: this lane's 192-byte neighbour-cache entry and the wave's slice of the LDS staging area.
-__device__ bool loam_prologue(const LoamArgs& a, int k, double* sh_sum /* 8*32 */, Prologue* sh, unsigned long long* tl = nullptr,
-                              const float4* pre_src = nullptr, float4* pre_dst = nullptr) {
-    const LoamState* prev = &a.state[(k + 1) & 1];
-    LoamState* cur = &a.state[k & 1];
+__device__ bool loam_prologue(const LoamHead hd, const HeadLoads& L, const LoamArgs& a, int k, double* sh_sum /* 8*32 */, Prologue* sh,
+                              unsigned long long* tl = nullptr, const float4* pre_src = nullptr, float4* pre_dst = nullptr) {
+    const LoamState* prev = &hd.state[(k + 1) & 1];
+    LoamState* cur = &hd.state[k & 1];
     const int t = threadIdx.x;
     if (k == 0) {
         if (t < 16) sh->pose[t] = a.init_pose[t];
@@ -917,30 +952,17 @@ __device__ bool loam_prologue(const LoamArgs& a, int k, double* sh_sum /* 8*32 *
         __syncthreads();
         return false;
     }
-    // Request this thread's share of the previous launch's partial sums together with the state it guards
-    // (one memory round trip instead of two); they are simply unused when the loop has already finished.
     const int comp = t & 31, slice = t >> 5;
-    const uint32_t n_rows = a.n_partials;      // rows of launch k - 1
-    // the state first: loads complete in issue order, so testing `done` then waits for nothing younger
-    const int prev_done = prev->done;
-    const double prev_pose_t = t < 16 ? prev->pose[t] : 0.0;
-    double pv[32];
-    {
-        const double* part = a.partials + (size_t)((k + 1) & 1) * kMaxPartials * kAccum + comp;
-        const uint32_t last = n_rows ? n_rows - 1u : 0u;
-#pragma unroll
-        for (int u = 0; u < 32; ++u) {
-            const uint32_t b = (uint32_t)slice + 8u * u;
-            pv[u] = part[(size_t)(b < last ? b : last) * kAccum];      // unconditional: rows past the end are masked in the fold
-        }
-    }
+    const uint32_t n_rows = hd.n_partials;      // rows of launch k - 1
+    const int prev_done = L.prev_done;
+    const double prev_pose_t = L.prev_pose_t;   // (lanes 0..15)
     // fixed-order reduction of the partial sums of launch k-1.  Straight-line code (selects, no branches): every
     // conditional region here made the compiler either sink the loads below it or wait for all of them at its join.
-    const double* const part0 = a.partials + (size_t)((k + 1) & 1) * kMaxPartials * kAccum + comp;
-    const double red = *(a.reduced ? a.reduced + comp : part0);       // sharded mode: sums already all-reduced
+    const double* const part0 = hd.partials + (size_t)((k + 1) & 1) * kMaxPartials * kAccum + comp;
+    const double red = L.red;
     double acc = 0.0;
 #pragma unroll
-    for (int u = 0; u < 32; ++u) acc += ((uint32_t)slice + 8u * u < n_rows) ? pv[u] : 0.0;
+    for (int u = 0; u < 32; ++u) acc += ((uint32_t)slice + 8u * u < n_rows) ? L.pv[u] : 0.0;
     // more than 256 blocks (scans beyond 65 536 points): sixteen loads in flight per step, added in the same order as a plain
     // loop (one load per step cost 11 us of every launch on a 131 072-point scan)
     for (uint32_t b0 = (uint32_t)slice + 256u; b0 < n_rows; b0 += 128u) {
@@ -951,7 +973,7 @@ __device__ bool loam_prologue(const LoamArgs& a, int k, double* sh_sum /* 8*32 *
 #pragma unroll
         for (int u = 0; u < 16; ++u) acc += (b0 + 8u * u < n_rows) ? w[u] : 0.0;
     }
-    if (a.reduced) acc = slice == 0 ? red : 0.0;
+    if (hd.reduced) acc = slice == 0 ? red : 0.0;
     sh_sum[slice * 32 + comp] = acc;
     if (t < 16) sh->pose[t] = prev_pose_t;
     __syncthreads();
@@ -960,7 +982,7 @@ __device__ bool loam_prologue(const LoamArgs& a, int k, double* sh_sum /* 8*32 *
     // equations are solved.  Issued from inline asm on purpose: the compiler's wait-count bookkeeping treats an LDS-DMA
     // in flight as "wait for everything" at every barrier and at every use of any other load; the consumer waits by hand.
     if (pre_dst) {
-        const float4* src = pre_src ? pre_src : reinterpret_cast<const float4*>(a.partials) + (size_t)t * kEntryVec;   // harmless address
+        const float4* src = pre_src ? pre_src : reinterpret_cast<const float4*>(hd.partials) + (size_t)t * kEntryVec;   // harmless address
 #pragma unroll
         for (int f = 0; f < kEntryVec; ++f) lds_dma16(src + f, pre_dst + f * 256);
     }
@@ -985,11 +1007,13 @@ __device__ bool loam_prologue(const LoamArgs& a, int k, double* sh_sum /* 8*32 *
     // instructions on a single lane while 255 threads of every block wait.  When the geometry does NOT constrain all six
     // degrees of freedom (a single plane, a corridor: a pivot collapses) the answer depends on how the factorisation
     // treats the null space, so that case is redone exactly as Eigen does it: pivoted LDLT, zero pivots dropped. ----
-    double* const sh_m = sh_sum + 64;      // 42 entries of the augmented matrix
     double* const sh_x = sh_sum + 112;     // 6 entries of the solution
+    // Eight lanes per row (i = t >> 3, j = t & 7, column 7 idle), the matrix in registers: the pivot is read off its lane (the lane
+    // number is a constant of the unrolled step), so its reciprocal -- the long part of a step -- starts at once, while the row and
+    // column factors come by lane permute.  No LDS store, no read-back.
     if (t < 64) {
-        const int i = t / 7, j = t - 7 * i;
-        const bool in = t < 42;
+        const int i = t >> 3, j = t & 7;
+        const bool in = i < 6 && j < 7;
         double v = 0.0;
         if (in) {
             const int r = i < j ? i : j, c = i < j ? j : i;
@@ -1001,10 +1025,8 @@ __device__ bool loam_prologue(const LoamArgs& a, int k, double* sh_sum /* 8*32 *
         bool weak = false;
 #pragma unroll
         for (int kk = 0; kk < 6; ++kk) {
-            if (in) sh_m[t] = v;
-            __builtin_amdgcn_wave_barrier();
-            const double pk = sh_m[kk * 7 + kk], aik = in ? sh_m[i * 7 + kk] : 0.0, akj = in ? sh_m[kk * 7 + j] : 0.0;
-            __builtin_amdgcn_wave_barrier();
+            const double pk = readlane_f64(v, kk * 9);
+            const double aik = __shfl(v, (t & ~7) | kk, 64), akj = __shfl(v, kk * 8 + j, 64);
             weak = weak || !(fabs(pk) > 1e-6 * maxd);        // also catches NaN
             const double rp = 1.0 / pk;                      // one division per elimination step instead of two
             if (in) v = (i == kk) ? akj * rp : v - (aik * rp) * akj;
@@ -1014,56 +1036,81 @@ __device__ bool loam_prologue(const LoamArgs& a, int k, double* sh_sum /* 8*32 *
     }
     __syncthreads();
     if (tl) tl[11] = wall_clock64();      // normal equations solved
-    if (t == 0) {
-        double JtJ[36], rhs[6], x[6];
-        int q = 0;
-        for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { JtJ[r * 6 + c] = JtJ[c * 6 + r] = sh_sum[q++]; }
-        for (int r = 0; r < 6; ++r) { rhs[r] = -sh_sum[21 + r]; x[r] = sh_x[r]; }
-        if (sh_x[6] != 0.0) ldlt6_solve(JtJ, rhs, x);         // rank-deficient or ill-conditioned: Eigen's LDLT, step for step
-        const double n = sh_sum[27];
-        int done = 0, conv = 0, fail = 0;
-        double pose[16];
-        for (int i = 0; i < 16; ++i) pose[i] = sh->pose[i];      // previous pose, staged below
-        if (a.reduced && sh_sum[kSlotRankFail] != 0.0) { done = 1; fail = 2; for (int r = 0; r < 6; ++r) x[r] = 0.0; }   // a rank has no index: every rank stops here
-        else if (sh_sum[kSlotEscapes] != 0.0) { done = 1; fail = 3; for (int r = 0; r < 6; ++r) x[r] = 0.0; }        // the clamped index was too small
-        else if (n < 6.0) { done = 1; fail = 1; for (int r = 0; r < 6; ++r) x[r] = 0.0; }   // LoamRegister.cpp:173-176
-        else {
-            const double np = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-            const double nr = sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
-            if (a.c.early_exit && np <= a.c.pos_conv && nr <= a.c.rot_conv) { done = 1; conv = 1; }   // :202-206
-            else {
-                double E[16], out[16];
-                se3_exp(x, E);                                     // :213-216
-                for (int c = 0; c < 4; ++c)
-                    for (int r = 0; r < 4; ++r) {
-                        double s = 0;
-                        for (int kk = 0; kk < 4; ++kk) s += E[kk * 4 + r] * pose[c * 4 + kk];
-                        out[c * 4 + r] = s;
-                    }
-                for (int i = 0; i < 16; ++i) pose[i] = out[i];
-            }
-        }
-        if (k >= a.c.iters) done = 1;
-        for (int i = 0; i < 16; ++i) sh->pose[i] = pose[i];
-        sh->done = done;
-        // A cache entry proves its five neighbours while the query has moved by less than the gap between the 5th and the 9th neighbour
-        // distance -- centimetres on a 0.5 m map.  A step that moves a point 10 m from the sensor by more than kBigStep makes four
-        // entries in five fail (launch 1 after a 0.3 m / 2 degree guess: 52 682 of 65 536): then nobody reads or tests an entry and
-        // every lane searches its own query, without the exchange.  A performance decision only -- a search is exact whatever the cache
-        // would have said.  Measured (A/B on one box, profiles/r03_notes.md): launch 1 30.5 -> 28.6 us, and launch 2 searches 7 140
-        // instead of 11 682 queries because every entry is now anchored at the pose after the big step; 3 803 -> 3 894 scans/s.
-        sh->big_step = (!done && sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]) + 10.0 * sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]) > kBigStep) ? 1 : 0;
-        if (blockIdx.x == 0) {
-            for (int i = 0; i < 16; ++i) cur->pose[i] = pose[i];
-            cur->done = done; cur->converged = conv; cur->fail = fail; cur->iters_run = k;
-            // (the host may be queueing launches only a few ahead of this word: run_loam)
-            __hip_atomic_store(&a.result->progress, (k << 1) | (done ? 1 : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if (a.trace) {
+    // Wave 0, every lane with the same values and hence the same decisions: nothing has to be handed from one lane to the others
+    // before lanes 0..15 each take one entry of exp(x) * pose.
+    if (t < 64) {
+        double x[6];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) x[r] = sh_x[r];
+        const bool weak = sh_x[6] != 0.0;
+        const int oc = (t >> 2) & 3, orow = t & 3;          // lane t < 16 owns pose entry t = oc * 4 + orow (column-major)
+        double pcol[4];                                      // column oc of the previous pose (staged above)
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) pcol[kk] = sh->pose[oc * 4 + kk];
+        const bool writer = blockIdx.x == 0 && t == 0;
+        if (weak || a.trace) {      // the full matrix is needed by the fallback and by the trace only
+            double JtJ[36], rhs[6];
+            int q = 0;
+            for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { JtJ[r * 6 + c] = JtJ[c * 6 + r] = sh_sum[q++]; }
+            for (int r = 0; r < 6; ++r) rhs[r] = -sh_sum[21 + r];
+            if (weak) ldlt6_solve(JtJ, rhs, x);               // rank-deficient or ill-conditioned: Eigen's LDLT, step for step
+            if (writer && a.trace) {
                 LoamTrace* tr = &a.trace[k - 1];
                 for (int i = 0; i < 36; ++i) tr->JtJ[i] = JtJ[i];
-                for (int i = 0; i < 6; ++i) { tr->JtE[i] = -rhs[i]; tr->x[i] = x[i]; }
-                tr->n = (int64_t)n;
+                for (int i = 0; i < 6; ++i) tr->JtE[i] = -rhs[i];
+                tr->n = (int64_t)sh_sum[27];
                 tr->cache_hits = (int64_t)sh_sum[28]; tr->searches = (int64_t)sh_sum[29];
+            }
+        }
+        const double n = sh_sum[27];
+        int done = 0, conv = 0, fail = 0, big = 0;
+        bool step = false;
+        double np = 0.0, nr = 0.0;
+        if (hd.reduced && sh_sum[kSlotRankFail] != 0.0) { done = 1; fail = 2; }   // a rank has no index: every rank stops here
+        else if (sh_sum[kSlotEscapes] != 0.0) { done = 1; fail = 3; }              // the clamped index was too small
+        else if (n < 6.0) { done = 1; fail = 1; }                                  // LoamRegister.cpp:173-176
+        else {
+            np = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+            nr = sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
+            if (a.c.early_exit && np <= a.c.pos_conv && nr <= a.c.rot_conv) { done = 1; conv = 1; }   // :202-206
+            else step = true;
+        }
+        if (fail) { for (int r = 0; r < 6; ++r) x[r] = 0.0; }
+        if (k >= a.c.iters) done = 1;
+        double mine = prev_pose_t;      // (lanes 0..15) the pose stays when no step is taken
+        if (step) {
+            double E[16];
+            se3_exp(x, E);                                     // :213-216
+            // Row orow of E by way of LDS (a register array indexed by the lane would live in scratch memory).  Same wave: its LDS
+            // operations complete in order.
+            double* const sh_E = sh_sum + 128;
+            if (t == 0) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) sh_E[i] = E[i];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            double s = 0;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) s += sh_E[kk * 4 + orow] * pcol[kk];      // entry (orow, oc) of E * pose, in the order of a plain triple loop
+            mine = s;
+            // A cache entry proves its five neighbours while the query has moved by less than the gap between the 5th and the 9th neighbour
+            // distance -- centimetres on a 0.5 m map.  A step that moves a point 10 m from the sensor by more than kBigStep makes four
+            // entries in five fail (launch 1 after a 0.3 m / 2 degree guess: 52 682 of 65 536): then nobody reads or tests an entry and
+            // every lane searches its own query, without the exchange.  A performance decision only -- a search is exact whatever the cache
+            // would have said.  Measured (A/B on one box, profiles/r03_notes.md): launch 1 30.5 -> 28.6 us, and launch 2 searches 7 140
+            // instead of 11 682 queries because every entry is now anchored at the pose after the big step; 3 803 -> 3 894 scans/s.
+            big = (!done && np + 10.0 * nr > kBigStep) ? 1 : 0;
+        }
+        if (step && t < 16) sh->pose[t] = mine;               // (every lane's read of the old pose is in pcol by now: same wave, LDS in order)
+        if (t == 0) { sh->done = done; sh->big_step = big; }
+        if (blockIdx.x == 0) {
+            if (t < 16) cur->pose[t] = mine;
+            if (t == 0) {
+                cur->done = done; cur->converged = conv; cur->fail = fail; cur->iters_run = k;
+                // (the host may be queueing launches only a few ahead of this word: run_loam)
+                __hip_atomic_store(&a.result->progress, (k << 1) | (done ? 1 : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if (a.trace) { for (int i = 0; i < 6; ++i) a.trace[k - 1].x[i] = x[i]; }
             }
         }
     }
@@ -1078,7 +1125,13 @@ __device__ bool loam_prologue(const LoamArgs& a, int k, double* sh_sum /* 8*32 *
 // that 65 536 queries give anyway); <4, 2> fits two waves per SIMD so that the blocks of ANOTHER handle's launch can share the
 // CUs: a little slower alone, more scans/s with several handles in flight (pcr_params.loam_coresident = 1).
 template <int kGroup, int kWavesPerSimd>
-__global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const LoamArgs a, const int k) {
+__global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(double* const partials, LoamState* const state, const double* const reduced,
+                                                                          const uint32_t n_partials, const int k, NnCacheEntry* const nn_cache,
+                                                                          const float* const src, const LoamArgs a) {
+    const unsigned long long t_entry = wall_clock64();
+    const LoamHead hd = {partials, state, reduced, n_partials};
+    HeadLoads head;
+    loam_head_issue(hd, k, head);
     __shared__ double sh_sum[8 * 32];
     __shared__ Prologue sh_pro;
     // The staging area of the prefetched cache entries (48 KB, dead once every lane has read its entry) shares its
@@ -1092,29 +1145,39 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const 
     double* const sh_rows = sh_ex.u.rows;
     const int tid = threadIdx.x;
     unsigned long long* const tl = (a.timeline && tid == 0) ? a.timeline + ((size_t)k * kMaxPartials + blockIdx.x) * kTimelineSlots : nullptr;
-    if (tl) tl[0] = wall_clock64();
+    if (tl) tl[0] = t_entry;
     // XCD-aware mapping: consecutive logical blocks (adjacent lidar rings) share an XCD's L2
     uint32_t blk = blockIdx.x;
     if ((gridDim.x & 7u) == 0) blk = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    // (the partial sums the prologue folds are already on their way: loam_head_issue above)
     // Everything the first round needs from memory is requested before/inside the prologue, so that the scan point and
     // the 128-byte neighbour-cache entry arrive while the previous iteration's normal equations are being solved.
     // The entry goes straight to LDS ([field][thread], 48 KB): held in registers it was spilled to AGPRs, which made
     // the wave wait for it before the prologue had even started.
     float4* const sh_pre = reinterpret_cast<float4*>(sh_ov);
-    const GridHeader h = *a.grid.hdr;      // uniform: scalar loads, in flight during the prologue
+    // (read through the constant address space: nothing in this launch writes the header, and only so do the loads stay scalar --
+    //  as ordinary global loads they came back through vector registers, with a wait in front of the partial sums)
+    GridHeader h;                          // uniform: scalar loads, in flight during the prologue
+    {
+        static_assert(sizeof(GridHeader) % 4 == 0, "header copied by words");
+        const __attribute__((address_space(4))) uint32_t* const hw = (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)a.grid.hdr;
+        uint32_t* const w = reinterpret_cast<uint32_t*>(&h);
+#pragma unroll
+        for (size_t i = 0; i < sizeof(GridHeader) / 4; ++i) w[i] = hw[i];
+    }
     float pre_x = 0.f, pre_y = 0.f, pre_z = 0.f;
-    const bool use_cache = k > 0 && a.nn_cache != nullptr;
+    const bool use_cache = k > 0 && nn_cache != nullptr;
     const float4* pre_src = nullptr;
     const uint32_t qpb = 256u;      // queries per block
     {
         const uint32_t q = blk * qpb + (uint32_t)tid;
         // unconditional load of a clamped index: a conditional one makes the wave wait for it at the join
-        const float* sp = a.n_src ? a.src + (size_t)(q < a.n_src ? q : a.n_src - 1u) * a.src_stride
-                                  : reinterpret_cast<const float*>(a.partials);      // empty scan: any readable address
+        const float* sp = a.n_src ? src + (size_t)(q < a.n_src ? q : a.n_src - 1u) * a.src_stride
+                                  : reinterpret_cast<const float*>(partials);      // empty scan: any readable address
         pre_x = sp[0]; pre_y = sp[1]; pre_z = sp[2];
-        pre_src = (use_cache && q < a.n_src) ? reinterpret_cast<const float4*>(a.nn_cache + q) : nullptr;
+        pre_src = (use_cache && q < a.n_src) ? reinterpret_cast<const float4*>(nn_cache + q) : nullptr;
     }
-    if (loam_prologue(a, k, sh_sum, &sh_pro, tl, pre_src, use_cache ? sh_pre + (tid & ~63) : nullptr)) {
+    if (loam_prologue(hd, head, a, k, sh_sum, &sh_pro, tl, pre_src, use_cache ? sh_pre + (tid & ~63) : nullptr)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // never leave with an LDS-DMA in flight
         return;
     }
@@ -1164,9 +1227,9 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const 
         } else {                      // later rounds of a grid-stride launch
             sx = sy = sz = 0.f;
             if (valid) {
-                const float* sp = a.src + (size_t)q * a.src_stride;
+                const float* sp = src + (size_t)q * a.src_stride;
                 sx = sp[0]; sy = sp[1]; sz = sp[2];
-                if (use_cache) ce.e = a.nn_cache[q];
+                if (use_cache) ce.e = nn_cache[q];
             }
         }
         const int st = loam_point<kGroup>(a, h, pose, sx, sy, sz, valid, ce.e, use_cache && valid && !all_search, sh_knn, sh_ex, row, nn, q, &how, &esc, ew,
@@ -1192,7 +1255,7 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const 
         __syncthreads();
         // The cache entries go out last, behind everything the block waits for; the rows and the search scratch are dead, so
         // their LDS stages the transposition.  (wave-uniform test: nothing is staged or stored in a wave of unchanged entries)
-        if (__any(ew.what != 0u)) entry_store_wave(a.nn_cache + (q - (uint32_t)(tid & 63)), ew, reinterpret_cast<float4*>(sh_ov) + (tid >> 6) * (64 * kEntryVec));
+        if (__any(ew.what != 0u)) entry_store_wave(nn_cache + (q - (uint32_t)(tid & 63)), ew, reinterpret_cast<float4*>(sh_ov) + (tid >> 6) * (64 * kEntryVec));
         if (base + gridDim.x * qpb < a.n_src) __syncthreads();      // (grid-stride launch: the next round reuses that LDS)
     }
     if (tl) tl[5] = wall_clock64();
@@ -1208,21 +1271,25 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(const 
         if (tid == 28) v = (double)(sh_cnt[0] + sh_cnt[2] + sh_cnt[4] + sh_cnt[6]);
         if (tid == 29) v = (double)(sh_cnt[1] + sh_cnt[3] + sh_cnt[5] + sh_cnt[7]);
         if (tid == kSlotEscapes) v = (double)(sh_cnt[8] + sh_cnt[9] + sh_cnt[10] + sh_cnt[11]);
-        a.partials[((size_t)(k & 1) * kMaxPartials + blockIdx.x) * kAccum + tid] = v;
+        partials[((size_t)(k & 1) * kMaxPartials + blockIdx.x) * kAccum + tid] = v;
     }
     if (tl) tl[6] = wall_clock64();
 }
 
 // last launch: prologue only, then T2SE3 and the output pose (LoamRegister.cpp:220)
-__global__ __launch_bounds__(256) void loam_finalize_kernel(const LoamArgs a, const int k) {
+__global__ __launch_bounds__(256) void loam_finalize_kernel(const double* const partials, LoamState* const state, const double* const reduced,
+                                                            const uint32_t n_partials, const int k, const LoamArgs a) {
     __shared__ double sh_sum[8 * 32];
     __shared__ Prologue sh_pro;
-    loam_prologue(a, k, sh_sum, &sh_pro);
+    const LoamHead hd = {partials, state, reduced, n_partials};
+    HeadLoads head;
+    loam_head_issue(hd, k, head);
+    loam_prologue(hd, head, a, k, sh_sum, &sh_pro);
     if (threadIdx.x == 0) {
         double T[16];
         for (int i = 0; i < 16; ++i) T[i] = sh_pro.pose[i];
         t2se3(T);
-        const LoamState* cur = &a.state[k & 1];   // written by this thread in the prologue
+        const LoamState* cur = &state[k & 1];   // written by this thread in the prologue
         LoamResult* r = a.result;
         for (int i = 0; i < 16; ++i) r->pose[i] = T[i];
         r->converged = cur->converged; r->iters_run = cur->iters_run; r->fail = cur->fail;
@@ -1313,16 +1380,16 @@ uint32_t loam_grid_blocks(uint32_t n_src) {
 // dispatch latency (~2 us here).
 hipError_t loam_launch_iteration(const LoamArgs& a, int k, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     if (start && stop) {
-        if (a.coresident) hipExtLaunchKernelGGL((loam_iterate_kernel<4, 2>), dim3(a.n_partials), dim3(256), 0, s, start, stop, 0, a, k);
-        else hipExtLaunchKernelGGL((loam_iterate_kernel<8, 1>), dim3(a.n_partials), dim3(256), 0, s, start, stop, 0, a, k);
+        if (a.coresident) hipExtLaunchKernelGGL((loam_iterate_kernel<4, 2>), dim3(a.n_partials), dim3(256), 0, s, start, stop, 0, a.partials, a.state, a.reduced, a.n_partials, k, a.nn_cache, a.src, a);
+        else hipExtLaunchKernelGGL((loam_iterate_kernel<8, 1>), dim3(a.n_partials), dim3(256), 0, s, start, stop, 0, a.partials, a.state, a.reduced, a.n_partials, k, a.nn_cache, a.src, a);
         return hipGetLastError();
     }
-    if (a.coresident) hipLaunchKernelGGL((loam_iterate_kernel<4, 2>), dim3(a.n_partials), dim3(256), 0, s, a, k);
-    else hipLaunchKernelGGL((loam_iterate_kernel<8, 1>), dim3(a.n_partials), dim3(256), 0, s, a, k);
+    if (a.coresident) hipLaunchKernelGGL((loam_iterate_kernel<4, 2>), dim3(a.n_partials), dim3(256), 0, s, a.partials, a.state, a.reduced, a.n_partials, k, a.nn_cache, a.src, a);
+    else hipLaunchKernelGGL((loam_iterate_kernel<8, 1>), dim3(a.n_partials), dim3(256), 0, s, a.partials, a.state, a.reduced, a.n_partials, k, a.nn_cache, a.src, a);
     return hipGetLastError();
 }
 hipError_t loam_launch_finalize(const LoamArgs& a, int k, hipStream_t s) {
-    hipLaunchKernelGGL(loam_finalize_kernel, dim3(1), dim3(256), 0, s, a, k);
+    hipLaunchKernelGGL(loam_finalize_kernel, dim3(1), dim3(256), 0, s, a.partials, a.state, a.reduced, a.n_partials, k, a);
     return hipGetLastError();
 }
 hipError_t loam_launch_reduce(const LoamArgs& a, int k, double* d_out, hipStream_t s) {
