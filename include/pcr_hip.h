@@ -542,8 +542,9 @@ int pcr_vgicp_opt_result(const pcr_vgicp_opt* o, double pose16[16], int* converg
 
 /* Profiling aid: with pcr_params.record_timeline = 1 thread 0 of every linearisation block records seven
  * s_memrealtime stamps (100 MHz ticks): entry, prologue done, misses posted, search done, plane+cache done,
- * accumulation done, partial sums stored (+ the fold inside the prologue and three stamps of the dense search).  out receives
- * [launches][blocks][16] u64; call with out = NULL to size it. */
+ * accumulation done, partial sums stored (+ the fold inside the prologue, three stamps of the dense search and the stamps inside
+ * the refine, post and accumulate stages: LoamRegister.timeline in pcr.py lists the columns).  out receives
+ * [launches][blocks][24] u64; call with out = NULL to size it. */
 int pcr_get_timeline(pcr_handle* h, uint64_t* out, size_t capacity, int* launches, int* blocks);
 
 /* NDT introspection: one computeDerivatives pass (ndt_omp_impl.hpp:180-285) at the parameter vector

@@ -44,6 +44,14 @@ for k in range(min(4, tl.shape[0])):
     t = tl[k]; ok = (t[:, 6] > 0) & (t[:, 12] > 0)
     if ok.any():
         print(f'  launch {k}: ' + ' | '.join(f'{np.mean(t[ok, b] - t[ok, a]):5.2f}' for _, a, b in sub) + f' | {np.mean(t[ok, 4] - t[ok, 3]):5.2f}')
+# the body around the search: 'posted' (prologue -> posted) and 'accum' + 'stored' (plane -> accum -> stored), split by the stamps inside them
+sub = (('pose in registers', 1, 16), ('hit test', 16, 17), ('posting', 17, 2), ('rows to LDS', 4, 18), ('chunk sums', 18, 19), ('entry stores', 19, 5),
+       ('block row', 5, 6))
+print('post / accumulate / store stages, mean block, us:  ' + ' | '.join(n for n, _, _ in sub) + ' | mean block end')
+for k in range(tl.shape[0]):
+    t = tl[k]; ok = (t[:, 6] > 0) & (t[:, 18] > 0)
+    if ok.any():
+        print(f'  launch {k}: ' + ' | '.join(f'{np.mean(t[ok, b] - t[ok, a]):5.2f}' for _, a, b in sub) + f' | {t[ok, 6].mean():6.2f}')
 import hashlib
 print('pose sha1', hashlib.sha1(np.ascontiguousarray(pose).tobytes()).hexdigest())
 reg.set_profile(2)

@@ -555,11 +555,12 @@ __device__ __forceinline__ bool knn8_wave(const GridHeader& h, const float4* __r
 static constexpr int kRowStride = 258;   // doubles per component row in LDS (256 + pad: conflict-free reads)
 static constexpr int kSparseMisses = 8;  // up to this many posted queries per block go the wave-cooperative way
 struct MissExchange {
-    uint32_t count, fallback;
-    uint32_t list[256];                  // owner thread of the m-th posted query (order immaterial)
+    uint32_t wcount[4];                  // queries posted by each of the block's four waves
+    uint32_t fallback, pad_[3];          // (32 bytes in front of the arrays: the rows below start on a 16-byte boundary)
+    uint32_t list[256];                  // [wave][i]: owner thread of the i-th query a wave posted, in lane order (posted_owner)
     float qx[256], qy[256], qz[256];     // query (float-valued)
     double seed[256];                    // upper bound of the kNb-th squared distance (max_sq when nothing is known)
-    union {
+    union alignas(16) {
         struct {
             uint32_t pos[kNb][256];      // by owner: positions of the listed candidates in the cell-sorted array
             double bound[256];           // by owner: squared-distance bound of every target point not listed
@@ -570,6 +571,17 @@ struct MissExchange {
         double rows[8 * kRowStride];     // later: [component][point] rows of the normal equations
     } u;
 };
+static_assert(offsetof(MissExchange, u) % 16 == 0 && (kRowStride * sizeof(double)) % 16 == 0 && sizeof(KnnRuns) % 16 == 0,
+              "the chunk sums read two doubles of a row per instruction");
+
+// Owner of the m-th posted query (m < the sum of c[]).  Every wave compacts its own misses by ballot into its quarter of the list, so posting
+// takes no atomic, no cleared counter and a single barrier; the m-th query of the block is found from the four counts.  c: ex.wcount.
+__device__ __forceinline__ uint32_t posted_owner(const MissExchange& ex, const uint32_t c[4], uint32_t m) {
+    const uint32_t p1 = c[0], p2 = p1 + c[1], p3 = p2 + c[2];
+    const uint32_t w = (m >= p1 ? 1u : 0u) + (m >= p2 ? 1u : 0u) + (m >= p3 ? 1u : 0u);
+    const uint32_t first = w == 0u ? 0u : (w == 1u ? p1 : (w == 2u ? p2 : p3));
+    return ex.list[w * 64u + (m - first)];
+}
 
 // What one scan point leaves in its cache entry for the next launch.  loam_point only fills this in (registers); the caller
 // stores it once the block's accumulate phase is over (entry_store_wave).
@@ -582,6 +594,34 @@ struct EntryWrite {
     uint32_t flags;
 };
 
+// the twelve 16-byte fields of an entry as its owner would write them, and which of them it rewrites
+__device__ __forceinline__ uint32_t entry_fields(const EntryWrite& w, float4 v[kEntryVec]) {
+#pragma unroll
+    for (int j = 0; j < kNb; ++j) v[j] = make_float4(w.s.x[j], w.s.y[j], w.s.z[j], __uint_as_float(w.s.idx[j]));
+    // the anchor of the entry: this search's query position and what it proved about everything it did not list
+    v[kNb] = make_float4(w.q[0], w.q[1], w.q[2], __double2float_rd(sqrt(w.bound_sq) * (1.0 - 1e-15)));
+    union { struct { double x[3]; uint32_t pidx[5]; uint32_t flags; } t; float4 v[3]; } tail;
+    tail.t.x[0] = w.x[0]; tail.t.x[1] = w.x[1]; tail.t.x[2] = w.x[2];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) tail.t.pidx[j] = w.s.idx[j];
+    tail.t.flags = w.flags;
+#pragma unroll
+    for (int f = 0; f < 3; ++f) v[kNb + 1 + f] = tail.v[f];
+    return ((w.what & 1u) ? 0x0ffu : 0u) | ((w.what & 2u) ? 0x100u : 0u) | ((w.what & 4u) ? 0xe00u : 0u);
+}
+
+// A wave in which only a few lanes rewrite anything -- the late launches, where a handful of planes are refitted -- does not pay for staging 64
+// entries: each writer stores its own fields, under the same mask.
+static constexpr int kFewWriters = 8;      // up to this many writing lanes in a wave go the per-lane way
+__device__ __forceinline__ void entry_store_lane(NnCacheEntry* __restrict__ mine_e, const EntryWrite& w) {
+    if (w.what & 8u) mine_e->flags = 0;
+    float4 v[kEntryVec];
+    const uint32_t fields = entry_fields(w, v);
+    float4* const dst = reinterpret_cast<float4*>(mine_e);
+#pragma unroll
+    for (int f = 0; f < kEntryVec; ++f) if ((fields >> f) & 1u) dst[f] = v[f];
+}
+
 // The entries of a wave's 64 consecutive scan points are 12 KB of contiguous memory.  Written by their owners they are twelve
 // 16-byte stores per lane at a 192-byte lane stride -- 64 cache lines per instruction, 2.7 us of every launch that searches
 // (profiles/loam_refine_notes.md).  Here the wave transposes them through its own 12 KB slice of LDS (the block's search and
@@ -592,18 +632,10 @@ __device__ __forceinline__ void entry_store_wave(NnCacheEntry* __restrict__ e0, 
     const int lane = threadIdx.x & 63;
     if (w.what & 8u) e0[lane].flags = 0;
     float4* const mine = stage + lane * kEntryVec;
+    float4 mv[kEntryVec];
+    const uint32_t fields = entry_fields(w, mv);
 #pragma unroll
-    for (int j = 0; j < kNb; ++j) mine[j] = make_float4(w.s.x[j], w.s.y[j], w.s.z[j], __uint_as_float(w.s.idx[j]));
-    // the anchor of the entry: this search's query position and what it proved about everything it did not list
-    mine[kNb] = make_float4(w.q[0], w.q[1], w.q[2], __double2float_rd(sqrt(w.bound_sq) * (1.0 - 1e-15)));
-    union { struct { double x[3]; uint32_t pidx[5]; uint32_t flags; } t; float4 v[3]; } tail;
-    tail.t.x[0] = w.x[0]; tail.t.x[1] = w.x[1]; tail.t.x[2] = w.x[2];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) tail.t.pidx[j] = w.s.idx[j];
-    tail.t.flags = w.flags;
-#pragma unroll
-    for (int f = 0; f < 3; ++f) mine[kNb + 1 + f] = tail.v[f];
-    const uint32_t fields = ((w.what & 1u) ? 0x0ffu : 0u) | ((w.what & 2u) ? 0x100u : 0u) | ((w.what & 4u) ? 0xe00u : 0u);
+    for (int f = 0; f < kEntryVec; ++f) mine[f] = mv[f];
     // (same wave: its LDS operations complete in order, so the slice is visible to the reads below)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     float4* const dst = reinterpret_cast<float4*>(e0);
@@ -654,7 +686,9 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
     bool moved = false;
     const bool have_seed = have_entry && active && (ce_in.flags & 1u);
     bool hit = false;
+    if (tl) { if (px + py + pz == 1.2345e38f) moved = true; tl[16] = wall_clock64(); }   // pose in registers, query transformed
     if (have_seed) hit = knn_from_cache(ce_in, qx, qy, qz, s, &moved);
+    if (tl) { if (hit && s.d[4] == 1.2345e300) moved = true; tl[17] = wall_clock64(); }   // hit test done
     const int tid = threadIdx.x;
     // ---- post the queries that need a search ----
     const bool miss = active && !hit;
@@ -665,12 +699,13 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
 #pragma unroll
     for (int r = 0; r < 9; ++r) { own_ranges.ra[r] = 0u; own_ranges.rb[r] = 0u; }
     if (__any(miss)) knn_ranges_issue(h, a.grid.cell_start, px, py, pz, miss, own_ranges);      // (wave-uniform: nothing is loaded in an all-hit wave)
+    uint32_t posted[4] = {0u, 0u, 0u, 0u};      // queries posted by each wave (block-uniform)
     if (!all_search) {      // (block-uniform)
-    if (tid == 0) ex.count = 0;
-    __syncthreads();
+    // every wave compacts its own misses, in lane order, into its quarter of the list: no atomic, no counter to clear, one barrier
+    const unsigned long long mb = __ballot(miss);
+    if ((tid & 63) == 0) ex.wcount[tid >> 6] = (uint32_t)__popcll(mb);
     if (miss) {
-        const uint32_t m = atomicAdd(&ex.count, 1u);
-        ex.list[m] = (uint32_t)tid;
+        ex.list[(uint32_t)(tid & ~63) + __builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, 0u))] = (uint32_t)tid;
         ex.qx[tid] = px; ex.qy[tid] = py; ex.qz[tid] = pz;
         // kept points that could not be proven final still bound the kNb-th distance from above (when all kNb are real)
         double sb = a.c.knn_max_sq;
@@ -683,15 +718,17 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
         ex.seed[tid] = sb;
     }
     __syncthreads();
+#pragma unroll
+    for (int wv = 0; wv < 4; ++wv) posted[wv] = ex.wcount[wv];
     }
-    if (tl) tl[2] = wall_clock64();
+    if (tl) { if (posted[0] == 0x12345678u) moved = true; tl[2] = wall_clock64(); }
     // ---- the posted queries are searched: a few -> one wave per query (lanes = candidates); many -> thread m
     //      serves the m-th posted query (lanes = queries) ----
     bool self = false;
     uint32_t self_pos[kNb], self_state = 0u;
     double self_bound = 0.0;
     {
-        const uint32_t n_miss = all_search ? 256u : ex.count;           // block-uniform
+        const uint32_t n_miss = all_search ? 256u : posted[0] + posted[1] + posted[2] + posted[3];           // block-uniform
         bool dense = n_miss > (uint32_t)kSparseMisses;
         if (n_miss && !dense) {
             if (tid == 0) ex.fallback = 0;
@@ -699,7 +736,7 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
             const int wave = tid >> 6;
             WaveCand* tab = reinterpret_cast<WaveCand*>(&sh) + (size_t)wave * (kWaveTab + 16);
             for (uint32_t m = wave; m < n_miss; m += 4) {
-                const uint32_t owner = ex.list[m];
+                const uint32_t owner = posted_owner(ex, posted, m);
                 uint32_t rp[kNb];
                 double nxt = 0.0;
                 bool ins = false;
@@ -734,7 +771,7 @@ __device__ __forceinline__ int loam_point(const LoamArgs& a, const GridHeader& h
             const uint32_t per = 256u >> pl2;                          // lanes per part
             const uint32_t m = (uint32_t)tid & (per - 1u), part = (uint32_t)tid >> (8u - pl2);
             const bool worker = m < n_miss;
-            const uint32_t owner = worker ? ex.list[m] : 0u;
+            const uint32_t owner = worker ? posted_owner(ex, posted, m) : 0u;      // (a lazy select: the list is read for m < n_miss only)
             uint32_t key[kNb + 1], idmask = 0u;
             const float gate_f = __double2float_ru(a.c.knn_max_sq * (1.0 + 1e-5));      // every candidate inside the gate has a float distance <= this
             const int rc = knn_scan<kGroup>(h, a.grid.pts, a.grid.cell_start, ex.qx[owner], ex.qy[owner], ex.qz[owner], gate_f, worker, sh, part, pl2, key,
@@ -1244,18 +1281,31 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(double
         for (int c = 0; c < 7; ++c) sh_rows[c * kRowStride + tid] = st == 0 ? row[c] : 0.0;
         sh_rows[7 * kRowStride + tid] = st == 0 ? 1.0 : 0.0;
         __syncthreads();
+        if (tl && base == blk * qpb) tl[18] = wall_clock64();      // rows in LDS
         n_hit += (uint32_t)__popcll(__ballot(how == 1)); n_search += (uint32_t)__popcll(__ballot(how == 2));   // per wave
         if (h.clamped) n_esc += (uint32_t)__popcll(__ballot(esc));
         if (e < 28) {
-            const double* ra = sh_rows + er * kRowStride + ch * 32;
-            const double* rb = sh_rows + ec * kRowStride + ch * 32;
+            // two doubles of each row per LDS read (the rows start on 16-byte boundaries, see MissExchange); the products are added one by one,
+            // i = 0 .. 31, as a plain loop would
+            const double2* ra = reinterpret_cast<const double2*>(sh_rows + er * kRowStride + ch * 32);
+            const double2* rb = reinterpret_cast<const double2*>(sh_rows + ec * kRowStride + ch * 32);
 #pragma unroll 8
-            for (int i = 0; i < 32; ++i) acc += ra[i] * rb[i];
+            for (int i = 0; i < 16; ++i) {
+                const double2 va = ra[i], vb = rb[i];
+                acc += va.x * vb.x;
+                acc += va.y * vb.y;
+            }
         }
+        if (tl && base == blk * qpb) { if (acc == 1.2345e300) n_hit = 0u; tl[19] = wall_clock64(); }   // chunk sums done
         __syncthreads();
         // The cache entries go out last, behind everything the block waits for; the rows and the search scratch are dead, so
-        // their LDS stages the transposition.  (wave-uniform test: nothing is staged or stored in a wave of unchanged entries)
-        if (__any(ew.what != 0u)) entry_store_wave(nn_cache + (q - (uint32_t)(tid & 63)), ew, reinterpret_cast<float4*>(sh_ov) + (tid >> 6) * (64 * kEntryVec));
+        // their LDS stages the transposition.  (wave-uniform tests: nothing is staged or stored in a wave of unchanged entries, and a wave with
+        // only a few writers stores per lane)
+        const int writers = __popcll(__ballot(ew.what != 0u));
+        if (writers) {      // (nested: side by side, what the two ways share -- the fields -- was computed in front of both tests, also for no writer)
+            if (writers > kFewWriters) entry_store_wave(nn_cache + (q - (uint32_t)(tid & 63)), ew, reinterpret_cast<float4*>(sh_ov) + (tid >> 6) * (64 * kEntryVec));
+            else entry_store_lane(nn_cache + q, ew);
+        }
         if (base + gridDim.x * qpb < a.n_src) __syncthreads();      // (grid-stride launch: the next round reuses that LDS)
     }
     if (tl) tl[5] = wall_clock64();

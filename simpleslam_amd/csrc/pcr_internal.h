@@ -87,7 +87,7 @@ static constexpr int kAccum = 32;        // 21 JtJ (upper) + 6 JtE + 1 count, pa
 static constexpr int kSlotRankFail = 30; //   sharded: > 0 when a rank's index is unusable (summed over the ranks by the exchange)
 static constexpr int kSlotEscapes = 31;  //   queries that left the region a clamped index covers
 static constexpr int kMaxPartials = 512; // linearisation blocks
-static constexpr int kTimelineSlots = 16; // s_memrealtime stamps per block and launch (pcr_get_timeline)
+static constexpr int kTimelineSlots = 24; // s_memrealtime stamps per block and launch (pcr_get_timeline)
 
 struct LoamConsts {
     double knn_max_sq, plane_thresh, point_thresh, pos_conv, rot_conv;

@@ -738,13 +738,14 @@ class LoamRegister(PointCloudRegister):
         return dict(iters_run=k, JtJ=JtJ[:k].reshape(-1, 6, 6), JtE=JtE[:k], n=n[:k], x=x[:k], cache_hits=hits[:k], searches=srch[:k])
 
     def timeline(self):
-        """[launch][block][8] stamps in microseconds relative to each launch's earliest block entry
-        (needs pcr_params.record_timeline = 1).  Columns 0-7: entry, prologue, posted, searched, plane, accumulated, stored, partial sums folded (inside the
-        prologue); 8-10 (dense search only): row ranges in LDS, first candidate chunk arrived, candidate stream done; 11: normal
-        equations solved (inside the prologue)."""
+        """[launch][block][24] stamps in microseconds relative to each launch's earliest block entry
+        (needs pcr_params.record_timeline = 1).  Columns 0-7: entry, prologue, posted, searched, plane, accumulated (entry stores issued), stored, partial
+        sums folded (inside the prologue); 8-10 (dense search only): row ranges in LDS, first candidate chunk arrived, candidate stream done; 11: normal
+        equations solved (inside the prologue); 12-15 (lanes that searched): gather returned, distances and proof, plane solved, plane gate; 16: pose in
+        registers, 17: hit test done (both before 'posted'); 18: rows in LDS, 19: chunk sums done (both before 'accumulated'); 20-23 unused."""
         nl, nb = C.c_int(0), C.c_int(0)
         self._check(self._lib.pcr_get_timeline(self._h, None, 0, C.byref(nl), C.byref(nb)))
-        raw = np.zeros((nl.value, nb.value, 16), np.uint64)
+        raw = np.zeros((nl.value, nb.value, 24), np.uint64)
         self._check(self._lib.pcr_get_timeline(self._h, raw.ctypes.data_as(C.c_void_p), raw.size, C.byref(nl), C.byref(nb)))
         t = raw.astype(np.int64)
         return (t - t[:, :, :1].min(axis=1, keepdims=True)) / 100.0
