@@ -246,6 +246,7 @@ public:
         return std::unique_ptr<SubMap>(new SubMap(v));
     }
     const pcr_map* handle() const { return m_; }
+    pcr_map* handle() { return m_; }
     uint64_t generation() const { uint64_t id = 0, g = 0; pcr_map_generation(m_, &id, &g); return g; }
 };
 
@@ -272,6 +273,57 @@ inline bool HipRegister::scan2Map(const void* d_src, size_t n_src, const SubMap&
     isConverge = conv != 0;
     return isConverge;
 }
+
+// trans::SixDof2Mobile (common/geometry/trans.hpp:68-86; applied to every refined pose at LidarOdometry.cpp:211): x, y and the rotation about Z
+// when the pose's rotation axis is within ~18 degrees of it; otherwise the heading is dropped, as in the reference (pcr_pose_to_mobile)
+inline pose_t SixDof2Mobile(const pose_t& p) {
+    pose_t res;
+    if (pcr_pose_to_mobile(p.data(), res.data())) throw std::runtime_error("pcr_pose_to_mobile failed");
+    return res;
+}
+
+// The per-scan loop of LidarOdometry::handler around scan2Map (LidarOdometry.cpp:160-214, MapManager.cpp:109-201) over a registrar and a SubMap,
+// both borrowed: pcr_frontend_*.  step(): voxel filter -> scan2Map against the sub-map -> SixDof2Mobile (params.mobile) -> setCurPose -> putKeyFrame
+// -> updateMap (queued; the next step, or finish(), collects it).  Failures throw with the library's message.
+class Frontend {
+    pcr_frontend* fe_ = nullptr;
+    static pcr_frontend_params params_or_default(const pcr_frontend_params* p) {
+        pcr_frontend_params d;
+        pcr_frontend_default_params(&d);
+        return p ? *p : d;
+    }
+public:
+    Frontend(HipRegister& reg, SubMap& map, const pcr_frontend_params* p = nullptr) {
+        const pcr_frontend_params prm = params_or_default(p);
+        fe_ = pcr_frontend_create(reg.handle(), map.handle(), &prm);
+        if (!fe_) throw std::runtime_error(pcr_frontend_last_error(nullptr));
+    }
+    Frontend(const Frontend&) = delete;
+    Frontend& operator=(const Frontend&) = delete;
+    ~Frontend() { pcr_frontend_destroy(fe_); }
+    // one scan from `init` (generateOdom's guess: previous pose o odometry) -> the pose; info: what the step did and how long its parts took
+    pose_t step(const PC_cPtr& scan, const pose_t& init, pcr_frontend_info* info = nullptr) {
+        return step(scan->points.data(), scan->size(), false, init, info);
+    }
+    // ... a scan that is in HBM already (PointXYZI layout)
+    pose_t step(const void* pts, size_t n, bool on_device, const pose_t& init, pcr_frontend_info* info = nullptr) {
+        pose_t res;
+        if (pcr_frontend_step(fe_, pts, n, sizeof(PointXYZI), on_device ? 1 : 0, init.data(), res.data(), info)) throw std::runtime_error(pcr_frontend_last_error(fe_));
+        return res;
+    }
+    // the NEXT scan's voxel filter, queued beside this scan's registration
+    void prefetch(const PC_cPtr& next) { prefetch(next->points.data(), next->size(), false); }
+    void prefetch(const void* pts, size_t n, bool on_device) {
+        if (pcr_frontend_prefetch(fe_, pts, n, sizeof(PointXYZI), on_device ? 1 : 0)) throw std::runtime_error(pcr_frontend_last_error(fe_));
+    }
+    size_t finish() {
+        size_t n = 0;
+        if (pcr_frontend_finish(fe_, &n)) throw std::runtime_error(pcr_frontend_last_error(fe_));
+        return n;
+    }
+    void reset() { if (pcr_frontend_reset(fe_)) throw std::runtime_error(pcr_frontend_last_error(fe_)); }
+    pcr_frontend* handle() { return fe_; }
+};
 
 class LoamRegister : public HipRegister {
 public:

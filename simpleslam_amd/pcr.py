@@ -84,6 +84,8 @@ ABI_SYMBOLS = [
     "pcr_sc_distances", "pcr_global_reloc_default_params", "pcr_global_reloc_hypotheses", "pcr_relocalize_global",
     "pcr_sc_rank_stored", "pcr_sc_shift_yaw",
     "pcr_liorf_pose_to_6dof", "pcr_liorf_6dof_to_pose", "pcr_liorf_linearize", "pcr_liorf_result",
+    "pcr_pose_to_mobile", "pcr_frontend_default_params", "pcr_frontend_create", "pcr_frontend_destroy", "pcr_frontend_last_error", "pcr_frontend_step",
+    "pcr_frontend_prefetch", "pcr_frontend_finish", "pcr_frontend_reset",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -111,6 +113,17 @@ class RelocCandidate(C.Structure):
 class GlobalRelocParams(C.Structure):
     """struct pcr_global_reloc_params (include/pcr_hip.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("places", C.c_int32), ("max_dist", C.c_double), ("local", RelocParams)]
+
+
+class FrontendParams(C.Structure):
+    """struct pcr_frontend_params (include/pcr_hip.h)."""
+    _fields_ = [("grid_size", C.c_double), ("radius", C.c_double), ("kf_gap", C.c_double), ("mobile", C.c_int32)]
+
+
+class FrontendInfo(C.Structure):
+    """struct pcr_frontend_info (include/pcr_hip.h)."""
+    _fields_ = [("registered", C.c_int32), ("converged", C.c_int32), ("iterations", C.c_int32), ("keyframe_added", C.c_int32), ("update_queued", C.c_int32),
+                ("n_filtered", C.c_int64), ("n_submap", C.c_int64), ("keyframes", C.c_int64), ("updates", C.c_int64), ("seconds", C.c_double * 5)]
 
 
 class GlobalRelocCandidate(C.Structure):
@@ -269,6 +282,19 @@ def load_library():
     L.pcr_global_reloc_hypotheses.argtypes = [dp, C.c_int32, C.POINTER(RelocParams), dp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.pcr_relocalize_global.argtypes = [vp, vp, dp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(GlobalRelocParams), dp, ip,
                                         C.POINTER(GlobalRelocCandidate), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.pcr_pose_to_mobile.argtypes = [dp, dp]
+    L.pcr_frontend_default_params.argtypes = [C.POINTER(FrontendParams)]
+    L.pcr_frontend_default_params.restype = None
+    L.pcr_frontend_create.argtypes = [vp, vp, C.POINTER(FrontendParams)]
+    L.pcr_frontend_create.restype = vp
+    L.pcr_frontend_destroy.argtypes = [vp]
+    L.pcr_frontend_destroy.restype = None
+    L.pcr_frontend_last_error.argtypes = [vp]
+    L.pcr_frontend_last_error.restype = C.c_char_p
+    L.pcr_frontend_step.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, dp, C.POINTER(FrontendInfo)]
+    L.pcr_frontend_prefetch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
+    L.pcr_frontend_finish.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.pcr_frontend_reset.argtypes = [vp]
     _lib = L
     return L
 
@@ -1153,6 +1179,89 @@ class SubMap:
             if rc:
                 raise PcrError(f"hipMemcpy failed: {rc}")
         return out.cpu().numpy()
+
+
+def pose_to_mobile(T):
+    """pcr_pose_to_mobile (host only): trans::SixDof2Mobile (common/geometry/trans.hpp:68-86) -- x, y and the rotation about Z; the heading is
+    dropped when the rotation's axis is not within |axis.z| > 0.95 of Z, as in the reference.  -> a new 4x4."""
+    c = _pose_in(T)
+    out = np.zeros(16)
+    dp = C.POINTER(C.c_double)
+    if load_library().pcr_pose_to_mobile(c.ctypes.data_as(dp), out.ctypes.data_as(dp)) != 0:
+        raise PcrError("pcr_pose_to_mobile failed")
+    return _pose_out(out)
+
+
+def frontend_default_params():
+    p = FrontendParams()
+    load_library().pcr_frontend_default_params(C.byref(p))
+    return p
+
+
+class Frontend:
+    """The per-scan loop of the reference's front end around scan2Map, in the library (pcr_frontend_*): voxel filter -> scan2Map against the sub-map ->
+    SixDof2Mobile (mobile=True) -> setCurPose -> putKeyFrame -> updateMap, queued.  sequence.drive() over sequence.GpuFront is the same loop in Python;
+    sequence.drive_frontend() drives this one.  The register and the sub-map are borrowed (and kept alive by this object)."""
+
+    _INFO_INTS = ("registered", "converged", "iterations", "keyframe_added", "update_queued", "n_filtered", "n_submap", "keyframes", "updates")
+    STEPS = ("voxel", "wait", "scan2map", "add_keyframe", "update_map")      # pcr_frontend_info.seconds
+
+    def __init__(self, register, submap=None, grid=0.5, radius=8.0, kf_gap=1.0, mobile=False):
+        self._lib = load_library()
+        self._fe = None
+        self.reg = register
+        self.map = submap or SubMap()
+        p = FrontendParams(float(grid), float(radius), float(kf_gap), 1 if mobile else 0)
+        self._fe = self._lib.pcr_frontend_create(register._h, self.map._m, C.byref(p))
+        if not self._fe:
+            raise PcrError(self._lib.pcr_frontend_last_error(None).decode())
+        # (per-call marshalling kept off the hot path, as in PointCloudRegister: persistent pose buffers and info block)
+        self._in_buf, self._out_buf = (C.c_double * 16)(), (C.c_double * 16)()
+        self._in_cm = np.frombuffer(self._in_buf, dtype=np.float64).reshape(4, 4)       # column-major 4x4 = transposed view
+        self._out_cm = np.frombuffer(self._out_buf, dtype=np.float64).reshape(4, 4)
+        self._info = FrontendInfo()
+        self._info_ref = C.byref(self._info)
+
+    def __del__(self):
+        try:
+            if self._fe:
+                self._lib.pcr_frontend_destroy(self._fe)
+                self._fe = None
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc:
+            raise PcrError(self._lib.pcr_frontend_last_error(self._fe).decode())
+
+    def step(self, scan, init_pose):
+        """pcr_frontend_step: one scan from `init_pose` (previous pose o odometry: the caller's) -> (pose 4x4, info dict: the fields of
+        pcr_frontend_info, `seconds` as a dict by step name)."""
+        p, n, s, dev, _keep = self.reg._cloud_cached(scan)
+        T = np.asarray(init_pose, dtype=np.float64)
+        if T.shape != (4, 4):
+            raise ValueError("pose must be 4x4")
+        self._in_cm[...] = T.T
+        self._check(self._lib.pcr_frontend_step(self._fe, p, n, s, dev, self._in_buf, self._out_buf, self._info_ref))
+        i = self._info
+        info = {f: int(getattr(i, f)) for f in self._INFO_INTS}
+        info["seconds"] = dict(zip(self.STEPS, i.seconds))
+        return self._out_cm.T.copy(), info
+
+    def prefetch(self, scan):
+        """pcr_frontend_prefetch: queue the voxel filter of a scan that a LATER step takes (the same object must be passed to that step)."""
+        p, n, s, dev, _keep = self.reg._cloud_cached(scan)
+        self._check(self._lib.pcr_frontend_prefetch(self._fe, p, n, s, dev))
+
+    def finish(self):
+        """pcr_frontend_finish: collect a queued assembly -> points of the sub-map."""
+        n = C.c_size_t(0)
+        self._check(self._lib.pcr_frontend_finish(self._fe, C.byref(n)))
+        return n.value
+
+    def reset(self):
+        """pcr_frontend_reset: a new session on the same handles (key frames, sub-map and the loop's state forgotten, device memory kept)."""
+        self._check(self._lib.pcr_frontend_reset(self._fe))
 
 
 class ScanContext:

@@ -20,6 +20,7 @@ import time
 import numpy as np
 
 from . import synth
+from .pcr import pose_to_mobile
 
 MIN_KF_GAP = 1.0          # MapManager.hpp:67
 SEARCH_RADIUS = 8.0       # MapManager.hpp:68
@@ -38,12 +39,14 @@ def make_drive(n_scans, seed, map_points=200_000, beams=64, azimuths=1024, step=
     return scans, truth, cmds
 
 
-def drive(front, scans, cmds, start_pose, grid=0.5, radius=SEARCH_RADIUS, kf_gap=MIN_KF_GAP, prefetch=False):
+def drive(front, scans, cmds, start_pose, grid=0.5, radius=SEARCH_RADIUS, kf_gap=MIN_KF_GAP, prefetch=False, mobile=False):
     """Run the loop; -> dict(poses, converged, iterations, submap_points, keyframes, updates, seconds, scan2map_seconds, step_seconds).
     step_seconds: host time per step of the loop, summed over the drive (every step but a queued assembly returns when its result is there, so no
     synchronisation is added to measure them): voxel, wait (collecting a queued sub-map), scan2map, add_keyframe, update_map.
     prefetch: the NEXT scan's voxel filter is queued (front.prefetch) before this scan is registered -- a caller that has the next scan already (a
-    recording replayed, a front end that lags its sensor); a front without prefetch() filters in place, so the results are the same either way."""
+    recording replayed, a front end that lags its sensor); a front without prefetch() filters in place, so the results are the same either way.
+    mobile: trans::SixDof2Mobile on every pose (LidarOdometry.cpp:211) -- before setCurPose, before the key frame is made, before the pose becomes the
+    next scan's starting point; registered or not.  Applied here, so it acts on every front alike."""
     pose = np.array(start_pose, float)
     kf_pos, n_kf, last_update = np.zeros((len(scans), 3)), 0, None      # (one array: the nearest key frame by one numpy expression, not a Python loop over them)
     poses, conv, iters, sub_n = [], [], [], []
@@ -66,6 +69,8 @@ def drive(front, scans, cmds, start_pose, grid=0.5, radius=SEARCH_RADIUS, kf_gap
             conv.append(bool(c)); iters.append(int(it))
         else:
             conv.append(True); iters.append(0)
+        if mobile:
+            pose = pose_to_mobile(pose)
         t = pose[:3, 3]
         need_update = last_update is None or float(np.linalg.norm(last_update - t)) > kf_gap       # setCurPose
         # putKeyFrame: nearestKSearch's squared distance against minKFGap (MapManager.cpp:141-143)
@@ -82,6 +87,29 @@ def drive(front, scans, cmds, start_pose, grid=0.5, radius=SEARCH_RADIUS, kf_gap
     ts["scan2map"] = t_s2m
     return dict(poses=poses, converged=conv, iterations=iters, submap_points=sub_n, keyframes=n_kf, updates=updates,
                 seconds=time.perf_counter() - t0, scan2map_seconds=t_s2m, step_seconds=ts)
+
+
+def drive_frontend(fe, scans, cmds, start_pose, prefetch=False):
+    """drive() with the loop in the library: fe = pcr.Frontend (pcr_frontend_step does the voxel filter, the wait, scan2map, the mobile projection,
+    both key-frame rules and the queued assembly; grid, radius, kf_gap and mobile are the Frontend's).  What stays here is the caller's part, as in the
+    reference: the starting point of every scan, pose @ cmds[k], formed exactly as drive() forms it.  -> the dict drive() returns."""
+    pose = np.array(start_pose, float)
+    poses, conv, iters, sub_n = [], [], [], []
+    ts = dict.fromkeys(fe.STEPS, 0.0)
+    clock = time.perf_counter
+    info = None
+    t0 = clock()
+    for k, scan in enumerate(scans):
+        if prefetch and k + 1 < len(scans):
+            t1 = clock(); fe.prefetch(scans[k + 1]); ts["voxel"] += clock() - t1      # (collects scan k's filter first: this step finds it ready)
+        pose, info = fe.step(scan, pose @ cmds[k])
+        if k: sub_n.append(info["n_submap"])
+        conv.append(bool(info["converged"])); iters.append(info["iterations"])
+        for name, sec in info["seconds"].items(): ts[name] += sec
+        poses.append(pose)
+    t1 = clock(); sub_n.append(fe.finish()); ts["wait"] += clock() - t1
+    return dict(poses=poses, converged=conv, iterations=iters, submap_points=sub_n, keyframes=info["keyframes"] if info else 0,
+                updates=info["updates"] if info else 0, seconds=clock() - t0, scan2map_seconds=ts["scan2map"], step_seconds=ts)
 
 
 class GpuFront:
