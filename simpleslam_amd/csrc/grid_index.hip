@@ -16,10 +16,6 @@
 
 namespace pcr {
 
-static constexpr int kScanPerThread = 8;
-static constexpr int kScanBlock = 256;
-static constexpr int kScanTile = kScanPerThread * kScanBlock;  // 2048 cells per block
-
 // ---- wave64 helpers --------------------------------------------------------
 __device__ inline float wave_min(float v) {
 #pragma unroll
@@ -392,7 +388,6 @@ static constexpr int kBinStride = 16;                  // counters 64 bytes apar
 //  rows instead of one line per counter at ~2.3 ns a line -- shorten that block's tail from 3.6 to 3 us at 1 M points and make the claims come back after
 //  41 us instead of 16: a chunk of a map in generator order touches every ground tile, ~300 claims per counter, and sixteen counters' claims then queue up
 //  on one line.  What bounds the claim phase is the serial handling of the claims on its hottest LINE.)
-static constexpr int kBinPerThread = 8;               // points per thread and chunk of the bin kernel
 
 // ---- BINS: the units of the two passes.  A build without a layout hint bins by TILE (2^shift consecutive cells: bin b = tile b).  A ground tile of a
 // 1 m grid over a 0.5 m map holds eight times the points of the median tile, and the tile pass lasted as long as its heaviest tile's ONE block (24 us of
@@ -1269,12 +1264,101 @@ hipError_t GridIndex::ensure_tables(hipStream_t s, std::string* err) {
     }
     return hipSuccess;
 }
-// The cell count a build may use: the table's capacity, or -- once a header of this index has been seen (note_cells) -- twice that header's count.
-size_t GridIndex::effective_capacity() const {
-    size_t cap_eff = cell_capacity;
-    if (cells_hint) cap_eff = std::min<size_t>(cell_capacity, std::max<size_t>(2 * (size_t)cells_hint + 64, 1024));
-    return cap_eff;
+// ---- the build: reserve, plan (grid_plan.h: every decision, on the host, tested without a GPU), enqueue what the plan says, commit the hints ----
+namespace {
+struct BuildArgs {      // what the launches of one build share beside the plan
+    const float* pts; uint32_t n, stride; hipStream_t s;
+    const uint8_t* keep_mask; int keep_mshift;      // a filtered build: the region's mask (BuildFilter)
+};
+
+void launch_box(GridIndex& g, const BuildPlan& p, const BuildArgs& a, double cell, double shift, int pcl_mode, const ClampBox& cb, const HeaderTwin& tw) {
+    hipLaunchKernelGGL(grid_bbox_header_kernel, dim3(kBBoxBlocks), dim3(256), 0, a.s, a.pts, a.n, a.stride, g.bbox_partials.as<float>(),
+                       g.ticket.as<uint32_t>(), g.header.as<GridHeader>(), (uint64_t)p.cap_eff, cell, shift, pcl_mode, cb,
+                       p.box_margin, g.header_mirror, tw, p.box_margin_z_pcl);
 }
+
+void launch_one_level(GridIndex& g, const BuildPlan& p, const BuildArgs& a) {
+    hipLaunchKernelGGL(grid_count_kernel, dim3(p.pt_blocks), dim3(256), 0, a.s, a.pts, a.n, a.stride, g.header.as<GridHeader>(),
+                       g.cell_count.as<uint32_t>(), g.keys.as<uint32_t>(), g.ranks.as<uint32_t>());
+    hipLaunchKernelGGL(grid_scan_local_kernel, dim3(p.scan_blocks), dim3(kScanBlock), 0, a.s, g.cell_count.as<uint32_t>(),
+                       g.cell_start.as<uint32_t>(), g.block_sums.as<uint32_t>(), g.header.as<GridHeader>());
+    hipLaunchKernelGGL(grid_scan_add_kernel, dim3(p.scan_blocks), dim3(kScanBlock), 0, a.s, g.cell_start.as<uint32_t>(),
+                       g.block_sums.as<uint32_t>(), g.header.as<GridHeader>());
+    hipLaunchKernelGGL(grid_scatter_kernel, dim3(p.pt_blocks), dim3(256), 0, a.s, a.pts, a.n, a.stride, g.header.as<GridHeader>(),
+                       g.keys.as<uint32_t>(), g.ranks.as<uint32_t>(), g.cell_start.as<uint32_t>(), g.sorted.as<float4>());
+}
+
+// region-only builds of large clouds: the region's points are listed first (n_kept: zero between builds, the bin pass's last block puts it back)
+void launch_keep(GridIndex& g, const BuildPlan& p, const BuildArgs& a) {
+    uint32_t* const n_kept = g.ticket.as<uint32_t>() + 16;
+    const uint32_t kept_cap = (uint32_t)std::min<size_t>(g.kept.cap / sizeof(float4), 0xfffffff0u);
+    if (p.vec) hipLaunchKernelGGL(grid_keep_kernel<true>, dim3(p.keep_blocks), dim3(256), 0, a.s, a.pts, a.n, a.stride, g.header.as<GridHeader>(), a.keep_mask, a.keep_mshift, g.kept.as<float4>(), kept_cap, n_kept);
+    else hipLaunchKernelGGL(grid_keep_kernel<false>, dim3(p.keep_blocks), dim3(256), 0, a.s, a.pts, a.n, a.stride, g.header.as<GridHeader>(), a.keep_mask, a.keep_mshift, g.kept.as<float4>(), kept_cap, n_kept);
+}
+
+// the bin pass: kBinVariant[kVariant] and no other instantiation (a packed one reads the list the keep pass left, which holds the region's points only)
+template <int kVariant>
+void launch_bin_as(GridIndex& g, const BuildPlan& p, const BuildArgs& a) {
+    constexpr BinVariant v = kBinVariant[kVariant];
+    const uint32_t tiled_cap = (uint32_t)std::min<size_t>(g.tiled.cap / sizeof(float4), 0xfffffff0u);
+    hipLaunchKernelGGL((grid_bin_kernel<v.vec, kBinPerThread, v.place, v.sub, v.packed>), dim3(v.packed ? p.packed_blocks : p.bin_blocks), dim3(256), p.bin_lds, a.s,
+                       v.packed ? g.kept.as<float>() : a.pts, a.n, v.packed ? 4u : a.stride, g.header.as<GridHeader>(),
+                       g.bin_count.as<uint32_t>(), g.ranks.as<uint32_t>(), p.tshift, p.max_bins, p.nb_bin, g.ticket.as<uint32_t>() + 8, g.bin_start.as<uint32_t>(),
+                       (const uint32_t*)g.layout[g.lay_idx].as<uint32_t>(), g.tiled.as<float4>(), tiled_cap, v.packed ? (const uint8_t*)nullptr : a.keep_mask, v.packed ? 0 : a.keep_mshift,
+                       v.packed ? g.ticket.as<uint32_t>() + 16 : (uint32_t*)nullptr);
+}
+hipError_t launch_bin(GridIndex& g, const BuildPlan& p, const BuildArgs& a) {
+    switch (variant_index(p.bin)) {
+    case 0: launch_bin_as<0>(g, p, a); break;
+    case 1: launch_bin_as<1>(g, p, a); break;
+    case 2: launch_bin_as<2>(g, p, a); break;
+    case 3: launch_bin_as<3>(g, p, a); break;
+    case 4: launch_bin_as<4>(g, p, a); break;
+    case 5: launch_bin_as<5>(g, p, a); break;
+    case 6: launch_bin_as<6>(g, p, a); break;
+    case 7: launch_bin_as<7>(g, p, a); break;
+    default: return hipErrorInvalidValue;      // (a variant that is not built: index_plan_check holds plan_build to the lists)
+    }
+    static_assert(kBinVariants == 8, "one case per variant");
+    return hipSuccess;
+}
+
+void launch_place(GridIndex& g, const BuildPlan& p, const BuildArgs& a) {
+    if (p.vec)
+        hipLaunchKernelGGL(grid_place_kernel<true>, dim3(p.place_blocks), dim3(256), p.place_lds, a.s, a.pts, a.n, a.stride, g.header.as<GridHeader>(), g.bin_count.as<uint32_t>(),
+                           g.ranks.as<uint32_t>(), g.bin_start.as<uint32_t>(), g.tiled.as<float4>(), p.tshift);
+    else
+        hipLaunchKernelGGL(grid_place_kernel<false>, dim3(p.place_blocks), dim3(256), p.place_lds, a.s, a.pts, a.n, a.stride, g.header.as<GridHeader>(), g.bin_count.as<uint32_t>(),
+                           g.ranks.as<uint32_t>(), g.bin_start.as<uint32_t>(), g.tiled.as<float4>(), p.tshift);
+}
+
+// launch i of the tile pass: kTileVariant[kVariant] and no other instantiation
+template <int kVariant>
+void launch_tile_as(GridIndex& g, const BuildPlan& p, int i, const BuildArgs& a, const TilePlan& next, const TileTail& tail) {
+    constexpr TileVariant v = kTileVariant[kVariant];
+    const uint32_t* const lay_cur = g.layout[g.lay_idx].as<uint32_t>();
+    hipLaunchKernelGGL((grid_tile_kernel<v.per, v.mode, v.threads, v.tail, v.plan, v.runs>), dim3(p.tile_blocks), dim3(v.threads), p.tile_lds[i], a.s, g.header.as<GridHeader>(), g.tile_sq.as<unsigned long long>(),
+                       g.bin_start.as<uint32_t>(), g.bin_count.as<uint32_t>(), g.tiled.as<float4>(), g.cell_start.as<uint32_t>(), g.sorted.as<float4>(), g.keys.as<uint32_t>(), p.tshift,
+                       p.use_layout ? lay_cur : (const uint32_t*)g.bin_start.as<uint32_t>(), p.use_layout ? lay_cur : (const uint32_t*)nullptr, next, tail);
+}
+hipError_t launch_tile(GridIndex& g, const BuildPlan& p, int i, const BuildArgs& a, const TilePlan& next, const TileTail& tail) {
+    switch (variant_index(p.tile[i])) {
+    case 0: launch_tile_as<0>(g, p, i, a, next, tail); break;
+    case 1: launch_tile_as<1>(g, p, i, a, next, tail); break;
+    case 2: launch_tile_as<2>(g, p, i, a, next, tail); break;
+    case 3: launch_tile_as<3>(g, p, i, a, next, tail); break;
+    case 4: launch_tile_as<4>(g, p, i, a, next, tail); break;
+    case 5: launch_tile_as<5>(g, p, i, a, next, tail); break;
+    case 6: launch_tile_as<6>(g, p, i, a, next, tail); break;
+    case 7: launch_tile_as<7>(g, p, i, a, next, tail); break;
+    case 8: launch_tile_as<8>(g, p, i, a, next, tail); break;
+    case 9: launch_tile_as<9>(g, p, i, a, next, tail); break;
+    default: return hipErrorInvalidValue;
+    }
+    static_assert(kTileVariants == 10, "one case per variant");
+    return hipSuccess;
+}
+}  // namespace
 
 hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, double cell, hipStream_t s, std::string* err, double shift,
                             int pcl_mode, const ClampBox* clamp, bool allow_hint, BuildFilter* filter) {
@@ -1282,6 +1366,7 @@ hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, 
     filtered = false;
     if (filter) { filter->applied = false; filter->tail_applied = false; }
     if (n > 0xfffffff0ull) { if (err) *err = "target cloud too large (>= 2^32 points)"; return hipErrorInvalidValue; }
+    // 1. reserve what every build needs
     const size_t n_res = std::max(n, reserve_points);      // (reserve_points: the caller knows its clouds will grow to that -- the sub-map assembly's concatenations)
     PCR_TRY(sorted.reserve((n_res + 16) * sizeof(float4)));   // padded: the search reads whole chunks
     PCR_TRY(bbox_partials.reserve(kBBoxBlocks * 6 * sizeof(float)));
@@ -1292,209 +1377,76 @@ hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, 
         PCR_TRY(hipMemsetAsync(ticket.p, 0, 256, s));
     }
     PCR_TRY(ensure_tables(s, err));
+    // 2. plan
     ClampBox cb;
     memset(&cb, 0, sizeof cb);
     if (clamp) cb = *clamp;
-    const uint32_t n32 = (uint32_t)n, st = (uint32_t)stride_floats;
-    const int pt_blocks = (int)std::min<size_t>(2048, (n + 255) / 256 ? (n + 255) / 256 : 1);
-    // The cell count this build may use: the table's capacity, or -- once a header of this index has been seen (note_cells) -- twice that
-    // header's count.  The tile size follows from it, and a grid of a few hundred cells (the coarse levels of the covariance search)
-    // must not be cut into 256-cell tiles: two blocks then sorted a whole scan between them (158 us).  A cloud that needs more cells
-    // than the bound raises header.overflow like a table that is too small, and grow_cells() lifts the bound.
-    const size_t cap_eff = effective_capacity();
-    // tile size: ~512 points per tile on average, at most 4096 tiles, at least 4 cells per tile (16-byte accesses of the tile kernel)
-    // (the bound was 2048: the 5 M-point map of the NDT configuration -- 2.45 M cells of 1 m -- then got 1 195 tiles of 2 048 cells; with 2 390 tiles
-    //  of 1 024 a call takes 0.321 instead of 0.337 ms, with 4 780 of 512 0.361, A/B on one box; clouds of up to 1 M points are not affected)
-    const size_t tiles_target = std::min<size_t>(4096, std::max<size_t>(64, n / 512));
-    // (never more than 2^11 cells per tile unless the counter array forces it: a tile's block zeroes, scans and writes every cell of it,
-    //  and a sparse fine grid -- 3.6 M cells for a 65 k-point scan -- is better served by many small tiles than by 440 blocks of 8 192 cells)
-    int tshift;
-    // (the voxel filter's grids -- 65 536 points over 2.3 M cells of 0.5 m -- take tiles of 4 096 cells: half the bins for the bin pass's last block to read back,
-    //  7 % off a scan's filter; 8 192 cells: slower again.  Round 5, scripts/seq_breakdown.py, two rounds on one box.)
-    const int tshift_cap = cut_sparse ? 12 : 11;
-    if (cells_hint) { tshift = 2; while ((cells_hint >> tshift) > tiles_target && tshift < tshift_cap) ++tshift; }
-    else { tshift = 8; while (((uint64_t)cap_eff >> tshift) + 2 > 2048 && tshift < 11) ++tshift; }
-    while (((uint64_t)cap_eff >> tshift) + 2 > (uint64_t)kMaxBins) ++tshift;
-    const bool tiled_path = tshift <= kMaxTileShift && !prefer_one_level;
-    const bool reuse_header = allow_hint && !no_hints && hint_ok && tiled_path && hint_pcl == pcl_mode && hint_shift == shift && !cb.use && hint_cell == cell && tiled_shift == tshift;
-    hint_ok = false;      // until the host has seen this build's header (confirm())
-    used_hint = reuse_header;
-    hint_cell = cell; hint_shift = shift; hint_pcl = pcl_mode;
-    // (a header written by the twin's build -- see below -- serves if it was made for this very cloud and cell)
-    const bool preset = header_preset && preset_pts == d_pts && preset_n == n && preset_cell == cell && !reuse_header && !cb.use && pcl_mode == 0 && shift == 0.0;
-    header_preset = false;
-    mirrored = false;
-    if (!reuse_header && !preset) {
-        HeaderTwin tw;
-        memset(&tw, 0, sizeof tw);
-        if (twin && twin != this && !cb.use && pcl_mode == 0 && shift == 0.0 && !allow_hint) {
-            PCR_TRY(twin->ensure_tables(s, err));
-            tw.hdr = twin->header.as<GridHeader>(); tw.mirror = twin->header_mirror; tw.capacity = (uint64_t)twin->effective_capacity(); tw.cell = twin_cell;
-            twin->header_preset = true; twin->preset_pts = d_pts; twin->preset_n = n; twin->preset_cell = twin_cell; twin->mirrored = twin->header_mirror != nullptr;
-        }
-        hipLaunchKernelGGL(grid_bbox_header_kernel, dim3(kBBoxBlocks), dim3(256), 0, s, d_pts, n32, st, bbox_partials.as<float>(),
-                           ticket.as<uint32_t>(), header.as<GridHeader>(), (uint64_t)cap_eff, cell, shift, pcl_mode, cb,
-                           (allow_hint && !cb.use) ? hint_margin : 0, header_mirror, tw, (allow_hint && !cb.use) ? hint_margin_z_pcl : 0);
-        mirrored = header_mirror != nullptr;
-    } else if (preset) mirrored = header_mirror != nullptr;
-    // Tile size from the CAPACITY of the cell table (the device-side cell count never exceeds it: a larger box is an overflow):
-    // ~2048 tiles when the table allows it -- 8 KB of LDS counters per block in the bin kernel, tiles of a few hundred to a few
-    // thousand points -- never more than kMaxBins.
-    if (tiled_path) {
-        const uint32_t max_bins = (uint32_t)(((uint64_t)cap_eff >> tshift) + 2);      // tiles the (bounded) cell table can make
-        PCR_TRY(tiled.reserve((n_res + 16) * sizeof(float4)));
-        PCR_TRY(bin_start.reserve((kMaxBins + 8) * sizeof(uint32_t)));
-        PCR_TRY(tile_sq.reserve((kMaxBins + 8) * sizeof(unsigned long long)));
-        tiled_shift = tshift;
-        if (!bin_count.p) {
-            PCR_TRY(bin_count.reserve(((size_t)kMaxBins + 64) * kBinStride * sizeof(uint32_t)));
-            PCR_TRY(hipMemsetAsync(bin_count.p, 0, bin_count.cap, s));      // builds expect and leave the counters zeroed
-        }
-        const bool vec = (stride_floats % 4 == 0) && ((uintptr_t)d_pts % 16 == 0);
-        const size_t bin_chunk = (size_t)256 * kBinPerThread;
-        const int bin_blocks = (int)std::min<size_t>(4096, (n + bin_chunk - 1) / bin_chunk ? (n + bin_chunk - 1) / bin_chunk : 1);
-        const int place_blocks = (int)std::min<size_t>(2048, (n + 1023) / 1024 ? (n + 1023) / 1024 : 1);
-        // (a grid with many more cells than points: light tiles and heavy tiles by an instantiation each, see grid_tile_kernel)
-        const bool sparse = split_sparse_tiles && cells_hint > 4 * (uint64_t)n + 65536;
-        const uint64_t tiles_est = cells_hint ? (cells_hint >> tshift) + 1 : 0;
-        // dense grids: eight points per thread (135 VGPRs, three waves per SIMD) while a tile holds ~1 000 points or fewer on average, sixteen
-        // beyond (A/B: 1 M points in 1 464 tiles 48.4 -> 46.8 us with eight; 5 M and 10 M points are faster with sixteen)
-        const bool per8 = !sparse && tiles_est && n / tiles_est <= 1024;
-        // BINS (see the top of the tiled path): a tile whose fullest slab holds more than `hs` points is cut one step further in the layout this build
-        // leaves -- three quarters of what a block of the tile pass holds in registers -- while the bins stay within nb_max.  pcr_params.index_no_hints:
-        // no layout is ever used, so nothing is cut.
-        // Measured (round 5, A/B on one box, profiles/r05_notes.md): at 1 M points hs = 2 048 or 3 072 takes the tile pass from 26.0 to 18.6 us and costs the bin pass
-        // 1.5 us (more bins: more claims); 1 024 costs it 4 us.  At 10 M points (tiles of 8 192 cells, sixteen points per thread) cutting does NOT pay: the bin
-        // pass's stores scatter over twice the bins (151 -> 186-235 us) and the tile pass, whose length there is blocks x latency / occupancy and not its heaviest
-        // block, stays at 153-169 us: clouds whose tiles hold more than ~1 000 points on average are never cut.
-        // (cut_sparse -- the voxel filter's index: a concatenation of raw key frames on the 0.5 m lattice is a sparse grid whose few tiles next to the vehicle's
-        //  path hold tens of thousands of points each; one block sorted such a tile alone, 95 us of a 150 us build.  Its bins hold up to 4 096 points in registers.)
-        const uint32_t hs = per8 ? 2048u : (sparse && cut_sparse ? 3072u : 0xffffffffu);
-        // bins a layout may hold: the tiles + two bins per `hs` points (a slab that was cut holds between hs / 2 and hs), never fewer than the tiles the table
-        // can make, and never fewer than the layout in hand was planned for (the bin pass sizes its LDS by it)
-        uint32_t nb_max = (uint32_t)std::min<uint64_t>((uint64_t)kMaxBins, std::max<uint64_t>((uint64_t)max_bins, (tiles_est ? tiles_est + 2 : (uint64_t)max_bins) + (hs != 0xffffffffu ? 2 * (uint64_t)n / hs : 0)));
-        if (hs == 0xffffffffu && !(lay_ok && lay_cuts)) nb_max = max_bins;
-        if (lay_ok && lay_shift == tshift) nb_max = std::max(nb_max, lay_nb_max);
-        // Layout hint (see grid_bin_kernel<.., kPlace>): the previous build of this index left, next to its header, where each bin's
-        // points may go; a build that reuses the header places by it and skips the placing pass.
-        const bool use_layout = reuse_header && lay_ok && lay_shift == tshift && lay_nb_max <= nb_max;
-        for (int i = 0; i < 2; ++i)
-            if (!layout[i].p) { PCR_TRY(layout[i].reserve(kLayWords * sizeof(uint32_t))); PCR_TRY(hipMemsetAsync(layout[i].p, 0, kLayWords * sizeof(uint32_t), s)); }      // (meta word 0: no layout)
-        if (use_layout) {      // room for every bin's slack, the children of a tile that is cut one step further get their parent's room each:
-                               // at most twice the cloud's (the device also checks every store against the capacity it is told)
-            const size_t need = 2 * (lay_n + (lay_n >> lay_room_shift)) + (size_t)lay_room_add * (nb_max + 1) + 16;
-            if (need > n + 16) PCR_TRY(tiled.reserve(need * sizeof(float4)));
-        }
-        const uint32_t tiled_cap = (uint32_t)std::min<size_t>(tiled.cap / sizeof(float4), 0xfffffff0u);
-        const uint32_t* const lay_cur = layout[lay_idx].as<uint32_t>();
-        uint32_t* const lay_next = layout[lay_idx ^ 1].as<uint32_t>();
-        used_layout = use_layout;
-        const uint8_t* keep_mask = nullptr;
-        int keep_mshift = 0;
-        if (filter && use_layout && filter->enqueue_mask) {      // the lattice is the reused header's, the rooms are the full cloud's: this build may leave points out
-            PCR_TRY(filter->enqueue_mask());
-            keep_mask = filter->mask; keep_mshift = filter->mshift;
-            filter->applied = filtered = keep_mask != nullptr;
-        }
-        const bool cuts_now = hs != 0xffffffffu;                      // the layout this build plans may cut tiles
-        const bool use_sub = use_layout && lay_cuts;                   // the layout in hand may hold tiles that are cut
-        const bool plan_lds = cuts_now || use_sub;                     // block 0 of the tile pass plans with cuts (or merges some back): it keeps the bins' positions + the tiles' words in LDS
-        // (sizing the bin pass's LDS by the tiles the reused header HAS instead of the tiles the table could make -- four blocks per CU instead of three at
-        //  10 M points -- changed nothing: 300 / 306 us against 298 / 310, round 5.  At 10 M points the two passes move ~750 MB in 300 us: 2.5 TB/s of real traffic)
-        const uint32_t nb_bin = use_layout ? nb_max : max_bins;      // bins the bin pass counts in LDS
-        const size_t bin_lds = (size_t)nb_bin * 4 + (use_layout ? ((size_t)nb_bin + 4) * 4 : 0) + (use_sub ? ((size_t)max_bins + 8) * 2 : 0), place_lds = ((size_t)max_bins + 4) * 4,
-                     tile_lds = std::max<size_t>((size_t)(1u << tshift) * 4, plan_lds ? ((size_t)nb_max + 4) * 4 + ((size_t)max_bins + 8) * 2 : 0);
-#define PCR_LAUNCH_BIN(VEC, PER, PLACE, SUB) hipLaunchKernelGGL((grid_bin_kernel<VEC, PER, PLACE, SUB>), dim3(bin_blocks), dim3(256), bin_lds, s, d_pts, n32, st, header.as<GridHeader>(), \
-                                                    bin_count.as<uint32_t>(), ranks.as<uint32_t>(), tshift, max_bins, nb_bin, ticket.as<uint32_t>() + 8, bin_start.as<uint32_t>(), \
-                                                    lay_cur, tiled.as<float4>(), tiled_cap, keep_mask, keep_mshift)
-#define PCR_LAUNCH_BIN_P(VEC, PLACE, SUB) PCR_LAUNCH_BIN(VEC, kBinPerThread, PLACE, SUB)
-        // region-only builds of large clouds: the region's points are listed first, the bin pass reads the list (grid_keep_kernel; smaller clouds: the bin
-        // pass tests the mask itself)
-        const bool keep_pass = keep_mask != nullptr && n >= 2000000;      // (a 1 M-point lattice build -- VGICP's -- is 1.5 % SLOWER with the extra launch)
-        if (keep_pass) {
-            PCR_TRY(kept.reserve((n + 16) * sizeof(float4)));
-            uint32_t* const n_kept = ticket.as<uint32_t>() + 16;      // (zero between builds: the bin pass's last block puts it back)
-            const int keep_blocks = (int)std::min<size_t>(1024, (n + 2047) / 2048);
-            const uint32_t kept_cap = (uint32_t)std::min<size_t>(kept.cap / sizeof(float4), 0xfffffff0u);
-            if (vec) hipLaunchKernelGGL(grid_keep_kernel<true>, dim3(keep_blocks), dim3(256), 0, s, d_pts, n32, st, header.as<GridHeader>(), keep_mask, keep_mshift, kept.as<float4>(), kept_cap, n_kept);
-            else hipLaunchKernelGGL(grid_keep_kernel<false>, dim3(keep_blocks), dim3(256), 0, s, d_pts, n32, st, header.as<GridHeader>(), keep_mask, keep_mshift, kept.as<float4>(), kept_cap, n_kept);
-            const int packed_blocks = std::min(bin_blocks, 512);      // (a block takes chunk after chunk: the list's length is the device's to know)
-            const size_t lds8 = bin_lds;
-#define PCR_LAUNCH_BIN_PACKED(SUB) hipLaunchKernelGGL((grid_bin_kernel<true, kBinPerThread, true, SUB, true>), dim3(packed_blocks), dim3(256), lds8, s, kept.as<float>(), n32, 4u, header.as<GridHeader>(), \
-                                                    bin_count.as<uint32_t>(), ranks.as<uint32_t>(), tshift, max_bins, nb_bin, ticket.as<uint32_t>() + 8, bin_start.as<uint32_t>(), \
-                                                    lay_cur, tiled.as<float4>(), tiled_cap, (const uint8_t*)nullptr, 0, n_kept)
-            if (use_sub) PCR_LAUNCH_BIN_PACKED(true); else PCR_LAUNCH_BIN_PACKED(false);
-#undef PCR_LAUNCH_BIN_PACKED
-        }
-        else if (use_layout && use_sub) { if (vec) PCR_LAUNCH_BIN_P(true, true, true); else PCR_LAUNCH_BIN_P(false, true, true); }
-        else if (use_layout) { if (vec) PCR_LAUNCH_BIN_P(true, true, false); else PCR_LAUNCH_BIN_P(false, true, false); }
-        else { if (vec) PCR_LAUNCH_BIN_P(true, false, false); else PCR_LAUNCH_BIN_P(false, false, false); }
-#undef PCR_LAUNCH_BIN_P
-#undef PCR_LAUNCH_BIN
-        if (!use_layout) {
-            if (vec)
-                hipLaunchKernelGGL(grid_place_kernel<true>, dim3(place_blocks), dim3(256), place_lds, s, d_pts, n32, st, header.as<GridHeader>(), bin_count.as<uint32_t>(),
-                                   ranks.as<uint32_t>(), bin_start.as<uint32_t>(), tiled.as<float4>(), tshift);
-            else
-                hipLaunchKernelGGL(grid_place_kernel<false>, dim3(place_blocks), dim3(256), place_lds, s, d_pts, n32, st, header.as<GridHeader>(), bin_count.as<uint32_t>(),
-                                   ranks.as<uint32_t>(), bin_start.as<uint32_t>(), tiled.as<float4>(), tshift);
-        }
-        TileTail tail;
-        memset(&tail, 0, sizeof tail);
-        // block 0 of the (first) tile launch plans the layout of the next build; the others take a bin each
-        TilePlan plan;
-        plan.lay_next = lay_next; plan.hs = hs; plan.nb_max = nb_max; plan.enabled = 1; plan.copy_only = filtered ? 1 : 0; plan.cuts = cuts_now ? 1 : 0; plan.room_shift = lay_room_shift; plan.room_add = lay_room_add; plan.pad_ = 0;
-        // the tile pass: a block per bin, + block 0 (persistent blocks -- 6 / 4 / 2 per CU by their registers -- measured no better at 1 M points and
-        // 6 % worse at 10 M, round 5)
-        // (a block per bin the host EXPECTS -- the tiles of the header it has seen + a bin per hs points when tiles are cut -- not per bin the table could
-        //  make: a block that finds no bin still waits for the header, ~2 us of a slot each, and there were 3 000 of them at 10 M points; a block takes
-        //  bin after bin, so more bins than blocks are served all the same)
-        const uint32_t bins_bound = use_layout ? nb_max : max_bins;
-        const uint32_t bins_expected = tiles_est ? (uint32_t)std::min<uint64_t>(bins_bound, tiles_est + 16 + (use_layout && hs != 0xffffffffu ? (uint64_t)n / hs : 0)) : bins_bound;
-        const int tile_blocks = (int)bins_expected + 1;
-#define PCR_LAUNCH_TILE_R(PER, MODE, THREADS, TAIL, PLAN, RUNS) hipLaunchKernelGGL((grid_tile_kernel<PER, MODE, THREADS, TAIL, PLAN, RUNS>), dim3(tile_blocks), dim3(THREADS), (PLAN) ? tile_lds : (size_t)(1u << tshift) * 4, s, header.as<GridHeader>(), tile_sq.as<unsigned long long>(), \
-                           bin_start.as<uint32_t>(), bin_count.as<uint32_t>(), tiled.as<float4>(), cell_start.as<uint32_t>(), sorted.as<float4>(), keys.as<uint32_t>(), tshift, \
-                           use_layout ? lay_cur : (const uint32_t*)bin_start.as<uint32_t>(), use_layout ? lay_cur : (const uint32_t*)nullptr, plan, tail)
-#define PCR_LAUNCH_TILE_T(PER, MODE, THREADS, TAIL, PLAN) PCR_LAUNCH_TILE_R(PER, MODE, THREADS, TAIL, PLAN, false)
-#define PCR_LAUNCH_TILE(PER, MODE, THREADS) PCR_LAUNCH_TILE_T(PER, MODE, THREADS, false, true)
-        // (measured and not kept: blocks of 1 024 threads for the 5 M and 10 M-point maps cut the slowest tile of the 10 M-point map from 165 to 69 us
-        //  and left the kernel at 165 us: one block per CU then, 19 rounds of ~8 us; profiles/r04_notes.md)
-        // (the tile pass lists NDT's voxel cells beside its own work: dense grids, tiles of at most 2^13 cells -- 32 per thread)
-        const bool with_tail = filtered && filter->want_tail && !sparse && tshift <= 13;
-        if (with_tail) { tail = filter->tail; tail.mask = keep_mask; tail.mshift = keep_mshift; filter->tail_applied = true; }
-        // (sparse grids: the launch of the light tiles carries no planning block -- its 58 registers are what lets eight of its blocks share a CU)
-        // (the heavy bins of the voxel filter's clouds by blocks of 1 024 threads: what a block holds in registers is the same 4 096 points, a bin of 12 000 --
-        //  three chunks, two sweeps each -- is through four times sooner)
-        if (coherent_input && sparse) { PCR_LAUNCH_TILE_R(1, 1, 256, false, false, true); PCR_LAUNCH_TILE_R(4, 2, 1024, false, true, true); }
-        else if (coherent_input && !with_tail) { if (per8) PCR_LAUNCH_TILE_R(8, 0, 256, false, true, true); else PCR_LAUNCH_TILE_R(16, 0, 256, false, true, true); }
-        else if (sparse) { PCR_LAUNCH_TILE_T(1, 1, 256, false, false); PCR_LAUNCH_TILE(16, 2, 256); }
-        else if (with_tail) { if (per8) PCR_LAUNCH_TILE_T(8, 0, 256, true, true); else PCR_LAUNCH_TILE_T(16, 0, 256, true, true); }
-        else if (per8) PCR_LAUNCH_TILE(8, 0, 256);
-        else PCR_LAUNCH_TILE(16, 0, 256);
-#undef PCR_LAUNCH_TILE
-#undef PCR_LAUNCH_TILE_T
-#undef PCR_LAUNCH_TILE_R
-        lay_nb_max = nb_max; lay_cuts = cuts_now || use_sub;
-        lay_idx ^= 1; lay_ok = true; lay_shift = tshift;      // (what this build's last block wrote serves the next one)
-        if (!filtered) lay_n = n;
-        PCR_TRY(hipGetLastError());
-        n_points = n;
-        valid = true;
-        return hipSuccess;
-    }
-    tiled_shift = -1;
-    hipLaunchKernelGGL(grid_count_kernel, dim3(pt_blocks), dim3(256), 0, s, d_pts, n32, st, header.as<GridHeader>(),
-                       cell_count.as<uint32_t>(), keys.as<uint32_t>(), ranks.as<uint32_t>());
-    const int scan_blocks = (int)((cell_capacity + kScanTile - 1) / kScanTile);
-    hipLaunchKernelGGL(grid_scan_local_kernel, dim3(scan_blocks), dim3(kScanBlock), 0, s, cell_count.as<uint32_t>(),
-                       cell_start.as<uint32_t>(), block_sums.as<uint32_t>(), header.as<GridHeader>());
-    hipLaunchKernelGGL(grid_scan_add_kernel, dim3(scan_blocks), dim3(kScanBlock), 0, s, cell_start.as<uint32_t>(),
-                       block_sums.as<uint32_t>(), header.as<GridHeader>());
-    hipLaunchKernelGGL(grid_scatter_kernel, dim3(pt_blocks), dim3(256), 0, s, d_pts, n32, st, header.as<GridHeader>(),
-                       keys.as<uint32_t>(), ranks.as<uint32_t>(), cell_start.as<uint32_t>(), sorted.as<float4>());
-    PCR_TRY(hipGetLastError());
+    has_mirror = header_mirror != nullptr; has_twin = twin && twin != this;
+    BuildRequest rq;
+    rq.pts = d_pts; rq.n = n; rq.stride_floats = stride_floats; rq.cell = cell; rq.shift = shift; rq.pcl_mode = pcl_mode; rq.clamp = cb.use != 0; rq.allow_hint = allow_hint;
+    rq.mask_callback = filter && filter->enqueue_mask; rq.want_tail = filter && filter->want_tail;
+    BuildPlan p = plan_build(*this, rq);
+    // 3. enqueue (a failed build leaves nothing for the next one to reuse)
+    const hipError_t e = enqueue_build(p, rq, n_res, cb, s, err, filter);
+    if (e != hipSuccess) { hint_ok = false; header_preset = false; return e; }
+    // 4. commit the hints: what the next build of this index -- and of its twin -- may count on
+    if (p.feeds_twin) { twin->header_preset = true; twin->preset_pts = d_pts; twin->preset_n = n; twin->preset_cell = twin_cell; twin->mirrored = twin->header_mirror != nullptr; }
+    commit_build(*this, rq, p);
     n_points = n;
     valid = true;
+    return hipSuccess;
+}
+
+// What `p` says, onto the stream.  A build that reuses a layout may be a filtered one: the filter's callback is called once the buffers it may touch
+// exist, and the plan is completed with its answer (no box kernel precedes it: a layout is used only with a reused header).
+hipError_t GridIndex::enqueue_build(BuildPlan& p, BuildRequest& rq, size_t n_res, const ClampBox& cb, hipStream_t s, std::string* err, BuildFilter* filter) {
+    BuildArgs a = {rq.pts, (uint32_t)rq.n, (uint32_t)rq.stride_floats, s, nullptr, 0};
+    if (p.box) {
+        HeaderTwin tw;
+        memset(&tw, 0, sizeof tw);
+        if (p.feeds_twin) {
+            PCR_TRY(twin->ensure_tables(s, err));
+            tw.hdr = twin->header.as<GridHeader>(); tw.mirror = twin->header_mirror; tw.capacity = (uint64_t)twin->effective_capacity(); tw.cell = twin_cell;
+        }
+        launch_box(*this, p, a, rq.cell, rq.shift, rq.pcl_mode, cb, tw);
+    }
+    if (!p.tiled_path) {
+        launch_one_level(*this, p, a);
+        PCR_TRY(hipGetLastError());
+        return hipSuccess;
+    }
+    PCR_TRY(tiled.reserve((n_res + 16) * sizeof(float4)));
+    PCR_TRY(bin_start.reserve((kMaxBins + 8) * sizeof(uint32_t)));
+    PCR_TRY(tile_sq.reserve((kMaxBins + 8) * sizeof(unsigned long long)));
+    if (!bin_count.p) {
+        PCR_TRY(bin_count.reserve(((size_t)kMaxBins + 64) * kBinStride * sizeof(uint32_t)));
+        PCR_TRY(hipMemsetAsync(bin_count.p, 0, bin_count.cap, s));      // builds expect and leave the counters zeroed
+    }
+    for (int i = 0; i < 2; ++i)
+        if (!layout[i].p) { PCR_TRY(layout[i].reserve(kLayWords * sizeof(uint32_t))); PCR_TRY(hipMemsetAsync(layout[i].p, 0, kLayWords * sizeof(uint32_t), s)); }      // (meta word 0: no layout)
+    if (p.tiled_need) PCR_TRY(tiled.reserve(p.tiled_need * sizeof(float4)));
+    if (p.asks_mask) {
+        PCR_TRY(filter->enqueue_mask());
+        a.keep_mask = filter->mask; a.keep_mshift = filter->mshift;
+        rq.mask_set = a.keep_mask != nullptr;
+        p = plan_build(*this, rq);
+        filter->applied = p.filtered;
+    }
+    if (p.keep_pass) {
+        PCR_TRY(kept.reserve((rq.n + 16) * sizeof(float4)));
+        launch_keep(*this, p, a);
+    }
+    PCR_TRY(launch_bin(*this, p, a));
+    if (p.place) launch_place(*this, p, a);
+    TileTail tail;
+    memset(&tail, 0, sizeof tail);
+    if (p.with_tail) { tail = filter->tail; tail.mask = a.keep_mask; tail.mshift = a.keep_mshift; filter->tail_applied = true; }
+    // block 0 of the (first) tile launch plans the layout of the next build; the others take a bin each
+    TilePlan next;
+    next.lay_next = layout[lay_idx ^ 1].as<uint32_t>(); next.hs = p.hs; next.nb_max = p.nb_max; next.enabled = 1; next.copy_only = p.filtered ? 1 : 0; next.cuts = p.cuts_now ? 1 : 0;
+    next.room_shift = lay_room_shift; next.room_add = lay_room_add; next.pad_ = 0;
+    for (int i = 0; i < p.n_tile; ++i) PCR_TRY(launch_tile(*this, p, i, a, next, tail));
+    PCR_TRY(hipGetLastError());
     return hipSuccess;
 }
 

@@ -67,6 +67,11 @@ int build_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_
     h->tgt_ptr = d_dst; h->tgt_n = n_dst; h->tgt_stride = stride_floats; h->have_target = true;
     return 0;
 }
+// The box taken over from the previous target does not hold this one (header.stale): the kept target again, with a fresh box, padded from now on.
+int rebuild_stale_target(pcr_handle* h) {
+    h->grid.hint_margin = 8; h->grid.cells_hint = 0;      // (a cloud that left the old box: its cell count is anybody's guess too)
+    return build_target(h, h->tgt_ptr, h->tgt_n, h->tgt_stride);
+}
 
 // After a synchronisation: did the device-side build overflow the cell table?  Then grow and rebuild.
 // Returns 0 ok (no overflow), 2 rebuilt (caller must rerun), 1 error.
@@ -166,9 +171,8 @@ int settle_loam_index(pcr_handle* h, const float* d_src, size_t n_src, size_t st
         GridHeader hdr;
         H_TRY(hipMemcpyAsync(&hdr, h->grid.header.p, sizeof(hdr), hipMemcpyDeviceToHost, h->stream));
         H_TRY(hipStreamSynchronize(h->stream));
-        if (hdr.stale) {      // the box taken over from the previous target does not hold this one: fresh box, padded from now on
-            h->grid.hint_margin = 8; h->grid.cells_hint = 0;      // (a cloud that left the old box: its cell count is anybody's guess too)
-            if (build_target(h, h->tgt_ptr, h->tgt_n, h->tgt_stride)) return 1;
+        if (hdr.stale) {
+            if (rebuild_stale_target(h)) return 1;
             continue;
         }
         const int ov = check_grid_overflow(h, hdr.overflow, hdr.n_cells, h->clamp_allowed ? d_src : nullptr, n_src, stride_floats, pose);
@@ -287,9 +291,8 @@ int run_loam(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floa
             continue;
         }
         if (!shard) {
-            if (r.grid_stale) {      // the box taken over from the previous target does not hold this one: fresh box, padded from now on
-                h->grid.hint_margin = 8; h->grid.cells_hint = 0;      // (a cloud that left the old box: its cell count is anybody's guess too)
-                if (build_target(h, h->tgt_ptr, h->tgt_n, h->tgt_stride)) return 1;
+            if (r.grid_stale) {
+                if (rebuild_stale_target(h)) return 1;
                 index_timed = false;
                 continue;
             }

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "../../include/pcr_hip.h"
+#include "grid_plan.h"
 
 namespace pcr {
 
@@ -66,7 +67,6 @@ static constexpr int kPad = 2;           // pad cells per side (see grid_index.h
 // progress word of the device-resident optimisers (NdtOut / VgOut): call number * kProgressWindow + passes consumed.  The pass budget
 // of a call ((ndt_max_iters + 3) * 13 + 5, vgicp_max_iters * lm_inner + 3) must stay inside the window: checked by pace_passes (handle.h).
 static constexpr double kProgressWindow = 1048576.0;
-static constexpr int kBBoxBlocks = 256;  // partial bounding boxes
 
 struct Pose16 { double m[16]; };
 
@@ -154,9 +154,6 @@ struct DeviceBuf {
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
-static constexpr int kMaxBins = 8192;    // tiles of the tiled build path (grid_index.hip): one 32 KB LDS histogram
-static constexpr int kMaxTileShift = 13; // a tile's cells are histogrammed in LDS too
-
 // A build that indexes only the points inside a region (pcr_scan2map of NDT: voxel Gaussians depend on a voxel's own points alone, so
 // a lattice that holds nothing outside the region the scan can reach serves that scan as the full one would).  Possible only when the
 // build reuses the header and the tile layout of a previous FULL build (the lattice the mask is laid over must be known before the
@@ -182,51 +179,19 @@ struct BuildFilter {
     bool tail_applied = false;          // ... and did (only together with `applied`, on the dense tile kernel)
 };
 
-struct GridIndex {
+// The hints a build leaves for the next one, and the switches its owner sets, are the base (grid_plan.h: BuildHints): build() reserves, plans
+// (plan_build: a pure host function), enqueues what the plan says and commits the hints (commit_build).
+struct GridIndex : BuildHints {
     DeviceBuf sorted, cell_count, cell_start, block_sums, bbox_partials, header, keys, ranks, ticket;
     DeviceBuf kept;                             // region-only builds: the points of the region as (x, y, z, original index), listed by grid_keep_kernel for the bin pass
     DeviceBuf tiled, bin_count, bin_start, tile_sq;      // tiled build path: points grouped by tile, points per tile, first point of every tile, sum of count^2 per tile
-    int tiled_shift = -1;                       // log2(cells per tile) of the last build when it took the tiled path
-    // Bounding-box hint: a build whose header the host has seen to be good (confirm()) lets the NEXT build of the same kind skip
-    // the bounding-box pass and reuse that header -- a sub-map changes by a key frame at a time.  The bin kernel checks every
-    // point against the box; one outside sets header.stale and the caller rebuilds with a fresh (and from then on padded) box.
-    bool hint_ok = false;
-    double hint_cell = 0.0, hint_shift = 0.0;
-    int hint_pcl = 0;                           // lattice kind of the build the hint comes from (a hint serves only a build of the same kind)
-    int hint_margin = 0;                        // cells added around a fresh box in x and y (0 until a hint has failed once)
-    int hint_margin_z_pcl = 0;                  // ... and in z, for a pcl::VoxelGrid lattice (the voxel filter; the other lattices: see grid_bbox_header_kernel)
-    bool used_hint = false;                     // the last build() reused the header
-    bool no_hints = false;                      // pcr_params.index_no_hints: never reuse a header or a tile layout
-    bool coherent_input = false;                // the clouds are stored in a spatially coherent order (scans, ring by ring): the tile pass counts by runs of equal cells (grid_tile_kernel: kRuns)
-    bool cut_sparse = false;                    // sparse grids too have their heavy tiles cut into slabs by the layout hint (grid_index.hip: BINS); the voxel filter's index
-    bool split_sparse_tiles = true;             // sparse grids: light and heavy tiles by an instantiation of the tile kernel each (grid_index.hip)
-    bool prefer_one_level = false;              // build by the one-level path (histogram with ranks -> scan -> scatter): a small cloud on a COARSE grid puts
-                                                // a third of its points into one tile, which one block of the tiled path then sorts alone
-    // Layout hint: where each BIN's points may go in `tiled` (an eighth more room than the bin held + 32) and which bins the tiles are cut into
-    // (grid_index.hip: BINS), planned by one block of every tiled build's tile pass for the next one; two buffers, alternating.  Used only
-    // together with a reused header.
-    DeviceBuf layout[2];
-    int lay_idx = 0, lay_shift = -1;
-    uint32_t lay_nb_max = 0;                    // bins the layout in hand was planned for (the next build must have room for as many)
-    bool lay_cuts = false;                      // ... and it may hold tiles that are cut (the bin pass then reads the tiles' words)
-    size_t lay_n = 0;
-    uint32_t lay_room_add = 32;                 // ... + lay_room_add
-    int lay_room_shift = 3;                     // a bin's room in the layout: what it held + that >> lay_room_shift + 32 (the voxel filter's clouds change more from call to call: 1)
-    bool lay_ok = false, used_layout = false;
-    bool filtered = false;                      // the last build() indexed the points of a region only (BuildFilter)
+    DeviceBuf layout[2];                        // the layout hint's two buffers, alternating (BuildHints::lay_idx)
     // A build WITHOUT hints computes the bounding box itself; then (grid_bbox_header_kernel)
     GridHeader* header_mirror = nullptr;        //   the header is also written to this host-mapped address (no copy queued behind the build): `mirrored` says so
-    bool mirrored = false;
     GridIndex* twin = nullptr;                  //   and `twin`, an index the caller builds NEXT over the same cloud with cell twin_cell, gets its header from the
     double twin_cell = 0.0;                     //   same pass (its build() then launches no box kernel)
-    bool header_preset = false;
-    const float* preset_pts = nullptr; size_t preset_n = 0; double preset_cell = 0.0;
     hipError_t ensure_tables(hipStream_t s, std::string* err);
-    size_t effective_capacity() const;
     void confirm() { hint_ok = valid && tiled_shift >= 0; }
-    size_t cell_capacity = 0;   // entries available in cell_count / cell_start
-    uint64_t cells_hint = 0;    // cells of the last header of this index the host has seen (0: none): bounds the next build's cell count and sets its tile size
-    void note_cells(uint64_t n_cells) { if (n_cells) cells_hint = n_cells; }
     size_t n_points = 0;
     size_t reserve_points = 0;  // build() sizes its point-sized buffers for at least that many points (a caller whose clouds grow: every growth is an allocation and a free, device-wide stops)
     bool valid = false;
@@ -238,6 +203,8 @@ struct GridIndex {
     hipError_t build(const float* d_pts, size_t n, size_t stride_floats, double cell, hipStream_t s,
                      std::string* err, double shift = 0.0, int pcl_mode = 0, const ClampBox* clamp = nullptr, bool allow_hint = false,
                      BuildFilter* filter = nullptr);
+    // build()'s third step: what the plan says, onto the stream (it completes the plan with the answer of the filter's mask callback)
+    hipError_t enqueue_build(BuildPlan& p, BuildRequest& rq, size_t n_res, const ClampBox& cb, hipStream_t s, std::string* err, BuildFilter* filter);
     // Make room for `need_cells` cells (+1 start) after the device reported overflow.
     hipError_t grow_cells(uint64_t need_cells, std::string* err);
     // header.sum_sq_u <- sum over the cells of count^2 (enqueued; VGICP reads it back with the header)
