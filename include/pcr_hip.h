@@ -467,6 +467,21 @@ void pcr_sc_destroy(pcr_sc* sc);
 const char* pcr_sc_last_error(const pcr_sc* sc);
 int pcr_sc_size(const pcr_sc* sc, size_t* n);
 int pcr_sc_add(pcr_sc* sc, const void* pts, size_t n, size_t stride_bytes, int on_device);
+/* LoopClosureManager::addContext (backend/src/LoopClosureManager.cpp:28-37) over key frames [first, first + count) of a key-frame store, parent or
+ * view, in one batched pass: one context per key frame, in key-frame order, from the key frame's stored points in the lidar frame as
+ * pcr_map_keyframe returns them (its pose is not applied).  Every new context -- the row of the device store and the host's descriptor, ring key
+ * and sector key -- is bit for bit what pcr_map_keyframe -> pcr_voxel_filter at leaf grid_size -> pcr_sc_add of the filter's output leaves, so
+ * every reader (pcr_sc_descriptor, _distance, _query, _distances, _rank_stored, pcr_relocalize_global) works on it unchanged.  grid_size <= 0: no
+ * filter, the stored points are binned as they are (key frames already filtered by pcr_map_downsample_keyframes: a loaded map); the whole range is
+ * then one table up, one launch and one copy back, with no synchronisation per key frame.  grid_size > 0: the key frames pass the voxel filter one
+ * by one, on a handle the database creates at the first such call, into one packed buffer (room for the unfiltered points of the range), which is
+ * binned the same way; a key frame the filter returns unfiltered (a grid too fine for PCL's voxel index) is binned as returned.  A key frame of 0
+ * points adds an all-empty context, as pcr_sc_add with n = 0 does.  count == 0 succeeds and adds nothing; *n_added (may be NULL) = count.
+ * The device store grows straight to the capacity its doubling rule reaches for the new size: one allocation and one copy.
+ * Fails with a message in pcr_sc_last_error, the database left as it was (size, stored contexts, host entries), when sc or m is NULL (sc NULL:
+ * pcr_sc_last_error(NULL)), first + count exceeds pcr_map_keyframes(m), m is a view whose parent was destroyed, sc and m are on different devices,
+ * the store cannot grow, or on any HIP or filter error.  m is used as pcr_map_keyframe uses it: no call that changes the store may overlap. */
+int pcr_sc_add_keyframes(pcr_sc* sc, const pcr_map* m, size_t first, size_t count, double grid_size, size_t* n_added);
 int pcr_sc_descriptor(const pcr_sc* sc, size_t id, double* desc_row_major_20x60, double* ring_key_20, double* sector_key_60);
 int pcr_sc_distance(const pcr_sc* sc, size_t id1, size_t id2, double* dist, int* shift);
 int pcr_sc_query(pcr_sc* sc, long long id, long long* match, float* yaw_rad, double* min_dist);

@@ -399,6 +399,8 @@ uint32_t liorf_blocks(uint32_t n_src);
 struct RelocPart { double sum; uint32_t cnt, viol; };
 // the device a ScanContext database lives on (scancontext.hip)
 int sc_device(const pcr_sc* sc);
+// the device a key-frame store, or a view of one, lives on (submap.hip)
+int map_device(const pcr_map* m);
 struct RelocSum { double sum; unsigned long long cnt, viol, pad_; };
 hipError_t fitness_batch_launch(const GridIndex& grid, const float* d_src, size_t n_src, size_t stride_floats, size_t m, const float* d_poses,
                                 size_t n_poses, double max_sq, RelocPart* d_part, RelocSum* d_out, hipStream_t s);

@@ -10,11 +10,13 @@
 // against EVERY stored context, one wave per context (sc_rank_kernel), each sum in the host's order so that the result is the host's bit for bit.
 // pcr_sc_rank_stored does the same for stored queries against stored candidates -- lcHandler's walk over a range of key frames
 // (LoopClosureManager.cpp:73) -- in tiles of 8 queries x 128 candidates (sc_rank_stored_kernel), the k best per query merged in a fixed order.
+// pcr_sc_add_keyframes fills the database from a range of a key-frame store's key frames in one batched pass (sc_polar_batch_kernel).
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include <algorithm>
 #include <limits>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -115,6 +117,47 @@ __global__ __launch_bounds__(256) void sc_polar_kernel(const float* __restrict__
         if (!(isfinite(x) && isfinite(y) && z == z)) continue;   // the reference's int(ceil(NaN)) is undefined behaviour; a NaN z never wins its '<'
         if (!sc_bin(x, y, &ring, &sector)) continue;
         atomicMax(&desc[ring * kSectors + sector], z);
+    }
+}
+
+// ---- a range of stored key frames in one pass: pcr_sc_add_keyframes ----
+// LoopClosureManager::addContext (LoopClosureManager.cpp:28-37) walks the new key frames and bins each one's own cloud; here the walk is one launch.
+// Key frame f of the table has n points from float `off` behind pts and owns row f of `rows`.  A block bins one slab of kScSlab points of one
+// key frame (jobs[blockIdx.x]: the key frame and the slab's first point) into a descriptor in LDS -- sc_bin and the tests of sc_polar_kernel,
+// float max by LDS atomic -- and writes it out along the row: with plain stores when the key frame is that one slab (an empty key frame's one
+// block writes the empty row), else by the float atomic max of sc_polar_kernel onto a row preset to kNoPoint (sc_fill_kernel), bins the slab
+// left empty skipped.  The maximum of a set of floats does not depend on how the set is cut, so every row holds the bits sc_polar_kernel leaves.
+constexpr unsigned int kScSlab = 4096;
+struct ScKf { unsigned long long off; unsigned int n, pad_; };
+struct ScJob { unsigned int kf, start; };
+
+__global__ __launch_bounds__(256) void sc_fill_kernel(float* __restrict__ p, size_t n, float v) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = v;
+}
+
+__global__ __launch_bounds__(256) void sc_polar_batch_kernel(const float* __restrict__ pts, const ScKf* __restrict__ kfs, const ScJob* __restrict__ jobs,
+                                                             unsigned int stride, float lidar_height, float* __restrict__ rows) {
+    __shared__ float s_desc[kRings * kSectors];
+    const ScJob job = jobs[blockIdx.x];
+    const ScKf kf = kfs[job.kf];
+    for (int i = threadIdx.x; i < kRings * kSectors; i += 256) s_desc[i] = kNoPoint;
+    __syncthreads();
+    const unsigned int len = kf.n - job.start < kScSlab ? kf.n - job.start : kScSlab;      // (job.start < kf.n, or both 0)
+    const float* base = pts + kf.off + (size_t)job.start * stride;
+    for (unsigned int t = threadIdx.x; t < len; t += 256) {
+        const float* p = base + (size_t)t * stride;
+        const float x = p[0], y = p[1], z = p[2] + lidar_height;
+        int ring, sector;
+        if (!(isfinite(x) && isfinite(y) && z == z)) continue;   // as sc_polar_kernel
+        if (!sc_bin(x, y, &ring, &sector)) continue;
+        atomicMax(&s_desc[ring * kSectors + sector], z);
+    }
+    __syncthreads();
+    float* row = rows + (size_t)job.kf * (kRings * kSectors);
+    if (kf.n <= kScSlab) {
+        for (int i = threadIdx.x; i < kRings * kSectors; i += 256) row[i] = s_desc[i];
+    } else {
+        for (int i = threadIdx.x; i < kRings * kSectors; i += 256) { const float v = s_desc[i]; if (v != kNoPoint) atomicMax(&row[i], v); }
     }
 }
 
@@ -384,10 +427,21 @@ struct pcr_sc {
     double* d_keys = nullptr; size_t keys_cap = 0, keys_n = 0;
     void* d_part = nullptr; size_t part_cap = 0;
     void* d_rank = nullptr; size_t rank_cap = 0;
+    // pcr_sc_add_keyframes: the key-frame and block tables of one call; with a grid_size, the filter (a handle of its own, made by the first
+    // such call) and the filtered key frames packed one behind the other
+    void* d_tab = nullptr; size_t tab_cap = 0;
+    pcr_handle* filter = nullptr;
+    void* d_pack = nullptr; size_t pack_cap = 0;
     std::string err;
 };
 
-namespace pcr { int sc_device(const pcr_sc* sc) { return sc->device; } }      // (pcr_internal.h)
+namespace pcr {
+int sc_device(const pcr_sc* sc) { return sc->device; }      // (pcr_internal.h)
+int map_device(const pcr_map* m);                           // (submap.hip)
+}
+// (library-internal, voxel_host.hip) the voxel filter in two halves, device memory into device memory: what pcr_map_downsample_keyframes runs per key frame
+int pcr_internal_vf_begin(pcr_handle* h, const void* d_pts, size_t n, size_t stride_bytes, double leaf, void* d_out, size_t out_capacity);
+int pcr_internal_vf_end(pcr_handle* h, size_t* n_out);
 
 static thread_local std::string g_sc_err;
 static int scfail(pcr_sc* s, const std::string& m) { if (s) s->err = m; else g_sc_err = m; return 1; }
@@ -458,8 +512,9 @@ void pcr_sc_destroy(pcr_sc* sc) {
     if (!sc) return;
     (void)hipSetDevice(sc->device);
     for (void* p : {(void*)sc->d_desc, (void*)sc->d_stage, (void*)sc->d_db, (void*)sc->d_query, (void*)sc->d_qkeys, (void*)sc->d_dist, (void*)sc->d_shift,
-                    (void*)sc->d_keys, sc->d_part, sc->d_rank})
+                    (void*)sc->d_keys, sc->d_part, sc->d_rank, sc->d_tab, sc->d_pack})
         if (p) (void)hipFree(p);
+    if (sc->filter) pcr_destroy(sc->filter);
     delete sc;
 }
 
@@ -522,6 +577,36 @@ int sc_reserve_one(pcr_sc* sc) {
     return 0;
 }
 
+// What the host keeps of one binned row (1200 floats): the descriptor with empty bins as 0.0 (:186-190), ring key and sector key (:198-229),
+// each a sequential double sum in index order
+void sc_host_entry(const float* row, Desc& d, std::vector<double>& rk, std::vector<double>& sk) {
+    for (int i = 0; i < kRings * kSectors; ++i) d.m[i] = row[i] == kNoPoint ? 0.0 : (double)row[i];
+    for (int r = 0; r < kRings; ++r) { double s = 0; for (int c = 0; c < kSectors; ++c) s += d.m[r * kSectors + c]; rk[r] = s / kSectors; }
+    for (int c = 0; c < kSectors; ++c) { double s = 0; for (int r = 0; r < kRings; ++r) s += d.m[r * kSectors + c]; sk[c] = s / kRings; }
+}
+
+// Room for `more` contexts behind the stored ones: the capacity the doubling above arrives at, reached with one allocation and one copy.
+int sc_reserve_more(pcr_sc* sc, size_t more) {
+    const size_t n = sc->polar.size(), per = (size_t)kRings * kSectors * sizeof(float);
+    if (more > std::numeric_limits<size_t>::max() / (4 * per) - n) return scfail(sc, "too many contexts");
+    if (n + more <= sc->db_cap) return 0;
+    size_t cap = sc->db_cap;
+    while (cap < n + more) cap = std::max<size_t>(64, 2 * cap);
+    float* p = nullptr;
+    const hipError_t e = hipMalloc((void**)&p, cap * per);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return scfail(sc, "the device store of " + std::to_string(n) + " contexts cannot grow to " + std::to_string(cap) + ": " + hipGetErrorString(e));
+    }
+    if (n) {
+        const hipError_t c = hipMemcpy(p, sc->d_db, n * per, hipMemcpyDeviceToDevice);
+        if (c != hipSuccess) { (void)hipFree(p); return scfail(sc, std::string("growing the device store: ") + hipGetErrorString(c)); }
+    }
+    if (sc->d_db) (void)hipFree(sc->d_db);
+    sc->d_db = p; sc->db_cap = cap;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -536,10 +621,8 @@ int pcr_sc_add(pcr_sc* sc, const void* pts, size_t n, size_t stride_bytes, int o
     float host[kRings * kSectors];
     S_TRY(hipMemcpy(host, sc->d_desc, sizeof host, hipMemcpyDeviceToHost));
     Desc d;
-    for (int i = 0; i < kRings * kSectors; ++i) d.m[i] = host[i] == kNoPoint ? 0.0 : (double)host[i];      // :186-190
     std::vector<double> rk(kRings), sk(kSectors);
-    for (int r = 0; r < kRings; ++r) { double s = 0; for (int c = 0; c < kSectors; ++c) s += d.m[r * kSectors + c]; rk[r] = s / kSectors; }
-    for (int c = 0; c < kSectors; ++c) { double s = 0; for (int r = 0; r < kRings; ++r) s += d.m[r * kSectors + c]; sk[c] = s / kRings; }
+    sc_host_entry(host, d, rk, sk);
     sc->polar.push_back(d); sc->ring.push_back(rk); sc->sector.push_back(sk);
     return 0;
 }
@@ -643,6 +726,109 @@ int sc_keys_upto(pcr_sc* sc, size_t n) {
 }  // namespace
 
 extern "C" {
+
+/* LoopClosureManager::addContext (LoopClosureManager.cpp:28-37) over key frames [first, first + count) of a key-frame store: every stage once for the
+ * range -- one table up, one binning launch (sc_polar_batch_kernel) into the rows of the device store, one copy of those rows back, keys on the host
+ * as pcr_sc_add takes them.  With a grid_size the key frames first pass the voxel filter one by one (its centroids depend on its own summation order:
+ * voxel_filter.hip) into one packed buffer, which is then binned the same way. */
+int pcr_sc_add_keyframes(pcr_sc* sc, const pcr_map* m, size_t first, size_t count, double grid_size, size_t* n_added) {
+    if (!sc) return scfail(nullptr, "pcr_sc_add_keyframes: sc is NULL");
+    sc->err.clear();
+    if (!m) return scfail(sc, "pcr_sc_add_keyframes: map is NULL");
+    size_t n_kf = 0;
+    if (pcr_map_keyframes(m, &n_kf)) return scfail(sc, std::string("pcr_sc_add_keyframes: ") + pcr_map_last_error(m));
+    if (first > n_kf || count > n_kf - first)
+        return scfail(sc, "pcr_sc_add_keyframes: first + count = " + std::to_string(first) + " + " + std::to_string(count) + " exceeds the " + std::to_string(n_kf) + " key frames");
+    if (pcr::map_device(m) != sc->device)
+        return scfail(sc, "pcr_sc_add_keyframes: the map is on device " + std::to_string(pcr::map_device(m)) + ", the database on device " + std::to_string(sc->device));
+    if (count == 0) { if (n_added) *n_added = 0; return 0; }
+    if (count > 0x7fffff00ull) return scfail(sc, "too many key frames in one call");
+    S_TRY(hipSetDevice(sc->device));
+    const size_t n0 = sc->polar.size(), per = (size_t)kRings * kSectors;
+    try {
+        // the key frames as pcr_map_keyframe hands them out
+        std::vector<const float*> src(count);
+        std::vector<size_t> src_n(count);
+        size_t stride = 0, total = 0;
+        for (size_t i = 0; i < count; ++i) {
+            src[i] = static_cast<const float*>(pcr_map_keyframe(m, first + i, &src_n[i], &stride, nullptr));
+            if (!src[i] && src_n[i]) return scfail(sc, std::string("pcr_sc_add_keyframes: ") + pcr_map_last_error(m));
+            if (src_n[i] > 0xfffffff0ull) return scfail(sc, "cloud too large");
+            total += src_n[i];
+        }
+        if (stride < 12 || stride % 4) return scfail(sc, "stride_bytes must be a multiple of 4 and >= 12");
+        const size_t sf = stride / 4;
+        std::vector<ScKf> kfs(count);
+        const float* base = nullptr;
+        if (grid_size > 0 && total) {
+            // every key frame through the filter, one behind the other (room for the unfiltered sizes: a grid too fine for a key frame returns it as it is)
+            if (!sc->filter) {
+                pcr_params p;
+                pcr_default_params(&p);
+                p.device = sc->device;
+                sc->filter = pcr_create("loam", &p);
+                if (!sc->filter) return scfail(sc, std::string("pcr_sc_add_keyframes: ") + pcr_last_error(nullptr));
+            }
+            if (sc_room(sc, &sc->d_pack, &sc->pack_cap, total * stride)) return 1;
+            float* pack = static_cast<float*>(sc->d_pack);
+            size_t w = 0;
+            for (size_t i = 0; i < count; ++i) {
+                size_t n_out = 0;
+                if (src_n[i] && (pcr_internal_vf_begin(sc->filter, src[i], src_n[i], stride, grid_size, pack + w * sf, src_n[i]) || pcr_internal_vf_end(sc->filter, &n_out)))
+                    return scfail(sc, std::string("voxel filter: ") + pcr_last_error(sc->filter));
+                kfs[i] = ScKf{(unsigned long long)(w * sf), (unsigned int)n_out, 0};
+                w += n_out;
+            }
+            base = pack;
+        } else {
+            for (size_t i = 0; i < count; ++i) if (src[i] && (!base || src[i] < base)) base = src[i];
+            for (size_t i = 0; i < count; ++i) kfs[i] = ScKf{src[i] ? (unsigned long long)(src[i] - base) : 0ull, (unsigned int)src_n[i], 0};
+        }
+        // a block per slab, at least one per key frame
+        std::vector<ScJob> jobs;
+        jobs.reserve(count);
+        bool shared_rows = false;
+        for (size_t i = 0; i < count; ++i) {
+            jobs.push_back(ScJob{(unsigned int)i, 0});
+            for (size_t s = kScSlab; s < kfs[i].n; s += kScSlab) jobs.push_back(ScJob{(unsigned int)i, (unsigned int)s});
+            shared_rows |= kfs[i].n > kScSlab;
+        }
+        if (jobs.size() > 0x7fffffffull) return scfail(sc, "too many points in one call");
+        const size_t kf_bytes = count * sizeof(ScKf), job_bytes = jobs.size() * sizeof(ScJob);
+        if (sc_room(sc, &sc->d_tab, &sc->tab_cap, kf_bytes + job_bytes)) return 1;
+        std::vector<char> tab(kf_bytes + job_bytes);
+        std::copy(reinterpret_cast<const char*>(kfs.data()), reinterpret_cast<const char*>(kfs.data()) + kf_bytes, tab.begin());
+        std::copy(reinterpret_cast<const char*>(jobs.data()), reinterpret_cast<const char*>(jobs.data()) + job_bytes, tab.begin() + kf_bytes);
+        std::vector<float> host(count * per);
+        sc->polar.reserve(n0 + count); sc->ring.reserve(n0 + count); sc->sector.reserve(n0 + count);
+        S_TRY(hipMemcpy(sc->d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice));
+        if (sc_reserve_more(sc, count)) return 1;
+        float* rows = sc->d_db + n0 * per;
+        if (shared_rows) {
+            hipLaunchKernelGGL(sc_fill_kernel, dim3((unsigned int)std::min<size_t>((count * per + 255) / 256, 4096)), dim3(256), 0, 0, rows, count * per, kNoPoint);
+            S_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(sc_polar_batch_kernel, dim3((unsigned int)jobs.size()), dim3(256), 0, 0, base, static_cast<const ScKf*>(sc->d_tab),
+                           reinterpret_cast<const ScJob*>(static_cast<const char*>(sc->d_tab) + kf_bytes), (unsigned int)sf, (float)sc->prm.lidar_height, rows);
+        S_TRY(hipGetLastError());
+        S_TRY(hipMemcpy(host.data(), rows, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+        try {
+            std::vector<double> rk(kRings), sk(kSectors);
+            for (size_t i = 0; i < count; ++i) {
+                sc->polar.emplace_back();
+                sc_host_entry(host.data() + i * per, sc->polar.back(), rk, sk);
+                sc->ring.push_back(rk); sc->sector.push_back(sk);
+            }
+        } catch (const std::bad_alloc&) {
+            sc->polar.resize(n0); sc->ring.resize(n0); sc->sector.resize(n0);
+            throw;
+        }
+    } catch (const std::bad_alloc&) {
+        return scfail(sc, "pcr_sc_add_keyframes: out of host memory");
+    }
+    if (n_added) *n_added = count;
+    return 0;
+}
 
 /* distanceBtnScanContext of stored queries [first, first + count) against every older stored context, the k best each (sc_rank_stored_kernel) */
 int pcr_sc_rank_stored(pcr_sc* sc, size_t first, size_t count, int k, int64_t* idx, double* dist, int32_t* shift) {

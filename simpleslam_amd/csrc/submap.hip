@@ -127,6 +127,7 @@ static thread_local std::string g_map_err;
 static int mfail(pcr_map* m, const std::string& s) { if (m) m->err = s; else g_map_err = s; return 1; }
 static int mfail(const pcr_map* m, const std::string& s) { return mfail(const_cast<pcr_map*>(m), s); }
 static const pcr_map* store_of(const pcr_map* m) { return m->parent ? m->parent : m; }
+namespace pcr { int map_device(const pcr_map* m) { return m->device; } }      // (pcr_internal.h: the device a store, or a view of one, lives on)
 // every entry point but pcr_map_destroy: a view that outlived its parent has no store to read
 #define M_ALIVE(m) do { if ((m)->detached) return mfail(m, "parent destroyed: this view can only be destroyed"); } while (0)
 #define M_OWNER(m, what) do { if ((m)->parent) return mfail(m, std::string(what) + ": this pcr_map is a view (pcr_map_view) and cannot change the store; call it on the parent"); } while (0)

@@ -549,6 +549,13 @@ public:
     void addContext(const PCR::PointCloud& scan_down) {
         if (pcr_sc_add(s_, scan_down.points.data(), scan_down.size(), sizeof(PCR::PointXYZI), 0)) throw std::runtime_error(pcr_sc_last_error(s_));
     }
+    // LoopClosureManager::addContext (LoopClosureManager.cpp:28-37) over stored key frames [first, first + count) of a SubMap (or a view of one) in
+    // one batched pass (pcr_sc_add_keyframes): each key frame's own cloud, voxel-filtered at grid_size when that is positive -> contexts added
+    size_t addKeyFrames(const PCR::SubMap& map, size_t first, size_t count, double grid_size = 0) {
+        size_t n = 0;
+        if (pcr_sc_add_keyframes(s_, map.handle(), first, count, grid_size, &n)) throw std::runtime_error(pcr_sc_last_error(s_));
+        return n;
+    }
     QueryResult query(int id) {
         long long match = -1;
         float yaw = 0;

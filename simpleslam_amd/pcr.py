@@ -82,7 +82,7 @@ ABI_SYMBOLS = [
     "pcr_sc_default_params", "pcr_sc_create", "pcr_sc_destroy", "pcr_sc_last_error", "pcr_sc_size", "pcr_sc_add", "pcr_sc_descriptor", "pcr_sc_distance",
     "pcr_sc_query", "pcr_knn", "pcr_radius_search", "pcr_fitness_batch", "pcr_reloc_default_params", "pcr_reloc_hypotheses", "pcr_relocalize",
     "pcr_sc_distances", "pcr_global_reloc_default_params", "pcr_global_reloc_hypotheses", "pcr_relocalize_global",
-    "pcr_sc_rank_stored", "pcr_sc_shift_yaw",
+    "pcr_sc_rank_stored", "pcr_sc_shift_yaw", "pcr_sc_add_keyframes",
     "pcr_liorf_pose_to_6dof", "pcr_liorf_6dof_to_pose", "pcr_liorf_linearize", "pcr_liorf_result",
     "pcr_pose_to_mobile", "pcr_frontend_default_params", "pcr_frontend_create", "pcr_frontend_destroy", "pcr_frontend_last_error", "pcr_frontend_step",
     "pcr_frontend_prefetch", "pcr_frontend_finish", "pcr_frontend_reset",
@@ -261,6 +261,7 @@ def load_library():
     L.pcr_sc_last_error.restype = C.c_char_p
     L.pcr_sc_size.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.pcr_sc_add.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
+    L.pcr_sc_add_keyframes.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(C.c_size_t)]
     L.pcr_sc_descriptor.argtypes = [vp, C.c_size_t, vp, vp, vp]
     L.pcr_sc_distance.argtypes = [vp, C.c_size_t, C.c_size_t, dp, ip]
     L.pcr_sc_query.argtypes = [vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_float), dp]
@@ -1297,6 +1298,20 @@ class ScanContext:
     def addContext(self, cloud):
         p, n, s, dev, _keep = _cloud(cloud)
         self._check(self._lib.pcr_sc_add(self._s, p, n, s, dev))
+
+    def addKeyFrames(self, submap, first=0, count=None, grid_size=0.0):
+        """pcr_sc_add_keyframes: one context per stored key frame of [first, first + count) of a SubMap or a view of one (count=None: to the
+        last one), in one batched pass on the device -- what keyFramePointer -> voxelDownSample(grid_size) -> addContext leaves for each,
+        bit for bit; grid_size <= 0 bins the stored points as they are.  -> the number of contexts added."""
+        first = int(first)
+        if count is None:
+            count = max(submap.keyframes() - first, 0) if submap is not None else 0      # (a missing map, a first past the end: the library's to refuse)
+        count = int(count)
+        if first < 0 or count < 0:
+            raise PcrError("first and count must not be negative")
+        n = C.c_size_t(0)
+        self._check(self._lib.pcr_sc_add_keyframes(self._s, submap._m if submap is not None else None, first, count, float(grid_size), C.byref(n)))
+        return n.value
 
     def __len__(self):
         n = C.c_size_t(0)
