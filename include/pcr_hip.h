@@ -508,6 +508,86 @@ int pcr_sc_rank_stored(pcr_sc* sc, size_t first, size_t count, int k, int64_t* i
 /* Host-only: the yaw of a match, trans::deg2rad<float>(6 degrees * shift), as pcr_sc_query forms it. */
 float pcr_sc_shift_yaw(int32_t shift);
 
+/* ---- the pose-graph back end: Backend::optimHandler (backend/src/Backend.cpp:224-347), on the device ----
+ * An SE(3) pose graph of prior and between factors, optimised by Levenberg-Marquardt whose linear solve is a preconditioned conjugate
+ * gradient that runs wholly on the device.  GTSAM is not reproduced bit for bit; the contract is this definition:
+ *   poses     16 doubles, column-major, like every pose of this header.  Tangent vectors are [omega; v], rotation first (GTSAM's Pose3 order);
+ *             the update is X <- X Exp(delta) with the full SE(3) exponential.
+ *   between   (from, to, Z, Omega): r = Log(Z^-1 X_from^-1 X_to).        prior (id, P, Omega): r = Log(P^-1 X_id).
+ *   Omega     a full symmetric 6x6 information matrix in [omega; v] order, passed as its 21 upper-triangular entries, row by row.
+ *   cost      1/2 sum r^T Omega r;  chi2 = sum r^T Omega r.  Jacobians are exact (the inverse right Jacobian of SE(3)).
+ *   optimiser (H + lambda I) delta = -g, H = sum J^T Omega J.  A step is accepted when chi2 falls; lambda is divided by lambda_factor on
+ *             acceptance and multiplied on rejection.  It stops when an accepted step lowered chi2 by less than abs_tol or by less than
+ *             rel_tol * chi2 (converged), when a rejected step raised chi2 by less than abs_tol (converged), when lambda exceeds
+ *             lambda_max, or after max_iterations trial steps.
+ * Ids are positions: the poses are numbered from 0 in the order they were added.  Factors may be added before their poses; the graph is
+ * checked when it is used.  A pcr_graph is used by one thread at a time. */
+typedef struct pcr_graph pcr_graph;
+#define PCR_GRAPH_HOST (-2)
+enum { PCR_GRAPH_PRIOR = 0, PCR_GRAPH_ODOM = 1, PCR_GRAPH_LOOP = 2 };
+typedef struct pcr_graph_params {
+    uint32_t struct_size;          /* sizeof(pcr_graph_params), set by pcr_graph_default_params */
+    int32_t max_iterations;        /* 100: trial steps (GTSAM's LevenbergMarquardtParams defaults throughout) */
+    double rel_tol, abs_tol;       /* 1e-5, 1e-5 */
+    double lambda_init, lambda_factor, lambda_max;      /* 1e-5, 10, 1e5 */
+    int64_t pcg_max_iterations;    /* 0 = max(100, 10 * poses) */
+    double pcg_rel_tol;            /* 1e-10, on |residual| / |g| */
+} pcr_graph_params;
+typedef struct pcr_graph_result {
+    int32_t iterations, accepted;  /* trial steps (one linear solve each); those that were accepted */
+    int64_t pcg_iterations;        /* over all solves */
+    int32_t pcg_capped;            /* solves that pcg_max_iterations ended */
+    int32_t converged;
+    double chi2_initial, chi2_final, lambda;
+    double delta[16];              /* X_last after * X_last before ^-1 for the highest id, re-orthonormalised as trans::T2SE3 does: what optimHandler
+                                      hands to the front end (Backend.cpp:321-346) */
+} pcr_graph_result;
+/* device: an ordinal, -1 = current, PCR_GRAPH_HOST = no device at all (everything but optimize and apply works; linearize runs on the host
+ * through the same header the kernels compile).  NULL on failure (pcr_graph_last_error(NULL)). */
+pcr_graph* pcr_graph_create(int device);
+void pcr_graph_destroy(pcr_graph* g);
+const char* pcr_graph_last_error(const pcr_graph* g);
+/* The reference's three diagonal noise models (Backend.cpp:90-97; variances, so Omega = diag(1 / variance)):
+ * PRIOR 1e-2 1e-2 pi/72 1e-1 1e-1 1e-1, ODOM 1e-4 x3 1e-1 x3, LOOP 1e-1 x6.  Nonzero for another kind. */
+int pcr_graph_noise(int kind, double info21[21]);
+int pcr_graph_add_poses(pcr_graph* g, const double* poses16, size_t count);         /* ids are consecutive from 0 */
+int pcr_graph_add_prior(pcr_graph* g, size_t id, const double pose[16], const double info21[21]);
+int pcr_graph_add_between(pcr_graph* g, size_t from, size_t to, const double z[16], const double info21[21]);
+/* z = X_from^-1 X_to of the current estimates (Backend::addOdomFactor, Backend.cpp:241-247); both ids must exist */
+int pcr_graph_add_between_poses(pcr_graph* g, size_t from, size_t to, const double info21[21]);
+int pcr_graph_size(const pcr_graph* g, size_t* n_poses, size_t* n_priors, size_t* n_between);
+int pcr_graph_clear(pcr_graph* g);
+void pcr_graph_default_params(pcr_graph_params* p);
+/* Refused with a message, before anything is solved: an id out of range; a between factor with from == to; a pose, a measurement or an
+ * information matrix that is not finite; a connected component that holds no prior (the message names its first pose); a PCR_GRAPH_HOST
+ * graph.  Duplicate edges are allowed and add up.  An empty graph returns 0 and does nothing; so does (0 iterations, converged = 1) a graph
+ * to which nothing was added since an optimize that converged under tolerances no looser than this call's -- one that ran out of iterations
+ * or of lambda, or converged under looser tolerances, goes on from the current estimates.  params == NULL: the defaults; result may be NULL.  Per trial step one launch holds the whole
+ * conjugate-gradient loop (bounded on the device by pcg_max_iterations) and 24 bytes come back to the host. */
+int pcr_graph_optimize(pcr_graph* g, const pcr_graph_params* params, pcr_graph_result* result);
+int pcr_graph_poses(const pcr_graph* g, size_t first, size_t count, double* poses16);
+/* The current estimates in device memory, *n of them, 16 doubles each (valid until the next call that adds poses or optimises); NULL on a host
+ * graph.  Uploads poses added since the last use and reads no factor: it serves a graph whose factors name poses that do not exist yet. */
+const double* pcr_graph_device_poses(const pcr_graph* g, size_t* n);
+/* Introspection: every factor linearised at the current estimates, priors first, then betweens, each in the order added: r [E][6],
+ * j_from = dr/d(delta_from) and j_to = dr/d(delta_to) [E][36] row-major (a prior's j_from is zero), *chi2.  Any pointer may be NULL.
+ * A device graph runs the optimiser's kernel, a PCR_GRAPH_HOST graph the same code on the host: the two agree bit for bit. */
+int pcr_graph_linearize(pcr_graph* g, double* r, double* j_from, double* j_to, double* chi2);
+/* Introspection (device graphs): y = (H + lambda I) x at the current estimates, x and y 6 doubles per pose, by the solve kernel's own product. */
+int pcr_graph_apply(pcr_graph* g, double lambda, const double* x, double* y);
+/* Poses first .. first+count-1 of the graph become the poses of key frames first .. first+count-1 of the store, read from the graph's device
+ * memory.  The store keeps its pose table on the HOST (beside the key frames' offsets), so this is one device-to-host copy inside the library,
+ * not a device-to-device one; what it spares is the caller's buffer and second call.  The bits pcr_map_set_poses would store from pcr_graph_poses, with its rules (a parent, not a view; no generation moves).  Refused
+ * when the two are on different devices (a host graph is on none) or when either holds fewer than first + count entries. */
+int pcr_map_set_poses_from_graph(pcr_map* m, const pcr_graph* g, size_t first, size_t count);
+/* g2o text files: VERTEX_SE3:QUAT and EDGE_SE3:QUAT as Backend::Gtsam::myReadG2o reads them (Backend.cpp:148-193): vertex ids consecutive
+ * (continuing the graph's), the information matrix mirrored to both triangles, its translation and rotation blocks swapped into [omega; v]
+ * order and its off-diagonal blocks taken as they stand (not transposed, as there); the PRIOR preset is added on vertex 0.  VERTEX3 and EDGE3
+ * are refused with a message; other records are skipped.  A file that is refused leaves the graph as it was.  save writes the poses and the
+ * between factors with 17 significant digits (no priors: they are the reader's own). */
+int pcr_graph_load_g2o(pcr_graph* g, const char* path);
+int pcr_graph_save_g2o(const pcr_graph* g, const char* path);
+
 /* The NDT optimiser on its own (host only, no GPU): pclomp's computeTransformation + computeStepLengthMT (ndt_omp_impl.hpp:81-171,
  * 735-932) as the state machine that pcr_scan2map runs on the device (csrc/ndt_opt.h), driven from outside -- the caller evaluates what
  * it asks for and feeds the 43 sums back.  An introspection entry point like pcr_ndt_derivatives: the CPU test suite drives it with the

@@ -1,0 +1,315 @@
+// graph.hip -- the pose-graph back end's kernels (gfx950): linearise, solve, retract.  DESIGN.md 4.17.
+//
+// Backend::optimHandler (backend/src/Backend.cpp:224-347 of the reference) relinearises a GTSAM graph of one prior and one BetweenFactor per key
+// frame and per loop on every key-frame event.  Here the graph lives in HBM: one launch linearises every factor (one factor per lane), one
+// launch holds the whole preconditioned conjugate gradient of a Levenberg-Marquardt trial step on ONE workgroup, one launch retracts.
+// No atomics anywhere: every sum is taken in a fixed order, so the same graph gives the same bits on every run.
+#include "graph_dev.h"
+#include "graph_math.h"
+
+namespace pcr {
+namespace graph {
+
+namespace {
+
+// sum over the wave, in lane 0 (a fixed tree: 32, 16, 8, 4, 2, 1)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// ---- linearise: the whole grid, one factor per lane --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kLinBlock) void graph_linearize_kernel(const double* __restrict__ poses, const Factors f, const Lin out,
+                                                                    double* __restrict__ partial) {
+    __shared__ double wsum[kLinBlock / 64];
+    const int F = f.F;
+    const int e = blockIdx.x * kLinBlock + threadIdx.x;
+    double c = 0.0;
+    if (e < F) {
+        const int from = f.from[e], to = f.to[e];
+        double Xi[16], Xj[16], Z[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            Xj[k] = poses[(size_t)to * 16 + k];
+            Xi[k] = (from >= 0) ? poses[(size_t)from * 16 + k] : 0.0;
+            Z[k] = f.z[(size_t)k * F + e];
+        }
+        double r[6], Jf[36], Jt[36];
+        gm::factor_linearize(from >= 0, Xi, Xj, Z, r, Jf, Jt);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            double o[6];
+#pragma unroll
+            for (int m = 0; m < 6; ++m) o[m] = f.omega[(size_t)(k * 6 + m) * F + e];
+            double w = 0.0;
+#pragma unroll
+            for (int m = 0; m < 6; ++m) w += o[m] * r[m];
+            out.r[(size_t)k * F + e] = r[k];
+            out.wr[(size_t)k * F + e] = w;
+            c += r[k] * w;
+#pragma unroll
+            for (int b = 0; b < 6; ++b) {
+                double sf = 0.0, st = 0.0;
+#pragma unroll
+                for (int m = 0; m < 6; ++m) { sf += o[m] * Jf[m * 6 + b]; st += o[m] * Jt[m * 6 + b]; }
+                out.wjf[(size_t)(k * 6 + b) * F + e] = sf;
+                out.wjt[(size_t)(k * 6 + b) * F + e] = st;
+                out.jf[(size_t)(k * 6 + b) * F + e] = Jf[k * 6 + b];
+                out.jt[(size_t)(k * 6 + b) * F + e] = Jt[k * 6 + b];
+            }
+        }
+        out.c[e] = c;
+    }
+    // chi2: lanes past the end add 0; the wave's tree, then the block's four waves in order
+    const double ws = wave_sum(c);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = ws;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// one wave folds the blocks' partial sums: lane l takes blocks l, l + 64, ... in that order, then the tree
+__global__ __launch_bounds__(64) void graph_chi2_fold_kernel(const double* __restrict__ partial, int n_blocks, double* __restrict__ status) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < n_blocks; b += 64) s += partial[b];
+    s = wave_sum(s);
+    if (threadIdx.x == 0) status[0] = s;
+}
+
+// ---- the two passes of y = (H + lambda I) x, shared by the solve and by pcr_graph_apply --------------------------------------------------
+// pass 1, over the factors: u_e = J_from x_from + J_to x_to
+__device__ __forceinline__ void edge_pass(const Factors& f, const Lin& lin, const double* __restrict__ x, double* __restrict__ u, int tid, int nthreads) {
+    const int F = f.F;
+    for (int e = tid; e < F; e += nthreads) {
+        const int from = f.from[e], to = f.to[e];
+        double xt[6], xf[6], acc[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { xt[k] = x[(size_t)to * 6 + k]; xf[k] = (from >= 0) ? x[(size_t)from * 6 + k] : 0.0; }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            double s = 0.0;
+#pragma unroll
+            for (int m = 0; m < 6; ++m) s += lin.jt[(size_t)(k * 6 + m) * F + e] * xt[m];
+            if (from >= 0) {
+#pragma unroll
+                for (int m = 0; m < 6; ++m) s += lin.jf[(size_t)(k * 6 + m) * F + e] * xf[m];
+            }
+            acc[k] = s;
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) u[(size_t)e * 6 + k] = acc[k];
+    }
+}
+
+// pass 2, one pose: y_p = lambda x_p + sum over p's incident factors, in CSR order, of (Omega J_p)^T u_e
+__device__ __forceinline__ void pose_product(int p, const Factors& f, const Lin& lin, const Csr& csr, double lambda, const double* xp,
+                                             const double* __restrict__ u, double* y) {
+    const int F = f.F;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) y[k] = lambda * xp[k];
+    const int lo = csr.row_ptr[p], hi = csr.row_ptr[p + 1];
+    for (int i = lo; i < hi; ++i) {
+        const int ent = csr.ent[i];
+        const int e = ent >> 1;
+        const double* __restrict__ wj = (ent & 1) ? lin.wjt : lin.wjf;
+        double ue[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) ue[k] = u[(size_t)e * 6 + k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+#pragma unroll
+            for (int m = 0; m < 6; ++m) y[m] += wj[(size_t)(k * 6 + m) * F + e] * ue[k];
+        }
+    }
+}
+
+// block-wide sums of NV values, the same bits in every thread: the wave's tree, then the 16 waves in order.  `lds` holds NV * 16 doubles and is
+// not written again before another barrier has passed (the call sites alternate between two arrays).
+template <int NV>
+__device__ __forceinline__ void block_sum(double (&v)[NV], double* lds) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const double s = wave_sum(v[i]);
+        if ((threadIdx.x & 63) == 0) lds[i * 16 + (threadIdx.x >> 6)] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < kSolveThreads / 64; ++w) s += lds[i * 16 + w];
+        v[i] = s;
+    }
+}
+
+// ---- solve: the whole PCG of one trial step on one workgroup ------------------------------------------------------------------------------
+// (H + lambda I) x = -g with H = sum J^T Omega J, g = sum J^T Omega r; preconditioner: the inverse of every pose's 6x6 diagonal block.
+// Threads stride over the poses and over the factors.  Writes are made visible to the workgroup by the barriers: one workgroup is one CU.
+__global__ __launch_bounds__(kSolveThreads) void graph_solve_kernel(const int N, const Factors f, const Lin lin, const Csr csr, const double lambda,
+                                                                    const int max_it, const double tol, const SolveBufs b, double* __restrict__ status) {
+    __shared__ double red_a[2 * 16], red_b[2 * 16];
+    const int tid = threadIdx.x;
+    const int F = f.F;
+
+    // set-up: g_p, the diagonal block, its Cholesky factor; x = 0, res = -g, z = M^-1 res, dir = z
+    double acc[2] = {0.0, 0.0};      // |g|^2, res . z
+    for (int p = tid; p < N; p += kSolveThreads) {
+        double g[6], D[21];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) g[k] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) D[gm::tri(i, j)] = (i == j) ? lambda : 0.0;
+        const int lo = csr.row_ptr[p], hi = csr.row_ptr[p + 1];
+        for (int i = lo; i < hi; ++i) {
+            const int ent = csr.ent[i];
+            const int e = ent >> 1;
+            const double* __restrict__ J = (ent & 1) ? lin.jt : lin.jf;
+            const double* __restrict__ WJ = (ent & 1) ? lin.wjt : lin.wjf;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {      // row k of J and of Omega J: a rank-one update of the block, one term of g
+                double jr[6], wr6[6];
+#pragma unroll
+                for (int m = 0; m < 6; ++m) { jr[m] = J[(size_t)(k * 6 + m) * F + e]; wr6[m] = WJ[(size_t)(k * 6 + m) * F + e]; }
+                const double wrk = lin.wr[(size_t)k * F + e];
+#pragma unroll
+                for (int m = 0; m < 6; ++m) g[m] += jr[m] * wrk;
+#pragma unroll
+                for (int r = 0; r < 6; ++r)
+#pragma unroll
+                    for (int c = 0; c <= r; ++c) D[gm::tri(r, c)] += jr[r] * wr6[c];
+            }
+        }
+        gm::chol6(D);
+        double res[6], z[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) res[k] = -g[k];
+        gm::chol6_solve(D, res, z);
+#pragma unroll
+        for (int k = 0; k < 21; ++k) b.L[(size_t)p * 21 + k] = D[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            b.x[(size_t)p * 6 + k] = 0.0;
+            b.res[(size_t)p * 6 + k] = res[k];
+            b.dir[(size_t)p * 6 + k] = z[k];
+            acc[0] += g[k] * g[k];
+            acc[1] += res[k] * z[k];
+        }
+    }
+    block_sum(acc, red_b);
+    const double gnorm = sqrt(acc[0]);
+    double rz = acc[1];
+    double relres = (gnorm > 0.0) ? 1.0 : 0.0;
+    int it = 0, flag = (gnorm > 0.0) ? 1 : 0;      // (1 until the tolerance is met: a loop that runs out was ended by the cap)
+    if (gnorm > 0.0 && relres <= tol) flag = 0;
+
+    while (flag == 1 && it < max_it) {
+        // (a barrier stands between the writes of dir and this pass: the set-up's block_sum on entry, the loop's own afterwards)
+        edge_pass(f, lin, b.dir, b.u, tid, kSolveThreads);
+        __syncthreads();
+        double pap[1] = {0.0};
+        for (int p = tid; p < N; p += kSolveThreads) {
+            double d[6], y[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) d[k] = b.dir[(size_t)p * 6 + k];
+            pose_product(p, f, lin, csr, lambda, d, b.u, y);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) { b.ap[(size_t)p * 6 + k] = y[k]; pap[0] += d[k] * y[k]; }
+        }
+        block_sum(pap, red_a);
+        if (!(pap[0] > 0.0)) { flag = 2; break; }
+        const double alpha = rz / pap[0];
+        double nn[2] = {0.0, 0.0};      // res . z, |res|^2 after the update
+        for (int p = tid; p < N; p += kSolveThreads) {
+            double res[6], z[6], L[21];
+#pragma unroll
+            for (int k = 0; k < 21; ++k) L[k] = b.L[(size_t)p * 21 + k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                b.x[(size_t)p * 6 + k] += alpha * b.dir[(size_t)p * 6 + k];
+                res[k] = b.res[(size_t)p * 6 + k] - alpha * b.ap[(size_t)p * 6 + k];
+                b.res[(size_t)p * 6 + k] = res[k];
+            }
+            gm::chol6_solve(L, res, z);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) { b.z[(size_t)p * 6 + k] = z[k]; nn[0] += res[k] * z[k]; nn[1] += res[k] * res[k]; }
+        }
+        block_sum(nn, red_b);
+        ++it;
+        relres = sqrt(nn[1]) / gnorm;
+        if (!(relres > tol)) { flag = 0; break; }      // (a residual that is not a number ends the loop too: the host sees it in relres)
+        const double beta = nn[0] / rz;
+        rz = nn[0];
+        for (int p = tid; p < N; p += kSolveThreads) {      // every thread updates the poses it owns: nobody else reads dir before the next barrier
+#pragma unroll
+            for (int k = 0; k < 6; ++k) b.dir[(size_t)p * 6 + k] = b.z[(size_t)p * 6 + k] + beta * b.dir[(size_t)p * 6 + k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        status[1] = relres;
+        int* w = reinterpret_cast<int*>(status + 2);
+        w[0] = it;
+        w[1] = flag;
+    }
+}
+
+__global__ __launch_bounds__(kSolveThreads) void graph_apply_kernel(const int N, const Factors f, const Lin lin, const Csr csr, const double lambda,
+                                                                    const double* __restrict__ x, double* __restrict__ y, double* __restrict__ u) {
+    edge_pass(f, lin, x, u, threadIdx.x, kSolveThreads);
+    __syncthreads();
+    for (int p = threadIdx.x; p < N; p += kSolveThreads) {
+        double xp[6], yp[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) xp[k] = x[(size_t)p * 6 + k];
+        pose_product(p, f, lin, csr, lambda, xp, u, yp);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) y[(size_t)p * 6 + k] = yp[k];
+    }
+}
+
+// ---- retract: X_trial = X Exp(delta) ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void graph_retract_kernel(const int N, const double* __restrict__ poses, const double* __restrict__ delta,
+                                                            double* __restrict__ out) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= N) return;
+    double X[16], d[6], E[16], Y[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) X[k] = poses[(size_t)p * 16 + k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) d[k] = delta[(size_t)p * 6 + k];
+    gm::se3_exp(d, E);
+    gm::pose_mul(X, E, Y);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) out[(size_t)p * 16 + k] = Y[k];
+}
+
+}  // namespace
+
+hipError_t launch_linearize(const double* poses, const Factors& f, const Lin& out, double* partial, double* status, hipStream_t s) {
+    const int nb = lin_blocks(f.F);
+    if (nb > 0) hipLaunchKernelGGL(graph_linearize_kernel, dim3(nb), dim3(kLinBlock), 0, s, poses, f, out, partial);
+    hipLaunchKernelGGL(graph_chi2_fold_kernel, dim3(1), dim3(64), 0, s, partial, nb, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_solve(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, int max_it, double tol, const SolveBufs& b,
+                        double* status, hipStream_t s) {
+    hipLaunchKernelGGL(graph_solve_kernel, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, lambda, max_it, tol, b, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_apply(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, const double* x, double* y, double* u, hipStream_t s) {
+    hipLaunchKernelGGL(graph_apply_kernel, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, lambda, x, y, u);
+    return hipGetLastError();
+}
+
+hipError_t launch_retract(int N, const double* poses, const double* delta, double* out, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    hipLaunchKernelGGL(graph_retract_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, poses, delta, out);
+    return hipGetLastError();
+}
+
+}  // namespace graph
+}  // namespace pcr

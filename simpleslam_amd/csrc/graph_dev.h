@@ -1,0 +1,51 @@
+// graph_dev.h -- what graph_host.hip launches and graph.hip defines: the device layout of a pose graph and its three kernels.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace pcr {
+namespace graph {
+
+// Factors in the order priors, then betweens; F of them.  Per-factor arrays are structure-of-arrays: entry k of factor e at [k * F + e].
+struct Factors {
+    int F;
+    const int* from;          // -1: a prior
+    const int* to;
+    const double* z;          // [16][F] measurement (a prior: the prior pose), column-major pose entries
+    const double* omega;      // [36][F] information, full symmetric, row-major entries
+};
+
+// One linearisation: per factor r (6), Omega r (6), J_from, J_to, Omega J_from, Omega J_to (36 each, row-major entries), r^T Omega r.
+struct Lin {
+    double *r, *wr, *jf, *jt, *wjf, *wjt, *c;
+    static constexpr size_t kDoublesPerFactor = 6 + 6 + 4 * 36 + 1;
+};
+inline Lin lin_view(double* base, size_t F) {
+    Lin l;
+    l.r = base; l.wr = l.r + 6 * F; l.jf = l.wr + 6 * F; l.jt = l.jf + 36 * F; l.wjf = l.jt + 36 * F; l.wjt = l.wjf + 36 * F; l.c = l.wjt + 36 * F;
+    return l;
+}
+
+// Incident factors of pose p: ent[row_ptr[p] .. row_ptr[p + 1]), ascending by factor, entry = factor * 2 + (1: p is the "to" end, 0: the "from" end)
+struct Csr { const int* row_ptr; const int* ent; };
+
+// Work vectors of the solve, pose-major ([p * 6 + k]); L: the preconditioner's factors [p * 21 + k]; u: per factor [e * 6 + k]
+struct SolveBufs { double *x, *res, *z, *dir, *ap, *u, *L; };
+
+// status (3 doubles, one 24-byte read per trial step): [0] chi2 of the last linearisation folded into it, [1] the solve's final
+// |residual| / |g|, [2] two ints: PCG iterations, flag (0: tolerance met, 1: the cap ended it, 2: the curvature p^T A p was not positive)
+constexpr int kLinBlock = 256;
+constexpr int kSolveThreads = 1024;
+inline int lin_blocks(int F) { return (F + kLinBlock - 1) / kLinBlock; }
+
+// linearise every factor at `poses` into `out`, chi2 into status[0] (partial: lin_blocks(F) doubles)
+hipError_t launch_linearize(const double* poses, const Factors& f, const Lin& out, double* partial, double* status, hipStream_t s);
+// delta (= bufs.x) <- PCG on (H + lambda I) delta = -g, one workgroup; status[1], status[2]
+hipError_t launch_solve(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, int max_it, double tol, const SolveBufs& b,
+                        double* status, hipStream_t s);
+// y = (H + lambda I) x by the solve's own two passes (b.u is used)
+hipError_t launch_apply(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, const double* x, double* y, double* u, hipStream_t s);
+// out[p] = poses[p] * Exp(delta[p])
+hipError_t launch_retract(int N, const double* poses, const double* delta, double* out, hipStream_t s);
+
+}  // namespace graph
+}  // namespace pcr

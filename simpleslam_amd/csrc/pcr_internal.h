@@ -401,6 +401,8 @@ struct RelocPart { double sum; uint32_t cnt, viol; };
 int sc_device(const pcr_sc* sc);
 // the device a key-frame store, or a view of one, lives on (submap.hip)
 int map_device(const pcr_map* m);
+// the device a pose graph lives on, PCR_GRAPH_HOST (-2) for a graph without one (graph_host.hip)
+int graph_device(const pcr_graph* g);
 struct RelocSum { double sum; unsigned long long cnt, viol, pad_; };
 hipError_t fitness_batch_launch(const GridIndex& grid, const float* d_src, size_t n_src, size_t stride_floats, size_t m, const float* d_poses,
                                 size_t n_poses, double max_sq, RelocPart* d_part, RelocSum* d_out, hipStream_t s);

@@ -29,6 +29,8 @@ hipStream_t pcr_internal_stream(const pcr_handle* h);
 int pcr_internal_vf_begin(pcr_handle* h, const void* d_pts, size_t n, size_t stride_bytes, double leaf, void* d_out, size_t out_capacity);
 int pcr_internal_vf_end(pcr_handle* h, size_t* n_out);
 void pcr_internal_vf_reserve(pcr_handle* h, size_t points);
+// (pcr_internal.h, defined in graph_host.hip) the device a pose graph lives on, PCR_GRAPH_HOST for a graph without one
+namespace pcr { int graph_device(const pcr_graph* g); }
 
 namespace {
 
@@ -273,6 +275,31 @@ int pcr_map_set_poses(pcr_map* m, size_t first, size_t count, const double* pose
     if (views_quiesce(m)) return 1;
     for (size_t i = 0; i < count; ++i) memcpy(m->kfs[first + i].pose, poses + 16 * i, 16 * sizeof(double));
     return 0;      // (no sub-map, selection or generation is touched: the reference's mSubmap stays what it is until the next updateMap)
+}
+
+// The optimiser's poses straight from the graph's device memory (graph_host.hip) into the store's pose table, which lives on the host next to
+// the key frames' offsets: one copy, no buffer of the caller's in between.  Everything else is pcr_map_set_poses.
+int pcr_map_set_poses_from_graph(pcr_map* m, const pcr_graph* g, size_t first, size_t count) {
+    if (!m) return 1;
+    m->err.clear();
+    M_ALIVE(m);
+    M_OWNER(m, "pcr_map_set_poses_from_graph");
+    if (!g) return mfail(m, "pcr_map_set_poses_from_graph: graph is NULL");
+    if (pcr::graph_device(g) != m->device)
+        return mfail(m, "pcr_map_set_poses_from_graph: the graph (device " + std::to_string(pcr::graph_device(g)) + ") and the map (device " +
+                            std::to_string(m->device) + ") are on different devices");
+    if (first > m->kfs.size() || count > m->kfs.size() - first) return mfail(m, "pcr_map_set_poses_from_graph: first + count exceeds the number of key frames");
+    size_t n_graph = 0;
+    if (pcr_graph_size(g, &n_graph, nullptr, nullptr)) return mfail(m, "pcr_map_set_poses_from_graph: the graph is not usable");
+    if (first > n_graph || count > n_graph - first) return mfail(m, "pcr_map_set_poses_from_graph: first + count exceeds the number of poses in the graph");
+    if (count == 0) return 0;
+    M_TRY(hipSetDevice(m->device));
+    size_t n_dev = 0;
+    const double* d = pcr_graph_device_poses(g, &n_dev);
+    if (!d || n_dev < first + count) return mfail(m, std::string("pcr_map_set_poses_from_graph: ") + pcr_graph_last_error(g));
+    std::vector<double> tmp(16 * count);
+    M_TRY(hipMemcpy(tmp.data(), d + 16 * first, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
+    return pcr_map_set_poses(m, first, count, tmp.data());
 }
 
 const void* pcr_map_keyframe(const pcr_map* m, size_t i, size_t* n, size_t* stride_bytes, double pose[16]) {

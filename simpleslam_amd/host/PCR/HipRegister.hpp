@@ -599,6 +599,71 @@ public:
 };
 }  // namespace context
 
+// backend/src/Backend.cpp: Backend::Gtsam (addPrior, addEstimate, addBetween, addLC) and what Backend::optimHandler does with it, on the
+// device (pcr_graph).  Ids are positions: addEstimate(id, pose) must be called with id = the number of poses so far.
+namespace backend {
+class PoseGraph {
+    pcr_graph* g_ = nullptr;
+    static const double* noise(int kind, const double* info21, double* buf) {
+        if (info21) return info21;
+        pcr_graph_noise(kind, buf);
+        return buf;
+    }
+    void check(int rc) const { if (rc) throw std::runtime_error(pcr_graph_last_error(g_)); }
+public:
+    using Result = pcr_graph_result;
+    explicit PoseGraph(int device = -1) : g_(pcr_graph_create(device)) { if (!g_) throw std::runtime_error(pcr_graph_last_error(nullptr)); }
+    PoseGraph(const PoseGraph&) = delete;
+    PoseGraph& operator=(const PoseGraph&) = delete;
+    ~PoseGraph() { pcr_graph_destroy(g_); }
+    // info21 = the 21 upper-triangular entries of the information matrix in [omega; v] order; nullptr = the reference's preset (Backend.cpp:90-97)
+    void addPrior(const PCR::pose_t& pose, size_t id = 0, const double* info21 = nullptr) {
+        double buf[21];
+        check(pcr_graph_add_prior(g_, id, pose.data(), noise(PCR_GRAPH_PRIOR, info21, buf)));
+    }
+    void addEstimate(size_t id, const PCR::pose_t& pose) {
+        if (id != poses()) throw std::invalid_argument("PoseGraph::addEstimate: ids are consecutive from 0");
+        check(pcr_graph_add_poses(g_, pose.data(), 1));
+    }
+    void addBetween(size_t from, size_t to, const PCR::pose_t& between, const double* info21 = nullptr) {
+        double buf[21];
+        check(pcr_graph_add_between(g_, from, to, between.data(), noise(PCR_GRAPH_ODOM, info21, buf)));
+    }
+    void addLC(size_t from, size_t to, const PCR::pose_t& between, const double* info21 = nullptr) {
+        double buf[21];
+        check(pcr_graph_add_between(g_, from, to, between.data(), noise(PCR_GRAPH_LOOP, info21, buf)));
+    }
+    // Backend::addOdomFactor (Backend.cpp:241-247): the between factor of the two current estimates
+    void addOdomFactor(size_t from, size_t to, const double* info21 = nullptr) {
+        double buf[21];
+        check(pcr_graph_add_between_poses(g_, from, to, noise(PCR_GRAPH_ODOM, info21, buf)));
+    }
+    Result optimize(const pcr_graph_params* p = nullptr) {
+        Result r;
+        check(pcr_graph_optimize(g_, p, &r));
+        return r;
+    }
+    size_t poses() const { size_t n = 0; pcr_graph_size(g_, &n, nullptr, nullptr); return n; }
+    size_t factors() const { size_t p = 0, b = 0; pcr_graph_size(g_, nullptr, &p, &b); return p + b; }
+    std::vector<PCR::pose_t> poses(size_t first, size_t count) const {
+        static_assert(sizeof(PCR::pose_t) == 16 * sizeof(double), "poses are handed over as 16 doubles each");
+        std::vector<PCR::pose_t> out(count);
+        check(pcr_graph_poses(g_, first, count, count ? out.front().data() : nullptr));
+        return out;
+    }
+    // Backend.cpp:315-318: the optimised poses become the key frames' poses, device to store (pcr_map_set_poses_from_graph)
+    void applyTo(PCR::SubMap& map, size_t first = 0, size_t count = (size_t)-1) const {
+        if (count == (size_t)-1) count = poses() - std::min(first, poses());
+        if (pcr_map_set_poses_from_graph(map.handle(), g_, first, count)) throw std::runtime_error(pcr_map_last_error(map.handle()));
+    }
+    double chi2() { double c = 0; check(pcr_graph_linearize(g_, nullptr, nullptr, nullptr, &c)); return c; }
+    void loadG2o(const std::string& path) { check(pcr_graph_load_g2o(g_, path.c_str())); }
+    void saveG2o(const std::string& path) const { check(pcr_graph_save_g2o(g_, path.c_str())); }
+    void clear() { check(pcr_graph_clear(g_)); }
+    pcr_graph* handle() const { return g_; }
+};
+}  // namespace backend
+
 namespace PCR {
 inline bool HipRegister::relocalizeGlobal(const PC_cPtr& src, const context::ScanContext& sc, const std::vector<pose_t>& kf_poses, pose_t& res,
                                           const pcr_global_reloc_params* p, std::vector<pcr_global_reloc_candidate>* cands, size_t* chosen) {

@@ -86,6 +86,9 @@ ABI_SYMBOLS = [
     "pcr_liorf_pose_to_6dof", "pcr_liorf_6dof_to_pose", "pcr_liorf_linearize", "pcr_liorf_result",
     "pcr_pose_to_mobile", "pcr_frontend_default_params", "pcr_frontend_create", "pcr_frontend_destroy", "pcr_frontend_last_error", "pcr_frontend_step",
     "pcr_frontend_prefetch", "pcr_frontend_finish", "pcr_frontend_reset",
+    "pcr_graph_create", "pcr_graph_destroy", "pcr_graph_last_error", "pcr_graph_noise", "pcr_graph_add_poses", "pcr_graph_add_prior", "pcr_graph_add_between",
+    "pcr_graph_add_between_poses", "pcr_graph_size", "pcr_graph_clear", "pcr_graph_default_params", "pcr_graph_optimize", "pcr_graph_poses",
+    "pcr_graph_device_poses", "pcr_graph_linearize", "pcr_graph_apply", "pcr_map_set_poses_from_graph", "pcr_graph_load_g2o", "pcr_graph_save_g2o",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -124,6 +127,18 @@ class FrontendInfo(C.Structure):
     """struct pcr_frontend_info (include/pcr_hip.h)."""
     _fields_ = [("registered", C.c_int32), ("converged", C.c_int32), ("iterations", C.c_int32), ("keyframe_added", C.c_int32), ("update_queued", C.c_int32),
                 ("n_filtered", C.c_int64), ("n_submap", C.c_int64), ("keyframes", C.c_int64), ("updates", C.c_int64), ("seconds", C.c_double * 5)]
+
+
+class GraphParams(C.Structure):
+    """struct pcr_graph_params (include/pcr_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_iterations", C.c_int32), ("rel_tol", C.c_double), ("abs_tol", C.c_double), ("lambda_init", C.c_double),
+                ("lambda_factor", C.c_double), ("lambda_max", C.c_double), ("pcg_max_iterations", C.c_int64), ("pcg_rel_tol", C.c_double)]
+
+
+class GraphResult(C.Structure):
+    """struct pcr_graph_result (include/pcr_hip.h)."""
+    _fields_ = [("iterations", C.c_int32), ("accepted", C.c_int32), ("pcg_iterations", C.c_int64), ("pcg_capped", C.c_int32), ("converged", C.c_int32),
+                ("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("lambda_", C.c_double), ("delta", C.c_double * 16)]
 
 
 class GlobalRelocCandidate(C.Structure):
@@ -296,6 +311,30 @@ def load_library():
     L.pcr_frontend_prefetch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
     L.pcr_frontend_finish.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.pcr_frontend_reset.argtypes = [vp]
+    L.pcr_graph_create.argtypes = [C.c_int]
+    L.pcr_graph_create.restype = vp
+    L.pcr_graph_destroy.argtypes = [vp]
+    L.pcr_graph_destroy.restype = None
+    L.pcr_graph_last_error.argtypes = [vp]
+    L.pcr_graph_last_error.restype = C.c_char_p
+    L.pcr_graph_noise.argtypes = [C.c_int, dp]
+    L.pcr_graph_add_poses.argtypes = [vp, dp, C.c_size_t]
+    L.pcr_graph_add_prior.argtypes = [vp, C.c_size_t, dp, dp]
+    L.pcr_graph_add_between.argtypes = [vp, C.c_size_t, C.c_size_t, dp, dp]
+    L.pcr_graph_add_between_poses.argtypes = [vp, C.c_size_t, C.c_size_t, dp]
+    L.pcr_graph_size.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.pcr_graph_clear.argtypes = [vp]
+    L.pcr_graph_default_params.argtypes = [C.POINTER(GraphParams)]
+    L.pcr_graph_default_params.restype = None
+    L.pcr_graph_optimize.argtypes = [vp, C.POINTER(GraphParams), C.POINTER(GraphResult)]
+    L.pcr_graph_poses.argtypes = [vp, C.c_size_t, C.c_size_t, dp]
+    L.pcr_graph_device_poses.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.pcr_graph_device_poses.restype = vp
+    L.pcr_graph_linearize.argtypes = [vp, dp, dp, dp, dp]
+    L.pcr_graph_apply.argtypes = [vp, C.c_double, dp, dp]
+    L.pcr_map_set_poses_from_graph.argtypes = [vp, vp, C.c_size_t, C.c_size_t]
+    L.pcr_graph_load_g2o.argtypes = [vp, C.c_char_p]
+    L.pcr_graph_save_g2o.argtypes = [vp, C.c_char_p]
     _lib = L
     return L
 
@@ -1376,3 +1415,187 @@ class ScanContext:
             else:
                 out.append((first + r, i, np.float32(self._lib.pcr_sc_shift_yaw(s)), d))
         return out
+
+
+GRAPH_HOST = -2                                   # PCR_GRAPH_HOST: a graph without a device (no optimize)
+GRAPH_PRIOR, GRAPH_ODOM, GRAPH_LOOP = 0, 1, 2     # pcr_graph_noise kinds
+
+
+def graph_noise(kind):
+    """pcr_graph_noise -> the 6 x 6 information matrix of one of the reference's noise models (Backend.cpp:90-97), [omega; v] order."""
+    buf = np.zeros(21)
+    if load_library().pcr_graph_noise(int(kind), buf.ctypes.data_as(C.POINTER(C.c_double))):
+        raise PcrError(f"unknown noise kind {kind}")
+    return _info_full(buf)
+
+
+def _info21(info):
+    a = np.asarray(info, dtype=np.float64)
+    if a.shape == (6, 6):
+        a = a[np.triu_indices(6)]
+    if a.shape != (21,):
+        raise ValueError("an information matrix is 6 x 6, or its 21 upper-triangular entries")
+    return np.ascontiguousarray(a)
+
+
+def _info_full(info21):
+    m = np.zeros((6, 6))
+    m[np.triu_indices(6)] = info21
+    return m + np.triu(m, 1).T
+
+
+class GraphResultView:
+    """What PoseGraph.optimize() returns: pcr_graph_result with delta as a 4 x 4 matrix."""
+
+    def __init__(self, r):
+        self.iterations, self.accepted, self.pcg_iterations, self.pcg_capped = int(r.iterations), int(r.accepted), int(r.pcg_iterations), int(r.pcg_capped)
+        self.converged = bool(r.converged)
+        self.chi2_initial, self.chi2_final, self.lambda_ = float(r.chi2_initial), float(r.chi2_final), float(r.lambda_)
+        self.delta = _pose_out(np.array(r.delta[:], dtype=np.float64))
+
+    def __repr__(self):
+        return (f"GraphResult(iterations={self.iterations}, accepted={self.accepted}, pcg_iterations={self.pcg_iterations}, pcg_capped={self.pcg_capped}, "
+                f"converged={self.converged}, chi2_initial={self.chi2_initial:.6g}, chi2_final={self.chi2_final:.6g}, lambda_={self.lambda_:.3g})")
+
+
+class PoseGraph:
+    """Backend::Gtsam and Backend::optimHandler (backend/src/Backend.cpp:85-103, 224-347) on the device: an SE(3) pose graph of prior and
+    between factors, Levenberg-Marquardt over a conjugate gradient that runs on the GPU (pcr_graph, DESIGN.md 4.17).  Poses are 4 x 4;
+    information matrices are 6 x 6 in [omega; v] order (or their 21 upper-triangular entries); None takes the reference's preset.
+    device=GRAPH_HOST builds a graph that touches no device: everything but optimize() and apply()."""
+
+    def __init__(self, device=-1):
+        self._lib = load_library()
+        self._g = self._lib.pcr_graph_create(int(device))
+        if not self._g:
+            raise PcrError(self._lib.pcr_graph_last_error(None).decode())
+
+    def __del__(self):
+        try:
+            if self._g:
+                self._lib.pcr_graph_destroy(self._g)
+                self._g = None
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc:
+            raise PcrError(self._lib.pcr_graph_last_error(self._g).decode())
+
+    def _noise(self, kind, info):
+        buf = np.zeros(21)
+        if info is None:
+            self._lib.pcr_graph_noise(kind, buf.ctypes.data_as(C.POINTER(C.c_double)))
+        else:
+            buf = _info21(info)
+        return buf, buf.ctypes.data_as(C.POINTER(C.c_double))
+
+    def addPoses(self, poses):
+        """pcr_graph_add_poses: (k, 4, 4); their ids continue the graph's."""
+        P = np.asarray(poses, dtype=np.float64)
+        if P.ndim == 2:
+            P = P[None]
+        if P.ndim != 3 or P.shape[1:] != (4, 4):
+            raise ValueError("poses must have shape (k, 4, 4)")
+        cm = np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(-1)
+        self._check(self._lib.pcr_graph_add_poses(self._g, cm.ctypes.data_as(C.POINTER(C.c_double)), P.shape[0]))
+
+    def addEstimate(self, id, pose):
+        if int(id) != self.size()[0]:
+            raise PcrError("addEstimate: ids are consecutive from 0")
+        self.addPoses(pose)
+
+    def addPrior(self, pose, id=0, info=None):
+        _k, ip = self._noise(GRAPH_PRIOR, info)
+        pc = _pose_in(pose)
+        self._check(self._lib.pcr_graph_add_prior(self._g, int(id), pc.ctypes.data_as(C.POINTER(C.c_double)), ip))
+
+    def _between(self, kind, frm, to, between, info):
+        _k, ip = self._noise(kind, info)
+        pc = _pose_in(between)
+        if int(frm) < 0 or int(to) < 0:
+            raise PcrError("ids must not be negative")
+        self._check(self._lib.pcr_graph_add_between(self._g, int(frm), int(to), pc.ctypes.data_as(C.POINTER(C.c_double)), ip))
+
+    def addBetween(self, frm, to, between, info=None):
+        self._between(GRAPH_ODOM, frm, to, between, info)
+
+    def addLC(self, frm, to, between, info=None):
+        self._between(GRAPH_LOOP, frm, to, between, info)
+
+    def addOdomFactor(self, frm, to, info=None):
+        """Backend::addOdomFactor: the between factor of the two current estimates."""
+        _k, ip = self._noise(GRAPH_ODOM, info)
+        if int(frm) < 0 or int(to) < 0:
+            raise PcrError("ids must not be negative")
+        self._check(self._lib.pcr_graph_add_between_poses(self._g, int(frm), int(to), ip))
+
+    def size(self):
+        """-> (poses, priors, between factors)"""
+        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.pcr_graph_size(self._g, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def clear(self):
+        self._check(self._lib.pcr_graph_clear(self._g))
+
+    def optimize(self, **params):
+        """pcr_graph_optimize with pcr_graph_params fields overridden (max_iterations, rel_tol, abs_tol, lambda_init, lambda_factor, lambda_max,
+        pcg_max_iterations, pcg_rel_tol) -> GraphResultView."""
+        p = GraphParams()
+        self._lib.pcr_graph_default_params(C.byref(p))
+        for k, v in params.items():
+            if k == "struct_size" or not hasattr(p, k):
+                raise ValueError(f"unknown pose-graph parameter {k}")
+            setattr(p, k, v)
+        r = GraphResult()
+        self._check(self._lib.pcr_graph_optimize(self._g, C.byref(p), C.byref(r)))
+        return GraphResultView(r)
+
+    def poses(self, first=0, count=None):
+        """-> (count, 4, 4), the current estimates."""
+        n = self.size()[0]
+        if count is None:
+            count = max(n - int(first), 0)
+        buf = np.zeros(16 * max(int(count), 1))
+        self._check(self._lib.pcr_graph_poses(self._g, int(first), int(count), buf.ctypes.data_as(C.POINTER(C.c_double))))
+        return buf[:16 * int(count)].reshape(-1, 4, 4).transpose(0, 2, 1).copy()
+
+    def devicePoses(self):
+        """pcr_graph_device_poses -> (device pointer, number of poses)"""
+        n = C.c_size_t(0)
+        p = self._lib.pcr_graph_device_poses(self._g, C.byref(n))
+        return p, n.value
+
+    def linearize(self):
+        """pcr_graph_linearize -> (r (E, 6), J_from (E, 6, 6), J_to (E, 6, 6), chi2), priors first, then the between factors."""
+        _n, a, b = self.size()
+        E = a + b
+        r, jf, jt, c = np.zeros((max(E, 1), 6)), np.zeros((max(E, 1), 6, 6)), np.zeros((max(E, 1), 6, 6)), C.c_double(0)
+        d = C.POINTER(C.c_double)
+        self._check(self._lib.pcr_graph_linearize(self._g, r.ctypes.data_as(d), jf.ctypes.data_as(d), jt.ctypes.data_as(d), C.byref(c)))
+        return r[:E], jf[:E], jt[:E], c.value
+
+    def apply(self, lam, x):
+        """pcr_graph_apply -> y = (H + lam I) x, x of 6 entries per pose."""
+        n = self.size()[0]
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
+        if x.size != 6 * n:
+            raise ValueError("x must hold 6 entries per pose")
+        y = np.zeros(max(6 * n, 1))
+        d = C.POINTER(C.c_double)
+        self._check(self._lib.pcr_graph_apply(self._g, float(lam), x.ctypes.data_as(d), y.ctypes.data_as(d)))
+        return y[:6 * n]
+
+    def applyTo(self, submap, first=0, count=None):
+        """pcr_map_set_poses_from_graph (Backend.cpp:315-318): the estimates become the key frames' poses."""
+        if count is None:
+            count = max(self.size()[0] - int(first), 0)
+        if self._lib.pcr_map_set_poses_from_graph(submap._m, self._g, int(first), int(count)):
+            raise PcrError(self._lib.pcr_map_last_error(submap._m).decode())
+
+    def loadG2o(self, path):
+        self._check(self._lib.pcr_graph_load_g2o(self._g, os.fsencode(path)))
+
+    def saveG2o(self, path):
+        self._check(self._lib.pcr_graph_save_g2o(self._g, os.fsencode(path)))
