@@ -52,6 +52,21 @@ for k in range(tl.shape[0]):
     t = tl[k]; ok = (t[:, 6] > 0) & (t[:, 18] > 0)
     if ok.any():
         print(f'  launch {k}: ' + ' | '.join(f'{np.mean(t[ok, b] - t[ok, a]):5.2f}' for _, a, b in sub) + f' | {t[ok, 6].mean():6.2f}')
+# solved -> query transformed, split by the stamps inside it, in the order thread 0 passes them: 21 the wave's LDS-DMA has landed, 22 entry in
+# registers, 23 the prologue's closing barrier (which also frees the staging area), 1 prologue left, 20 pose in registers, 16 query transformed
+# (launch 0 fetches no entry: 21 and 22 are not taken there, and its stretch starts at the kernel's entry)
+names = {1: 'prologue left', 20: 'pose in regs', 21: 'DMA landed', 22: 'entry read', 23: 'barrier', 16: 'transformed'}
+print('solved -> query transformed, mean block, us (each stamp: time since the one before it)')
+for k in range(tl.shape[0]):
+    t = tl[k]; ok = (t[:, 6] > 0) & (t[:, 16] > 0)
+    if not ok.any():
+        continue
+    start = 11 if k else 0
+    at = sorted((np.mean(t[ok, s] - t[ok, start]), s) for s in names if (t[ok, s] > 0).all())
+    prev, cells = 0.0, []
+    for v, s in at:
+        cells.append(f'{names[s]}:{v - prev:5.2f}'); prev = v
+    print(f'  launch {k}: ' + ' | '.join(cells) + f' | whole stretch {prev:5.2f}')
 import hashlib
 print('pose sha1', hashlib.sha1(np.ascontiguousarray(pose).tobytes()).hexdigest())
 reg.set_profile(2)

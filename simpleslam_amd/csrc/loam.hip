@@ -296,7 +296,7 @@ __device__ __forceinline__ double knn_list_bound(const uint32_t key[kNb + 1], ui
 // Otherwise the search runs again.  The plane through the five (which does not depend on the query) is kept with the
 // indices it was fitted to and reused while the five and their order stay the same.
 // ------------------------------------------------------------------------------
-struct NnCacheEntry {          // 192 bytes per scan point = 12 x 16 (fetched by LDS-DMA)
+struct NnCacheEntry {          // a scan point's entry as its lane holds it in registers: 12 fields of 16 bytes (in memory: entry_field)
     float4 nb[kNb];            // x y z | original index bits; +inf coordinates and index 0xffffffff: empty slot
     float q0[3];               // query position of the SEARCH that produced the entry (never moved afterwards: a bound
                                // anchored there is at least as tight as one chained through the iterations)
@@ -305,8 +305,15 @@ struct NnCacheEntry {          // 192 bytes per scan point = 12 x 16 (fetched by
     uint32_t pidx[5];
     uint32_t flags;            // bit0: entry valid  bit1: x valid  bit2: plane passed its validity gate
 };
-static_assert(sizeof(NnCacheEntry) == 192, "cache entry layout");
-static constexpr int kEntryVec = sizeof(NnCacheEntry) / 16;
+static constexpr int kEntryVec = kCacheFields;
+static_assert(sizeof(NnCacheEntry) == kEntryVec * sizeof(float4), "cache entry fields");
+// Where field 0 of scan point q's entry lives: tile q / 64 of kCacheTileBytes, ordered [field][lane].  Field f of the same entry
+// is kEntryStride float4 further on, so one instruction of a wave -- a load, a store, an LDS-DMA -- touches 1 KB of contiguous
+// memory instead of 64 cache lines 192 bytes apart.
+static constexpr int kEntryStride = 64;
+__device__ __forceinline__ float4* entry_field(float4* cache, uint32_t q) {
+    return cache + (size_t)(q >> 6) * (kEntryVec * 64) + (q & 63u);
+}
 
 // Distances from the new query to the kept points, put in (distance, index) order.  Returns true when the first five are
 // proven to be the exact 5-NN (see above).  *moved: the order of the kept points changed (the entry is rewritten so that the
@@ -584,7 +591,7 @@ __device__ __forceinline__ uint32_t posted_owner(const MissExchange& ex, const u
 }
 
 // What one scan point leaves in its cache entry for the next launch.  loam_point only fills this in (registers); the caller
-// stores it once the block's accumulate phase is over (entry_store_wave).
+// stores it once the block's accumulate phase is over (entry_store).
 struct EntryWrite {
     uint32_t what;             // bit0: neighbours  bit1: anchor  bit2: plane tail  bit3: invalidate only
     Nb8 s;
@@ -610,43 +617,15 @@ __device__ __forceinline__ uint32_t entry_fields(const EntryWrite& w, float4 v[k
     return ((w.what & 1u) ? 0x0ffu : 0u) | ((w.what & 2u) ? 0x100u : 0u) | ((w.what & 4u) ? 0xe00u : 0u);
 }
 
-// A wave in which only a few lanes rewrite anything -- the late launches, where a handful of planes are refitted -- does not pay for staging 64
-// entries: each writer stores its own fields, under the same mask.
-static constexpr int kFewWriters = 8;      // up to this many writing lanes in a wave go the per-lane way
-__device__ __forceinline__ void entry_store_lane(NnCacheEntry* __restrict__ mine_e, const EntryWrite& w) {
-    if (w.what & 8u) mine_e->flags = 0;
+// Every lane stores the fields it rewrites, straight from its registers: field f of a wave's 64 entries is 1 KB of contiguous memory
+// (entry_field), so a wave in which every lane writes issues twelve full-width stores and one in which a handful of planes are refitted
+// touches a handful of lines.  A field that is not rewritten keeps what it holds.  mine: field 0 of this lane's entry.
+__device__ __forceinline__ void entry_store(float4* __restrict__ mine, const EntryWrite& w) {
+    if (w.what & 8u) reinterpret_cast<uint32_t*>(mine + (kEntryVec - 1) * kEntryStride)[3] = 0;      // NnCacheEntry::flags
     float4 v[kEntryVec];
     const uint32_t fields = entry_fields(w, v);
-    float4* const dst = reinterpret_cast<float4*>(mine_e);
 #pragma unroll
-    for (int f = 0; f < kEntryVec; ++f) if ((fields >> f) & 1u) dst[f] = v[f];
-}
-
-// The entries of a wave's 64 consecutive scan points are 12 KB of contiguous memory.  Written by their owners they are twelve
-// 16-byte stores per lane at a 192-byte lane stride -- 64 cache lines per instruction, 2.7 us of every launch that searches
-// (profiles/loam_refine_notes.md).  Here the wave transposes them through its own 12 KB slice of LDS (the block's search and
-// row scratch, dead by now) and stores 1 KB of contiguous memory per instruction; every 16-byte field is stored iff its owner
-// marked it (the owner's mask comes by lane permute), so a field that is not rewritten keeps what it holds.
-// e0: entry of the wave's lane 0.  stage: kEntryVec * 64 float4 of this wave.  All 64 lanes call it together.
-__device__ __forceinline__ void entry_store_wave(NnCacheEntry* __restrict__ e0, const EntryWrite& w, float4* stage) {
-    const int lane = threadIdx.x & 63;
-    if (w.what & 8u) e0[lane].flags = 0;
-    float4* const mine = stage + lane * kEntryVec;
-    float4 mv[kEntryVec];
-    const uint32_t fields = entry_fields(w, mv);
-#pragma unroll
-    for (int f = 0; f < kEntryVec; ++f) mine[f] = mv[f];
-    // (same wave: its LDS operations complete in order, so the slice is visible to the reads below)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    float4* const dst = reinterpret_cast<float4*>(e0);
-#pragma unroll
-    for (int i = 0; i < kEntryVec; ++i) {
-        const uint32_t c = (uint32_t)(i * 64 + lane);      // 16-byte field c of the wave's 64 x 12
-        const uint32_t owner = c / (uint32_t)kEntryVec, f = c - owner * (uint32_t)kEntryVec;
-        const uint32_t m = (uint32_t)__shfl((int)fields, (int)owner, 64);
-        const float4 v = stage[c];
-        if ((m >> f) & 1u) dst[c] = v;
-    }
+    for (int f = 0; f < kEntryVec; ++f) if ((fields >> f) & 1u) mine[f * kEntryStride] = v[f];
 }
 
 // ------------------------------------------------------------------------------
@@ -973,9 +952,13 @@ __device__ __forceinline__ void loam_head_issue(const LoamHead hd, int k, HeadLo
     L.red = *(hd.reduced ? hd.reduced + comp : part0);       // sharded mode: sums already all-reduced
 }
 
-// pre_src / pre_dst: this lane's 192-byte neighbour-cache entry and the wave's slice of the LDS staging area.
+// pre_src / pre_dst: field 0 of this lane's neighbour-cache entry and the wave's slice of the LDS staging area.
+// caller_closes: the barrier that publishes sh->pose / big_step / done is left to the caller, who has something to put in front of it
+// (the iterate kernel: every wave's reads of the staging area); the return value is then true only for a loop that had ended before
+// this launch, and the caller tests sh->done behind its barrier.
 __device__ bool loam_prologue(const LoamHead hd, const HeadLoads& L, const LoamArgs& a, int k, double* sh_sum /* 8*32 */, Prologue* sh,
-                              unsigned long long* tl = nullptr, const float4* pre_src = nullptr, float4* pre_dst = nullptr) {
+                              unsigned long long* tl = nullptr, const float4* pre_src = nullptr, float4* pre_dst = nullptr,
+                              const bool caller_closes = false) {
     const LoamState* prev = &hd.state[(k + 1) & 1];
     LoamState* cur = &hd.state[k & 1];
     const int t = threadIdx.x;
@@ -986,7 +969,7 @@ __device__ bool loam_prologue(const LoamHead hd, const HeadLoads& L, const LoamA
             for (int i = 0; i < 16; ++i) cur->pose[i] = a.init_pose[i];
             cur->done = 0; cur->converged = 0; cur->iters_run = 0; cur->fail = 0;
         }
-        __syncthreads();
+        if (!caller_closes) __syncthreads();
         return false;
     }
     const int comp = t & 31, slice = t >> 5;
@@ -1019,9 +1002,8 @@ __device__ bool loam_prologue(const LoamHead hd, const HeadLoads& L, const LoamA
     // equations are solved.  Issued from inline asm on purpose: the compiler's wait-count bookkeeping treats an LDS-DMA
     // in flight as "wait for everything" at every barrier and at every use of any other load; the consumer waits by hand.
     if (pre_dst) {
-        const float4* src = pre_src ? pre_src : reinterpret_cast<const float4*>(hd.partials) + (size_t)t * kEntryVec;   // harmless address
 #pragma unroll
-        for (int f = 0; f < kEntryVec; ++f) lds_dma16(src + f, pre_dst + f * 256);
+        for (int f = 0; f < kEntryVec; ++f) lds_dma16(pre_src + f * kEntryStride, pre_dst + f * 256);      // 1 KB of contiguous memory each
     }
     // (the tests of the previous state come only now: placed before the loads above they made the compiler sink the
     // partial-sum loads below the branch, i.e. two dependent round trips instead of one)
@@ -1151,6 +1133,7 @@ __device__ bool loam_prologue(const LoamHead hd, const HeadLoads& L, const LoamA
             }
         }
     }
+    if (caller_closes) return false;
     __syncthreads();
     return sh->done != 0;
 }
@@ -1163,7 +1146,7 @@ __device__ bool loam_prologue(const LoamHead hd, const HeadLoads& L, const LoamA
 // CUs: a little slower alone, more scans/s with several handles in flight (pcr_params.loam_coresident = 1).
 template <int kGroup, int kWavesPerSimd>
 __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(double* const partials, LoamState* const state, const double* const reduced,
-                                                                          const uint32_t n_partials, const int k, NnCacheEntry* const nn_cache,
+                                                                          const uint32_t n_partials, const int k, float4* const nn_cache,
                                                                           const float* const src, const LoamArgs a) {
     const unsigned long long t_entry = wall_clock64();
     const LoamHead hd = {partials, state, reduced, n_partials};
@@ -1188,9 +1171,10 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(double
     if ((gridDim.x & 7u) == 0) blk = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     // (the partial sums the prologue folds are already on their way: loam_head_issue above)
     // Everything the first round needs from memory is requested before/inside the prologue, so that the scan point and
-    // the 128-byte neighbour-cache entry arrive while the previous iteration's normal equations are being solved.
-    // The entry goes straight to LDS ([field][thread], 48 KB): held in registers it was spilled to AGPRs, which made
-    // the wave wait for it before the prologue had even started.
+    // the neighbour-cache entry arrive while the previous iteration's normal equations are being solved.
+    // The entry goes straight to LDS ([field][thread], 48 KB -- the order its tile has in memory): held in registers across the
+    // solve it was spilled to AGPRs, which made the wave wait for it before the prologue had even started.  It is read out of LDS
+    // behind the solve, in front of the prologue's closing barrier (below).
     float4* const sh_pre = reinterpret_cast<float4*>(sh_ov);
     // (read through the constant address space: nothing in this launch writes the header, and only so do the loads stay scalar --
     //  as ordinary global loads they came back through vector registers, with a wait in front of the partial sums)
@@ -1212,16 +1196,42 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(double
         const float* sp = a.n_src ? src + (size_t)(q < a.n_src ? q : a.n_src - 1u) * a.src_stride
                                   : reinterpret_cast<const float*>(partials);      // empty scan: any readable address
         pre_x = sp[0]; pre_y = sp[1]; pre_z = sp[2];
-        pre_src = (use_cache && q < a.n_src) ? reinterpret_cast<const float4*>(nn_cache + q) : nullptr;
+        // A lane past the end of the scan fetches too (its wave's transfer is whole 1 KB rows): its own slot of the last tile, or,
+        // in a wave without a single scan point, of the spare tile behind it (loam_cache_bytes)
+        const uint32_t tiles = (a.n_src + 63u) >> 6;
+        if (use_cache) pre_src = entry_field(nn_cache, ((q >> 6) < tiles ? (q & ~63u) : (tiles << 6)) + (q & 63u));
     }
-    if (loam_prologue(hd, head, a, k, sh_sum, &sh_pro, tl, pre_src, use_cache ? sh_pre + (tid & ~63) : nullptr)) {
+    union EntryRegs { NnCacheEntry e; float4 v[kEntryVec]; };
+    if (loam_prologue(hd, head, a, k, sh_sum, &sh_pro, tl, pre_src, use_cache ? sh_pre + (tid & ~63) : nullptr, true)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // never leave with an LDS-DMA in flight
         return;
     }
+    // Every wave reads its entries out of the staging area IN FRONT of the barrier that closes the prologue -- the three waves that
+    // do not update the pose while the fourth does -- so that this one barrier both publishes the pose and frees the staging area for the
+    // search scratch.  Unconditional: big_step is not known on this side of the barrier (a launch that searches everything ignores
+    // what was read).  The entry is live in registers across the barrier only, not across the solve.
+    // EVERY wave waits for its own LDS-DMA, also one without a single valid query: a transfer still in flight behind the barrier would
+    // land in the search scratch of the other waves.
+    EntryRegs ce0;
+    ce0.e.flags = 0;
+    if (use_cache) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (tl) tl[21] = wall_clock64();      // the wave's LDS-DMA has landed
+        if (blk * qpb + (uint32_t)tid < a.n_src) {
+#pragma unroll
+            for (int f = 0; f < kEntryVec; ++f) ce0.v[f] = sh_pre[f * 256 + tid];
+            if (tl) { float t_ = 0.f; for (int f = 0; f < kEntryVec; ++f) t_ += ce0.v[f].x; if (t_ == 1.2345e38f) ce0.e.flags = 0u; }
+        }
+        if (tl) tl[22] = wall_clock64();      // entry in registers
+    }
+    __syncthreads();
+    if (tl) tl[23] = wall_clock64();          // the prologue's closing barrier = the staging barrier
+    if (sh_pro.done) return;                  // (no LDS-DMA in flight: waited for above)
     if (tl) tl[1] = wall_clock64();
     double pose[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) pose[i] = sh_pro.pose[i];
+    if (tl) { double t_ = 0.0; for (int i = 0; i < 16; ++i) t_ += pose[i]; if (t_ == 1.2345e300) pose[12] = 0.0; tl[20] = wall_clock64(); }   // pose in registers
 
     // This thread accumulates ONE entry of the normal equations over a 32-point chunk:
     // e < 21: JtJ(er,ec) upper triangle; 21..26: JtE(er) = sum row[er]*row[6]; 27: accepted count.
@@ -1247,26 +1257,22 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(double
         bool esc = false;
         EntryWrite ew;
         float sx = pre_x, sy = pre_y, sz = pre_z;
-        union { NnCacheEntry e; float4 v[kEntryVec]; } ce;
+        EntryRegs ce;
         ce.e.flags = 0;
         bool all_search = false;      // (later rounds of a grid-stride launch go the ordinary way)
         if (base == blk * qpb) {
             all_search = sh_pro.big_step != 0;
-            // EVERY wave waits for its own LDS-DMA, also one without a single valid query (its lanes fetched a dummy address):
-            // the staging area is reused right after the barrier, and a transfer still in flight would land in the search
-            // scratch of the other waves.
-            if (use_cache) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (use_cache && valid && !sh_pro.big_step) {
-#pragma unroll
-                for (int f = 0; f < kEntryVec; ++f) ce.v[f] = sh_pre[f * 256 + tid];
-            }
-            __syncthreads();          // the staging area is about to be reused by the search scratch and the exchange
+            ce = ce0;                 // read in front of the prologue's closing barrier
         } else {                      // later rounds of a grid-stride launch
             sx = sy = sz = 0.f;
             if (valid) {
                 const float* sp = src + (size_t)q * a.src_stride;
                 sx = sp[0]; sy = sp[1]; sz = sp[2];
-                if (use_cache) ce.e = nn_cache[q];
+                if (use_cache) {
+                    const float4* const mine = entry_field(nn_cache, q);
+#pragma unroll
+                    for (int f = 0; f < kEntryVec; ++f) ce.v[f] = mine[f * kEntryStride];
+                }
             }
         }
         const int st = loam_point<kGroup>(a, h, pose, sx, sy, sz, valid, ce.e, use_cache && valid && !all_search, sh_knn, sh_ex, row, nn, q, &how, &esc, ew,
@@ -1297,15 +1303,9 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void loam_iterate_kernel(double
             }
         }
         if (tl && base == blk * qpb) { if (acc == 1.2345e300) n_hit = 0u; tl[19] = wall_clock64(); }   // chunk sums done
-        __syncthreads();
-        // The cache entries go out last, behind everything the block waits for; the rows and the search scratch are dead, so
-        // their LDS stages the transposition.  (wave-uniform tests: nothing is staged or stored in a wave of unchanged entries, and a wave with
-        // only a few writers stores per lane)
-        const int writers = __popcll(__ballot(ew.what != 0u));
-        if (writers) {      // (nested: side by side, what the two ways share -- the fields -- was computed in front of both tests, also for no writer)
-            if (writers > kFewWriters) entry_store_wave(nn_cache + (q - (uint32_t)(tid & 63)), ew, reinterpret_cast<float4*>(sh_ov) + (tid >> 6) * (64 * kEntryVec));
-            else entry_store_lane(nn_cache + q, ew);
-        }
+        // The cache entries go out last, behind everything the block waits for, each lane's fields straight from its registers.  No
+        // barrier in front: the stores touch no LDS.  (wave-uniform test, so that a wave of unchanged entries does not even compute the fields)
+        if (__ballot(ew.what != 0u)) entry_store(entry_field(nn_cache, q), ew);
         if (base + gridDim.x * qpb < a.n_src) __syncthreads();      // (grid-stride launch: the next round reuses that LDS)
     }
     if (tl) tl[5] = wall_clock64();

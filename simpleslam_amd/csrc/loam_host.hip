@@ -45,7 +45,7 @@ void fill_loam_args(pcr_handle* h, LoamArgs* a, const float* d_src, size_t n_src
     a->trace = h->prm.record_trace ? h->loam.trace.as<LoamTrace>() : nullptr;
     a->result = h->loam.result.dev;
     a->coresident = h->prm.loam_coresident == 1;
-    if (h->prm.loam_disable_cache == 0 && h->loam.nn_cache.reserve((n_src + 1) * 192) == hipSuccess) a->nn_cache = (NnCacheEntry*)h->loam.nn_cache.p;
+    if (h->prm.loam_disable_cache == 0 && h->loam.nn_cache.reserve(loam_cache_bytes(n_src)) == hipSuccess) a->nn_cache = h->loam.nn_cache.as<float4>();
     if (h->prm.record_timeline == 1 && h->loam.timeline.reserve((size_t)(std::max(1, h->prm.loam_iters) + 1) * kMaxPartials * kTimelineSlots * sizeof(unsigned long long)) == hipSuccess)
         a->timeline = h->loam.timeline.as<unsigned long long>();
     a->use_tile = h->use_tile;

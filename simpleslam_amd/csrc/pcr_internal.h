@@ -110,7 +110,12 @@ struct LoamTrace {           // per consumed linearisation
     int64_t cache_hits, searches;   // queries served by the neighbour cache / by a full search in that linearisation
 };
 
-struct NnCacheEntry;
+// The LOAM neighbour cache in memory (loam.hip reads and writes it, fill_loam_args sizes it): the entries of 64 consecutive scan
+// points -- one wave's -- form one tile, ordered [field][lane], so that every 16-byte field of a wave is 1 KB of contiguous memory.
+static constexpr int kCacheFields = 12;                                              // 16-byte fields of an entry (NnCacheEntry)
+static constexpr size_t kCacheTileBytes = (size_t)kCacheFields * 64 * 16;
+// (one spare tile behind the last: where the waves of a block without a single scan point aim their fetch)
+static inline size_t loam_cache_bytes(size_t n_src) { return ((n_src + 63) / 64 + 1) * kCacheTileBytes; }
 
 struct LoamArgs {
     const float* src;        // scan points, stride in floats
@@ -130,7 +135,7 @@ struct LoamArgs {
     double* dbg_rows;
     int32_t* dbg_nn;
     // optional query tile (multi-GPU): process only queries inside [lo,hi)
-    struct NnCacheEntry* nn_cache;   // [n_src] neighbours of the previous iteration (loam.hip), or null
+    float4* nn_cache;        // [tiles][kCacheFields][64] neighbours of the previous iteration (loam.hip: entry_field), or null
     int32_t use_tile;
     double tile_lo[3], tile_hi[3];
     int32_t coresident;      // pcr_params.loam_coresident = 1: the two-waves-per-SIMD variant of the iterate kernel (loam.hip)

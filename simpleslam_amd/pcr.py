@@ -808,7 +808,9 @@ class LoamRegister(PointCloudRegister):
         (needs pcr_params.record_timeline = 1).  Columns 0-7: entry, prologue, posted, searched, plane, accumulated (entry stores issued), stored, partial
         sums folded (inside the prologue); 8-10 (dense search only): row ranges in LDS, first candidate chunk arrived, candidate stream done; 11: normal
         equations solved (inside the prologue); 12-15 (lanes that searched): gather returned, distances and proof, plane solved, plane gate; 16: pose in
-        registers, 17: hit test done (both before 'posted'); 18: rows in LDS, 19: chunk sums done (both before 'accumulated'); 20-23 unused."""
+        registers, 17: hit test done (both before 'posted'); 18: rows in LDS, 19: chunk sums done (both before 'accumulated'); 21: the wave's LDS-DMA of its cache
+        entries has landed, 22: entry in registers, 23: the prologue's closing barrier passed (21-23 before 'prologue'; 21 and 22 not in launch 0),
+        20: pose in registers (before 16)."""
         nl, nb = C.c_int(0), C.c_int(0)
         self._check(self._lib.pcr_get_timeline(self._h, None, 0, C.byref(nl), C.byref(nb)))
         raw = np.zeros((nl.value, nb.value, 24), np.uint64)
