@@ -525,6 +525,15 @@ float pcr_sc_shift_yaw(int32_t shift);
 typedef struct pcr_graph pcr_graph;
 #define PCR_GRAPH_HOST (-2)
 enum { PCR_GRAPH_PRIOR = 0, PCR_GRAPH_ODOM = 1, PCR_GRAPH_LOOP = 2 };
+/* The preconditioner M of the conjugate gradient.
+ *   BLOCK_JACOBI  every pose's 6x6 diagonal block of H + lambda I.  Information moves one edge per iteration: right for the tens to hundreds
+ *                 of key frames one event meets, and for graphs dense in loop edges (a hub with full information matrices).
+ *   TREE          lambda I + every prior + the between factors of a spanning forest, solved exactly by a block Cholesky without fill (two
+ *                 sweeps over the poses per iteration).  The forest: the between factors in the order added, each joining when its ends lie in
+ *                 different components -- Backend::addOdomFactor's edges, one per key frame, are that forest; every other between factor is
+ *                 left to the conjugate gradient.  Right for an odometry tree plus few loops at thousands of poses (a loaded map); on a hub
+ *                 graph with many loops it can need MORE iterations than BLOCK_JACOBI. */
+enum { PCR_GRAPH_PRECOND_BLOCK_JACOBI = 0, PCR_GRAPH_PRECOND_TREE = 1 };
 typedef struct pcr_graph_params {
     uint32_t struct_size;          /* sizeof(pcr_graph_params), set by pcr_graph_default_params */
     int32_t max_iterations;        /* 100: trial steps (GTSAM's LevenbergMarquardtParams defaults throughout) */
@@ -532,6 +541,7 @@ typedef struct pcr_graph_params {
     double lambda_init, lambda_factor, lambda_max;      /* 1e-5, 10, 1e5 */
     int64_t pcg_max_iterations;    /* 0 = max(100, 10 * poses) */
     double pcg_rel_tol;            /* 1e-10, on |residual| / |g| */
+    int32_t pcg_preconditioner;    /* PCR_GRAPH_PRECOND_BLOCK_JACOBI; another value than the two above is refused */
 } pcr_graph_params;
 typedef struct pcr_graph_result {
     int32_t iterations, accepted;  /* trial steps (one linear solve each); those that were accepted */
@@ -575,6 +585,15 @@ const double* pcr_graph_device_poses(const pcr_graph* g, size_t* n);
 int pcr_graph_linearize(pcr_graph* g, double* r, double* j_from, double* j_to, double* chi2);
 /* Introspection (device graphs): y = (H + lambda I) x at the current estimates, x and y 6 doubles per pose, by the solve kernel's own product. */
 int pcr_graph_apply(pcr_graph* g, double lambda, const double* x, double* y);
+/* Introspection (host code only; serves a PCR_GRAPH_HOST graph): the spanning forest PCR_GRAPH_PRECOND_TREE would use.  parent[p] = the parent
+ * pose of p, -1 for a root (the lowest-numbered pose of its component that holds a prior); n = the entries parent has room for, at least the
+ * number of poses (parent may be NULL, then only the counts are written).  *n_tree_edges between factors are in the forest, *n_other_edges are
+ * not (loops, duplicates of a tree edge).  Refuses what pcr_graph_optimize refuses of the graph itself. */
+int pcr_graph_tree(const pcr_graph* g, int64_t* parent, size_t n, size_t* n_tree_edges, size_t* n_other_edges);
+/* Introspection (device graphs): z = M^-1 r at the current estimates, kind = one of PCR_GRAPH_PRECOND_*, r and z 6 doubles per pose, by the
+ * factorisation and the sweeps the solve runs.  lambda >= 0; 0 is legal when every pose has a factor.  Nonzero with a message when a block
+ * is not positive definite. */
+int pcr_graph_precondition(pcr_graph* g, double lambda, int kind, const double* r, double* z);
 /* Poses first .. first+count-1 of the graph become the poses of key frames first .. first+count-1 of the store, read from the graph's device
  * memory.  The store keeps its pose table on the HOST (beside the key frames' offsets), so this is one device-to-host copy inside the library,
  * not a device-to-device one; what it spares is the caller's buffer and second call.  The bits pcr_map_set_poses would store from pcr_graph_poses, with its rules (a parent, not a view; no generation moves).  Refused

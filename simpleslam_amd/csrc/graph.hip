@@ -3,6 +3,8 @@
 // Backend::optimHandler (backend/src/Backend.cpp:224-347 of the reference) relinearises a GTSAM graph of one prior and one BetweenFactor per key
 // frame and per loop on every key-frame event.  Here the graph lives in HBM: one launch linearises every factor (one factor per lane), one
 // launch holds the whole preconditioned conjugate gradient of a Levenberg-Marquardt trial step on ONE workgroup, one launch retracts.
+// Two preconditioners, a kernel each: every pose's diagonal block (graph_solve_kernel), or the spanning forest of the between factors
+// solved exactly by a block Cholesky and two sweeps along a path schedule planned on the host (graph_solve_tree_kernel, graph_forest.h).
 // No atomics anywhere: every sum is taken in a fixed order, so the same graph gives the same bits on every run.
 #include "graph_dev.h"
 #include "graph_math.h"
@@ -142,6 +144,204 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* lds) {
     }
 }
 
+// one pose's gradient g_p and its diagonal block of the preconditioner (lower triangle), over p's incident factors in CSR order:
+// lambda I + sum J^T Omega J -- over every factor for the block-diagonal preconditioner, over the priors and the tree edges (in_m) for the
+// tree's.  g takes every factor either way.
+template <bool TREE>
+__device__ __forceinline__ void pose_blocks(int p, const Factors& f, const Lin& lin, const Csr& csr, const unsigned char* __restrict__ in_m,
+                                            double lambda, double* g, double* D) {
+    const int F = f.F;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) g[k] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) D[gm::tri(i, j)] = (i == j) ? lambda : 0.0;
+    const int lo = csr.row_ptr[p], hi = csr.row_ptr[p + 1];
+    for (int i = lo; i < hi; ++i) {
+        const int ent = csr.ent[i];
+        const int e = ent >> 1;
+        const double* __restrict__ J = (ent & 1) ? lin.jt : lin.jf;
+        const double* __restrict__ WJ = (ent & 1) ? lin.wjt : lin.wjf;
+        const bool in_block = TREE ? (in_m[e] != 0) : true;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {      // row k of J and of Omega J: a rank-one update of the block, one term of g
+            double jr[6], wr6[6];
+#pragma unroll
+            for (int m = 0; m < 6; ++m) { jr[m] = J[(size_t)(k * 6 + m) * F + e]; wr6[m] = WJ[(size_t)(k * 6 + m) * F + e]; }
+            const double wrk = lin.wr[(size_t)k * F + e];
+#pragma unroll
+            for (int m = 0; m < 6; ++m) g[m] += jr[m] * wrk;
+            if (in_block) {
+#pragma unroll
+                for (int r = 0; r < 6; ++r)
+#pragma unroll
+                    for (int c = 0; c <= r; ++c) D[gm::tri(r, c)] += jr[r] * wr6[c];
+            }
+        }
+    }
+}
+
+// ---- the tree preconditioner: M = lambda I + the priors + the forest's between factors, block Cholesky from the leaves to the roots -------
+// The schedule is graph_forest.h's: one lane walks one path, the paths of a round run on different lanes, a barrier separates the rounds.
+// A node gathers from its heavy child (the position before it, carried in registers) and then from its light children in ascending id,
+// whose results an earlier round finished: nothing is scattered, the order of every sum is fixed.
+//
+// On entry L[q] holds position q's diagonal block of M (a barrier has passed since it was written).  On return L[q] is the Cholesky factor
+// of D_q = A_qq - sum over children G_c A_cq, t.G[q] = A_pq D_q^-1 for the parent p, and a barrier has passed.  false: some D_q of this
+// lane's was not positive definite.
+__device__ __forceinline__ bool tree_factorize(const Factors& f, const Lin& lin, const Tree& t, double* __restrict__ L, int tid) {
+    const int F = f.F;
+    bool ok = true;
+    for (int r = 0; r < t.R; ++r) {
+        for (int path = t.rptr[r] + tid; path < t.rptr[r + 1]; path += kSolveThreads) {
+            const int q0 = t.pbeg[path], q1 = t.pbeg[path + 1];
+            double Sp[21];      // G_c A_cq of the node below
+#pragma unroll
+            for (int k = 0; k < 21; ++k) Sp[k] = 0.0;
+            for (int q = q0; q < q1; ++q) {
+                double D[21];
+#pragma unroll
+                for (int k = 0; k < 21; ++k) D[k] = L[(size_t)q * 21 + k] - Sp[k];
+                for (int i = t.lptr[q]; i < t.lptr[q + 1]; ++i) {
+                    const int c = t.lch[i];
+#pragma unroll
+                    for (int k = 0; k < 21; ++k) D[k] -= t.S[(size_t)c * 21 + k];
+                }
+                ok = gm::chol6(D) && ok;
+#pragma unroll
+                for (int k = 0; k < 21; ++k) L[(size_t)q * 21 + k] = D[k];
+                const int ent = t.tf[q];
+                if (ent < 0) continue;      // a root
+                const int e = ent >> 1;
+                const double* __restrict__ J = (ent & 1) ? lin.jt : lin.jf;        // this node's end
+                const double* __restrict__ WJ = (ent & 1) ? lin.wjf : lin.wjt;     // Omega J of the parent's end
+                double A[36];      // A_qp = J_q^T Omega J_p, rows in this node's space
+#pragma unroll
+                for (int k = 0; k < 36; ++k) A[k] = 0.0;
+#pragma unroll
+                for (int m = 0; m < 6; ++m) {
+                    double jr[6], wr6[6];
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) { jr[k] = J[(size_t)(m * 6 + k) * F + e]; wr6[k] = WJ[(size_t)(m * 6 + k) * F + e]; }
+#pragma unroll
+                    for (int k = 0; k < 6; ++k)
+#pragma unroll
+                        for (int j = 0; j < 6; ++j) A[k * 6 + j] += jr[k] * wr6[j];
+                }
+                double G[36];      // row j: D_q^-1 (column j of A_qp)
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    double a[6], s[6];
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) a[k] = A[k * 6 + j];
+                    gm::chol6_solve(D, a, s);
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) { G[j * 6 + k] = s[k]; t.G[(size_t)q * 36 + j * 6 + k] = s[k]; }
+                }
+#pragma unroll
+                for (int i = 0; i < 6; ++i)
+#pragma unroll
+                    for (int j = 0; j <= i; ++j) {
+                        double s = 0.0;
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) s += G[i * 6 + k] * A[k * 6 + j];
+                        Sp[gm::tri(i, j)] = s;
+                    }
+                if (q == q1 - 1) {      // a head: its parent reads it from memory in a later round
+#pragma unroll
+                    for (int k = 0; k < 21; ++k) t.S[(size_t)q * 21 + k] = Sp[k];
+                }
+            }
+        }
+        __syncthreads();
+    }
+    return ok;
+}
+
+// z = M^-1 r: r by pose (a barrier has passed since it was written), z in t.y by POSITION; a barrier has passed on return.
+// Forward y_q = r_q - sum over children G_c y_c, rounds ascending; then D_q^-1 y_q for all positions at once, so that only the 6x6 product
+// is on the serial chain of the way down, z_q = D_q^-1 y_q - G_q^T z_parent, rounds descending.
+__device__ __forceinline__ void tree_solve(int N, const Tree& t, const double* __restrict__ L, const double* __restrict__ r, int tid) {
+    for (int q = tid; q < N; q += kSolveThreads) {
+        const int p = t.node[q];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) t.y[(size_t)q * 6 + k] = r[(size_t)p * 6 + k];
+    }
+    __syncthreads();
+    for (int rd = 0; rd < t.R; ++rd) {
+        for (int path = t.rptr[rd] + tid; path < t.rptr[rd + 1]; path += kSolveThreads) {
+            const int q0 = t.pbeg[path], q1 = t.pbeg[path + 1];
+            double yp[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) yp[k] = 0.0;
+            for (int q = q0; q < q1; ++q) {
+                double y[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) y[k] = t.y[(size_t)q * 6 + k];
+                if (q > q0) {
+                    const double* __restrict__ G = t.G + (size_t)(q - 1) * 36;
+#pragma unroll
+                    for (int j = 0; j < 6; ++j)
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) y[j] -= G[j * 6 + k] * yp[k];
+                }
+                for (int i = t.lptr[q]; i < t.lptr[q + 1]; ++i) {
+                    const int c = t.lch[i];
+                    const double* __restrict__ G = t.G + (size_t)c * 36;
+                    double yc[6];
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) yc[k] = t.y[(size_t)c * 6 + k];
+#pragma unroll
+                    for (int j = 0; j < 6; ++j)
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) y[j] -= G[j * 6 + k] * yc[k];
+                }
+#pragma unroll
+                for (int k = 0; k < 6; ++k) { t.y[(size_t)q * 6 + k] = y[k]; yp[k] = y[k]; }
+            }
+        }
+        __syncthreads();
+    }
+    for (int q = tid; q < N; q += kSolveThreads) {
+        double Lq[21], y[6], w[6];
+#pragma unroll
+        for (int k = 0; k < 21; ++k) Lq[k] = L[(size_t)q * 21 + k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) y[k] = t.y[(size_t)q * 6 + k];
+        gm::chol6_solve(Lq, y, w);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) t.y[(size_t)q * 6 + k] = w[k];
+    }
+    __syncthreads();
+    for (int rd = t.R - 1; rd >= 0; --rd) {
+        for (int path = t.rptr[rd] + tid; path < t.rptr[rd + 1]; path += kSolveThreads) {
+            const int q0 = t.pbeg[path], q1 = t.pbeg[path + 1];
+            const int up = t.up[q1 - 1];
+            bool has = up >= 0;
+            double zp[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) zp[k] = has ? t.y[(size_t)up * 6 + k] : 0.0;
+            for (int q = q1 - 1; q >= q0; --q) {
+                double z[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) z[k] = t.y[(size_t)q * 6 + k];
+                if (has) {
+                    const double* __restrict__ G = t.G + (size_t)q * 36;
+#pragma unroll
+                    for (int j = 0; j < 6; ++j)
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) z[k] -= G[j * 6 + k] * zp[j];
+                }
+#pragma unroll
+                for (int k = 0; k < 6; ++k) { t.y[(size_t)q * 6 + k] = z[k]; zp[k] = z[k]; }
+                has = true;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // ---- solve: the whole PCG of one trial step on one workgroup ------------------------------------------------------------------------------
 // (H + lambda I) x = -g with H = sum J^T Omega J, g = sum J^T Omega r; preconditioner: the inverse of every pose's 6x6 diagonal block.
 // Threads stride over the poses and over the factors.  Writes are made visible to the workgroup by the barriers: one workgroup is one CU.
@@ -154,7 +354,7 @@ __global__ __launch_bounds__(kSolveThreads) void graph_solve_kernel(const int N,
     // set-up: g_p, the diagonal block, its Cholesky factor; x = 0, res = -g, z = M^-1 res, dir = z
     double acc[2] = {0.0, 0.0};      // |g|^2, res . z
     for (int p = tid; p < N; p += kSolveThreads) {
-        double g[6], D[21];
+        double g[6], D[21];      // (pose_blocks<false> below, kept inline: this kernel's code and registers are as they were measured)
 #pragma unroll
         for (int k = 0; k < 6; ++k) g[k] = 0.0;
 #pragma unroll
@@ -255,6 +455,145 @@ __global__ __launch_bounds__(kSolveThreads) void graph_solve_kernel(const int N,
     }
 }
 
+// The same PCG with the tree preconditioner.  M is factorised once per launch (lambda and the linearisation change per trial step); a block
+// that is not positive definite ends the launch with flag 2 and x = 0, as a curvature that is not positive does.  b.L is indexed by position.
+__global__ __launch_bounds__(kSolveThreads) void graph_solve_tree_kernel(const int N, const Factors f, const Lin lin, const Csr csr, const Tree t,
+                                                                         const double lambda, const int max_it, const double tol, const SolveBufs b,
+                                                                         double* __restrict__ status) {
+    __shared__ double red_a[2 * 16], red_b[2 * 16];
+    const int tid = threadIdx.x;
+
+    // set-up: g_p and the pose's block of M; x = 0, res = -g
+    double gg[1] = {0.0};
+    for (int q = tid; q < N; q += kSolveThreads) {
+        const int p = t.node[q];
+        double g[6], D[21];
+        pose_blocks<true>(p, f, lin, csr, t.in_m, lambda, g, D);
+#pragma unroll
+        for (int k = 0; k < 21; ++k) b.L[(size_t)q * 21 + k] = D[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            b.x[(size_t)p * 6 + k] = 0.0;
+            b.res[(size_t)p * 6 + k] = -g[k];
+            gg[0] += g[k] * g[k];
+        }
+    }
+    block_sum(gg, red_b);      // (its barrier stands between the blocks' writes and the factorisation)
+    const bool ok = tree_factorize(f, lin, t, b.L, tid);
+    const int bad = __syncthreads_or(ok ? 0 : 1);
+    const double gnorm = sqrt(gg[0]);
+    double relres = (gnorm > 0.0) ? 1.0 : 0.0;
+    int it = 0, flag = (gnorm > 0.0) ? 1 : 0;
+    if (gnorm > 0.0 && relres <= tol) flag = 0;
+    if (bad) flag = 2;
+    double rz = 0.0;
+    if (flag == 1) {      // z = M^-1 res, dir = z
+        tree_solve(N, t, b.L, b.res, tid);
+        double acc[1] = {0.0};
+        for (int p = tid; p < N; p += kSolveThreads) {
+            const int q = t.pos_of[p];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const double z = t.y[(size_t)q * 6 + k];
+                b.dir[(size_t)p * 6 + k] = z;
+                acc[0] += b.res[(size_t)p * 6 + k] * z;
+            }
+        }
+        block_sum(acc, red_a);
+        rz = acc[0];
+    }
+
+    while (flag == 1 && it < max_it) {
+        edge_pass(f, lin, b.dir, b.u, tid, kSolveThreads);
+        __syncthreads();
+        double pap[1] = {0.0};
+        for (int p = tid; p < N; p += kSolveThreads) {
+            double d[6], y[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) d[k] = b.dir[(size_t)p * 6 + k];
+            pose_product(p, f, lin, csr, lambda, d, b.u, y);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) { b.ap[(size_t)p * 6 + k] = y[k]; pap[0] += d[k] * y[k]; }
+        }
+        block_sum(pap, red_b);
+        if (!(pap[0] > 0.0)) { flag = 2; break; }
+        const double alpha = rz / pap[0];
+        double rr[1] = {0.0};      // |res|^2 after the update
+        for (int p = tid; p < N; p += kSolveThreads) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                b.x[(size_t)p * 6 + k] += alpha * b.dir[(size_t)p * 6 + k];
+                const double res = b.res[(size_t)p * 6 + k] - alpha * b.ap[(size_t)p * 6 + k];
+                b.res[(size_t)p * 6 + k] = res;
+                rr[0] += res * res;
+            }
+        }
+        block_sum(rr, red_a);
+        ++it;
+        relres = sqrt(rr[0]) / gnorm;
+        if (!(relres > tol)) { flag = 0; break; }
+        tree_solve(N, t, b.L, b.res, tid);
+        double nz[1] = {0.0};      // res . z
+        for (int p = tid; p < N; p += kSolveThreads) {
+            const int q = t.pos_of[p];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) nz[0] += b.res[(size_t)p * 6 + k] * t.y[(size_t)q * 6 + k];
+        }
+        block_sum(nz, red_b);
+        const double beta = nz[0] / rz;
+        rz = nz[0];
+        for (int p = tid; p < N; p += kSolveThreads) {
+            const int q = t.pos_of[p];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) b.dir[(size_t)p * 6 + k] = t.y[(size_t)q * 6 + k] + beta * b.dir[(size_t)p * 6 + k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        status[1] = relres;
+        int* w = reinterpret_cast<int*>(status + 2);
+        w[0] = it;
+        w[1] = flag;
+    }
+}
+
+// pcr_graph_precondition: z = M^-1 r by the factorisation and the sweeps of the solve of that kind; r in b.res, z into b.z, both by pose
+template <bool TREE>
+__global__ __launch_bounds__(kSolveThreads) void graph_precondition_kernel(const int N, const Factors f, const Lin lin, const Csr csr, const Tree t,
+                                                                           const double lambda, const SolveBufs b, int* __restrict__ flag) {
+    const int tid = threadIdx.x;
+    bool ok = true;
+    if (TREE) {
+        for (int q = tid; q < N; q += kSolveThreads) {
+            double g[6], D[21];
+            pose_blocks<true>(t.node[q], f, lin, csr, t.in_m, lambda, g, D);
+#pragma unroll
+            for (int k = 0; k < 21; ++k) b.L[(size_t)q * 21 + k] = D[k];
+        }
+        __syncthreads();
+        ok = tree_factorize(f, lin, t, b.L, tid);
+        tree_solve(N, t, b.L, b.res, tid);
+        for (int p = tid; p < N; p += kSolveThreads) {
+            const int q = t.pos_of[p];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) b.z[(size_t)p * 6 + k] = t.y[(size_t)q * 6 + k];
+        }
+    } else {
+        for (int p = tid; p < N; p += kSolveThreads) {
+            double g[6], D[21], res[6], z[6];
+            pose_blocks<false>(p, f, lin, csr, nullptr, lambda, g, D);
+            ok = gm::chol6(D) && ok;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) res[k] = b.res[(size_t)p * 6 + k];
+            gm::chol6_solve(D, res, z);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) b.z[(size_t)p * 6 + k] = z[k];
+        }
+    }
+    const int bad = __syncthreads_or(ok ? 0 : 1);
+    if (tid == 0) flag[0] = bad ? 2 : 0;
+}
+
 __global__ __launch_bounds__(kSolveThreads) void graph_apply_kernel(const int N, const Factors f, const Lin lin, const Csr csr, const double lambda,
                                                                     const double* __restrict__ x, double* __restrict__ y, double* __restrict__ u) {
     edge_pass(f, lin, x, u, threadIdx.x, kSolveThreads);
@@ -297,6 +636,19 @@ hipError_t launch_linearize(const double* poses, const Factors& f, const Lin& ou
 hipError_t launch_solve(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, int max_it, double tol, const SolveBufs& b,
                         double* status, hipStream_t s) {
     hipLaunchKernelGGL(graph_solve_kernel, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, lambda, max_it, tol, b, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_solve_tree(int N, const Factors& f, const Lin& lin, const Csr& csr, const Tree& t, double lambda, int max_it, double tol,
+                             const SolveBufs& b, double* status, hipStream_t s) {
+    hipLaunchKernelGGL(graph_solve_tree_kernel, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, t, lambda, max_it, tol, b, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_precondition(int N, const Factors& f, const Lin& lin, const Csr& csr, const Tree* t, double lambda, const SolveBufs& b, int* flag,
+                               hipStream_t s) {
+    if (t) hipLaunchKernelGGL(graph_precondition_kernel<true>, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, *t, lambda, b, flag);
+    else hipLaunchKernelGGL(graph_precondition_kernel<false>, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, Tree{}, lambda, b, flag);
     return hipGetLastError();
 }
 

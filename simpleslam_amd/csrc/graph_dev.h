@@ -31,6 +31,24 @@ struct Csr { const int* row_ptr; const int* ent; };
 // Work vectors of the solve, pose-major ([p * 6 + k]); L: the preconditioner's factors [p * 21 + k]; u: per factor [e * 6 + k]
 struct SolveBufs { double *x, *res, *z, *dir, *ap, *u, *L; };
 
+// The tree preconditioner's schedule (graph_forest.h: plan_forest) and its factors, indexed by POSITION: the nodes path by path, paths by
+// round, inside a path from the bottom node to the head, so that a node's heavy child is the position before it.
+struct Tree {
+    int R;                    // rounds
+    const int* node;          // [N] position -> pose
+    const int* pos_of;        // [N] pose -> position
+    const int* up;            // [N] position of the parent, -1 for a root
+    const int* tf;            // [N] the tree factor: factor * 2 + (1: this node is its "to" end), -1 for a root
+    const int* lptr;          // [N + 1] light children of a position: lch[lptr[q] .. lptr[q + 1]), positions, ascending pose id
+    const int* lch;
+    const int* pbeg;          // [paths + 1] path k holds positions [pbeg[k], pbeg[k + 1])
+    const int* rptr;          // [R + 1] round r holds paths [rptr[r], rptr[r + 1])
+    const unsigned char* in_m;      // [F] the factor belongs to M: a prior or a tree edge
+    double* G;                // [N][36] G_c = A_pc D_c^-1, row-major (p: the parent)
+    double* S;                // [N][21] G_c A_cp, lower triangle: what the child takes from its parent's block
+    double* y;                // [N][6] the sweeps' vector
+};
+
 // status (3 doubles, one 24-byte read per trial step): [0] chi2 of the last linearisation folded into it, [1] the solve's final
 // |residual| / |g|, [2] two ints: PCG iterations, flag (0: tolerance met, 1: the cap ended it, 2: the curvature p^T A p was not positive)
 constexpr int kLinBlock = 256;
@@ -42,6 +60,13 @@ hipError_t launch_linearize(const double* poses, const Factors& f, const Lin& ou
 // delta (= bufs.x) <- PCG on (H + lambda I) delta = -g, one workgroup; status[1], status[2]
 hipError_t launch_solve(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, int max_it, double tol, const SolveBufs& b,
                         double* status, hipStream_t s);
+// the same solve preconditioned by the spanning forest: M = lambda I + priors + tree edges, factorised once per launch (b.L by position)
+hipError_t launch_solve_tree(int N, const Factors& f, const Lin& lin, const Csr& csr, const Tree& t, double lambda, int max_it, double tol,
+                             const SolveBufs& b, double* status, hipStream_t s);
+// z = M^-1 r by the factorisation and the sweeps of the solve of that kind (tree: the forest's; otherwise the diagonal blocks'); flag[0] = 2 when a
+// block was not positive definite, else 0.  b.L, b.res (= r) and b.z are used.
+hipError_t launch_precondition(int N, const Factors& f, const Lin& lin, const Csr& csr, const Tree* t, double lambda, const SolveBufs& b, int* flag,
+                               hipStream_t s);
 // y = (H + lambda I) x by the solve's own two passes (b.u is used)
 hipError_t launch_apply(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, const double* x, double* y, double* u, hipStream_t s);
 // out[p] = poses[p] * Exp(delta[p])

@@ -19,6 +19,7 @@
 
 #include "../../include/pcr_hip.h"
 #include "graph_dev.h"
+#include "graph_forest.h"
 #include "graph_math.h"
 #include "small_math.h"
 
@@ -63,6 +64,9 @@ struct pcr_graph {
     std::vector<Factor> priors, betweens;
     bool dirty = false;                      // something was added since the last optimize
     bool dirty_factors = true;               // the device's factor arrays and CSR are older than the lists
+    bool dirty_forest = true;                // ... and so is `forest` (poses or factors were added since it was planned)
+    bool dirty_tree_dev = true;              // ... and so are the device's copies of its schedule
+    ForestPlan forest;                       // the tree preconditioner's spanning forest and schedule (graph_forest.h)
     size_t n_uploaded = 0;
     bool host_stale = false;
     double last_chi2 = 0.0;
@@ -70,7 +74,8 @@ struct pcr_graph {
     std::string err;
     // device side
     hipStream_t stream = nullptr;
-    DBuf d_poses[2], d_lin[2], d_from, d_to, d_z, d_omega, d_rowptr, d_ent, d_vec, d_u, d_partial, d_status;
+    DBuf d_poses[2], d_lin[2], d_from, d_to, d_z, d_omega, d_rowptr, d_ent, d_vec, d_u, d_partial, d_status, d_tree_i, d_tree_d, d_in_m;
+    size_t tree_lch = 0, tree_paths = 0;     // entries of the device's light-children list and paths
     int cur = 0;
     size_t F_dev = 0;
     double* h_status = nullptr;              // page-locked, 3 doubles
@@ -253,6 +258,69 @@ static SolveBufs dev_bufs(const pcr_graph* g, size_t N) {
     return b;
 }
 
+// The tree preconditioner's forest, planned anew only when poses or factors were added since it was made.  ONLY after validate().
+static const ForestPlan& forest_of(pcr_graph* g) {
+    if (g->dirty_forest) {
+        std::vector<long long> from(g->betweens.size()), to(g->betweens.size()), prior(g->priors.size());
+        for (size_t e = 0; e < g->betweens.size(); ++e) { from[e] = g->betweens[e].from; to[e] = g->betweens[e].to; }
+        for (size_t i = 0; i < g->priors.size(); ++i) prior[i] = g->priors[i].to;
+        g->forest = plan_forest(n_poses(g), from.data(), to.data(), from.size(), prior.data(), prior.size());
+        g->dirty_forest = false;
+        g->dirty_tree_dev = true;
+    }
+    return g->forest;
+}
+
+// ... and its schedule on the device, by position (graph_dev.h: Tree).  After upload().
+static int upload_tree(pcr_graph* g) {
+    const ForestPlan& fp = forest_of(g);
+    const size_t N = n_poses(g), P = g->priors.size(), F = P + g->betweens.size();
+    G_TRY(g->d_tree_d.reserve((N * (36 + 21 + 6) + 8) * sizeof(double), false));
+    if (!g->dirty_tree_dev) return 0;
+    std::vector<int> up(N), tf(N), lptr(N + 1, 0), lch;
+    for (size_t q = 0; q < N; ++q) {
+        const int p = fp.node[q];
+        up[q] = fp.parent[p] >= 0 ? fp.pos_of[fp.parent[p]] : -1;
+        tf[q] = fp.tree_factor[p] >= 0 ? (int)((P + (size_t)fp.tree_factor[p]) * 2 + fp.is_to[p]) : -1;
+        for (int k = fp.child_ptr[p]; k < fp.child_ptr[p + 1]; ++k)
+            if (fp.child[k] != fp.heavy[p]) lch.push_back(fp.pos_of[fp.child[k]]);
+        lptr[q + 1] = (int)lch.size();
+    }
+    std::vector<unsigned char> in_m(F + 1, 1);
+    for (size_t e = 0; e < g->betweens.size(); ++e) in_m[P + e] = fp.in_tree[e];
+    // one int buffer: node, pos_of, up, tf (N each), lptr (N + 1), lch, pbeg (paths + 1), rptr (R + 1)
+    std::vector<int> all;
+    all.reserve(5 * N + lch.size() + fp.path_ptr.size() + fp.round_ptr.size() + 8);
+    all.insert(all.end(), fp.node.begin(), fp.node.end());
+    all.insert(all.end(), fp.pos_of.begin(), fp.pos_of.end());
+    all.insert(all.end(), up.begin(), up.end());
+    all.insert(all.end(), tf.begin(), tf.end());
+    all.insert(all.end(), lptr.begin(), lptr.end());
+    all.insert(all.end(), lch.begin(), lch.end());
+    all.insert(all.end(), fp.path_ptr.begin(), fp.path_ptr.end());
+    all.insert(all.end(), fp.round_ptr.begin(), fp.round_ptr.end());
+    g->tree_lch = lch.size();
+    g->tree_paths = fp.path_ptr.size() - 1;
+    G_TRY(g->d_tree_i.reserve(all.size() * sizeof(int), false));
+    G_TRY(g->d_in_m.reserve(in_m.size(), false));
+    G_TRY(hipMemcpy(g->d_tree_i.p, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
+    G_TRY(hipMemcpy(g->d_in_m.p, in_m.data(), in_m.size(), hipMemcpyHostToDevice));
+    g->dirty_tree_dev = false;
+    return 0;
+}
+
+static Tree dev_tree(const pcr_graph* g, size_t N) {
+    Tree t;
+    const int* i = g->d_tree_i.as<int>();
+    t.R = g->forest.rounds();
+    t.node = i; t.pos_of = i + N; t.up = i + 2 * N; t.tf = i + 3 * N; t.lptr = i + 4 * N; t.lch = i + 5 * N + 1;
+    t.pbeg = t.lch + g->tree_lch; t.rptr = t.pbeg + g->tree_paths + 1;
+    t.in_m = g->d_in_m.as<unsigned char>();
+    double* d = g->d_tree_d.as<double>();
+    t.G = d; t.S = d + 36 * N; t.y = d + 57 * N;
+    return t;
+}
+
 // quaternion (x, y, z, w) of a rotation, Eigen's Quaternion(Matrix3) (the trace branch, or the branch of the largest diagonal element)
 static void rot_to_quat(const double* T, double q[4]) {
 #define M_(i, j) T[(j) * 4 + (i)]
@@ -345,7 +413,7 @@ int pcr_graph_add_poses(pcr_graph* g, const double* poses16, size_t count) {
     if (n_poses(g) + count > 0x7fffff00u / 36) return gfail(g, "pcr_graph_add_poses: more poses than the device's 32-bit indices address");
     g->poses.insert(g->poses.end(), poses16, poses16 + 16 * count);
     g->dirty = true;
-    g->dirty_factors = true;      // (the CSR has a row per pose)
+    g->dirty_factors = true; g->dirty_forest = true; g->dirty_tree_dev = true;      // (the CSR has a row per pose)
     return 0;
 }
 
@@ -360,7 +428,7 @@ static int add_factor(pcr_graph* g, const char* what, long long from, size_t to,
     expand_info(info21, f.info);
     (from < 0 ? g->priors : g->betweens).push_back(f);
     g->dirty = true;
-    g->dirty_factors = true;
+    g->dirty_factors = true; g->dirty_forest = true; g->dirty_tree_dev = true;
     return 0;
 }
 
@@ -398,7 +466,7 @@ int pcr_graph_clear(pcr_graph* g) {
     if (!g) return 1;
     g->err.clear();
     g->poses.clear(); g->priors.clear(); g->betweens.clear();
-    g->dirty = false; g->dirty_factors = true; g->n_uploaded = 0; g->host_stale = false; g->F_dev = 0; g->last_chi2 = 0.0; g->last_rel_tol = g->last_abs_tol = 0.0;
+    g->dirty = false; g->dirty_factors = true; g->dirty_forest = true; g->dirty_tree_dev = true; g->n_uploaded = 0; g->host_stale = false; g->F_dev = 0; g->last_chi2 = 0.0; g->last_rel_tol = g->last_abs_tol = 0.0;
     return 0;
 }
 
@@ -411,6 +479,7 @@ void pcr_graph_default_params(pcr_graph_params* p) {
     p->lambda_init = 1e-5; p->lambda_factor = 10.0; p->lambda_max = 1e5;
     p->pcg_max_iterations = 0;      // max(100, 10 * poses)
     p->pcg_rel_tol = 1e-10;
+    p->pcg_preconditioner = PCR_GRAPH_PRECOND_BLOCK_JACOBI;
 }
 
 int pcr_graph_poses(const pcr_graph* gc, size_t first, size_t count, double* poses16) {
@@ -503,6 +572,57 @@ int pcr_graph_apply(pcr_graph* g, double lambda, const double* x, double* y) {
     return 0;
 }
 
+int pcr_graph_tree(const pcr_graph* gc, int64_t* parent, size_t n, size_t* n_tree_edges, size_t* n_other_edges) {
+    pcr_graph* g = const_cast<pcr_graph*>(gc);
+    if (!g) return 1;
+    g->err.clear();
+    const size_t N = n_poses(g);
+    if (validate(g, "pcr_graph_tree")) return 1;
+    const long long lone = first_pose_without_prior(g);
+    if (lone >= 0)
+        return gfail(g, "pcr_graph_tree: pose " + std::to_string(lone) + " lies in a connected component without a prior: the system would be singular");
+    if (parent && n < N) return gfail(g, "pcr_graph_tree: parent has room for " + std::to_string(n) + " entries, the graph holds " + std::to_string(N) + " poses");
+    const ForestPlan& fp = forest_of(g);
+    if (parent) for (size_t p = 0; p < N; ++p) parent[p] = fp.parent[p];
+    if (n_tree_edges) *n_tree_edges = fp.n_tree;
+    if (n_other_edges) *n_other_edges = fp.n_other;
+    return 0;
+}
+
+int pcr_graph_precondition(pcr_graph* g, double lambda, int kind, const double* r, double* z) {
+    if (!g) return 1;
+    g->err.clear();
+    if (kind != PCR_GRAPH_PRECOND_BLOCK_JACOBI && kind != PCR_GRAPH_PRECOND_TREE)
+        return gfail(g, "pcr_graph_precondition: unknown preconditioner " + std::to_string(kind) + " (PCR_GRAPH_PRECOND_BLOCK_JACOBI = 0, PCR_GRAPH_PRECOND_TREE = 1)");
+    if (validate(g, "pcr_graph_precondition")) return 1;
+    const long long lone = first_pose_without_prior(g);
+    if (lone >= 0)
+        return gfail(g, "pcr_graph_precondition: pose " + std::to_string(lone) + " lies in a connected component without a prior: the system would be singular");
+    if (g->host_only) return gfail(g, "pcr_graph_precondition: a PCR_GRAPH_HOST graph has no device: the sweeps are the solve kernel's");
+    const size_t N = n_poses(g);
+    if (N == 0) return 0;
+    if (!r || !z) return gfail(g, "pcr_graph_precondition: NULL vector");
+    if (!(lambda >= 0.0) || !std::isfinite(lambda)) return gfail(g, "pcr_graph_precondition: lambda must be finite and not negative");
+    if (upload(g)) return 1;
+    const bool tree = kind == PCR_GRAPH_PRECOND_TREE;
+    if (tree && upload_tree(g)) return 1;
+    const Tree tr = tree ? dev_tree(g, N) : Tree{};
+    const size_t F = g->F_dev;
+    const Lin lin = lin_view(g->d_lin[g->cur].as<double>(), F);
+    const SolveBufs b = dev_bufs(g, N);
+    int* d_flag = reinterpret_cast<int*>(g->d_status.as<double>() + 3);
+    G_TRY(launch_linearize(g->d_poses[g->cur].as<double>(), dev_factors(g), lin, g->d_partial.as<double>(), g->d_status.as<double>(), g->stream));
+    G_TRY(hipMemcpyAsync(b.res, r, 6 * N * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    G_TRY(launch_precondition((int)N, dev_factors(g), lin, dev_csr(g), tree ? &tr : nullptr, lambda, b, d_flag, g->stream));
+    G_TRY(hipMemcpyAsync(z, b.z, 6 * N * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    G_TRY(hipMemcpyAsync(g->h_status + 3, d_flag, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+    G_TRY(hipStreamSynchronize(g->stream));
+    int flag = 0;
+    memcpy(&flag, g->h_status + 3, sizeof flag);
+    if (flag) return gfail(g, "pcr_graph_precondition: a block of the preconditioner is not positive definite");
+    return 0;
+}
+
 int pcr_graph_optimize(pcr_graph* g, const pcr_graph_params* params, pcr_graph_result* out) {
     if (!g) return 1;
     g->err.clear();
@@ -518,6 +638,9 @@ int pcr_graph_optimize(pcr_graph* g, const pcr_graph_params* params, pcr_graph_r
     if (!(prm.lambda_factor > 1.0) || !(prm.lambda_init > 0.0) || !std::isfinite(prm.lambda_max) || prm.max_iterations < 0 || prm.pcg_max_iterations < 0 ||
         !(prm.pcg_rel_tol >= 0.0) || !(prm.rel_tol >= 0.0) || !(prm.abs_tol >= 0.0))
         return gfail(g, "pcr_graph_optimize: parameters out of range (lambda_factor > 1, lambda_init > 0, tolerances and caps >= 0)");
+    if (prm.pcg_preconditioner != PCR_GRAPH_PRECOND_BLOCK_JACOBI && prm.pcg_preconditioner != PCR_GRAPH_PRECOND_TREE)
+        return gfail(g, "pcr_graph_optimize: unknown pcg_preconditioner " + std::to_string(prm.pcg_preconditioner) +
+                            " (PCR_GRAPH_PRECOND_BLOCK_JACOBI = 0, PCR_GRAPH_PRECOND_TREE = 1)");
     const size_t N = n_poses(g);
     if (N == 0 && g->priors.empty() && g->betweens.empty()) { if (out) *out = res; return 0; }      // an empty graph: nothing to do
     if (validate(g, "pcr_graph_optimize")) return 1;
@@ -537,6 +660,9 @@ int pcr_graph_optimize(pcr_graph* g, const pcr_graph_params* params, pcr_graph_r
     double last_old[16];
     if (current_pose(g, N - 1, last_old)) return 1;
     if (upload(g)) return 1;
+    const bool tree = prm.pcg_preconditioner == PCR_GRAPH_PRECOND_TREE;
+    if (tree && upload_tree(g)) return 1;
+    const Tree tr = tree ? dev_tree(g, N) : Tree{};
     const size_t F = g->F_dev;
     const Factors fac = dev_factors(g);
     const Csr csr = dev_csr(g);
@@ -558,7 +684,8 @@ int pcr_graph_optimize(pcr_graph* g, const pcr_graph_params* params, pcr_graph_r
     while (res.iterations < prm.max_iterations) {
         const int trial = g->cur ^ 1;
         const Lin lin_trial = lin_view(g->d_lin[trial].as<double>(), F);
-        G_TRY(launch_solve((int)N, fac, lin, csr, lambda, cap, prm.pcg_rel_tol, b, d_status, g->stream));
+        if (tree) G_TRY(launch_solve_tree((int)N, fac, lin, csr, tr, lambda, cap, prm.pcg_rel_tol, b, d_status, g->stream));
+        else G_TRY(launch_solve((int)N, fac, lin, csr, lambda, cap, prm.pcg_rel_tol, b, d_status, g->stream));
         G_TRY(launch_retract((int)N, g->d_poses[g->cur].as<double>(), b.x, g->d_poses[trial].as<double>(), g->stream));
         G_TRY(launch_linearize(g->d_poses[trial].as<double>(), fac, lin_trial, d_partial, d_status, g->stream));
         G_TRY(hipMemcpyAsync(g->h_status, d_status, 3 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
@@ -664,7 +791,7 @@ int pcr_graph_load_g2o(pcr_graph* g, const char* path) {
     g->poses.insert(g->poses.end(), poses.begin(), poses.end());
     g->priors.insert(g->priors.end(), priors.begin(), priors.end());
     g->betweens.insert(g->betweens.end(), betweens.begin(), betweens.end());
-    g->dirty = true; g->dirty_factors = true;
+    g->dirty = true; g->dirty_factors = true; g->dirty_forest = true; g->dirty_tree_dev = true;
     return 0;
 }
 

@@ -643,6 +643,26 @@ public:
         check(pcr_graph_optimize(g_, p, &r));
         return r;
     }
+    // the defaults with another preconditioner: PCR_GRAPH_PRECOND_TREE for a loaded map (an odometry tree plus few loops, thousands of poses)
+    Result optimize(int pcg_preconditioner) {
+        pcr_graph_params p;
+        pcr_graph_default_params(&p);
+        p.pcg_preconditioner = pcg_preconditioner;
+        return optimize(&p);
+    }
+    // the spanning forest the tree preconditioner uses: parent[p], -1 at the roots; the between factors in it, the others (host code)
+    std::vector<int64_t> tree(size_t* n_tree_edges = nullptr, size_t* n_other_edges = nullptr) const {
+        std::vector<int64_t> parent(poses());
+        check(pcr_graph_tree(g_, parent.data(), parent.size(), n_tree_edges, n_other_edges));
+        return parent;
+    }
+    // z = M^-1 r at the current estimates, 6 doubles per pose, by the solve's own factorisation and sweeps
+    std::vector<double> precondition(double lambda, const std::vector<double>& r, int kind = PCR_GRAPH_PRECOND_TREE) {
+        if (r.size() != 6 * poses()) throw std::invalid_argument("PoseGraph::precondition: r holds 6 entries per pose");
+        std::vector<double> z(r.size());
+        check(pcr_graph_precondition(g_, lambda, kind, r.data(), z.data()));
+        return z;
+    }
     size_t poses() const { size_t n = 0; pcr_graph_size(g_, &n, nullptr, nullptr); return n; }
     size_t factors() const { size_t p = 0, b = 0; pcr_graph_size(g_, nullptr, &p, &b); return p + b; }
     std::vector<PCR::pose_t> poses(size_t first, size_t count) const {

@@ -89,6 +89,7 @@ ABI_SYMBOLS = [
     "pcr_graph_create", "pcr_graph_destroy", "pcr_graph_last_error", "pcr_graph_noise", "pcr_graph_add_poses", "pcr_graph_add_prior", "pcr_graph_add_between",
     "pcr_graph_add_between_poses", "pcr_graph_size", "pcr_graph_clear", "pcr_graph_default_params", "pcr_graph_optimize", "pcr_graph_poses",
     "pcr_graph_device_poses", "pcr_graph_linearize", "pcr_graph_apply", "pcr_map_set_poses_from_graph", "pcr_graph_load_g2o", "pcr_graph_save_g2o",
+    "pcr_graph_tree", "pcr_graph_precondition",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -132,7 +133,7 @@ class FrontendInfo(C.Structure):
 class GraphParams(C.Structure):
     """struct pcr_graph_params (include/pcr_hip.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("max_iterations", C.c_int32), ("rel_tol", C.c_double), ("abs_tol", C.c_double), ("lambda_init", C.c_double),
-                ("lambda_factor", C.c_double), ("lambda_max", C.c_double), ("pcg_max_iterations", C.c_int64), ("pcg_rel_tol", C.c_double)]
+                ("lambda_factor", C.c_double), ("lambda_max", C.c_double), ("pcg_max_iterations", C.c_int64), ("pcg_rel_tol", C.c_double), ("pcg_preconditioner", C.c_int32)]
 
 
 class GraphResult(C.Structure):
@@ -332,6 +333,8 @@ def load_library():
     L.pcr_graph_device_poses.restype = vp
     L.pcr_graph_linearize.argtypes = [vp, dp, dp, dp, dp]
     L.pcr_graph_apply.argtypes = [vp, C.c_double, dp, dp]
+    L.pcr_graph_tree.argtypes = [vp, C.POINTER(C.c_int64), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.pcr_graph_precondition.argtypes = [vp, C.c_double, C.c_int, dp, dp]
     L.pcr_map_set_poses_from_graph.argtypes = [vp, vp, C.c_size_t, C.c_size_t]
     L.pcr_graph_load_g2o.argtypes = [vp, C.c_char_p]
     L.pcr_graph_save_g2o.argtypes = [vp, C.c_char_p]
@@ -1421,6 +1424,17 @@ class ScanContext:
 
 GRAPH_HOST = -2                                   # PCR_GRAPH_HOST: a graph without a device (no optimize)
 GRAPH_PRIOR, GRAPH_ODOM, GRAPH_LOOP = 0, 1, 2     # pcr_graph_noise kinds
+GRAPH_PRECOND_BLOCK_JACOBI, GRAPH_PRECOND_TREE = 0, 1      # PCR_GRAPH_PRECOND_*: pcr_graph_params.pcg_preconditioner
+_GRAPH_PRECOND = {"block_jacobi": GRAPH_PRECOND_BLOCK_JACOBI, "tree": GRAPH_PRECOND_TREE}
+
+
+def _graph_precond(kind):
+    """a PCR_GRAPH_PRECOND_* value, or one of the strings "block_jacobi" and "tree" """
+    if isinstance(kind, str):
+        if kind not in _GRAPH_PRECOND:
+            raise ValueError(f"unknown preconditioner {kind!r}: one of {sorted(_GRAPH_PRECOND)}")
+        return _GRAPH_PRECOND[kind]
+    return int(kind)
 
 
 def graph_noise(kind):
@@ -1543,13 +1557,14 @@ class PoseGraph:
 
     def optimize(self, **params):
         """pcr_graph_optimize with pcr_graph_params fields overridden (max_iterations, rel_tol, abs_tol, lambda_init, lambda_factor, lambda_max,
-        pcg_max_iterations, pcg_rel_tol) -> GraphResultView."""
+        pcg_max_iterations, pcg_rel_tol, pcg_preconditioner -- GRAPH_PRECOND_BLOCK_JACOBI (the default) or GRAPH_PRECOND_TREE, or the strings
+        "block_jacobi" and "tree"; the tree serves an odometry tree with few loops at thousands of poses) -> GraphResultView."""
         p = GraphParams()
         self._lib.pcr_graph_default_params(C.byref(p))
         for k, v in params.items():
             if k == "struct_size" or not hasattr(p, k):
                 raise ValueError(f"unknown pose-graph parameter {k}")
-            setattr(p, k, v)
+            setattr(p, k, _graph_precond(v) if k == "pcg_preconditioner" else v)
         r = GraphResult()
         self._check(self._lib.pcr_graph_optimize(self._g, C.byref(p), C.byref(r)))
         return GraphResultView(r)
@@ -1588,6 +1603,26 @@ class PoseGraph:
         d = C.POINTER(C.c_double)
         self._check(self._lib.pcr_graph_apply(self._g, float(lam), x.ctypes.data_as(d), y.ctypes.data_as(d)))
         return y[:6 * n]
+
+    def tree(self):
+        """pcr_graph_tree -> (parent (poses,) int64 with -1 at the roots, between factors in the forest, the others): the spanning forest of
+        the tree preconditioner.  Host code: it serves a GRAPH_HOST graph."""
+        n = self.size()[0]
+        parent = np.full(max(n, 1), -1, dtype=np.int64)
+        a, b = C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.pcr_graph_tree(self._g, parent.ctypes.data_as(C.POINTER(C.c_int64)), n, C.byref(a), C.byref(b)))
+        return parent[:n], a.value, b.value
+
+    def precondition(self, lam, r, kind=GRAPH_PRECOND_TREE):
+        """pcr_graph_precondition -> z = M^-1 r at the current estimates, r of 6 entries per pose, by the solve's own factorisation and sweeps."""
+        n = self.size()[0]
+        r = np.ascontiguousarray(np.asarray(r, dtype=np.float64).reshape(-1))
+        if r.size != 6 * n:
+            raise ValueError("r must hold 6 entries per pose")
+        z = np.zeros(max(6 * n, 1))
+        d = C.POINTER(C.c_double)
+        self._check(self._lib.pcr_graph_precondition(self._g, float(lam), _graph_precond(kind), r.ctypes.data_as(d), z.ctypes.data_as(d)))
+        return z[:6 * n]
 
     def applyTo(self, submap, first=0, count=None):
         """pcr_map_set_poses_from_graph (Backend.cpp:315-318): the estimates become the key frames' poses."""
