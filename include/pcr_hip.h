@@ -520,6 +520,12 @@ float pcr_sc_shift_yaw(int32_t shift);
  *             acceptance and multiplied on rejection.  It stops when an accepted step lowered chi2 by less than abs_tol or by less than
  *             rel_tol * chi2 (converged), when a rejected step raised chi2 by less than abs_tol (converged), when lambda exceeds
  *             lambda_max, or after max_iterations trial steps.
+ *   robust    a between factor that carries the robust mark (pcr_graph_add_loop, pcr_graph_set_between_robust) enters through the graph's
+ *             kernel (pcr_graph_set_robust_kernel): with s = r^T Omega r it adds rho(s) to chi2, w(s) J^T Omega r to g and w(s) J^T Omega J
+ *             to H, w = rho' (the second-order term is dropped, as g2o and GTSAM drop it).  The cost is 1/2 sum rho; the optimiser accepts
+ *             and stops on sum rho.  Priors and unmarked between factors are never robust.  A between factor that is switched off
+ *             (pcr_graph_set_between_enabled) adds nothing to chi2, g and H and links nothing.  Under the defaults -- kernel NONE, every
+ *             factor on -- everything above is as if this paragraph were absent, bit for bit.
  * Ids are positions: the poses are numbered from 0 in the order they were added.  Factors may be added before their poses; the graph is
  * checked when it is used.  A pcr_graph is used by one thread at a time. */
 typedef struct pcr_graph pcr_graph;
@@ -565,6 +571,35 @@ int pcr_graph_add_prior(pcr_graph* g, size_t id, const double pose[16], const do
 int pcr_graph_add_between(pcr_graph* g, size_t from, size_t to, const double z[16], const double info21[21]);
 /* z = X_from^-1 X_to of the current estimates (Backend::addOdomFactor, Backend.cpp:241-247); both ids must exist */
 int pcr_graph_add_between_poses(pcr_graph* g, size_t from, size_t to, const double info21[21]);
+/* Robust kernels on s = r^T Omega r, d = delta^2 (the square of a residual's Mahalanobis length where the kernel departs from least squares):
+ *   NONE           rho = s                                                   w = 1
+ *   HUBER          rho = s (s <= d), 2 delta sqrt(s) - d beyond              w = 1, delta / sqrt(s)
+ *   GEMAN_MCCLURE  rho = d s / (d + s)                                       w = d^2 / (d + s)^2
+ *   TUKEY          rho = d/3 (1 - (1 - s/d)^3) (s <= d), d/3 beyond          w = (1 - s/d)^2, 0
+ * Cauchy is absent on purpose: its rho needs a logarithm, and this back end calls no math library (that is how host and device agree bit
+ * for bit); these need + - * / sqrt only.  GEMAN_MCCLURE and TUKEY redescend: the optimum they reach depends on the start.  TUKEY reaches
+ * w = 0, so marking odometry edges can leave H singular but for lambda I -- the caller's choice, not refused. */
+enum { PCR_GRAPH_ROBUST_NONE = 0, PCR_GRAPH_ROBUST_HUBER = 1, PCR_GRAPH_ROBUST_GEMAN_MCCLURE = 2, PCR_GRAPH_ROBUST_TUKEY = 3 };
+/* The graph's kernel for its marked between factors (NONE until set; pcr_graph_clear keeps it).  Another kind is refused; delta must be finite
+ * and greater than 0 unless kind is NONE. */
+int pcr_graph_set_robust_kernel(pcr_graph* g, int kind, double delta);
+int pcr_graph_get_robust_kernel(const pcr_graph* g, int* kind, double* delta);
+/* Marks (on != 0) or unmarks between factors first .. first+count-1, by index among the between factors in the order added. */
+int pcr_graph_set_between_robust(pcr_graph* g, size_t first, size_t count, int on);
+/* Switches between factors on or off, same indexing.  One that is off is left out of chi2, g and H, of the connectivity check (a component
+ * that loses its only link to a prior is refused, its first pose named) and of PCR_GRAPH_PRECOND_TREE's forest and pcr_graph_tree's counts.
+ * It stays in pcr_graph_size, in pcr_graph_linearize's r and J and in pcr_graph_save_g2o.  Setting the kernel, a mark or a switch counts as
+ * something new for pcr_graph_optimize. */
+int pcr_graph_set_between_enabled(pcr_graph* g, size_t first, size_t count, int on);
+/* pcr_graph_add_between plus the robust mark (under NONE the mark changes nothing) */
+int pcr_graph_add_loop(pcr_graph* g, size_t from, size_t to, const double z[16], const double info21[21]);
+/* The verdict, at the current estimates, on device and host graphs (bit for bit alike): for between factors first .. first+count-1, s = r^T Omega r
+ * and the weight w the graph's kernel gives at s (1 for an unmarked factor; for one that is off, the weight it would have if switched on),
+ * the mark and the switch.  Any output pointer may be NULL. */
+int pcr_graph_between_weights(pcr_graph* g, size_t first, size_t count, double* s, double* w, uint8_t* robust, uint8_t* enabled);
+/* Host only: rho(s) and w(s) by the function the kernel compiles.  Nonzero for an unknown kind, a delta that pcr_graph_set_robust_kernel
+ * would refuse, or an s that is negative or not a number. */
+int pcr_graph_robust_rho_w(int kind, double delta, double s, double* rho, double* w);
 int pcr_graph_size(const pcr_graph* g, size_t* n_poses, size_t* n_priors, size_t* n_between);
 int pcr_graph_clear(pcr_graph* g);
 void pcr_graph_default_params(pcr_graph_params* p);
@@ -580,7 +615,8 @@ int pcr_graph_poses(const pcr_graph* g, size_t first, size_t count, double* pose
  * graph.  Uploads poses added since the last use and reads no factor: it serves a graph whose factors name poses that do not exist yet. */
 const double* pcr_graph_device_poses(const pcr_graph* g, size_t* n);
 /* Introspection: every factor linearised at the current estimates, priors first, then betweens, each in the order added: r [E][6],
- * j_from = dr/d(delta_from) and j_to = dr/d(delta_to) [E][36] row-major (a prior's j_from is zero), *chi2.  Any pointer may be NULL.
+ * j_from = dr/d(delta_from) and j_to = dr/d(delta_to) [E][36] row-major (a prior's j_from is zero), unweighted for every factor, switched
+ * off or not; *chi2 = sum rho over the factors that are on.  Any pointer may be NULL.
  * A device graph runs the optimiser's kernel, a PCR_GRAPH_HOST graph the same code on the host: the two agree bit for bit. */
 int pcr_graph_linearize(pcr_graph* g, double* r, double* j_from, double* j_to, double* chi2);
 /* Introspection (device graphs): y = (H + lambda I) x at the current estimates, x and y 6 doubles per pose, by the solve kernel's own product. */
@@ -603,7 +639,8 @@ int pcr_map_set_poses_from_graph(pcr_map* m, const pcr_graph* g, size_t first, s
  * (continuing the graph's), the information matrix mirrored to both triangles, its translation and rotation blocks swapped into [omega; v]
  * order and its off-diagonal blocks taken as they stand (not transposed, as there); the PRIOR preset is added on vertex 0.  VERTEX3 and EDGE3
  * are refused with a message; other records are skipped.  A file that is refused leaves the graph as it was.  save writes the poses and the
- * between factors with 17 significant digits (no priors: they are the reader's own). */
+ * between factors with 17 significant digits (no priors: they are the reader's own).  The files carry neither robust marks nor switches: save
+ * writes every between factor, switched off or not, and a loaded graph has every factor on and unmarked. */
 int pcr_graph_load_g2o(pcr_graph* g, const char* path);
 int pcr_graph_save_g2o(const pcr_graph* g, const char* path);
 

@@ -22,7 +22,12 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // ---- linearise: the whole grid, one factor per lane --------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kLinBlock) void graph_linearize_kernel(const double* __restrict__ poses, const Factors f, const Lin out,
+// What the solve reads of Omega are the weighted arrays written here (w Omega r, w Omega J): a robust kernel or a switch changes nothing else.
+// ROBUST = PCR_GRAPH_ROBUST_*, chosen on the host.  Under NONE every weight is known up front (1, or 0 when switched off), so Omega r and
+// Omega J leave row by row while s = r^T Omega r still accumulates.  A robust kind needs s before it can scale: the rows of Omega are read
+// twice, first for Omega r and s, then for Omega J, and only six doubles stay live in between.
+template <int ROBUST>
+__global__ __launch_bounds__(kLinBlock) void graph_linearize_kernel(const double* __restrict__ poses, const Factors f, const Robust rb, const Lin out,
                                                                     double* __restrict__ partial) {
     __shared__ double wsum[kLinBlock / 64];
     const int F = f.F;
@@ -30,6 +35,8 @@ __global__ __launch_bounds__(kLinBlock) void graph_linearize_kernel(const double
     double c = 0.0;
     if (e < F) {
         const int from = f.from[e], to = f.to[e];
+        const unsigned char fl = f.flags[e];
+        const bool on = (fl & kFactorOff) == 0;
         double Xi[16], Xj[16], Z[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
@@ -39,27 +46,65 @@ __global__ __launch_bounds__(kLinBlock) void graph_linearize_kernel(const double
         }
         double r[6], Jf[36], Jt[36];
         gm::factor_linearize(from >= 0, Xi, Xj, Z, r, Jf, Jt);
+        if constexpr (ROBUST == 0) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            double o[6];
+            for (int k = 0; k < 6; ++k) {
+                double o[6];
 #pragma unroll
-            for (int m = 0; m < 6; ++m) o[m] = f.omega[(size_t)(k * 6 + m) * F + e];
-            double w = 0.0;
+                for (int m = 0; m < 6; ++m) o[m] = f.omega[(size_t)(k * 6 + m) * F + e];
+                double w = 0.0;
 #pragma unroll
-            for (int m = 0; m < 6; ++m) w += o[m] * r[m];
-            out.r[(size_t)k * F + e] = r[k];
-            out.wr[(size_t)k * F + e] = w;
-            c += r[k] * w;
+                for (int m = 0; m < 6; ++m) w += o[m] * r[m];
+                out.r[(size_t)k * F + e] = r[k];
+                out.wr[(size_t)k * F + e] = on ? w : 0.0;
+                c += r[k] * w;
 #pragma unroll
-            for (int b = 0; b < 6; ++b) {
-                double sf = 0.0, st = 0.0;
+                for (int b = 0; b < 6; ++b) {
+                    double sf = 0.0, st = 0.0;
 #pragma unroll
-                for (int m = 0; m < 6; ++m) { sf += o[m] * Jf[m * 6 + b]; st += o[m] * Jt[m * 6 + b]; }
-                out.wjf[(size_t)(k * 6 + b) * F + e] = sf;
-                out.wjt[(size_t)(k * 6 + b) * F + e] = st;
-                out.jf[(size_t)(k * 6 + b) * F + e] = Jf[k * 6 + b];
-                out.jt[(size_t)(k * 6 + b) * F + e] = Jt[k * 6 + b];
+                    for (int m = 0; m < 6; ++m) { sf += o[m] * Jf[m * 6 + b]; st += o[m] * Jt[m * 6 + b]; }
+                    out.wjf[(size_t)(k * 6 + b) * F + e] = on ? sf : 0.0;
+                    out.wjt[(size_t)(k * 6 + b) * F + e] = on ? st : 0.0;
+                    out.jf[(size_t)(k * 6 + b) * F + e] = Jf[k * 6 + b];
+                    out.jt[(size_t)(k * 6 + b) * F + e] = Jt[k * 6 + b];
+                }
             }
+            out.s[e] = c;
+            out.w[e] = 1.0;
+            c = on ? c : 0.0;
+        } else {
+            double wr[6], s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                double w = 0.0;
+#pragma unroll
+                for (int m = 0; m < 6; ++m) w += f.omega[(size_t)(k * 6 + m) * F + e] * r[m];
+                out.r[(size_t)k * F + e] = r[k];
+                wr[k] = w;
+                s += r[k] * w;
+            }
+            double rho, wk;
+            gm::robust_rho_w((fl & kFactorRobust) ? ROBUST : 0, s, rb.delta, rb.d, &rho, &wk);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                double o[6];
+#pragma unroll
+                for (int m = 0; m < 6; ++m) o[m] = f.omega[(size_t)(k * 6 + m) * F + e];
+                out.wr[(size_t)k * F + e] = on ? wk * wr[k] : 0.0;
+#pragma unroll
+                for (int b = 0; b < 6; ++b) {
+                    double sf = 0.0, st = 0.0;
+#pragma unroll
+                    for (int m = 0; m < 6; ++m) { sf += o[m] * Jf[m * 6 + b]; st += o[m] * Jt[m * 6 + b]; }
+                    out.wjf[(size_t)(k * 6 + b) * F + e] = on ? wk * sf : 0.0;
+                    out.wjt[(size_t)(k * 6 + b) * F + e] = on ? wk * st : 0.0;
+                    out.jf[(size_t)(k * 6 + b) * F + e] = Jf[k * 6 + b];
+                    out.jt[(size_t)(k * 6 + b) * F + e] = Jt[k * 6 + b];
+                }
+            }
+            out.s[e] = s;
+            out.w[e] = wk;
+            c = on ? rho : 0.0;
         }
         out.c[e] = c;
     }
@@ -626,9 +671,17 @@ __global__ __launch_bounds__(256) void graph_retract_kernel(const int N, const d
 
 }  // namespace
 
-hipError_t launch_linearize(const double* poses, const Factors& f, const Lin& out, double* partial, double* status, hipStream_t s) {
+hipError_t launch_linearize(const double* poses, const Factors& f, const Robust& rb, const Lin& out, double* partial, double* status, hipStream_t s) {
     const int nb = lin_blocks(f.F);
-    if (nb > 0) hipLaunchKernelGGL(graph_linearize_kernel, dim3(nb), dim3(kLinBlock), 0, s, poses, f, out, partial);
+    if (nb > 0) {
+        switch (rb.kind) {
+            case 0: hipLaunchKernelGGL(graph_linearize_kernel<0>, dim3(nb), dim3(kLinBlock), 0, s, poses, f, rb, out, partial); break;
+            case 1: hipLaunchKernelGGL(graph_linearize_kernel<1>, dim3(nb), dim3(kLinBlock), 0, s, poses, f, rb, out, partial); break;
+            case 2: hipLaunchKernelGGL(graph_linearize_kernel<2>, dim3(nb), dim3(kLinBlock), 0, s, poses, f, rb, out, partial); break;
+            case 3: hipLaunchKernelGGL(graph_linearize_kernel<3>, dim3(nb), dim3(kLinBlock), 0, s, poses, f, rb, out, partial); break;
+            default: return hipErrorInvalidValue;      // (pcr_graph_set_robust_kernel refuses every other kind)
+        }
+    }
     hipLaunchKernelGGL(graph_chi2_fold_kernel, dim3(1), dim3(64), 0, s, partial, nb, status);
     return hipGetLastError();
 }

@@ -12,16 +12,21 @@ struct Factors {
     const int* to;
     const double* z;          // [16][F] measurement (a prior: the prior pose), column-major pose entries
     const double* omega;      // [36][F] information, full symmetric, row-major entries
+    const unsigned char* flags;      // [F] kFactorRobust: the robust kernel applies (between factors only); kFactorOff: switched off
 };
+constexpr unsigned char kFactorRobust = 1, kFactorOff = 2;
 
-// One linearisation: per factor r (6), Omega r (6), J_from, J_to, Omega J_from, Omega J_to (36 each, row-major entries), r^T Omega r.
+// One linearisation: per factor r (6), J_from, J_to (36 each, row-major entries) as they are; w Omega r (6), w Omega J_from, w Omega J_to with
+// the factor's weight w (1; the robust kernel's w(s) on a marked factor; 0 on one switched off), which is all the solve reads of Omega;
+// c = rho(s) (0 when switched off); s = r^T Omega r and the kernel's w(s) whatever the switch says (pcr_graph_between_weights).
 struct Lin {
-    double *r, *wr, *jf, *jt, *wjf, *wjt, *c;
-    static constexpr size_t kDoublesPerFactor = 6 + 6 + 4 * 36 + 1;
+    double *r, *wr, *jf, *jt, *wjf, *wjt, *c, *s, *w;
+    static constexpr size_t kDoublesPerFactor = 6 + 6 + 4 * 36 + 3;
 };
 inline Lin lin_view(double* base, size_t F) {
     Lin l;
     l.r = base; l.wr = l.r + 6 * F; l.jf = l.wr + 6 * F; l.jt = l.jf + 36 * F; l.wjf = l.jt + 36 * F; l.wjt = l.wjf + 36 * F; l.c = l.wjt + 36 * F;
+    l.s = l.c + F; l.w = l.s + F;
     return l;
 }
 
@@ -55,8 +60,11 @@ constexpr int kLinBlock = 256;
 constexpr int kSolveThreads = 1024;
 inline int lin_blocks(int F) { return (F + kLinBlock - 1) / kLinBlock; }
 
-// linearise every factor at `poses` into `out`, chi2 into status[0] (partial: lin_blocks(F) doubles)
-hipError_t launch_linearize(const double* poses, const Factors& f, const Lin& out, double* partial, double* status, hipStream_t s);
+// The robust kernel of the marked factors: kind = PCR_GRAPH_ROBUST_*, d = delta^2.  The kernel is chosen on the host and compiled in.
+struct Robust { int kind = 0; double delta = 0.0, d = 0.0; };
+
+// linearise every factor at `poses` into `out`, the sum of rho into status[0] (partial: lin_blocks(F) doubles)
+hipError_t launch_linearize(const double* poses, const Factors& f, const Robust& rb, const Lin& out, double* partial, double* status, hipStream_t s);
 // delta (= bufs.x) <- PCG on (H + lambda I) delta = -g, one workgroup; status[1], status[2]
 hipError_t launch_solve(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, int max_it, double tol, const SolveBufs& b,
                         double* status, hipStream_t s);

@@ -53,6 +53,7 @@ struct Factor {
     long long to;
     double z[16];
     double info[36];     // full symmetric, row-major
+    unsigned char flags = 0;      // kFactorRobust, kFactorOff (between factors only): nothing a g2o file carries
 };
 
 }  // namespace
@@ -62,7 +63,9 @@ struct pcr_graph {
     bool host_only = false;
     std::vector<double> poses;               // 16 per pose, column-major; entries below n_uploaded are older than the device's while host_stale
     std::vector<Factor> priors, betweens;
-    bool dirty = false;                      // something was added since the last optimize
+    int robust_kind = PCR_GRAPH_ROBUST_NONE; // the kernel of the marked between factors; it outlives pcr_graph_clear
+    double robust_delta = 0.0;
+    bool dirty = false;                      // something was added, marked, switched or set since the last optimize
     bool dirty_factors = true;               // the device's factor arrays and CSR are older than the lists
     bool dirty_forest = true;                // ... and so is `forest` (poses or factors were added since it was planned)
     bool dirty_tree_dev = true;              // ... and so are the device's copies of its schedule
@@ -74,7 +77,7 @@ struct pcr_graph {
     std::string err;
     // device side
     hipStream_t stream = nullptr;
-    DBuf d_poses[2], d_lin[2], d_from, d_to, d_z, d_omega, d_rowptr, d_ent, d_vec, d_u, d_partial, d_status, d_tree_i, d_tree_d, d_in_m;
+    DBuf d_poses[2], d_lin[2], d_from, d_to, d_z, d_omega, d_rowptr, d_ent, d_vec, d_u, d_partial, d_status, d_tree_i, d_tree_d, d_in_m, d_flags;
     size_t tree_lch = 0, tree_paths = 0;     // entries of the device's light-children list and paths
     int cur = 0;
     size_t F_dev = 0;
@@ -130,13 +133,14 @@ static int validate(pcr_graph* g, const char* what) {
     return 0;
 }
 
-// union-find over the between factors: the first pose whose connected component holds no prior, or -1
+// union-find over the between factors that are switched on: the first pose whose connected component holds no prior, or -1
 static long long first_pose_without_prior(const pcr_graph* g) {
     const size_t N = n_poses(g);
     std::vector<size_t> parent(N);
     std::iota(parent.begin(), parent.end(), (size_t)0);
     auto find = [&](size_t a) { while (parent[a] != a) { parent[a] = parent[parent[a]]; a = parent[a]; } return a; };
     for (const Factor& f : g->betweens) {
+        if (f.flags & kFactorOff) continue;
         const size_t a = find((size_t)f.from), b = find((size_t)f.to);
         if (a != b) parent[a > b ? a : b] = a > b ? b : a;
     }
@@ -208,10 +212,12 @@ static int upload(pcr_graph* g) {
     const size_t P = g->priors.size(), F = P + g->betweens.size();
     std::vector<int> from(F), to(F);
     std::vector<double> z(16 * F), om(36 * F);
+    std::vector<unsigned char> flags(F + 1, 0);
     std::vector<int> rowptr(N + 1, 0);
     for (size_t e = 0; e < F; ++e) {
         const Factor& f = e < P ? g->priors[e] : g->betweens[e - P];
         from[e] = (int)f.from; to[e] = (int)f.to;
+        flags[e] = f.flags;
         for (int k = 0; k < 16; ++k) z[k * F + e] = f.z[k];
         for (int k = 0; k < 36; ++k) om[k * F + e] = f.info[k];
         if (f.from >= 0) rowptr[f.from + 1]++;
@@ -225,6 +231,7 @@ static int upload(pcr_graph* g) {
     }
     G_TRY(g->d_from.reserve((F + 1) * sizeof(int), false));
     G_TRY(g->d_to.reserve((F + 1) * sizeof(int), false));
+    G_TRY(g->d_flags.reserve(flags.size(), false));
     G_TRY(g->d_z.reserve((16 * F + 1) * sizeof(double), false));
     G_TRY(g->d_omega.reserve((36 * F + 1) * sizeof(double), false));
     G_TRY(g->d_rowptr.reserve((N + 1) * sizeof(int), false));
@@ -235,6 +242,7 @@ static int upload(pcr_graph* g) {
     if (F) {
         G_TRY(hipMemcpy(g->d_from.p, from.data(), F * sizeof(int), hipMemcpyHostToDevice));
         G_TRY(hipMemcpy(g->d_to.p, to.data(), F * sizeof(int), hipMemcpyHostToDevice));
+        G_TRY(hipMemcpy(g->d_flags.p, flags.data(), F, hipMemcpyHostToDevice));
         G_TRY(hipMemcpy(g->d_z.p, z.data(), 16 * F * sizeof(double), hipMemcpyHostToDevice));
         G_TRY(hipMemcpy(g->d_omega.p, om.data(), 36 * F * sizeof(double), hipMemcpyHostToDevice));
     }
@@ -248,7 +256,13 @@ static int upload(pcr_graph* g) {
 static Factors dev_factors(const pcr_graph* g) {
     Factors f;
     f.F = (int)g->F_dev; f.from = g->d_from.as<int>(); f.to = g->d_to.as<int>(); f.z = g->d_z.as<double>(); f.omega = g->d_omega.as<double>();
+    f.flags = g->d_flags.as<unsigned char>();
     return f;
+}
+static Robust robust_of(const pcr_graph* g) {
+    Robust rb;
+    rb.kind = g->robust_kind; rb.delta = g->robust_delta; rb.d = g->robust_delta * g->robust_delta;
+    return rb;
 }
 static Csr dev_csr(const pcr_graph* g) { return Csr{g->d_rowptr.as<int>(), g->d_ent.as<int>()}; }
 static SolveBufs dev_bufs(const pcr_graph* g, size_t N) {
@@ -258,13 +272,22 @@ static SolveBufs dev_bufs(const pcr_graph* g, size_t N) {
     return b;
 }
 
-// The tree preconditioner's forest, planned anew only when poses or factors were added since it was made.  ONLY after validate().
+// The tree preconditioner's forest, planned anew only when poses or factors were added, or a factor switched, since it was made.  ONLY after validate().
 static const ForestPlan& forest_of(pcr_graph* g) {
     if (g->dirty_forest) {
-        std::vector<long long> from(g->betweens.size()), to(g->betweens.size()), prior(g->priors.size());
-        for (size_t e = 0; e < g->betweens.size(); ++e) { from[e] = g->betweens[e].from; to[e] = g->betweens[e].to; }
+        // over the between factors that are switched on; the plan's factor indices are then put back into the full list's
+        std::vector<long long> from, to, prior(g->priors.size());
+        std::vector<int> full;
+        for (size_t e = 0; e < g->betweens.size(); ++e) {
+            if (g->betweens[e].flags & kFactorOff) continue;
+            from.push_back(g->betweens[e].from); to.push_back(g->betweens[e].to); full.push_back((int)e);
+        }
         for (size_t i = 0; i < g->priors.size(); ++i) prior[i] = g->priors[i].to;
         g->forest = plan_forest(n_poses(g), from.data(), to.data(), from.size(), prior.data(), prior.size());
+        std::vector<uint8_t> in_tree(g->betweens.size(), 0);
+        for (size_t k = 0; k < full.size(); ++k) in_tree[full[k]] = g->forest.in_tree[k];
+        g->forest.in_tree.swap(in_tree);
+        for (int& e : g->forest.tree_factor) if (e >= 0) e = full[e];
         g->dirty_forest = false;
         g->dirty_tree_dev = true;
     }
@@ -454,6 +477,66 @@ int pcr_graph_add_between_poses(pcr_graph* g, size_t from, size_t to, const doub
     return add_factor(g, "pcr_graph_add_between_poses", (long long)from, to, Z, info21);
 }
 
+int pcr_graph_add_loop(pcr_graph* g, size_t from, size_t to, const double z[16], const double info21[21]) {
+    if (g && (long long)from < 0) return gfail(g, "pcr_graph_add_loop: id out of range");
+    if (add_factor(g, "pcr_graph_add_loop", (long long)from, to, z, info21)) return 1;
+    g->betweens.back().flags |= kFactorRobust;
+    return 0;
+}
+
+int pcr_graph_robust_rho_w(int kind, double delta, double s, double* rho, double* w) {
+    if (kind < PCR_GRAPH_ROBUST_NONE || kind > PCR_GRAPH_ROBUST_TUKEY) return 1;
+    if (kind != PCR_GRAPH_ROBUST_NONE && !(std::isfinite(delta) && delta > 0.0)) return 1;
+    if (!(s >= 0.0)) return 1;
+    double ro, wo;
+    gm::robust_rho_w(kind, s, delta, delta * delta, &ro, &wo);
+    if (rho) *rho = ro;
+    if (w) *w = wo;
+    return 0;
+}
+
+int pcr_graph_set_robust_kernel(pcr_graph* g, int kind, double delta) {
+    if (!g) return 1;
+    g->err.clear();
+    if (kind < PCR_GRAPH_ROBUST_NONE || kind > PCR_GRAPH_ROBUST_TUKEY)
+        return gfail(g, "pcr_graph_set_robust_kernel: unknown kind " + std::to_string(kind) +
+                            " (PCR_GRAPH_ROBUST_NONE = 0, PCR_GRAPH_ROBUST_HUBER = 1, PCR_GRAPH_ROBUST_GEMAN_MCCLURE = 2, PCR_GRAPH_ROBUST_TUKEY = 3)");
+    if (kind != PCR_GRAPH_ROBUST_NONE && !(std::isfinite(delta) && delta > 0.0))
+        return gfail(g, "pcr_graph_set_robust_kernel: delta must be finite and greater than 0");
+    g->robust_kind = kind;
+    g->robust_delta = kind == PCR_GRAPH_ROBUST_NONE ? 0.0 : delta;
+    g->dirty = true;      // (the kernel and delta travel with every launch: no table is older for it)
+    return 0;
+}
+
+int pcr_graph_get_robust_kernel(const pcr_graph* g, int* kind, double* delta) {
+    if (!g) return 1;
+    if (kind) *kind = g->robust_kind;
+    if (delta) *delta = g->robust_delta;
+    return 0;
+}
+
+static int set_between_flag(pcr_graph* g, const char* what, size_t first, size_t count, unsigned char bit, bool set) {
+    if (!g) return 1;
+    g->err.clear();
+    const size_t B = g->betweens.size();
+    if (first > B || count > B - first)
+        return gfail(g, std::string(what) + ": first + count exceeds the number of between factors (" + std::to_string(B) + ")");
+    if (count == 0) return 0;
+    for (size_t e = first; e < first + count; ++e) g->betweens[e].flags = set ? (g->betweens[e].flags | bit) : (g->betweens[e].flags & (unsigned char)~bit);
+    g->dirty = true;
+    g->dirty_factors = true; g->dirty_forest = true; g->dirty_tree_dev = true;      // as after an add
+    return 0;
+}
+
+int pcr_graph_set_between_robust(pcr_graph* g, size_t first, size_t count, int on) {
+    return set_between_flag(g, "pcr_graph_set_between_robust", first, count, kFactorRobust, on != 0);
+}
+
+int pcr_graph_set_between_enabled(pcr_graph* g, size_t first, size_t count, int on) {
+    return set_between_flag(g, "pcr_graph_set_between_enabled", first, count, kFactorOff, on == 0);
+}
+
 int pcr_graph_size(const pcr_graph* g, size_t* np, size_t* n_priors, size_t* n_between) {
     if (!g) return 1;
     if (np) *np = n_poses(g);
@@ -507,6 +590,21 @@ const double* pcr_graph_device_poses(const pcr_graph* gc, size_t* n) {
     return g->d_poses[g->cur].as<double>();
 }
 
+// s = r^T Omega r in the linearise kernel's order, and the kernel's rho(s) and w(s) for this factor (s and 1 unless it is marked)
+static double factor_rho(const pcr_graph* g, const Factor& f, const double* rr, double* s_out, double* w_out) {
+    double s = 0.0;
+    for (int k = 0; k < 6; ++k) {
+        double w = 0.0;
+        for (int m = 0; m < 6; ++m) w += f.info[k * 6 + m] * rr[m];
+        s += rr[k] * w;
+    }
+    double rho, wk;
+    gm::robust_rho_w((f.flags & kFactorRobust) ? g->robust_kind : 0, s, g->robust_delta, g->robust_delta * g->robust_delta, &rho, &wk);
+    if (s_out) *s_out = s;
+    if (w_out) *w_out = wk;
+    return rho;
+}
+
 int pcr_graph_linearize(pcr_graph* g, double* r, double* j_from, double* j_to, double* chi2) {
     if (!g) return 1;
     g->err.clear();
@@ -519,13 +617,7 @@ int pcr_graph_linearize(pcr_graph* g, double* r, double* j_from, double* j_to, d
             double rr[6], Jf[36], Jt[36];
             const double* Xj = &g->poses[16 * f.to];
             gm::factor_linearize(f.from >= 0, f.from >= 0 ? &g->poses[16 * f.from] : Xj, Xj, f.z, rr, Jf, Jt);
-            double ce = 0.0;
-            for (int k = 0; k < 6; ++k) {
-                double w = 0.0;
-                for (int m = 0; m < 6; ++m) w += f.info[k * 6 + m] * rr[m];
-                ce += rr[k] * w;
-            }
-            c[e] = ce;
+            c[e] = (f.flags & kFactorOff) ? 0.0 : factor_rho(g, f, rr, nullptr, nullptr);
             if (r) memcpy(r + 6 * e, rr, sizeof rr);
             if (j_from) memcpy(j_from + 36 * e, Jf, sizeof Jf);
             if (j_to) memcpy(j_to + 36 * e, Jt, sizeof Jt);
@@ -536,7 +628,7 @@ int pcr_graph_linearize(pcr_graph* g, double* r, double* j_from, double* j_to, d
     if (upload(g)) return 1;
     if (F == 0) { if (chi2) *chi2 = 0.0; return 0; }
     const Lin lin = lin_view(g->d_lin[g->cur].as<double>(), F);
-    G_TRY(launch_linearize(g->d_poses[g->cur].as<double>(), dev_factors(g), lin, g->d_partial.as<double>(), g->d_status.as<double>(), g->stream));
+    G_TRY(launch_linearize(g->d_poses[g->cur].as<double>(), dev_factors(g), robust_of(g), lin, g->d_partial.as<double>(), g->d_status.as<double>(), g->stream));
     G_TRY(hipMemcpyAsync(g->h_status, g->d_status.p, 3 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
     std::vector<double> buf((6 + 72) * F);
     G_TRY(hipMemcpyAsync(buf.data(), lin.r, 6 * F * sizeof(double), hipMemcpyDeviceToHost, g->stream));
@@ -548,6 +640,37 @@ int pcr_graph_linearize(pcr_graph* g, double* r, double* j_from, double* j_to, d
         if (j_to) for (int k = 0; k < 36; ++k) j_to[36 * e + k] = buf[42 * F + k * F + e];
     }
     if (chi2) *chi2 = g->h_status[0];
+    return 0;
+}
+
+int pcr_graph_between_weights(pcr_graph* g, size_t first, size_t count, double* s, double* w, uint8_t* robust, uint8_t* enabled) {
+    if (!g) return 1;
+    g->err.clear();
+    const size_t P = g->priors.size(), B = g->betweens.size(), F = P + B;
+    if (first > B || count > B - first)
+        return gfail(g, "pcr_graph_between_weights: first + count exceeds the number of between factors (" + std::to_string(B) + ")");
+    if (validate(g, "pcr_graph_between_weights")) return 1;
+    for (size_t i = 0; i < count; ++i) {
+        const unsigned char fl = g->betweens[first + i].flags;
+        if (robust) robust[i] = (fl & kFactorRobust) ? 1 : 0;
+        if (enabled) enabled[i] = (fl & kFactorOff) ? 0 : 1;
+    }
+    if (count == 0 || (!s && !w)) return 0;
+    if (g->host_only) {
+        for (size_t i = 0; i < count; ++i) {
+            const Factor& f = g->betweens[first + i];
+            double rr[6], Jf[36], Jt[36];
+            gm::factor_linearize(true, &g->poses[16 * f.from], &g->poses[16 * f.to], f.z, rr, Jf, Jt);
+            (void)factor_rho(g, f, rr, s ? s + i : nullptr, w ? w + i : nullptr);
+        }
+        return 0;
+    }
+    if (upload(g)) return 1;
+    const Lin lin = lin_view(g->d_lin[g->cur].as<double>(), F);
+    G_TRY(launch_linearize(g->d_poses[g->cur].as<double>(), dev_factors(g), robust_of(g), lin, g->d_partial.as<double>(), g->d_status.as<double>(), g->stream));
+    if (s) G_TRY(hipMemcpyAsync(s, lin.s + P + first, count * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (w) G_TRY(hipMemcpyAsync(w, lin.w + P + first, count * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    G_TRY(hipStreamSynchronize(g->stream));
     return 0;
 }
 
@@ -564,7 +687,7 @@ int pcr_graph_apply(pcr_graph* g, double lambda, const double* x, double* y) {
     const size_t F = g->F_dev;
     const Lin lin = lin_view(g->d_lin[g->cur].as<double>(), F);
     const SolveBufs b = dev_bufs(g, N);
-    G_TRY(launch_linearize(g->d_poses[g->cur].as<double>(), dev_factors(g), lin, g->d_partial.as<double>(), g->d_status.as<double>(), g->stream));
+    G_TRY(launch_linearize(g->d_poses[g->cur].as<double>(), dev_factors(g), robust_of(g), lin, g->d_partial.as<double>(), g->d_status.as<double>(), g->stream));
     G_TRY(hipMemcpyAsync(b.res, x, 6 * N * sizeof(double), hipMemcpyHostToDevice, g->stream));
     G_TRY(launch_apply((int)N, dev_factors(g), lin, dev_csr(g), lambda, b.res, b.ap, g->d_u.as<double>(), g->stream));
     G_TRY(hipMemcpyAsync(y, b.ap, 6 * N * sizeof(double), hipMemcpyDeviceToHost, g->stream));
@@ -611,7 +734,7 @@ int pcr_graph_precondition(pcr_graph* g, double lambda, int kind, const double* 
     const Lin lin = lin_view(g->d_lin[g->cur].as<double>(), F);
     const SolveBufs b = dev_bufs(g, N);
     int* d_flag = reinterpret_cast<int*>(g->d_status.as<double>() + 3);
-    G_TRY(launch_linearize(g->d_poses[g->cur].as<double>(), dev_factors(g), lin, g->d_partial.as<double>(), g->d_status.as<double>(), g->stream));
+    G_TRY(launch_linearize(g->d_poses[g->cur].as<double>(), dev_factors(g), robust_of(g), lin, g->d_partial.as<double>(), g->d_status.as<double>(), g->stream));
     G_TRY(hipMemcpyAsync(b.res, r, 6 * N * sizeof(double), hipMemcpyHostToDevice, g->stream));
     G_TRY(launch_precondition((int)N, dev_factors(g), lin, dev_csr(g), tree ? &tr : nullptr, lambda, b, d_flag, g->stream));
     G_TRY(hipMemcpyAsync(z, b.z, 6 * N * sizeof(double), hipMemcpyDeviceToHost, g->stream));
@@ -665,6 +788,7 @@ int pcr_graph_optimize(pcr_graph* g, const pcr_graph_params* params, pcr_graph_r
     const Tree tr = tree ? dev_tree(g, N) : Tree{};
     const size_t F = g->F_dev;
     const Factors fac = dev_factors(g);
+    const Robust rb = robust_of(g);
     const Csr csr = dev_csr(g);
     SolveBufs b = dev_bufs(g, N);
     b.u = g->d_u.as<double>();
@@ -674,7 +798,7 @@ int pcr_graph_optimize(pcr_graph* g, const pcr_graph_params* params, pcr_graph_r
     const int cap = (int)std::min<long long>(cap64, 0x7fffffff);
 
     Lin lin = lin_view(g->d_lin[g->cur].as<double>(), F);
-    G_TRY(launch_linearize(g->d_poses[g->cur].as<double>(), fac, lin, d_partial, d_status, g->stream));
+    G_TRY(launch_linearize(g->d_poses[g->cur].as<double>(), fac, rb, lin, d_partial, d_status, g->stream));
     G_TRY(hipMemcpyAsync(g->h_status, d_status, 3 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
     G_TRY(hipStreamSynchronize(g->stream));
     double chi2 = g->h_status[0];
@@ -687,7 +811,7 @@ int pcr_graph_optimize(pcr_graph* g, const pcr_graph_params* params, pcr_graph_r
         if (tree) G_TRY(launch_solve_tree((int)N, fac, lin, csr, tr, lambda, cap, prm.pcg_rel_tol, b, d_status, g->stream));
         else G_TRY(launch_solve((int)N, fac, lin, csr, lambda, cap, prm.pcg_rel_tol, b, d_status, g->stream));
         G_TRY(launch_retract((int)N, g->d_poses[g->cur].as<double>(), b.x, g->d_poses[trial].as<double>(), g->stream));
-        G_TRY(launch_linearize(g->d_poses[trial].as<double>(), fac, lin_trial, d_partial, d_status, g->stream));
+        G_TRY(launch_linearize(g->d_poses[trial].as<double>(), fac, rb, lin_trial, d_partial, d_status, g->stream));
         G_TRY(hipMemcpyAsync(g->h_status, d_status, 3 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
         G_TRY(hipStreamSynchronize(g->stream));
         int words[2];

@@ -283,6 +283,30 @@ GM_HD void factor_linearize(bool has_from, const double* Xi, const double* Xj, c
         }
 }
 
+// Robust kernels on s = r^T Omega r (PCR_GRAPH_ROBUST_* of pcr_hip.h): rho(s) and w(s) = rho'(s), d = delta^2.  The cost of a marked factor is
+// rho / 2; it enters g and H as w J^T Omega r and w J^T Omega J (the second-order term is dropped, as g2o and GTSAM drop it).
+//   1 Huber          rho = s               (s <= d),  2 delta sqrt(s) - d  beyond      w = 1, delta / sqrt(s)
+//   2 Geman-McClure  rho = d s / (d + s)                                               w = d^2 / (d + s)^2
+//   3 Tukey          rho = d/3 (1 - (1 - s/d)^3) (s <= d),  d/3 beyond                 w = (1 - s/d)^2, 0
+// Only + - * / sqrt, so host and device agree bit for bit (Cauchy's logarithm is why Cauchy is absent).  Written so that nothing overflows for any
+// s >= 0: Geman-McClure through q = d / (d + s), Tukey's rho as s ((1 - q) + q^2 / 3) with q = s / d, which also spares the cancellation of
+// 1 - (1 - q)^3 at small s and equals d (1/3) at s = d, the value beyond.  Huber at s = 0 divides by nothing.  Any other kind is plain least squares.
+GM_HD void robust_rho_w(int kind, double s, double delta, double d, double* rho, double* w) {
+    double ro = s, wo = 1.0;
+    if (kind == 1) {
+        if (s > d) { const double q = sqrt(s); ro = 2.0 * delta * q - d; wo = delta / q; }
+    } else if (kind == 2) {
+        const double q = d / (d + s);
+        ro = q * s;
+        wo = q * q;
+    } else if (kind == 3) {
+        if (s > d) { ro = d * (1.0 / 3.0); wo = 0.0; }
+        else { const double q = s / d, u = 1.0 - q; ro = s * (u + q * q * (1.0 / 3.0)); wo = u * u; }
+    }
+    *rho = ro;
+    *w = wo;
+}
+
 // Packed lower triangle: entry (i, j), j <= i, at i (i + 1) / 2 + j.
 GM_HD constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }
 

@@ -631,7 +631,23 @@ public:
     }
     void addLC(size_t from, size_t to, const PCR::pose_t& between, const double* info21 = nullptr) {
         double buf[21];
-        check(pcr_graph_add_between(g_, from, to, between.data(), noise(PCR_GRAPH_LOOP, info21, buf)));
+        check(pcr_graph_add_loop(g_, from, to, between.data(), noise(PCR_GRAPH_LOOP, info21, buf)));      // the robust mark: nothing under NONE
+    }
+    // The kernel of the marked between factors (PCR_GRAPH_ROBUST_*; delta in units of a residual's Mahalanobis length); marks and switches by
+    // index among the between factors in the order added.  A factor that is off adds nothing and links nothing.
+    void setRobustKernel(int kind, double delta = 0.0) { check(pcr_graph_set_robust_kernel(g_, kind, delta)); }
+    void setBetweenRobust(size_t first, size_t count = 1, bool on = true) { check(pcr_graph_set_between_robust(g_, first, count, on ? 1 : 0)); }
+    void setBetweenEnabled(size_t first, size_t count = 1, bool on = true) { check(pcr_graph_set_between_enabled(g_, first, count, on ? 1 : 0)); }
+    // the verdict at the current estimates, per between factor: s = r^T Omega r, the kernel's weight at s (1 when unmarked), the mark, the switch
+    struct Weights { std::vector<double> s, w; std::vector<uint8_t> robust, enabled; };
+    Weights betweenWeights(size_t first = 0, size_t count = (size_t)-1) {
+        size_t b = 0;
+        pcr_graph_size(g_, nullptr, nullptr, &b);
+        if (count == (size_t)-1) count = b - std::min(first, b);
+        Weights o;
+        o.s.resize(count); o.w.resize(count); o.robust.resize(count); o.enabled.resize(count);
+        check(pcr_graph_between_weights(g_, first, count, o.s.data(), o.w.data(), o.robust.data(), o.enabled.data()));
+        return o;
     }
     // Backend::addOdomFactor (Backend.cpp:241-247): the between factor of the two current estimates
     void addOdomFactor(size_t from, size_t to, const double* info21 = nullptr) {

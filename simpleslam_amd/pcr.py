@@ -89,7 +89,8 @@ ABI_SYMBOLS = [
     "pcr_graph_create", "pcr_graph_destroy", "pcr_graph_last_error", "pcr_graph_noise", "pcr_graph_add_poses", "pcr_graph_add_prior", "pcr_graph_add_between",
     "pcr_graph_add_between_poses", "pcr_graph_size", "pcr_graph_clear", "pcr_graph_default_params", "pcr_graph_optimize", "pcr_graph_poses",
     "pcr_graph_device_poses", "pcr_graph_linearize", "pcr_graph_apply", "pcr_map_set_poses_from_graph", "pcr_graph_load_g2o", "pcr_graph_save_g2o",
-    "pcr_graph_tree", "pcr_graph_precondition",
+    "pcr_graph_tree", "pcr_graph_precondition", "pcr_graph_set_robust_kernel", "pcr_graph_get_robust_kernel", "pcr_graph_set_between_robust",
+    "pcr_graph_set_between_enabled", "pcr_graph_add_loop", "pcr_graph_between_weights", "pcr_graph_robust_rho_w",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -336,6 +337,13 @@ def load_library():
     L.pcr_graph_tree.argtypes = [vp, C.POINTER(C.c_int64), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.pcr_graph_precondition.argtypes = [vp, C.c_double, C.c_int, dp, dp]
     L.pcr_map_set_poses_from_graph.argtypes = [vp, vp, C.c_size_t, C.c_size_t]
+    L.pcr_graph_set_robust_kernel.argtypes = [vp, C.c_int, C.c_double]
+    L.pcr_graph_get_robust_kernel.argtypes = [vp, C.POINTER(C.c_int), dp]
+    L.pcr_graph_set_between_robust.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int]
+    L.pcr_graph_set_between_enabled.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int]
+    L.pcr_graph_add_loop.argtypes = [vp, C.c_size_t, C.c_size_t, dp, dp]
+    L.pcr_graph_between_weights.argtypes = [vp, C.c_size_t, C.c_size_t, dp, dp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
+    L.pcr_graph_robust_rho_w.argtypes = [C.c_int, C.c_double, C.c_double, dp, dp]
     L.pcr_graph_load_g2o.argtypes = [vp, C.c_char_p]
     L.pcr_graph_save_g2o.argtypes = [vp, C.c_char_p]
     _lib = L
@@ -1437,6 +1445,27 @@ def _graph_precond(kind):
     return int(kind)
 
 
+GRAPH_ROBUST_NONE, GRAPH_ROBUST_HUBER, GRAPH_ROBUST_GEMAN_MCCLURE, GRAPH_ROBUST_TUKEY = 0, 1, 2, 3      # PCR_GRAPH_ROBUST_*
+_GRAPH_ROBUST = {"none": GRAPH_ROBUST_NONE, "huber": GRAPH_ROBUST_HUBER, "geman_mcclure": GRAPH_ROBUST_GEMAN_MCCLURE, "tukey": GRAPH_ROBUST_TUKEY}
+
+
+def _graph_robust(kind):
+    """a PCR_GRAPH_ROBUST_* value, or one of the strings "none", "huber", "geman_mcclure" and "tukey" """
+    if isinstance(kind, str):
+        if kind not in _GRAPH_ROBUST:
+            raise ValueError(f"unknown robust kernel {kind!r}: one of {sorted(_GRAPH_ROBUST)}")
+        return _GRAPH_ROBUST[kind]
+    return int(kind)
+
+
+def graph_robust_rho_w(kind, delta, s):
+    """pcr_graph_robust_rho_w -> (rho(s), w(s)) by the function the linearise kernel compiles (host code)."""
+    rho, w = C.c_double(0), C.c_double(0)
+    if load_library().pcr_graph_robust_rho_w(_graph_robust(kind), float(delta), float(s), C.byref(rho), C.byref(w)):
+        raise PcrError(f"pcr_graph_robust_rho_w: refused (kind {kind}, delta {delta}, s {s})")
+    return rho.value, w.value
+
+
 def graph_noise(kind):
     """pcr_graph_noise -> the 6 x 6 information matrix of one of the reference's noise models (Backend.cpp:90-97), [omega; v] order."""
     buf = np.zeros(21)
@@ -1537,7 +1566,43 @@ class PoseGraph:
         self._between(GRAPH_ODOM, frm, to, between, info)
 
     def addLC(self, frm, to, between, info=None):
-        self._between(GRAPH_LOOP, frm, to, between, info)
+        """pcr_graph_add_loop: a between factor with the LOOP preset that carries the robust mark (under kernel "none" the mark changes nothing)."""
+        _k, ip = self._noise(GRAPH_LOOP, info)
+        pc = _pose_in(between)
+        if int(frm) < 0 or int(to) < 0:
+            raise PcrError("ids must not be negative")
+        self._check(self._lib.pcr_graph_add_loop(self._g, int(frm), int(to), pc.ctypes.data_as(C.POINTER(C.c_double)), ip))
+
+    def setRobustKernel(self, kind, delta=0.0):
+        """pcr_graph_set_robust_kernel: GRAPH_ROBUST_* or "none", "huber", "geman_mcclure", "tukey"; delta in units of a residual's Mahalanobis length."""
+        self._check(self._lib.pcr_graph_set_robust_kernel(self._g, _graph_robust(kind), float(delta)))
+
+    def robustKernel(self):
+        """-> (kind, delta)"""
+        k, d = C.c_int(0), C.c_double(0)
+        self._check(self._lib.pcr_graph_get_robust_kernel(self._g, C.byref(k), C.byref(d)))
+        return k.value, d.value
+
+    def setBetweenRobust(self, first, count=1, on=True):
+        """pcr_graph_set_between_robust: by index among the between factors, in the order added."""
+        self._check(self._lib.pcr_graph_set_between_robust(self._g, int(first), int(count), 1 if on else 0))
+
+    def setBetweenEnabled(self, first, count=1, on=True):
+        """pcr_graph_set_between_enabled: a factor that is off adds nothing and links nothing; it stays in size(), linearize()'s r and J, saveG2o()."""
+        self._check(self._lib.pcr_graph_set_between_enabled(self._g, int(first), int(count), 1 if on else 0))
+
+    def betweenWeights(self, first=0, count=None):
+        """pcr_graph_between_weights -> (s, w, robust, enabled) per between factor at the current estimates: s = r^T Omega r, the kernel's
+        weight at s (1 when unmarked), the mark and the switch as bool arrays."""
+        if count is None:
+            count = max(self.size()[2] - int(first), 0)
+        n = max(int(count), 1)
+        s, w, rb, en = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        d, u = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        self._check(self._lib.pcr_graph_between_weights(self._g, int(first), int(count), s.ctypes.data_as(d), w.ctypes.data_as(d), rb.ctypes.data_as(u),
+                                                        en.ctypes.data_as(u)))
+        c = int(count)
+        return s[:c], w[:c], rb[:c].astype(bool), en[:c].astype(bool)
 
     def addOdomFactor(self, frm, to, info=None):
         """Backend::addOdomFactor: the between factor of the two current estimates."""
