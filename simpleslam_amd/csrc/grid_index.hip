@@ -1388,6 +1388,7 @@ hipError_t GridIndex::build(const float* d_pts, size_t n, size_t stride_floats, 
     BuildPlan p = plan_build(*this, rq);
     // 3. enqueue (a failed build leaves nothing for the next one to reuse)
     const hipError_t e = enqueue_build(p, rq, n_res, cb, s, err, filter);
+    last_plan = p;
     if (e != hipSuccess) { hint_ok = false; header_preset = false; return e; }
     // 4. commit the hints: what the next build of this index -- and of its twin -- may count on
     if (p.feeds_twin) { twin->header_preset = true; twin->preset_pts = d_pts; twin->preset_n = n; twin->preset_cell = twin_cell; twin->mirrored = twin->header_mirror != nullptr; }

@@ -30,7 +30,7 @@ struct GridHeader {
     double cell;             // edge length (a power of two >= gate radius: x/cell is exact)
     double inv_cell;
     int32_t dims[3];         // cells per axis, including 2 pad cells on every side
-    uint32_t n_points;       // points kept (finite coordinates)
+    uint32_t n_points;       // points the build that wrote the header was given (the number INDEXED -- finite, inside the box -- is cell_start[n_cells])
     uint64_t n_cells;        // dims[0]*dims[1]*dims[2]
     int32_t overflow;        // n_cells + 1 exceeds the allocated cell table
     int32_t empty;           // no finite point
@@ -200,6 +200,7 @@ struct GridIndex : BuildHints {
     size_t n_points = 0;
     size_t reserve_points = 0;  // build() sizes its point-sized buffers for at least that many points (a caller whose clouds grow: every growth is an allocation and a free, device-wide stops)
     bool valid = false;
+    BuildPlan last_plan;        // what the last build() enqueued (completed with the answer of the filter's mask callback): for checks and statistics, read by no decision
     GridView view() const {
         return GridView{header.as<GridHeader>(), sorted.as<float4>(), cell_start.as<uint32_t>()};
     }
