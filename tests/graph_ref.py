@@ -136,6 +136,44 @@ def prior_jacobian(X, P):
     return r, jr_inv(r)
 
 
+LM_DEFAULTS = dict(max_iterations=100, rel_tol=1e-5, abs_tol=1e-5, lambda_init=1e-5, lambda_factor=10.0, lambda_max=1e5)
+
+
+def lm_decisions(params, chi2_0, steps):
+    """The Levenberg-Marquardt controller of pcr_graph_optimize (csrc/graph_opt.h) restated: `params` over LM_DEFAULTS, the chi2 of the
+    initial estimates, and per trial step (chi2_new, pcg_iterations, pcg_flag).  Yields per step that is taken a dict: accept (the trial
+    becomes the estimate), stop, and the state after it -- chi2, lambda_, converged, iterations, accepted, pcg_iterations, pcg_capped.
+    `steps` is drawn from only while a trial is wanted, so it may compute each trial from what the last decision left."""
+    assert set(params) <= set(LM_DEFAULTS), sorted(set(params) - set(LM_DEFAULTS))
+    p = {**LM_DEFAULTS, **params}
+    chi2, lam = chi2_0, p["lambda_init"]
+    n = dict(converged=False, iterations=0, accepted=0, pcg_iterations=0, pcg_capped=0)
+    steps = iter(steps)
+    stop = False
+    while not stop and n["iterations"] < p["max_iterations"]:
+        try:
+            c_new, pcg_it, pcg_flag = next(steps)
+        except StopIteration:
+            return
+        n["iterations"] += 1
+        n["pcg_iterations"] += pcg_it
+        n["pcg_capped"] += 1 if pcg_flag == 1 else 0
+        accept = bool(c_new < chi2)
+        if accept:
+            dec, before = chi2 - c_new, chi2
+            chi2 = c_new
+            n["accepted"] += 1
+            lam /= p["lambda_factor"]
+            if dec < p["abs_tol"] or dec < p["rel_tol"] * before:
+                n["converged"] = stop = True
+        elif c_new - chi2 < p["abs_tol"]:      # could not lower chi2 and raised it by less than abs_tol: at its minimum to that tolerance
+            n["converged"] = stop = True
+        else:
+            lam *= p["lambda_factor"]
+            stop = lam > p["lambda_max"]
+        yield dict(accept=accept, stop=bool(stop), chi2=chi2, lambda_=lam, **n)
+
+
 class Graph:
     """priors: (id, P, Omega); betweens: (i, j, Z, Omega); poses: list of 4 x 4."""
 
@@ -193,37 +231,28 @@ class Graph:
             g[sj] += jt[e].T @ Om @ r[e]
         return H, g, chi2
 
-    def optimize(self, max_iterations=100, rel_tol=1e-5, abs_tol=1e-5, lambda_init=1e-5, lambda_factor=10.0, lambda_max=1e5):
-        """Levenberg-Marquardt as pcr_graph_optimize defines it, the step by a dense solve.  -> dict(iterations, accepted, chi2_initial,
-        chi2_final, lambda_, converged); self.poses are updated."""
+    def optimize(self, **params):
+        """Levenberg-Marquardt as pcr_graph_optimize defines it (lm_decisions), the step by a dense solve.  -> dict(iterations, accepted,
+        chi2_initial, chi2_final, lambda_, converged); self.poses are updated."""
         X = [p.copy() for p in self.poses]
         N = len(X)
         H, g, chi2 = self.normal_equations(X)
-        out = dict(iterations=0, accepted=0, chi2_initial=chi2, converged=False)
-        lam = lambda_init
-        while out["iterations"] < max_iterations:
-            d = np.linalg.solve(H + lam * np.eye(6 * N), -g)
-            trial = [X[p] @ exp(d[6 * p:6 * p + 6]) for p in range(N)]
-            c_new = self.chi2(trial)
-            out["iterations"] += 1
-            if c_new < chi2:
-                dec, before = chi2 - c_new, chi2
-                X, chi2 = trial, c_new
+        out = dict(iterations=0, accepted=0, chi2_initial=chi2, converged=False, chi2_final=chi2, lambda_={**LM_DEFAULTS, **params}["lambda_init"])
+        trial = None
+
+        def trials():
+            nonlocal trial
+            while True:
+                d = np.linalg.solve(H + out["lambda_"] * np.eye(6 * N), -g)
+                trial = [X[p] @ exp(d[6 * p:6 * p + 6]) for p in range(N)]
+                yield self.chi2(trial), 0, 0
+
+        for step in lm_decisions(params, chi2, trials()):
+            if step["accept"]:
+                X = trial
                 H, g, _ = self.normal_equations(X)
-                out["accepted"] += 1
-                lam /= lambda_factor
-                if dec < abs_tol or dec < rel_tol * before:
-                    out["converged"] = True
-                    break
-            else:
-                if c_new - chi2 < abs_tol:
-                    out["converged"] = True
-                    break
-                lam *= lambda_factor
-                if lam > lambda_max:
-                    break
+            out.update(chi2_final=step["chi2"], **{k: step[k] for k in ("lambda_", "converged", "iterations", "accepted")})
         self.poses = X
-        out.update(chi2_final=chi2, lambda_=lam)
         return out
 
 
