@@ -526,6 +526,11 @@ float pcr_sc_shift_yaw(int32_t shift);
  *             and stops on sum rho.  Priors and unmarked between factors are never robust.  A between factor that is switched off
  *             (pcr_graph_set_between_enabled) adds nothing to chi2, g and H and links nothing.  Under the defaults -- kernel NONE, every
  *             factor on -- everything above is as if this paragraph were absent, bit for bit.
+ *   fixed     a pose that carries the fixed flag (pcr_graph_set_fixed, a FIX record of a g2o file) is a constant of the problem: the unknowns
+ *             are the free poses, the normal equations those of the full problem without the fixed poses' rows and columns, and every
+ *             pcr_graph_optimize leaves a fixed pose's 16 doubles as they were, bit for bit.  chi2 stays the sum over every factor that is on
+ *             (one between two fixed poses is a constant term; it counts), robust weights are as above.  A fixed pose anchors its connected
+ *             component as a prior does.  With no flag set everything is as if this paragraph were absent, bit for bit.
  * Ids are positions: the poses are numbered from 0 in the order they were added.  Factors may be added before their poses; the graph is
  * checked when it is used.  A pcr_graph is used by one thread at a time. */
 typedef struct pcr_graph pcr_graph;
@@ -556,7 +561,7 @@ typedef struct pcr_graph_result {
     int32_t converged;
     double chi2_initial, chi2_final, lambda;
     double delta[16];              /* X_last after * X_last before ^-1 for the highest id, re-orthonormalised as trans::T2SE3 does: what optimHandler
-                                      hands to the front end (Backend.cpp:321-346) */
+                                      hands to the front end (Backend.cpp:321-346); the identity when that pose is fixed */
 } pcr_graph_result;
 /* device: an ordinal, -1 = current, PCR_GRAPH_HOST = no device at all (everything but optimize and apply works; linearize runs on the host
  * through the same header the kernels compile).  NULL on failure (pcr_graph_last_error(NULL)). */
@@ -591,6 +596,11 @@ int pcr_graph_set_between_robust(pcr_graph* g, size_t first, size_t count, int o
  * It stays in pcr_graph_size, in pcr_graph_linearize's r and J and in pcr_graph_save_g2o.  Setting the kernel, a mark or a switch counts as
  * something new for pcr_graph_optimize. */
 int pcr_graph_set_between_enabled(pcr_graph* g, size_t first, size_t count, int on);
+/* Fixes (on != 0) or frees poses first .. first+count-1.  A range beyond the poses is refused and changes nothing.  Setting or clearing a flag
+ * counts as something new for pcr_graph_optimize; pcr_graph_clear drops the flags with the poses.  pcr_graph_fixed reads them back, one byte
+ * per pose (1: fixed). */
+int pcr_graph_set_fixed(pcr_graph* g, size_t first, size_t count, int on);
+int pcr_graph_fixed(const pcr_graph* g, size_t first, size_t count, uint8_t* fixed);
 /* pcr_graph_add_between plus the robust mark (under NONE the mark changes nothing) */
 int pcr_graph_add_loop(pcr_graph* g, size_t from, size_t to, const double z[16], const double info21[21]);
 /* The verdict, at the current estimates, on device and host graphs (bit for bit alike): for between factors first .. first+count-1, s = r^T Omega r
@@ -604,8 +614,9 @@ int pcr_graph_size(const pcr_graph* g, size_t* n_poses, size_t* n_priors, size_t
 int pcr_graph_clear(pcr_graph* g);
 void pcr_graph_default_params(pcr_graph_params* p);
 /* Refused with a message, before anything is solved: an id out of range; a between factor with from == to; a pose, a measurement or an
- * information matrix that is not finite; a connected component that holds no prior (the message names its first pose); a PCR_GRAPH_HOST
- * graph.  Duplicate edges are allowed and add up.  An empty graph returns 0 and does nothing; so does (0 iterations, converged = 1) a graph
+ * information matrix that is not finite; a connected component that holds neither a prior nor a fixed pose (the message names its first
+ * pose); a PCR_GRAPH_HOST graph.  Duplicate edges are allowed and add up.  An empty graph returns 0 and does nothing; a graph whose poses are
+ * all fixed returns 0 at once with 0 iterations, converged = 1 and chi2 evaluated; so does (0 iterations, converged = 1) a graph
  * to which nothing was added since an optimize that converged under tolerances no looser than this call's -- one that ran out of iterations
  * or of lambda, or converged under looser tolerances, goes on from the current estimates.  params == NULL: the defaults; result may be NULL.  Per trial step one launch holds the whole
  * conjugate-gradient loop (bounded on the device by pcg_max_iterations) and 24 bytes come back to the host. */
@@ -616,19 +627,20 @@ int pcr_graph_poses(const pcr_graph* g, size_t first, size_t count, double* pose
 const double* pcr_graph_device_poses(const pcr_graph* g, size_t* n);
 /* Introspection: every factor linearised at the current estimates, priors first, then betweens, each in the order added: r [E][6],
  * j_from = dr/d(delta_from) and j_to = dr/d(delta_to) [E][36] row-major (a prior's j_from is zero), unweighted for every factor, switched
- * off or not; *chi2 = sum rho over the factors that are on.  Any pointer may be NULL.
+ * off or not, between fixed poses or not; *chi2 = sum rho over the factors that are on.  Any pointer may be NULL.
  * A device graph runs the optimiser's kernel, a PCR_GRAPH_HOST graph the same code on the host: the two agree bit for bit. */
 int pcr_graph_linearize(pcr_graph* g, double* r, double* j_from, double* j_to, double* chi2);
-/* Introspection (device graphs): y = (H + lambda I) x at the current estimates, x and y 6 doubles per pose, by the solve kernel's own product. */
+/* Introspection (device graphs): y = (H + lambda I) x at the current estimates, x and y 6 doubles per pose, by the solve kernel's own product.
+ * H is the solve's: a fixed pose's rows and columns are lambda I (y_p = lambda x_p exactly, and x_p reaches no other row). */
 int pcr_graph_apply(pcr_graph* g, double lambda, const double* x, double* y);
 /* Introspection (host code only; serves a PCR_GRAPH_HOST graph): the spanning forest PCR_GRAPH_PRECOND_TREE would use.  parent[p] = the parent
- * pose of p, -1 for a root (the lowest-numbered pose of its component that holds a prior); n = the entries parent has room for, at least the
+ * pose of p, -1 for a root (the lowest-numbered pose of its component that holds a prior or is fixed); n = the entries parent has room for, at least the
  * number of poses (parent may be NULL, then only the counts are written).  *n_tree_edges between factors are in the forest, *n_other_edges are
  * not (loops, duplicates of a tree edge).  Refuses what pcr_graph_optimize refuses of the graph itself. */
 int pcr_graph_tree(const pcr_graph* g, int64_t* parent, size_t n, size_t* n_tree_edges, size_t* n_other_edges);
 /* Introspection (device graphs): z = M^-1 r at the current estimates, kind = one of PCR_GRAPH_PRECOND_*, r and z 6 doubles per pose, by the
- * factorisation and the sweeps the solve runs.  lambda >= 0; 0 is legal when every pose has a factor.  Nonzero with a message when a block
- * is not positive definite. */
+ * factorisation and the sweeps the solve runs.  lambda >= 0; 0 is legal when every pose has a factor and none is fixed (a fixed pose's block
+ * of M is lambda I: z_p = r_p / lambda, coupled to nothing).  Nonzero with a message when a block is not positive definite. */
 int pcr_graph_precondition(pcr_graph* g, double lambda, int kind, const double* r, double* z);
 /* Poses first .. first+count-1 of the graph become the poses of key frames first .. first+count-1 of the store, read from the graph's device
  * memory.  The store keeps its pose table on the HOST (beside the key frames' offsets), so this is one device-to-host copy inside the library,
@@ -638,7 +650,9 @@ int pcr_map_set_poses_from_graph(pcr_map* m, const pcr_graph* g, size_t first, s
 /* g2o text files: VERTEX_SE3:QUAT and EDGE_SE3:QUAT as Backend::Gtsam::myReadG2o reads them (Backend.cpp:148-193): vertex ids consecutive
  * (continuing the graph's), the information matrix mirrored to both triangles, its translation and rotation blocks swapped into [omega; v]
  * order and its off-diagonal blocks taken as they stand (not transposed, as there); the PRIOR preset is added on vertex 0.  VERTEX3 and EDGE3
- * are refused with a message; other records are skipped.  A file that is refused leaves the graph as it was.  save writes the poses and the
+ * are refused with a message; a FIX record (g2o's convention: "FIX id", one or more ids) fixes those vertices and is refused when the file
+ * defines no vertex of that id (the reference's reader ignores such records); other records are skipped.  A file that is refused leaves the
+ * graph as it was.  save writes the poses, one FIX record per fixed pose after them, and the
  * between factors with 17 significant digits (no priors: they are the reader's own).  The files carry neither robust marks nor switches: save
  * writes every between factor, switched off or not, and a loaded graph has every factor on and unmarked. */
 int pcr_graph_load_g2o(pcr_graph* g, const char* path);

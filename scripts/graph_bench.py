@@ -6,7 +6,10 @@ Reports LM iterations, PCG iterations, microseconds per PCG iteration, milliseco
 same poses as far as it exists here: both host copies plus pcr_map_set_poses (there is no CPU solver in the image to race).
 
 usage: python scripts/graph_bench.py [--sizes 1000,5000,20000] [--cases 'tree+loops,one long loop'] [--pcg-cap 4000] [--json out.json]
-                                    [--preconditioner block_jacobi|tree] [--repeat 1]"""
+                                    [--preconditioner block_jacobi|tree] [--repeat 1] [--free-last W]
+
+--free-last W fixes every pose but the last W before optimising (pcr_graph_set_fixed; profiles/graph_fixed_notes.md): what a key-frame event
+costs with a window."""
 import argparse
 import json
 import os
@@ -84,6 +87,7 @@ def main():
     ap.add_argument("--cases", default="tree+loops,one long loop")
     ap.add_argument("--json", default=None)
     ap.add_argument("--preconditioner", default="block_jacobi", choices=("block_jacobi", "tree"))
+    ap.add_argument("--free-last", type=int, default=0, help="fix every pose but the last W before optimising (0: every pose is free)")
     ap.add_argument("--repeat", type=int, default=1, help="optimisations of a fresh copy of every graph; the fastest is reported (the counts are the same in each)")
     a = ap.parse_args()
     rows = []
@@ -94,12 +98,14 @@ def main():
             ms = None
             for _ in range(max(a.repeat, 1)):
                 pg, n_loops = build(n, kind)
+                if 0 < a.free_last < n:
+                    pg.setFixed(0, n - a.free_last)
                 t0 = time.perf_counter()
                 out = pg.optimize(pcg_max_iterations=a.pcg_cap, max_iterations=a.max_iterations, pcg_preconditioner=a.preconditioner)
                 t = (time.perf_counter() - t0) * 1e3
                 ms = t if ms is None else min(ms, t)
             get_ms, set_ms, apply_ms = alternative_ms(pg, n)
-            row = dict(poses=n, case=kind, preconditioner=a.preconditioner, loops=n_loops, lm_iterations=out.iterations, accepted=out.accepted, pcg_iterations=out.pcg_iterations,
+            row = dict(poses=n, free=int(n - pg.fixed().sum()), case=kind, preconditioner=a.preconditioner, loops=n_loops, lm_iterations=out.iterations, accepted=out.accepted, pcg_iterations=out.pcg_iterations,
                        pcg_capped=out.pcg_capped, converged=out.converged, chi2_initial=out.chi2_initial, chi2_final=out.chi2_final, total_ms=ms,
                        us_per_pcg_iteration=1e3 * ms / max(out.pcg_iterations, 1), host_copy_out_ms=get_ms, set_poses_ms=set_ms, apply_to_ms=apply_ms)
             rows.append(row)

@@ -26,7 +26,9 @@ __device__ __forceinline__ double wave_sum(double v) {
 // ROBUST = PCR_GRAPH_ROBUST_*, chosen on the host.  Under NONE every weight is known up front (1, or 0 when switched off), so Omega r and
 // Omega J leave row by row while s = r^T Omega r still accumulates.  A robust kind needs s before it can scale: the rows of Omega are read
 // twice, first for Omega r and s, then for Omega J, and only six doubles stay live in between.
-template <int ROBUST>
+// FIXED, chosen on the host like ROBUST: the graph holds a fixed pose, and w Omega J of an end that is one leaves as zeros, as both do for a
+// factor that is off.  Without it the two bits are never looked at.
+template <int ROBUST, bool FIXED>
 __global__ __launch_bounds__(kLinBlock) void graph_linearize_kernel(const double* __restrict__ poses, const Factors f, const Robust rb, const Lin out,
                                                                     double* __restrict__ partial) {
     __shared__ double wsum[kLinBlock / 64];
@@ -37,6 +39,7 @@ __global__ __launch_bounds__(kLinBlock) void graph_linearize_kernel(const double
         const int from = f.from[e], to = f.to[e];
         const unsigned char fl = f.flags[e];
         const bool on = (fl & kFactorOff) == 0;
+        const bool on_f = FIXED ? (on && (fl & kFactorFromFixed) == 0) : on, on_t = FIXED ? (on && (fl & kFactorToFixed) == 0) : on;
         double Xi[16], Xj[16], Z[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
@@ -63,8 +66,8 @@ __global__ __launch_bounds__(kLinBlock) void graph_linearize_kernel(const double
                     double sf = 0.0, st = 0.0;
 #pragma unroll
                     for (int m = 0; m < 6; ++m) { sf += o[m] * Jf[m * 6 + b]; st += o[m] * Jt[m * 6 + b]; }
-                    out.wjf[(size_t)(k * 6 + b) * F + e] = on ? sf : 0.0;
-                    out.wjt[(size_t)(k * 6 + b) * F + e] = on ? st : 0.0;
+                    out.wjf[(size_t)(k * 6 + b) * F + e] = on_f ? sf : 0.0;
+                    out.wjt[(size_t)(k * 6 + b) * F + e] = on_t ? st : 0.0;
                     out.jf[(size_t)(k * 6 + b) * F + e] = Jf[k * 6 + b];
                     out.jt[(size_t)(k * 6 + b) * F + e] = Jt[k * 6 + b];
                 }
@@ -96,8 +99,8 @@ __global__ __launch_bounds__(kLinBlock) void graph_linearize_kernel(const double
                     double sf = 0.0, st = 0.0;
 #pragma unroll
                     for (int m = 0; m < 6; ++m) { sf += o[m] * Jf[m * 6 + b]; st += o[m] * Jt[m * 6 + b]; }
-                    out.wjf[(size_t)(k * 6 + b) * F + e] = on ? wk * sf : 0.0;
-                    out.wjt[(size_t)(k * 6 + b) * F + e] = on ? wk * st : 0.0;
+                    out.wjf[(size_t)(k * 6 + b) * F + e] = on_f ? wk * sf : 0.0;
+                    out.wjt[(size_t)(k * 6 + b) * F + e] = on_t ? wk * st : 0.0;
                     out.jf[(size_t)(k * 6 + b) * F + e] = Jf[k * 6 + b];
                     out.jt[(size_t)(k * 6 + b) * F + e] = Jt[k * 6 + b];
                 }
@@ -124,7 +127,18 @@ __global__ __launch_bounds__(64) void graph_chi2_fold_kernel(const double* __res
 }
 
 // ---- the two passes of y = (H + lambda I) x, shared by the solve and by pcr_graph_apply --------------------------------------------------
+// Fixed poses (FIXED: the graph holds one).  The linearisation wrote zeros for Omega J of a fixed end, which alone makes the pose's row of H
+// vanish (pose_product), its diagonal block lambda I and the tree's coupling A_qp zero when the PARENT is fixed.  Three terms read the
+// unweighted J of an end and are masked by the factor's two bits: u_e (below: x of a fixed end counts as 0, its column of H), g_p (the set-up
+// loops leave a fixed pose's row out altogether: J_p^T w Omega r is not taken, and its block J_p^T (w Omega J_p) would be a sum of zeros) and
+// A_qp when the CHILD is fixed (tree_factorize).  With these g_p = 0, res_p = z_p = dir_p = 0 from the start, and the
+// conjugate gradient keeps x_p at exactly 0 under both preconditioners.
+__device__ __forceinline__ bool end_is_fixed(const Factors& f, int ent) {
+    return (f.flags[ent >> 1] & ((ent & 1) ? kFactorToFixed : kFactorFromFixed)) != 0;
+}
+
 // pass 1, over the factors: u_e = J_from x_from + J_to x_to
+template <bool FIXED>
 __device__ __forceinline__ void edge_pass(const Factors& f, const Lin& lin, const double* __restrict__ x, double* __restrict__ u, int tid, int nthreads) {
     const int F = f.F;
     for (int e = tid; e < F; e += nthreads) {
@@ -132,6 +146,11 @@ __device__ __forceinline__ void edge_pass(const Factors& f, const Lin& lin, cons
         double xt[6], xf[6], acc[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) { xt[k] = x[(size_t)to * 6 + k]; xf[k] = (from >= 0) ? x[(size_t)from * 6 + k] : 0.0; }
+        if (FIXED) {
+            const unsigned char fl = f.flags[e];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) { if (fl & kFactorToFixed) xt[k] = 0.0; if (fl & kFactorFromFixed) xf[k] = 0.0; }
+        }
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
             double s = 0.0;
@@ -192,7 +211,7 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* lds) {
 // one pose's gradient g_p and its diagonal block of the preconditioner (lower triangle), over p's incident factors in CSR order:
 // lambda I + sum J^T Omega J -- over every factor for the block-diagonal preconditioner, over the priors and the tree edges (in_m) for the
 // tree's.  g takes every factor either way.
-template <bool TREE>
+template <bool TREE, bool FIXED>
 __device__ __forceinline__ void pose_blocks(int p, const Factors& f, const Lin& lin, const Csr& csr, const unsigned char* __restrict__ in_m,
                                             double lambda, double* g, double* D) {
     const int F = f.F;
@@ -202,7 +221,9 @@ __device__ __forceinline__ void pose_blocks(int p, const Factors& f, const Lin& 
     for (int i = 0; i < 6; ++i)
 #pragma unroll
         for (int j = 0; j <= i; ++j) D[gm::tri(i, j)] = (i == j) ? lambda : 0.0;
-    const int lo = csr.row_ptr[p], hi = csr.row_ptr[p + 1];
+    // p is a fixed pose (every entry of its row says so): its row is left out, g_p = 0 and the block lambda I
+    const int lo = csr.row_ptr[p], row_end = csr.row_ptr[p + 1];
+    const int hi = (FIXED && lo < row_end && end_is_fixed(f, csr.ent[lo])) ? lo : row_end;
     for (int i = lo; i < hi; ++i) {
         const int ent = csr.ent[i];
         const int e = ent >> 1;
@@ -235,6 +256,7 @@ __device__ __forceinline__ void pose_blocks(int p, const Factors& f, const Lin& 
 // On entry L[q] holds position q's diagonal block of M (a barrier has passed since it was written).  On return L[q] is the Cholesky factor
 // of D_q = A_qq - sum over children G_c A_cq, t.G[q] = A_pq D_q^-1 for the parent p, and a barrier has passed.  false: some D_q of this
 // lane's was not positive definite.
+template <bool FIXED>
 __device__ __forceinline__ bool tree_factorize(const Factors& f, const Lin& lin, const Tree& t, double* __restrict__ L, int tid) {
     const int F = f.F;
     bool ok = true;
@@ -261,6 +283,17 @@ __device__ __forceinline__ bool tree_factorize(const Factors& f, const Lin& lin,
                 const int e = ent >> 1;
                 const double* __restrict__ J = (ent & 1) ? lin.jt : lin.jf;        // this node's end
                 const double* __restrict__ WJ = (ent & 1) ? lin.wjf : lin.wjt;     // Omega J of the parent's end
+                if (FIXED && end_is_fixed(f, ent)) {      // this node is a fixed pose: no coupling to its parent, A_qp = 0
+#pragma unroll
+                    for (int k = 0; k < 36; ++k) t.G[(size_t)q * 36 + k] = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 21; ++k) Sp[k] = 0.0;
+                    if (q == q1 - 1) {
+#pragma unroll
+                        for (int k = 0; k < 21; ++k) t.S[(size_t)q * 21 + k] = 0.0;
+                    }
+                    continue;
+                }
                 double A[36];      // A_qp = J_q^T Omega J_p, rows in this node's space
 #pragma unroll
                 for (int k = 0; k < 36; ++k) A[k] = 0.0;
@@ -390,6 +423,7 @@ __device__ __forceinline__ void tree_solve(int N, const Tree& t, const double* _
 // ---- solve: the whole PCG of one trial step on one workgroup ------------------------------------------------------------------------------
 // (H + lambda I) x = -g with H = sum J^T Omega J, g = sum J^T Omega r; preconditioner: the inverse of every pose's 6x6 diagonal block.
 // Threads stride over the poses and over the factors.  Writes are made visible to the workgroup by the barriers: one workgroup is one CU.
+template <bool FIXED>
 __global__ __launch_bounds__(kSolveThreads) void graph_solve_kernel(const int N, const Factors f, const Lin lin, const Csr csr, const double lambda,
                                                                     const int max_it, const double tol, const SolveBufs b, double* __restrict__ status) {
     __shared__ double red_a[2 * 16], red_b[2 * 16];
@@ -399,14 +433,15 @@ __global__ __launch_bounds__(kSolveThreads) void graph_solve_kernel(const int N,
     // set-up: g_p, the diagonal block, its Cholesky factor; x = 0, res = -g, z = M^-1 res, dir = z
     double acc[2] = {0.0, 0.0};      // |g|^2, res . z
     for (int p = tid; p < N; p += kSolveThreads) {
-        double g[6], D[21];      // (pose_blocks<false> below, kept inline: this kernel's code and registers are as they were measured)
+        double g[6], D[21];      // (pose_blocks<false, FIXED> below, kept inline: this kernel's code and registers are as they were measured)
 #pragma unroll
         for (int k = 0; k < 6; ++k) g[k] = 0.0;
 #pragma unroll
         for (int i = 0; i < 6; ++i)
 #pragma unroll
             for (int j = 0; j <= i; ++j) D[gm::tri(i, j)] = (i == j) ? lambda : 0.0;
-        const int lo = csr.row_ptr[p], hi = csr.row_ptr[p + 1];
+        const int lo = csr.row_ptr[p], row_end = csr.row_ptr[p + 1];
+        const int hi = (FIXED && lo < row_end && end_is_fixed(f, csr.ent[lo])) ? lo : row_end;      // a fixed pose's row is left out: g_p = 0, the block lambda I
         for (int i = lo; i < hi; ++i) {
             const int ent = csr.ent[i];
             const int e = ent >> 1;
@@ -451,7 +486,7 @@ __global__ __launch_bounds__(kSolveThreads) void graph_solve_kernel(const int N,
 
     while (flag == 1 && it < max_it) {
         // (a barrier stands between the writes of dir and this pass: the set-up's block_sum on entry, the loop's own afterwards)
-        edge_pass(f, lin, b.dir, b.u, tid, kSolveThreads);
+        edge_pass<FIXED>(f, lin, b.dir, b.u, tid, kSolveThreads);
         __syncthreads();
         double pap[1] = {0.0};
         for (int p = tid; p < N; p += kSolveThreads) {
@@ -502,6 +537,7 @@ __global__ __launch_bounds__(kSolveThreads) void graph_solve_kernel(const int N,
 
 // The same PCG with the tree preconditioner.  M is factorised once per launch (lambda and the linearisation change per trial step); a block
 // that is not positive definite ends the launch with flag 2 and x = 0, as a curvature that is not positive does.  b.L is indexed by position.
+template <bool FIXED>
 __global__ __launch_bounds__(kSolveThreads) void graph_solve_tree_kernel(const int N, const Factors f, const Lin lin, const Csr csr, const Tree t,
                                                                          const double lambda, const int max_it, const double tol, const SolveBufs b,
                                                                          double* __restrict__ status) {
@@ -513,7 +549,7 @@ __global__ __launch_bounds__(kSolveThreads) void graph_solve_tree_kernel(const i
     for (int q = tid; q < N; q += kSolveThreads) {
         const int p = t.node[q];
         double g[6], D[21];
-        pose_blocks<true>(p, f, lin, csr, t.in_m, lambda, g, D);
+        pose_blocks<true, FIXED>(p, f, lin, csr, t.in_m, lambda, g, D);
 #pragma unroll
         for (int k = 0; k < 21; ++k) b.L[(size_t)q * 21 + k] = D[k];
 #pragma unroll
@@ -524,7 +560,7 @@ __global__ __launch_bounds__(kSolveThreads) void graph_solve_tree_kernel(const i
         }
     }
     block_sum(gg, red_b);      // (its barrier stands between the blocks' writes and the factorisation)
-    const bool ok = tree_factorize(f, lin, t, b.L, tid);
+    const bool ok = tree_factorize<FIXED>(f, lin, t, b.L, tid);
     const int bad = __syncthreads_or(ok ? 0 : 1);
     const double gnorm = sqrt(gg[0]);
     double relres = (gnorm > 0.0) ? 1.0 : 0.0;
@@ -549,7 +585,7 @@ __global__ __launch_bounds__(kSolveThreads) void graph_solve_tree_kernel(const i
     }
 
     while (flag == 1 && it < max_it) {
-        edge_pass(f, lin, b.dir, b.u, tid, kSolveThreads);
+        edge_pass<FIXED>(f, lin, b.dir, b.u, tid, kSolveThreads);
         __syncthreads();
         double pap[1] = {0.0};
         for (int p = tid; p < N; p += kSolveThreads) {
@@ -603,7 +639,7 @@ __global__ __launch_bounds__(kSolveThreads) void graph_solve_tree_kernel(const i
 }
 
 // pcr_graph_precondition: z = M^-1 r by the factorisation and the sweeps of the solve of that kind; r in b.res, z into b.z, both by pose
-template <bool TREE>
+template <bool TREE, bool FIXED>
 __global__ __launch_bounds__(kSolveThreads) void graph_precondition_kernel(const int N, const Factors f, const Lin lin, const Csr csr, const Tree t,
                                                                            const double lambda, const SolveBufs b, int* __restrict__ flag) {
     const int tid = threadIdx.x;
@@ -611,12 +647,12 @@ __global__ __launch_bounds__(kSolveThreads) void graph_precondition_kernel(const
     if (TREE) {
         for (int q = tid; q < N; q += kSolveThreads) {
             double g[6], D[21];
-            pose_blocks<true>(t.node[q], f, lin, csr, t.in_m, lambda, g, D);
+            pose_blocks<true, FIXED>(t.node[q], f, lin, csr, t.in_m, lambda, g, D);
 #pragma unroll
             for (int k = 0; k < 21; ++k) b.L[(size_t)q * 21 + k] = D[k];
         }
         __syncthreads();
-        ok = tree_factorize(f, lin, t, b.L, tid);
+        ok = tree_factorize<FIXED>(f, lin, t, b.L, tid);
         tree_solve(N, t, b.L, b.res, tid);
         for (int p = tid; p < N; p += kSolveThreads) {
             const int q = t.pos_of[p];
@@ -626,7 +662,7 @@ __global__ __launch_bounds__(kSolveThreads) void graph_precondition_kernel(const
     } else {
         for (int p = tid; p < N; p += kSolveThreads) {
             double g[6], D[21], res[6], z[6];
-            pose_blocks<false>(p, f, lin, csr, nullptr, lambda, g, D);
+            pose_blocks<false, FIXED>(p, f, lin, csr, nullptr, lambda, g, D);
             ok = gm::chol6(D) && ok;
 #pragma unroll
             for (int k = 0; k < 6; ++k) res[k] = b.res[(size_t)p * 6 + k];
@@ -639,9 +675,10 @@ __global__ __launch_bounds__(kSolveThreads) void graph_precondition_kernel(const
     if (tid == 0) flag[0] = bad ? 2 : 0;
 }
 
+template <bool FIXED>
 __global__ __launch_bounds__(kSolveThreads) void graph_apply_kernel(const int N, const Factors f, const Lin lin, const Csr csr, const double lambda,
                                                                     const double* __restrict__ x, double* __restrict__ y, double* __restrict__ u) {
-    edge_pass(f, lin, x, u, threadIdx.x, kSolveThreads);
+    edge_pass<FIXED>(f, lin, x, u, threadIdx.x, kSolveThreads);
     __syncthreads();
     for (int p = threadIdx.x; p < N; p += kSolveThreads) {
         double xp[6], yp[6];
@@ -654,13 +691,20 @@ __global__ __launch_bounds__(kSolveThreads) void graph_apply_kernel(const int N,
 }
 
 // ---- retract: X_trial = X Exp(delta) ----------------------------------------------------------------------------------------------------
+// A fixed pose's 16 doubles are COPIED (FIXED; pose_fixed per pose): its delta is 0, but nothing here rests on X Exp(0) returning X's bits.
+template <bool FIXED>
 __global__ __launch_bounds__(256) void graph_retract_kernel(const int N, const double* __restrict__ poses, const double* __restrict__ delta,
-                                                            double* __restrict__ out) {
+                                                            const unsigned char* __restrict__ pose_fixed, double* __restrict__ out) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= N) return;
     double X[16], d[6], E[16], Y[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) X[k] = poses[(size_t)p * 16 + k];
+    if (FIXED && pose_fixed[p]) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) out[(size_t)p * 16 + k] = X[k];
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < 6; ++k) d[k] = delta[(size_t)p * 6 + k];
     gm::se3_exp(d, E);
@@ -671,48 +715,61 @@ __global__ __launch_bounds__(256) void graph_retract_kernel(const int N, const d
 
 }  // namespace
 
-hipError_t launch_linearize(const double* poses, const Factors& f, const Robust& rb, const Lin& out, double* partial, double* status, hipStream_t s) {
+hipError_t launch_linearize(const double* poses, const Factors& f, const Robust& rb, bool fixed, const Lin& out, double* partial, double* status,
+                            hipStream_t s) {
     const int nb = lin_blocks(f.F);
     if (nb > 0) {
+#define PCR_GRAPH_LIN(K) \
+    if (fixed) hipLaunchKernelGGL((graph_linearize_kernel<K, true>), dim3(nb), dim3(kLinBlock), 0, s, poses, f, rb, out, partial); \
+    else hipLaunchKernelGGL((graph_linearize_kernel<K, false>), dim3(nb), dim3(kLinBlock), 0, s, poses, f, rb, out, partial)
         switch (rb.kind) {
-            case 0: hipLaunchKernelGGL(graph_linearize_kernel<0>, dim3(nb), dim3(kLinBlock), 0, s, poses, f, rb, out, partial); break;
-            case 1: hipLaunchKernelGGL(graph_linearize_kernel<1>, dim3(nb), dim3(kLinBlock), 0, s, poses, f, rb, out, partial); break;
-            case 2: hipLaunchKernelGGL(graph_linearize_kernel<2>, dim3(nb), dim3(kLinBlock), 0, s, poses, f, rb, out, partial); break;
-            case 3: hipLaunchKernelGGL(graph_linearize_kernel<3>, dim3(nb), dim3(kLinBlock), 0, s, poses, f, rb, out, partial); break;
+            case 0: PCR_GRAPH_LIN(0); break;
+            case 1: PCR_GRAPH_LIN(1); break;
+            case 2: PCR_GRAPH_LIN(2); break;
+            case 3: PCR_GRAPH_LIN(3); break;
             default: return hipErrorInvalidValue;      // (pcr_graph_set_robust_kernel refuses every other kind)
         }
+#undef PCR_GRAPH_LIN
     }
     hipLaunchKernelGGL(graph_chi2_fold_kernel, dim3(1), dim3(64), 0, s, partial, nb, status);
     return hipGetLastError();
 }
 
-hipError_t launch_solve(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, int max_it, double tol, const SolveBufs& b,
+hipError_t launch_solve(int N, const Factors& f, bool fixed, const Lin& lin, const Csr& csr, double lambda, int max_it, double tol, const SolveBufs& b,
                         double* status, hipStream_t s) {
-    hipLaunchKernelGGL(graph_solve_kernel, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, lambda, max_it, tol, b, status);
+    if (fixed) hipLaunchKernelGGL(graph_solve_kernel<true>, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, lambda, max_it, tol, b, status);
+    else hipLaunchKernelGGL(graph_solve_kernel<false>, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, lambda, max_it, tol, b, status);
     return hipGetLastError();
 }
 
-hipError_t launch_solve_tree(int N, const Factors& f, const Lin& lin, const Csr& csr, const Tree& t, double lambda, int max_it, double tol,
+hipError_t launch_solve_tree(int N, const Factors& f, bool fixed, const Lin& lin, const Csr& csr, const Tree& t, double lambda, int max_it, double tol,
                              const SolveBufs& b, double* status, hipStream_t s) {
-    hipLaunchKernelGGL(graph_solve_tree_kernel, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, t, lambda, max_it, tol, b, status);
+    if (fixed) hipLaunchKernelGGL(graph_solve_tree_kernel<true>, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, t, lambda, max_it, tol, b, status);
+    else hipLaunchKernelGGL(graph_solve_tree_kernel<false>, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, t, lambda, max_it, tol, b, status);
     return hipGetLastError();
 }
 
-hipError_t launch_precondition(int N, const Factors& f, const Lin& lin, const Csr& csr, const Tree* t, double lambda, const SolveBufs& b, int* flag,
-                               hipStream_t s) {
-    if (t) hipLaunchKernelGGL(graph_precondition_kernel<true>, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, *t, lambda, b, flag);
-    else hipLaunchKernelGGL(graph_precondition_kernel<false>, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, Tree{}, lambda, b, flag);
+hipError_t launch_precondition(int N, const Factors& f, bool fixed, const Lin& lin, const Csr& csr, const Tree* t, double lambda, const SolveBufs& b,
+                               int* flag, hipStream_t s) {
+    const Tree tr = t ? *t : Tree{};
+    if (t && fixed) hipLaunchKernelGGL((graph_precondition_kernel<true, true>), dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, tr, lambda, b, flag);
+    else if (t) hipLaunchKernelGGL((graph_precondition_kernel<true, false>), dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, tr, lambda, b, flag);
+    else if (fixed) hipLaunchKernelGGL((graph_precondition_kernel<false, true>), dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, tr, lambda, b, flag);
+    else hipLaunchKernelGGL((graph_precondition_kernel<false, false>), dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, tr, lambda, b, flag);
     return hipGetLastError();
 }
 
-hipError_t launch_apply(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, const double* x, double* y, double* u, hipStream_t s) {
-    hipLaunchKernelGGL(graph_apply_kernel, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, lambda, x, y, u);
+hipError_t launch_apply(int N, const Factors& f, bool fixed, const Lin& lin, const Csr& csr, double lambda, const double* x, double* y, double* u,
+                        hipStream_t s) {
+    if (fixed) hipLaunchKernelGGL(graph_apply_kernel<true>, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, lambda, x, y, u);
+    else hipLaunchKernelGGL(graph_apply_kernel<false>, dim3(1), dim3(kSolveThreads), 0, s, N, f, lin, csr, lambda, x, y, u);
     return hipGetLastError();
 }
 
-hipError_t launch_retract(int N, const double* poses, const double* delta, double* out, hipStream_t s) {
+hipError_t launch_retract(int N, const double* poses, const double* delta, const unsigned char* pose_fixed, double* out, hipStream_t s) {
     if (N <= 0) return hipSuccess;
-    hipLaunchKernelGGL(graph_retract_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, poses, delta, out);
+    if (pose_fixed) hipLaunchKernelGGL(graph_retract_kernel<true>, dim3((N + 255) / 256), dim3(256), 0, s, N, poses, delta, pose_fixed, out);
+    else hipLaunchKernelGGL(graph_retract_kernel<false>, dim3((N + 255) / 256), dim3(256), 0, s, N, poses, delta, pose_fixed, out);
     return hipGetLastError();
 }
 

@@ -12,13 +12,16 @@ struct Factors {
     const int* to;
     const double* z;          // [16][F] measurement (a prior: the prior pose), column-major pose entries
     const double* omega;      // [36][F] information, full symmetric, row-major entries
-    const unsigned char* flags;      // [F] kFactorRobust: the robust kernel applies (between factors only); kFactorOff: switched off
+    const unsigned char* flags;      // [F] kFactorRobust: the robust kernel applies (between factors only); kFactorOff: switched off;
+                                     //     kFactorFromFixed, kFactorToFixed: that end is a fixed pose
 };
-constexpr unsigned char kFactorRobust = 1, kFactorOff = 2;
+constexpr unsigned char kFactorRobust = 1, kFactorOff = 2, kFactorFromFixed = 4, kFactorToFixed = 8;
 
 // One linearisation: per factor r (6), J_from, J_to (36 each, row-major entries) as they are; w Omega r (6), w Omega J_from, w Omega J_to with
 // the factor's weight w (1; the robust kernel's w(s) on a marked factor; 0 on one switched off), which is all the solve reads of Omega;
 // c = rho(s) (0 when switched off); s = r^T Omega r and the kernel's w(s) whatever the switch says (pcr_graph_between_weights).
+// Fixed poses: w Omega J of an end that is a fixed pose is written as zeros (its rows and columns leave H); r, J, w Omega r, c, s and w are as
+// without the flag.  What the solve reads of the unweighted J of such an end (g_p, u_e, the tree's couplings) it masks by the same two bits.
 struct Lin {
     double *r, *wr, *jf, *jt, *wjf, *wjt, *c, *s, *w;
     static constexpr size_t kDoublesPerFactor = 6 + 6 + 4 * 36 + 3;
@@ -62,23 +65,27 @@ inline int lin_blocks(int F) { return (F + kLinBlock - 1) / kLinBlock; }
 
 // The robust kernel of the marked factors: kind = PCR_GRAPH_ROBUST_*, d = delta^2.  The kernel is chosen on the host and compiled in.
 struct Robust { int kind = 0; double delta = 0.0, d = 0.0; };
+// `fixed` below: the graph holds a fixed pose.  It too is chosen on the host and compiled in: a graph without one runs the instantiations that
+// never look at the two bits.
 
 // linearise every factor at `poses` into `out`, the sum of rho into status[0] (partial: lin_blocks(F) doubles)
-hipError_t launch_linearize(const double* poses, const Factors& f, const Robust& rb, const Lin& out, double* partial, double* status, hipStream_t s);
+hipError_t launch_linearize(const double* poses, const Factors& f, const Robust& rb, bool fixed, const Lin& out, double* partial, double* status,
+                            hipStream_t s);
 // delta (= bufs.x) <- PCG on (H + lambda I) delta = -g, one workgroup; status[1], status[2]
-hipError_t launch_solve(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, int max_it, double tol, const SolveBufs& b,
+hipError_t launch_solve(int N, const Factors& f, bool fixed, const Lin& lin, const Csr& csr, double lambda, int max_it, double tol, const SolveBufs& b,
                         double* status, hipStream_t s);
 // the same solve preconditioned by the spanning forest: M = lambda I + priors + tree edges, factorised once per launch (b.L by position)
-hipError_t launch_solve_tree(int N, const Factors& f, const Lin& lin, const Csr& csr, const Tree& t, double lambda, int max_it, double tol,
+hipError_t launch_solve_tree(int N, const Factors& f, bool fixed, const Lin& lin, const Csr& csr, const Tree& t, double lambda, int max_it, double tol,
                              const SolveBufs& b, double* status, hipStream_t s);
 // z = M^-1 r by the factorisation and the sweeps of the solve of that kind (tree: the forest's; otherwise the diagonal blocks'); flag[0] = 2 when a
 // block was not positive definite, else 0.  b.L, b.res (= r) and b.z are used.
-hipError_t launch_precondition(int N, const Factors& f, const Lin& lin, const Csr& csr, const Tree* t, double lambda, const SolveBufs& b, int* flag,
-                               hipStream_t s);
+hipError_t launch_precondition(int N, const Factors& f, bool fixed, const Lin& lin, const Csr& csr, const Tree* t, double lambda, const SolveBufs& b,
+                               int* flag, hipStream_t s);
 // y = (H + lambda I) x by the solve's own two passes (b.u is used)
-hipError_t launch_apply(int N, const Factors& f, const Lin& lin, const Csr& csr, double lambda, const double* x, double* y, double* u, hipStream_t s);
-// out[p] = poses[p] * Exp(delta[p])
-hipError_t launch_retract(int N, const double* poses, const double* delta, double* out, hipStream_t s);
+hipError_t launch_apply(int N, const Factors& f, bool fixed, const Lin& lin, const Csr& csr, double lambda, const double* x, double* y, double* u,
+                        hipStream_t s);
+// out[p] = poses[p] * Exp(delta[p]); with pose_fixed (per pose, or NULL: no pose is fixed) a fixed pose's 16 doubles are copied instead
+hipError_t launch_retract(int N, const double* poses, const double* delta, const unsigned char* pose_fixed, double* out, hipStream_t s);
 
 }  // namespace graph
 }  // namespace pcr

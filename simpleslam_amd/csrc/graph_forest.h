@@ -4,8 +4,9 @@
 //
 // The rule.  The between factors are taken in the order they were added; one joins the forest when its two ends lie in different components
 // (union-find).  Every other between factor -- a loop closure, a duplicate of a tree edge, whatever its noise and whichever way it points --
-// is left to the conjugate gradient.  The root of a component is its lowest-numbered pose that holds a prior (a component without a prior,
-// which pcr_graph_optimize refuses, is rooted at its lowest-numbered pose).  No ordering of the ids is assumed.
+// is left to the conjugate gradient.  The root of a component is its lowest-numbered ANCHOR: a pose that holds a prior or is fixed (a component
+// without one, which pcr_graph_optimize refuses, is rooted at its lowest-numbered pose).  The caller lists the fixed poses among prior_id[]:
+// to this function the two kinds of anchor are one, and without a fixed pose the plan is what it was before poses could be fixed.  No ordering of the ids is assumed.
 //
 // The schedule.  Every tree is cut into paths: a node continues into its child with the largest subtree (the lowest id on a tie), every
 // other ("light") child heads a path of its own.  A path's round is 0 when no light child hangs off its nodes, otherwise 1 + the largest
@@ -36,7 +37,8 @@ struct ForestPlan {
     int rounds() const { return (int)round_ptr.size() - 1; }
 };
 
-// N poses; B between factors (from[e], to[e], every id in [0, N), from != to); P priors on the poses prior_id[].
+// N poses; B between factors (from[e], to[e], every id in [0, N), from != to); P anchors: the poses prior_id[] hold a prior or are fixed
+// (in any order, repeats allowed).
 inline ForestPlan plan_forest(size_t N, const long long* from, const long long* to, size_t B, const long long* prior_id, size_t P) {
     ForestPlan f;
     const int n = (int)N;
@@ -72,7 +74,7 @@ inline ForestPlan plan_forest(size_t N, const long long* from, const long long* 
         adj[fill[to[e]]++] = (int)(e * 2 + 1);         // ... its "from" end
     }
 
-    // roots: per component the lowest-numbered pose with a prior, else the lowest-numbered pose
+    // roots: per component the lowest-numbered anchor, else the lowest-numbered pose
     std::vector<int> root(N, -1);
     std::vector<uint8_t> has_prior(N, 0);
     for (size_t i = 0; i < P; ++i) has_prior[prior_id[i]] = 1;

@@ -27,7 +27,8 @@ using namespace pcr::graph;
 using namespace pcr::graph_opt;
 namespace gm = pcr::gm;
 
-static_assert(kMarkRobust == kFactorRobust && kMarkOff == kFactorOff, "the store's flags are the bits the kernels read");
+static_assert(kMarkRobust == kFactorRobust && kMarkOff == kFactorOff && kPackFromFixed == kFactorFromFixed && kPackToFixed == kFactorToFixed,
+              "the store's flags are the bits the kernels read");
 
 namespace {
 
@@ -71,7 +72,8 @@ struct Device {
     int ordinal = 0;
     hipStream_t stream = nullptr;
     Status* h_status = nullptr;      // page-locked
-    DBuf poses[2], lin[2], from, to, z, omega, flags, rowptr, ent, vec, u, partial, status, tree_i, tree_d, in_m;
+    DBuf poses[2], lin[2], from, to, z, omega, flags, pose_fixed, rowptr, ent, vec, u, partial, status, tree_i, tree_d, in_m;
+    bool any_fixed = false;          // a pose of the packed tables is fixed: the launches take the instantiations that read the flags
     int cur = 0;                     // which of poses[] / lin[] holds the current estimates
     size_t n_poses = 0;              // poses the device holds
     bool ahead = false;              // ... and an optimisation moved them: the store's first n_poses are older
@@ -176,6 +178,7 @@ static int upload(pcr_graph* g) {
         {d.from, k.from.data(), (F + 1) * sizeof(int), F * sizeof(int)},
         {d.to, k.to.data(), (F + 1) * sizeof(int), F * sizeof(int)},
         {d.flags, k.flags.data(), k.flags.size(), F},
+        {d.pose_fixed, k.pose_fixed.data(), k.pose_fixed.size(), N},
         {d.z, k.z.data(), (16 * F + 1) * sizeof(double), 16 * F * sizeof(double)},
         {d.omega, k.omega.data(), (36 * F + 1) * sizeof(double), 36 * F * sizeof(double)},
         {d.rowptr, k.row_ptr.data(), (N + 1) * sizeof(int), (N + 1) * sizeof(int)},
@@ -187,6 +190,7 @@ static int upload(pcr_graph* g) {
     G_TRY(d.u.reserve((6 * F + 1) * sizeof(double), false));
     for (const auto& t : tables) if (t.bytes) G_TRY(hipMemcpy(t.buf.p, t.src, t.bytes, hipMemcpyHostToDevice));
     d.F = F;
+    d.any_fixed = k.any_fixed;
     d.factors_rev = g->store.structure;
     return 0;
 }
@@ -195,7 +199,8 @@ static int upload(pcr_graph* g) {
 static const ForestPlan& forest_of(pcr_graph* g) {
     const Store& s = g->store;
     if (g->forest_rev != s.structure) {
-        // over the between factors that are switched on; the plan's factor indices are then put back into the full list's
+        // over the between factors that are switched on; the plan's factor indices are then put back into the full list's.  The anchors a
+        // root is chosen among: the poses that hold a prior and the fixed poses.
         std::vector<long long> from, to, prior(s.priors.size());
         std::vector<int> full;
         for (size_t e = 0; e < s.betweens.size(); ++e) {
@@ -203,6 +208,7 @@ static const ForestPlan& forest_of(pcr_graph* g) {
             from.push_back(s.betweens[e].from); to.push_back(s.betweens[e].to); full.push_back((int)e);
         }
         for (size_t i = 0; i < s.priors.size(); ++i) prior[i] = s.priors[i].to;
+        for (size_t p = 0; p < s.n_poses(); ++p) if (s.is_fixed(p)) prior.push_back((long long)p);
         g->forest = plan_forest(s.n_poses(), from.data(), to.data(), from.size(), prior.data(), prior.size());
         std::vector<uint8_t> in_tree(s.betweens.size(), 0);
         for (size_t k = 0; k < full.size(); ++k) in_tree[full[k]] = g->forest.in_tree[k];
@@ -249,6 +255,8 @@ struct Ctx {
     size_t N = 0, P = 0, F = 0;
     Factors fac;
     Robust rb;
+    bool fixed = false;         // the graph holds a fixed pose ...
+    const unsigned char* pose_fixed = nullptr;      // ... and then the flag per pose
     Csr csr;
     double* poses[2];
     Lin lin[2];
@@ -269,6 +277,7 @@ static int prepare(pcr_graph* g, bool tree, Ctx* c) {
     c->fac.F = (int)F; c->fac.from = d.from.as<int>(); c->fac.to = d.to.as<int>(); c->fac.z = d.z.as<double>(); c->fac.omega = d.omega.as<double>();
     c->fac.flags = d.flags.as<unsigned char>();
     c->rb.kind = g->store.robust_kind; c->rb.delta = g->store.robust_delta; c->rb.d = g->store.robust_delta * g->store.robust_delta;
+    c->fixed = d.any_fixed; c->pose_fixed = d.any_fixed ? d.pose_fixed.as<unsigned char>() : nullptr;
     c->csr = Csr{d.rowptr.as<int>(), d.ent.as<int>()};
     for (int i = 0; i < 2; ++i) { c->poses[i] = d.poses[i].as<double>(); c->lin[i] = lin_view(d.lin[i].as<double>(), F); }
     double* v = d.vec.as<double>();
@@ -294,7 +303,7 @@ static int prepare(pcr_graph* g, bool tree, Ctx* c) {
 
 // linearise every factor at poses[which] into lin[which]; chi2 into status[0]
 static hipError_t linearize_at(const Ctx& c, int which) {
-    return launch_linearize(c.poses[which], c.fac, c.rb, c.lin[which], c.partial, c.status, c.stream);
+    return launch_linearize(c.poses[which], c.fac, c.rb, c.fixed, c.lin[which], c.partial, c.status, c.stream);
 }
 
 // one trial step's read: chi2 and the solve's words into g->dev.h_status
@@ -406,6 +415,22 @@ int pcr_graph_set_between_robust(pcr_graph* g, size_t first, size_t count, int o
 int pcr_graph_set_between_enabled(pcr_graph* g, size_t first, size_t count, int on) {
     G_ENTER(g);
     return refuse(g, set_between_flag(g->store, "pcr_graph_set_between_enabled", first, count, kMarkOff, on == 0));
+}
+
+int pcr_graph_set_fixed(pcr_graph* g, size_t first, size_t count, int on) {
+    G_ENTER(g);
+    return refuse(g, set_fixed(g->store, "pcr_graph_set_fixed", first, count, on != 0));
+}
+
+int pcr_graph_fixed(const pcr_graph* gc, size_t first, size_t count, uint8_t* fixed) {
+    pcr_graph* g = const_cast<pcr_graph*>(gc);
+    G_ENTER(g);
+    const size_t N = g->store.n_poses();
+    if (first > N || count > N - first) return gfail(g, "pcr_graph_fixed: first + count exceeds the number of poses (" + std::to_string(N) + ")");
+    if (count == 0) return 0;
+    if (!fixed) return gfail(g, "pcr_graph_fixed: NULL output");
+    for (size_t i = 0; i < count; ++i) fixed[i] = g->store.is_fixed(first + i) ? 1 : 0;
+    return 0;
 }
 
 int pcr_graph_size(const pcr_graph* g, size_t* np, size_t* n_priors, size_t* n_between) {
@@ -558,7 +583,7 @@ int pcr_graph_apply(pcr_graph* g, double lambda, const double* x, double* y) {
     if (prepare(g, false, &c)) return 1;
     G_TRY(linearize_at(c, g->dev.cur));
     G_TRY(hipMemcpyAsync(c.b.res, x, 6 * N * sizeof(double), hipMemcpyHostToDevice, c.stream));
-    G_TRY(launch_apply((int)N, c.fac, c.lin[g->dev.cur], c.csr, lambda, c.b.res, c.b.ap, c.b.u, c.stream));
+    G_TRY(launch_apply((int)N, c.fac, c.fixed, c.lin[g->dev.cur], c.csr, lambda, c.b.res, c.b.ap, c.b.u, c.stream));
     G_TRY(hipMemcpyAsync(y, c.b.ap, 6 * N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
     G_TRY(hipStreamSynchronize(c.stream));
     return 0;
@@ -595,7 +620,7 @@ int pcr_graph_precondition(pcr_graph* g, double lambda, int kind, const double* 
     Status* h = g->dev.h_status;
     G_TRY(linearize_at(c, g->dev.cur));
     G_TRY(hipMemcpyAsync(c.b.res, r, 6 * N * sizeof(double), hipMemcpyHostToDevice, c.stream));
-    G_TRY(launch_precondition((int)N, c.fac, c.lin[g->dev.cur], c.csr, tree ? &c.tree : nullptr, lambda, c.b, c.precond_flag, c.stream));
+    G_TRY(launch_precondition((int)N, c.fac, c.fixed, c.lin[g->dev.cur], c.csr, tree ? &c.tree : nullptr, lambda, c.b, c.precond_flag, c.stream));
     G_TRY(hipMemcpyAsync(z, c.b.z, 6 * N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
     G_TRY(hipMemcpyAsync(&h->precond_flag, c.precond_flag, sizeof(int), hipMemcpyDeviceToHost, c.stream));
     G_TRY(hipStreamSynchronize(c.stream));
@@ -619,6 +644,20 @@ int pcr_graph_optimize(pcr_graph* g, const pcr_graph_params* params, pcr_graph_r
     if (refuse(g, check_priors(st, "pcr_graph_optimize"))) return 1;
     if (g->host_only) return gfail(g, "pcr_graph_optimize: a PCR_GRAPH_HOST graph has no device (create the graph with a device ordinal, or -1)");
     if (lm_stands(g->settled, st.revision, prm)) { if (out) *out = lm_standing_result(g->settled, prm); return 0; }
+    if (!has_free_pose_with_factor(st)) {      // every pose is fixed: nothing to move, chi2 is a constant and is evaluated
+        Ctx c;
+        if (prepare(g, false, &c)) return 1;
+        pcr_graph_result res = empty_result();
+        if (c.F > 0) {
+            G_TRY(linearize_at(c, g->dev.cur));
+            G_TRY(read_status(g, c));
+            res.chi2_initial = res.chi2_final = g->dev.h_status->chi2;
+        }
+        res.converged = 1;
+        res.lambda = prm.lambda_init;
+        if (out) *out = res;
+        return 0;
+    }
     double last_old[16];
     if (current_pose(g, N - 1, last_old)) return 1;
     const bool tree = prm.pcg_preconditioner == PCR_GRAPH_PRECOND_TREE;
@@ -636,20 +675,22 @@ int pcr_graph_optimize(pcr_graph* g, const pcr_graph_params* params, pcr_graph_r
     lm_init(&lm, prm, h->chi2);
     while (lm_wants_trial(lm)) {
         const int cur = d.cur, trial = cur ^ 1;
-        if (tree) G_TRY(launch_solve_tree((int)N, c.fac, c.lin[cur], c.csr, c.tree, lm.lambda, cap, prm.pcg_rel_tol, c.b, c.status, c.stream));
-        else G_TRY(launch_solve((int)N, c.fac, c.lin[cur], c.csr, lm.lambda, cap, prm.pcg_rel_tol, c.b, c.status, c.stream));
-        G_TRY(launch_retract((int)N, c.poses[cur], c.b.x, c.poses[trial], c.stream));
+        if (tree) G_TRY(launch_solve_tree((int)N, c.fac, c.fixed, c.lin[cur], c.csr, c.tree, lm.lambda, cap, prm.pcg_rel_tol, c.b, c.status, c.stream));
+        else G_TRY(launch_solve((int)N, c.fac, c.fixed, c.lin[cur], c.csr, lm.lambda, cap, prm.pcg_rel_tol, c.b, c.status, c.stream));
+        G_TRY(launch_retract((int)N, c.poses[cur], c.b.x, c.pose_fixed, c.poses[trial], c.stream));
         G_TRY(linearize_at(c, trial));
         G_TRY(read_status(g, c));
         if (lm_step(&lm, h->chi2, h->pcg_iterations, h->pcg_flag) & kLmAccept) { d.cur = trial; d.ahead = true; }      // the trial's buffers become the current ones
     }
     pcr_graph_result res = lm_result(lm);
     g->settled = lm_settle(lm, st.revision);
-    double last_new[16], inv_old[16];
-    if (current_pose(g, N - 1, last_new)) return 1;
-    gm::pose_inv(last_old, inv_old);
-    gm::pose_mul(last_new, inv_old, res.delta);      // Backend.cpp:321: keyframes.back().pose * latest_pose.inverse()
-    pcr::t2se3(res.delta);                           // :331
+    if (!st.is_fixed(N - 1)) {      // (a fixed last pose did not move: delta stays the identity lm_result starts from)
+        double last_new[16], inv_old[16];
+        if (current_pose(g, N - 1, last_new)) return 1;
+        gm::pose_inv(last_old, inv_old);
+        gm::pose_mul(last_new, inv_old, res.delta);      // Backend.cpp:321: keyframes.back().pose * latest_pose.inverse()
+        pcr::t2se3(res.delta);                           // :331
+    }
     if (out) *out = res;
     return 0;
 }

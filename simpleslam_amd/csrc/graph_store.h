@@ -14,6 +14,7 @@
 #include <numeric>
 #include <sstream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pcr_hip.h"
@@ -29,6 +30,8 @@ struct Factor {
     unsigned char flags = 0;      // kMarkRobust, kMarkOff (between factors only): nothing a g2o file carries
 };
 constexpr unsigned char kMarkRobust = 1, kMarkOff = 2;      // the bits of graph_dev.h's Factors::flags (graph_host.hip asserts it)
+// ... and the two pack() adds for the device, from the poses' fixed flags: the factor's "from" end, its "to" end is a fixed pose
+constexpr unsigned char kPackFromFixed = 4, kPackToFixed = 8;
 
 // Poses and factors each: the device indexes entry k of factor e at [k * F + e] with k < 36 (and [p * 51 + k] per pose) in 32-bit ints, and the
 // host rounds buffer sizes up by 256 bytes.
@@ -37,16 +40,19 @@ constexpr size_t kMaxCount = 0x7fffff00u / 36;
 struct Store {
     std::vector<double> poses;               // 16 per pose, column-major
     std::vector<Factor> priors, betweens;
+    std::vector<unsigned char> fixed;        // per pose: 1 when the pose is a constant of the problem (set_fixed); as long as the poses are many
     int robust_kind = PCR_GRAPH_ROBUST_NONE; // the kernel of the marked between factors; it outlives clear()
     double robust_delta = 0.0;
     // THE staleness rule: every mutator ends in touch().  `revision` counts every change, `structure` is the revision of the last one that
-    // added or cleared poses or factors or set a mark or a switch.  Whoever keeps something derived (the device's factor tables and CSR, the
+    // added or cleared poses or factors or set a mark, a switch or a pose's fixed flag.  Whoever keeps something derived (the device's factor tables and CSR, the
     // forest, its schedule on the device, a converged optimisation) remembers the number it was made at and compares.
     uint64_t revision = 1, structure = 1;
     void touch(bool structural) { ++revision; if (structural) structure = revision; }
 
     size_t n_poses() const { return poses.size() / 16; }
     size_t n_factors() const { return priors.size() + betweens.size(); }
+    bool is_fixed(size_t p) const { return p < fixed.size() && fixed[p] != 0; }
+    size_t n_fixed() const { size_t n = 0; for (unsigned char f : fixed) n += f ? 1 : 0; return n; }
     const Factor& factor(size_t e) const { return e < priors.size() ? priors[e] : betweens[e - priors.size()]; }      // priors first
 };
 
@@ -79,6 +85,7 @@ inline std::string add_poses(Store& s, const char* what, const double* poses16, 
     if (!poses16) return std::string(what) + ": NULL poses";
     if (s.n_poses() + count > kMaxCount) return std::string(what) + ": more poses than the device's 32-bit indices address";
     s.poses.insert(s.poses.end(), poses16, poses16 + 16 * count);
+    s.fixed.resize(s.n_poses(), 0);      // a new pose is free
     s.touch(true);      // (the CSR has a row per pose)
     return "";
 }
@@ -104,6 +111,18 @@ inline std::string set_between_flag(Store& s, const char* what, size_t first, si
     return "";
 }
 
+// The fixed flag of poses first .. first + count - 1: a fixed pose is a constant of the problem ("Fixed poses").  The checks in
+// their order: the range, then nothing to do.
+inline std::string set_fixed(Store& s, const char* what, size_t first, size_t count, bool on) {
+    const size_t N = s.n_poses();
+    if (first > N || count > N - first) return std::string(what) + ": first + count exceeds the number of poses (" + std::to_string(N) + ")";
+    if (count == 0) return "";
+    s.fixed.resize(N, 0);
+    for (size_t p = first; p < first + count; ++p) s.fixed[p] = on ? 1 : 0;
+    s.touch(true);      // the factor tables carry the flags of their ends, the forest's roots follow them
+    return "";
+}
+
 inline std::string set_robust_kernel(Store& s, const char* what, int kind, double delta) {
     if (kind < PCR_GRAPH_ROBUST_NONE || kind > PCR_GRAPH_ROBUST_TUKEY)
         return std::string(what) + ": unknown kind " + std::to_string(kind) +
@@ -116,7 +135,7 @@ inline std::string set_robust_kernel(Store& s, const char* what, int kind, doubl
 }
 
 inline void clear(Store& s) {
-    s.poses.clear(); s.priors.clear(); s.betweens.clear();
+    s.poses.clear(); s.priors.clear(); s.betweens.clear(); s.fixed.clear();
     s.touch(true);
 }
 
@@ -151,7 +170,8 @@ inline std::string check(const Store& s, const char* what, size_t first_pose = 0
     return "";
 }
 
-// union-find over the between factors that are switched on: the first pose whose connected component holds no prior, or -1.  ONLY after check().
+// union-find over the between factors that are switched on: the first pose whose connected component holds no anchor -- neither a prior nor
+// a fixed pose -- or -1.  ONLY after check().
 inline long long first_pose_without_prior(const Store& s) {
     const size_t N = s.n_poses();
     std::vector<size_t> parent(N);
@@ -164,6 +184,7 @@ inline long long first_pose_without_prior(const Store& s) {
     }
     std::vector<char> has(N, 0);
     for (const Factor& f : s.priors) has[find((size_t)f.to)] = 1;
+    for (size_t p = 0; p < N; ++p) if (s.is_fixed(p)) has[find(p)] = 1;
     for (size_t p = 0; p < N; ++p) if (!has[find(p)]) return (long long)p;
     return -1;
 }
@@ -175,14 +196,27 @@ inline std::string check_priors(const Store& s, const char* what) {
     return std::string(what) + ": pose " + std::to_string(lone) + " lies in a connected component without a prior: the system would be singular";
 }
 
+// Is there anything to optimise: a factor that is switched on with a free pose at one of its ends.  (After check_priors() every free pose has
+// one, so this is false exactly when every pose is fixed -- or the graph holds none.)  ONLY after check().
+inline bool has_free_pose_with_factor(const Store& s) {
+    for (const Factor& f : s.priors) if (!s.is_fixed((size_t)f.to)) return true;
+    for (const Factor& f : s.betweens) {
+        if (f.flags & kMarkOff) continue;
+        if (!s.is_fixed((size_t)f.from) || !s.is_fixed((size_t)f.to)) return true;
+    }
+    return false;
+}
+
 // ---- what the device reads ---------------------------------------------------------------------------------------------------------------
 
 // Factors in the order priors, betweens, structure-of-arrays (entry k of factor e at [k * F + e]), and the CSR of every pose's incident factors:
 // ent[row_ptr[p] .. row_ptr[p + 1]), ascending by factor, entry = factor * 2 + (1: p is the "to" end).  flags holds F + 1 entries and ent at least
-// one, so that no upload is of nothing.  ONLY after check(): the CSR is indexed by the factors' ids, and a wrong row here is a fault on the device.
+// one, so that no upload is of nothing.  A factor's flags carry kPackFromFixed / kPackToFixed when that end is a fixed pose (a prior has no
+// "from" end); pose_fixed holds N + 1 entries, any_fixed says whether one of them is set.  ONLY after check(): the CSR is indexed by the factors' ids, and a wrong row here is a fault on the device.
 struct Packed {
     std::vector<int> from, to, row_ptr, ent;
-    std::vector<unsigned char> flags;
+    std::vector<unsigned char> flags, pose_fixed;
+    bool any_fixed = false;
     std::vector<double> z, omega;
 };
 inline Packed pack(const Store& s) {
@@ -192,10 +226,12 @@ inline Packed pack(const Store& s) {
     k.z.resize(16 * F); k.omega.resize(36 * F);
     k.flags.assign(F + 1, 0);
     k.row_ptr.assign(N + 1, 0);
+    k.pose_fixed.assign(N + 1, 0);
+    for (size_t p = 0; p < N; ++p) if (s.is_fixed(p)) { k.pose_fixed[p] = 1; k.any_fixed = true; }
     for (size_t e = 0; e < F; ++e) {
         const Factor& f = s.factor(e);
         k.from[e] = (int)f.from; k.to[e] = (int)f.to;
-        k.flags[e] = f.flags;
+        k.flags[e] = (unsigned char)(f.flags | (f.from >= 0 && k.pose_fixed[f.from] ? kPackFromFixed : 0) | (k.pose_fixed[f.to] ? kPackToFixed : 0));
         for (int i = 0; i < 16; ++i) k.z[i * F + e] = f.z[i];
         for (int i = 0; i < 36; ++i) k.omega[i * F + e] = f.info[i];
         if (f.from >= 0) k.row_ptr[f.from + 1]++;
@@ -255,6 +291,7 @@ inline std::string load_g2o(Store& s, const char* what, const char* path) {
     if (!in.is_open()) return std::string(what) + ": cannot open " + path;
     std::vector<double> poses;
     std::vector<Factor> priors, betweens;
+    std::vector<std::pair<long long, std::string>> fix;      // FIX records: the id and where it stood
     const size_t N0 = s.n_poses();
     std::string line;
     size_t lineno = 0;
@@ -303,18 +340,28 @@ inline std::string load_g2o(Store& s, const char* what, const char* path) {
                     f.info[(3 + i) * 6 + j] = m[3 + i][j];
                 }
             betweens.push_back(f);
+        } else if (tag == "FIX") {      // g2o's convention for a vertex that is held constant: one or more ids
+            long long id;
+            if (!(ss >> id)) return at + "malformed FIX";
+            do fix.emplace_back(id, at); while (ss >> id);
         }
     }
+    // (a FIX record may stand before its vertex: looked at once the whole file is read)
+    for (const auto& f : fix)
+        if (f.first < (long long)N0 || f.first >= (long long)(N0 + poses.size() / 16))
+            return f.second + "FIX " + std::to_string(f.first) + ": the file defines no vertex of that id";
     if (N0 + poses.size() / 16 > kMaxCount || s.n_factors() + priors.size() + betweens.size() > kMaxCount)
         return std::string(what) + ": more poses or factors than the device's 32-bit indices address";
     s.poses.insert(s.poses.end(), poses.begin(), poses.end());
     s.priors.insert(s.priors.end(), priors.begin(), priors.end());
     s.betweens.insert(s.betweens.end(), betweens.begin(), betweens.end());
+    s.fixed.resize(s.n_poses(), 0);
+    for (const auto& f : fix) s.fixed[(size_t)f.first] = 1;
     s.touch(true);
     return "";
 }
 
-// The poses and the between factors (g2o files carry neither priors nor marks nor switches), 17 digits each.
+// The poses, a FIX record per fixed pose and the between factors (g2o files carry neither priors nor marks nor switches), 17 digits each.
 inline std::string save_g2o(const Store& s, const char* what, const char* path) {
     if (!path) return std::string(what) + ": NULL path";
     FILE* fp = fopen(path, "w");
@@ -326,6 +373,7 @@ inline std::string save_g2o(const Store& s, const char* what, const char* path) 
         rot_to_quat(T, q);
         fprintf(fp, "VERTEX_SE3:QUAT %zu %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", p, T[12], T[13], T[14], q[0], q[1], q[2], q[3]);
     }
+    for (size_t p = 0; p < N; ++p) if (s.is_fixed(p)) fprintf(fp, "FIX %zu\n", p);
     for (const Factor& f : s.betweens) {
         double q[4], m[6][6];
         rot_to_quat(f.z, q);

@@ -638,6 +638,13 @@ public:
     void setRobustKernel(int kind, double delta = 0.0) { check(pcr_graph_set_robust_kernel(g_, kind, delta)); }
     void setBetweenRobust(size_t first, size_t count = 1, bool on = true) { check(pcr_graph_set_between_robust(g_, first, count, on ? 1 : 0)); }
     void setBetweenEnabled(size_t first, size_t count = 1, bool on = true) { check(pcr_graph_set_between_enabled(g_, first, count, on ? 1 : 0)); }
+    // A fixed pose is a constant of the problem: optimize() moves the free poses only and hands the fixed ones back bit for bit (g2o's setFixed)
+    void setFixed(size_t first, size_t count = 1, bool on = true) { check(pcr_graph_set_fixed(g_, first, count, on ? 1 : 0)); }
+    std::vector<uint8_t> fixed() const {
+        std::vector<uint8_t> out(poses());
+        check(pcr_graph_fixed(g_, 0, out.size(), out.data()));
+        return out;
+    }
     // the verdict at the current estimates, per between factor: s = r^T Omega r, the kernel's weight at s (1 when unmarked), the mark, the switch
     struct Weights { std::vector<double> s, w; std::vector<uint8_t> robust, enabled; };
     Weights betweenWeights(size_t first = 0, size_t count = (size_t)-1) {

@@ -1,7 +1,9 @@
 // graph_check -- backend::PoseGraph (PCR/HipRegister.hpp) over a graph read from a g2o file, on the GPU: chi2 before, chi2 after and the
 // iteration counts.  usage: graph_check graph.g2o [out.g2o] [--preconditioner block_jacobi|tree] [--robust none|huber|geman_mcclure|tukey
-// --delta D] [--loops-robust]   (block_jacobi and none when absent).  --loops-robust marks every between factor that pcr_graph_tree leaves
-// outside the forest (g2o files carry no marks); with a robust kernel the s and w of the ten lowest-weight factors are printed after the solve.
+// --delta D] [--loops-robust] [--fix-before N]   (block_jacobi and none when absent).  --loops-robust marks every between factor that
+// pcr_graph_tree leaves outside the forest (g2o files carry no marks); with a robust kernel the s and w of the ten lowest-weight factors are
+// printed after the solve.  --fix-before N fixes poses [0, N) before optimising (on top of the file's FIX records) and prints how many poses
+// were free; the fixed ones are checked to come back bit for bit.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +44,7 @@ int main(int argc, char** argv) {
     int precond = PCR_GRAPH_PRECOND_BLOCK_JACOBI, robust = PCR_GRAPH_ROBUST_NONE;
     double delta = 1.0;
     bool loops_robust = false;
+    long long fix_before = 0;
     const char* files[2] = {nullptr, nullptr};
     int n_files = 0;
     bool bad = false;
@@ -60,11 +63,12 @@ int main(int argc, char** argv) {
             else bad = true;
         } else if (!strcmp(argv[i], "--delta") && i + 1 < argc) delta = atof(argv[++i]);
         else if (!strcmp(argv[i], "--loops-robust")) loops_robust = true;
+        else if (!strcmp(argv[i], "--fix-before") && i + 1 < argc) { fix_before = atoll(argv[++i]); if (fix_before < 0) bad = true; }
         else if (n_files < 2 && argv[i][0] != '-') files[n_files++] = argv[i];
         else bad = true;
     }
     if (bad || n_files < 1) {
-        fprintf(stderr, "usage: %s graph.g2o [out.g2o] [--preconditioner block_jacobi|tree] [--robust none|huber|geman_mcclure|tukey --delta D] [--loops-robust]\n",
+        fprintf(stderr, "usage: %s graph.g2o [out.g2o] [--preconditioner block_jacobi|tree] [--robust none|huber|geman_mcclure|tukey --delta D] [--loops-robust] [--fix-before N]\n",
                 argv[0]);
         return 2;
     }
@@ -83,8 +87,21 @@ int main(int argc, char** argv) {
             printf("loops_marked %zu\n", loops.size());
         }
         if (robust != PCR_GRAPH_ROBUST_NONE) graph.setRobustKernel(robust, delta);
+        if (fix_before > 0) graph.setFixed(0, (size_t)fix_before);      // (a range beyond the poses is the library's to refuse)
+        const std::vector<uint8_t> fixed = graph.fixed();
+        const size_t n_fixed = (size_t)std::count(fixed.begin(), fixed.end(), (uint8_t)1);
+        if (n_fixed) printf("poses_fixed %zu poses_free %zu\n", n_fixed, fixed.size() - n_fixed);
+        const std::vector<PCR::pose_t> held = n_fixed ? graph.poses(0, fixed.size()) : std::vector<PCR::pose_t>();
         const double before = graph.chi2();
         const backend::PoseGraph::Result r = graph.optimize(precond);
+        if (n_fixed) {
+            const std::vector<PCR::pose_t> now = graph.poses(0, fixed.size());
+            for (size_t p = 0; p < fixed.size(); ++p)
+                if (fixed[p] && memcmp(held[p].data(), now[p].data(), 16 * sizeof(double)) != 0) {
+                    fprintf(stderr, "graph_check: fixed pose %zu moved\n", p);
+                    return 1;
+                }
+        }
         printf("poses %zu factors %zu\n", graph.poses(), graph.factors());
         printf("chi2_before %.17g\nchi2_after %.17g\n", before, r.chi2_final);
         printf("lm_iterations %d accepted %d pcg_iterations %lld pcg_capped %d converged %d lambda %g\n", r.iterations, r.accepted,

@@ -2,7 +2,7 @@
 // the CPU: no GPU call, no HIP header.  Plans every edge list it is given (or a built-in set), checks the plan's invariants and prints one
 // line per graph.  Built with -fsanitize=address,undefined it is the checked run of the forest function.
 //
-// usage: graph_forest_check [edges.txt ...]      a file holds graphs, each: "graph NAME N", then lines "prior ID" and "edge FROM TO"
+// usage: graph_forest_check [edges.txt ...]      a file holds graphs, each: "graph NAME N", then lines "prior ID", "fixed ID" and "edge FROM TO"
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -18,7 +18,8 @@ using pcr::graph::plan_forest;
 struct Case {
     std::string name;
     size_t N = 0;
-    std::vector<long long> from, to, prior;
+    std::vector<long long> from, to, prior, fixed;      // fixed: the poses that carry the fixed flag, anchors like the priors'
+    std::vector<int> roots;                             // when not empty: the roots worked by hand, ascending
 };
 
 static int fail(const Case& c, const char* what, long long at) {
@@ -27,7 +28,10 @@ static int fail(const Case& c, const char* what, long long at) {
 }
 
 static int check(const Case& c) {
-    const ForestPlan f = plan_forest(c.N, c.from.data(), c.to.data(), c.from.size(), c.prior.data(), c.prior.size());
+    // the anchors as pcr_graph hands them over: the priors' poses, then the fixed poses
+    std::vector<long long> anchors(c.prior);
+    anchors.insert(anchors.end(), c.fixed.begin(), c.fixed.end());
+    const ForestPlan f = plan_forest(c.N, c.from.data(), c.to.data(), c.from.size(), anchors.data(), anchors.size());
     const int N = (int)c.N;
     if (f.n_tree + f.n_other != c.from.size()) return fail(c, "tree + other edges != between factors", (long long)f.n_tree);
     if ((int)f.node.size() != N || (int)f.pos_of.size() != N) return fail(c, "positions do not cover the poses", (long long)f.node.size());
@@ -43,6 +47,22 @@ static int check(const Case& c) {
         if (me != p || other != par) return fail(c, "the tree factor does not join the pose to its parent", p);
     }
     if ((size_t)(N - roots) != f.n_tree) return fail(c, "poses - roots != tree edges", roots);
+    // the root rule: a component's root is its lowest-numbered anchor (a prior's pose or a fixed pose), its lowest-numbered pose when it has none
+    {
+        std::vector<uint8_t> anchor(N, 0);
+        for (long long a : anchors) anchor[a] = 1;
+        std::vector<int> root_of(N, -1), want(N, -1);      // by walking up; per root the pose the rule names
+        for (int p = 0; p < N; ++p) { int r = p; while (f.parent[r] >= 0) r = f.parent[r]; root_of[p] = r; }
+        for (int p = 0; p < N; ++p) if (anchor[p] && want[root_of[p]] < 0) want[root_of[p]] = p;
+        for (int p = 0; p < N; ++p) if (want[root_of[p]] < 0) want[root_of[p]] = p;
+        std::vector<int> got;
+        for (int p = 0; p < N; ++p) {
+            if (f.parent[p] >= 0) continue;
+            got.push_back(p);
+            if (want[p] != p) return fail(c, "a root is not the lowest-numbered anchor of its component", p);
+        }
+        if (!c.roots.empty() && got != c.roots) return fail(c, "the roots are not the ones worked by hand", got.empty() ? -1 : got[0]);
+    }
     // children CSR: ascending, complete; the heavy child
     std::vector<int> size(N, 1);
     for (int q = 0; q < N; ++q) { const int p = f.node[q]; if (f.parent[p] >= 0) size[f.parent[p]] += size[p]; }
@@ -86,8 +106,10 @@ static int check(const Case& c) {
     int log2n = 0;
     while ((1 << log2n) < N) ++log2n;
     if (f.rounds() > log2n + 1) return fail(c, "more rounds than log2(N) + 1", f.rounds());
-    printf("%s: poses %d priors %zu between %zu | tree %zu other %zu roots %d paths %d rounds %d\n", c.name.c_str(), N, c.prior.size(), c.from.size(),
+    printf("%s: poses %d priors %zu between %zu | tree %zu other %zu roots %d paths %d rounds %d", c.name.c_str(), N, c.prior.size(), c.from.size(),
            f.n_tree, f.n_other, roots, paths, f.rounds());
+    if (!c.fixed.empty()) printf(" | fixed %zu", c.fixed.size());
+    printf("\n");
     return 0;
 }
 
@@ -124,6 +146,24 @@ static std::vector<Case> built_in() {
       const int e[][2] = {{0, 1}, {1, 2}, {2, 0}, {5, 4}, {4, 7}, {3, 8}, {8, 2}};
       for (auto& x : e) { c.from.push_back(x[0]); c.to.push_back(x[1]); }
       out.push_back(c); }
+    // fixed poses as roots, worked by hand.  A chain 0 - 1 - ... - 11:
+    { Case c; c.name = "fixed root, no prior"; c.N = 12; c.fixed = {5}; c.roots = {5};
+      for (int i = 0; i + 1 < 12; ++i) { c.from.push_back(i); c.to.push_back(i + 1); }
+      out.push_back(c); }
+    { Case c; c.name = "fixed block below the prior"; c.N = 12; c.prior = {8}; c.fixed = {4, 5, 6, 7}; c.roots = {4};      // 4 < 8: the fixed pose wins
+      for (int i = 0; i + 1 < 12; ++i) { c.from.push_back(i); c.to.push_back(i + 1); }
+      c.from.push_back(11); c.to.push_back(0);
+      out.push_back(c); }
+    { Case c; c.name = "prior below the fixed block"; c.N = 12; c.prior = {0}; c.fixed = {7, 6, 5, 4}; c.roots = {0};       // in any order
+      for (int i = 0; i + 1 < 12; ++i) { c.from.push_back(i); c.to.push_back(i + 1); }
+      out.push_back(c); }
+    { Case c; c.name = "two components, a fixed pose holds the second"; c.N = 9; c.prior = {1}; c.fixed = {7, 6}; c.roots = {1, 4 /* no anchor */, 6, 7};
+      const int e[][2] = {{0, 1}, {1, 2}, {2, 0}, {5, 4}, {3, 8}, {8, 2}};      // {0 1 2 3 8}, {4 5}, {6}, {7}
+      for (auto& x : e) { c.from.push_back(x[0]); c.to.push_back(x[1]); }
+      out.push_back(c); }
+    { Case c; c.name = "the same pose holds a prior and is fixed"; c.N = 3; c.prior = {2}; c.fixed = {2}; c.roots = {2};
+      c.from = {0, 1}; c.to = {1, 2};
+      out.push_back(c); }
     { Case c; c.name = "binary tree"; c.N = 1023; c.prior = {0};
       for (int i = 1; i < 1023; ++i) { c.from.push_back((i - 1) / 2); c.to.push_back(i); }
       out.push_back(c); }
@@ -144,17 +184,18 @@ static int read_file(const char* path, std::vector<Case>& out) {
             if (!(ss >> c.name >> n) || n < 0) { fprintf(stderr, "graph_forest_check: %s: malformed graph line\n", path); return 1; }
             c.N = (size_t)n;
             out.push_back(c);
-        } else if (tag == "prior" || tag == "edge") {
+        } else if (tag == "prior" || tag == "fixed" || tag == "edge") {
             if (out.empty()) { fprintf(stderr, "graph_forest_check: %s: a record before the first graph line\n", path); return 1; }
             Case& c = out.back();
             long long a = -1, b = -1;
-            const bool ok = tag == "prior" ? !!(ss >> a) : !!(ss >> a >> b);
+            const bool ok = tag != "edge" ? !!(ss >> a) : !!(ss >> a >> b);
             // what pcr_graph's own check refuses before anything is planned
             if (!ok || a < 0 || (size_t)a >= c.N || (tag == "edge" && (b < 0 || (size_t)b >= c.N || a == b))) {
                 fprintf(stderr, "graph_forest_check: %s: %s: id out of range or from == to in \"%s\"\n", path, c.name.c_str(), line.c_str());
                 return 1;
             }
             if (tag == "prior") c.prior.push_back(a);
+            else if (tag == "fixed") c.fixed.push_back(a);
             else { c.from.push_back(a); c.to.push_back(b); }
         }
     }

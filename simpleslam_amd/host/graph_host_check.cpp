@@ -85,6 +85,27 @@ static void check_pack() {
         const Packed k = pack(s);
         expect(k.from.empty() && k.to.empty() && k.z.empty() && k.omega.empty() && k.flags.size() == 1, "pack 3: no factor");
         expect(k.row_ptr == std::vector<int>({0, 0, 0}) && k.ent.size() == 1, "pack 3: row_ptr all zero, ent not empty");
+        expect(k.pose_fixed == std::vector<unsigned char>({0, 0, 0}) && !k.any_fixed, "pack 3: pose_fixed, N + 1 of them, none set");
+    }
+    {   // pack 1's graph with poses 0 and 2 fixed: every factor carries the bits of its ends, beside the mark it has; nothing else moves
+        Store s;
+        add_eye_poses(s, 3);
+        add_tagged(s, 0, 1, 1); add_tagged(s, 2, 1, 2); add_tagged(s, 0, 2, 3);
+        add_tagged(s, -1, 1, 0);
+        expect(set_between_flag(s, "t", 2, 1, kMarkOff, true).empty(), "switch off");
+        const Packed free_k = pack(s);
+        expect(!free_k.any_fixed && free_k.flags == std::vector<unsigned char>({0, 0, 0, kMarkOff, 0}), "pack 4: no flag, no bit");
+        expect(set_fixed(s, "t", 0, 1, true).empty() && set_fixed(s, "t", 2, 1, true).empty(), "fix 0 and 2");
+        const Packed k = pack(s);
+        expect(k.any_fixed && k.pose_fixed == std::vector<unsigned char>({1, 0, 1, 0}), "pack 4: pose_fixed");
+        // factor 0: the prior on 1 (free); 1: 0 -> 1; 2: 2 -> 1; 3: 0 -> 2, off, both ends fixed
+        expect(k.flags == std::vector<unsigned char>({0, kPackFromFixed, kPackFromFixed, (unsigned char)(kMarkOff | kPackFromFixed | kPackToFixed), 0}), "pack 4: the ends' bits");
+        expect(k.from == free_k.from && k.to == free_k.to && k.row_ptr == free_k.row_ptr && k.ent == free_k.ent && k.z == free_k.z && k.omega == free_k.omega,
+               "pack 4: the flags change nothing else");
+        Store p;      // a prior on a fixed pose: the "to" bit, never the "from" bit
+        add_eye_poses(p, 1);
+        add_tagged(p, -1, 0, 0);
+        expect(set_fixed(p, "t", 0, 1, true).empty() && pack(p).flags[0] == kPackToFixed, "pack 4: a prior on a fixed pose");
     }
 }
 
@@ -130,6 +151,7 @@ static void check_checks() {
     expect_msg(set_between_flag(m, "t", 0, 1, kMarkOff, true), "t: first + count exceeds the number of between factors (0)");
     expect_msg(set_robust_kernel(m, "t", 4, 1.0), "t: unknown kind 4 (PCR_GRAPH_ROBUST_NONE = 0, PCR_GRAPH_ROBUST_HUBER = 1, PCR_GRAPH_ROBUST_GEMAN_MCCLURE = 2, PCR_GRAPH_ROBUST_TUKEY = 3)");
     expect_msg(set_robust_kernel(m, "t", PCR_GRAPH_ROBUST_HUBER, 0.0), "t: delta must be finite and greater than 0");
+    expect_msg(set_fixed(m, "t", 0, 1, true), "t: first + count exceeds the number of poses (0)");
     expect(m.revision == r0 && m.structure == r0, "a refused change is none");
     expect(add_poses(m, "t", kEye, 0).empty() && set_between_flag(m, "t", 0, 0, kMarkOff, true).empty() && m.revision == r0, "nothing added, nothing changed");
     add_eye_poses(m, 2);
@@ -138,8 +160,28 @@ static void check_checks() {
     expect(r1 == r0 + 3 && m.structure == r1, "every add is a structural change");
     expect(set_robust_kernel(m, "t", PCR_GRAPH_ROBUST_TUKEY, 2.0).empty() && m.revision == r1 + 1 && m.structure == r1, "the kernel is a change, not a structural one");
     expect(set_between_flag(m, "t", 0, 1, kMarkRobust, true).empty() && m.structure == m.revision && m.betweens[0].flags == kMarkRobust, "a mark is structural");
+    {   // the fixed flag: the range first (the store untouched), then nothing to do, then a structural change either way
+        const uint64_t rf = m.revision;
+        expect(m.fixed == std::vector<unsigned char>({0, 0}) && m.n_fixed() == 0, "a new pose is free");
+        expect_msg(set_fixed(m, "t", 1, 2, true), "t: first + count exceeds the number of poses (2)");
+        expect_msg(set_fixed(m, "t", 3, 0, true), "t: first + count exceeds the number of poses (2)");
+        expect_msg(set_fixed(m, "t", 2, (size_t)-1, true), "t: first + count exceeds the number of poses (2)");
+        expect(m.revision == rf && m.n_fixed() == 0, "a refused range fixes nothing");
+        expect(set_fixed(m, "t", 2, 0, true).empty() && m.revision == rf, "an empty range at the end: nothing changed");
+        expect(set_fixed(m, "t", 1, 1, true).empty() && m.revision == rf + 1 && m.structure == m.revision && m.is_fixed(1) && !m.is_fixed(0) && m.n_fixed() == 1,
+               "a flag is structural");
+        expect(set_fixed(m, "t", 0, 2, false).empty() && m.revision == rf + 2 && m.structure == m.revision && m.n_fixed() == 0, "clearing one is too");
+        expect(set_fixed(m, "t", 0, 2, true).empty() && !has_free_pose_with_factor(m), "every pose fixed: nothing to optimise");
+        expect(set_fixed(m, "t", 1, 1, false).empty() && has_free_pose_with_factor(m), "one free end of a factor: something to optimise");
+        expect(set_between_flag(m, "t", 0, 1, kMarkOff, true).empty() && !has_free_pose_with_factor(m), "... unless the factor is off");
+        expect(set_between_flag(m, "t", 0, 1, kMarkOff, false).empty() && set_fixed(m, "t", 0, 1, true).empty(), "as before");
+        add_eye_poses(m, 1);
+        expect(m.fixed == std::vector<unsigned char>({1, 0, 0}), "the flags stay with their poses when one is added");
+    }
     clear(m);
     expect(m.n_poses() == 0 && m.n_factors() == 0 && m.structure == m.revision && m.robust_kind == PCR_GRAPH_ROBUST_TUKEY, "clear keeps the kernel");
+    add_eye_poses(m, 1);
+    expect(m.fixed == std::vector<unsigned char>({0}), "clear drops the fixed flags");
     double i21[21];
     expect(noise_preset(PCR_GRAPH_ODOM, i21) && i21[0] == 1.0 / 1e-4 && i21[1] == 0.0 && i21[20] == 1.0 / 1e-1 && !noise_preset(3, i21), "noise presets");
 }
@@ -163,13 +205,32 @@ static void check_union_find() {
     Store one;
     add_eye_poses(one, 1);
     expect(first_pose_without_prior(one) == 0, "union-find: a lone pose");
+    expect(set_fixed(one, "t", 0, 1, true).empty() && first_pose_without_prior(one) == -1, "union-find: a lone fixed pose anchors itself");
+
+    // the anchor rule: a component is anchored by a prior or by a fixed pose
+    Store a;
+    add_eye_poses(a, 9);
+    for (auto& x : e) add_tagged(a, x[0], x[1], 1);      // the same components, no prior anywhere
+    expect(first_pose_without_prior(a) == 0, "anchor: no prior, no fixed pose");
+    expect(set_fixed(a, "t", 8, 1, true).empty() && first_pose_without_prior(a) == 4, "anchor: pose 8 fixed holds {0 1 2 3 8}");
+    expect_msg(check_priors(a, "entry"), "entry: pose 4 lies in a connected component without a prior: the system would be singular");
+    expect(set_fixed(a, "t", 4, 4, true).empty() && first_pose_without_prior(a) == -1, "anchor: 4 .. 7 fixed hold {4 5 7} and {6}");
+    expect(set_between_flag(a, "t", 5, 1, kMarkOff, true).empty(), "switch (3, 8) off");
+    expect(first_pose_without_prior(a) == 3, "anchor: pose 3 once its only edge to the fixed pose is off");
+    expect(set_between_flag(a, "t", 5, 1, kMarkOff, false).empty(), "switch (3, 8) on");
+    expect(set_between_flag(a, "t", 6, 1, kMarkOff, true).empty(), "switch (8, 2) off");
+    expect(first_pose_without_prior(a) == 0, "anchor: the edge that joins {0 1 2} to its fixed pose is off: its first pose is named");
+    expect_msg(check_priors(a, "entry"), "entry: pose 0 lies in a connected component without a prior: the system would be singular");
+    add_tagged(a, -1, 1, 0);
+    expect(first_pose_without_prior(a) == -1, "anchor: a prior holds what the fixed pose no longer does");
+    expect(set_fixed(a, "t", 0, 9, false).empty() && first_pose_without_prior(a) == 3, "anchor: the flags cleared, the prior-only rule is back");
 }
 
 static bool same(const Factor& a, const Factor& b) {
     return a.from == b.from && a.to == b.to && a.flags == b.flags && memcmp(a.z, b.z, sizeof a.z) == 0 && memcmp(a.info, b.info, sizeof a.info) == 0;
 }
 static bool same(const Store& a, const Store& b) {
-    bool ok = a.poses.size() == b.poses.size() && a.priors.size() == b.priors.size() && a.betweens.size() == b.betweens.size() &&
+    bool ok = a.poses.size() == b.poses.size() && a.priors.size() == b.priors.size() && a.betweens.size() == b.betweens.size() && a.fixed == b.fixed &&
               (a.poses.empty() || memcmp(a.poses.data(), b.poses.data(), a.poses.size() * sizeof(double)) == 0);
     for (size_t i = 0; ok && i < a.priors.size(); ++i) ok = same(a.priors[i], b.priors[i]);
     for (size_t i = 0; ok && i < a.betweens.size(); ++i) ok = same(a.betweens[i], b.betweens[i]);
@@ -240,6 +301,11 @@ static void check_g2o() {
         {vertex4 + "# a comment\nVERTEX_SE3:QUAT 5 1 2", ":3: malformed VERTEX_SE3:QUAT"},
         {vertex4 + "EDGE_SE3:QUAT 3", ":2: malformed EDGE_SE3:QUAT"},
         {"EDGE_SE3:QUAT -1 2 0 0 0 0 0 0 1 1 0 0 0 0 0 1 0 0 0 0 1 0 0 0 1 0 0 1 0 1\n", ":1: negative id"},
+        {vertex4 + "FIX 5\n", ":2: FIX 5: the file defines no vertex of that id"},
+        {vertex4 + "FIX 3\n", ":2: FIX 3: the file defines no vertex of that id"},      // the store's own pose: not the file's
+        {"FIX 4 9\n" + vertex4, ":1: FIX 9: the file defines no vertex of that id"},     // the first id is fine (defined further down), the second is not
+        {vertex4 + "FIX -1\n", ":2: FIX -1: the file defines no vertex of that id"},
+        {vertex4 + "FIX\n", ":2: malformed FIX"},
     };
     for (const auto& r : refused) {
         write_text(bad, r.text);
@@ -256,6 +322,34 @@ static void check_g2o() {
     expect_msg(load_g2o(s, "load", bad.c_str()), "");
     expect(s.n_poses() == 5 && s.priors.size() == 1 && s.betweens.size() == 4 && s.betweens[3].from == 4 && s.betweens[3].to == 0 && s.poses[16 * 4 + 13] == 2.0,
            "g2o: a good file is appended, no second prior (vertex 0 is not in it)");
+    expect(s.fixed == std::vector<unsigned char>({0, 0, 0, 0, 1}), "g2o: FIX 4 fixes the file's vertex 4 and no other pose");
+
+    // FIX records: written after the vertices, read back, and the second save is the first one's bytes; without a flag no record is written
+    {
+        const std::string one = dir + "/one.g2o", two = dir + "/two.g2o", plain = dir + "/plain.g2o";
+        auto slurp = [](const std::string& path) { std::ifstream in(path); std::stringstream ss; ss << in.rdbuf(); return ss.str(); };
+        expect_msg(save_g2o(a, "save", plain.c_str()), "");
+        const std::string plain_text = slurp(plain);
+        expect(plain_text.find("FIX") == std::string::npos && plain_text == slurp(good), "g2o: no flag, no FIX record");
+        Store f = a;
+        expect(set_fixed(f, "t", 0, 1, true).empty() && set_fixed(f, "t", 2, 1, true).empty(), "fix 0 and 2");
+        expect_msg(save_g2o(f, "save", one.c_str()), "");
+        const std::string text = slurp(one);
+        const size_t last_vertex = text.rfind("VERTEX_SE3:QUAT"), fix0 = text.find("FIX 0\nFIX 2\n"), first_edge = text.find("EDGE_SE3:QUAT");
+        expect(fix0 != std::string::npos && last_vertex < fix0 && fix0 < first_edge, "g2o: one FIX record per fixed pose, after the vertices");
+        Store back;
+        expect_msg(load_g2o(back, "load", one.c_str()), "");
+        expect(back.fixed == std::vector<unsigned char>({1, 0, 1}), "g2o: the flags come back");
+        // (poses pass through a quaternion: the text of a second save is compared after a second load, whose quaternions are the first save's)
+        expect_msg(save_g2o(back, "save", two.c_str()), "");
+        Store again;
+        expect_msg(load_g2o(again, "load", two.c_str()), "");
+        expect(again.fixed == back.fixed, "g2o: ... and again");
+        expect(set_fixed(f, "t", 0, 3, false).empty(), "free them");
+        expect_msg(save_g2o(f, "save", one.c_str()), "");
+        expect(slurp(one) == plain_text, "g2o: flags set and cleared: the bytes of a store that never had one");
+        unlink(one.c_str()); unlink(two.c_str()); unlink(plain.c_str());
+    }
     unlink(good.c_str()); unlink(bad.c_str()); rmdir(dir.c_str());
 }
 

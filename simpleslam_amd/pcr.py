@@ -91,6 +91,7 @@ ABI_SYMBOLS = [
     "pcr_graph_device_poses", "pcr_graph_linearize", "pcr_graph_apply", "pcr_map_set_poses_from_graph", "pcr_graph_load_g2o", "pcr_graph_save_g2o",
     "pcr_graph_tree", "pcr_graph_precondition", "pcr_graph_set_robust_kernel", "pcr_graph_get_robust_kernel", "pcr_graph_set_between_robust",
     "pcr_graph_set_between_enabled", "pcr_graph_add_loop", "pcr_graph_between_weights", "pcr_graph_robust_rho_w",
+    "pcr_graph_set_fixed", "pcr_graph_fixed",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -344,6 +345,8 @@ def load_library():
     L.pcr_graph_add_loop.argtypes = [vp, C.c_size_t, C.c_size_t, dp, dp]
     L.pcr_graph_between_weights.argtypes = [vp, C.c_size_t, C.c_size_t, dp, dp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
     L.pcr_graph_robust_rho_w.argtypes = [C.c_int, C.c_double, C.c_double, dp, dp]
+    L.pcr_graph_set_fixed.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int]
+    L.pcr_graph_fixed.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8)]
     L.pcr_graph_load_g2o.argtypes = [vp, C.c_char_p]
     L.pcr_graph_save_g2o.argtypes = [vp, C.c_char_p]
     _lib = L
@@ -1590,6 +1593,20 @@ class PoseGraph:
     def setBetweenEnabled(self, first, count=1, on=True):
         """pcr_graph_set_between_enabled: a factor that is off adds nothing and links nothing; it stays in size(), linearize()'s r and J, saveG2o()."""
         self._check(self._lib.pcr_graph_set_between_enabled(self._g, int(first), int(count), 1 if on else 0))
+
+    def setFixed(self, first, count=1, on=True):
+        """pcr_graph_set_fixed: poses first .. first+count-1 become constants of the problem (on=False frees them): optimize() moves the free
+        poses only and hands the fixed ones back bit for bit.  A fixed pose anchors its component as a prior does."""
+        if int(first) < 0 or int(count) < 0:
+            raise PcrError("pcr_graph_set_fixed: first and count must not be negative")
+        self._check(self._lib.pcr_graph_set_fixed(self._g, int(first), int(count), 1 if on else 0))
+
+    def fixed(self):
+        """pcr_graph_fixed -> (poses,) bool array: which poses are fixed."""
+        n = self.size()[0]
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        self._check(self._lib.pcr_graph_fixed(self._g, 0, n, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out[:n].astype(bool)
 
     def betweenWeights(self, first=0, count=None):
         """pcr_graph_between_weights -> (s, w, robust, enabled) per between factor at the current estimates: s = r^T Omega r, the kernel's
