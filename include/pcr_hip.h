@@ -362,6 +362,43 @@ int pcr_voxel_filter(pcr_handle* h, const void* pts, size_t n, size_t stride_byt
 int pcr_voxel_filter_begin(pcr_handle* h, const void* d_pts, size_t n, size_t stride_bytes, double leaf, void* d_out, size_t out_capacity);
 int pcr_voxel_filter_end(pcr_handle* h, size_t* n_out);
 
+/* ---- the reference's own sparse voxel filters: pcp::VoxelDownSampleV3 and pcp::VoxelDownSampleV2 (common/pcp/pcp.hpp:157-263, :78-154) ----
+ * pcl::VoxelGrid -- and pcr_voxel_filter with it -- gives up once the voxel box exceeds INT_MAX cells.  These two hold the occupied voxels
+ * only: device memory grows with n, never with the box.  Same argument conventions as pcr_voxel_filter: any handle, records of stride_bytes
+ * with x, y, z as floats first, the output record's fields by the rule of the 16- and 32-byte layouts, *n_out = the voxel count also when
+ * out_capacity was too small (the call then fails and the caller can retry), leaf cast to float (the reference's `float gs`).
+ *   Both kinds.  A row with a non-finite coordinate is dropped and renumbers nothing (the reference casts such a value to an integer, which
+ *   is undefined).  An empty input, or one without a finite row, gives *n_out = 0 and rc 0.  A voxel is its integer triple; the kept rows'
+ *   triples, each axis relative to its smallest value over the kept rows, are packed into one 64-bit key -- z most significant, then y, then
+ *   x, an axis of extent e taking bits(e - 1) bits -- and the (key, row) pairs are sorted by a stable radix sort.  OUTPUT ORDER: ascending
+ *   key, i.e. ascending (z, y, x) -- pcr_voxel_filter's order, so the two compare row for row where both filter.  (The reference's own order
+ *   is std::unordered_map's and specifies nothing.)  The same call twice gives the same bytes.
+ *   Refused, with a message: a cloud whose three extents need more than 64 key bits (the message gives the extents; the reference's size_t
+ *   index wraps), a cloud in which floor(p * inv) (V3) or p / gs (V2) leaves the int range on a kept row (undefined in the reference),
+ *   a non-positive leaf, max_voxel_pts < 1, min_voxel_pts < 0, an unknown kind -- each named.
+ *   V3 (pcp.hpp:172-254): inv = 1.0f / gs, min_b = (int)floor(min_p * inv), ijk = floor(p * inv) - (float)min_b, all in float without
+ *   contraction: pcl::VoxelGrid's lattice without its too-fine test.  Output: the centroid of all fields (pcl::CentroidPoint), data[3] = 1 in
+ *   the 32-byte layout; sums in double in sorted order, rounded to float once.
+ *   V2 (pcp.hpp:102-152, KISS-ICP's voxel hash): voxel = (int)(p / gs), a float division truncated toward zero -- the voxels touching zero
+ *   are two leaves wide on that axis.  Per voxel the max_voxel_pts rows of lowest index are kept; the voxel is emitted when that count is
+ *   strictly greater than min_voxel_pts; the record is the lowest-index row's bytes with x, y, z replaced by the float mean: a sequential
+ *   float sum in ascending row index divided by (float)count. */
+#define PCR_VOXEL_SPARSE_V3 3     /* pcp::VoxelDownSampleV3, pcp.hpp:157-263 */
+#define PCR_VOXEL_SPARSE_V2 2     /* pcp::VoxelDownSampleV2, pcp.hpp:78-154  */
+typedef struct {
+    int32_t kind;              /* default V3 */
+    int32_t max_voxel_pts;     /* V2 only, default 20 */
+    int32_t min_voxel_pts;     /* V2 only, default 0  */
+} pcr_voxel_sparse_params;
+void pcr_voxel_sparse_default_params(pcr_voxel_sparse_params* p);
+/* p = NULL: the defaults */
+int  pcr_voxel_filter_sparse(pcr_handle* h, const void* pts, size_t n, size_t stride_bytes, int on_device, double leaf,
+                             const pcr_voxel_sparse_params* p, void* out, size_t out_capacity, int out_on_device, size_t* n_out);
+/* what the last sparse call on this handle sorted: per kept input row, in sorted order, its packed voxel key and its original row index.
+ * *count = the kept rows (also when capacity was too small: the call then fails and writes nothing else); keys / rows may be NULL.  Fails
+ * when the handle's last sparse call was refused or none was made. */
+int  pcr_voxel_sparse_order(pcr_handle* h, uint64_t* keys, uint32_t* rows, size_t capacity, size_t* count);
+
 /* ---- the producer of `dst`: MapManager's key-frame store and sub-map assembly, on the device ----
  * MapManager::updateMap (frontend/src/MapManager.cpp:151-201): key frames whose position lies within `radius`
  * (mSurroundingKeyframeSearchRadius = 8 m, MapManager.hpp:68; squared L2 in double, strict '<' like
@@ -419,6 +456,10 @@ int pcr_map_downsample_keyframes(pcr_map* m, size_t first, double grid_size, siz
  * pcr_map_update -- a new generation, transform, concatenate, voxel-filter; more than 0xfffffff0 points are an error, and a map whose extent
  * is beyond pcl::VoxelGrid's index range at grid_size comes back unfiltered, as PCL returns it.  Parent or view. */
 int pcr_map_update_all(pcr_map* m, double grid_size, size_t* n_submap);
+/* pcr_map_update_all with pcp::VoxelDownSampleV3 in place of pcl::VoxelGrid: every key frame selected, a new generation, the same transform
+ * pass and 0xfffffff0 cap, a queued assembly collected first; the sub-map is byte for byte pcr_voxel_filter_sparse (V3) of the concatenation,
+ * so a map of any extent comes back filtered (more than 64 key bits are an error).  Parent or view. */
+int pcr_map_update_all_sparse(pcr_map* m, double grid_size, size_t* n_submap);
 /* A second (third, ...) sub-map over the SAME key frames: LoopClosureManager's lc_map_ (LoopClosureManager.cpp:85-99) beside MapManager's
  * mSubmap.  The view has its own stream and filter, concatenation, sub-map, selection, queued-assembly state, id and generation, on the
  * parent's device; it reads the parent's key frames, poses and point layout.  NULL on failure (pcr_map_last_error(parent)).

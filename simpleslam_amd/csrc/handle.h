@@ -1,7 +1,7 @@
 // handle.h -- struct pcr_handle and what the host units of the C ABI share (host code only; no kernel includes this).
 // The units: capi.hip (handle, the method table, the common part of scan2map / set_target / align, getters and setters), staging_host.hip,
 // comm_host.hip, one unit per method -- loam_host.hip, ndt_host.hip, vgicp_host.hip, gicp_host.hip (the two share lsq_host.h), liorf_host.hip:
-// each owns the functions of its row of the table (MethodOps) --, fitness_host.hip, voxel_host.hip, query_host.hip.
+// each owns the functions of its row of the table (MethodOps) --, fitness_host.hip, voxel_host.hip, voxel_sparse_host.hip, query_host.hip.
 // A nested struct of the handle belongs to the unit it is named after: that unit sets it up and writes it (pcr_destroy reaches
 // into all of them); where another unit looks into one, the member's comment says so.  What several units share stays at the
 // top level, with its users named.
@@ -192,6 +192,14 @@ struct pcr_handle {
         bool inflight = false; size_t inflight_n = 0;      // pcr_voxel_filter_begin has queued a filter that pcr_voxel_filter_end has not collected
         char* ret = nullptr;             // page-locked: what the voxel filter's last block reports (VfResult: the voxel count + the index header's verdict)
     } vf;
+
+    // the sparse voxel filters (voxel_sparse_host.hip): buffers kept between calls, all sized by the number of points
+    struct Vs {
+        pcr::DeviceBuf in, out, hdr, key[2], row[2], hist, cnt, first, lead, tile;
+        pcr::host::Mapped<pcr::VsResult> ret;      // what the last launch reports (the call's one synchronisation reads it)
+        bool have_order = false;         // the last call sorted something that pcr_voxel_sparse_order can hand out
+        size_t order_n = 0; int order_buf = 0;
+    } vs;
 
     // scores of many poses and exact queries on the kept target (query_host.hip)
     struct Query {

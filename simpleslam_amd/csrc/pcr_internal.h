@@ -434,6 +434,28 @@ hipError_t voxel_filter_launch(const GridIndex& grid, const float* d_orig, size_
                                void* d_wave, float* d_out, size_t out_capacity, void* result_mapped, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Sparse voxel filters (voxel_sparse.hip): pcp::VoxelDownSampleV3 / V2 by a stable radix sort of packed voxel keys
+// ---------------------------------------------------------------------------
+static constexpr int kVsV3 = 3, kVsV2 = 2;                       // PCR_VOXEL_SPARSE_V3 / _V2
+static constexpr int kVsRefusedRange = 1, kVsRefusedBits = 2;    // VsResult::refused
+// what the filter's last launch reports into page-locked memory: the voxels emitted, the rows kept (finite), the digit passes the sort took
+// (the sorted pairs lie in pair buffer `passes & 1`), the verdict and the three extents the key was laid out for
+struct VsResult { uint32_t count, kept; int32_t passes, refused, bits; int32_t pad_; unsigned long long ext[3]; };
+struct VsBuffers {           // device memory of one call, all of it sized by n (voxel_sparse_bytes)
+    void* hdr;               // the call's header: box, key layout, counts
+    unsigned long long* key[2]; uint32_t* row[2];      // the (key, row) pairs, sorted from one into the other digit by digit
+    uint32_t* hist;          // per digit pass: [bin][tile] counts, scanned in place
+    uint32_t* cnt;           // per sorted row: the rows of the voxel it starts if that voxel is emitted, else 0
+    uint32_t* first;         // per wave of 64 sorted rows: its first voxel start (64: none)
+    void* lead;              // per wave: the double sums in front of that start (V3)
+    uint32_t* tile;          // per block of 256 sorted rows: voxels emitted, scanned in place
+};
+struct VsSizes { size_t hdr, key, row, hist, cnt, first, lead, tile; };
+VsSizes voxel_sparse_bytes(size_t n);
+hipError_t voxel_sparse_launch(const VsBuffers& b, const float* d_pts, size_t stride_floats, size_t n, float leaf, int kind, int max_voxel_pts,
+                               int min_voxel_pts, float* d_out, size_t out_capacity, VsResult* result_mapped, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // NDT (ndt.hip)
 // ---------------------------------------------------------------------------
 struct NdtVoxel {            // VoxelGridCovariance::Leaf (pclomp/voxel_grid_covariance_omp.h:98-193): mean_, icov_

@@ -29,6 +29,8 @@ hipStream_t pcr_internal_stream(const pcr_handle* h);
 int pcr_internal_vf_begin(pcr_handle* h, const void* d_pts, size_t n, size_t stride_bytes, double leaf, void* d_out, size_t out_capacity);
 int pcr_internal_vf_end(pcr_handle* h, size_t* n_out);
 void pcr_internal_vf_reserve(pcr_handle* h, size_t points);
+// (defined in voxel_sparse_host.hip) pcp::VoxelDownSampleV3 of device memory into device memory, synchronous
+int pcr_internal_vs_v3(pcr_handle* h, const void* d_pts, size_t n, size_t stride_bytes, double leaf, void* d_out, size_t out_capacity, size_t* n_out);
 // (pcr_internal.h, defined in graph_host.hip) the device a pose graph lives on, PCR_GRAPH_HOST for a graph without one
 namespace pcr { int graph_device(const pcr_graph* g); }
 
@@ -371,9 +373,10 @@ int pcr_map_downsample_keyframes(pcr_map* m, size_t first, double grid_size, siz
     return 0;
 }
 
-// transform + concatenate the selected key frames (m->selected, ascending) and voxel-filter the result into m->submap
-static int assemble_selected(pcr_map* m, double grid_size, size_t* n_submap, bool wait = true) {
+// transform + concatenate the selected key frames (m->selected, ascending) into m->concat, queued on the filter's stream; room for the result in m->submap
+static int concat_selected(pcr_map* m, size_t* n_total) {
     const pcr_map* s = store_of(m);
+    *n_total = 0;
     std::vector<KfDesc> desc;
     size_t total = 0;
     for (long long i : m->selected) {
@@ -415,6 +418,16 @@ static int assemble_selected(pcr_map* m, double grid_size, size_t* n_submap, boo
                        static_cast<const KfDesc*>(m->desc.p), (int)desc.size(), (unsigned int)total, (unsigned int)sf, static_cast<float*>(m->concat.p));
     }
     M_TRY(hipGetLastError());
+    *n_total = total;
+    return 0;
+}
+
+// transform + concatenate the selected key frames (m->selected, ascending) and voxel-filter the result into m->submap
+static int assemble_selected(pcr_map* m, double grid_size, size_t* n_submap, bool wait = true) {
+    size_t total = 0;
+    if (concat_selected(m, &total)) return 1;
+    if (total == 0) return 0;
+    const size_t stride = store_of(m)->stride;
     if (pcr_internal_vf_begin(m->filter, m->concat.p, total, stride, grid_size, m->submap.p, total))
         return mfail(m, std::string("voxel filter: ") + pcr_last_error(m->filter));
     m->pending = true;
@@ -500,6 +513,30 @@ int pcr_map_update_all(pcr_map* m, double grid_size, size_t* n_submap) {
     const size_t count = store_of(m)->kfs.size();
     for (size_t i = 0; i < count; ++i) m->selected.push_back((long long)i);      // test/vis_globalmap.cpp:40-47
     return assemble_selected(m, grid_size, n_submap);
+}
+
+int pcr_map_update_all_sparse(pcr_map* m, double grid_size, size_t* n_submap) {
+    if (!m) return 1;
+    m->err.clear();
+    M_ALIVE(m);
+    if (!(grid_size > 0)) return mfail(m, "grid_size must be positive");
+    M_TRY(hipSetDevice(m->device));
+    (void)finish_pending(m); m->err.clear();
+    m->selected.clear();
+    m->n_submap = 0;
+    m->generation += 1;           // whatever happens below, the previous sub-map is gone
+    if (n_submap) *n_submap = 0;
+    const size_t count = store_of(m)->kfs.size();
+    for (size_t i = 0; i < count; ++i) m->selected.push_back((long long)i);
+    size_t total = 0, n_out = 0;
+    if (concat_selected(m, &total)) return 1;
+    if (total == 0) return 0;
+    // pcp::VoxelDownSampleV3 where pcr_map_update_all runs pcl::VoxelGrid: behind the transform pass on the same stream, collected at once
+    if (pcr_internal_vs_v3(m->filter, m->concat.p, total, store_of(m)->stride, grid_size, m->submap.p, total, &n_out))
+        return mfail(m, std::string("sparse voxel filter: ") + pcr_last_error(m->filter));
+    m->n_submap = n_out;
+    if (n_submap) *n_submap = n_out;
+    return 0;
 }
 
 const void* pcr_map_submap(const pcr_map* m, size_t* n, size_t* stride_bytes) {

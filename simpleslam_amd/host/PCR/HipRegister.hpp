@@ -214,6 +214,12 @@ public:
         if (pcr_map_update_all(m_, grid_size, &n)) throw std::runtime_error(pcr_map_last_error(m_));
         return n;
     }
+    // ... with pcp::VoxelDownSampleV3 in place of pcl::VoxelGrid (pcr_map_update_all_sparse): filtered whatever the map's extent
+    size_t updateAllSparse(double grid_size = 0.4) {
+        size_t n = 0;
+        if (pcr_map_update_all_sparse(m_, grid_size, &n)) throw std::runtime_error(pcr_map_last_error(m_));
+        return n;
+    }
     // Backend::optimHandler (Backend.cpp:315-318): the optimised poses of key frames first .. first + poses.size() - 1
     void setPoses(size_t first, const std::vector<pose_t>& poses) {
         static_assert(sizeof(pose_t) == 16 * sizeof(double), "poses are handed over as one array");
@@ -753,4 +759,54 @@ inline void voxelDownSample(PCR::PC_Ptr& cloud, float grid_size) {      // in pl
     voxelDownSample(PCR::PC_cPtr(cloud), out, grid_size);
     cloud->points.swap(out.points);
 }
+
+// common/pcp/pcp.hpp:78-263: the reference's own sparse voxel filters, on the device (pcr_voxel_filter_sparse).  Objects of both classes are
+// long-lived members in the reference (LidarOdometry.hpp:58-59): each keeps one handle, and with it the device buffers, between calls.
+// Output in ascending (z, y, x) voxel order; rows with a non-finite coordinate are dropped; a refused cloud throws with the library's message.
+class VoxelSparseBase {
+protected:
+    pcr_handle* h_ = nullptr;
+    pcr_voxel_sparse_params prm_;
+    float _grid_size = 0.f;
+    VoxelSparseBase() { pcr_voxel_sparse_default_params(&prm_); }
+    ~VoxelSparseBase() { if (h_) pcr_destroy(h_); }
+    VoxelSparseBase(const VoxelSparseBase& o) : prm_(o.prm_), _grid_size(o._grid_size) {}      // (a copy gets a handle of its own when it first filters)
+    VoxelSparseBase& operator=(const VoxelSparseBase& o) { prm_ = o.prm_; _grid_size = o._grid_size; return *this; }
+    void run(const PCR::PointCloud& in, std::vector<PCR::PointXYZI>& out) {
+        if (!h_ && !(h_ = pcr_create("loam", nullptr))) throw std::runtime_error(pcr_last_error(nullptr));      // any method: the filter only needs a device context
+        const size_t n = in.size();
+        out.assign(n ? n : 1, PCR::PointXYZI());
+        size_t n_out = 0;
+        if (pcr_voxel_filter_sparse(h_, in.points.data(), n, sizeof(PCR::PointXYZI), 0, _grid_size, &prm_, out.data(), n, 0, &n_out))
+            throw std::runtime_error(pcr_last_error(h_));
+        out.resize(n_out);
+    }
+};
+
+class VoxelDownSampleV2 : public VoxelSparseBase {
+public:
+    VoxelDownSampleV2() = default;
+    VoxelDownSampleV2(float gs, int max_vp = 20, int min_vp = 0) {
+        _grid_size = gs; prm_.kind = PCR_VOXEL_SPARSE_V2; prm_.max_voxel_pts = max_vp; prm_.min_voxel_pts = min_vp;
+    }
+    template <typename PointType = PCR::PointXYZI>
+    PCR::PC_Ptr filter(const PCR::PC_cPtr& cloud) {
+        PCR::PC_Ptr out = std::make_shared<PCR::PointCloud>();
+        run(*cloud, out->points);
+        return out;
+    }
+};
+
+class VoxelDownSampleV3 : public VoxelSparseBase {
+public:
+    VoxelDownSampleV3() = default;
+    VoxelDownSampleV3(float gs) { _grid_size = gs; prm_.kind = PCR_VOXEL_SPARSE_V3; }
+    template <typename PointType = PCR::PointXYZI>
+    void filter(const PCR::PC_cPtr& cloud, PCR::PC_Ptr& out) {
+        if (cloud->points.empty()) return;                       // pcp.hpp:175
+        std::vector<PCR::PointXYZI> tmp;
+        run(*cloud, tmp);
+        out->points.swap(tmp);                                   // (cloud.get() == out.get(), pcp.hpp:222,253: the input was read in full before this)
+    }
+};
 }  // namespace pcp

@@ -92,10 +92,20 @@ ABI_SYMBOLS = [
     "pcr_graph_tree", "pcr_graph_precondition", "pcr_graph_set_robust_kernel", "pcr_graph_get_robust_kernel", "pcr_graph_set_between_robust",
     "pcr_graph_set_between_enabled", "pcr_graph_add_loop", "pcr_graph_between_weights", "pcr_graph_robust_rho_w",
     "pcr_graph_set_fixed", "pcr_graph_fixed",
+    "pcr_voxel_sparse_default_params", "pcr_voxel_filter_sparse", "pcr_voxel_sparse_order", "pcr_map_update_all_sparse",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_size_t, C.c_int, C.c_void_p)
+
+
+# pcr_voxel_sparse_params.kind (include/pcr_hip.h: PCR_VOXEL_SPARSE_*)
+VOXEL_SPARSE_V3, VOXEL_SPARSE_V2 = 3, 2
+
+
+class VoxelSparseParams(C.Structure):
+    """pcr_voxel_sparse_params (include/pcr_hip.h)"""
+    _fields_ = [("kind", C.c_int32), ("max_voxel_pts", C.c_int32), ("min_voxel_pts", C.c_int32)]
 
 
 class ScParams(C.Structure):
@@ -208,6 +218,12 @@ def load_library():
     L.pcr_voxel_filter.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_double, vp, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
     L.pcr_voxel_filter_begin.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_double, vp, C.c_size_t]
     L.pcr_voxel_filter_end.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.pcr_voxel_sparse_default_params.argtypes = [C.POINTER(VoxelSparseParams)]
+    L.pcr_voxel_sparse_default_params.restype = None
+    L.pcr_voxel_filter_sparse.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_double, C.POINTER(VoxelSparseParams), vp, C.c_size_t, C.c_int,
+                                          C.POINTER(C.c_size_t)]
+    L.pcr_voxel_sparse_order.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pcr_map_update_all_sparse.argtypes = [vp, C.c_double, C.POINTER(C.c_size_t)]
     L.pcr_get_stats.argtypes = [vp, C.POINTER(PcrStats)]
     L.pcr_scan2map_submap.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, dp, ip]
     L.pcr_ndt_opt_create.restype = vp
@@ -583,6 +599,39 @@ class PointCloudRegister:
         out = np.zeros((max(n, 1), s // 4), np.float32)
         self._check(self._lib.pcr_voxel_filter(self._h, p, n, s, 0, float(grid_size), out.ctypes.data_as(C.c_void_p), n, 0, C.byref(cnt)))
         return out[:cnt.value].copy()
+
+    def _voxel_sparse(self, cloud, grid_size, prm):
+        p, n, s, dev, keep = _cloud(cloud)
+        cnt = C.c_size_t(0)
+        if dev:
+            import torch
+            out = torch.empty((max(n, 1), s // 4), dtype=torch.float32, device=keep.device)
+            self._check(self._lib.pcr_voxel_filter_sparse(self._h, p, n, s, 1, float(grid_size), C.byref(prm), C.c_void_p(out.data_ptr()), n, 1, C.byref(cnt)))
+            return out[:cnt.value]
+        out = np.zeros((max(n, 1), s // 4), np.float32)
+        self._check(self._lib.pcr_voxel_filter_sparse(self._h, p, n, s, 0, float(grid_size), C.byref(prm), out.ctypes.data_as(C.c_void_p), n, 0, C.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    def voxelDownSampleV3(self, cloud, grid_size):
+        """pcp::VoxelDownSampleV3 (reference common/pcp/pcp.hpp:157-263; pcr_voxel_filter_sparse): pcl::VoxelGrid's lattice without its limit on
+        the voxel box -- the centroid per occupied voxel, ascending (z, y, x).  Host array in -> numpy array out; CUDA tensor in -> CUDA tensor out."""
+        return self._voxel_sparse(cloud, grid_size, VoxelSparseParams(VOXEL_SPARSE_V3, 20, 0))
+
+    def voxelDownSampleV2(self, cloud, grid_size, max_voxel_pts=20, min_voxel_pts=0):
+        """pcp::VoxelDownSampleV2 (pcp.hpp:78-154, KISS-ICP's voxel hash; pcr_voxel_filter_sparse): voxel = (int)(p / grid_size); per voxel the
+        max_voxel_pts rows of lowest index, emitted when more than min_voxel_pts: the first row's record with x, y, z replaced by their float mean.
+        Ascending (z, y, x).  Host array in -> numpy array out; CUDA tensor in -> CUDA tensor out."""
+        return self._voxel_sparse(cloud, grid_size, VoxelSparseParams(VOXEL_SPARSE_V2, int(max_voxel_pts), int(min_voxel_pts)))
+
+    def sparseOrder(self):
+        """pcr_voxel_sparse_order: what the last voxelDownSampleV3 / V2 on this registrar sorted -> (keys (m,) uint64, rows (m,) uint32): per kept
+        input row, in sorted order, its packed voxel key and its original row index."""
+        cnt = C.c_size_t(0)
+        self._check(self._lib.pcr_voxel_sparse_order(self._h, None, None, 0, C.byref(cnt)))
+        keys, rows = np.zeros(cnt.value, np.uint64), np.zeros(cnt.value, np.uint32)
+        if cnt.value:
+            self._check(self._lib.pcr_voxel_sparse_order(self._h, keys.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p), cnt.value, C.byref(cnt)))
+        return keys, rows
 
     def voxelDownSampleBegin(self, cloud, grid_size):
         """pcr_voxel_filter_begin for a CUDA tensor: queue the filter, return a token for voxelDownSampleEnd (the input must stay alive until then)."""
@@ -1149,6 +1198,12 @@ class SubMap:
         """pcr_map_update_all (test/vis_globalmap.cpp:33-66): the whole map -- every key frame under its pose, concatenated, voxel-filtered."""
         n = C.c_size_t(0)
         self._check(self._lib.pcr_map_update_all(self._m, float(grid_size), C.byref(n)))
+        return n.value
+
+    def updateAllSparse(self, grid_size=0.4):
+        """pcr_map_update_all_sparse: updateAll with pcp::VoxelDownSampleV3 in place of pcl::VoxelGrid -- the whole map filtered whatever its extent."""
+        n = C.c_size_t(0)
+        self._check(self._lib.pcr_map_update_all_sparse(self._m, float(grid_size), C.byref(n)))
         return n.value
 
     def __del__(self):
