@@ -124,6 +124,10 @@ typedef struct pcr_params {
                                 *    uploaded (a pitched hipMemcpy2DAsync into a staging area of the same stride; registration reads x, y, z and nothing
                                 *    else).  Off by default: measured on MI355X / ROCm 7.2 the pitched copy of a 1 M-point map takes 3.5 ms where the
                                 *    verbatim copy of twice the bytes takes 0.6 ms (profiles/r04_notes.md) */
+    int32_t query_index;       /* PCR_QUERY_INDEX_*: the index pcr_knn and pcr_radius_search answer from (no other call reads it).  AUTO (0, the default): the
+                                *    dense cell table whenever it holds every point, the sparse index (sorted cell keys, memory by the points alone) for a
+                                *    target whose box no dense table can hold.  SPARSE (1): always the sparse index.  Same answers bit for bit.  A value
+                                *    out of range is refused by pcr_create and pcr_set_params */
 
     /* LIORF -- test/comp/liorf_scan2map.cpp (LioScan2map: LIO-SAM's surface scan-to-map).  Read by liorf handles only; every handle refuses a
      * value out of range, by name (pcr_create, pcr_set_params).  (The block stands in front of the struct's last three fields, whose place
@@ -183,6 +187,11 @@ typedef struct pcr_params {
 #define PCR_VOXEL_ADDITIVE 0
 #define PCR_VOXEL_ADDITIVE_WEIGHTED 1
 #define PCR_VOXEL_MULTIPLICATIVE 2
+
+/* pcr_params.query_index, and the `kind` pcr_query_index_info reports */
+#define PCR_QUERY_INDEX_AUTO 0
+#define PCR_QUERY_INDEX_SPARSE 1
+#define PCR_QUERY_INDEX_DENSE 0      /* pcr_query_index_info: the dense cell table answered */
 
 /* Per-call device timings, from HIP events on the handle's stream. */
 typedef struct pcr_stats {
@@ -888,8 +897,21 @@ int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t strid
  * coordinate that is not finite are not indexed and do not renumber the others.  Results ascend by (d2, idx): ties go to the lower
  * index (nanoflann's tie order follows its tree walk and is not reproduced).
  * queries: n_q records of stride_bytes (x, y, z floats first; 16 or 32 bytes in the reference's clouds), host or device memory.  The
- * outputs are host arrays.  Neither call changes what a later registration computes.  Sharded handles, handles with a query tile, and
- * an index that was cut to a region of interest (a target whose box cannot be tabulated) are refused with a message. */
+ * outputs are host arrays.  Neither call changes what a later registration computes.  Sharded handles and handles with a query tile
+ * are refused with a message.
+ * A target whose box cannot be tabulated (two sessions 30 km apart, one stray return kilometres off: the registrations cut the dense
+ * index to the bulk of the cloud) is answered from the SPARSE index: the points sorted by a 64-bit cell key (1 m cells, z then y then x,
+ * each axis a power-of-two field) and nothing else -- 24 bytes per point whatever the box, every row of cells found by binary search.
+ * pcr_params.query_index = PCR_QUERY_INDEX_SPARSE asks for it on every target; the answers are the dense index's bit for bit.  It is built
+ * by the first query that needs it after the target was set, from the handle's OWN copy of the target's points (pcr_set_target copies
+ * host and device buffers alike; a host target of pcr_scan2map lies in the handle's staging area) -- never from a caller's device
+ * buffer, which may be gone by then: after pcr_scan2map_device or pcr_scan2map_submap the sparse index is refused with a message
+ * that says so -- and kept until the target changes (pcr_set_target, pcr_scan2map*, pcr_invalidate_target, a pcr_set_params that
+ * drops the target, pcr_destroy).  AUTO goes by the dense index's own mark of a cut: a handle whose LAST target was cut may take that
+ * target's box over as the hint of its next index, and the mark with it, so that a compact target set on the same handle is answered
+ * from the sparse index too (exactly; before, it was refused) -- a fresh handle, or pcr_params.index_no_hints, answers it from the dense one.
+ * Refused, with the three extents in the message: a cloud whose cell box needs more than 63 key
+ * bits, or has a cell number of 2^62 or beyond (a stray point at 3e38 m); the handle stays usable. */
 #define PCR_KNN_MAX_K 32
 
 /* The k nearest target points of every query, 1 <= k <= PCR_KNN_MAX_K, with no range gate.  Row q of idx / d2 (k entries) ascends by
@@ -906,6 +928,11 @@ int pcr_knn(pcr_handle* h, const void* queries, size_t n_q, size_t stride_bytes,
  * A query with a coordinate that is not finite has no results. */
 int pcr_radius_search(pcr_handle* h, const void* queries, size_t n_q, size_t stride_bytes, int on_device, double radius, int sorted,
                       size_t capacity, uint64_t* offsets, int64_t* idx, double* d2, size_t* n_total);
+
+/* Which index answered the last pcr_knn / pcr_radius_search of the handle: *kind = PCR_QUERY_INDEX_DENSE or PCR_QUERY_INDEX_SPARSE (-1: no
+ * query has been answered since the target was set), *n_points = the points it holds (the finite ones), *bytes = the device memory it
+ * occupies (dense: the sorted points and the cell table; sparse: 24 bytes per point).  Any pointer may be NULL. */
+int pcr_query_index_info(pcr_handle* h, int* kind, size_t* n_points, size_t* bytes);
 
 /* ---- Relocalisation from a coarse pose ----------------------------------------------------------------------------------------------
  * The caller: the localisation program's operator sets the robot's pose by a click (/initialpose, dataproxy/src/RelocDataProxy.cpp:34-48)

@@ -89,6 +89,7 @@ int do_scan2map(pcr_handle* h, const void* src, size_t n_src, const void* dst, s
     if (!pose) return fail(h, "pose_inout is NULL");
     if ((n_src && !src) || (n_dst && !dst)) return fail(h, "NULL cloud with nonzero size");
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
+    drop_query_index(h);      // (from here on the target is replaced: the staging area is written over next)
     const float *d_src, *d_dst;
     if (ops(h).passes_profiled && prof_begin(h)) return 1;
     if (h->profile >= 1) H_TRY(hipEventRecord(h->ev_start, h->stream));
@@ -104,6 +105,7 @@ int do_scan2map(pcr_handle* h, const void* src, size_t n_src, const void* dst, s
 // pcr_map's sub-map for as long as its generation lasts)
 int prepare_target_from(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_bytes) {
     h->map_id = 0; h->map_gen = 0;      // (pcr_scan2map_submap sets them after a successful preparation)
+    drop_query_index(h);
     return ops(h).prepare_target(h, d_dst, n_dst, stride_bytes / 4);
 }
 
@@ -150,6 +152,7 @@ const char* settings_out_of_range(const pcr_params& p) {
     if (p.vgicp_search == PCR_VGICP_DIRECT_RADIUS)
         return "vgicp_search = 3 (DIRECT_RADIUS) is not served: the reference implements it in its CUDA variant only (gicp_settings.hpp:8) and "
                "FastVGICP aborts on it (fast_vgicp_voxel.hpp:13-15); use 0 (DIRECT27), 1 (DIRECT7) or 2 (DIRECT1)";
+    if (p.query_index != PCR_QUERY_INDEX_AUTO && p.query_index != PCR_QUERY_INDEX_SPARSE) return "query_index must be 0 (AUTO) or 1 (SPARSE)";
     // liorf_scan2map.cpp's constants.  Every handle is checked; only liorf handles read the values.
     return liorf_params_out_of_range(p);
 }
@@ -254,6 +257,7 @@ int pcr_set_target(pcr_handle* h, const void* dst, size_t n_dst, size_t stride_b
     h->err.clear();
     if (n_dst && !dst) return fail(h, "NULL cloud with nonzero size");
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
+    drop_query_index(h);      // (before the staging copy it was built from is written over: a copy that fails must not leave it standing)
     // the library copies what it keeps: the index holds its own sorted copy, but a rebuild after a
     // cell-table overflow needs the raw points, so they are staged in HBM either way
     const size_t bytes = n_dst * stride_bytes;
@@ -322,6 +326,7 @@ int pcr_invalidate_target(pcr_handle* h) {
     if (!h) return 1;
     h->have_target = false; h->grid.valid = false; h->target_ready = false;
     h->map_id = 0; h->map_gen = 0; h->roi_on = false;
+    drop_query_index(h);
     return 0;
 }
 
@@ -377,7 +382,7 @@ int pcr_set_params(pcr_handle* h, const pcr_params* p) {
     h->prm.device = old.device;
     // whatever was derived from a parameter that changed is dropped (each method's unit says what its target is derived from); the optimiser
     // settings are read at every call.  (A loam handle never sets target_ready: there is none to clear.)
-    if (ops(h).target_from_changed(old, *p)) { h->target_ready = false; h->have_target = false; h->grid.valid = false; }
+    if (ops(h).target_from_changed(old, *p)) { h->target_ready = false; h->have_target = false; h->grid.valid = false; drop_query_index(h); }
     // the regularisation shaped every covariance the handle holds: a scan's side that is still in flight (pcr_scan2map_submap queues it ahead) is
     // collected and forgotten -- its covariances are the old setting's
     const bool reg_changed = p->vgicp_regularization != old.vgicp_regularization;

@@ -76,6 +76,7 @@ struct pcr_handle {
     pcr::ClampBox clamp{};           // LOAM scan2map fallback: region of interest of a target whose full box cannot be tabulated (capi, loam, vgicp)
     bool clamp_allowed = false;      // set while a scan2map call (target rebuilt for this very scan) is running (capi, loam)
     bool clamp_from_bulk = false;    // pcr_set_target in progress: an untabulatable box may be cut to the bulk of the target (capi, loam)
+    int clamp_bulk_stage = 0;        // ... how far that has gone: 0 not cut, 1 cut to the bulk box, 2 to the room around one point (loam)
     double clamp_margin = 10.0;      // LOAM ClampBox: room around the scan, doubled when a query reached a cut face (loam, vgicp)
     uint64_t map_id = 0, map_gen = 0;    // pcr_scan2map_submap: the sub-map the target structures were built from (capi)
     long long target_builds = 0;         // ... and how often it had to build them
@@ -205,6 +206,16 @@ struct pcr_handle {
     struct Query {
         pcr::DeviceBuf rl_poses, rl_part, rl_out, rl_src;   // pcr_fitness_batch: the poses in float, the [pose][chunk] partials, the sums; pcr_relocalize: its staged host source
         pcr::DeviceBuf idx, d2, idx2, d22, counts, offsets;      // pcr_knn / pcr_radius_search: results (radius, sorted: filled into one pair, sorted into the other), counts, offsets
+        // the sparse index of the kept target (sparse_index.hip), built by the first query that needs it and dropped with the target (drop_query_index):
+        // the keys and the points in key order, exactly 24 bytes per row of the target; what its build reported
+        struct Sparse {
+            pcr::DeviceBuf keys, pts;
+            bool valid = false;
+            pcr::sw::View view = {};
+            pcr::host::Mapped<pcr::SiResult> ret;
+        } sparse;
+        int last_kind = -1;              // the index that answered the last query (PCR_QUERY_INDEX_DENSE / _SPARSE), -1: none since the target was set
+        size_t last_points = 0, last_bytes = 0;
     } q;
 
     // multi-GPU: the tile of the map this rank holds (set by comm: pcr_set_shard / pcr_set_query_tile; read by loam, vgicp, ndt, query)
@@ -326,7 +337,7 @@ std::string ndt_halo_message(int search, double need);
 // ---- loam_host.hip ----
 int build_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t stride_floats);
 int set_clamp_from_scan(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, const double pose[16]);
-int set_clamp_from_target_sample(pcr_handle* h);
+int set_clamp_from_target_sample(pcr_handle* h, bool room = false);
 int settle_loam_index(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, const double* pose);
 int run_loam(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_floats, double pose[16], int* converged, bool index_timed);
 
@@ -394,6 +405,8 @@ void arm_fitness(pcr_handle* h, const double pose[16], size_t n, size_t stride_f
 
 // ---- query_host.hip ----
 std::string cut_fitness_message(double n);
+// the kept target has changed or is gone: the sparse index built from it goes too (capi: every entry point that sets or drops a target)
+void drop_query_index(pcr_handle* h);
 
 // How a device-resident optimiser's passes (run_lsq, run_ndt) are queued ahead of the progress word of its result block
 struct PaceRule {

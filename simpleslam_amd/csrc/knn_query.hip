@@ -22,10 +22,15 @@
 #include <string.h>
 
 #include "pcr_internal.h"
+#include "nb_list.h"
+#include "sparse_walk.h"
 
 namespace pcr {
 
 namespace {
+
+using sw::slab_gap;      // (the bounds of this file, shared with the sparse index's walk)
+using sw::slop_of;
 
 struct Lattice {
     int d0, d1, d2;
@@ -41,57 +46,9 @@ __device__ __forceinline__ Lattice lattice_of(const GridHeader& h) {
     return l;
 }
 
-__device__ __forceinline__ double slop_of(double face, double q, double cell) { return (fabs(face) + fabs(q) + cell) * 0x1p-20; }
-
-// distance from q to the slab of cells i of one axis (0 inside it), never more than the true gap to any point the build put there
-__device__ __forceinline__ double slab_gap(double o, int i, double cell, double q) {
-    const double lo = (o + (double)i) * cell, hi = (o + (double)i + 1.0) * cell;
-    const double g = fmax(fmax(lo - q, q - hi), 0.0);
-    return fmax(g - slop_of(fmax(fabs(lo), fabs(hi)), q, cell), 0.0);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // k nearest neighbours
 // ---------------------------------------------------------------------------------------------------------------------------
-template <int K>
-struct NbList {
-    double d[K];
-    uint32_t i[K];
-};
-
-template <int K>
-__device__ __forceinline__ void nb_insert(NbList<K>& L, double d, uint32_t idx) {
-    bool c[K];
-#pragma unroll
-    for (int i = 0; i < K; ++i) c[i] = d < L.d[i] || (d == L.d[i] && idx < L.i[i]);
-#pragma unroll
-    for (int i = K - 1; i >= 1; --i) {
-        L.d[i] = c[i - 1] ? L.d[i - 1] : (c[i] ? d : L.d[i]);
-        L.i[i] = c[i - 1] ? L.i[i - 1] : (c[i] ? idx : L.i[i]);
-    }
-    L.d[0] = c[0] ? d : L.d[0];
-    L.i[0] = c[0] ? idx : L.i[0];
-}
-
-template <int K>
-__device__ __forceinline__ void nb_scan_run(const float4* __restrict__ pts, uint32_t s, uint32_t e, double qx, double qy, double qz, NbList<K>& L) {
-    // four candidates per step, their loads issued together (ring_search.h: ring_scan_run)
-    for (uint32_t j = s; j < e; j += 4) {
-        float4 p[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) p[u] = pts[j + u < e ? j + u : j];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const double dx = qx - (double)p[u].x, dy = qy - (double)p[u].y, dz = qz - (double)p[u].z;
-            double d = dx * dx;
-            d += dy * dy;
-            d += dz * dz;
-            const uint32_t idx = __float_as_uint(p[u].w);
-            if (j + u < e && (d < L.d[K - 1] || (d == L.d[K - 1] && idx < L.i[K - 1]))) nb_insert<K>(L, d, idx);
-        }
-    }
-}
-
 // Rings 1, 2, ... around the (clamped) centre cell until the K-th distance is proven final.  Ring r adds the shell of the block
 // [c - r, c + r]; ring 1 is the whole 3 x 3 x 3 block.  Every point is visited once.
 template <int K>
@@ -302,6 +259,12 @@ hipError_t knn_query_launch(const GridIndex& grid, const float* d_q, size_t n_q,
     return hipGetLastError();
 }
 
+hipError_t radius_scan_launch(const uint32_t* d_counts, size_t n_q, unsigned long long* d_offsets, hipStream_t s) {
+    if (n_q > 0xfffffff0ull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(radius_scan_kernel, dim3(1), dim3(1024), 0, s, d_counts, (uint32_t)n_q, d_offsets);
+    return hipGetLastError();
+}
+
 hipError_t radius_count_launch(const GridIndex& grid, const float* d_q, size_t n_q, size_t stride_floats, double radius, uint32_t* d_counts,
                                unsigned long long* d_offsets, hipStream_t s) {
     if (n_q > 0xfffffff0ull) return hipErrorInvalidValue;
@@ -309,8 +272,7 @@ hipError_t radius_count_launch(const GridIndex& grid, const float* d_q, size_t n
     if (n)
         hipLaunchKernelGGL((radius_query_kernel<false>), dim3((n + 3) / 4), dim3(256), 0, s, grid.view(), d_q, n, (uint32_t)stride_floats, radius, radius * radius,
                            d_counts, (const unsigned long long*)nullptr, (int64_t*)nullptr, (double*)nullptr);
-    hipLaunchKernelGGL(radius_scan_kernel, dim3(1), dim3(1024), 0, s, d_counts, n, d_offsets);
-    return hipGetLastError();
+    return radius_scan_launch(d_counts, n_q, d_offsets, s);
 }
 
 hipError_t radius_fill_launch(const GridIndex& grid, const float* d_q, size_t n_q, size_t stride_floats, double radius, const unsigned long long* d_offsets,

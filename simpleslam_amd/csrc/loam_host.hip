@@ -113,7 +113,7 @@ int set_clamp_from_scan(pcr_handle* h, const float* d_src, size_t n_src, size_t 
 // leaves a stray one out.  What lies outside is not indexed -- and, as with the scan-centred cut, not silently: a face with target
 // points beyond it is marked (header.cut_mask), a query whose 3x3x3 block touches such a face is counted, and the registration is
 // then redone on a region cut around the scan (run_loam), so a scan that really visits the far part of the cloud is still served.
-int set_clamp_from_target_sample(pcr_handle* h) {
+int set_clamp_from_target_sample(pcr_handle* h, bool room) {
     const size_t n = h->tgt_n, stride_b = h->tgt_stride * 4;
     if (!n || !h->tgt_ptr) return fail(h, "target bounding box too large for the dense index");
     const size_t step = std::max<size_t>(1, n / 4096), m = (n + step - 1) / step;
@@ -129,6 +129,18 @@ int set_clamp_from_target_sample(pcr_handle* h) {
         const double q_lo = v[(size_t)(0.02 * (double)(v.size() - 1))], q_hi = v[(size_t)(0.98 * (double)(v.size() - 1) + 0.5)];
         const double pad = 0.5 * (q_hi - q_lo) + 20.0;
         h->clamp.lo[d] = q_lo - pad; h->clamp.hi[d] = q_hi + pad;
+    }
+    // room: the index over the bulk box has itself reported more cells than a dense table can have, at the cell the caller builds with (two
+    // sessions 30 km apart: the percentiles span both; such a target was refused).  Then the room around ONE point of the cloud -- the finite
+    // sample whose x is the median -- 500 m x 500 m x 200 m: an index that can be built, cut faces that are marked as above, and a registration
+    // elsewhere in the cloud redone on a region cut around its scan.  (pcr_knn / pcr_radius_search answer such a target from the sparse index.)
+    if (room) {
+        std::vector<size_t> fin;
+        for (size_t i = 0; i < m; ++i) if (std::isfinite(xyz[i * 3]) && std::isfinite(xyz[i * 3 + 1]) && std::isfinite(xyz[i * 3 + 2])) fin.push_back(i);
+        std::nth_element(fin.begin(), fin.begin() + fin.size() / 2, fin.end(), [&](size_t a, size_t b) { return xyz[a * 3] != xyz[b * 3] ? xyz[a * 3] < xyz[b * 3] : a < b; });
+        const size_t c = fin[fin.size() / 2];
+        const double half[3] = {250.0, 250.0, 100.0};
+        for (int d = 0; d < 3; ++d) { h->clamp.lo[d] = (double)xyz[c * 3 + d] - half[d]; h->clamp.hi[d] = (double)xyz[c * 3 + d] + half[d]; }
     }
     h->clamp.use = 1;
     return 0;
@@ -147,8 +159,10 @@ int check_grid_overflow(pcr_handle* h, int overflow, uint64_t need_cells, const 
         if (build_target(h, h->tgt_ptr, h->tgt_n, h->tgt_stride)) return 1;
         return 2;
     }
-    if (need_cells > 4000000000ull && h->method == kLoam && h->clamp_from_bulk && !h->clamp.use) {      // pcr_set_target: no scan to go by
-        if (set_clamp_from_target_sample(h)) return 1;
+    if (need_cells > 4000000000ull && h->method == kLoam && h->clamp_from_bulk && h->clamp_bulk_stage < 2) {      // pcr_set_target: no scan to go by
+        // the bulk of the cloud first; when the index over THAT box reports more than 4e9 cells too, the room around one point of it
+        if (set_clamp_from_target_sample(h, h->clamp_bulk_stage == 1)) return 1;
+        h->clamp_bulk_stage += 1;
         if (build_target(h, h->tgt_ptr, h->tgt_n, h->tgt_stride)) return 1;
         return 2;
     }
@@ -346,6 +360,7 @@ int loam_prepare_target(pcr_handle* h, const float* d_dst, size_t n_dst, size_t 
     h->clamp.use = 0;
     // settle the cell-table size now so that pcr_align never has to rebuild
     int rc = build_target(h, d_dst, n_dst, stride_floats);
+    h->clamp_bulk_stage = 0;
     h->clamp_from_bulk = true;          // a box that cannot be tabulated is cut to the bulk of the cloud (set_clamp_from_target_sample)
     if (!rc) rc = settle_loam_index(h, nullptr, 0, 0, nullptr);
     h->clamp_from_bulk = false;

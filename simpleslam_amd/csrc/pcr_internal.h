@@ -11,6 +11,7 @@
 
 #include "../../include/pcr_hip.h"
 #include "grid_plan.h"
+#include "sparse_walk.h"
 
 namespace pcr {
 
@@ -424,6 +425,28 @@ hipError_t radius_fill_launch(const GridIndex& grid, const float* d_q, size_t n_
                               int64_t* d_idx, double* d_d2, hipStream_t s);
 hipError_t radius_sort_launch(size_t n_q, const unsigned long long* d_offsets, const int64_t* d_in_idx, const double* d_in_d2, int64_t* d_out_idx,
                               double* d_out_d2, hipStream_t s);
+// (the exclusive scan of the counts alone: d_offsets[i] = d_counts[0] + ... + d_counts[i - 1], i = 0 .. n_q)
+hipError_t radius_scan_launch(const uint32_t* d_counts, size_t n_q, unsigned long long* d_offsets, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// Sparse target index (sparse_index.hip; the walk: sparse_walk.h): the same two queries on a target whose box no dense table can hold
+// ---------------------------------------------------------------------------
+static constexpr double kSparseCell = 1.0;      // cell edge of the sparse index (a power of two: x / cell is exact)
+// what the build's last launch reports into page-locked memory: the points stored (the finite rows), the key layout and its verdict
+struct SiResult { uint32_t kept; int32_t pad_; sw::Layout lay; };
+struct SiBuffers {           // the build's scratch, all of it sized by n and freed after the build
+    void* hdr;               // 256 bytes
+    unsigned long long* key[2]; uint32_t* row[2];
+    uint32_t* hist;          // key_sort_hist_bytes(n)
+};
+// d_keys (n x 8 bytes) / d_pts (n x 16 bytes): the index, in key order, entries [0, kept)
+hipError_t sparse_index_build_launch(const SiBuffers& b, const float* d_src, size_t stride_floats, size_t n, unsigned long long* d_keys, sw::Point* d_pts,
+                                     SiResult* result_mapped, hipStream_t s);
+hipError_t knn_sparse_launch(const sw::View& v, const float* d_q, size_t n_q, size_t stride_floats, int k, int64_t* d_idx, double* d_d2, hipStream_t s);
+hipError_t radius_sparse_count_launch(const sw::View& v, const float* d_q, size_t n_q, size_t stride_floats, double radius, uint32_t* d_counts,
+                                      unsigned long long* d_offsets, hipStream_t s);
+hipError_t radius_sparse_fill_launch(const sw::View& v, const float* d_q, size_t n_q, size_t stride_floats, double radius, const unsigned long long* d_offsets,
+                                     int64_t* d_idx, double* d_d2, hipStream_t s);
 
 // pcl::VoxelGrid on the device (voxel_filter.hip); grid must have been built with pcl_mode = 1
 // (two launches queued behind the build; they read the header themselves and do nothing when it says overflow, stale or empty.  d_inten: n floats,
@@ -451,6 +474,12 @@ struct VsBuffers {           // device memory of one call, all of it sized by n 
     uint32_t* tile;          // per block of 256 sorted rows: voxels emitted, scanned in place
 };
 struct VsSizes { size_t hdr, key, row, hist, cnt, first, lead, tile; };
+// ... and its stable radix sort of (64-bit key, row) pairs on its own (voxel_sparse.hip: key_sort_launch says what goes in and comes out): device
+// memory by the number of pairs alone.  The control block lives in device memory: the launch in front of the sort sets `passes` there.
+static constexpr uint32_t kVsDropped = 0xffffffffu;      // row number of a pair that leaves in the first pass (a non-finite row; rows end at 0xfffffff0)
+struct KeySortCtl { uint32_t kept; int32_t passes; };
+size_t key_sort_hist_bytes(size_t n);
+void key_sort_launch(KeySortCtl* d_ctl, size_t n, unsigned long long* const key[2], uint32_t* const row[2], uint32_t* hist, hipStream_t s);
 VsSizes voxel_sparse_bytes(size_t n);
 hipError_t voxel_sparse_launch(const VsBuffers& b, const float* d_pts, size_t stride_floats, size_t n, float leaf, int kind, int max_voxel_pts,
                                int min_voxel_pts, float* d_out, size_t out_capacity, VsResult* result_mapped, hipStream_t s);

@@ -1,6 +1,8 @@
 // query_host.hip -- questions to the target a handle keeps: fitness scores at given poses (pcr_fitness_gated, pcr_fitness_batch),
 // relocalisation from a coarse pose and over every key frame, exact k-NN and radius queries.
 
+#include <stdio.h>
+
 #include <algorithm>
 #include <vector>
 
@@ -14,6 +16,14 @@ namespace host {
 
 // An index cut to a region (a target too spread out for the dense tables: its bulk, or the room around a scan) cannot tell the nearest target
 // point of a source point that lies beyond a cut face, or nearer to one than to every point it holds.  Such a score is refused, never guessed.
+void drop_query_index(pcr_handle* h) {
+    pcr_handle::Query::Sparse& sp = h->q.sparse;
+    if (sp.keys.p || sp.pts.p) (void)hipSetDevice(h->device);
+    sp.keys.release(); sp.pts.release();
+    sp.valid = false; sp.view = sw::View{};
+    h->q.last_kind = -1; h->q.last_points = 0; h->q.last_bytes = 0;
+}
+
 std::string cut_fitness_message(double n) {
     return std::to_string((long long)n) + " source points may have their nearest target point in the part of the target the index was cut off "
            "(a target too spread out for the dense index, a stray point far from the map?): no fitness score against a cut index";
@@ -266,18 +276,81 @@ void reloc_point_fitness_at(pcr_handle* h, const double pose[16]) {
     if (h->fit_pending) { memcpy(h->fit_pose, pose, sizeof h->fit_pose); h->fitness = DBL_MAX; }
 }
 
-// pcr_knn / pcr_radius_search: the full index of the kept target (prepared in full first, as pcr_relocalize does), its header checked on the host
+// exactly `bytes` of device memory (DeviceBuf::reserve doubles, for buffers that grow; the sparse index is built once per target)
+hipError_t reserve_exact(DeviceBuf& b, size_t bytes) {
+    if (b.p && b.cap == bytes) return hipSuccess;
+    b.release();
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e != hipSuccess) { b.p = nullptr; return e; }
+    b.cap = bytes;
+    return hipSuccess;
+}
+
+// The sparse index of the kept target, built when the handle has none: from the handle's own copy of the target's points (pcr_set_target's, or the
+// staged host target of pcr_scan2map) -- a caller's device buffer may be gone by now.  One synchronisation; the sort's scratch is freed on return.
+int sparse_index_for(pcr_handle* h, const char* who) {
+    pcr_handle::Query::Sparse& sp = h->q.sparse;
+    if (sp.valid) return 0;
+    if (h->tgt_n && h->tgt_ptr != h->tgt_stage.as<float>())      // (a target of no points is nobody's buffer: its index is empty)
+        return fail(h, std::string(who) + ": the sparse index is built from the handle's own copy of the target, and this target was a device buffer of the caller's "
+                       "(pcr_scan2map_device, pcr_scan2map_submap) that may be gone: call pcr_set_target");
+    const size_t n = h->tgt_n;
+    if (n > kMaxPoints) return fail(h, std::string(who) + ": target too large");
+    DeviceBuf hdr, key[2], row[2], hist;
+    H_TRY(hdr.reserve(256));
+    for (int i = 0; i < 2; ++i) { H_TRY(key[i].reserve((n + 1) * sizeof(unsigned long long))); H_TRY(row[i].reserve((n + 1) * sizeof(uint32_t))); }
+    H_TRY(hist.reserve(key_sort_hist_bytes(n)));
+    H_TRY(reserve_exact(sp.keys, (n ? n : 1) * sizeof(unsigned long long)));
+    H_TRY(reserve_exact(sp.pts, (n ? n : 1) * sizeof(sw::Point)));
+    H_TRY(sp.ret.ensure());
+    SiBuffers b;
+    b.hdr = hdr.p; b.hist = hist.as<uint32_t>();
+    for (int i = 0; i < 2; ++i) { b.key[i] = key[i].as<unsigned long long>(); b.row[i] = row[i].as<uint32_t>(); }
+    H_TRY(sparse_index_build_launch(b, h->tgt_ptr, h->tgt_stride, n, sp.keys.as<unsigned long long>(), sp.pts.as<sw::Point>(), sp.ret.dev, h->stream));
+    H_TRY(hipStreamSynchronize(h->stream));
+    const SiResult r = *sp.ret.host;
+    if (r.lay.refused) {
+        char ext[160];
+        snprintf(ext, sizeof ext, "%.6g x %.6g x %.6g", r.lay.extd[0], r.lay.extd[1], r.lay.extd[2]);
+        sp.keys.release(); sp.pts.release();
+        return fail(h, std::string(who) + (r.lay.refused == sw::kRefusedBits
+                           ? ": the sparse index's cell key needs " + std::to_string(r.lay.b[0] + r.lay.b[1] + r.lay.b[2]) + " bits, more than 63"
+                           : std::string(": a cell number of the sparse index leaves the 62-bit range")) +
+                       ": extents " + ext + " cells of " + std::to_string(kSparseCell) + " m (x, y, z): refused (a stray point far from the map?)");
+    }
+    sw::View v;
+    v.keys = sp.keys.as<unsigned long long>(); v.pts = sp.pts.as<sw::Point>();
+    v.n = r.kept; v.b0 = r.lay.b[0]; v.b1 = r.lay.b[1]; v.b2 = r.lay.b[2];
+    for (int a = 0; a < 3; ++a) { v.lo[a] = r.lay.lo[a]; v.ext[a] = r.lay.ext[a]; }
+    v.cell = kSparseCell;
+    sp.view = v; sp.valid = true;
+    return 0;
+}
+
+// pcr_knn / pcr_radius_search: the index that answers (pcr_params.query_index).  The dense one: the full index of the kept target (prepared in full
+// first, as pcr_relocalize does), its header checked on the host; *grid = nullptr: the sparse one (h->q.sparse.view), for a target whose dense
+// index was cut to the bulk of the cloud, or when the caller asks for it.
 int query_index_for(pcr_handle* h, const char* who, size_t n_q, size_t stride_bytes, const GridIndex** grid) {
+    *grid = nullptr;
     if (!h->have_target || !h->grid.valid) return fail(h, std::string(who) + ": no kept target: call pcr_set_target first");
     if (batch_preconditions(h, n_q, stride_bytes)) { h->err = std::string(who) + ": " + h->err; return 1; }
-    if (ensure_full_target(h)) return 1;
-    if (fit_grid_for(h, grid)) return 1;
-    GridHeader hdr;
-    H_TRY(hipMemcpyAsync(&hdr, (*grid)->header.p, sizeof hdr, hipMemcpyDeviceToHost, h->stream));
-    H_TRY(hipStreamSynchronize(h->stream));
-    if (hdr.overflow || hdr.stale || (*grid)->filtered) return fail(h, std::string(who) + ": the target index is not complete (internal)");
-    if (hdr.clamped)
-        return fail(h, std::string(who) + ": the target's box cannot be tabulated and its index was cut to the bulk of the cloud: an exact query needs every point");
+    if (h->prm.query_index != PCR_QUERY_INDEX_SPARSE) {
+        if (ensure_full_target(h)) return 1;
+        if (fit_grid_for(h, grid)) return 1;
+        GridHeader hdr;
+        H_TRY(hipMemcpyAsync(&hdr, (*grid)->header.p, sizeof hdr, hipMemcpyDeviceToHost, h->stream));
+        H_TRY(hipStreamSynchronize(h->stream));
+        if (hdr.overflow || hdr.stale || (*grid)->filtered) return fail(h, std::string(who) + ": the target index is not complete (internal)");
+        if (!hdr.clamped) {
+            h->q.last_kind = PCR_QUERY_INDEX_DENSE; h->q.last_points = (*grid)->n_points;
+            h->q.last_bytes = (*grid)->sorted.cap + (*grid)->cell_start.cap + (*grid)->header.cap;
+            return 0;
+        }
+        *grid = nullptr;      // the box cannot be tabulated and the index was cut to the bulk of the cloud: an exact query needs every point
+    }
+    if (sparse_index_for(h, who)) return 1;
+    h->q.last_kind = PCR_QUERY_INDEX_SPARSE; h->q.last_points = h->q.sparse.view.n;
+    h->q.last_bytes = h->q.sparse.keys.cap + h->q.sparse.pts.cap;
     return 0;
 }
 
@@ -318,7 +391,8 @@ int pcr_knn(pcr_handle* h, const void* queries, size_t n_q, size_t stride_bytes,
     H_TRY(h->q.d2.reserve(std::min(n_q, chunk) * (size_t)k * sizeof(double)));
     for (size_t q0 = 0; q0 < n_q; q0 += chunk) {
         const size_t m = std::min(chunk, n_q - q0);
-        H_TRY(knn_query_launch(*grid, d_q + q0 * (stride_bytes / 4), m, stride_bytes / 4, k, h->q.idx.as<int64_t>(), h->q.d2.as<double>(), h->stream));
+        if (grid) H_TRY(knn_query_launch(*grid, d_q + q0 * (stride_bytes / 4), m, stride_bytes / 4, k, h->q.idx.as<int64_t>(), h->q.d2.as<double>(), h->stream));
+        else H_TRY(knn_sparse_launch(h->q.sparse.view, d_q + q0 * (stride_bytes / 4), m, stride_bytes / 4, k, h->q.idx.as<int64_t>(), h->q.d2.as<double>(), h->stream));
         H_TRY(hipMemcpyAsync(idx + q0 * (size_t)k, h->q.idx.p, m * (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
         H_TRY(hipMemcpyAsync(d2 + q0 * (size_t)k, h->q.d2.p, m * (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         H_TRY(hipStreamSynchronize(h->stream));
@@ -342,7 +416,8 @@ int pcr_radius_search(pcr_handle* h, const void* queries, size_t n_q, size_t str
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "offsets are 64-bit");
     H_TRY(h->q.counts.reserve((n_q + 1) * sizeof(uint32_t)));
     H_TRY(h->q.offsets.reserve((n_q + 1) * sizeof(uint64_t)));
-    H_TRY(radius_count_launch(*grid, d_q, n_q, stride_bytes / 4, radius, h->q.counts.as<uint32_t>(), h->q.offsets.as<unsigned long long>(), h->stream));
+    if (grid) H_TRY(radius_count_launch(*grid, d_q, n_q, stride_bytes / 4, radius, h->q.counts.as<uint32_t>(), h->q.offsets.as<unsigned long long>(), h->stream));
+    else H_TRY(radius_sparse_count_launch(h->q.sparse.view, d_q, n_q, stride_bytes / 4, radius, h->q.counts.as<uint32_t>(), h->q.offsets.as<unsigned long long>(), h->stream));
     H_TRY(hipMemcpyAsync(offsets, h->q.offsets.p, (n_q + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     H_TRY(hipStreamSynchronize(h->stream));
     const uint64_t total = offsets[n_q];
@@ -354,7 +429,8 @@ int pcr_radius_search(pcr_handle* h, const void* queries, size_t n_q, size_t str
     const size_t t = (size_t)total;
     H_TRY(h->q.idx.reserve(t * sizeof(int64_t)));
     H_TRY(h->q.d2.reserve(t * sizeof(double)));
-    H_TRY(radius_fill_launch(*grid, d_q, n_q, stride_bytes / 4, radius, h->q.offsets.as<unsigned long long>(), h->q.idx.as<int64_t>(), h->q.d2.as<double>(), h->stream));
+    if (grid) H_TRY(radius_fill_launch(*grid, d_q, n_q, stride_bytes / 4, radius, h->q.offsets.as<unsigned long long>(), h->q.idx.as<int64_t>(), h->q.d2.as<double>(), h->stream));
+    else H_TRY(radius_sparse_fill_launch(h->q.sparse.view, d_q, n_q, stride_bytes / 4, radius, h->q.offsets.as<unsigned long long>(), h->q.idx.as<int64_t>(), h->q.d2.as<double>(), h->stream));
     const void *r_idx = h->q.idx.p, *r_d2 = h->q.d2.p;
     if (sorted) {
         H_TRY(h->q.idx2.reserve(t * sizeof(int64_t)));
@@ -366,6 +442,14 @@ int pcr_radius_search(pcr_handle* h, const void* queries, size_t n_q, size_t str
     H_TRY(hipMemcpyAsync(idx, r_idx, t * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     H_TRY(hipMemcpyAsync(d2, r_d2, t * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     H_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int pcr_query_index_info(pcr_handle* h, int* kind, size_t* n_points, size_t* bytes) {
+    if (!h) return 1;
+    if (kind) *kind = h->q.last_kind;
+    if (n_points) *n_points = h->q.last_points;
+    if (bytes) *bytes = h->q.last_bytes;
     return 0;
 }
 

@@ -89,7 +89,8 @@ int settle_cov_levels(pcr_handle* h, GridIndex& g, GridIndex& l1, GridIndex& l2,
     bool todo[3] = {true, levels > 1, levels > 2};
     if (after_clean) *after_clean = false;
     if (after_ahead && vgicp_side_init(h)) return 1;
-    for (int attempt = 0; attempt < 4; ++attempt) {
+    int bulk_stage = 0;      // this call has cut the cloud to its bulk (1), to the room around one point (2)
+    for (int attempt = 0; attempt < 5; ++attempt) {
         if (attempt > 0 && filter0) filter0->applied = filter0->tail_applied = false;      // (a repeat is a full build)
         GridHeader hdr_stack[4];
         GridHeader* hdr = after_ahead ? h->side_hdr + 3 : hdr_stack;      // (page-locked when the host is not to block in the copies)
@@ -146,9 +147,11 @@ int settle_cov_levels(pcr_handle* h, GridIndex& g, GridIndex& l1, GridIndex& l2,
                 continue;
             }
             if (hdr[l].overflow) {
-                if (hdr[l].n_cells > 4000000000ull && may_cut && !h->clamp.use) {
-                    // a box no dense table can hold (a stray point far from the map): index the bulk of the cloud instead, all levels alike
-                    if (set_clamp_from_target_sample(h)) return 1;
+                if (hdr[l].n_cells > 4000000000ull && may_cut && (!h->clamp.use || bulk_stage == 1)) {
+                    // a box no dense table can hold (a stray point far from the map): index the bulk of the cloud instead, all levels alike; when
+                    // the index over the bulk box reports as much again (two sessions far apart), the room around one point of it
+                    if (set_clamp_from_target_sample(h, bulk_stage == 1)) return 1;
+                    bulk_stage += 1;
                     for (int k = 0; k < 3; ++k) todo[k] = k < levels;
                     again = true;
                     break;

@@ -24,14 +24,13 @@ static constexpr int kVsTile = 2048;          // rows per block of the box, key 
 static constexpr int kVsBins = 257;           // 256 digit values + one bin behind them for the dropped rows (first pass only)
 static constexpr int kVsScan = 1024;          // threads of the one-block scans
 static constexpr int kVsMaxPasses = 8;
-static constexpr uint32_t kVsDropped = 0xffffffffu;      // row number of a non-finite row (rows end at 0xfffffff0)
 
 struct VsHdr {
     int32_t lo[3], hi[3];          // box of the lattice integers over the kept rows
     uint32_t range_bad;            // a finite row's lattice value left the int range
-    uint32_t kept;                 // finite rows (known after the first digit pass)
     uint32_t total;                // voxels emitted
-    int32_t passes, refused, bits;
+    KeySortCtl sort;               // the sort's digit passes; its kept rows -- the finite ones -- are known after the first
+    int32_t refused, bits;
     int32_t shift[3];
     int32_t pad_;
     unsigned long long ext[3];
@@ -48,7 +47,7 @@ __global__ __launch_bounds__(64) void vs_init_kernel(VsHdr* __restrict__ hdr) {
     if (threadIdx.x != 0) return;
     VsHdr h;
     for (int a = 0; a < 3; ++a) { h.lo[a] = INT_MAX; h.hi[a] = INT_MIN; h.shift[a] = 0; h.ext[a] = 0; }
-    h.range_bad = 0; h.kept = 0; h.total = 0; h.passes = 0; h.refused = 0; h.bits = 0; h.pad_ = 0;
+    h.range_bad = 0; h.sort.kept = 0; h.total = 0; h.sort.passes = 0; h.refused = 0; h.bits = 0; h.pad_ = 0;
     *hdr = h;
 }
 
@@ -83,10 +82,10 @@ __global__ __launch_bounds__(256) void vs_box_kernel(const float* __restrict__ p
 // The key layout the box asks for.  V3: extent = (floor(max * inv) - (float)min_b) + 1 with the subtraction in float, as a row's own ijk is
 // formed; V2: the exact integer difference.
 __device__ inline void vs_layout(VsHdr& h, int kind) {
-    h.passes = 0; h.refused = 0; h.bits = 0;
+    h.sort.passes = 0; h.refused = 0; h.bits = 0;
     for (int a = 0; a < 3; ++a) { h.shift[a] = 0; h.ext[a] = 0; }
     if (h.range_bad) { h.refused = kVsRefusedRange; return; }
-    if (h.lo[0] > h.hi[0]) { h.passes = 1; return; }      // no finite row: the first pass still runs and counts none kept
+    if (h.lo[0] > h.hi[0]) { h.sort.passes = 1; return; }      // no finite row: the first pass still runs and counts none kept
     int at = 0;
     for (int a = 0; a < 3; ++a) {
         const unsigned long long span = kind == kVsV3 ? (unsigned long long)((float)h.hi[a] - (float)h.lo[a])
@@ -97,7 +96,7 @@ __device__ inline void vs_layout(VsHdr& h, int kind) {
     }
     h.bits = at;
     if (at > 64) { h.refused = kVsRefusedBits; return; }
-    h.passes = at ? (at + 7) / 8 : 1;
+    h.sort.passes = at ? (at + 7) / 8 : 1;
 }
 
 __global__ __launch_bounds__(256) void vs_key_kernel(const float* __restrict__ pts, uint32_t sf, uint32_t n, float gs, float inv, int kind,
@@ -108,12 +107,12 @@ __global__ __launch_bounds__(256) void vs_key_kernel(const float* __restrict__ p
         vs_layout(h, kind);
         sh = h;
         if (blockIdx.x == 0) {      // (every block computes the same from the same box; the later launches read it from here)
-            hdr->passes = h.passes; hdr->refused = h.refused; hdr->bits = h.bits;
+            hdr->sort.passes = h.sort.passes; hdr->refused = h.refused; hdr->bits = h.bits;
             for (int a = 0; a < 3; ++a) { hdr->shift[a] = h.shift[a]; hdr->ext[a] = h.ext[a]; }
         }
     }
     __syncthreads();
-    if (sh.passes == 0) return;
+    if (sh.sort.passes == 0) return;
     const uint32_t base = blockIdx.x * kVsTile;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
@@ -139,11 +138,11 @@ __global__ __launch_bounds__(256) void vs_key_kernel(const float* __restrict__ p
 __device__ inline uint32_t vs_digit(unsigned long long k, uint32_t r, int d) { return (d == 0 && r == kVsDropped) ? 256u : (uint32_t)((k >> (8 * d)) & 255ull); }
 
 // Digit pass d, first launch: per tile of 2048 rows the count of every digit value, to hist[bin][tile].
-__global__ __launch_bounds__(256) void vs_hist_kernel(const VsHdr* __restrict__ hdr, int d, uint32_t n, const unsigned long long* __restrict__ key,
+__global__ __launch_bounds__(256) void vs_hist_kernel(const KeySortCtl* __restrict__ ctl, int d, uint32_t n, const unsigned long long* __restrict__ key,
                                                       const uint32_t* __restrict__ row, uint32_t* __restrict__ hist) {
     __shared__ uint32_t sh[kVsBins];
-    if (d >= hdr->passes) return;
-    const uint32_t n_cur = d == 0 ? n : hdr->kept;
+    if (d >= ctl->passes) return;
+    const uint32_t n_cur = d == 0 ? n : ctl->kept;
     const uint32_t tiles = (uint32_t)(((size_t)n_cur + kVsTile - 1) / kVsTile);
     if (blockIdx.x >= tiles) return;
     for (int b = threadIdx.x; b < kVsBins; b += 256) sh[b] = 0;
@@ -180,24 +179,24 @@ __device__ inline uint32_t vs_scan_block(uint32_t* __restrict__ a, size_t m) {
 
 // Digit pass d, second launch: hist[bin][tile] -> where the rows of (bin, tile) go.  The first pass also learns the number of kept rows:
 // everything in front of the bin of the dropped ones.
-__global__ __launch_bounds__(kVsScan) void vs_scan_hist_kernel(VsHdr* __restrict__ hdr, int d, uint32_t n, uint32_t* __restrict__ hist) {
-    if (d >= hdr->passes) return;
-    const uint32_t n_cur = d == 0 ? n : hdr->kept;
+__global__ __launch_bounds__(kVsScan) void vs_scan_hist_kernel(KeySortCtl* __restrict__ ctl, int d, uint32_t n, uint32_t* __restrict__ hist) {
+    if (d >= ctl->passes) return;
+    const uint32_t n_cur = d == 0 ? n : ctl->kept;
     const uint32_t tiles = (uint32_t)(((size_t)n_cur + kVsTile - 1) / kVsTile);
     (void)vs_scan_block(hist, (size_t)kVsBins * tiles);
     __syncthreads();
-    if (d == 0 && threadIdx.x == 0) hdr->kept = tiles ? hist[(size_t)256 * tiles] : 0u;
+    if (d == 0 && threadIdx.x == 0) ctl->kept = tiles ? hist[(size_t)256 * tiles] : 0u;
 }
 
 // Digit pass d, third launch: the stable scatter.  A tile's rows go round by round (256 rows each), wave by wave, lane by lane: a row's place is
 // the start of its (bin, tile), plus the rows of its digit in earlier rounds, in lower waves of its round and in lower lanes of its wave.
-__global__ __launch_bounds__(256) void vs_scatter_kernel(const VsHdr* __restrict__ hdr, int d, uint32_t n, const unsigned long long* __restrict__ key,
+__global__ __launch_bounds__(256) void vs_scatter_kernel(const KeySortCtl* __restrict__ ctl, int d, uint32_t n, const unsigned long long* __restrict__ key,
                                                          const uint32_t* __restrict__ row, const uint32_t* __restrict__ hist,
                                                          unsigned long long* __restrict__ key_out, uint32_t* __restrict__ row_out) {
     __shared__ uint32_t sh_base[kVsBins];
     __shared__ uint32_t sh_cnt[4][kVsBins];
-    if (d >= hdr->passes) return;
-    const uint32_t n_cur = d == 0 ? n : hdr->kept;
+    if (d >= ctl->passes) return;
+    const uint32_t n_cur = d == 0 ? n : ctl->kept;
     const uint32_t tiles = (uint32_t)(((size_t)n_cur + kVsTile - 1) / kVsTile);
     if (blockIdx.x >= tiles) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -255,11 +254,11 @@ __global__ __launch_bounds__(256) void vs_mark_kernel(const VsHdr* __restrict__ 
                                                       const unsigned long long* __restrict__ key1, const uint32_t* __restrict__ row0,
                                                       const uint32_t* __restrict__ row1, const float* __restrict__ pts, uint32_t sf, int intensity_at,
                                                       int kind, uint32_t* __restrict__ first, VsLead* __restrict__ lead) {
-    const uint32_t kept = hdr->kept;
+    const uint32_t kept = hdr->sort.kept;
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if ((j & ~63u) >= kept) return;      // (wave-uniform)
-    const unsigned long long* key = (hdr->passes & 1) ? key1 : key0;
-    const uint32_t* row = (hdr->passes & 1) ? row1 : row0;
+    const unsigned long long* key = (hdr->sort.passes & 1) ? key1 : key0;
+    const uint32_t* row = (hdr->sort.passes & 1) ? row1 : row0;
     const int lane = threadIdx.x & 63;
     const bool valid = j < kept;
     const unsigned long long k = valid ? key[j] : 0ull;
@@ -281,9 +280,9 @@ __global__ __launch_bounds__(256) void vs_count_kernel(const VsHdr* __restrict__
                                                        const unsigned long long* __restrict__ key1, const uint32_t* __restrict__ first, int kind,
                                                        uint32_t max_pts, uint32_t min_pts, uint32_t* __restrict__ cnt, uint32_t* __restrict__ tile) {
     __shared__ uint32_t sh[4];
-    const uint32_t kept = hdr->kept;
+    const uint32_t kept = hdr->sort.kept;
     if ((size_t)blockIdx.x * 256 >= kept) return;      // (block-uniform)
-    const unsigned long long* key = (hdr->passes & 1) ? key1 : key0;
+    const unsigned long long* key = (hdr->sort.passes & 1) ? key1 : key0;
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const bool valid = j < kept;
@@ -304,7 +303,7 @@ __global__ __launch_bounds__(256) void vs_count_kernel(const VsHdr* __restrict__
 }
 
 __global__ __launch_bounds__(kVsScan) void vs_scan_tile_kernel(VsHdr* __restrict__ hdr, uint32_t* __restrict__ tile) {
-    const uint32_t total = vs_scan_block(tile, ((size_t)hdr->kept + 255) / 256);
+    const uint32_t total = vs_scan_block(tile, ((size_t)hdr->sort.kept + 255) / 256);
     if (threadIdx.x == 0) hdr->total = total;
 }
 
@@ -315,7 +314,7 @@ __device__ inline uint32_t vs_out_pos(const VsHdr* __restrict__ hdr, const uint3
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         VsResult r;
-        r.count = hdr->total; r.kept = hdr->kept; r.passes = hdr->passes; r.refused = hdr->refused; r.bits = hdr->bits; r.pad_ = 0;
+        r.count = hdr->total; r.kept = hdr->sort.kept; r.passes = hdr->sort.passes; r.refused = hdr->refused; r.bits = hdr->bits; r.pad_ = 0;
         for (int a = 0; a < 3; ++a) r.ext[a] = hdr->ext[a];
         *result = r;
     }
@@ -324,7 +323,7 @@ __device__ inline uint32_t vs_out_pos(const VsHdr* __restrict__ hdr, const uint3
     __syncthreads();
     uint32_t pos = (uint32_t)__popcll(em & ((1ull << lane) - 1ull));
     for (int w = 0; w < wave; ++w) pos += sh[w];
-    return pos + ((size_t)blockIdx.x * 256 < hdr->kept ? tile[blockIdx.x] : 0u);
+    return pos + ((size_t)blockIdx.x * 256 < hdr->sort.kept ? tile[blockIdx.x] : 0u);
 }
 
 // Run pass of V3, last launch, a thread per sorted row: the start of a voxel gets the sum of its run -- its wave's part by a backward segmented scan,
@@ -335,8 +334,8 @@ __global__ __launch_bounds__(256) void vs_emit_v3_kernel(const VsHdr* __restrict
                                                          const uint32_t* __restrict__ first, const VsLead* __restrict__ lead,
                                                          const uint32_t* __restrict__ tile, float* __restrict__ out, uint32_t out_capacity,
                                                          VsResult* __restrict__ result) {
-    const uint32_t kept = hdr->kept;
-    const uint32_t* row = (hdr->passes & 1) ? row1 : row0;
+    const uint32_t kept = hdr->sort.kept;
+    const uint32_t* row = (hdr->sort.passes & 1) ? row1 : row0;
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const bool valid = j < kept;
@@ -377,8 +376,8 @@ __global__ __launch_bounds__(256) void vs_emit_v2_kernel(const VsHdr* __restrict
                                                          const float* __restrict__ pts, uint32_t sf, uint32_t max_pts, const uint32_t* __restrict__ cnt,
                                                          const uint32_t* __restrict__ tile, float* __restrict__ out, uint32_t out_capacity,
                                                          VsResult* __restrict__ result) {
-    const uint32_t kept = hdr->kept;
-    const uint32_t* row = (hdr->passes & 1) ? row1 : row0;
+    const uint32_t kept = hdr->sort.kept;
+    const uint32_t* row = (hdr->sort.passes & 1) ? row1 : row0;
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     const uint32_t c = j < kept ? cnt[j] : 0u;
     const uint32_t pos = vs_out_pos(hdr, tile, c > 0u, result);
@@ -393,12 +392,28 @@ __global__ __launch_bounds__(256) void vs_emit_v2_kernel(const VsHdr* __restrict
     o[0] = __float_as_uint(sx / fm); o[1] = __float_as_uint(sy / fm); o[2] = __float_as_uint(sz / fm);
 }
 
+// The stable sort of n (key, row) pairs on its own, for every user of it (the voxel filters here, the sparse target index of sparse_index.hip).
+// In: the pairs in key[0] / row[0], rows marked kVsDropped leave in the first pass; ctl->passes = the digit passes the keys' used bits reach, set on
+// the device by the launch in front (0: nothing runs).  All eight passes are queued and those beyond ctl->passes leave at once.  Out: the
+// sorted pairs in key[ctl->passes & 1] / row[ctl->passes & 1], ctl->kept = their number.
+size_t key_sort_hist_bytes(size_t n) { return (size_t)kVsBins * (n / kVsTile + 1) * sizeof(uint32_t); }
+void key_sort_launch(KeySortCtl* d_ctl, size_t n, unsigned long long* const key[2], uint32_t* const row[2], uint32_t* hist, hipStream_t s) {
+    const uint32_t n32 = (uint32_t)n;
+    const int tiles = (int)((n + kVsTile - 1) / kVsTile ? (n + kVsTile - 1) / kVsTile : 1);
+    for (int d = 0; d < kVsMaxPasses; ++d) {
+        const int from = d & 1, to = from ^ 1;
+        hipLaunchKernelGGL(vs_hist_kernel, dim3(tiles), dim3(256), 0, s, d_ctl, d, n32, key[from], row[from], hist);
+        hipLaunchKernelGGL(vs_scan_hist_kernel, dim3(1), dim3(kVsScan), 0, s, d_ctl, d, n32, hist);
+        hipLaunchKernelGGL(vs_scatter_kernel, dim3(tiles), dim3(256), 0, s, d_ctl, d, n32, key[from], row[from], hist, key[to], row[to]);
+    }
+}
+
 VsSizes voxel_sparse_bytes(size_t n) {
     VsSizes s;
     s.hdr = 256;
     s.key = (n + 1) * sizeof(unsigned long long);
     s.row = (n + 1) * sizeof(uint32_t);
-    s.hist = (size_t)kVsBins * (n / kVsTile + 1) * sizeof(uint32_t);
+    s.hist = key_sort_hist_bytes(n);
     s.cnt = (n + 1) * sizeof(uint32_t);
     s.first = (n / 64 + 1) * sizeof(uint32_t);
     s.lead = (n / 64 + 1) * sizeof(VsLead);
@@ -419,12 +434,7 @@ hipError_t voxel_sparse_launch(const VsBuffers& b, const float* d_pts, size_t st
     hipLaunchKernelGGL(vs_init_kernel, dim3(1), dim3(64), 0, s, hdr);
     hipLaunchKernelGGL(vs_box_kernel, dim3(tiles), dim3(256), 0, s, d_pts, sf, n32, leaf, inv, kind, hdr);
     hipLaunchKernelGGL(vs_key_kernel, dim3(tiles), dim3(256), 0, s, d_pts, sf, n32, leaf, inv, kind, hdr, b.key[0], b.row[0]);
-    for (int d = 0; d < kVsMaxPasses; ++d) {
-        const int from = d & 1, to = from ^ 1;
-        hipLaunchKernelGGL(vs_hist_kernel, dim3(tiles), dim3(256), 0, s, hdr, d, n32, b.key[from], b.row[from], b.hist);
-        hipLaunchKernelGGL(vs_scan_hist_kernel, dim3(1), dim3(kVsScan), 0, s, hdr, d, n32, b.hist);
-        hipLaunchKernelGGL(vs_scatter_kernel, dim3(tiles), dim3(256), 0, s, hdr, d, n32, b.key[from], b.row[from], b.hist, b.key[to], b.row[to]);
-    }
+    key_sort_launch(&hdr->sort, n, b.key, b.row, b.hist, s);
     hipLaunchKernelGGL(vs_mark_kernel, dim3(blocks), dim3(256), 0, s, hdr, b.key[0], b.key[1], b.row[0], b.row[1], d_pts, sf, intensity_at, kind, b.first,
                        static_cast<VsLead*>(b.lead));
     hipLaunchKernelGGL(vs_count_kernel, dim3(blocks), dim3(256), 0, s, hdr, b.key[0], b.key[1], b.first, kind, (uint32_t)max_voxel_pts,

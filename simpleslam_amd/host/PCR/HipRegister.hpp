@@ -479,6 +479,21 @@ public:
     void setInputCloud(const PC_cPtr& cloud) {
         if (pcr_set_target(h_, cloud->points.data(), cloud->size(), sizeof(PointXYZI), 0)) throw std::runtime_error(pcr_last_error(h_));
     }
+    // pcr_params.query_index: PCR_QUERY_INDEX_AUTO (the dense cell table wherever it holds every point, the sparse index for a target whose box
+    // cannot be tabulated) or PCR_QUERY_INDEX_SPARSE (always the sparse index); the same answers.  A value out of range throws.
+    void setQueryIndex(int query_index) {
+        pcr_params p;
+        if (pcr_get_params(h_, &p)) throw std::runtime_error(pcr_last_error(h_));
+        p.query_index = query_index;
+        if (pcr_set_params(h_, &p)) throw std::runtime_error(pcr_last_error(h_));
+    }
+    // the index that answered the last search: its kind (PCR_QUERY_INDEX_DENSE / _SPARSE; -1: none yet), its points, its bytes of device memory
+    struct QueryIndexInfo { int kind; size_t n_points, bytes; };
+    QueryIndexInfo queryIndexInfo() const {
+        QueryIndexInfo i{-1, 0, 0};
+        if (pcr_query_index_info(h_, &i.kind, &i.n_points, &i.bytes)) throw std::runtime_error(pcr_last_error(h_));
+        return i;
+    }
     size_t nearestKSearch(double* point, int k, std::vector<size_t>& k_indices, std::vector<double>& k_sqr_distances) const {
         const float q[4] = {(float)point[0], (float)point[1], (float)point[2], 0.f};
         std::vector<int64_t> idx((size_t)(k > 0 ? k : 0));

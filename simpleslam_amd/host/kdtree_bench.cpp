@@ -1,12 +1,12 @@
 // kdtree_bench.cpp -- counterpart of the reference's test/benchmark/kdtree.cpp:58-127 (Google Benchmark of PCL-FLANN vs nanoflann:
 // index build, k = 5 and radius queries) for the spatial index of this library:
-//   kdtree_bench <map.f32> [queries.f32] [repeats] [k radius]
+//   kdtree_bench <map.f32> [queries.f32] [repeats] [k radius [sparse]]
 // prints the build time of the uniform-grid index over the map (seconds, host clock around pcr_set_target) and the time per query of
 // one LOAM linearisation -- its 5-NN search inside the 1 m gate with the plane fit and the row (ns/query; the reference benchmarks one
 // query at the origin in a loop, a GPU answers a whole cloud of queries per call: the map's own points, or the given query cloud).
 // With k and radius two more lines follow: the general queries of the index, ungated and exact -- ns/query of pcr_knn at that k, and
 // ns/query and the mean number of neighbours of pcr_radius_search (sorted) at that radius, host clock around the call, best of
-// `repeats`.  The reference's nanoflann on the same map is timed by bench.py's cpu_baseline leg ("index": "nanoflann(_ref)") and by
+// `repeats`; a sixth argument `sparse` answers them from the sparse index (pcr_params.query_index) and says so in a fifth line.  The reference's nanoflann on the same map is timed by bench.py's cpu_baseline leg ("index": "nanoflann(_ref)") and by
 // scripts/knn_query_bench.py -- this program never touches the checker.
 #include <chrono>
 #include <cstdio>
@@ -28,7 +28,7 @@ static std::vector<float> load(const char* path) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s <map.f32> [queries.f32] [repeats] [k radius]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s <map.f32> [queries.f32] [repeats] [k radius [sparse]]\n", argv[0]); return 2; }
     try {
         const std::vector<float> map = load(argv[1]);
         const std::vector<float> qry = argc > 2 ? load(argv[2]) : map;
@@ -62,6 +62,9 @@ int main(int argc, char** argv) {
             const int k = std::atoi(argv[4]);
             const double radius = std::atof(argv[5]);
             PCR::PointCloudKdtree tree(h);
+            const bool sparse = argc > 6 && std::string(argv[6]) == "sparse";
+            if (argc > 6 && !sparse) throw std::runtime_error(std::string("unknown argument ") + argv[6] + " (sparse?)");
+            if (sparse) tree.setQueryIndex(PCR_QUERY_INDEX_SPARSE);
             std::vector<int64_t> idx;
             std::vector<double> d2;
             std::vector<uint64_t> offsets;
@@ -79,6 +82,13 @@ int main(int argc, char** argv) {
             std::printf("pcr_knn k = %d: %zu queries, %.1f ns/query\n", k, n_q, 1e9 * knn_s / (double)n_q);
             std::printf("pcr_radius_search r = %g: %zu queries, %.1f ns/query, mean count %.2f\n", radius, n_q, 1e9 * rad_s / (double)n_q,
                         n_q ? (double)idx.size() / (double)n_q : 0.0);
+            if (sparse) {
+                const PCR::PointCloudKdtree::QueryIndexInfo info = tree.queryIndexInfo();
+                unsigned long long sum = 0;      // (of the last search's indices: what a caller compares with another binding's answer)
+                for (int64_t i : idx) sum += (unsigned long long)i;
+                std::printf("query index: %s, %zu points, %zu bytes, radius index sum %llu\n", info.kind == PCR_QUERY_INDEX_SPARSE ? "sparse" : "dense",
+                            info.n_points, info.bytes, sum);
+            }
         }
         pcr_destroy(h);
     } catch (const std::exception& e) {

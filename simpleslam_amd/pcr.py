@@ -39,7 +39,7 @@ class PcrParams(C.Structure):
         ("record_trace", C.c_int32),
         ("index_no_hints", C.c_int32), ("ndt_evaluate_repeats", C.c_int32), ("loam_disable_cache", C.c_int32), ("record_timeline", C.c_int32),
         ("loam_coresident", C.c_int32), ("loam_clamp_margin_mm", C.c_int32), ("full_target", C.c_int32), ("host_optimiser", C.c_int32),
-        ("host_copy_xyz", C.c_int32),
+        ("host_copy_xyz", C.c_int32), ("query_index", C.c_int32),
         ("liorf_iters", C.c_int32), ("liorf_file_row", C.c_int32), ("liorf_knn_max_sq", C.c_double), ("liorf_plane_thresh", C.c_double), ("liorf_point_thresh", C.c_double),
         ("liorf_min_rows", C.c_int32), ("liorf_min_scan", C.c_int32), ("liorf_rot_conv_deg", C.c_double), ("liorf_trans_conv_cm", C.c_double),
         ("liorf_degenerate_eig", C.c_double),
@@ -55,6 +55,9 @@ VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = range(3)
 VGICP_DIRECT27, VGICP_DIRECT7, VGICP_DIRECT1, VGICP_DIRECT_RADIUS = range(4)
 # pcr_params.ndt_search (include/pcr_hip.h: PCR_NDT_*; pclomp::NeighborSearchMethod, ndt_omp.h:52-57).  NDT_KDTREE is refused.
 NDT_KDTREE, NDT_DIRECT26, NDT_DIRECT7, NDT_DIRECT1 = range(4)
+# pcr_params.query_index (include/pcr_hip.h: PCR_QUERY_INDEX_*), and the kinds queryIndexInfo() reports
+QUERY_INDEX_AUTO, QUERY_INDEX_SPARSE = 0, 1
+QUERY_INDEX_DENSE = 0
 
 
 class PcrStats(C.Structure):
@@ -80,7 +83,7 @@ ABI_SYMBOLS = [
     "pcr_ndt_opt_create_device", "pcr_ndt_opt_set_replay", "pcr_ndt_opt_state", "pcr_ndt_opt_tables", "pcr_ndt_opt_hessian",
     "pcr_vgicp_opt_create", "pcr_vgicp_opt_destroy", "pcr_vgicp_opt_request", "pcr_vgicp_opt_feed", "pcr_vgicp_opt_result",
     "pcr_sc_default_params", "pcr_sc_create", "pcr_sc_destroy", "pcr_sc_last_error", "pcr_sc_size", "pcr_sc_add", "pcr_sc_descriptor", "pcr_sc_distance",
-    "pcr_sc_query", "pcr_knn", "pcr_radius_search", "pcr_fitness_batch", "pcr_reloc_default_params", "pcr_reloc_hypotheses", "pcr_relocalize",
+    "pcr_sc_query", "pcr_knn", "pcr_radius_search", "pcr_query_index_info", "pcr_fitness_batch", "pcr_reloc_default_params", "pcr_reloc_hypotheses", "pcr_relocalize",
     "pcr_sc_distances", "pcr_global_reloc_default_params", "pcr_global_reloc_hypotheses", "pcr_relocalize_global",
     "pcr_sc_rank_stored", "pcr_sc_shift_yaw", "pcr_sc_add_keyframes",
     "pcr_liorf_pose_to_6dof", "pcr_liorf_6dof_to_pose", "pcr_liorf_linearize", "pcr_liorf_result",
@@ -302,6 +305,7 @@ def load_library():
     L.pcr_knn.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int64), dp]
     L.pcr_radius_search.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), dp,
                                     C.POINTER(C.c_size_t)]
+    L.pcr_query_index_info.argtypes = [vp, ip, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.pcr_fitness_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, dp, C.c_size_t, C.c_double, C.c_size_t, dp, C.POINTER(C.c_int64)]
     L.pcr_reloc_default_params.argtypes = [C.POINTER(RelocParams)]
     L.pcr_reloc_default_params.restype = None
@@ -762,6 +766,13 @@ class PointCloudRegister:
             self._check(self._lib.pcr_radius_search(self._h, p, n, s, dev, float(radius), int(bool(sorted)), total.value, offsets.ctypes.data_as(op),
                                                     idx.ctypes.data_as(ip), d2.ctypes.data_as(dp), C.byref(total)))
         return offsets, idx, d2
+
+    def queryIndexInfo(self):
+        """pcr_query_index_info -> dict(kind, n_points, bytes): the index that answered the last knn / radiusSearch ("dense", "sparse", or None
+        when none has been answered since the target was set), the points it holds and the device memory it occupies."""
+        kind, n, b = C.c_int(-1), C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.pcr_query_index_info(self._h, C.byref(kind), C.byref(n), C.byref(b)))
+        return dict(kind={QUERY_INDEX_DENSE: "dense", QUERY_INDEX_SPARSE: "sparse"}.get(kind.value), n_points=int(n.value), bytes=int(b.value))
 
     def relocalize(self, src, pose, **params):
         """pcr_relocalize from the coarse pose `pose` (4x4, updated in place as align() does) against the kept target (setTarget):
