@@ -273,7 +273,9 @@ int pcr_invalidate_target(pcr_handle* h);
  * every rank takes part in the sum.)  The distances are PCL's float distances bit for bit; only the order of the double sum differs.
  * A voxel lattice that holds the scan's region only hands the search to the covariance search grid, which holds every point.  An index
  * cut to a region (a target too spread out for the dense tables: its bulk, or the room around a scan) answers only when every source point's
- * nearest indexed point is provably nearer than the cut faces; otherwise this returns -1 and pcr_last_error names the cut. */
+ * nearest indexed point is provably nearer than the cut faces; otherwise the score is taken on the sparse index of the kept target, which
+ * holds every point (pcr_fitness_gated says how), and only where that index cannot be had this returns -1 and pcr_last_error names the cut
+ * and the sparse index's reason.  pcr_params.query_index = PCR_QUERY_INDEX_SPARSE: always on the sparse index. */
 double pcr_fitness(pcr_handle* h);
 
 /* ---- introspection used by tests and bench.py ---- */
@@ -882,8 +884,18 @@ int pcr_get_params(const pcr_handle* h, pcr_params* out);
  * handle's staging copy); a DEVICE target is the caller's and may be gone: the call fails and says so (pcr_set_target, or
  * pcr_params.full_target = 1, avoid it).
  * An index cut to a region (a target too spread out for the dense tables: its bulk, or the room around a scan): when a source point's
- * nearest indexed point is not provably nearer than the cut faces (and than the gate), the call fails, score = -1, *n_in = 0, and the
- * message names the cut -- it never returns the score of the part that was indexed. */
+ * nearest indexed point is not provably nearer than the cut faces (and than the gate), the dense index cannot answer, and the score is
+ * taken again on the SPARSE index of the kept target (below, at the neighbour queries: built by the first call that needs it, kept until
+ * the target changes), which holds every point: the same float distances, the same gate, the sums in the same order -- the number the
+ * dense index would have given had it held the whole target.  It never returns the score of the part that was indexed.  Where the sparse
+ * index cannot be had -- the target was a caller's device buffer that the handle did not copy (pcr_scan2map_device, pcr_scan2map_submap),
+ * or its cell box needs more than 63 key bits -- the call fails as it used to: score = -1, *n_in = 0, and the message names the cut and
+ * then the sparse index's reason.
+ * pcr_params.query_index governs the scores as it governs the queries: under PCR_QUERY_INDEX_SPARSE pcr_fitness, pcr_fitness_gated,
+ * pcr_fitness_batch and the scores of pcr_relocalize / pcr_relocalize_global always run on the sparse index (a handle of any method; bit
+ * for bit the dense index's scores wherever that one answers); under AUTO they run on the dense index as ever, with the same launches, and
+ * go to the sparse one only for what a cut dense index refuses.  Sharded handles and handles with a query tile are not served by the
+ * sparse index: their refusals stand.  pcr_query_index_info says which index answered the last score. */
 int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double pose[16],
                       double max_sq, double* score, int64_t* n_in);
 
@@ -929,9 +941,10 @@ int pcr_knn(pcr_handle* h, const void* queries, size_t n_q, size_t stride_bytes,
 int pcr_radius_search(pcr_handle* h, const void* queries, size_t n_q, size_t stride_bytes, int on_device, double radius, int sorted,
                       size_t capacity, uint64_t* offsets, int64_t* idx, double* d2, size_t* n_total);
 
-/* Which index answered the last pcr_knn / pcr_radius_search of the handle: *kind = PCR_QUERY_INDEX_DENSE or PCR_QUERY_INDEX_SPARSE (-1: no
- * query has been answered since the target was set), *n_points = the points it holds (the finite ones), *bytes = the device memory it
- * occupies (dense: the sorted points and the cell table; sparse: 24 bytes per point).  Any pointer may be NULL. */
+/* Which index answered the last pcr_knn / pcr_radius_search or the last fitness score (pcr_fitness, pcr_fitness_gated, pcr_fitness_batch,
+ * the scores of a relocalisation) of the handle: *kind = PCR_QUERY_INDEX_DENSE or PCR_QUERY_INDEX_SPARSE (-1: none has been answered
+ * since the target was set; a batch says SPARSE when any of its poses went there), *n_points = the points it holds (the finite ones),
+ * *bytes = the device memory it occupies (dense: the sorted points and the cell table; sparse: 24 bytes per point).  Any pointer may be NULL. */
 int pcr_query_index_info(pcr_handle* h, int* kind, size_t* n_points, size_t* bytes);
 
 /* ---- Relocalisation from a coarse pose ----------------------------------------------------------------------------------------------
@@ -951,8 +964,9 @@ int pcr_query_index_info(pcr_handle* h, int* kind, size_t* n_points, size_t* byt
  * score_points: 0, or a value >= n_src, scores every point; otherwise the points i_j = floor(j n_src / score_points) (64-bit integer
  * arithmetic), j = 0 .. score_points - 1, indexed on the device in place.
  * The index searched is pcr_fitness_gated's (a region-only lattice: VGICP's covariance grid, or an NDT host target indexed again).
- * An index cut to a region: a pose with a point whose nearest target point cannot be proved gets scores[k] = -1, n_in[k] = -1 (where
- * pcr_fitness_gated fails); the others are scored, and the call returns 0.
+ * An index cut to a region: exactly the poses with a point whose nearest target point the dense index cannot prove are scored again on
+ * the sparse index (pcr_fitness_gated's rule; bit for bit its result, whichever index answered either).  Only where the sparse index cannot
+ * be had do they get scores[k] = -1, n_in[k] = -1 (where pcr_fitness_gated fails); the others are scored, and the call returns 0.
  * K <= PCR_RELOC_MAX_POSES, and at most PCR_BATCH_MAX_POINTS points are scored per pose (n_src, or score_points when it is smaller;
  * more is refused with a message).  Sharded handles and handles with a query tile (pcr_set_query_tile) are refused. */
 int pcr_fitness_batch(pcr_handle* h, const void* src, size_t n_src, size_t stride_bytes, int on_device, const double* poses, size_t K,

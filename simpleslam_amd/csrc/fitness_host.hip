@@ -52,6 +52,17 @@ extern "C" double pcr_fitness(pcr_handle* h) {
         h->fitness = m.fit_none;
         if (h->target_ready && h->fit_n > 0) {
             if (set_device(h) || ensure_out32(h)) return -1.0;
+            // the score of the kept scan on the sparse index, which holds every point: where pcr_params.query_index asks for it, and below where
+            // the dense index was cut and cannot answer (n_viol: for how many points)
+            auto on_sparse = [&](double n_viol) {
+                if (sparse_fitness_run(h, "pcr_fitness", n_viol, h->fit_src.as<float>(), h->fit_n, h->fit_stride, h->fit_pose, m.fit_max_sq)) {
+                    h->fitness = -1.0;
+                    return -1.0;
+                }
+                h->fitness = h->out32.host[1] > 0 ? h->out32.host[0] / h->out32.host[1] : m.fit_none;
+                return h->fitness;
+            };
+            if (scores_on_sparse(h)) return on_sparse(0.0);
             h->seq += 1.0;
             // (a lattice that holds the scan's region only cannot answer a nearest-neighbour question; the grid its covariances were searched on holds every point)
             const bool full_search_grid = h->cov_l1.valid && !h->cov_l1.filtered;
@@ -64,11 +75,8 @@ extern "C" double pcr_fitness(pcr_handle* h) {
             if (fitness_launch(fit_grid, h->fit_src.as<float>(), h->fit_n, h->fit_stride, h->fit_pose, m.fit_max_sq, h->vg_partials.as<double>(),
                                h->out32.dev, h->stream, h->seq, nullptr) != hipSuccess) { h->err = "fitness_launch failed"; return -1.0; }
             if (wait_result(h, &h->out32.host[31], h->seq)) return -1.0;
-            if (h->out32.host[2] > 0) {      // (fitness_kernel: points whose nearest target point may lie beyond a cut face of the index)
-                h->err = cut_fitness_message(h->out32.host[2]);
-                h->fitness = -1.0;
-                return -1.0;
-            }
+            // (fitness_kernel: points whose nearest target point may lie beyond a cut face of the index)
+            if (h->out32.host[2] > 0) return on_sparse(h->out32.host[2]);
             h->fitness = h->out32.host[1] > 0 ? h->out32.host[0] / h->out32.host[1] : m.fit_none;
         }
     }

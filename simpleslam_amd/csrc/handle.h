@@ -407,6 +407,13 @@ void arm_fitness(pcr_handle* h, const double pose[16], size_t n, size_t stride_f
 std::string cut_fitness_message(double n);
 // the kept target has changed or is gone: the sparse index built from it goes too (capi: every entry point that sets or drops a target)
 void drop_query_index(pcr_handle* h);
+// pcr_params.query_index = SPARSE governs this handle's scores: always the sparse index (not a sharded handle, not one with a query tile)
+inline bool scores_on_sparse(const pcr_handle* h) { return h->prm.query_index == PCR_QUERY_INDEX_SPARSE && !sharded(h) && !h->use_tile; }
+// One pose scored on the sparse index of the kept target (built when the handle has none), the sums left in h->out32.host[0..2] as fitness_launch
+// leaves them.  n_viol > 0: the dense kernel could not answer for that many points (a cut index) and this is the fall-back -- where the sparse
+// index cannot be had either, the message is cut_fitness_message's followed by the index's own reason; n_viol = 0: the caller asked for the index.
+int sparse_fitness_run(pcr_handle* h, const char* who, double n_viol, const float* d_src, size_t n_src, size_t stride_floats, const double pose[16],
+                       double max_sq);
 
 // How a device-resident optimiser's passes (run_lsq, run_ndt) are queued ahead of the progress word of its result block
 struct PaceRule {

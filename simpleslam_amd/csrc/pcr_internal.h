@@ -344,6 +344,14 @@ hipError_t fitness_launch(const GridIndex& grid, const float* d_src, size_t n_sr
 uint32_t vgicp_blocks(uint32_t n_src);
 // the fold of a pass's [block][32] rows into d_out32 (vgicp.hip: sum_partials_kernel), `seq` written last into d_out32[31]
 hipError_t sum_partials_launch(const double* d_partials, uint32_t nblocks, double* d_out32, hipStream_t s, double seq = 0.0);
+// the same score and the batched one (fitness_batch_launch below) on the sparse target index (sparse_fitness.hip): the same launch shape, the same
+// order of summation and the same outputs, out32[2] / RelocSum::viol always 0 -- the index holds every finite point of the target
+struct RelocPart;
+struct RelocSum;
+hipError_t sparse_fitness_launch(const sw::View& v, const float* d_src, size_t n_src, size_t stride_floats, const double pose[16], double max_range,
+                                 double* d_partials, double* d_out32, hipStream_t s, double seq = 0.0);
+hipError_t sparse_fitness_batch_launch(const sw::View& v, const float* d_src, size_t n_src, size_t stride_floats, size_t m, const float* d_poses,
+                                       size_t n_poses, double max_sq, RelocPart* d_part, RelocSum* d_out, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // GICP (gicp.hip): fast_gicp::FastGICP, correspondences by exact nearest neighbour
@@ -413,6 +421,8 @@ int graph_device(const pcr_graph* g);
 struct RelocSum { double sum; unsigned long long cnt, viol, pad_; };
 hipError_t fitness_batch_launch(const GridIndex& grid, const float* d_src, size_t n_src, size_t stride_floats, size_t m, const float* d_poses,
                                 size_t n_poses, double max_sq, RelocPart* d_part, RelocSum* d_out, hipStream_t s);
+// its second launch alone: d_part[pose][chunk] folded in chunk order into d_out[pose]
+hipError_t fitness_batch_reduce_launch(const RelocPart* d_part, size_t n_poses, uint32_t chunks, RelocSum* d_out, hipStream_t s);
 
 // pcr_knn / pcr_radius_search (knn_query.hip): exact queries in f64 on an index that holds every point of its cloud (any lattice kind; the
 // caller has checked the header: not overflowing, stale or cut).  d_idx / d_d2 of the k-NN: n_q x k, ascending by (d2, index), tails -1 / +inf.

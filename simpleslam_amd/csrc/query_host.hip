@@ -66,7 +66,43 @@ int fit_grid_for(pcr_handle* h, const GridIndex** out) {
     return 0;
 }
 
+int sparse_index_for(pcr_handle* h, const char* who);      // (below, with the queries)
+
+// pcr_query_index_info after a score or a query: the index that answered
+void note_dense_index(pcr_handle* h, const GridIndex& g) {
+    h->q.last_kind = PCR_QUERY_INDEX_DENSE; h->q.last_points = g.n_points;
+    h->q.last_bytes = g.sorted.cap + g.cell_start.cap + g.header.cap;
+}
+void note_sparse_index(pcr_handle* h) {
+    h->q.last_kind = PCR_QUERY_INDEX_SPARSE; h->q.last_points = h->q.sparse.view.n;
+    h->q.last_bytes = h->q.sparse.keys.cap + h->q.sparse.pts.cap;
+}
+
+// The sparse index for a score.  n_viol > 0: the fall-back of a score the cut dense index refused for that many points; an index that cannot be had
+// (the target was a caller's device buffer, a key of more than 63 bits) then leaves the refusal standing, with its own reason behind it.
+int sparse_index_for_score(pcr_handle* h, const char* who, double n_viol) {
+    if (!sparse_index_for(h, who)) return 0;
+    if (n_viol > 0) h->err = cut_fitness_message(n_viol) + "; and the sparse index, which holds every point, cannot be had: " + h->err;
+    return 1;
+}
+
 }  // namespace
+
+namespace pcr {
+namespace host {
+
+int sparse_fitness_run(pcr_handle* h, const char* who, double n_viol, const float* d_src, size_t n_src, size_t stride_floats, const double pose[16],
+                       double max_sq) {
+    if (sparse_index_for_score(h, who, n_viol) || ensure_out32(h)) return 1;
+    h->seq += 1.0;
+    H_TRY(sparse_fitness_launch(h->q.sparse.view, d_src, n_src, stride_floats, pose, max_sq, h->vg_partials.as<double>(), h->out32.dev, h->stream, h->seq));
+    if (wait_result(h, &h->out32.host[31], h->seq)) return 1;
+    note_sparse_index(h);
+    return 0;
+}
+
+}  // namespace host
+}  // namespace pcr
 
 extern "C" {
 
@@ -79,9 +115,21 @@ int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t strid
     if (check_stride(h, stride_bytes) || set_device(h)) return 1;
     if (!h->have_target || !h->grid.valid) return fail(h, "no target: register a scan or call pcr_set_target first");
     if (n_src > kMaxPoints) return fail(h, "source cloud too large");
+    const float* d_src = (const float*)src;
+    // the score as read from h->out32.host, whichever index left it there
+    auto answer = [&]() {
+        const double cnt = h->out32.host[1];
+        *score = cnt > 0 ? h->out32.host[0] / cnt : -1.0;      // align.cpp:56-59
+        if (n_in) *n_in = (int64_t)cnt;
+    };
+    if (scores_on_sparse(h)) {
+        if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
+        if (sparse_fitness_run(h, "pcr_fitness_gated", 0.0, d_src, n_src, stride_bytes / 4, pose, max_sq)) return 1;
+        answer();
+        return 0;
+    }
     const GridIndex* fit_grid = nullptr;
     if (fit_grid_for(h, &fit_grid)) return 1;
-    const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
     if (ensure_out32(h)) return 1;
     FitTile ft;
@@ -96,11 +144,17 @@ int pcr_fitness_gated(pcr_handle* h, const void* src, size_t n_src, size_t strid
                          h->use_tile ? &ft : nullptr));
     if (wait_result(h, &h->out32.host[31], h->seq)) return 1;
     if (sharded(h) && ranks_allreduce(h, h->out32.host, 3)) return 1;
-    const double cnt = h->out32.host[1];
-    *score = cnt > 0 ? h->out32.host[0] / cnt : -1.0;      // align.cpp:56-59
-    if (n_in) *n_in = (int64_t)cnt;
+    answer();
     if (h->use_tile && h->out32.host[2] > 0) return fail(h, "sharded fitness: a source point's nearest map point may lie beyond this rank's halo");
-    if (h->out32.host[2] > 0) { *score = -1.0; if (n_in) *n_in = 0; return fail(h, cut_fitness_message(h->out32.host[2])); }
+    if (h->out32.host[2] > 0) {
+        // the index was cut and a nearest neighbour may lie in what it left out: the sparse index holds every point (a sharded handle has none)
+        *score = -1.0; if (n_in) *n_in = 0;
+        if (sharded(h)) return fail(h, cut_fitness_message(h->out32.host[2]));
+        if (sparse_fitness_run(h, "pcr_fitness_gated", h->out32.host[2], d_src, n_src, stride_bytes / 4, pose, max_sq)) return 1;
+        answer();
+        return 0;
+    }
+    note_dense_index(h, *fit_grid);
     return 0;
 }
 
@@ -159,38 +213,74 @@ int batch_points_check(pcr_handle* h, size_t n_src, size_t score_points) {
     return 0;
 }
 
-// pcr_fitness_batch on a device source (arguments checked): poses in groups whose partials stay within kPartMax entries.
-int fitness_batch_run(pcr_handle* h, const GridIndex& grid, const float* d_src, size_t n_src, size_t stride_floats, const double* poses, size_t K,
-                      double max_sq, size_t score_points, double* scores, int64_t* n_in) {
+// One pass of pcr_fitness_batch over the poses which[0 .. count) (nullptr: poses 0 .. count - 1), in groups whose partials stay within kPartMax
+// entries: on the dense index `grid`, or on the handle's sparse index (grid = nullptr).  A pose the dense kernel cannot answer (a cut index) gets
+// (-1, -1) and is listed in *refused.
+int fitness_batch_pass(pcr_handle* h, const GridIndex* grid, const float* d_src, size_t n_src, size_t stride_floats, size_t m, const double* poses,
+                       const size_t* which, size_t count, double max_sq, double* scores, int64_t* n_in, std::vector<size_t>* refused) {
     static constexpr size_t kPartMax = size_t(1) << 21, kGroupMax = 16384;
-    const size_t m = score_points == 0 || score_points >= n_src ? n_src : score_points;
-    if (batch_points_check(h, n_src, score_points)) return 1;
     const size_t chunks = std::max<size_t>((m + 255) / 256, 1);      // <= 2^18
     const size_t group = std::min(kGroupMax, kPartMax / chunks / 8 * 8);      // >= 8: group x chunks <= kPartMax
     std::vector<float> pf;
     std::vector<RelocSum> sums;
-    for (size_t k0 = 0; k0 < K; k0 += group) {
-        const size_t g = std::min(group, K - k0);
+    for (size_t k0 = 0; k0 < count; k0 += group) {
+        const size_t g = std::min(group, count - k0);
         pf.assign(g * 16, 0.f);
-        for (size_t q = 0; q < g * 16; ++q) pf[q] = (float)poses[k0 * 16 + q];
+        for (size_t q = 0; q < g; ++q) {
+            const double* P = poses + (which ? which[k0 + q] : k0 + q) * 16;
+            for (int e = 0; e < 16; ++e) pf[q * 16 + e] = (float)P[e];
+        }
         sums.resize(g);
         H_TRY(h->q.rl_poses.reserve(g * 16 * sizeof(float)));
         H_TRY(h->q.rl_part.reserve(g * chunks * sizeof(RelocPart)));
         H_TRY(h->q.rl_out.reserve(g * sizeof(RelocSum)));
         H_TRY(hipMemcpyAsync(h->q.rl_poses.p, pf.data(), g * 16 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        H_TRY(fitness_batch_launch(grid, d_src, n_src, stride_floats, m, h->q.rl_poses.as<float>(), g, max_sq, h->q.rl_part.as<RelocPart>(),
-                                   h->q.rl_out.as<RelocSum>(), h->stream));
+        if (grid) H_TRY(fitness_batch_launch(*grid, d_src, n_src, stride_floats, m, h->q.rl_poses.as<float>(), g, max_sq, h->q.rl_part.as<RelocPart>(),
+                                             h->q.rl_out.as<RelocSum>(), h->stream));
+        else H_TRY(sparse_fitness_batch_launch(h->q.sparse.view, d_src, n_src, stride_floats, m, h->q.rl_poses.as<float>(), g, max_sq,
+                                               h->q.rl_part.as<RelocPart>(), h->q.rl_out.as<RelocSum>(), h->stream));
         H_TRY(hipMemcpyAsync(sums.data(), h->q.rl_out.p, g * sizeof(RelocSum), hipMemcpyDeviceToHost, h->stream));
         H_TRY(hipStreamSynchronize(h->stream));
         for (size_t q = 0; q < g; ++q) {
             const RelocSum& r = sums[q];
-            if (r.viol > 0) { scores[k0 + q] = -1.0; n_in[k0 + q] = -1; continue; }      // (pcr_fitness_gated fails for this pose: cut_fitness_message)
+            const size_t at = which ? which[k0 + q] : k0 + q;
+            if (r.viol > 0) { scores[at] = -1.0; n_in[at] = -1; refused->push_back(at); continue; }
             const double cnt = (double)r.cnt;
-            scores[k0 + q] = cnt > 0 ? r.sum / cnt : -1.0;
-            n_in[k0 + q] = (int64_t)r.cnt;
+            scores[at] = cnt > 0 ? r.sum / cnt : -1.0;
+            n_in[at] = (int64_t)r.cnt;
         }
     }
     return 0;
+}
+
+// pcr_fitness_batch on a device source (arguments checked).  grid: the dense index (score_grid_for), every pose scored on it as ever, and exactly
+// the poses it refuses -- a cut index, a nearest neighbour that may lie in what was cut off -- scored again on the sparse index, which holds every
+// point; where that index cannot be had they keep (-1, -1), as pcr_fitness_gated keeps its refusal.  grid = nullptr (pcr_params.query_index =
+// SPARSE): every pose on the sparse index.
+int fitness_batch_run(pcr_handle* h, const GridIndex* grid, const float* d_src, size_t n_src, size_t stride_floats, const double* poses, size_t K,
+                      double max_sq, size_t score_points, double* scores, int64_t* n_in) {
+    const size_t m = score_points == 0 || score_points >= n_src ? n_src : score_points;
+    if (batch_points_check(h, n_src, score_points)) return 1;
+    std::vector<size_t> refused, none;
+    if (grid) {
+        if (fitness_batch_pass(h, grid, d_src, n_src, stride_floats, m, poses, nullptr, K, max_sq, scores, n_in, &refused)) return 1;
+        note_dense_index(h, *grid);
+        if (refused.empty()) return 0;
+        if (sparse_index_for(h, "pcr_fitness_batch")) { h->err.clear(); return 0; }
+    } else if (sparse_index_for(h, "pcr_fitness_batch")) {
+        return 1;
+    }
+    if (fitness_batch_pass(h, nullptr, d_src, n_src, stride_floats, m, poses, grid ? refused.data() : nullptr, grid ? refused.size() : K, max_sq, scores,
+                           n_in, &none)) return 1;
+    note_sparse_index(h);
+    return 0;
+}
+
+// The index the scores of pcr_fitness_batch and of relocalisation run on: the dense one (fit_grid_for), or none (*out = nullptr) where
+// pcr_params.query_index sends every score to the sparse index
+int score_grid_for(pcr_handle* h, const GridIndex** out) {
+    *out = nullptr;
+    return scores_on_sparse(h) ? 0 : fit_grid_for(h, out);
 }
 
 int batch_preconditions(pcr_handle* h, size_t n_src, size_t stride_bytes) {
@@ -257,8 +347,8 @@ int reloc_choose(pcr_handle* h, const float* d_src, size_t n_src, size_t stride_
     std::vector<int64_t> fn(nc);
     for (size_t c = 0; c < nc; ++c) memcpy(&refined[c * 16], cands[c]->pose, 16 * sizeof(double));
     const GridIndex* fit_grid = nullptr;
-    if (fit_grid_for(h, &fit_grid)) return 1;
-    if (fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, refined.data(), nc, max_sq, 0, fs.data(), fn.data())) return 1;
+    if (score_grid_for(h, &fit_grid)) return 1;
+    if (fitness_batch_run(h, fit_grid, d_src, n_src, stride_bytes / 4, refined.data(), nc, max_sq, 0, fs.data(), fn.data())) return 1;
     *any = false;
     for (size_t c = 0; c < nc; ++c) {
         cands[c]->n_in = fn[c];
@@ -341,16 +431,11 @@ int query_index_for(pcr_handle* h, const char* who, size_t n_q, size_t stride_by
         H_TRY(hipMemcpyAsync(&hdr, (*grid)->header.p, sizeof hdr, hipMemcpyDeviceToHost, h->stream));
         H_TRY(hipStreamSynchronize(h->stream));
         if (hdr.overflow || hdr.stale || (*grid)->filtered) return fail(h, std::string(who) + ": the target index is not complete (internal)");
-        if (!hdr.clamped) {
-            h->q.last_kind = PCR_QUERY_INDEX_DENSE; h->q.last_points = (*grid)->n_points;
-            h->q.last_bytes = (*grid)->sorted.cap + (*grid)->cell_start.cap + (*grid)->header.cap;
-            return 0;
-        }
+        if (!hdr.clamped) { note_dense_index(h, **grid); return 0; }
         *grid = nullptr;      // the box cannot be tabulated and the index was cut to the bulk of the cloud: an exact query needs every point
     }
     if (sparse_index_for(h, who)) return 1;
-    h->q.last_kind = PCR_QUERY_INDEX_SPARSE; h->q.last_points = h->q.sparse.view.n;
-    h->q.last_bytes = h->q.sparse.keys.cap + h->q.sparse.pts.cap;
+    note_sparse_index(h);
     return 0;
 }
 
@@ -367,12 +452,12 @@ int pcr_fitness_batch(pcr_handle* h, const void* src, size_t n_src, size_t strid
     if (n_src && !src) return fail(h, "NULL cloud with nonzero size");
     if (batch_preconditions(h, n_src, stride_bytes)) return 1;
     const GridIndex* fit_grid = nullptr;
-    if (fit_grid_for(h, &fit_grid)) return 1;
+    if (score_grid_for(h, &fit_grid)) return 1;
     if (K == 0) return 0;
     if (batch_points_check(h, n_src, score_points)) return 1;
     const float* d_src = (const float*)src;
     if (!on_device && stage_host(h, &h->src_stage, src, n_src, stride_bytes, &d_src)) return 1;
-    return fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, poses, K, max_sq, score_points, scores, n_in);
+    return fitness_batch_run(h, fit_grid, d_src, n_src, stride_bytes / 4, poses, K, max_sq, score_points, scores, n_in);
 }
 
 int pcr_knn(pcr_handle* h, const void* queries, size_t n_q, size_t stride_bytes, int on_device, int k, int64_t* idx, double* d2) {
@@ -502,8 +587,8 @@ int pcr_relocalize(pcr_handle* h, const void* src, size_t n_src, size_t stride_b
     std::vector<int64_t> nin(K);
     for (size_t q = 0; q < K; ++q) reloc_pose(click, p, nx, nk, q, &poses[q * 16]);
     const GridIndex* fit_grid = nullptr;
-    if (fit_grid_for(h, &fit_grid)) return 1;
-    if (fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, poses.data(), K, p->max_sq, (size_t)p->score_points, score.data(), nin.data())) return 1;
+    if (score_grid_for(h, &fit_grid)) return 1;
+    if (fitness_batch_run(h, fit_grid, d_src, n_src, stride_bytes / 4, poses.data(), K, p->max_sq, (size_t)p->score_points, score.data(), nin.data())) return 1;
     // 2. ranked by (-n_in, score, h); refused hypotheses and those with nothing in the gate are not ranked
     const std::vector<size_t> rank = reloc_rank(score.data(), nin.data(), K);
     if (rank.empty())
@@ -655,8 +740,8 @@ int pcr_relocalize_global(pcr_handle* h, pcr_sc* sc, const double* kf_poses, siz
         for (size_t q = 0; q < K; ++q) reloc_pose(coarse, &p->local, nx, nk, q, &poses[(pl * K + q) * 16]);
     }
     const GridIndex* fit_grid = nullptr;
-    if (fit_grid_for(h, &fit_grid)) return 1;
-    if (fitness_batch_run(h, *fit_grid, d_src, n_src, stride_bytes / 4, poses.data(), np * K, p->local.max_sq, (size_t)p->local.score_points,
+    if (score_grid_for(h, &fit_grid)) return 1;
+    if (fitness_batch_run(h, fit_grid, d_src, n_src, stride_bytes / 4, poses.data(), np * K, p->local.max_sq, (size_t)p->local.score_points,
                           score.data(), nin.data())) return 1;
     // 3. per place: ranked by (-n_in, score, h), distinct winners (pcr_relocalize steps 2-3, no click)
     std::vector<std::pair<size_t, size_t>> taken;      // (place rank, hypothesis)

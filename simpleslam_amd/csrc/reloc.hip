@@ -144,6 +144,11 @@ hipError_t fitness_batch_launch(const GridIndex& grid, const float* d_src, size_
     if (chunks > 0)
         hipLaunchKernelGGL(reloc_score_kernel, dim3((uint32_t)nb), dim3(256), 0, s, grid.view(), d_src, (uint64_t)n_src, (uint32_t)stride_floats, (uint64_t)m,
                            d_poses, (uint32_t)n_poses, chunks, tiles, mr, d_part);
+    return fitness_batch_reduce_launch(d_part, n_poses, chunks, d_out, s);
+}
+
+// (the second launch of every batched score: here and sparse_fitness.hip)
+hipError_t fitness_batch_reduce_launch(const RelocPart* d_part, size_t n_poses, uint32_t chunks, RelocSum* d_out, hipStream_t s) {
     hipLaunchKernelGGL(reloc_reduce_kernel, dim3((uint32_t)((n_poses + 3) / 4)), dim3(256), 0, s, d_part, (uint32_t)n_poses, chunks, d_out);
     return hipGetLastError();
 }

@@ -261,5 +261,43 @@ SW_FN void knn_walk(const View& v, double qx, double qy, double qz, uint32_t K, 
     box_scan(v, b, &ex, qy, qz, vis, st);
 }
 
+// The fitness scores' visitor (sparse_fitness.hip; host/sparse_index_check.cpp runs it on the CPU): knn_walk with K = 1 in the SCORE's metric.
+// The score wants the least FLOAT squared distance d = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)), dx = fl(q - p) (ring_search.h: ring_scan_run;
+// FLANN's L2_Simple<float>, no FMA), and only when it is within the gate; which point has it does not matter, so ties need no order and a point
+// offered twice changes nothing.  The walk's bounds are exact (f64) distances, so the visitor widens every comparison by how far d can fall below the
+// exact squared distance D of the same two float points:
+//   dx = (q - p)(1 + e), |e| <= u = 2^-24 (a float difference is never subnormal-rounded); the square and the two sums round once each, and all terms
+//   are >= 0, so every one of them only scales by (1 - u) at worst: d >= D (1 - u)^5 - 3 x 2^-150 > D (1 - 5 x 2^-24) - 2^-148 (the last term: products
+//   that underflow).  kWiden = 2^-20 > 5 x 2^-24 with eleven parts in sixteen to spare; the underflow term never decides, because every bound the walk
+//   hands over (slab_gap, the face distances of knn_walk, the box of axis_range) already lies slop_of >= cell x 2^-20 inside the true one.
+// Hence: a row, a face or a box whose exact bound g2 has g2 (1 - kWiden) > lim holds no point with d <= lim, where lim = min(least d so far, the gate).
+// skip() says exactly that; kth() hands the walk lim (1 + kWiden), so that its own tests "kth() < bound^2" and "the box of radius sqrt(kth())" leave
+// out only points with D > lim (1 + kWiden), i.e. d > lim.  The gate is a bound from the start: a point farther than it from everything costs the rings'
+// look-ups and nothing more.  The visitor alone computes d.
+static constexpr double kWiden = 0x1p-20;
+struct NearestF32 {
+    const Point* pts;
+    float qx, qy, qz;
+    float best;      // the least d so far; kNone: no point yet (fitness_kernel's 3.0e38f)
+    double lim;
+    static constexpr float kNone = 3.0e38f;
+    SW_FN void start(const Point* p, float x, float y, float z, float gate) { pts = p; qx = x; qy = y; qz = z; best = kNone; lim = (double)gate; }
+    SW_FN bool skip(double g2) const { return g2 * (1.0 - kWiden) > lim; }
+    SW_FN double kth() const { return lim * (1.0 + kWiden); }
+    SW_FN void cap(double) {}      // (kth() has said it already)
+    SW_FN void run(uint32_t s, uint32_t e) {
+        for (uint32_t j = s; j < e; ++j) {
+            const Point p = pts[j];
+            const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
+            float d = dx * dx;
+            d += dy * dy;
+            d += dz * dz;
+            if (d < best) { best = d; lim = fmin(lim, (double)d); }
+        }
+    }
+    // the seed: its points may as well be taken (a second offer changes nothing), and the bound is the list's own again
+    SW_FN double max_d2(uint32_t s, uint32_t e) { run(s, e); return kth(); }
+};
+
 }  // namespace sw
 }  // namespace pcr

@@ -487,7 +487,7 @@ public:
         p.query_index = query_index;
         if (pcr_set_params(h_, &p)) throw std::runtime_error(pcr_last_error(h_));
     }
-    // the index that answered the last search: its kind (PCR_QUERY_INDEX_DENSE / _SPARSE; -1: none yet), its points, its bytes of device memory
+    // the index that answered the last search or fitness score (a score a cut dense index cannot give is taken on the sparse one): its kind (PCR_QUERY_INDEX_DENSE / _SPARSE; -1: none yet), its points, its bytes of device memory
     struct QueryIndexInfo { int kind; size_t n_points, bytes; };
     QueryIndexInfo queryIndexInfo() const {
         QueryIndexInfo i{-1, 0, 0};

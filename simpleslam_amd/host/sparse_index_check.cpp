@@ -8,11 +8,18 @@
 // rows R and layers L of the block scanned (counted here from the sorted keys, not by the walk) -- the walk's bound is
 // kRingLookups + 2 + kRowLookups R + kLayerLookups L -- and the same for its radius walk (bound: 1 + kRowLookups R + kLayerLookups L).
 // A cloud the index refuses: "refused <reason> <extents>" and exit status 3.
+//   sparse_index_check fitness <points.f32> <queries.f32> <gate>
+// The fitness scores' search (csrc/sparse_fitness.hip) on the CPU: the same walk with K = 1 under the same visitor, sw::NearestF32 -- the least
+// FLOAT squared distance within the gate (a float; 3.4028235e38 for none) -- against a brute force over every stored point in the same float
+// arithmetic.  stdout, one line per query: the bits of the walk's answer and of the brute force's (a distance beyond the gate is nobody's
+// answer: both print the bits of 3.0e38f), the walk's look-ups and points, whether it came to the box scan and that block's occupied rows and
+// layers; then "mismatches <count>".  The walk's bound is the k-NN walk's: kRingLookups + 1 + box (1 + kRowLookups R + kLayerLookups L).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <numeric>
 #include <set>
@@ -98,51 +105,106 @@ static void rows_layers(const sw::View& v, const sw::Box& b, unsigned long long*
     *rows = r.size(); *layers = l.size();
 }
 
+// the build: box of the lattice values over the finite rows, layout, keys, a stable sort
+struct Index {
+    sw::View v;
+    sw::Layout lay;
+    std::vector<unsigned long long> keys;
+    std::vector<sw::Point> pts;
+};
+static bool build_index(const std::vector<float>& P, double cell, Index& ix) {
+    const size_t n = P.size() / 4;
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    std::vector<uint32_t> kept;
+    for (size_t i = 0; i < n; ++i) {
+        const float* p = &P[i * 4];
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) continue;
+        kept.push_back((uint32_t)i);
+        for (int a = 0; a < 3; ++a) { const double f = std::floor((double)p[a] / cell); lo[a] = std::fmin(lo[a], f); hi[a] = std::fmax(hi[a], f); }
+    }
+    if (kept.empty()) for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0.0;
+    const sw::Layout lay = sw::layout_of(lo, hi);
+    ix.lay = lay;
+    if (lay.refused) {
+        std::printf("refused %s %.6g x %.6g x %.6g\n", lay.refused == sw::kRefusedBits ? "bits" : "range", lay.extd[0], lay.extd[1], lay.extd[2]);
+        return false;
+    }
+    sw::View& v = ix.v;
+    v.n = (uint32_t)kept.size(); v.b0 = lay.b[0]; v.b1 = lay.b[1]; v.b2 = lay.b[2]; v.cell = cell;
+    for (int a = 0; a < 3; ++a) { v.lo[a] = lay.lo[a]; v.ext[a] = lay.ext[a]; }
+    std::vector<unsigned long long> key_of_row(kept.size());
+    for (size_t j = 0; j < kept.size(); ++j) {
+        const float* p = &P[(size_t)kept[j] * 4];
+        long long c[3];
+        for (int a = 0; a < 3; ++a) c[a] = (long long)std::floor((double)p[a] / cell) - lay.lo[a];
+        key_of_row[j] = sw::key_of(v, c[2], c[1], c[0]);
+    }
+    std::vector<uint32_t> order(kept.size());
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key_of_row[a] < key_of_row[b]; });
+    ix.keys.assign(kept.size() + 1, 0ull);      // (+ 1: never an empty array behind the pointers)
+    ix.pts.assign(kept.size() + 1, sw::Point{0.f, 0.f, 0.f, 0u});
+    for (size_t j = 0; j < kept.size(); ++j) {
+        const uint32_t row = kept[order[j]];
+        ix.keys[j] = key_of_row[order[j]];
+        ix.pts[j] = sw::Point{P[(size_t)row * 4], P[(size_t)row * 4 + 1], P[(size_t)row * 4 + 2], row};
+    }
+    v.keys = ix.keys.data(); v.pts = ix.pts.data();
+    std::printf("index %u points, bits %d %d %d, extents %llu %llu %llu\n", v.n, v.b0, v.b1, v.b2, v.ext[0], v.ext[1], v.ext[2]);
+    return true;
+}
+
+static uint32_t bits_of_float(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+
+// the `fitness` mode
+static int fitness_mode(const char* points, const char* queries, const char* gate_text) {
+    const std::vector<float> P = load(points), Q = load(queries);
+    const float gate = std::strtof(gate_text, nullptr);
+    Index ix;
+    if (!build_index(P, 1.0, ix)) return 3;
+    const sw::View& v = ix.v;
+    unsigned long long mismatches = 0;
+    for (size_t i = 0; i < Q.size() / 4; ++i) {
+        const float* q = &Q[i * 4];
+        sw::Stats st;
+        unsigned long long rows = 0, layers = 0;
+        float got = sw::NearestF32::kNone, want = sw::NearestF32::kNone;
+        if (std::isfinite(q[0]) && std::isfinite(q[1]) && std::isfinite(q[2])) {
+            sw::NearestF32 vis;
+            vis.start(v.pts, q[0], q[1], q[2], gate);
+            sw::knn_walk(v, (double)q[0], (double)q[1], (double)q[2], 1u, vis, st);
+            if (vis.best <= gate) got = vis.best;
+            if (st.boxes) rows_layers(v, st.box, &rows, &layers);
+            sw::NearestF32 all;      // brute force: the visitor's own arithmetic over every stored point, no walk and no bound
+            all.start(v.pts, q[0], q[1], q[2], gate);
+            all.run(0u, v.n);
+            if (all.best <= gate) want = all.best;
+        }
+        mismatches += bits_of_float(got) != bits_of_float(want);
+        std::printf("q %zu got %u want %u lookups %llu points %llu box %d rows %llu layers %llu\n", i, bits_of_float(got), bits_of_float(want), st.lookups,
+                    st.points, st.boxes, rows, layers);
+    }
+    std::printf("bounds ring %d row %d layer %d\n", sw::kRingLookups, sw::kRowLookups, sw::kLayerLookups);
+    std::printf("mismatches %llu\n", mismatches);
+    return mismatches ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc == 5 && std::string(argv[1]) == "fitness") {
+        try { return fitness_mode(argv[2], argv[3], argv[4]); }
+        catch (const std::exception& e) { std::fprintf(stderr, "error: %s\n", e.what()); return 1; }
+    }
     if (argc != 6) { std::fprintf(stderr, "usage: %s <points.f32> <queries.f32> <k> <radius> <out.bin>\n", argv[0]); return 2; }
     try {
         const std::vector<float> P = load(argv[1]), Q = load(argv[2]);
-        const size_t n = P.size() / 4, nq = Q.size() / 4;
+        const size_t nq = Q.size() / 4;
         const size_t K = (size_t)std::atoi(argv[3]);
         const double radius = std::atof(argv[4]), cell = 1.0;
         if (K < 1 || K > 32 || !(radius > 0.0)) throw std::runtime_error("k must be 1 .. 32 and the radius positive");
-        // the build: box of the lattice values over the finite rows, layout, keys, a stable sort
-        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        std::vector<uint32_t> kept;
-        for (size_t i = 0; i < n; ++i) {
-            const float* p = &P[i * 4];
-            if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) continue;
-            kept.push_back((uint32_t)i);
-            for (int a = 0; a < 3; ++a) { const double f = std::floor((double)p[a] / cell); lo[a] = std::fmin(lo[a], f); hi[a] = std::fmax(hi[a], f); }
-        }
-        if (kept.empty()) for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0.0;
-        const sw::Layout lay = sw::layout_of(lo, hi);
-        if (lay.refused) {
-            std::printf("refused %s %.6g x %.6g x %.6g\n", lay.refused == sw::kRefusedBits ? "bits" : "range", lay.extd[0], lay.extd[1], lay.extd[2]);
-            return 3;
-        }
-        sw::View v;
-        v.n = (uint32_t)kept.size(); v.b0 = lay.b[0]; v.b1 = lay.b[1]; v.b2 = lay.b[2]; v.cell = cell;
-        for (int a = 0; a < 3; ++a) { v.lo[a] = lay.lo[a]; v.ext[a] = lay.ext[a]; }
-        std::vector<unsigned long long> key_of_row(kept.size());
-        for (size_t j = 0; j < kept.size(); ++j) {
-            const float* p = &P[(size_t)kept[j] * 4];
-            long long c[3];
-            for (int a = 0; a < 3; ++a) c[a] = (long long)std::floor((double)p[a] / cell) - lay.lo[a];
-            key_of_row[j] = sw::key_of(v, c[2], c[1], c[0]);
-        }
-        std::vector<uint32_t> order(kept.size());
-        std::iota(order.begin(), order.end(), 0u);
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key_of_row[a] < key_of_row[b]; });
-        std::vector<unsigned long long> keys(kept.size() + 1);      // (+ 1: never an empty array behind the pointers)
-        std::vector<sw::Point> pts(kept.size() + 1);
-        for (size_t j = 0; j < kept.size(); ++j) {
-            const uint32_t row = kept[order[j]];
-            keys[j] = key_of_row[order[j]];
-            pts[j] = sw::Point{P[(size_t)row * 4], P[(size_t)row * 4 + 1], P[(size_t)row * 4 + 2], row};
-        }
-        v.keys = keys.data(); v.pts = pts.data();
-        std::printf("index %u points, bits %d %d %d, extents %llu %llu %llu\n", v.n, v.b0, v.b1, v.b2, v.ext[0], v.ext[1], v.ext[2]);
+        Index ix;
+        if (!build_index(P, cell, ix)) return 3;
+        const sw::View& v = ix.v;
+        const std::vector<sw::Point>& pts = ix.pts;
 
         std::vector<int64_t> kidx(nq * K, -1);
         std::vector<double> kd2(nq * K, INFINITY);

@@ -728,7 +728,8 @@ class PointCloudRegister:
 
     def fitnessBatch(self, src, poses, max_sq=1.0, score_points=0):
         """pcr_fitness_batch: fitnessGated of every pose of `poses` (K, 4, 4) in one pass -> (scores (K,) float64, n_in (K,) int64).  A pose a
-        cut index cannot score gets (-1, -1).  score_points: 0 = every point, else the subset floor(j n / score_points)."""
+        cut dense index cannot score is scored on the sparse index of the kept target (exactly); (-1, -1) only where that cannot be had
+        (a caller's device target).  score_points: 0 = every point, else the subset floor(j n / score_points)."""
         p, n, s, dev, _k = _cloud(src)
         P = np.asarray(poses, np.float64).reshape(-1, 4, 4)
         cm = np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(-1)      # column-major per pose
@@ -768,8 +769,8 @@ class PointCloudRegister:
         return offsets, idx, d2
 
     def queryIndexInfo(self):
-        """pcr_query_index_info -> dict(kind, n_points, bytes): the index that answered the last knn / radiusSearch ("dense", "sparse", or None
-        when none has been answered since the target was set), the points it holds and the device memory it occupies."""
+        """pcr_query_index_info -> dict(kind, n_points, bytes): the index that answered the last knn / radiusSearch or fitness score ("dense",
+        "sparse", or None when none has been answered since the target was set), the points it holds and the device memory it occupies."""
         kind, n, b = C.c_int(-1), C.c_size_t(0), C.c_size_t(0)
         self._check(self._lib.pcr_query_index_info(self._h, C.byref(kind), C.byref(n), C.byref(b)))
         return dict(kind={QUERY_INDEX_DENSE: "dense", QUERY_INDEX_SPARSE: "sparse"}.get(kind.value), n_points=int(n.value), bytes=int(b.value))
