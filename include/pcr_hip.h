@@ -1120,6 +1120,116 @@ int pcr_frontend_step(pcr_frontend* fe, const void* scan, size_t n, size_t strid
 int pcr_frontend_prefetch(pcr_frontend* fe, const void* next_scan, size_t n, size_t stride_bytes, int on_device);
 int pcr_frontend_finish(pcr_frontend* fe, size_t* n_submap);   /* collects a queued assembly */
 int pcr_frontend_reset(pcr_frontend* fe);                      /* pcr_map_clear + the loop's own state; device memory kept */
+/* mClosestKfIdx (MapManager.cpp:146), which Backend::addOdomFactor reads: one entry per key frame this front end has added since create or
+ * reset, in order -- the index of the key frame whose squared distance step 6 found smallest (the lowest index on a tie), -1 for a key frame
+ * added to an empty store.  Recording only: no step's result depends on it.  *n (may be NULL) = the entries there are; idx == NULL writes
+ * the count alone; a capacity below the count fails and writes nothing else. */
+int pcr_frontend_closest(const pcr_frontend* fe, int64_t* idx, size_t capacity, size_t* n);
+
+/* ---- Key frames ranked by distance: the loop detector backend/DistContext.hpp declares (a kd-tree over key-frame positions) and leaves empty ----
+ * For every query key frame q of [first, first + count) and every candidate i of [0, q - num_exclude_recent): the squared distance of their
+ * positions, (dx*dx + dy*dy) + dz*dz in double, d = candidate - query, every operation rounded on its own (the order of pcr_frontend_step's
+ * step 6).  A candidate counts when d2 <= radius*radius; of those the k best by (d2, i) ascending are kept -- the lower index wins a tie.
+ * Row q - first of idx and d2 (count * k entries each) holds them in that order, the tail idx -1, d2 DBL_MAX.  k is 1..8.  A query or a
+ * candidate with a coordinate that is not finite never matches.  A row depends on its query alone: the same bits whatever the window.
+ * Fails, writing NOTHING, when k is out of range, radius is negative or not finite, num_exclude_recent < 0, first + count > n, or idx or d2
+ * is NULL while count > 0; count == 0 returns 0.
+ * pcr_kf_rank_near_host is the definition: host only, no GPU, positions xyz[3 n].  pcr_map_rank_near is the same over the positions of a
+ * store's key frames (parent or view; the translations of the poses the store holds now), on the device: the positions of key frames
+ * [0, first + count) go up once per call as three arrays of doubles, tiles of 16 queries meet the candidates in tiles of 256, every lane
+ * keeps its k best in registers and a query's lanes are merged in a fixed order -- no atomics, the result depends on no schedule and equals
+ * the host function's bit for bit.  Its failures report through pcr_map_last_error. */
+int pcr_kf_rank_near_host(const double* xyz, size_t n, size_t first, size_t count, int num_exclude_recent, double radius, int k, int64_t* idx,
+                          double* d2);
+int pcr_map_rank_near(const pcr_map* m, size_t first, size_t count, int num_exclude_recent, double radius, int k, int64_t* idx, double* d2);
+
+/* ---- The back end's key-frame and loop-closure loop -------------------------------------------------------------------------------------
+ * Backend::optimHandler (backend/src/Backend.cpp:270-347) and LoopClosureManager::lcHandler (backend/src/LoopClosureManager.cpp:62-119)
+ * strung together once, in the library, over handles that exist: a view of the store (lc_map_), a ScanContext database, a register with
+ * initForLC's settings and a pose graph.  No thread, queue or condition variable: the caller decides when an event runs, as with
+ * pcr_frontend.  The two events are pinned bit for bit to the same sequence of public calls made by a caller. */
+typedef struct pcr_backend pcr_backend;
+enum { PCR_BACKEND_SC_QUERY = 1, PCR_BACKEND_SC_RANK = 2, PCR_BACKEND_DISTANCE = 4 };      /* pcr_backend_params.detectors */
+enum { PCR_VGICP = 0, PCR_GICP = 1 };                                                      /* pcr_backend_params.lc_method */
+typedef struct pcr_backend_params {
+    double grid_size;            /* 0.5  downSampleVoxelGridSize: saveKfs' in-place filter; <= 0: key frames are left as they are */
+    double context_grid_size;    /* 0.5  backend.lc.contextDownSampleGridSize: contexts and the loop window */
+    int32_t history_range;       /* 1    backend.lc.historySubmapRange */
+    double fitness_threshold;    /* 0.3  backend.lc.fitnessThreshold */
+    int32_t detectors;           /* bit 0 SC_QUERY (default, lcHandler's pcr_sc_query), bit 1 SC_RANK (pcr_sc_rank_stored k = 1 + dist_thres),
+                                    bit 2 DISTANCE (pcr_map_rank_near, k = 1); 0: no loop is looked for */
+    double dist_radius;          /* 5.0  DISTANCE: metres */
+    int32_t dist_exclude_recent; /* DISTANCE: default -1 = sc.num_exclude_recent as pcr_backend_create finds it */
+    int32_t lc_method;           /* PCR_VGICP (default, the reference's) or PCR_GICP */
+    int32_t lc_between_refined;  /* 1 (default): the loop factor is old^-1 * refined pose; 0: the reference as written, old^-1 * cur (see below) */
+    pcr_sc_params sc;
+    pcr_graph_params graph;
+} pcr_backend_params;
+/* One candidate pair of pcr_backend_close_loops.  detector: the PCR_BACKEND_* bits of every detector that proposed the pair (it is verified
+ * once).  converged, iterations, fitness: the registration of key frame cur against the window about old (pcr_fitness of the register);
+ * a pair whose source or window is empty has converged 0, iterations 0, fitness DBL_MAX.  pose: the refined pose of cur. */
+typedef struct pcr_backend_loop {
+    int64_t cur, old;
+    int32_t detector, converged, iterations, accepted;
+    double fitness;
+    double pose[16];
+} pcr_backend_loop;
+typedef struct pcr_backend_info {
+    int64_t keyframes, contexts;     /* totals after the event: key frames in the graph, contexts in the database */
+    int32_t keyframes_added;         /* add_keyframes: key frames this event took */
+    int32_t candidates, accepted;    /* close_loops: pairs verified, pairs accepted */
+    int32_t factors_added;           /* between factors this event added (odometry or loop) */
+    int32_t optimized, pad_;         /* 1: pcr_graph_optimize and the pose write-back ran */
+    pcr_graph_result graph;          /* ... and what it returned */
+    double delta[16];                /* T2SE3(new_last * old_last^-1) of the newest key frame (graph.delta); the identity when nothing was optimised:
+                                        what the caller applies to its global odometry and odom2map (Backend.cpp:321-346) */
+    double seconds[9];               /* host time: contexts, downsample, factors, detect, window, scan2map, fitness, optimize, set_poses */
+} pcr_backend_info;
+
+void pcr_backend_default_params(pcr_backend_params* p);
+/* Borrows `map` (a parent, not a view), which must outlive the back end; owns a view of it, a pcr_sc (params.sc), a register of lc_method
+ * with initForLC's settings (100 iterations, translation epsilon 1e-6; gicp: correspondence distance 150) and a pcr_graph, all on the map's
+ * device.  p == NULL: the defaults.  NULL on failure (pcr_backend_last_error(NULL)). */
+pcr_backend* pcr_backend_create(pcr_map* map, const pcr_backend_params* p);
+void pcr_backend_destroy(pcr_backend* be);
+const char* pcr_backend_last_error(const pcr_backend* be);
+/* The owned handles, for the interfaces that exist: a robust kernel, fixed poses, pcr_graph_save_g2o, the contexts, the register's stats. */
+pcr_graph* pcr_backend_graph(pcr_backend* be);
+pcr_sc* pcr_backend_sc(pcr_backend* be);
+pcr_handle* pcr_backend_register(pcr_backend* be);
+/* optimHandler's NewKFCome event for key frames [done, pcr_map_keyframes) (done: the key frames earlier events took), in the reference's order:
+ *   1. pcr_sc_add_keyframes(map, done, count, context_grid_size): contexts from the RAW key frames, before saveKfs filters them;
+ *   2. grid_size > 0: pcr_map_downsample_keyframes(map, done, grid_size) (saveKfs);
+ *   3. an empty graph: pcr_graph_add_prior on pose 0 at key frame 0's pose with pcr_graph_noise(PRIOR) (the factor may precede its pose);
+ *   4. pcr_graph_add_poses of the new key frames' stored poses;
+ *   5. per new key frame i > 0 pcr_graph_add_between_poses(closest[i - done], i, pcr_graph_noise(ODOM)); closest == NULL: from i - 1.
+ *      closest (n_closest entries, at least count) is pcr_frontend_closest's tail for these key frames; an entry that is -1 for a key frame
+ *      other than 0, at or beyond its own index, or out of range -- or an n_closest below count -- fails the call BEFORE anything changes;
+ *   6. pcr_graph_optimize(params.graph);   7. pcr_map_set_poses_from_graph(map, graph, 0, all);   8. delta (info).
+ * No new key frame: returns 0, nothing changes, delta is the identity. */
+int pcr_backend_add_keyframes(pcr_backend* be, const int64_t* closest, size_t n_closest, pcr_backend_info* info);
+/* lcHandler over contexts [lc_done, pcr_sc_size), then the LC event when a loop was accepted.  Candidates (cur, old) come from the enabled
+ * detectors -- SC_QUERY: pcr_sc_query(cur); SC_RANK: pcr_sc_rank_stored(k = 1), kept when dist <= (float)sc.dist_thres; DISTANCE:
+ * pcr_map_rank_near(view, dist_exclude_recent, dist_radius, k = 1) -- in ascending cur, within one cur in the detectors' bit order, a pair once.
+ * Per candidate: pcr_map_update_window(view, old, history_range, context_grid_size); source = pcr_map_keyframe(cur) in HBM;
+ * pcr_scan2map_submap from guess = pose(cur); pcr_fitness.  Accepted when it converged and fitness < fitness_threshold: pcr_graph_add_loop
+ * (old, cur, Z, pcr_graph_noise(LOOP)).  Z = pose(old)^-1 * guess -- the inverse as [R^T, -(R^T t)], the product row by row as
+ * ((a0 b0 + a1 b1) + a2 b2) (+ t), in double without contraction.  lc_between_refined = 0 gives the reference as written
+ * (LoopClosureManager.cpp:97-107 registers into `guess` and then builds the factor from cur_pose, the UNREFINED pose): Z = X_old^-1 X_cur of
+ * the current estimates (pcr_graph_add_between_poses + the robust mark), a factor that agrees with the estimate and corrects nothing.
+ * Then, when a factor was added: pcr_graph_optimize, pcr_map_set_poses_from_graph(0, all), delta.  iSAM2's update counts (1, then 3 more
+ * after a loop) are not reproduced: the graph is optimised to params.graph's own convergence.  The records stay readable through
+ * pcr_backend_loops until the next pcr_backend_close_loops or reset. */
+int pcr_backend_close_loops(pcr_backend* be, pcr_backend_info* info);
+/* The records of the last pcr_backend_close_loops; *n (may be NULL) = how many there are; out == NULL writes the count alone; a capacity
+ * below the count fails and writes nothing else. */
+int pcr_backend_loops(const pcr_backend* be, pcr_backend_loop* out, size_t capacity, size_t* n);
+/* The two events in order; either info may be NULL.  close_loops runs also when no key frame was new (it then finds no new context). */
+int pcr_backend_step(pcr_backend* be, const int64_t* closest, size_t n_closest, pcr_backend_info* add_info, pcr_backend_info* loop_info);
+/* Starts over: the graph, the contexts, the records and the counters are cleared, the store is left alone (device memory kept).
+ * Failures follow pcr_frontend's rule: the inner call's message under the step's name, the state what the completed parts left, further
+ * events refused until pcr_backend_reset. */
+int pcr_backend_reset(pcr_backend* be);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,7 @@ struct pcr_frontend {
     DeviceBuf up_ahead[2];          // pcr_frontend_prefetch: host scans on their way in
     Ahead queued, ready;            // the filter in flight on `filt`; the one collected and not yet taken by a step
     std::vector<double> kf_pos;     // key-frame positions, xyz each
+    std::vector<int64_t> closest;   // per key frame this front end added: the key frame step 6 found nearest, -1 for the first (mClosestKfIdx, MapManager.cpp:146)
     bool have_update = false;       // an assembly has happened (setCurPose)
     double last_update[3] = {0, 0, 0};
     bool assembly_queued = false;   // pcr_map_update_begin has queued one that nobody collected
@@ -277,12 +278,13 @@ int pcr_frontend_step(pcr_frontend* fe, const void* scan, size_t n, size_t strid
 
     // 6. putKeyFrame (MapManager.cpp:121-149): nearestKSearch's SQUARED distance against minKFGap itself (:141-143)
     bool add = fe->kf_pos.empty();
+    int64_t nearest = -1;      // (recorded for pcr_frontend_closest; the rule reads `best` alone)
     if (!add) {
         double best = DBL_MAX;
         for (size_t i = 0; i + 2 < fe->kf_pos.size(); i += 3) {
             const double dx = fe->kf_pos[i] - t[0], dy = fe->kf_pos[i + 1] - t[1], dz = fe->kf_pos[i + 2] - t[2];
             const double d2 = (dx * dx + dy * dy) + dz * dz;
-            if (d2 < best) best = d2;
+            if (d2 < best) { best = d2; nearest = (int64_t)(i / 3); }
         }
         add = best > fe->prm.kf_gap;
     }
@@ -290,6 +292,7 @@ int pcr_frontend_step(pcr_frontend* fe, const void* scan, size_t n, size_t strid
         t0 = std::chrono::steady_clock::now();
         if (pcr_map_add_keyframe(fe->map, scan, n, stride_bytes, on_device, pose)) return inner_fail(fe, "add_keyframe", pcr_map_last_error(fe->map));
         fe->kf_pos.insert(fe->kf_pos.end(), {t[0], t[1], t[2]});
+        fe->closest.push_back(nearest);
         inf.keyframe_added = 1;
         inf.seconds[3] = seconds_since(t0);
     }
@@ -321,6 +324,17 @@ int pcr_frontend_finish(pcr_frontend* fe, size_t* n_submap) {
     return 0;
 }
 
+int pcr_frontend_closest(const pcr_frontend* fe, int64_t* idx, size_t capacity, size_t* n) {
+    if (!fe) return 1;
+    pcr_frontend* w = const_cast<pcr_frontend*>(fe);
+    w->err.clear();
+    if (n) *n = fe->closest.size();
+    if (!idx) return 0;      // (the count alone, as pcr_map_submap_indices)
+    if (capacity < fe->closest.size()) return ffail(w, "output capacity too small: " + std::to_string(fe->closest.size()) + " key frames were added");
+    std::copy(fe->closest.begin(), fe->closest.end(), idx);
+    return 0;
+}
+
 int pcr_frontend_reset(pcr_frontend* fe) {
     if (!fe) return 1;
     fe->err.clear();
@@ -333,6 +347,7 @@ int pcr_frontend_reset(pcr_frontend* fe) {
     }
     fe->ready.on = false;
     fe->kf_pos.clear();
+    fe->closest.clear();
     fe->have_update = false;
     fe->assembly_queued = false;
     fe->n_submap = 0;

@@ -416,6 +416,10 @@ struct RelocPart { double sum; uint32_t cnt, viol; };
 int sc_device(const pcr_sc* sc);
 // the device a key-frame store, or a view of one, lives on (submap.hip)
 int map_device(const pcr_map* m);
+// (submap.hip, for kf_rank.hip) sets pcr_map_last_error's message and returns 1; a device buffer of at least `bytes` that belongs to this
+// pcr_map object (contents not kept between calls), NULL when it cannot grow
+int map_set_error(const pcr_map* m, const std::string& s);
+void* map_scratch(const pcr_map* m, size_t bytes);
 // the device a pose graph lives on, PCR_GRAPH_HOST (-2) for a graph without one (graph_host.hip)
 int graph_device(const pcr_graph* g);
 struct RelocSum { double sum; unsigned long long cnt, viol, pad_; };

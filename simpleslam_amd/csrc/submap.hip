@@ -125,6 +125,7 @@ struct pcr_map {
     std::vector<pcr_map*> views;      // (parent) the views that read this store
     std::mutex views_mu;              // guards `views`: a view may be created and destroyed from different threads
     Buf scratch;                      // (parent) pcr_map_downsample_keyframes filters a key frame into it and copies back
+    Buf rank;                         // pcr_map_rank_near (kf_rank.hip): the positions it uploads and the rows it reads back; a view has its own
 };
 
 static thread_local std::string g_map_err;
@@ -132,6 +133,14 @@ static int mfail(pcr_map* m, const std::string& s) { if (m) m->err = s; else g_m
 static int mfail(const pcr_map* m, const std::string& s) { return mfail(const_cast<pcr_map*>(m), s); }
 static const pcr_map* store_of(const pcr_map* m) { return m->parent ? m->parent : m; }
 namespace pcr { int map_device(const pcr_map* m) { return m->device; } }      // (pcr_internal.h: the device a store, or a view of one, lives on)
+// (pcr_internal.h, for kf_rank.hip) pcr_map_last_error's message set from another unit, and this object's own buffer for the ranking
+namespace pcr {
+int map_set_error(const pcr_map* m, const std::string& s) { return mfail(m, s); }
+void* map_scratch(const pcr_map* m, size_t bytes) {
+    pcr_map* w = const_cast<pcr_map*>(m);
+    return w->rank.reserve(bytes, false) == hipSuccess ? w->rank.p : nullptr;
+}
+}  // namespace pcr
 // every entry point but pcr_map_destroy: a view that outlived its parent has no store to read
 #define M_ALIVE(m) do { if ((m)->detached) return mfail(m, "parent destroyed: this view can only be destroyed"); } while (0)
 #define M_OWNER(m, what) do { if ((m)->parent) return mfail(m, std::string(what) + ": this pcr_map is a view (pcr_map_view) and cannot change the store; call it on the parent"); } while (0)

@@ -196,6 +196,14 @@ public:
         return idx;
     }
     const void* devicePointer(size_t* n, size_t* stride_bytes) const { return pcr_map_submap(m_, n, stride_bytes); }
+    // pcr_map_rank_near: for every query key frame of [first, first + count) the k nearest of [0, q - num_exclude_recent) within `radius`, on the
+    // device; idx and d2 get count * k entries, row q - first, tails -1 / DBL_MAX
+    void rankNear(size_t first, size_t count, double radius, int k, int num_exclude_recent, std::vector<int64_t>& idx, std::vector<double>& d2) const {
+        std::vector<int64_t> i(count * (size_t)(k > 0 ? k : 0));
+        std::vector<double> d(i.size());
+        if (pcr_map_rank_near(m_, first, count, num_exclude_recent, radius, k, i.data(), d.data())) throw std::runtime_error(pcr_map_last_error(m_));
+        idx.swap(i); d2.swap(d);
+    }
     size_t keyframes() const {
         size_t n = 0;
         if (pcr_map_keyframes(m_, &n)) throw std::runtime_error(pcr_map_last_error(m_));
@@ -328,6 +336,14 @@ public:
         return n;
     }
     void reset() { if (pcr_frontend_reset(fe_)) throw std::runtime_error(pcr_frontend_last_error(fe_)); }
+    // mClosestKfIdx (MapManager.cpp:146): per key frame this front end added, the key frame nearest to it then; -1 for the first
+    std::vector<int64_t> closest() const {
+        size_t n = 0;
+        if (pcr_frontend_closest(fe_, nullptr, 0, &n)) throw std::runtime_error(pcr_frontend_last_error(fe_));
+        std::vector<int64_t> idx(n);
+        if (n && pcr_frontend_closest(fe_, idx.data(), n, &n)) throw std::runtime_error(pcr_frontend_last_error(fe_));
+        return idx;
+    }
     pcr_frontend* handle() { return fe_; }
 };
 
@@ -725,6 +741,40 @@ public:
     void saveG2o(const std::string& path) const { check(pcr_graph_save_g2o(g_, path.c_str())); }
     void clear() { check(pcr_graph_clear(g_)); }
     pcr_graph* handle() const { return g_; }
+};
+
+// Backend::optimHandler's NewKFCome and LC events and LoopClosureManager::lcHandler in the library (pcr_backend) over a SubMap it
+// borrows (a parent).  graph(), sc() and reg() are the owned handles, for the C interfaces that exist (pcr_graph_set_robust_kernel,
+// pcr_graph_save_g2o, pcr_sc_descriptor, pcr_get_stats, ...); sc() is a new handle after reset().
+class Backend {
+    pcr_backend* be_ = nullptr;
+    void check(int rc) const { if (rc) throw std::runtime_error(pcr_backend_last_error(be_)); }
+public:
+    using Info = pcr_backend_info;
+    using Loop = pcr_backend_loop;
+    static pcr_backend_params defaults() { pcr_backend_params p; pcr_backend_default_params(&p); return p; }
+    explicit Backend(PCR::SubMap& map, const pcr_backend_params* p = nullptr) : be_(pcr_backend_create(map.handle(), p)) {
+        if (!be_) throw std::runtime_error(pcr_backend_last_error(nullptr));
+    }
+    Backend(const Backend&) = delete;
+    Backend& operator=(const Backend&) = delete;
+    ~Backend() { pcr_backend_destroy(be_); }
+    // closest: Frontend::closest()'s entries for the key frames the store has gained since the last event (nullptr: every edge from i - 1)
+    Info addKeyFrames(const int64_t* closest = nullptr, size_t n_closest = 0) { Info i; check(pcr_backend_add_keyframes(be_, closest, n_closest, &i)); return i; }
+    Info closeLoops() { Info i; check(pcr_backend_close_loops(be_, &i)); return i; }
+    void step(const int64_t* closest, size_t n_closest, Info* add = nullptr, Info* lc = nullptr) { check(pcr_backend_step(be_, closest, n_closest, add, lc)); }
+    std::vector<Loop> loops() const {
+        size_t n = 0;
+        check(pcr_backend_loops(be_, nullptr, 0, &n));
+        std::vector<Loop> out(n);
+        if (n) check(pcr_backend_loops(be_, out.data(), n, &n));
+        return out;
+    }
+    void reset() { check(pcr_backend_reset(be_)); }
+    pcr_graph* graph() { return pcr_backend_graph(be_); }
+    pcr_sc* sc() { return pcr_backend_sc(be_); }
+    pcr_handle* reg() { return pcr_backend_register(be_); }
+    pcr_backend* handle() { return be_; }
 };
 }  // namespace backend
 

@@ -1,12 +1,15 @@
 // seq_harness.cpp -- the front end's per-scan loop driven from C++: LidarOdometry::handler around scan2Map (frontend/src/LidarOdometry.cpp:160-214,
 // frontend/src/MapManager.cpp:109-201) over a recording, through PCR::Frontend (pcr_frontend_*: the loop itself lives in the library).
-//   seq_harness <method> <list.txt> <cmds.txt> <start.txt> [--grid g] [--mobile] [--prefetch] [--reps r]
+//   seq_harness <method> <list.txt> <cmds.txt> <start.txt> [--grid g] [--mobile] [--prefetch] [--reps r] [--backend]
 // method     loam | ndt | vgicp | gicp | liorf (the factory of LidarOdometry.cpp:44-54: unknown throws)
 // list.txt   one scan file per line: .pcd (pcp/pcd_io.hpp) or raw float records x y z intensity (.f32, as the other harnesses read them)
 // cmds.txt   one 4x4 per line, 16 numbers row by row: cmds[k] = the motion from scan k-1 to scan k as the odometer reports it (cmds[0]: identity)
 // start.txt  the pose before scan 0, 16 numbers row by row
 // --grid g   downSampleVoxelGridSize (default 0.5);  --mobile  SixDof2Mobile on every refined pose (LidarOdometry.cpp:211)
 // --prefetch the next scan's voxel filter is queued before this scan is registered;  --reps r  the drive r times on the same handles
+// --backend  backend::Backend (pcr_backend_*) behind the front end, as sequence.drive_slam has it: after every scan that added a key frame,
+//            pcr_backend_step with Frontend::closest()'s new entries, and the next guess starts from lc.delta * (add.delta * pose) (the same
+//            fixed-order product).  Prints one "backend k ..." line per event of the first drive: key frames, candidates, accepted, LM iterations
 // The scans are uploaded before the timed loop (into a key-frame store of their own: no HIP call in this file).  generateOdom's guess is chained
 // here, init = pose * cmds[k], by one fixed-order product -- rows times columns, every entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3, no contraction --
 // so that any caller can repeat it to the bit.
@@ -18,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -25,7 +29,7 @@
 #include "PCR/HipRegister.hpp"
 #include "pcp/pcd_io.hpp"
 
-static const char* kUsage = "usage: %s <loam|ndt|vgicp|gicp|liorf> <list.txt> <cmds.txt> <start.txt> [--grid g] [--mobile] [--prefetch] [--reps r]\n";
+static const char* kUsage = "usage: %s <loam|ndt|vgicp|gicp|liorf> <list.txt> <cmds.txt> <start.txt> [--grid g] [--mobile] [--prefetch] [--reps r] [--backend]\n";
 
 static bool ends_with(const std::string& s, const char* suffix) {
     const size_t n = std::char_traits<char>::length(suffix);
@@ -97,13 +101,14 @@ static void summary(const char* which, const Drive& d) {
 int main(int argc, char** argv) {
     if (argc < 5) { std::fprintf(stderr, kUsage, argv[0]); return 2; }
     double grid = 0.5;
-    bool mobile = false, prefetch = false;
+    bool mobile = false, prefetch = false, with_backend = false;
     long reps = 1;
     for (int i = 5; i < argc; ++i) {
         const std::string a = argv[i];
         char* end = nullptr;
         if (a == "--mobile") mobile = true;
         else if (a == "--prefetch") prefetch = true;
+        else if (a == "--backend") with_backend = true;
         else if (a == "--grid" && i + 1 < argc) { grid = std::strtod(argv[++i], &end); if (end == argv[i] || *end || !(grid > 0)) { std::fprintf(stderr, "error: --grid takes a positive number\n"); return 2; } }
         else if (a == "--reps" && i + 1 < argc) { reps = std::strtol(argv[++i], &end, 10); if (end == argv[i] || *end || reps < 1) { std::fprintf(stderr, "error: --reps takes a count >= 1\n"); return 2; } }
         else { std::fprintf(stderr, "error: unknown or incomplete argument %s\n", a.c_str()); std::fprintf(stderr, kUsage, argv[0]); return 2; }
@@ -139,12 +144,16 @@ int main(int argc, char** argv) {
         prm.grid_size = grid;
         prm.mobile = mobile ? 1 : 0;
         PCR::Frontend fe(*reg, map, &prm);
+        std::unique_ptr<backend::Backend> be;
+        if (with_backend) be.reset(new backend::Backend(map));
+        std::vector<std::string> events;
 
         Drive first, last;
         int differing = 0;
         for (long rep = 0; rep < reps; ++rep) {
             Drive d;
-            if (rep) fe.reset();
+            if (rep) { fe.reset(); if (be) be->reset(); }
+            size_t taken = 0;
             PCR::pose_t pose = start[0];
             const auto t0 = std::chrono::steady_clock::now();
             for (size_t k = 0; k < scans.size(); ++k) {
@@ -160,6 +169,22 @@ int main(int argc, char** argv) {
                 d.infos.push_back(info);
                 for (int i = 0; i < 5; ++i) d.step[i] += info.seconds[i];
                 d.step[0] += ahead;
+                if (be && info.keyframe_added) {      // optimHandler's NewKFCome, then lcHandler and the LC event; delta onto the odometry (Backend.cpp:321-346)
+                    const std::vector<int64_t> closest = fe.closest();
+                    backend::Backend::Info add, lc;
+                    be->step(closest.data() + taken, closest.size() - taken, &add, &lc);
+                    taken = closest.size();
+                    PCR::pose_t da, dl;
+                    std::memcpy(da.data(), add.delta, sizeof add.delta);
+                    std::memcpy(dl.data(), lc.delta, sizeof lc.delta);
+                    pose = product(dl, product(da, pose));
+                    if (rep == 0) {
+                        char line[160];
+                        std::snprintf(line, sizeof line, "backend %zu keyframes %lld candidates %d accepted %d lm_iterations %d %d", k, (long long)add.keyframes,
+                                      (int)lc.candidates, (int)lc.accepted, (int)add.graph.iterations, (int)lc.graph.iterations);
+                        events.push_back(line);
+                    }
+                }
             }
             const auto t1 = std::chrono::steady_clock::now();
             fe.finish();
@@ -175,6 +200,7 @@ int main(int argc, char** argv) {
             const pcr_frontend_info& i = first.infos[k];
             std::printf(" %d %d %d %d %lld\n", (int)i.converged, (int)i.iterations, (int)i.keyframe_added, (int)i.update_queued, (long long)i.n_submap);
         }
+        for (const std::string& e : events) std::printf("%s\n", e.c_str());
         summary("first", first);
         if (reps > 1) {
             summary("last", last);

@@ -96,6 +96,9 @@ ABI_SYMBOLS = [
     "pcr_graph_set_between_enabled", "pcr_graph_add_loop", "pcr_graph_between_weights", "pcr_graph_robust_rho_w",
     "pcr_graph_set_fixed", "pcr_graph_fixed",
     "pcr_voxel_sparse_default_params", "pcr_voxel_filter_sparse", "pcr_voxel_sparse_order", "pcr_map_update_all_sparse",
+    "pcr_kf_rank_near_host", "pcr_map_rank_near", "pcr_frontend_closest",
+    "pcr_backend_default_params", "pcr_backend_create", "pcr_backend_destroy", "pcr_backend_last_error", "pcr_backend_graph", "pcr_backend_sc",
+    "pcr_backend_register", "pcr_backend_add_keyframes", "pcr_backend_close_loops", "pcr_backend_loops", "pcr_backend_step", "pcr_backend_reset",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -155,6 +158,26 @@ class GraphResult(C.Structure):
     """struct pcr_graph_result (include/pcr_hip.h)."""
     _fields_ = [("iterations", C.c_int32), ("accepted", C.c_int32), ("pcg_iterations", C.c_int64), ("pcg_capped", C.c_int32), ("converged", C.c_int32),
                 ("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("lambda_", C.c_double), ("delta", C.c_double * 16)]
+
+
+class BackendParams(C.Structure):
+    """struct pcr_backend_params (include/pcr_hip.h)."""
+    _fields_ = [("grid_size", C.c_double), ("context_grid_size", C.c_double), ("history_range", C.c_int32), ("fitness_threshold", C.c_double),
+                ("detectors", C.c_int32), ("dist_radius", C.c_double), ("dist_exclude_recent", C.c_int32), ("lc_method", C.c_int32),
+                ("lc_between_refined", C.c_int32), ("sc", ScParams), ("graph", GraphParams)]
+
+
+class BackendLoop(C.Structure):
+    """struct pcr_backend_loop (include/pcr_hip.h)."""
+    _fields_ = [("cur", C.c_int64), ("old", C.c_int64), ("detector", C.c_int32), ("converged", C.c_int32), ("iterations", C.c_int32),
+                ("accepted", C.c_int32), ("fitness", C.c_double), ("pose", C.c_double * 16)]
+
+
+class BackendInfo(C.Structure):
+    """struct pcr_backend_info (include/pcr_hip.h)."""
+    _fields_ = [("keyframes", C.c_int64), ("contexts", C.c_int64), ("keyframes_added", C.c_int32), ("candidates", C.c_int32), ("accepted", C.c_int32),
+                ("factors_added", C.c_int32), ("optimized", C.c_int32), ("pad_", C.c_int32), ("graph", GraphResult), ("delta", C.c_double * 16),
+                ("seconds", C.c_double * 9)]
 
 
 class GlobalRelocCandidate(C.Structure):
@@ -369,6 +392,26 @@ def load_library():
     L.pcr_graph_fixed.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8)]
     L.pcr_graph_load_g2o.argtypes = [vp, C.c_char_p]
     L.pcr_graph_save_g2o.argtypes = [vp, C.c_char_p]
+    i64p = C.POINTER(C.c_int64)
+    L.pcr_kf_rank_near_host.argtypes = [dp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_double, C.c_int, i64p, dp]
+    L.pcr_map_rank_near.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int, C.c_double, C.c_int, i64p, dp]
+    L.pcr_frontend_closest.argtypes = [vp, i64p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pcr_backend_default_params.argtypes = [C.POINTER(BackendParams)]
+    L.pcr_backend_default_params.restype = None
+    L.pcr_backend_create.argtypes = [vp, C.POINTER(BackendParams)]
+    L.pcr_backend_create.restype = vp
+    L.pcr_backend_destroy.argtypes = [vp]
+    L.pcr_backend_destroy.restype = None
+    L.pcr_backend_last_error.argtypes = [vp]
+    L.pcr_backend_last_error.restype = C.c_char_p
+    for name in ("pcr_backend_graph", "pcr_backend_sc", "pcr_backend_register"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = vp
+    L.pcr_backend_add_keyframes.argtypes = [vp, i64p, C.c_size_t, C.POINTER(BackendInfo)]
+    L.pcr_backend_close_loops.argtypes = [vp, C.POINTER(BackendInfo)]
+    L.pcr_backend_loops.argtypes = [vp, C.POINTER(BackendLoop), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pcr_backend_step.argtypes = [vp, i64p, C.c_size_t, C.POINTER(BackendInfo), C.POINTER(BackendInfo)]
+    L.pcr_backend_reset.argtypes = [vp]
     _lib = L
     return L
 
@@ -1276,6 +1319,19 @@ class SubMap:
         self._check(self._lib.pcr_map_update_window(self._m, int(key), int(search_num), float(grid_size), C.byref(n)))
         return n.value
 
+    def rankNear(self, first, count, radius, k=1, num_exclude_recent=0):
+        """pcr_map_rank_near: key frames against key frames by the distance of their positions, on the device: for every query q of
+        [first, first + count) the k nearest candidates of [0, q - num_exclude_recent) with d2 <= radius^2, by (d2, index) ascending
+        -> (idx int64, d2 float64), each (count, k), row q - first; the tail is idx -1, d2 DBL_MAX.  Parent or view."""
+        first, count, k = int(first), int(count), int(k)
+        if first < 0 or count < 0:
+            raise PcrError("first and count must not be negative")
+        shape = (count, max(k, 0))
+        idx, d2 = np.full(shape, -1, np.int64), np.full(shape, np.finfo(np.float64).max)
+        self._check(self._lib.pcr_map_rank_near(self._m, first, count, int(num_exclude_recent), float(radius), k,
+                                                idx.ctypes.data_as(C.POINTER(C.c_int64)), d2.ctypes.data_as(C.POINTER(C.c_double))))
+        return idx, d2
+
     def pointer(self):
         """-> (device pointer, number of points, stride in bytes) of the assembled sub-map."""
         n, s = C.c_size_t(0), C.c_size_t(0)
@@ -1302,6 +1358,20 @@ class SubMap:
             if rc:
                 raise PcrError(f"hipMemcpy failed: {rc}")
         return out.cpu().numpy()
+
+
+def kf_rank_near_host(xyz, first, count, radius, k=1, num_exclude_recent=0):
+    """pcr_kf_rank_near_host (host only, no GPU): the definition of SubMap.rankNear over positions xyz (n, 3) -> (idx, d2), each (count, k)."""
+    xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+    first, count, k = int(first), int(count), int(k)
+    if first < 0 or count < 0:
+        raise PcrError("first and count must not be negative")
+    shape = (count, max(k, 0))
+    idx, d2 = np.full(shape, -1, np.int64), np.full(shape, np.finfo(np.float64).max)
+    if load_library().pcr_kf_rank_near_host(xyz.ctypes.data_as(C.POINTER(C.c_double)), xyz.shape[0], first, count, int(num_exclude_recent), float(radius), k,
+                                            idx.ctypes.data_as(C.POINTER(C.c_int64)), d2.ctypes.data_as(C.POINTER(C.c_double))):
+        raise PcrError("pcr_kf_rank_near_host: refused")
+    return idx, d2
 
 
 def pose_to_mobile(T):
@@ -1385,6 +1455,16 @@ class Frontend:
     def reset(self):
         """pcr_frontend_reset: a new session on the same handles (key frames, sub-map and the loop's state forgotten, device memory kept)."""
         self._check(self._lib.pcr_frontend_reset(self._fe))
+
+    def closest(self):
+        """pcr_frontend_closest -> int64 array, one entry per key frame this front end added: the key frame nearest to it when it was added
+        (mClosestKfIdx, the `from` of Backend::addOdomFactor's edge), -1 for the first."""
+        n = C.c_size_t(0)
+        self._check(self._lib.pcr_frontend_closest(self._fe, None, 0, C.byref(n)))
+        idx = np.zeros(n.value, np.int64)
+        if n.value:
+            self._check(self._lib.pcr_frontend_closest(self._fe, idx.ctypes.data_as(C.POINTER(C.c_int64)), n.value, C.byref(n)))
+        return idx
 
 
 class ScanContext:
@@ -1785,3 +1865,146 @@ class PoseGraph:
 
     def saveG2o(self, path):
         self._check(self._lib.pcr_graph_save_g2o(self._g, os.fsencode(path)))
+
+
+BACKEND_SC_QUERY, BACKEND_SC_RANK, BACKEND_DISTANCE = 1, 2, 4      # PCR_BACKEND_*: pcr_backend_params.detectors
+LC_VGICP, LC_GICP = 0, 1                                           # PCR_VGICP, PCR_GICP: pcr_backend_params.lc_method
+_LC_METHOD = {"vgicp": LC_VGICP, "gicp": LC_GICP}
+
+
+def backend_default_params():
+    p = BackendParams()
+    load_library().pcr_backend_default_params(C.byref(p))
+    return p
+
+
+def _borrowed(cls, owner, **fields):
+    """An object of `cls` over a handle that `owner` owns: its methods work, it keeps the owner alive and destroys nothing."""
+    class Borrowed(cls):
+        def __del__(self):
+            pass
+
+        def close(self):
+            pass
+    Borrowed.__name__ = cls.__name__
+    o = Borrowed.__new__(Borrowed)
+    o._lib = load_library()
+    o._owner = owner
+    o.__dict__.update(fields)
+    return o
+
+
+class Backend:
+    """The back end's key-frame and loop-closure loop in the library (pcr_backend_*): Backend::optimHandler's NewKFCome and LC events and
+    LoopClosureManager::lcHandler over a SubMap (borrowed, a parent) -- contexts from the raw key frames, saveKfs, prior / poses / odometry
+    factors, optimise, poses back into the store; loop candidates from ScanContext and / or the distance ranking, verified by VGICP or GICP
+    against the history window, accepted ones as loop factors, optimise again.  Keyword arguments are pcr_backend_params fields
+    (lc_method also as "vgicp" / "gicp"); sc=dict(...) and graph=dict(...) override fields of the nested pcr_sc_params / pcr_graph_params."""
+
+    STEPS = ("contexts", "downsample", "factors", "detect", "window", "scan2map", "fitness", "optimize", "set_poses")      # pcr_backend_info.seconds
+    _INFO_INTS = ("keyframes", "contexts", "keyframes_added", "candidates", "accepted", "factors_added", "optimized")
+
+    def __init__(self, submap, sc=None, graph=None, **params):
+        self._lib = load_library()
+        self._be = None
+        self.map = submap
+        p = backend_default_params()
+        for k, v in params.items():
+            if k in ("sc", "graph", "pad_") or not hasattr(p, k):
+                raise ValueError(f"unknown back-end parameter {k}")
+            setattr(p, k, _LC_METHOD[v] if k == "lc_method" and isinstance(v, str) else v)
+        for k, v in (sc or {}).items():
+            if not hasattr(p.sc, k):
+                raise ValueError(f"unknown ScanContext parameter {k}")
+            setattr(p.sc, k, v)
+        for k, v in (graph or {}).items():
+            if k == "struct_size" or not hasattr(p.graph, k):
+                raise ValueError(f"unknown pose-graph parameter {k}")
+            setattr(p.graph, k, _graph_precond(v) if k == "pcg_preconditioner" else v)
+        self.params = p
+        self._be = self._lib.pcr_backend_create(submap._m, C.byref(p))
+        if not self._be:
+            raise PcrError(self._lib.pcr_backend_last_error(None).decode())
+
+    def __del__(self):
+        try:
+            if self._be:
+                self._lib.pcr_backend_destroy(self._be)
+                self._be = None
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc:
+            raise PcrError(self._lib.pcr_backend_last_error(self._be).decode())
+
+    @property
+    def graph(self):
+        """pcr_backend_graph as a PoseGraph (borrowed)."""
+        return _borrowed(PoseGraph, self, _g=self._lib.pcr_backend_graph(self._be))
+
+    @property
+    def sc(self):
+        """pcr_backend_sc as a ScanContext (borrowed; pcr_backend_reset replaces the handle, so ask again after a reset)."""
+        return _borrowed(ScanContext, self, _s=self._lib.pcr_backend_sc(self._be), _height=float(self.params.sc.lidar_height),
+                         _dist_thres=float(np.float32(self.params.sc.dist_thres)))
+
+    @property
+    def register(self):
+        """pcr_backend_register as a VgicpRegister / GicpRegister (borrowed)."""
+        h = self._lib.pcr_backend_register(self._be)
+        prm = PcrParams()
+        self._lib.pcr_get_params(h, C.byref(prm))
+        buf, conv = (C.c_double * 16)(), C.c_int(0)
+        return _borrowed(GicpRegister if self.params.lc_method == LC_GICP else VgicpRegister, self, _h=h, params=prm, isConverge=False, _pose_buf=buf,
+                         _pose_cm=np.frombuffer(buf, dtype=np.float64).reshape(4, 4), _conv=conv, _conv_ref=C.byref(conv), _seen={})
+
+    def _info(self, i):
+        out = {f: int(getattr(i, f)) for f in self._INFO_INTS}
+        out["graph"] = GraphResultView(i.graph)
+        out["delta"] = _pose_out(np.array(i.delta[:], dtype=np.float64))
+        out["seconds"] = dict(zip(self.STEPS, i.seconds))
+        return out
+
+    @staticmethod
+    def _closest(closest):
+        if closest is None:
+            return None, None, 0
+        a = np.ascontiguousarray(closest, dtype=np.int64).reshape(-1)
+        return a, a.ctypes.data_as(C.POINTER(C.c_int64)), a.size
+
+    def addKeyFrames(self, closest=None):
+        """pcr_backend_add_keyframes: the NewKFCome event for the key frames the store has gained.  closest: Frontend.closest()'s entries for
+        exactly those key frames (None: every odometry edge from i - 1) -> info dict (delta 4x4, graph: GraphResultView, seconds by step)."""
+        _keep, ptr, n = self._closest(closest)
+        i = BackendInfo()
+        self._check(self._lib.pcr_backend_add_keyframes(self._be, ptr, n, C.byref(i)))
+        return self._info(i)
+
+    def closeLoops(self):
+        """pcr_backend_close_loops: lcHandler over the contexts not yet walked, then the LC event when a loop was accepted -> info dict."""
+        i = BackendInfo()
+        self._check(self._lib.pcr_backend_close_loops(self._be, C.byref(i)))
+        return self._info(i)
+
+    def loops(self):
+        """pcr_backend_loops -> the candidate records of the last closeLoops(): list of dict(cur, old, detector, converged, iterations,
+        accepted, fitness, pose 4x4)."""
+        n = C.c_size_t(0)
+        self._check(self._lib.pcr_backend_loops(self._be, None, 0, C.byref(n)))
+        raw = (BackendLoop * max(n.value, 1))()
+        if n.value:
+            self._check(self._lib.pcr_backend_loops(self._be, raw, n.value, C.byref(n)))
+        return [dict(cur=int(r.cur), old=int(r.old), detector=int(r.detector), converged=int(r.converged), iterations=int(r.iterations),
+                     accepted=int(r.accepted), fitness=float(r.fitness), pose=_pose_out(np.array(r.pose[:], dtype=np.float64))) for r in raw[:n.value]]
+
+    def step(self, closest=None):
+        """pcr_backend_step: addKeyFrames then closeLoops -> (info of the first, info of the second)."""
+        _keep, ptr, n = self._closest(closest)
+        a, b = BackendInfo(), BackendInfo()
+        self._check(self._lib.pcr_backend_step(self._be, ptr, n, C.byref(a), C.byref(b)))
+        return self._info(a), self._info(b)
+
+    def reset(self):
+        """pcr_backend_reset: the graph, the contexts and the counters start over; the store is left alone."""
+        self._check(self._lib.pcr_backend_reset(self._be))

@@ -112,6 +112,38 @@ def drive_frontend(fe, scans, cmds, start_pose, prefetch=False):
                 updates=info["updates"] if info else 0, seconds=clock() - t0, scan2map_seconds=ts["scan2map"], step_seconds=ts)
 
 
+def drive_slam(fe, be, scans, cmds, start_pose, prefetch=False):
+    """drive_frontend() with the back end behind it: fe = pcr.Frontend, be = pcr.Backend over the same SubMap.  After every scan that added a key
+    frame, be.step(closest) runs both events -- the key frames since the last one with Frontend.closest()'s entries for them as the odometry edges'
+    `from`, then the loop closure -- and each event's delta is applied to the pose the next scan starts from (delta @ pose: what optimHandler does
+    to the global odometry and odom2map, Backend.cpp:321-346).  The front end's own key-frame positions (both gap rules) stay as it recorded them.
+    -> drive_frontend()'s dict plus events: a list of (scan index, add info, loop info, be.loops())."""
+    pose = np.array(start_pose, float)
+    poses, conv, iters, sub_n, events = [], [], [], [], []
+    ts = dict.fromkeys(fe.STEPS, 0.0)
+    clock = time.perf_counter
+    info = None
+    taken = 0
+    t0 = clock()
+    for k, scan in enumerate(scans):
+        if prefetch and k + 1 < len(scans):
+            t1 = clock(); fe.prefetch(scans[k + 1]); ts["voxel"] += clock() - t1
+        pose, info = fe.step(scan, pose @ cmds[k])
+        if k: sub_n.append(info["n_submap"])
+        conv.append(bool(info["converged"])); iters.append(info["iterations"])
+        for name, sec in info["seconds"].items(): ts[name] += sec
+        poses.append(pose)
+        if info["keyframe_added"]:
+            closest = fe.closest()
+            add, lc = be.step(closest[taken:])
+            taken = len(closest)
+            events.append((k, add, lc, be.loops()))
+            pose = lc["delta"] @ (add["delta"] @ pose)
+    t1 = clock(); sub_n.append(fe.finish()); ts["wait"] += clock() - t1
+    return dict(poses=poses, converged=conv, iterations=iters, submap_points=sub_n, keyframes=info["keyframes"] if info else 0,
+                updates=info["updates"] if info else 0, seconds=clock() - t0, scan2map_seconds=ts["scan2map"], step_seconds=ts, events=events)
+
+
 class GpuFront:
     """The four steps through the C ABI; scans are CUDA tensors (uploaded once, outside the timed loop), the sub-map never leaves HBM."""
 
