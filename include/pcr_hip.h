@@ -1199,7 +1199,8 @@ pcr_sc* pcr_backend_sc(pcr_backend* be);
 pcr_handle* pcr_backend_register(pcr_backend* be);
 /* optimHandler's NewKFCome event for key frames [done, pcr_map_keyframes) (done: the key frames earlier events took), in the reference's order:
  *   1. pcr_sc_add_keyframes(map, done, count, context_grid_size): contexts from the RAW key frames, before saveKfs filters them;
- *   2. grid_size > 0: pcr_map_downsample_keyframes(map, done, grid_size) (saveKfs);
+ *   2. grid_size > 0: pcr_map_downsample_keyframes(map, done, grid_size) (saveKfs); with a save directory (pcr_backend_set_save_dir) the new key
+ *      frames are written raw first;
  *   3. an empty graph: pcr_graph_add_prior on pose 0 at key frame 0's pose with pcr_graph_noise(PRIOR) (the factor may precede its pose);
  *   4. pcr_graph_add_poses of the new key frames' stored poses;
  *   5. per new key frame i > 0 pcr_graph_add_between_poses(closest[i - done], i, pcr_graph_noise(ODOM)); closest == NULL: from i - 1.
@@ -1230,6 +1231,77 @@ int pcr_backend_step(pcr_backend* be, const int64_t* closest, size_t n_closest, 
  * Failures follow pcr_frontend's rule: the inner call's message under the step's name, the state what the completed parts left, further
  * events refused until pcr_backend_reset. */
 int pcr_backend_reset(pcr_backend* be);
+
+/* ---- A session on disk: key-frame clouds, poses, graph and contexts ------------------------------------------------------------------------
+ * The reference's saveMapDir: {i}.pcd, the RAW key frame i (MapManager::saveKfs, frontend/src/MapManager.cpp:203-213); tum.txt, one pose per
+ * key frame (utils::file::writeAsTum in Backend::~Backend, common/utils/File.hpp:49-66, backend/src/Backend.cpp:349-358); fg.g2o, the factor
+ * graph (myWriteG2o).  MapManager::MapManager() (MapManager.cpp:18-50) and Backend::Gtsam::loadFactorGraph (Backend.cpp:202-222) read it at
+ * the next start.  No kernel of its own: a load is pcr_map_add_keyframe, pcr_sc_add_keyframes, pcr_map_downsample_keyframes and
+ * pcr_graph_load_g2o in the back end's order.  DESIGN 4.19.
+ *
+ * The file formats, host only (no GPU is needed to call them).  Their failures leave a message in pcr_session_last_error (per thread). */
+const char* pcr_session_last_error(void);
+/* One line of writeAsTum into buf, NUL-terminated: "%.3f %.3f %.3f %.3f %.6f %.6f %.6f %.6f\n" of stamp, t, q.x, q.y, q.z, q.w; the
+ * quaternion is Eigen::Quaternion(R)'s (the trace / largest-diagonal branches T2SE3 uses, NOT normalised); pose16 is column-major.  The
+ * format is LOSSY: a translation comes back within 5e-4 m, a quaternion component within 5e-7.  precise != 0 writes every number as %.17g
+ * instead: every double comes back as it was.  Nonzero when the stamp or the pose is not finite, or when capacity cannot hold the line
+ * and its NUL (the message says how many bytes it takes; buf is left alone). */
+int pcr_tum_format(double stamp, const double pose16[16], int precise, char* buf, size_t capacity);
+/* One line as loadFromTum reads it (File.hpp:69-95): stamp, t.x t.y t.z, q.x q.y q.z q.w, separated by blanks; what follows the eighth
+ * number is ignored.  pose = identity . translate(t) . rotate(q) with Eigen's toRotationMatrix of the quaternion AS READ, NOT normalised
+ * (the products with the identity are not carried out: they could change the sign of a zero and nothing else): six digits give a rotation
+ * that is orthonormal to about 1e-6 only, and a caller who wants more applies T2SE3.  PCR_TUM_OK: stamp (may be NULL) and pose16 are
+ * written.  PCR_TUM_SKIP: the line is empty or blank and nothing is written (the reference pushes a pose built from uninitialised numbers
+ * there).  PCR_TUM_ERROR: fewer than eight numbers; the message quotes the line. */
+enum { PCR_TUM_OK = 0, PCR_TUM_ERROR = 1, PCR_TUM_SKIP = 2 };
+int pcr_tum_parse(const char* line, double* stamp, double pose16[16]);
+/* pcp::savePCDFile (binary: pcl::io::savePCDFileBinary's "x y z intensity" F 4) and pcp::loadPCDFile over host memory of n points,
+ * stride_bytes apart (a multiple of 4, >= 12).  The intensity is float 3 of a 16-byte point, float 4 of a point of 20 bytes or more
+ * (pcl::PointXYZI: float 3 is then written as 1 on a read and the floats behind the intensity as 0) and absent from a 12-byte point (0 in
+ * the file).  n = 0 writes a valid file with POINTS 0, which reads back as 0 points.  Non-finite values travel as their bytes.
+ * read: *n is the file's point count whenever the header could be read; a capacity below it fails and writes nothing else (out == NULL
+ * with capacity 0: the count alone).  The reader takes every PCD the mirror's takes: ascii, binary, binary_compressed, any field order. */
+int pcr_pcd_write(const char* path, const void* pts, size_t n, size_t stride_bytes);
+int pcr_pcd_read(const char* path, void* out, size_t capacity_points, size_t stride_bytes, size_t* n);
+
+/* {dir}/{i}.pcd for key frames [first, n) as the store holds them NOW (after pcr_map_downsample_keyframes: the filtered clouds; the raw
+ * ones can only be written before it, see pcr_backend_set_save_dir) and {dir}/tum.txt, rewritten, for ALL n key frames.  stamps: n
+ * entries, or NULL for stamp i = i.  A queued assembly is collected first.  Parent or view; the directory must exist; first > n is an
+ * error.  The first failure names the file (pcr_map_last_error) and leaves earlier files as written. */
+int pcr_map_save(const pcr_map* m, const char* dir, size_t first, const double* stamps, int precise);
+/* The loading constructor (MapManager.cpp:33-49) into a store WITHOUT key frames (else refused, nothing changed): line i of {dir}/tum.txt
+ * (blank lines do not count) gives the pose of {dir}/{i}.pcd, added by pcr_map_add_keyframe in the store's point layout (16 bytes when it
+ * never held a key frame); grid_size > 0: then pcr_map_downsample_keyframes(m, 0, grid_size) (:46).  The poses are NOT normalised.
+ * stamps (may be NULL) gets the first `capacity` stamps; *n_loaded (may be NULL) the number of key frames.  Every file is read and checked
+ * before the store changes: a missing or unreadable PCD or a bad line fails with the store still empty and a message that names the file
+ * or the line (1-based).  A missing tum.txt returns 0 with *n_loaded = 0: the reference warns and starts fresh. */
+int pcr_map_load(pcr_map* m, const char* dir, double grid_size, double* stamps, size_t capacity, size_t* n_loaded);
+
+/* saveMapDir of the back end.  NULL or "": off (the default), every call does what it did.  Set: step 2 of pcr_backend_add_keyframes
+ * writes {dir}/{i}.pcd of each new key frame RAW, before the in-place filter (saveKfs' order: the filter destroys the raw cloud, so this
+ * is the one moment it can be saved); a failure there is the event's failure under the step name "save". */
+int pcr_backend_set_save_dir(pcr_backend* be, const char* dir);
+/* What ~Backend does: {dir}/tum.txt of all key frames of the store (pcr_map_save's writer; stamps: one per key frame or NULL) and
+ * {dir}/fg.g2o (pcr_graph_save_g2o: no priors, robust marks or switches; FIX records and switched-off factors as it writes them).
+ * Refused without a save directory. */
+int pcr_backend_save(pcr_backend* be, const double* stamps, int precise);
+/* A session back into a freshly created or reset back end over an EMPTY store, in the back end's own order:
+ *   1. pcr_map_load(map, dir, grid_size <= 0): the raw key frames;
+ *   2. pcr_sc_add_keyframes(map, 0, n, context_grid_size): the contexts from the raw clouds.  (The reference builds none for loaded key
+ *      frames -- addContext starts at mKFNums -- so a second session there never closes a loop onto the first; here it can.)
+ *   3. params.grid_size > 0: pcr_map_downsample_keyframes(map, 0, grid_size);
+ *   4. pcr_graph_load_g2o(graph, dir/fg.g2o).
+ * Then the counters stand behind the loaded key frames: the next pcr_backend_add_keyframes takes the key frames added after the load,
+ * pcr_backend_close_loops their contexts as queries with every loaded key frame as a candidate.  The store's poses are tum.txt's; the
+ * graph's are its own vertices until the next optimisation writes them back.  info (may be NULL): keyframes, contexts, keyframes_added,
+ * seconds[contexts, downsample, factors = the graph's load]; pcr_backend_load_seconds has the whole split.  stamps / capacity as
+ * pcr_map_load.  Refused BEFORE anything changes: key frames in the store or poses in the graph or contexts in the database; no fg.g2o
+ * (without the graph the first component has no prior: pcr_map_load is the map-only load, and the message says so); a fg.g2o that does
+ * not load or whose vertex count differs from tum.txt's key-frame count; a bad line or PCD.  A failure after that (a HIP error) leaves
+ * the back end failed until pcr_backend_reset, as with the events. */
+int pcr_backend_load(pcr_backend* be, const char* dir, double* stamps, size_t capacity, pcr_backend_info* info);
+/* Host time of the last pcr_backend_load: reading the files, uploading the key frames, contexts, in-place filter, graph. */
+int pcr_backend_load_seconds(const pcr_backend* be, double seconds[5]);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@
 
 #include "handle.h"
 #include "graph_math.h"
+#include "backend_state.h"
 
 using namespace pcr;
 
@@ -23,21 +24,7 @@ void identity16(double* T) { for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 
 
 }  // namespace
 
-struct pcr_backend {
-    pcr_map* map = nullptr;         // borrowed: the store (a parent)
-    pcr_map* view = nullptr;        // lc_map_
-    pcr_sc* sc = nullptr;
-    pcr_handle* reg = nullptr;      // pcr_ with initForLC's settings
-    pcr_graph* graph = nullptr;
-    pcr_backend_params prm{};
-    int device = 0;
-    size_t done = 0;                // key frames the graph holds
-    size_t lc_done = 0;             // contexts lcHandler has walked (lc_size_)
-    std::vector<pcr_backend_loop> loops;
-    bool failed = false;            // an inner call of an event failed: the state is partial until pcr_backend_reset
-    std::string failure;
-    std::string err;
-};
+// (struct pcr_backend: backend_state.h, shared with session_host.hip)
 
 namespace {
 
@@ -186,7 +173,11 @@ int pcr_backend_add_keyframes(pcr_backend* be, const int64_t* closest, size_t n_
     auto t0 = std::chrono::steady_clock::now();
     if (pcr_sc_add_keyframes(be->sc, be->map, first, count, be->prm.context_grid_size, nullptr)) return inner_fail(be, "contexts", pcr_sc_last_error(be->sc));
     inf.seconds[kContexts] = seconds_since(t0);
-    // 2. saveKfs (:288)
+    // 2. saveKfs (:288): with a save directory the raw clouds go to disk first -- the filter below destroys them (MapManager.cpp:209-211)
+    if (!be->save_dir.empty()) {
+        std::string msg;
+        if (session_write_keyframes(be->map, be->save_dir, first, &msg)) return inner_fail(be, "save", msg.c_str());
+    }
     if (be->prm.grid_size > 0) {
         t0 = std::chrono::steady_clock::now();
         if (pcr_map_downsample_keyframes(be->map, first, be->prm.grid_size, nullptr)) return inner_fail(be, "downsample", pcr_map_last_error(be->map));

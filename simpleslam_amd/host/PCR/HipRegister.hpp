@@ -253,6 +253,45 @@ public:
         if (pcr_map_downsample_keyframes(m_, first, grid_size, &n)) throw std::runtime_error(pcr_map_last_error(m_));
         return n;
     }
+    // A session on disk (pcr_map_save / pcr_map_load; the reference's saveMapDir).  save: {dir}/{i}.pcd for key frames first .. end as the
+    // store holds them now and tum.txt for all of them (stamps: one per key frame, empty: the index); the default tum.txt rounds to the
+    // millimetre and to 1e-6, precise writes 17 digits.  load (MapManager::MapManager(), MapManager.cpp:33-49) into a store without key frames:
+    // tum.txt's poses -- quaternions as read, NOT normalised -- and {i}.pcd, then with grid_size > 0 the in-place filter; returns the stamps
+    // (none when there is no tum.txt).  The loaded key frames are PointXYZI records, like every cloud of this class.
+    void save(const std::string& dir, size_t first = 0, const std::vector<double>& stamps = {}, bool precise = false) const {
+        if (!stamps.empty() && stamps.size() != keyframes()) throw std::runtime_error("SubMap::save: one stamp per key frame");
+        if (pcr_map_save(m_, dir.c_str(), first, stamps.empty() ? nullptr : stamps.data(), precise ? 1 : 0)) throw std::runtime_error(pcr_map_last_error(m_));
+    }
+    std::vector<double> load(const std::string& dir, double grid_size = 0.0) {
+        usePointXYZI();
+        size_t n = 0;
+        if (pcr_map_load(m_, dir.c_str(), grid_size, nullptr, 0, &n)) throw std::runtime_error(pcr_map_last_error(m_));
+        return stampsOf(dir, n);
+    }
+    // a store that never held a key frame takes its point layout from the first one: an empty PointXYZI key frame, added and cleared
+    // again, fixes it (pcr_map_clear keeps the layout) so that a load fills the store with the records addKeyFrame appends later
+    void usePointXYZI() {
+        size_t stride = 0;
+        (void)pcr_map_keyframe(m_, 0, nullptr, &stride, nullptr);
+        if (stride != 0 || m_ == nullptr || keyframes() != 0) return;
+        const pose_t eye;
+        if (pcr_map_add_keyframe(m_, nullptr, 0, sizeof(PointXYZI), 0, eye.data()) || pcr_map_clear(m_)) throw std::runtime_error(pcr_map_last_error(m_));
+    }
+    // the stamps of the first n non-blank lines of {dir}/tum.txt (pcr_tum_parse)
+    static std::vector<double> stampsOf(const std::string& dir, size_t n) {
+        std::vector<double> stamps;
+        FILE* f = n ? std::fopen((dir + "/tum.txt").c_str(), "r") : nullptr;
+        if (!f) return stamps;
+        std::string line;
+        for (int c = 0; stamps.size() < n && c != EOF;) {
+            line.clear();
+            while ((c = std::fgetc(f)) != EOF && c != '\n') line.push_back((char)c);
+            double stamp = 0, pose[16];
+            if (pcr_tum_parse(line.c_str(), &stamp, pose) == PCR_TUM_OK) stamps.push_back(stamp);
+        }
+        std::fclose(f);
+        return stamps;
+    }
     // another sub-map over the same key frames (pcr_map_view); this object must outlive it, or the view fails every call from then on
     std::unique_ptr<SubMap> view() {
         pcr_map* v = pcr_map_view(m_);
@@ -748,12 +787,13 @@ public:
 // pcr_graph_save_g2o, pcr_sc_descriptor, pcr_get_stats, ...); sc() is a new handle after reset().
 class Backend {
     pcr_backend* be_ = nullptr;
+    PCR::SubMap& map_;
     void check(int rc) const { if (rc) throw std::runtime_error(pcr_backend_last_error(be_)); }
 public:
     using Info = pcr_backend_info;
     using Loop = pcr_backend_loop;
     static pcr_backend_params defaults() { pcr_backend_params p; pcr_backend_default_params(&p); return p; }
-    explicit Backend(PCR::SubMap& map, const pcr_backend_params* p = nullptr) : be_(pcr_backend_create(map.handle(), p)) {
+    explicit Backend(PCR::SubMap& map, const pcr_backend_params* p = nullptr) : be_(pcr_backend_create(map.handle(), p)), map_(map) {
         if (!be_) throw std::runtime_error(pcr_backend_last_error(nullptr));
     }
     Backend(const Backend&) = delete;
@@ -771,6 +811,19 @@ public:
         return out;
     }
     void reset() { check(pcr_backend_reset(be_)); }
+    // saveMapDir (pcr_backend_set_save_dir; "" = off): addKeyFrames then writes {dir}/{i}.pcd of every new key frame raw, before saveKfs' filter
+    void setSaveDir(const std::string& dir) { check(pcr_backend_set_save_dir(be_, dir.c_str())); }
+    // ~Backend's tum.txt and fg.g2o into the save directory (stamps: one per key frame, empty: the index)
+    void save(const std::vector<double>& stamps = {}, bool precise = false) { check(pcr_backend_save(be_, stamps.empty() ? nullptr : stamps.data(), precise ? 1 : 0)); }
+    // pcr_backend_load into a fresh or reset back end over an empty store: raw key frames, their contexts, the filter, the graph; the next
+    // events take what comes after.  Returns the stamps.
+    std::vector<double> load(const std::string& dir, Info* info = nullptr) {
+        map_.usePointXYZI();
+        Info i;
+        check(pcr_backend_load(be_, dir.c_str(), nullptr, 0, &i));
+        if (info) *info = i;
+        return PCR::SubMap::stampsOf(dir, (size_t)i.keyframes);
+    }
     pcr_graph* graph() { return pcr_backend_graph(be_); }
     pcr_sc* sc() { return pcr_backend_sc(be_); }
     pcr_handle* reg() { return pcr_backend_register(be_); }

@@ -1,6 +1,6 @@
 // seq_harness.cpp -- the front end's per-scan loop driven from C++: LidarOdometry::handler around scan2Map (frontend/src/LidarOdometry.cpp:160-214,
 // frontend/src/MapManager.cpp:109-201) over a recording, through PCR::Frontend (pcr_frontend_*: the loop itself lives in the library).
-//   seq_harness <method> <list.txt> <cmds.txt> <start.txt> [--grid g] [--mobile] [--prefetch] [--reps r] [--backend]
+//   seq_harness <method> <list.txt> <cmds.txt> <start.txt> [--grid g] [--mobile] [--prefetch] [--reps r] [--backend] [--save DIR] [--load DIR]
 // method     loam | ndt | vgicp | gicp | liorf (the factory of LidarOdometry.cpp:44-54: unknown throws)
 // list.txt   one scan file per line: .pcd (pcp/pcd_io.hpp) or raw float records x y z intensity (.f32, as the other harnesses read them)
 // cmds.txt   one 4x4 per line, 16 numbers row by row: cmds[k] = the motion from scan k-1 to scan k as the odometer reports it (cmds[0]: identity)
@@ -10,6 +10,10 @@
 // --backend  backend::Backend (pcr_backend_*) behind the front end, as sequence.drive_slam has it: after every scan that added a key frame,
 //            pcr_backend_step with Frontend::closest()'s new entries, and the next guess starts from lc.delta * (add.delta * pose) (the same
 //            fixed-order product).  Prints one "backend k ..." line per event of the first drive: key frames, candidates, accepted, LM iterations
+// --save DIR the session goes to DIR (which must exist) as the reference's saveMapDir: every new key frame raw as {i}.pcd from inside the add event,
+//            tum.txt and fg.g2o at the end of the drive; prints "saved keyframes n".  --load DIR starts from such a session: backend::Backend::load
+//            before the first scan, the sub-map about the start pose, then the drive goes on behind the loaded key frames; prints "loaded keyframes
+//            n".  Both imply --backend and take one drive (--reps 1).
 // The scans are uploaded before the timed loop (into a key-frame store of their own: no HIP call in this file).  generateOdom's guess is chained
 // here, init = pose * cmds[k], by one fixed-order product -- rows times columns, every entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3, no contraction --
 // so that any caller can repeat it to the bit.
@@ -29,7 +33,7 @@
 #include "PCR/HipRegister.hpp"
 #include "pcp/pcd_io.hpp"
 
-static const char* kUsage = "usage: %s <loam|ndt|vgicp|gicp|liorf> <list.txt> <cmds.txt> <start.txt> [--grid g] [--mobile] [--prefetch] [--reps r] [--backend]\n";
+static const char* kUsage = "usage: %s <loam|ndt|vgicp|gicp|liorf> <list.txt> <cmds.txt> <start.txt> [--grid g] [--mobile] [--prefetch] [--reps r] [--backend] [--save DIR] [--load DIR]\n";
 
 static bool ends_with(const std::string& s, const char* suffix) {
     const size_t n = std::char_traits<char>::length(suffix);
@@ -103,16 +107,20 @@ int main(int argc, char** argv) {
     double grid = 0.5;
     bool mobile = false, prefetch = false, with_backend = false;
     long reps = 1;
+    std::string save_dir, load_dir;
     for (int i = 5; i < argc; ++i) {
         const std::string a = argv[i];
         char* end = nullptr;
         if (a == "--mobile") mobile = true;
         else if (a == "--prefetch") prefetch = true;
         else if (a == "--backend") with_backend = true;
+        else if (a == "--save" && i + 1 < argc) { save_dir = argv[++i]; with_backend = true; }
+        else if (a == "--load" && i + 1 < argc) { load_dir = argv[++i]; with_backend = true; }
         else if (a == "--grid" && i + 1 < argc) { grid = std::strtod(argv[++i], &end); if (end == argv[i] || *end || !(grid > 0)) { std::fprintf(stderr, "error: --grid takes a positive number\n"); return 2; } }
         else if (a == "--reps" && i + 1 < argc) { reps = std::strtol(argv[++i], &end, 10); if (end == argv[i] || *end || reps < 1) { std::fprintf(stderr, "error: --reps takes a count >= 1\n"); return 2; } }
         else { std::fprintf(stderr, "error: unknown or incomplete argument %s\n", a.c_str()); std::fprintf(stderr, kUsage, argv[0]); return 2; }
     }
+    if ((!save_dir.empty() || !load_dir.empty()) && reps != 1) { std::fprintf(stderr, "error: --save and --load take one drive (--reps 1)\n"); return 2; }
     try {
         auto reg = std::dynamic_pointer_cast<PCR::HipRegister>(PCR::makeRegister(argv[1]));      // throws on an unknown type, LidarOdometry.cpp:50-54
         pcr_set_profile(reg->handle(), 0);      // no timing events inside the calls: the drive is timed from outside, as bench.py times its own
@@ -143,9 +151,16 @@ int main(int argc, char** argv) {
         pcr_frontend_default_params(&prm);
         prm.grid_size = grid;
         prm.mobile = mobile ? 1 : 0;
-        PCR::Frontend fe(*reg, map, &prm);
         std::unique_ptr<backend::Backend> be;
         if (with_backend) be.reset(new backend::Backend(map));
+        if (!load_dir.empty()) {      // before the front end exists: it takes over the store as it finds it, key frames and sub-map
+            const std::vector<double> stamps = be->load(load_dir);
+            std::printf("loaded keyframes %zu\n", stamps.size());
+            const double at[3] = {start[0](0, 3), start[0](1, 3), start[0](2, 3)};
+            if (!stamps.empty()) map.updateMap(at, prm.radius, prm.grid_size);
+        }
+        if (!save_dir.empty()) be->setSaveDir(save_dir);
+        PCR::Frontend fe(*reg, map, &prm);
         std::vector<std::string> events;
 
         Drive first, last;
@@ -201,6 +216,10 @@ int main(int argc, char** argv) {
             std::printf(" %d %d %d %d %lld\n", (int)i.converged, (int)i.iterations, (int)i.keyframe_added, (int)i.update_queued, (long long)i.n_submap);
         }
         for (const std::string& e : events) std::printf("%s\n", e.c_str());
+        if (!save_dir.empty()) {
+            be->save();
+            std::printf("saved keyframes %zu\n", map.keyframes());
+        }
         summary("first", first);
         if (reps > 1) {
             summary("last", last);

@@ -99,6 +99,8 @@ ABI_SYMBOLS = [
     "pcr_kf_rank_near_host", "pcr_map_rank_near", "pcr_frontend_closest",
     "pcr_backend_default_params", "pcr_backend_create", "pcr_backend_destroy", "pcr_backend_last_error", "pcr_backend_graph", "pcr_backend_sc",
     "pcr_backend_register", "pcr_backend_add_keyframes", "pcr_backend_close_loops", "pcr_backend_loops", "pcr_backend_step", "pcr_backend_reset",
+    "pcr_session_last_error", "pcr_tum_format", "pcr_tum_parse", "pcr_pcd_write", "pcr_pcd_read", "pcr_map_save", "pcr_map_load",
+    "pcr_backend_set_save_dir", "pcr_backend_save", "pcr_backend_load", "pcr_backend_load_seconds",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -412,6 +414,18 @@ def load_library():
     L.pcr_backend_loops.argtypes = [vp, C.POINTER(BackendLoop), C.c_size_t, C.POINTER(C.c_size_t)]
     L.pcr_backend_step.argtypes = [vp, i64p, C.c_size_t, C.POINTER(BackendInfo), C.POINTER(BackendInfo)]
     L.pcr_backend_reset.argtypes = [vp]
+    L.pcr_session_last_error.argtypes = []
+    L.pcr_session_last_error.restype = C.c_char_p
+    L.pcr_tum_format.argtypes = [C.c_double, dp, C.c_int, C.c_char_p, C.c_size_t]
+    L.pcr_tum_parse.argtypes = [C.c_char_p, dp, dp]
+    L.pcr_pcd_write.argtypes = [C.c_char_p, vp, C.c_size_t, C.c_size_t]
+    L.pcr_pcd_read.argtypes = [C.c_char_p, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pcr_map_save.argtypes = [vp, C.c_char_p, C.c_size_t, dp, C.c_int]
+    L.pcr_map_load.argtypes = [vp, C.c_char_p, C.c_double, dp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pcr_backend_set_save_dir.argtypes = [vp, C.c_char_p]
+    L.pcr_backend_save.argtypes = [vp, dp, C.c_int]
+    L.pcr_backend_load.argtypes = [vp, C.c_char_p, dp, C.c_size_t, C.POINTER(BackendInfo)]
+    L.pcr_backend_load_seconds.argtypes = [vp, dp]
     _lib = L
     return L
 
@@ -1189,6 +1203,77 @@ def comm_unique_id():
     return bytes(buf)
 
 
+TUM_OK, TUM_ERROR, TUM_SKIP = 0, 1, 2      # PCR_TUM_*: what pcr_tum_parse returns
+
+
+def _session_error():
+    return PcrError(load_library().pcr_session_last_error().decode())
+
+
+def tum_format(stamp, pose, precise=False, capacity=512):
+    """pcr_tum_format -> one line of tum.txt (bytes, with its newline): writeAsTum's "%.3f %.3f %.3f %.3f %.6f %.6f %.6f %.6f" of stamp, t and
+    Eigen::Quaternion(R) as x y z w -- lossy; precise=True writes %.17g.  A non-finite pose or a capacity that cannot hold the line raises."""
+    buf = C.create_string_buffer(max(int(capacity), 1))
+    pc = _pose_in(pose)
+    if load_library().pcr_tum_format(float(stamp), pc.ctypes.data_as(C.POINTER(C.c_double)), int(bool(precise)), buf, int(capacity)):
+        raise _session_error()
+    return buf.value
+
+
+def tum_parse(line):
+    """pcr_tum_parse -> (stamp, 4x4 pose) as loadFromTum reads a line (the quaternion is NOT normalised), or None for a blank line; fewer than
+    eight numbers raise with the line in the message."""
+    if isinstance(line, str):
+        line = line.encode()
+    stamp, pose = C.c_double(0), np.zeros(16)
+    rc = load_library().pcr_tum_parse(line, C.byref(stamp), pose.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc == TUM_SKIP:
+        return None
+    if rc != TUM_OK:
+        raise _session_error()
+    return stamp.value, _pose_out(pose)
+
+
+def pcd_write(path, cloud):
+    """pcr_pcd_write: a host array (n, >=3) float32 as a binary "x y z intensity" PCD (pcp::savePCDFile); the intensity is column 3 of a
+    4-column cloud, column 4 of a wider one."""
+    a = np.ascontiguousarray(cloud, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] < 3:
+        raise ValueError("clouds must have shape (n, >=3)")
+    if load_library().pcr_pcd_write(os.fsencode(path), a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1] * 4):
+        raise _session_error()
+
+
+def pcd_read(path, columns=4):
+    """pcr_pcd_read -> (n, columns) float32 (pcp::loadPCDFile): 4 columns x y z intensity; 8 the pcl::PointXYZI layout x y z 1 intensity 0 0 0."""
+    L = load_library()
+    n = C.c_size_t(0)
+    if L.pcr_pcd_read(os.fsencode(path), None, 0, int(columns) * 4, C.byref(n)):
+        raise _session_error()
+    out = np.zeros((n.value, int(columns)), np.float32)
+    if L.pcr_pcd_read(os.fsencode(path), out.ctypes.data_as(C.c_void_p), n.value, int(columns) * 4, C.byref(n)):
+        raise _session_error()
+    return out
+
+
+def _stamps_in(stamps, n):
+    if stamps is None:
+        return None, None
+    a = np.ascontiguousarray(stamps, dtype=np.float64).reshape(-1)
+    if a.size != n:
+        raise ValueError(f"stamps holds {a.size} entries for {n} key frames")
+    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _tum_lines(directory):
+    """how many key frames a tum.txt can name at most (the size of the stamps buffer a load hands over)"""
+    try:
+        with open(os.path.join(os.fspath(directory), "tum.txt"), "rb") as f:
+            return sum(1 for _ in f)
+    except OSError:
+        return 0
+
+
 class SubMap:
     """The key-frame store and sub-map of the reference's MapManager (frontend/src/MapManager.cpp:151-201), kept in HBM.
 
@@ -1260,6 +1345,21 @@ class SubMap:
         n = C.c_size_t(0)
         self._check(self._lib.pcr_map_update_all_sparse(self._m, float(grid_size), C.byref(n)))
         return n.value
+
+    def save(self, directory, first=0, stamps=None, precise=False):
+        """pcr_map_save: {directory}/{i}.pcd for key frames first .. end as the store holds them now, and tum.txt for all of them (stamps: one
+        per key frame, None: the index).  The default tum.txt rounds to the millimetre and to 1e-6; precise=True writes 17 digits."""
+        _keep, sp = _stamps_in(stamps, self.keyframes())
+        self._check(self._lib.pcr_map_save(self._m, os.fsencode(directory), int(first), sp, int(bool(precise))))
+
+    def load(self, directory, grid_size=0.0):
+        """pcr_map_load into a store without key frames: tum.txt's poses (quaternions as read, not normalised) and {i}.pcd, then with
+        grid_size > 0 the in-place filter -> the stamps (one per loaded key frame; empty when there is no tum.txt)."""
+        cap = _tum_lines(directory)
+        stamps = np.zeros(max(cap, 1))
+        n = C.c_size_t(0)
+        self._check(self._lib.pcr_map_load(self._m, os.fsencode(directory), float(grid_size), stamps.ctypes.data_as(C.POINTER(C.c_double)), cap, C.byref(n)))
+        return stamps[:n.value].copy()
 
     def __del__(self):
         try:
@@ -2008,3 +2108,28 @@ class Backend:
     def reset(self):
         """pcr_backend_reset: the graph, the contexts and the counters start over; the store is left alone."""
         self._check(self._lib.pcr_backend_reset(self._be))
+
+    LOAD_STEPS = ("read", "upload", "contexts", "downsample", "graph")      # pcr_backend_load_seconds
+
+    def set_save_dir(self, directory):
+        """pcr_backend_set_save_dir: the reference's saveMapDir.  None or "": off.  Set: addKeyFrames writes {directory}/{i}.pcd of every new
+        key frame raw, before the in-place filter."""
+        self._check(self._lib.pcr_backend_set_save_dir(self._be, None if directory is None else os.fsencode(directory)))
+
+    def save(self, stamps=None, precise=False):
+        """pcr_backend_save: tum.txt of all key frames and fg.g2o into the save directory (what ~Backend writes)."""
+        _keep, sp = _stamps_in(stamps, self.map.keyframes())
+        self._check(self._lib.pcr_backend_save(self._be, sp, int(bool(precise))))
+
+    def load(self, directory):
+        """pcr_backend_load into a fresh or reset back end over an empty store: the raw key frames, their contexts, the in-place filter, the
+        graph; the next addKeyFrames / closeLoops take what comes after -> (stamps, info dict; info["load_seconds"]: host time by LOAD_STEPS)."""
+        cap = _tum_lines(directory)
+        stamps = np.zeros(max(cap, 1))
+        i = BackendInfo()
+        self._check(self._lib.pcr_backend_load(self._be, os.fsencode(directory), stamps.ctypes.data_as(C.POINTER(C.c_double)), cap, C.byref(i)))
+        sec = np.zeros(5)
+        self._lib.pcr_backend_load_seconds(self._be, sec.ctypes.data_as(C.POINTER(C.c_double)))
+        info = self._info(i)
+        info["load_seconds"] = dict(zip(self.LOAD_STEPS, sec.tolist()))
+        return stamps[:int(i.keyframes)].copy(), info

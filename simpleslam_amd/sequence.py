@@ -112,12 +112,17 @@ def drive_frontend(fe, scans, cmds, start_pose, prefetch=False):
                 updates=info["updates"] if info else 0, seconds=clock() - t0, scan2map_seconds=ts["scan2map"], step_seconds=ts)
 
 
-def drive_slam(fe, be, scans, cmds, start_pose, prefetch=False):
+def drive_slam(fe, be, scans, cmds, start_pose, prefetch=False, save_dir=None):
     """drive_frontend() with the back end behind it: fe = pcr.Frontend, be = pcr.Backend over the same SubMap.  After every scan that added a key
     frame, be.step(closest) runs both events -- the key frames since the last one with Frontend.closest()'s entries for them as the odometry edges'
     `from`, then the loop closure -- and each event's delta is applied to the pose the next scan starts from (delta @ pose: what optimHandler does
     to the global odometry and odom2map, Backend.cpp:321-346).  The front end's own key-frame positions (both gap rules) stay as it recorded them.
+    save_dir (default None: nothing is written, nothing changes): the session goes to that directory as the reference's saveMapDir -- every new
+    key frame raw as {i}.pcd from inside the add event (be.set_save_dir), tum.txt and fg.g2o at the end of the drive (be.save) -- for
+    Backend.load at the next start; be keeps the directory afterwards.
     -> drive_frontend()'s dict plus events: a list of (scan index, add info, loop info, be.loops())."""
+    if save_dir is not None:
+        be.set_save_dir(save_dir)
     pose = np.array(start_pose, float)
     poses, conv, iters, sub_n, events = [], [], [], [], []
     ts = dict.fromkeys(fe.STEPS, 0.0)
@@ -140,8 +145,11 @@ def drive_slam(fe, be, scans, cmds, start_pose, prefetch=False):
             events.append((k, add, lc, be.loops()))
             pose = lc["delta"] @ (add["delta"] @ pose)
     t1 = clock(); sub_n.append(fe.finish()); ts["wait"] += clock() - t1
+    seconds = clock() - t0
+    if save_dir is not None:
+        be.save()
     return dict(poses=poses, converged=conv, iterations=iters, submap_points=sub_n, keyframes=info["keyframes"] if info else 0,
-                updates=info["updates"] if info else 0, seconds=clock() - t0, scan2map_seconds=ts["scan2map"], step_seconds=ts, events=events)
+                updates=info["updates"] if info else 0, seconds=seconds, scan2map_seconds=ts["scan2map"], step_seconds=ts, events=events)
 
 
 class GpuFront:
