@@ -373,6 +373,44 @@ int pcr_voxel_filter(pcr_handle* h, const void* pts, size_t n, size_t stride_byt
 int pcr_voxel_filter_begin(pcr_handle* h, const void* d_pts, size_t n, size_t stride_bytes, double leaf, void* d_out, size_t out_capacity);
 int pcr_voxel_filter_end(pcr_handle* h, size_t* n_out);
 
+/* ---- A scan's motion distortion undone (deskew): every point moved into the sensor frame of ONE time of the sweep ------------------------
+ * The reference never does this (pcl::PointXYZI has no time field); a spinning lidar collects a sweep over ~0.1 s, and at 2 m/s and 0.5 rad/s
+ * its last point is displaced by 20 cm and 0.05 rad from its first.  The caller supplies the sensor's MOTION, the library applies it per point.
+ *   Motion: K control poses (2 <= K <= 1024; pose j = poses[16 j ..], the layout of every pose[16] here, the sensor's pose in any one fixed
+ *   frame) at strictly increasing finite stamps[K] (seconds).  A point's time is tau = t0 + its time field, by time_kind below.
+ *   Definition (csrc/deskew_math.h, f64 + - * / sqrt alone, every operation rounded on its own, so host and device give the same bits):
+ *   each rotation goes to a unit quaternion by Eigen's Quaternion(Matrix3) (the trace branch, else the largest diagonal element), negated
+ *   where its four-term dot product with its predecessor's is negative.  At a time tau, clamped to [stamps[0], stamps[K-1]], j is the largest
+ *   index of [0, K-2] with stamps[j] <= tau, s = (tau - stamps[j]) / (stamps[j+1] - stamps[j]), u = 1.0 - s, every component of the
+ *   quaternion and of the translation is u*a + s*b, the quaternion is divided by n = sqrt(((q0 q0 + q1 q1) + q2 q2) + q3 q3) and becomes a
+ *   rotation matrix R by Eigen's toRotationMatrix.  That is normalised linear interpolation: its rotation differs from one of constant
+ *   angular velocity by at most theta^3 / 240 rad in a segment that turns by theta <= 1 rad (5.7e-7 rad at 3 degrees, 2.1e-5 rad at 10): a
+ *   caller who wants less supplies denser control poses.  A point (x, y, z) widened to double becomes y_r = ((R_r0 x + R_r1 y) + R_r2 z) +
+ *   p_r at its own time and z = R_ref^T (y - p_ref), summed in the same association, at t_ref; z rounded to float replaces the coordinates and
+ *   every other byte of the record is copied.  (An all-identity motion returns the input bit for bit, a coordinate of -0 as +0.)
+ *   A record with a non-finite coordinate or a non-finite tau is copied unchanged and counted in info->nonfinite.
+ *   Time source: times != NULL is a packed array of n elements of the kind, living where pts lives; times == NULL reads a field of every
+ *   record at time_offset_bytes (Velodyne's 32-byte PointXYZIRT: PCR_TIME_F32_SECONDS at byte 24), which must be a multiple of the
+ *   element's size, not below 12 and with the whole field inside stride_bytes.
+ *   Output: n records of the input's stride_bytes (>= 16, a multiple of 4).  out == pts (in place) is allowed; any other overlap of out with
+ *   pts or times inside one memory space is refused.  info (may be NULL): the points whose time was clamped at either end, the records copied
+ *   unchanged, and whether t_ref was clamped.  n == 0 succeeds and writes nothing but *info.
+ *   Refused with a message that names the field, before anything is written: K outside 2..1024; stamps not strictly increasing or not finite;
+ *   poses, t0 or t_ref not finite, or a pose whose rotation yields no finite unit quaternion; an unknown time_kind; a bad
+ *   time_offset_bytes or stride_bytes; NULL pts, out, m, m->poses or m->stamps.
+ * pcr_deskew_host is the definition: host memory, no GPU; pcr_last_error(NULL) holds its refusal.  pcr_deskew is the same on the device, one
+ * launch on the handle's stream (any method; pcr_last_error(h)), pts / times and out each in host or device memory: a raw scan uploaded once
+ * can stay in HBM from here through the filter, the registration and the key-frame store.  The two agree bit for bit. */
+#define PCR_TIME_F32_SECONDS 0      /* tau = t0 + (double)f            */
+#define PCR_TIME_U32_NANOSECONDS 1  /* tau = t0 + (double)u * 1e-9     */
+#define PCR_TIME_F64_SECONDS 2      /* tau = t0 + d                    */
+typedef struct pcr_deskew_motion { const double* poses; const double* stamps; size_t K; double t0; double t_ref; } pcr_deskew_motion;
+typedef struct pcr_deskew_info { int64_t before, after, nonfinite; int32_t ref_clamped; } pcr_deskew_info;
+int pcr_deskew(pcr_handle* h, const void* pts, size_t n, size_t stride_bytes, int on_device, const void* times, int time_kind,
+               long long time_offset_bytes, const pcr_deskew_motion* m, void* out, int out_on_device, pcr_deskew_info* info);
+int pcr_deskew_host(const void* pts, size_t n, size_t stride_bytes, const void* times, int time_kind, long long time_offset_bytes,
+                    const pcr_deskew_motion* m, void* out, pcr_deskew_info* info);
+
 /* ---- the reference's own sparse voxel filters: pcp::VoxelDownSampleV3 and pcp::VoxelDownSampleV2 (common/pcp/pcp.hpp:157-263, :78-154) ----
  * pcl::VoxelGrid -- and pcr_voxel_filter with it -- gives up once the voxel box exceeds INT_MAX cells.  These two hold the occupied voxels
  * only: device memory grows with n, never with the box.  Same argument conventions as pcr_voxel_filter: any handle, records of stride_bytes
@@ -1114,6 +1152,13 @@ const char* pcr_frontend_last_error(const pcr_frontend* fe);   /* fe == NULL: th
  * starts over.  info may be NULL. */
 int pcr_frontend_step(pcr_frontend* fe, const void* scan, size_t n, size_t stride_bytes, int on_device,
                       const double init_pose[16], double pose_out[16], pcr_frontend_info* info);
+/* One scan of a moving sensor: pcr_deskew (above; on the register's handle) of the scan into a device buffer of the front end's own, then exactly
+ * pcr_frontend_step(on_device = 1) on that buffer -- the key frame of step 6 is therefore the DESKEWED scan.  The caller supplies the motion as it
+ * supplies init_pose: the front end composes nothing.  A filter queued by pcr_frontend_prefetch is collected and dropped (timed scans are not
+ * prefetched).  A refusal of the deskew comes back under "deskew: " and leaves the loop's state as it was.  dinfo may be NULL. */
+int pcr_frontend_step_timed(pcr_frontend* fe, const void* scan, size_t n, size_t stride_bytes, int on_device, const void* times, int time_kind,
+                            long long time_offset_bytes, const pcr_deskew_motion* m, const double init_pose[16], double pose_out[16],
+                            pcr_frontend_info* info, pcr_deskew_info* dinfo);
 /* Queue the voxel filter of a scan that is registered LATER (pcr_voxel_filter_begin on a second handle of the front end's own, on the
  * register's device, created on first use): for a caller that has the next scan already.  The scan must stay untouched until the step
  * that takes it.  A filter queued earlier and never taken is collected and dropped.  The results do not depend on it. */

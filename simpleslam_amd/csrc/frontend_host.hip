@@ -36,6 +36,7 @@ struct pcr_frontend {
     pcr_handle* filt = nullptr;     // pcr_frontend_prefetch: the filter's own handle (a stream of its own), created on first use
     DeviceBuf out[2], direct;       // filtered scans: the two a prefetch alternates between, and the one of a step that filters for itself
     DeviceBuf up_ahead[2];          // pcr_frontend_prefetch: host scans on their way in
+    DeviceBuf deskewed;             // pcr_frontend_step_timed: the scan with its motion taken out, which the step then runs on
     Ahead queued, ready;            // the filter in flight on `filt`; the one collected and not yet taken by a step
     std::vector<double> kf_pos;     // key-frame positions, xyz each
     std::vector<int64_t> closest;   // per key frame this front end added: the key frame step 6 found nearest, -1 for the first (mClosestKfIdx, MapManager.cpp:146)
@@ -313,6 +314,26 @@ int pcr_frontend_step(pcr_frontend* fe, const void* scan, size_t n, size_t strid
     for (int i = 0; i < 16; ++i) pose_out[i] = pose[i];
     if (info) *info = inf;
     return 0;
+}
+
+int pcr_frontend_step_timed(pcr_frontend* fe, const void* scan, size_t n, size_t stride_bytes, int on_device, const void* times, int time_kind,
+                            long long time_offset_bytes, const pcr_deskew_motion* m, const double init_pose[16], double pose_out[16],
+                            pcr_frontend_info* info, pcr_deskew_info* dinfo) {
+    if (!fe) return 1;
+    fe->err.clear();
+    if (fe->failed) return ffail(fe, "an earlier step of this front end failed (" + fe->failure + "): pcr_frontend_reset starts over");
+    if (check_scan(fe, scan, n, init_pose, pose_out)) return 1;
+    if (stride_bytes < 16 || stride_bytes % 4 != 0) return ffail(fe, "deskew: stride_bytes must be a multiple of 4 and >= 16");
+    if (n > SIZE_MAX / stride_bytes) return ffail(fe, "scan too large");
+    FE_HIP("deskew", hipSetDevice(fe->device));
+    // a filter queued ahead is of another scan (timed scans are not prefetched): collected and dropped
+    if (collect_queued(fe)) return 1;
+    fe->ready.on = false;
+    FE_HIP("deskew", fe->deskewed.reserve(n * stride_bytes));
+    // (a refusal writes nothing and the loop's state is as it was: no reset is needed after it)
+    if (pcr_deskew(fe->reg, scan, n, stride_bytes, on_device, times, time_kind, time_offset_bytes, m, fe->deskewed.p, 1, dinfo))
+        return ffail(fe, std::string("deskew: ") + pcr_last_error(fe->reg));
+    return pcr_frontend_step(fe, fe->deskewed.p, n, stride_bytes, 1, init_pose, pose_out, info);
 }
 
 int pcr_frontend_finish(pcr_frontend* fe, size_t* n_submap) {

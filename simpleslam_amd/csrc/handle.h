@@ -202,6 +202,13 @@ struct pcr_handle {
         size_t order_n = 0; int order_buf = 0;
     } vs;
 
+    // pcr_deskew (deskew_host.hip): a host scan and its packed times on their way in, the output of a call that returns it to the host, the control
+    // block (the three counts, then the table), and the counts as the call's one synchronisation reads them
+    struct Dsk {
+        pcr::DeviceBuf in, times, out, ctl;
+        pcr::host::Mapped<unsigned long long> ret;
+    } dsk;
+
     // scores of many poses and exact queries on the kept target (query_host.hip)
     struct Query {
         pcr::DeviceBuf rl_poses, rl_part, rl_out, rl_src;   // pcr_fitness_batch: the poses in float, the [pose][chunk] partials, the sums; pcr_relocalize: its staged host source

@@ -470,6 +470,19 @@ size_t voxel_filter_wave_bytes(size_t n);
 hipError_t voxel_filter_launch(const GridIndex& grid, const float* d_orig, size_t stride_floats, size_t n, uint32_t* d_inten, uint32_t* d_sums,
                                void* d_wave, float* d_out, size_t out_capacity, void* result_mapped, hipStream_t s);
 
+// A scan's motion distortion undone (deskew.hip; the arithmetic and the table's layout: deskew_math.h).  One launch, one point per lane.  pts, times
+// (or nullptr: the field at time_off of every record) and out are device memory, out == pts or disjoint from both; tab: K records of 8 doubles;
+// counts: three words (before, after, nonfinite) the launch ADDS to; Rr / pr: the trajectory at the reference time.
+struct DeskewArgs {
+    const char* pts; const char* times; char* out; const double* tab; unsigned long long* counts;
+    unsigned long long n;
+    uint32_t stride, time_off;
+    int32_t kind, K;
+    double t0, Rr[9], pr[3];
+};
+constexpr unsigned long long kDeskewMaxPoints = 0x7fffffffull * 256;      // (the grid's x extent times the block)
+hipError_t deskew_launch(const DeskewArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------------------
 // Sparse voxel filters (voxel_sparse.hip): pcp::VoxelDownSampleV3 / V2 by a stable radix sort of packed voxel keys
 // ---------------------------------------------------------------------------

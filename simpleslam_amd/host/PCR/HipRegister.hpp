@@ -364,6 +364,20 @@ public:
         if (pcr_frontend_step(fe_, pts, n, sizeof(PointXYZI), on_device ? 1 : 0, init.data(), res.data(), info)) throw std::runtime_error(pcr_frontend_last_error(fe_));
         return res;
     }
+    // one scan of a moving sensor: pcr_deskew into a device buffer of the front end's, then step() on that buffer (the key frame is the deskewed
+    // scan).  times: one float per point, seconds after m.t0, living where the scan lives; nullptr: the float at byte `time_offset` of every record
+    pose_t stepTimed(const void* pts, size_t n, bool on_device, const float* times, const pcr_deskew_motion& m, const pose_t& init,
+                     pcr_frontend_info* info = nullptr, pcr_deskew_info* dinfo = nullptr, long long time_offset = 0) {
+        pose_t res;
+        if (pcr_frontend_step_timed(fe_, pts, n, sizeof(PointXYZI), on_device ? 1 : 0, times, PCR_TIME_F32_SECONDS, time_offset, &m, init.data(), res.data(), info, dinfo))
+            throw std::runtime_error(pcr_frontend_last_error(fe_));
+        return res;
+    }
+    pose_t stepTimed(const PC_cPtr& scan, const std::vector<float>& times, const pcr_deskew_motion& m, const pose_t& init, pcr_frontend_info* info = nullptr,
+                     pcr_deskew_info* dinfo = nullptr) {
+        if (times.size() != scan->size()) throw std::runtime_error("stepTimed: one time per point");
+        return stepTimed(scan->points.data(), scan->size(), false, times.data(), m, init, info, dinfo);
+    }
     // the NEXT scan's voxel filter, queued beside this scan's registration
     void prefetch(const PC_cPtr& next) { prefetch(next->points.data(), next->size(), false); }
     void prefetch(const void* pts, size_t n, bool on_device) {
@@ -876,6 +890,38 @@ inline void voxelDownSample(PCR::PC_Ptr& cloud, float grid_size) {      // in pl
     PCR::PointCloud out;
     voxelDownSample(PCR::PC_cPtr(cloud), out, grid_size);
     cloud->points.swap(out.points);
+}
+
+// A scan's motion distortion undone (pcr_deskew; the reference has no counterpart: its points carry no time).  The sensor's motion as control poses
+// at stamps; times: one float per point, seconds after t0.  deskew() runs on the registrar's handle and stream, deskewHost() on the CPU (the
+// definition: the two agree bit for bit).  cloudOut may be the input's own cloud.  -> the counts; a refused call throws with the library's message.
+struct DeskewMotion {
+    std::vector<PCR::pose_t> poses;
+    std::vector<double> stamps;
+    double t0 = 0.0, t_ref = 0.0;
+    pcr_deskew_motion c() const {
+        static_assert(sizeof(PCR::pose_t) == 16 * sizeof(double), "poses are handed over as one array of doubles");
+        if (poses.size() != stamps.size()) throw std::runtime_error("DeskewMotion: one stamp per control pose");
+        return pcr_deskew_motion{poses.empty() ? nullptr : poses.front().data(), stamps.data(), stamps.size(), t0, t_ref};
+    }
+};
+inline pcr_deskew_info deskew(PCR::HipRegister& reg, const PCR::PointCloud& cloudIn, const std::vector<float>& times, const DeskewMotion& motion, PCR::PointCloud& cloudOut) {
+    if (times.size() != cloudIn.size()) throw std::runtime_error("deskew: one time per point");
+    const pcr_deskew_motion m = motion.c();
+    if (&cloudOut != &cloudIn) cloudOut.points.resize(cloudIn.size());
+    pcr_deskew_info info;
+    if (pcr_deskew(reg.handle(), cloudIn.points.data(), cloudIn.size(), sizeof(PCR::PointXYZI), 0, times.data(), PCR_TIME_F32_SECONDS, 0, &m, cloudOut.points.data(), 0, &info))
+        throw std::runtime_error(pcr_last_error(reg.handle()));
+    return info;
+}
+inline pcr_deskew_info deskewHost(const PCR::PointCloud& cloudIn, const std::vector<float>& times, const DeskewMotion& motion, PCR::PointCloud& cloudOut) {
+    if (times.size() != cloudIn.size()) throw std::runtime_error("deskewHost: one time per point");
+    const pcr_deskew_motion m = motion.c();
+    if (&cloudOut != &cloudIn) cloudOut.points.resize(cloudIn.size());
+    pcr_deskew_info info;
+    if (pcr_deskew_host(cloudIn.points.data(), cloudIn.size(), sizeof(PCR::PointXYZI), times.data(), PCR_TIME_F32_SECONDS, 0, &m, cloudOut.points.data(), &info))
+        throw std::runtime_error(pcr_last_error(nullptr));
+    return info;
 }
 
 // common/pcp/pcp.hpp:78-263: the reference's own sparse voxel filters, on the device (pcr_voxel_filter_sparse).  Objects of both classes are

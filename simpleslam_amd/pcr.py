@@ -101,6 +101,7 @@ ABI_SYMBOLS = [
     "pcr_backend_register", "pcr_backend_add_keyframes", "pcr_backend_close_loops", "pcr_backend_loops", "pcr_backend_step", "pcr_backend_reset",
     "pcr_session_last_error", "pcr_tum_format", "pcr_tum_parse", "pcr_pcd_write", "pcr_pcd_read", "pcr_map_save", "pcr_map_load",
     "pcr_backend_set_save_dir", "pcr_backend_save", "pcr_backend_load", "pcr_backend_load_seconds",
+    "pcr_deskew", "pcr_deskew_host", "pcr_frontend_step_timed",
 ]
 
 # pcr_allreduce_fn (include/pcr_hip.h): int fn(double* inout, size_t count, int op, void* user)
@@ -137,6 +138,21 @@ class RelocCandidate(C.Structure):
 class GlobalRelocParams(C.Structure):
     """struct pcr_global_reloc_params (include/pcr_hip.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("places", C.c_int32), ("max_dist", C.c_double), ("local", RelocParams)]
+
+
+# pcr_deskew's time_kind (include/pcr_hip.h: PCR_TIME_*) and the numpy type of its element
+TIME_F32_SECONDS, TIME_U32_NANOSECONDS, TIME_F64_SECONDS = 0, 1, 2
+_TIME_DTYPES = {TIME_F32_SECONDS: np.float32, TIME_U32_NANOSECONDS: np.uint32, TIME_F64_SECONDS: np.float64}
+
+
+class DeskewMotion(C.Structure):
+    """struct pcr_deskew_motion (include/pcr_hip.h)."""
+    _fields_ = [("poses", C.POINTER(C.c_double)), ("stamps", C.POINTER(C.c_double)), ("K", C.c_size_t), ("t0", C.c_double), ("t_ref", C.c_double)]
+
+
+class DeskewInfo(C.Structure):
+    """struct pcr_deskew_info (include/pcr_hip.h)."""
+    _fields_ = [("before", C.c_int64), ("after", C.c_int64), ("nonfinite", C.c_int64), ("ref_clamped", C.c_int32)]
 
 
 class FrontendParams(C.Structure):
@@ -426,6 +442,10 @@ def load_library():
     L.pcr_backend_save.argtypes = [vp, dp, C.c_int]
     L.pcr_backend_load.argtypes = [vp, C.c_char_p, dp, C.c_size_t, C.POINTER(BackendInfo)]
     L.pcr_backend_load_seconds.argtypes = [vp, dp]
+    L.pcr_deskew.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_int, C.c_longlong, C.POINTER(DeskewMotion), vp, C.c_int, C.POINTER(DeskewInfo)]
+    L.pcr_deskew_host.argtypes = [vp, C.c_size_t, C.c_size_t, vp, C.c_int, C.c_longlong, C.POINTER(DeskewMotion), vp, C.POINTER(DeskewInfo)]
+    L.pcr_frontend_step_timed.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_int, C.c_longlong, C.POINTER(DeskewMotion), dp, dp,
+                                          C.POINTER(FrontendInfo), C.POINTER(DeskewInfo)]
     _lib = L
     return L
 
@@ -1474,6 +1494,85 @@ def kf_rank_near_host(xyz, first, count, radius, k=1, num_exclude_recent=0):
     return idx, d2
 
 
+def deskew_motion(poses, stamps, t0=0.0, t_ref=0.0):
+    """-> (pcr_deskew_motion, keepalive): control poses (K, 4, 4) at stamps (K,), the offset t0 of every point time and the reference time."""
+    P = np.asarray(poses, dtype=np.float64)
+    if P.ndim != 3 or P.shape[1:] != (4, 4):
+        raise ValueError("poses must have shape (K, 4, 4)")
+    cm = np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(-1).copy()      # column-major, one pose after the other
+    st = np.ascontiguousarray(np.asarray(stamps, dtype=np.float64).reshape(-1)).copy()
+    if st.shape[0] != P.shape[0]:
+        raise ValueError("one stamp per control pose")
+    dp = C.POINTER(C.c_double)
+    return DeskewMotion(cm.ctypes.data_as(dp), st.ctypes.data_as(dp), P.shape[0], float(t0), float(t_ref)), (cm, st)
+
+
+def _deskew_times(times, time_kind, n, on_device):
+    """-> (pointer or None, keepalive) of a packed time array that lives where the cloud lives."""
+    if times is None:
+        return None, None
+    if time_kind not in _TIME_DTYPES:
+        raise ValueError("time_kind must be TIME_F32_SECONDS, TIME_U32_NANOSECONDS or TIME_F64_SECONDS")
+    if hasattr(times, "data_ptr"):
+        if not (times.is_cuda and on_device):
+            raise ValueError("times must live where the cloud lives")
+        if times.numel() != n or not times.is_contiguous() or times.element_size() != np.dtype(_TIME_DTYPES[time_kind]).itemsize:
+            raise ValueError("times must be a contiguous array of n elements of the time kind")
+        return C.c_void_p(times.data_ptr()), times
+    if on_device:
+        raise ValueError("times must live where the cloud lives")
+    t = np.ascontiguousarray(np.asarray(times).reshape(-1), dtype=_TIME_DTYPES[time_kind])
+    if t.shape[0] != n:
+        raise ValueError("one time per point")
+    return t.ctypes.data_as(C.c_void_p), t
+
+
+def _deskew_info(i):
+    return dict(before=int(i.before), after=int(i.after), nonfinite=int(i.nonfinite), ref_clamped=int(i.ref_clamped))
+
+
+def deskew_host(cloud, poses, stamps, times=None, time_kind=TIME_F32_SECONDS, time_offset=0, t0=0.0, t_ref=0.0, out=None):
+    """pcr_deskew_host (host only, no GPU; the definition of deskew): every point of `cloud` (numpy (n, >= 4) float32) moved from the sensor frame at
+    its own time into the sensor frame at t_ref, the sensor's motion given by control `poses` (K, 4, 4) at `stamps`.  times: a packed array of
+    the kind, or None for the field at byte `time_offset` of every record.  out: None (a new array), or a float32 array of the cloud's shape --
+    the cloud itself deskews in place.  -> (out, info dict: before, after, nonfinite, ref_clamped)."""
+    p, n, s, dev, keep = _cloud(cloud)
+    if dev:
+        raise ValueError("deskew_host takes host arrays")
+    if out is None:
+        out = np.zeros_like(keep)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == keep.shape and out.flags.c_contiguous):
+        raise ValueError("out must be a contiguous float32 array of the cloud's shape")
+    tp, _tk = _deskew_times(times, time_kind, n, 0)
+    m, _mk = deskew_motion(poses, stamps, t0, t_ref)
+    info = DeskewInfo()
+    L = load_library()
+    if L.pcr_deskew_host(p, n, s, tp, int(time_kind), int(time_offset), C.byref(m), out.ctypes.data_as(C.c_void_p), C.byref(info)):
+        raise PcrError(L.pcr_last_error(None).decode())
+    return out, _deskew_info(info)
+
+
+def deskew(register, cloud, poses, stamps, times=None, time_kind=TIME_F32_SECONDS, time_offset=0, t0=0.0, t_ref=0.0, out=None):
+    """pcr_deskew on `register`'s handle (any method): deskew_host on the device, bit for bit.  cloud (and times) numpy arrays or CUDA tensors;
+    out: None -- a new array or tensor like the cloud --, or a float32 numpy array / CUDA tensor of the cloud's shape (the cloud itself: in
+    place).  A CUDA cloud deskewed into a CUDA tensor never leaves HBM.  -> (out, info dict)."""
+    p, n, s, dev, keep = _cloud(cloud)
+    if out is None:
+        if dev:
+            import torch
+            out = torch.empty_like(keep)
+        else:
+            out = np.zeros_like(keep)
+    op, on, os_, odev, _ok = _cloud(out)
+    if (on, os_) != (n, s):
+        raise ValueError("out must have the cloud's shape")
+    tp, _tk = _deskew_times(times, time_kind, n, dev)
+    m, _mk = deskew_motion(poses, stamps, t0, t_ref)
+    info = DeskewInfo()
+    register._check(register._lib.pcr_deskew(register._h, p, n, s, dev, tp, int(time_kind), int(time_offset), C.byref(m), op, odev, C.byref(info)))
+    return out, _deskew_info(info)
+
+
 def pose_to_mobile(T):
     """pcr_pose_to_mobile (host only): trans::SixDof2Mobile (common/geometry/trans.hpp:68-86) -- x, y and the rotation about Z; the heading is
     dropped when the rotation's axis is not within |axis.z| > 0.95 of Z, as in the reference.  -> a new 4x4."""
@@ -1539,6 +1638,25 @@ class Frontend:
         i = self._info
         info = {f: int(getattr(i, f)) for f in self._INFO_INTS}
         info["seconds"] = dict(zip(self.STEPS, i.seconds))
+        return self._out_cm.T.copy(), info
+
+    def stepTimed(self, scan, init_pose, poses, stamps, times=None, time_kind=TIME_F32_SECONDS, time_offset=0, t0=0.0, t_ref=0.0):
+        """pcr_frontend_step_timed: deskew() of the scan into a device buffer of the front end's, then step() on that buffer (the key frame is
+        the deskewed scan).  -> (pose 4x4, info dict as step(), with the deskew's counts under "deskew")."""
+        p, n, s, dev, _keep = self.reg._cloud_cached(scan)
+        tp, _tk = _deskew_times(times, time_kind, n, dev)
+        m, _mk = deskew_motion(poses, stamps, t0, t_ref)
+        T = np.asarray(init_pose, dtype=np.float64)
+        if T.shape != (4, 4):
+            raise ValueError("pose must be 4x4")
+        self._in_cm[...] = T.T
+        dinfo = DeskewInfo()
+        self._check(self._lib.pcr_frontend_step_timed(self._fe, p, n, s, dev, tp, int(time_kind), int(time_offset), C.byref(m), self._in_buf, self._out_buf,
+                                                      self._info_ref, C.byref(dinfo)))
+        i = self._info
+        info = {f: int(getattr(i, f)) for f in self._INFO_INTS}
+        info["seconds"] = dict(zip(self.STEPS, i.seconds))
+        info["deskew"] = _deskew_info(dinfo)
         return self._out_cm.T.copy(), info
 
     def prefetch(self, scan):
